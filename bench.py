@@ -2,12 +2,20 @@
 """Headline benchmark: rendered frames/s at 1216x352 on a synthetic 30 M-point cloud.
 
     python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py --full                               (the same line with every check and figure below added)
     python bench.py --config kitti6_like                 (second line: BASELINE configs[1] stand-in, see below)
     python bench.py --config train                       (third line: BASELINE configs[4], training iterations/s)
 
-The default (headline) run at N = 1 also carries compact sub-records of the other configurations in the same JSON line —
-``"also": {"latency_mode", "kitti6_like", "train"}`` — each measured and VERIFIED against the oracle inside this run (their
-CPU timing legs are skipped, the verification frames / iteration are kept); ``--no-also`` drops them.
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (metric, value, unit, ms_per_step, dtype, config).
+--dump-outputs DIR also writes what the last timed step computed: DIR/frames.npy, that step's RGBA frames as its caller
+receives them (--config train: DIR/output.npy, the model's output, and DIR/loss.npy).  Every input is seeded, so two builds
+can be compared output for output.
+
+--full adds what takes runs of its own: the CPU baseline and the oracle check of a rendered frame ("verified"), per-stage and
+per-launch timings with the roofline block (--detail FILE: the per-launch table), and at N = 1 on slab30m compact sub-records
+of the other configurations — ``"also": {"latency_mode", "fp32_mfma", "shard_proxy", "kitti6_like", "train"}`` — each
+measured and VERIFIED against the oracle inside this run (their CPU timing legs are skipped, the verification frames /
+iteration are kept); ``--no-also`` drops them.
 
 A "step" is one full frame of READ's render path on one GPU: rasterise 5 scales (one pass over the
 cloud) -> gather 8-channel descriptors -> 99-conv gated UNet -> RGBA frame.  Inputs (xyz, descriptors,
@@ -23,7 +31,7 @@ frame's layer fill the CUs that the last, partly filled round of the other frame
 rarely divide by the 512 persistent workgroups).  Every frame is still rendered completely inside the timed region;
 --frames-in-flight 1 is the latency mode (one frame at a time).
 
-After the timed loop rank 0 re-renders pose 0 through the SAME warm renderer and compares it with the CPU
+With --full, after the timed loop rank 0 re-renders pose 0 through the SAME warm renderer and compares it with the CPU
 oracle's frame (which the cpu_baseline leg computes anyway): raster index/depth bit-exact on all five levels,
 RGB PSNR / max|diff| — "verified" in the JSON line; a mismatch exits non-zero.
 
@@ -62,7 +70,8 @@ PSNR_FLOOR_DB = 120.0            # same guard as tests/test_gpu_unet.py (measure
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=256, help="timed frames per GPU (default: one full 256-pose sweep)")
+    p.add_argument("--steps", type=int, default=None,
+                   help="timed steps per GPU (default: one full 256-pose sweep; --config train: 10 iterations)")
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--config", choices=("slab30m", "kitti6_like", "train"), default="slab30m")
     p.add_argument("--points", type=int, default=0, help="override the cloud size of the config")
@@ -84,7 +93,33 @@ def parse():
     p.add_argument("--train-mode", choices=("eval", "train"), default="eval",
                    help="--config train: BatchNorm in eval mode (eval_in_train: True, configs/train_example.yaml) or with "
                         "batch statistics (model.train(), the reference's default)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline figure: CPU baseline and oracle check, per-stage / per-kernel timings, roofline, "
+                        "and (slab30m on one GPU) the `also` sub-records")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    a = p.parse_args()
+    if a.steps is None:
+        a.steps = 10 if a.config == "train" else N_POSES
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    if a.detail and not a.full:
+        p.error("--detail writes per-launch timings: it needs --full")
+    return a
+
+
+def dump_outputs(d, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: {name: array} -> d/<name>.npy on the host, float64 kept, everything else as float32.  An array above
+    its share of `limit_bytes` is replaced by a fixed, seeded sample of its flattened elements (sorted indices)."""
+    os.makedirs(d, exist_ok=True)
+    share = limit_bytes // max(len(arrays), 1)
+    for name, v in arrays.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        v = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+        if v.nbytes > share:
+            keep = np.sort(np.random.default_rng(2019).choice(v.size, share // v.itemsize, replace=False))
+            v = v.reshape(-1)[keep]
+        np.save(os.path.join(d, name + ".npy"), v)
 
 
 def hip_time_ms(fn, iters, batches=5):
@@ -383,7 +418,7 @@ def _host_barrier(key="read_bench_verify_done", timeout_s=1800):
     store.wait([f"{key}_{i}" for i in range(n)], datetime.timedelta(seconds=timeout_s))
 
 
-def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_verify=True):
+def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_verify=True, dump=""):
     """One iteration = what src/train.py:150-265 does per batch with the headless renderer: rasterise 8 cameras x 5 scales
     (MyRender), look the descriptors up, UNet forward, loss, backward, Adam on the net, RMSprop on the descriptors.  The
     criterion is the Huber term (x 1e4, train.py:549) only: the VGG term needs downloaded VGG weights (no network).
@@ -443,6 +478,7 @@ def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_ve
     tex = pipe.textures[0]
 
     phases = {"render": 0.0, "forward": 0.0, "loss": 0.0, "backward": 0.0, "adam": 0.0, "rmsprop": 0.0}   # HOST time, no syncs
+    last_out = [None]                                             # the model's output of the latest step (--dump-outputs)
 
     def forward_backward(views, target):
         t0 = time.perf_counter()
@@ -451,6 +487,7 @@ def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_ve
         inputs, _ = renderer.render(data)
         t1 = time.perf_counter()
         out = model(inputs)
+        last_out[0] = out
         t2 = time.perf_counter()
         loss = pipe.criterion(out, target) * 1e4
         t3 = time.perf_counter()
@@ -477,7 +514,7 @@ def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_ve
 
     # ---- verification iteration (no optimizer step: the weights the timed loop starts from are the seeded ones)
     verified, base = None, None
-    if do_verify and not a.no_cpu_baseline:
+    if do_verify and a.full and not a.no_cpu_baseline:
         import oracle
         from oracle import unet_torch
         import torch.nn.functional as Fnn
@@ -560,9 +597,10 @@ def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_ve
             ext_r = torch.optim.RMSprop([tex_r], lr=1e-1)
             opt_r.zero_grad(); ext_r.zero_grad()
             n_cpu = 2
+            crng = np.random.default_rng(2019 + rank)                  # its own poses: the timed steps' do not depend on --full
             t0 = time.perf_counter()
             for i in range(n_cpu):
-                views = np.stack([synthetic.sweep_pose(int(k)) for k in rng.integers(0, N_POSES, B)])
+                views = np.stack([synthetic.sweep_pose(int(k)) for k in crng.integers(0, N_POSES, B)])
                 oracle_iteration(views, targets[i % 4].cpu(), st_r, tex_r)
                 opt_r.step(); opt_r.zero_grad(); ext_r.step(); ext_r.zero_grad()
             t_cpu = (time.perf_counter() - t0) / n_cpu
@@ -572,7 +610,7 @@ def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_ve
                               f"oracle rasteriser (C/OpenMP, {r_threads} threads, 8 cameras x 5 scales over {N} points) + torch-CPU "
                               "gather + UNet forward/backward + Huber through the oracle + torch Adam + dense torch RMSprop"}
 
-    steps = steps if steps is not None else (a.steps if a.steps != 256 else 10)
+    steps = steps if steps is not None else a.steps
     warm = warm if warm is not None else max(a.warmup, 2)
     if world > 1:
         # rank 0 alone ran the verification iteration (8 crops through the CPU oracle: tens of seconds): the other ranks wait for it
@@ -599,25 +637,41 @@ def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_ve
         t_ = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t_, op=dist.ReduceOp.MAX)
         dt = float(t_.item())
-    fwd_flops = 187.06e9 * B                                      # conv MACs x 2 at 256x256, measured on the reference module
-    algorithmic = 3.0 * fwd_flops / (dt / steps) / 1e12            # forward + dgrad + wgrad, direct-convolution count
-    # the flops the step's launches EXECUTE (the convention of the headline's roofline.frac): one instrumented step logs every
-    # convolution launch with the kernel family the library takes for it (read_conv_kernel_family) — F(4x4,3x3) executes 1/4
-    # of the direct count, F(2x2,3x3) 1/2.25, the Winograd-domain wgrad 1/4, direct kernels all of it (padded channels and
-    # dilated dgrads included)
+    if dump:
+        dump_outputs(dump, {"output": last_out[0], "loss": np.float64(float(loss.detach()))})
     from read_amd import train as _train
     step_path = _train.LAST_STEP_PATH                              # 'graph': the timed steps replayed the captured HIP graphs
-    _train.FLOP_LOG, graph_was = [], _train.GRAPH_TRAIN
-    _train.GRAPH_TRAIN = False                                     # the instrumented step runs the per-layer Python (same launches)
-    try:
-        step(warm + steps)
-        torch.cuda.synchronize()
-        log = list(_train.FLOP_LOG)
-    finally:
-        _train.FLOP_LOG, _train.GRAPH_TRAIN = None, graph_was
-    gain = {4: 4.0, 2: 2.25}
-    executed_flops = sum(fl / gain.get(fam, 1.0) for (_, fl, fam) in log)
-    achieved = executed_flops / (dt / steps) / 1e12 if log else algorithmic
+    roofline = None
+    if a.full:
+        fwd_flops = 187.06e9 * B                                      # conv MACs x 2 at 256x256, measured on the reference module
+        algorithmic = 3.0 * fwd_flops / (dt / steps) / 1e12            # forward + dgrad + wgrad, direct-convolution count
+        # the flops the step's launches EXECUTE (the convention of the headline's roofline.frac): one instrumented step logs every
+        # convolution launch with the kernel family the library takes for it (read_conv_kernel_family) — F(4x4,3x3) executes 1/4
+        # of the direct count, F(2x2,3x3) 1/2.25, the Winograd-domain wgrad 1/4, direct kernels all of it (padded channels and
+        # dilated dgrads included)
+        _train.FLOP_LOG, graph_was = [], _train.GRAPH_TRAIN
+        _train.GRAPH_TRAIN = False                                     # the instrumented step runs the per-layer Python (same launches)
+        try:
+            step(warm + steps)
+            torch.cuda.synchronize()
+            log = list(_train.FLOP_LOG)
+        finally:
+            _train.FLOP_LOG, _train.GRAPH_TRAIN = None, graph_was
+        gain = {4: 4.0, 2: 2.25}
+        executed_flops = sum(fl / gain.get(fam, 1.0) for (_, fl, fam) in log)
+        achieved = executed_flops / (dt / steps) / 1e12 if log else algorithmic
+        roofline = {"kernel": "whole step (MFMA convolutions forward + dgrad + wgrad)", "bound": "mfma",
+                    "achieved": achieved, "peak": FP32_MFMA_PEAK_TFS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFS,
+                    "traffic": None, "flops_per_step": executed_flops if log else 3.0 * fwd_flops,
+                    "algorithmic_flops_per_step": 3.0 * fwd_flops, "algorithmic_TFLOPs": algorithmic,
+                    "frac_algorithmic": algorithmic / FP32_MFMA_PEAK_TFS,
+                    "launches_logged": {k_: sum(1 for (kk, _, _) in log if kk == k_) for k_ in ("conv", "wgrad", "dgrad_valu")},
+                    "winograd_f4_launches": sum(1 for (_, _, f_) in log if f_ == 4),
+                    "winograd_f2_launches": sum(1 for (_, _, f_) in log if f_ == 2),
+                    "note": "achieved = MFMA flops the step's convolution launches EXECUTE (forward pre-activations and "
+                            "dgrad on the Winograd kernels at 1/4 or 1/2.25 of the direct count; the 3x3/s1 weight gradients "
+                            "in the Winograd F(4x4,3x3) domain at 1/4, the others direct) / wall time of a step, the "
+                            "headline's convention; frac_algorithmic = 3 x SURVEY 8d's forward count / wall time"}
     out = {"metric": "training iterations/sec (8 crops of 256x256 per iteration and GPU)", "value": world * steps / dt, "unit": "iters/s",
            "n_gpus": world, "steps": steps, "warmup": warm, "ms_per_step": 1e3 * dt / steps, "higher_is_better": True,
            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -629,18 +683,7 @@ def run_train(a, dev, street=None, steps=None, warm=None, cpu_timing=True, do_ve
                       "points": N, "crop": S, "batch": B, "parallelism": "single GPU" if world == 1 else f"data-parallel x{world}: one process per GPU, 8 crops each; per step one RCCL "
                                      "all-reduce of the flat gradient arena + one all-gather of the sparse descriptor pairs (read_amd/ddp.py)",
                       "gradient_arena_bytes": None if ddp_step is None else ddp_step.arena.nbytes},
-           "roofline": {"kernel": "whole step (MFMA convolutions forward + dgrad + wgrad)", "bound": "mfma",
-                        "achieved": achieved, "peak": FP32_MFMA_PEAK_TFS, "unit": "TFLOP/s", "frac": achieved / FP32_MFMA_PEAK_TFS,
-                        "traffic": None, "flops_per_step": executed_flops if log else 3.0 * fwd_flops,
-                        "algorithmic_flops_per_step": 3.0 * fwd_flops, "algorithmic_TFLOPs": algorithmic,
-                        "frac_algorithmic": algorithmic / FP32_MFMA_PEAK_TFS,
-                        "launches_logged": {k_: sum(1 for (kk, _, _) in log if kk == k_) for k_ in ("conv", "wgrad", "dgrad_valu")},
-                        "winograd_f4_launches": sum(1 for (_, _, f_) in log if f_ == 4),
-                        "winograd_f2_launches": sum(1 for (_, _, f_) in log if f_ == 2),
-                        "note": "achieved = MFMA flops the step's convolution launches EXECUTE (forward pre-activations and "
-                                "dgrad on the Winograd kernels at 1/4 or 1/2.25 of the direct count; the 3x3/s1 weight gradients "
-                                "in the Winograd F(4x4,3x3) domain at 1/4, the others direct) / wall time of a step, the "
-                                "headline's convention; frac_algorithmic = 3 x SURVEY 8d's forward count / wall time"},
+           "roofline": roofline,
            # host time inside the step's calls WITHOUT a sync: includes waiting for room in the launch queue — the Python / launch
            # path itself costs 17.5 ms per step (tools/train_host_probe.py: the same at 32 x 32 crops), the step is device-bound
            "host_enqueue_ms_per_step": 1e3 * dt_host / steps,
@@ -1022,6 +1065,93 @@ def profile_staleness():
     return stale, {"conv_hip_sha16_profiled": src.get("conv_hip_sha16"), "conv_hip_sha16_now": now, "files": src.get("files")}
 
 
+def kernel_figures(a, wl, dev, prof, ms_splat, ms_gather, ms_unet):
+    """--full: the roofline and per-stage records of the headline line from the stage timings and the per-launch profile."""
+    W, H, N = wl.W, wl.H, wl.N
+    c3_ms = sum(m for (_, m, _, c) in prof if c)
+    c3_fl = sum(fl for (_, _, fl, c) in prof if c)
+    n_c3 = sum(1 for (_, _, _, c) in prof if c)
+    all_fl = sum(fl for (_, _, fl, _) in prof)
+    algorithmic_tfs = c3_fl / (c3_ms * 1e-3) / 1e12
+    # a launch that ran a Winograd kernel executes fewer MFMA flops than the algorithmic (direct-convolution) count:
+    # F(2x2,3x3) 1/2.25 (c == 2), F(4x4,3x3) 1/4 (c == 4)
+    # ... and the split-operand F(4x4) kernel (c == 5) forms each of those products from THREE f16 piece pairs on the f16 matrix
+    # cores: it executes 3/4 of the direct count there.  `gain` = direct count / fp32-product count (what an fp32 kernel would run)
+    # the direct split-operand kernel (c == 6: FAM's launches) executes every product, three piece pairs each
+    gain = {0: 1.0, 1: 1.0, 2: 2.25, 4: 4.0, 5: 4.0, 6: 1.0}
+    c3_exec = sum(fl / gain.get(c, 1.0) for (_, _, fl, c) in prof if c)
+    n_wino = sum(1 for (_, _, _, c) in prof if c == 2)
+    n_wino4 = sum(1 for (_, _, _, c) in prof if c == 4)
+    n_w4h = sum(1 for (_, _, _, c) in prof if c == 5)
+    executed_tfs = c3_exec / (c3_ms * 1e-3) / 1e12          # fp32-product equivalent: comparable with rounds 3-5
+    all_exec = sum(fl / gain.get(c, 1.0) for (_, _, fl, c) in prof)
+    n_d3h = sum(1 for (_, _, _, c) in prof if c == 6)
+    w4h_ms = sum(m for (_, m, _, c) in prof if c == 5)
+    w4h_f16_flops = sum(3.0 * fl / 4.0 for (_, _, fl, c) in prof if c == 5)
+    w4h_tfs = w4h_f16_flops / (w4h_ms * 1e-3) / 1e12 if n_w4h else None
+    sizes = camera.level_sizes(W, H, 5)
+    splat_bytes = 12.0 * N + 8.0 * sum(w * h for (w, h) in sizes)
+    gather_bytes = 68.0 * sum(w * h for (w, h) in sizes)
+    traffic, traffic_src = profiled_traffic() if a.config == "slab30m" else (None, None)
+    sustained = mfma_sustained_tfs(dev)
+    return {
+        "roofline": {
+            "kernel": ("gated_conv_wino4h_kernel: Winograd F(4x4,3x3) with split fp32 operands on the f16 matrix cores "
+                       f"({n_w4h} of the {n_c3} launches of the 3x3/s1 C->C family; {n_d3h} (FAM's x1 * x2) on the direct split-operand kernel "
+                       f"gated_conv_d3h_kernel, {n_wino4} on the fp32-matrix-core F(4x4) kernel, "
+                       f"{n_wino} F(2x2), {n_c3 - n_wino - n_wino4 - n_w4h - n_d3h} direct fp32)") if n_w4h else
+                      ("3x3/s1 C->C gated conv family: Winograd kernels on the fp32 matrix cores "
+                       f"({n_wino} launches F(2x2,3x3), {n_wino4} launches F(4x4,3x3), {n_c3 - n_wino - n_wino4} direct)"),
+            "bound": "mfma",
+            "achieved": w4h_tfs if n_w4h else executed_tfs, "peak": F16_MFMA_PEAK_TFS if n_w4h else FP32_MFMA_PEAK_TFS, "unit": "TFLOP/s",
+            "frac": (w4h_tfs / F16_MFMA_PEAK_TFS) if n_w4h else executed_tfs / FP32_MFMA_PEAK_TFS,
+            "frac_note": ("executed f16 MFMA flops (3 piece pairs x 1/4 of the direct count) / launch time / the f16 dense peak.  The kernel "
+                          "is NOT matrix-pipe bound on this path: its MFMAs alone take 9 us of a 44 us launch (profiles/r6_w4h_ablation.md); what "
+                          "binds it is the operand stream — 288 KiB of weight fragments + 43 KiB of patch per unit and 32 channels from "
+                          "L2 into one CU, with 48 KiB in flight (`operand_stream`)") if n_w4h else None,
+            "fp32_equivalent": {"achieved": executed_tfs, "peak": FP32_MFMA_PEAK_TFS, "frac": executed_tfs / FP32_MFMA_PEAK_TFS,
+                                "note": "the fp32 products an fp32-matrix-core kernel would execute for the same launches (direct count / 4 "
+                                        "for F(4x4)) / the family's time / the fp32 MFMA peak: the figure rounds 3-5 reported as frac (0.40)"},
+            "traffic": traffic, "traffic_stale": profile_staleness()[0], "profile_sources": profile_staleness()[1],
+            "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE*2 + WRITE_SIZE)",
+            "traffic_source": f"static: profiles/{traffic_src} — separate --pmc passes of this command, committed; NOT measured "
+                              "in this run (counters need rocprofv3 around the process)" if traffic_src else None,
+            "mfma_busy": profiled_mfma_busy(),
+            "mfma_busy_source": "static: profiles/r6_pmc_mfma_busy.md — rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES per level, committed; NOT "
+                                "measured in this run; it agrees with executed flops / time per level (same file)",
+            "mfma_sustained": sustained, "frac_of_sustained": executed_tfs / sustained if sustained else None,
+            "mfma_sustained_note": "TFLOP/s of back-to-back v_mfma_f32_16x16x4_f32, one wave per SIMD on every CU, measured live in this run "
+                                   "(read_mfma_f32_rate_probe): the matrix pipe at the clock the chip sustains; `peak` is the guide's figure at 2.4 GHz",
+            "frac_algorithmic": algorithmic_tfs / FP32_MFMA_PEAK_TFS,
+            "launches_per_frame": n_c3, "avg_launch_ms": c3_ms / max(n_c3, 1),
+            "executed_flops_per_frame": c3_exec, "algorithmic_flops_per_frame": c3_fl,
+            "algorithmic_TFLOPs": algorithmic_tfs, "winograd_f2_launches": n_wino, "winograd_f4_launches": n_wino4,
+            "winograd_gain": c3_fl / c3_exec,
+            "note": "achieved = MFMA flops the launches EXECUTE / time (an F(2x2,3x3) launch executes 1/2.25 of the "
+                    "direct-convolution count, an F(4x4,3x3) launch 1/4); algorithmic_TFLOPs = SURVEY 8d's "
+                    "direct-convolution flops / time"},
+        "stages": {
+            "splat_ms": ms_splat, "splat_GBps": splat_bytes / (ms_splat * 1e-3) / 1e9,
+            "splat_frac_hbm": splat_bytes / (ms_splat * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "splat_algorithmic_bytes": splat_bytes, "splat_ms_queued": STAGE_EXTRA.get("splat_ms_queued"),
+            "splat_ms_unannounced": STAGE_EXTRA.get("splat_ms_unannounced"), "splat_ms_host_paced": STAGE_EXTRA.get("splat_ms_host_paced"),
+            "splat_kernels_ms": STAGE_EXTRA.get("splat_kernels_ms"), "splat_kernel_sum_ms": STAGE_EXTRA.get("splat_kernel_sum_ms"),
+            "splat_frac_hbm_kernels": (splat_bytes / (STAGE_EXTRA["splat_kernel_sum_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                       if STAGE_EXTRA.get("splat_kernel_sum_ms") else None),
+            "splat_note": "splat_ms / splat_frac_hbm (= splat_ms_queued): mean per frame over ONE WHOLE LAP of the 256-pose sweep, next pose "
+                          "announced as in the timed loop, frames queued back to back (median of 3 laps); _unannounced: a lap without "
+                          "the announcement (5 launches per frame); _host_paced: rounds 2-4's loop (64 frames, a host sync per frame, "
+                          "poses 1..64); _kernel_sum: HIP events around every launch, lap mean",
+            "gather_ms": ms_gather, "gather_GBps": gather_bytes / (ms_gather * 1e-3) / 1e9,
+            "gather_frac_hbm": gather_bytes / (ms_gather * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "unet_ms": ms_unet, "unet_launches": len(prof), "unet_family_ms": c3_ms, "unet_other_ms": sum(m for (_, m, _, c) in prof if not c),
+            "unet_other_launches": sum(1 for (_, _, _, c) in prof if not c),
+            "unet_executed_TFLOPs": all_exec / (ms_unet * 1e-3) / 1e12,
+            "unet_frac_mfma": all_exec / (ms_unet * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFS,
+            "unet_algorithmic_TFLOPs": all_fl / (ms_unet * 1e-3) / 1e12},
+    }
+
+
 def self_launch(a):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): start the N ranks ourselves — the same
     argv under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1 and a free port — and hand their exit
@@ -1090,7 +1220,7 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
 
     if a.config == "train":
-        out = run_train(a, dev, cpu_timing=(world == 1), do_verify=(rank == 0))
+        out = run_train(a, dev, cpu_timing=(world == 1), do_verify=(rank == 0), dump=a.dump_outputs if rank == 0 else "")
         bad = out["verified"] is not None and not out["verified"]["ok"]
         if rank == 0:
             print(json.dumps(out), flush=True)
@@ -1108,53 +1238,39 @@ def main():
     shard = (a.pose_offset, a.pose_stride) if a.pose_stride else None
     assert shard is None or (world == 1 and 0 <= a.pose_offset < a.pose_stride), "--pose-stride is a single-GPU proxy"
     dt = timed_sweep(wl, ex, a.warmup, a.steps, world, dev, a.pose_layout, shard)
+    if rank == 0 and a.dump_outputs:
+        # the last timed step's frames as its caller receives them: (ranks, H, W, RGBA); this rank's alone without an exchange
+        dump_outputs(a.dump_outputs, {"frames": ex.frames(a.warmup + a.steps - 1)})
 
-    # ---- every rank checks one of ITS OWN frames (the first pose it rendered) against the oracle on its host cores
     rc = 0
     my_verified = None
     base = None
-    my_pose0 = sweep.pose_of_step(0, *(shard or (rank, world)), N_POSES, a.pose_layout)
-    if not a.no_cpu_baseline:
-        base, first = cpu_leg(wl, a.cpu_frames if (rank == 0 and world == 1) else 0, pose0=my_pose0)
-        my_verified = verify(wl, first, pose=my_pose0)
-    verified_ranks = sweep.gather_objects(None if my_verified is None else bool(my_verified["ok"]))
+    verified_ranks = None
+    if a.full:
+        # ---- every rank checks one of ITS OWN frames (the first pose it rendered) against the oracle on its host cores
+        my_pose0 = sweep.pose_of_step(0, *(shard or (rank, world)), N_POSES, a.pose_layout)
+        if not a.no_cpu_baseline:
+            base, first = cpu_leg(wl, a.cpu_frames if (rank == 0 and world == 1) else 0, pose0=my_pose0)
+            my_verified = verify(wl, first, pose=my_pose0)
+        verified_ranks = sweep.gather_objects(None if my_verified is None else bool(my_verified["ok"]))
 
     if rank == 0:
-        # Per-kernel figures AFTER the CPU leg, as in rounds 1-3: the device has idled for the ~15 s of the CPU baseline and runs
-        # at the clocks the rocprofv3 tables in profiles/ were taken at.  Right after the sustained sweep the same rasteriser loop
-        # reads 94-99 us instead of 85-90 (measured in round 4: the rasteriser is latency / issue bound and follows the clock; the
-        # F(4x4) figure does not move).  Medians of five batches: a late host (the CPU leg's OpenMP threads) cannot leak into them.
-        ms_splat, ms_gather, ms_unet = stage_times(wl)
-        # per launch: the MEDIAN of five instrumented frames (event intervals around every launch) — one late launch in one pass
-        # (a host hiccup between two event records) moved the mean of three by 5 % in one of the round's runs
-        passes = [wl.profile() for _ in range(5)]
-        prof = [(l, float(np.median([p_[i][1] for p_ in passes])), fl, c) for i, (l, _, fl, c) in enumerate(passes[0])]
-        c3_ms = sum(m for (_, m, _, c) in prof if c)
-        c3_fl = sum(fl for (_, _, fl, c) in prof if c)
-        n_c3 = sum(1 for (_, _, _, c) in prof if c)
-        all_fl = sum(fl for (_, _, fl, _) in prof)
-        algorithmic_tfs = c3_fl / (c3_ms * 1e-3) / 1e12
-        # a launch that ran a Winograd kernel executes fewer MFMA flops than the algorithmic (direct-convolution) count:
-        # F(2x2,3x3) 1/2.25 (c == 2), F(4x4,3x3) 1/4 (c == 4)
-        # ... and the split-operand F(4x4) kernel (c == 5) forms each of those products from THREE f16 piece pairs on the f16 matrix
-        # cores: it executes 3/4 of the direct count there.  `gain` = direct count / fp32-product count (what an fp32 kernel would run)
-        # the direct split-operand kernel (c == 6: FAM's launches) executes every product, three piece pairs each
-        gain = {0: 1.0, 1: 1.0, 2: 2.25, 4: 4.0, 5: 4.0, 6: 1.0}
-        c3_exec = sum(fl / gain.get(c, 1.0) for (_, _, fl, c) in prof if c)
-        n_wino = sum(1 for (_, _, _, c) in prof if c == 2)
-        n_wino4 = sum(1 for (_, _, _, c) in prof if c == 4)
+        if a.full:
+            # Per-kernel figures AFTER the CPU leg, as in rounds 1-3: the device has idled for the ~15 s of the CPU baseline and runs
+            # at the clocks the rocprofv3 tables in profiles/ were taken at.  Right after the sustained sweep the same rasteriser loop
+            # reads 94-99 us instead of 85-90 (measured in round 4: the rasteriser is latency / issue bound and follows the clock; the
+            # F(4x4) figure does not move).  Medians of five batches: a late host (the CPU leg's OpenMP threads) cannot leak into them.
+            ms_splat, ms_gather, ms_unet = stage_times(wl)
+            # per launch: the MEDIAN of five instrumented frames (event intervals around every launch) — one late launch in one pass
+            # (a host hiccup between two event records) moved the mean of three by 5 % in one of the round's runs
+            passes = [wl.profile() for _ in range(5)]
+            prof = [(l, float(np.median([p_[i][1] for p_ in passes])), fl, c) for i, (l, _, fl, c) in enumerate(passes[0])]
+        else:
+            # one instrumented frame on pose 0's features: the kernel family of every launch, which the line's dtype names
+            wl.rasterize(0)
+            wl.gather()
+            prof = wl.profile()
         n_w4h = sum(1 for (_, _, _, c) in prof if c == 5)
-        executed_tfs = c3_exec / (c3_ms * 1e-3) / 1e12          # fp32-product equivalent: comparable with rounds 3-5
-        all_exec = sum(fl / gain.get(c, 1.0) for (_, _, fl, c) in prof)
-        n_d3h = sum(1 for (_, _, _, c) in prof if c == 6)
-        w4h_ms = sum(m for (_, m, _, c) in prof if c == 5)
-        w4h_f16_flops = sum(3.0 * fl / 4.0 for (_, _, fl, c) in prof if c == 5)
-        w4h_tfs = w4h_f16_flops / (w4h_ms * 1e-3) / 1e12 if n_w4h else None
-        sizes = camera.level_sizes(W, H, 5)
-        splat_bytes = 12.0 * N + 8.0 * sum(w * h for (w, h) in sizes)
-        gather_bytes = 68.0 * sum(w * h for (w, h) in sizes)
-        traffic, traffic_src = profiled_traffic() if a.config == "slab30m" else (None, None)
-        sustained = mfma_sustained_tfs(dev)
         out = {
             "metric": "rendered frames/sec @1216x352, 30M pts" if a.config == "slab30m"
                       else "rendered frames/sec @1216x368, kitti6-like 10M pts",
@@ -1168,62 +1284,10 @@ def main():
                        "shard_proxy_of": None if shard is None else {"rank": shard[0], "world": shard[1]},
                        "frame_exchange": ex.mode or "none",
                        "frames_in_flight": a.frames_in_flight},
-            "roofline": {
-                "kernel": ("gated_conv_wino4h_kernel: Winograd F(4x4,3x3) with split fp32 operands on the f16 matrix cores "
-                           f"({n_w4h} of the {n_c3} launches of the 3x3/s1 C->C family; {n_d3h} (FAM's x1 * x2) on the direct split-operand kernel "
-                           f"gated_conv_d3h_kernel, {n_wino4} on the fp32-matrix-core F(4x4) kernel, "
-                           f"{n_wino} F(2x2), {n_c3 - n_wino - n_wino4 - n_w4h - n_d3h} direct fp32)") if n_w4h else
-                          ("3x3/s1 C->C gated conv family: Winograd kernels on the fp32 matrix cores "
-                           f"({n_wino} launches F(2x2,3x3), {n_wino4} launches F(4x4,3x3), {n_c3 - n_wino - n_wino4} direct)"),
-                "bound": "mfma",
-                "achieved": w4h_tfs if n_w4h else executed_tfs, "peak": F16_MFMA_PEAK_TFS if n_w4h else FP32_MFMA_PEAK_TFS, "unit": "TFLOP/s",
-                "frac": (w4h_tfs / F16_MFMA_PEAK_TFS) if n_w4h else executed_tfs / FP32_MFMA_PEAK_TFS,
-                "frac_note": ("executed f16 MFMA flops (3 piece pairs x 1/4 of the direct count) / launch time / the f16 dense peak.  The kernel "
-                              "is NOT matrix-pipe bound on this path: its MFMAs alone take 9 us of a 44 us launch (profiles/r6_w4h_ablation.md); what "
-                              "binds it is the operand stream — 288 KiB of weight fragments + 43 KiB of patch per unit and 32 channels from "
-                              "L2 into one CU, with 48 KiB in flight (`operand_stream`)") if n_w4h else None,
-                "fp32_equivalent": {"achieved": executed_tfs, "peak": FP32_MFMA_PEAK_TFS, "frac": executed_tfs / FP32_MFMA_PEAK_TFS,
-                                    "note": "the fp32 products an fp32-matrix-core kernel would execute for the same launches (direct count / 4 "
-                                            "for F(4x4)) / the family's time / the fp32 MFMA peak: the figure rounds 3-5 reported as frac (0.40)"},
-                "traffic": traffic, "traffic_stale": profile_staleness()[0], "profile_sources": profile_staleness()[1],
-                "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE*2 + WRITE_SIZE)",
-                "traffic_source": f"static: profiles/{traffic_src} — separate --pmc passes of this command, committed; NOT measured "
-                                  "in this run (counters need rocprofv3 around the process)" if traffic_src else None,
-                "mfma_busy": profiled_mfma_busy(),
-                "mfma_busy_source": "static: profiles/r6_pmc_mfma_busy.md — rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES per level, committed; NOT "
-                                    "measured in this run; it agrees with executed flops / time per level (same file)",
-                "mfma_sustained": sustained, "frac_of_sustained": executed_tfs / sustained if sustained else None,
-                "mfma_sustained_note": "TFLOP/s of back-to-back v_mfma_f32_16x16x4_f32, one wave per SIMD on every CU, measured live in this run "
-                                       "(read_mfma_f32_rate_probe): the matrix pipe at the clock the chip sustains; `peak` is the guide's figure at 2.4 GHz",
-                "frac_algorithmic": algorithmic_tfs / FP32_MFMA_PEAK_TFS,
-                "launches_per_frame": n_c3, "avg_launch_ms": c3_ms / max(n_c3, 1),
-                "executed_flops_per_frame": c3_exec, "algorithmic_flops_per_frame": c3_fl,
-                "algorithmic_TFLOPs": algorithmic_tfs, "winograd_f2_launches": n_wino, "winograd_f4_launches": n_wino4,
-                "winograd_gain": c3_fl / c3_exec,
-                "note": "achieved = MFMA flops the launches EXECUTE / time (an F(2x2,3x3) launch executes 1/2.25 of the "
-                        "direct-convolution count, an F(4x4,3x3) launch 1/4); algorithmic_TFLOPs = SURVEY 8d's "
-                        "direct-convolution flops / time"},
-            "stages": {
-                "splat_ms": ms_splat, "splat_GBps": splat_bytes / (ms_splat * 1e-3) / 1e9,
-                "splat_frac_hbm": splat_bytes / (ms_splat * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "splat_algorithmic_bytes": splat_bytes, "splat_ms_queued": STAGE_EXTRA.get("splat_ms_queued"),
-                "splat_ms_unannounced": STAGE_EXTRA.get("splat_ms_unannounced"), "splat_ms_host_paced": STAGE_EXTRA.get("splat_ms_host_paced"),
-                "splat_kernels_ms": STAGE_EXTRA.get("splat_kernels_ms"), "splat_kernel_sum_ms": STAGE_EXTRA.get("splat_kernel_sum_ms"),
-                "splat_frac_hbm_kernels": (splat_bytes / (STAGE_EXTRA["splat_kernel_sum_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-                                           if STAGE_EXTRA.get("splat_kernel_sum_ms") else None),
-                "splat_note": "splat_ms / splat_frac_hbm (= splat_ms_queued): mean per frame over ONE WHOLE LAP of the 256-pose sweep, next pose "
-                              "announced as in the timed loop, frames queued back to back (median of 3 laps); _unannounced: a lap without "
-                              "the announcement (5 launches per frame); _host_paced: rounds 2-4's loop (64 frames, a host sync per frame, "
-                              "poses 1..64); _kernel_sum: HIP events around every launch, lap mean",
-                "gather_ms": ms_gather, "gather_GBps": gather_bytes / (ms_gather * 1e-3) / 1e9,
-                "gather_frac_hbm": gather_bytes / (ms_gather * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "unet_ms": ms_unet, "unet_launches": len(prof), "unet_family_ms": c3_ms, "unet_other_ms": sum(m for (_, m, _, c) in prof if not c),
-                "unet_other_launches": sum(1 for (_, _, _, c) in prof if not c),
-                "unet_executed_TFLOPs": all_exec / (ms_unet * 1e-3) / 1e12,
-                "unet_frac_mfma": all_exec / (ms_unet * 1e-3) / 1e12 / FP32_MFMA_PEAK_TFS,
-                "unet_algorithmic_TFLOPs": all_fl / (ms_unet * 1e-3) / 1e12},
-            "tuning": _lib.tuning_state(),
         }
+        if a.full:
+            out.update(kernel_figures(a, wl, dev, prof, ms_splat, ms_gather, ms_unet))
+        out["tuning"] = _lib.tuning_state()
         if a.detail:
             os.makedirs(os.path.dirname(os.path.abspath(a.detail)), exist_ok=True)
             with open(a.detail, "w") as fh:
@@ -1233,7 +1297,7 @@ def main():
         out["verified_ranks"] = verified_ranks
         if my_verified is not None and not all(bool(v) for v in verified_ranks):
             rc = 3
-        if a.config == "slab30m" and world == 1 and not a.no_also:
+        if a.full and a.config == "slab30m" and world == 1 and not a.no_also:
             out["also"] = also_records(a, dev, wl, first if not a.no_cpu_baseline else None)
             for k, r in out["also"].items():
                 v = r.get("verified")

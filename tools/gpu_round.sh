@@ -41,15 +41,15 @@ PY
             done
             python "$R/tools/splat_kstats.py" "$O"/${TAG}_sp_st_*/ | tee "$O/${TAG}_street_kernels.txt"
             ( cd "$R" && SPLAT_PROBE_SCENE=street SPLAT_PROBE_H=368 timeout 200 python tools/splat_cells_probe.py 10000000 ) 2>&1 | tail -14 ;;
-    bencht) run bencht 900 python bench.py --config train ;;
-    benchk) run benchk 600 python bench.py --config kitti6_like --detail "$O/${TAG}_detailk.json" ;;
+    bencht) run bencht 900 python bench.py --config train --full ;;
+    benchk) run benchk 600 python bench.py --config kitti6_like --full --detail "$O/${TAG}_detailk.json" ;;
     splat)  run splat 400 python tools/splat_modes.py --out "$O/${TAG}_splat_modes.json" ;;
     sweep)  run sweep 400 python tools/sweep_conv.py --out "$O/${TAG}_sweep.json" ;;
     trace)  run trace 300 bash -c "python tools/trace_conv.py --shape L0 --configs 0,10 --out $O/${TAG}_trace; python tools/trace_conv.py --shape L1 --configs 10 --out $O/${TAG}_trace; python tools/trace_conv.py --shape L2 --configs 4 --out $O/${TAG}_trace; python tools/trace_conv.py --shape L3 --configs 11 --out $O/${TAG}_trace" ;;
-    benchw) run benchw 500 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --tune conv_wave=1 --detail "$O/${TAG}_detailw.json" ;;
+    benchw) run benchw 500 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --tune conv_wave=1 --detail "$O/${TAG}_detailw.json" ;;
     pytestw) run pytestw 600 env READ_CONV_WAVE=1 python -m pytest tests/test_gpu_unet.py tests/test_gpu_api.py -m gpu -q --timeout 600 -p no:cacheprovider -s ;;
     stagger) for t in 0 400 800 1600; do run stagger$t 200 python tools/sweep_conv.py --shapes 4 --only wave --tune conv_stagger=$t --iters 10 --out "$O/${TAG}_stagger$t.json"; done ;;
-    bench)  run bench 600 python bench.py --detail "$O/${TAG}_detail.json" ;;
+    bench)  run bench 600 python bench.py --full --detail "$O/${TAG}_detail.json" ;;
     prof)   ( cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${TAG}_prof" -o bench -- python "$R/bench.py" --steps 20 --warmup 3 --no-cpu-baseline ) > "$O/${TAG}_prof.log" 2>&1; echo "rc=$?" >> "$O/${TAG}_prof.log"; tail -n 3 "$O/${TAG}_prof.log"
             find "$O/${TAG}_prof" -name "*kernel_stats*" | head -3 ;;
     pmcconv) ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d "$O/${TAG}_pmc_mfma" -o conv -- python "$R/tools/sweep_conv.py" --main-only --iters 2 --out "$O/${TAG}_pmc_sweep.json" ) > "$O/${TAG}_pmc_mfma.log" 2>&1; echo "rc=$?" >> "$O/${TAG}_pmc_mfma.log"; tail -n 2 "$O/${TAG}_pmc_mfma.log" ;;
