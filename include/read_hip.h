@@ -114,9 +114,10 @@ int read_splat_forward(const float *xyz, int64_t n, const float *M_host, int B, 
                        void *ws, size_t ws_bytes, void *stream);
 
 /* Cell-ordered copy of a cloud (optional accelerator of the single-camera path; results are bit-identical).
- * read_splat_cells_build_host() sorts the points once along a Morton curve into chunks of 1024 records
- * (x, y, z, original id) with their bounding boxes (host arrays in, host blob of read_splat_cells_bytes(n) out,
- * multi-threaded); the caller uploads the blob (256-byte aligned) and passes it to read_splat_forward_cells().
+ * read_splat_cells_build() sorts the points once along a Morton curve into chunks of 1024 records
+ * (x, y, z, original id) with their bounding boxes, on the device (device cloud in, device blob of read_splat_cells_bytes(n)
+ * out, a few milliseconds); read_splat_cells_build_host() writes the same blob on the host (multi-threaded; the caller uploads
+ * it, e.g. after one rank built it for all).  The blob (256-byte aligned) is then passed to read_splat_forward_cells().
  * Whole chunks outside the frustum, or behind the far depth bound of every 4x4 pixel block they can touch, are then
  * skipped without reading their points, and the z-test runs XCD-striped against an L2-resident bound image
  * (csrc/splat.hip).  The tail of the blob is per-frame scratch (chunk lists), so one blob serves one stream at a
@@ -136,6 +137,15 @@ int read_splat_hint_next_camera(void *workspace, const float *M_next_host);
 int read_splat_profile_last(float *ms5);
 size_t read_splat_cells_bytes(int64_t n);
 int read_splat_cells_build_host(const float *xyz_host, int64_t n, void *cells_host, size_t cells_bytes);
+/* The same blob built on the device from a cloud already in HBM (xyz, cells and scratch are device pointers; cells and scratch
+ * 256-byte aligned): byte for byte what read_splat_cells_build_host writes, except possibly the sign of a zero in a min / max
+ * field.  Stream-ordered; allocates nothing: the caller provides read_splat_cells_build_scratch_bytes(n) bytes of scratch
+ * (0 when n is out of range; about 8 bytes per point).  A non-finite point fails with the host builder's message and the smallest
+ * bad index, the blob left as it was; that costs one small device -> host read and one synchronisation of the stream at the end
+ * of the call, the only one.  Rewriting a blob in place includes read_splat_cells_invalidate(cells, n). */
+size_t read_splat_cells_build_scratch_bytes(int64_t n);
+int read_splat_cells_build(const float *xyz_dev, int64_t n, void *cells_dev, size_t cells_bytes, void *scratch_dev,
+                           size_t scratch_bytes, void *stream);
 /* The library keeps host-side bookkeeping per cell blob ADDRESS (which frames ran over its chunk lists; a frame prepared for an
  * announced camera is only consumed while nothing else touched them).  Whoever rewrites a blob in place, copies another cloud's
  * blob over it, or frees it (the allocator may hand the address out again) calls this: pending preparations made against the old

@@ -370,8 +370,8 @@ __global__ __launch_bounds__(256) void splat_seed_kernel(const float *__restrict
 
 
 // ---- cell-ordered cloud, XCD-striped passes -------------------------------------------------------------------------
-// read_splat_cells_build_host() sorts the cloud once along a Morton curve and cuts it into chunks of 1024 points with
-// their bounding boxes; every record is (x, y, z, original id), so keys carry the ORIGINAL id and the result is
+// read_splat_cells_build() (device; read_splat_cells_build_host() writes the same blob on the host) sorts the cloud once along
+// a Morton curve and cuts it into chunks of 1024 points with their bounding boxes; every record is (x, y, z, original id), so keys carry the ORIGINAL id and the result is
 // bit-identical to the unsorted pass (atomic min does not care about order).  Per frame, five launches — FOUR when the caller
 // announced this frame's camera one frame ahead (read_splat_hint_next_camera): the previous frame's resolve launch then already
 // did this frame's seeds and classification (cells_resolve_next_kernel), in the OTHER of the two sets of per-frame state:
@@ -1964,7 +1964,9 @@ CellOffsets cell_offsets(int64_t n)
     return o;
 }
 
-inline uint32_t spread10(uint32_t v)       // 10 bits -> every third bit
+// The arithmetic of the build, shared by the host builder and the device kernels below so that the two cannot drift apart
+// (fp contraction is off in this file: (v - lo) * scale stays two rounded operations; the fp32 division is correctly rounded).
+__host__ __device__ inline uint32_t spread10(uint32_t v)       // 10 bits -> every third bit
 {
     v &= 0x3ffu;
     v = (v | (v << 16)) & 0x30000ffu;
@@ -1972,6 +1974,41 @@ inline uint32_t spread10(uint32_t v)       // 10 bits -> every third bit
     v = (v | (v << 4)) & 0x30c30c3u;
     v = (v | (v << 2)) & 0x9249249u;
     return v;
+}
+
+__host__ __device__ inline bool cell_finite(float v) { return v == v && v - v == 0.0f; }
+
+__host__ __device__ inline float cell_extent(const float lo[3], const float hi[3])
+{
+    float ext = 0.0f;
+    for (int k = 0; k < 3; ++k) ext = (hi[k] - lo[k]) > ext ? (hi[k] - lo[k]) : ext;
+    return ext;
+}
+
+__host__ __device__ inline float cell_scale(float ext) { return ext > 0.0f ? 1023.999f / ext : 0.0f; }
+
+__host__ __device__ inline uint32_t cell_quant(float v, float lo, float scale)       // grid cell 0..1023 of one coordinate
+{
+    const float t = (v - lo) * scale;
+    return t <= 0.0f ? 0u : (t >= 1023.0f ? 1023u : (uint32_t)t);
+}
+
+// (30-bit Morton code << 32) | id: the sort key of one point
+__host__ __device__ inline uint64_t cell_key(float x, float y, float z, const float lo[3], float scale, uint32_t id)
+{
+    const uint64_t code = spread10(cell_quant(x, lo[0], scale)) | ((uint64_t)spread10(cell_quant(y, lo[1], scale)) << 1) |
+                          ((uint64_t)spread10(cell_quant(z, lo[2], scale)) << 2);
+    return (code << 32) | (uint64_t)id;
+}
+
+__host__ __device__ inline float cell_density(long long n, const float lo[3], const float hi[3], float ext)
+{
+    double vol = 1.0;
+    for (int k = 0; k < 3; ++k) {
+        const double e = (double)hi[k] - lo[k];
+        vol *= e > 1e-6 * ext ? e : (ext > 0 ? 1e-6 * ext : 1.0);   // a flat cloud still gets a finite density
+    }
+    return (float)((double)n / (vol > 0 ? vol : 1.0));
 }
 
 // run fn(t, begin, end) over [0, n) split into T contiguous ranges on T host threads
@@ -2017,7 +2054,7 @@ extern "C" int read_splat_cells_build_host(const float *xyz, int64_t n, void *bl
         for (size_t i = b; i < e; ++i)
             for (int k = 0; k < 3; ++k) {
                 const float v = xyz[3 * i + k];
-                if (!(v == v && v - v == 0.0f) && bad < 0) bad = (long long)i;
+                if (!cell_finite(v) && bad < 0) bad = (long long)i;
                 lo[k] = v < lo[k] ? v : lo[k];
                 hi[k] = v > hi[k] ? v : hi[k];
             }
@@ -2035,22 +2072,13 @@ extern "C" int read_splat_cells_build_host(const float *xyz, int64_t n, void *bl
             hi[k] = std::max(hi[k], thi[(size_t)t * 3 + k]);
         }
     }
-    float ext = 0.0f;
-    for (int k = 0; k < 3; ++k) ext = (hi[k] - lo[k]) > ext ? (hi[k] - lo[k]) : ext;
-    const float scale = ext > 0.0f ? 1023.999f / ext : 0.0f;
+    const float ext = cell_extent(lo, hi);
+    const float scale = cell_scale(ext);
 
     // 2. Morton codes (30 bits) with the id in the low word
     std::vector<uint64_t> a(N), b(N);
     parallel_ranges(N, T, [&](int, size_t bgn, size_t end) {
-        for (size_t i = bgn; i < end; ++i) {
-            uint32_t q[3];
-            for (int k = 0; k < 3; ++k) {
-                const float t = (xyz[3 * i + k] - lo[k]) * scale;
-                q[k] = t <= 0.0f ? 0u : (t >= 1023.0f ? 1023u : (uint32_t)t);
-            }
-            const uint64_t code = spread10(q[0]) | ((uint64_t)spread10(q[1]) << 1) | ((uint64_t)spread10(q[2]) << 2);
-            a[i] = (code << 32) | (uint64_t)(uint32_t)i;
-        }
+        for (size_t i = bgn; i < end; ++i) a[i] = cell_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], lo, scale, (uint32_t)i);
     });
 
     // 3. stable LSD radix sort, 10 bits per pass: per-thread histograms over contiguous ranges keep the order stable
@@ -2105,14 +2133,418 @@ extern "C" int read_splat_cells_build_host(const float *xyz, int64_t n, void *bl
     h->n = n;
     h->nchunks = (int)nc;
     h->version = CELL_VERSION;
-    double vol = 1.0;
     for (int k = 0; k < 3; ++k) {
         h->bbox[k] = lo[k];
         h->bbox[3 + k] = hi[k];
-        const double e = (double)hi[k] - lo[k];
-        vol *= e > 1e-6 * ext ? e : (ext > 0 ? 1e-6 * ext : 1.0);   // a flat cloud still gets a finite density
     }
-    h->density = (float)((double)n / (vol > 0 ? vol : 1.0));
+    h->density = cell_density(n, lo, hi, ext);
+    return READ_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// cell-ordered cloud: device build (read_splat_cells_build) — the host build's blob, from a cloud already in HBM
+// ---------------------------------------------------------------------------------------------------------------
+//   cells_bounds_kernel    per-block partial box + smallest non-finite index (grid-stride)
+//   cells_finalize_kernel  one block: the box, ext, scale (-> params), the header; nothing of the blob is written, here or
+//                          later, when a point is not finite (every later kernel returns at once; the host reports the index)
+//   cells_codes_kernel     key[i] = (morton30 << 32) | i
+//   4 passes of 8 bits over key bits 32..63 (stable LSD radix sort; the keys are unique, so the order is THE sorted order and
+//   equal codes keep ascending ids, as on the host):
+//     cells_hist_kernel    per tile of CB_TILE keys, the count of each digit -> hist[digit][tile]
+//     cells_scan_kernel    one block per digit: exclusive scan of its row in place, row total -> dtot[digit]
+//     cells_scatter_kernel per tile: stable rank of every key (wave64 ballots + LDS, round by round in index order), the tile
+//                          in digit order in LDS, then runs of equal digits to exclusive_scan(dtot)[d] + hist[d][tile] + rank
+//   cells_records_kernel   one block per chunk: records gathered through the sorted ids, tail copies of the last point,
+//                          exact chunk box; sticky flags zeroed
+// The keys ping-pong between the scratch and the blob's record region (16 B per point, a key is 8): codes -> scratch, then
+// scratch -> records -> scratch -> records -> scratch, so the sorted keys end in the scratch, from where the records kernel
+// fills the record region.  No workgroup waits for another within a launch.
+namespace {
+
+constexpr int CB_THREADS = 256;
+constexpr int CB_ITEMS = 16;                        // keys per thread of a sort tile
+constexpr int CB_TILE = CB_THREADS * CB_ITEMS;      // 4096 keys per sort tile
+constexpr int CB_WAVES = CB_THREADS / 64;
+constexpr int CB_BOUNDS_BLOCKS = 1024;
+constexpr int CB_CODES_BLOCKS = 8192;
+constexpr int CB_PASSES = 4;                        // 8 bits each over key bits 32..63 (the code has 30)
+constexpr long long CB_NO_BAD = 0x7fffffffffffffffll;
+
+struct CellBuildParams {
+    float lo[3];
+    float scale;
+    long long bad;                                  // smallest index of a non-finite point, or -1
+};
+struct CellBoundsPart {
+    float lo[3], hi[3];
+    long long bad;                                  // CB_NO_BAD: none
+};
+
+size_t cb_tiles(int64_t n) { return (size_t)((n + CB_TILE - 1) / CB_TILE); }
+
+struct CellBuildLayout {                            // byte offsets into the caller's scratch
+    size_t keys, hist, dtot, parts, params, total;
+};
+CellBuildLayout cell_build_layout(int64_t n)
+{
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    CellBuildLayout s;
+    s.keys = 0;
+    s.hist = up((size_t)n * sizeof(uint64_t));
+    s.dtot = s.hist + up(256 * cb_tiles(n) * sizeof(unsigned));
+    s.parts = s.dtot + up(256 * sizeof(unsigned));
+    s.params = s.parts + up(CB_BOUNDS_BLOCKS * sizeof(CellBoundsPart));
+    s.total = s.params + up(sizeof(CellBuildParams));
+    return s;
+}
+
+// box (min / max by the host's comparisons) and smallest bad index of the block, in thread 0
+__device__ __forceinline__ void cb_reduce_box(float lo[3], float hi[3], long long &bad)
+{
+    __shared__ float s_lo[CB_WAVES][3], s_hi[CB_WAVES][3];
+    __shared__ long long s_bad[CB_WAVES];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float a = __shfl_xor(lo[k], o), b = __shfl_xor(hi[k], o);
+            lo[k] = a < lo[k] ? a : lo[k];
+            hi[k] = b > hi[k] ? b : hi[k];
+        }
+        const long long c = __shfl_xor(bad, o);
+        bad = c < bad ? c : bad;
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        for (int k = 0; k < 3; ++k) {
+            s_lo[w][k] = lo[k];
+            s_hi[w][k] = hi[k];
+        }
+        s_bad[w] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int v = 1; v < CB_WAVES; ++v) {
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = s_lo[v][k] < lo[k] ? s_lo[v][k] : lo[k];
+                hi[k] = s_hi[v][k] > hi[k] ? s_hi[v][k] : hi[k];
+            }
+            bad = s_bad[v] < bad ? s_bad[v] : bad;
+        }
+}
+
+// exclusive prefix of v over the block's threads (in thread order) and the block total; every thread calls it
+__device__ __forceinline__ unsigned cb_block_exclusive_scan(unsigned v, unsigned &total, unsigned *wsum)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    unsigned x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned y = __shfl_up(x, o);
+        x += lane >= o ? y : 0u;
+    }
+    __syncthreads();                                // wsum is free: a previous call has read it
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    unsigned before = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < CB_WAVES; ++k) {
+        before += k < w ? wsum[k] : 0u;
+        total += wsum[k];
+    }
+    return before + x - v;
+}
+
+// lanes of this wave that hold a valid key with digit d (every lane of the wave calls it)
+__device__ __forceinline__ unsigned long long cb_peers(unsigned d, bool valid)
+{
+    unsigned long long m = __ballot(valid);
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const unsigned long long v = __ballot((d >> b) & 1u);
+        m &= ((d >> b) & 1u) ? v : ~v;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(CB_THREADS) void cells_bounds_kernel(const float *__restrict__ xyz, long long n,
+                                                                  CellBoundsPart *__restrict__ parts)
+{
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    long long bad = CB_NO_BAD;
+    for (long long i = (long long)blockIdx.x * CB_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * CB_THREADS) {
+        const float p[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (!cell_finite(p[k]) && bad == CB_NO_BAD) bad = i;      // a thread's indices ascend: its first is its smallest
+            lo[k] = p[k] < lo[k] ? p[k] : lo[k];
+            hi[k] = p[k] > hi[k] ? p[k] : hi[k];
+        }
+    }
+    cb_reduce_box(lo, hi, bad);
+    if (threadIdx.x == 0) {
+        CellBoundsPart &q = parts[blockIdx.x];
+        for (int k = 0; k < 3; ++k) {
+            q.lo[k] = lo[k];
+            q.hi[k] = hi[k];
+        }
+        q.bad = bad;
+    }
+}
+
+__global__ __launch_bounds__(CB_THREADS) void cells_finalize_kernel(const CellBoundsPart *__restrict__ parts, int nparts,
+                                                                    long long n, int nchunks, CellBuildParams *__restrict__ prm,
+                                                                    uint4 *__restrict__ hdr)
+{
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    long long bad = CB_NO_BAD;
+    for (int p = threadIdx.x; p < nparts; p += CB_THREADS) {
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = parts[p].lo[k] < lo[k] ? parts[p].lo[k] : lo[k];
+            hi[k] = parts[p].hi[k] > hi[k] ? parts[p].hi[k] : hi[k];
+        }
+        bad = parts[p].bad < bad ? parts[p].bad : bad;
+    }
+    cb_reduce_box(lo, hi, bad);
+    if (threadIdx.x != 0) return;
+    const float ext = cell_extent(lo, hi);
+    for (int k = 0; k < 3; ++k) prm->lo[k] = lo[k];
+    prm->scale = cell_scale(ext);
+    prm->bad = bad == CB_NO_BAD ? -1 : bad;
+    if (bad != CB_NO_BAD) return;                   // the blob stays as it was
+    union {
+        CellHeader h;
+        uint4 w[CELL_HEADER_BYTES / 16];
+    } u;
+    for (int i = 0; i < (int)(CELL_HEADER_BYTES / 16); ++i) u.w[i] = make_uint4(0u, 0u, 0u, 0u);
+    u.h.n = n;
+    u.h.nchunks = nchunks;
+    u.h.version = CELL_VERSION;
+    for (int k = 0; k < 3; ++k) {
+        u.h.bbox[k] = lo[k];
+        u.h.bbox[3 + k] = hi[k];
+    }
+    u.h.density = cell_density(n, lo, hi, ext);
+    for (int i = 0; i < (int)(CELL_HEADER_BYTES / 16); ++i) hdr[i] = u.w[i];
+}
+
+__global__ __launch_bounds__(CB_THREADS) void cells_codes_kernel(const float *__restrict__ xyz, long long n,
+                                                                 const CellBuildParams *__restrict__ prm,
+                                                                 unsigned long long *__restrict__ keys)
+{
+    if (prm->bad >= 0) return;
+    const float lo[3] = {prm->lo[0], prm->lo[1], prm->lo[2]};
+    const float scale = prm->scale;
+    for (long long i = (long long)blockIdx.x * CB_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * CB_THREADS)
+        keys[i] = cell_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], lo, scale, (uint32_t)i);
+}
+
+__global__ __launch_bounds__(CB_THREADS) void cells_hist_kernel(const unsigned long long *__restrict__ keys, long long n, int shift,
+                                                                unsigned *__restrict__ hist, unsigned tiles,
+                                                                const CellBuildParams *__restrict__ prm)
+{
+    __shared__ unsigned cnt[256];
+    if (prm->bad >= 0) return;
+    const unsigned t = threadIdx.x, lane = t & 63;
+    const size_t base = (size_t)blockIdx.x * CB_TILE;
+    unsigned long long k[CB_ITEMS];
+#pragma unroll
+    for (int r = 0; r < CB_ITEMS; ++r) {
+        const size_t i = base + (size_t)r * CB_THREADS + t;
+        k[r] = i < (size_t)n ? keys[i] : 0ull;
+    }
+    cnt[t] = 0u;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < CB_ITEMS; ++r) {
+        const bool valid = base + (size_t)r * CB_THREADS + t < (size_t)n;
+        const unsigned d = (unsigned)(k[r] >> shift) & 255u;
+        const unsigned long long m = cb_peers(d, valid);
+        if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&cnt[d], (unsigned)__popcll(m));   // one add per digit and wave
+    }
+    __syncthreads();
+    hist[(size_t)t * tiles + blockIdx.x] = cnt[t];
+}
+
+__global__ __launch_bounds__(CB_THREADS) void cells_scan_kernel(unsigned *__restrict__ hist, unsigned tiles, unsigned *__restrict__ dtot,
+                                                                const CellBuildParams *__restrict__ prm)
+{
+    __shared__ unsigned wsum[CB_WAVES];
+    if (prm->bad >= 0) return;
+    unsigned *row = hist + (size_t)blockIdx.x * tiles;
+    unsigned carry = 0;
+    for (unsigned b = 0; b < tiles; b += CB_THREADS) {
+        const unsigned i = b + threadIdx.x;
+        const unsigned v = i < tiles ? row[i] : 0u;
+        unsigned total;
+        const unsigned ex = cb_block_exclusive_scan(v, total, wsum);
+        if (i < tiles) row[i] = carry + ex;
+        carry += total;
+    }
+    if (threadIdx.x == 0) dtot[blockIdx.x] = carry;
+}
+
+__global__ __launch_bounds__(CB_THREADS) void cells_scatter_kernel(const unsigned long long *__restrict__ in,
+                                                                   unsigned long long *__restrict__ out, long long n, int shift,
+                                                                   const unsigned *__restrict__ hist, unsigned tiles,
+                                                                   const unsigned *__restrict__ dtot,
+                                                                   const CellBuildParams *__restrict__ prm)
+{
+    __shared__ unsigned long long sk[CB_TILE];      // the tile in digit order
+    __shared__ unsigned wc[2][CB_WAVES][256];       // per round: each wave's count of each digit, then its first rank (two rounds in flight)
+    __shared__ unsigned start[256];                 // first slot of each digit in sk
+    __shared__ unsigned gbase[256];                 // destination of the tile's first key of each digit
+    __shared__ unsigned wsum[CB_WAVES];
+    if (prm->bad >= 0) return;
+    const unsigned t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const size_t base = (size_t)blockIdx.x * CB_TILE;
+    unsigned long long k[CB_ITEMS];
+#pragma unroll
+    for (int r = 0; r < CB_ITEMS; ++r) {
+        const size_t i = base + (size_t)r * CB_THREADS + t;
+        k[r] = i < (size_t)n ? in[i] : 0ull;
+    }
+    unsigned total;
+    gbase[t] = cb_block_exclusive_scan(dtot[t], total, wsum) + hist[(size_t)t * tiles + blockIdx.x];
+    for (int j = t; j < 2 * CB_WAVES * 256; j += CB_THREADS) (&wc[0][0][0])[j] = 0u;
+    __syncthreads();
+    // Round r ranks keys base + r * 256 + [0, 256): index order = (round, wave, lane), so ranks are stable.  Thread t keeps the
+    // count of digit t so far (run).
+    const unsigned long long below_mask = (1ull << lane) - 1ull;
+    unsigned run = 0, pos[CB_ITEMS];
+#pragma unroll
+    for (int r = 0; r < CB_ITEMS; ++r) {
+        const int b = r & 1;
+        const bool valid = base + (size_t)r * CB_THREADS + t < (size_t)n;
+        const unsigned d = (unsigned)(k[r] >> shift) & 255u;
+        const unsigned long long m = cb_peers(d, valid);
+        const unsigned below = (unsigned)__popcll(m & below_mask);
+        if (valid && below == 0u) wc[b][w][d] = (unsigned)__popcll(m);
+        __syncthreads();
+        unsigned o = run;
+#pragma unroll
+        for (int v = 0; v < CB_WAVES; ++v) {
+            const unsigned c = wc[b][v][t];
+            wc[b][v][t] = o;
+            o += c;
+            wc[b ^ 1][v][t] = 0u;                   // the next round's counts (its last readers finished before the barrier above)
+        }
+        run = o;
+        __syncthreads();
+        pos[r] = wc[b][w][d] + below;
+    }
+    start[t] = cb_block_exclusive_scan(run, total, wsum);      // total = valid keys of the tile
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < CB_ITEMS; ++r) {
+        const unsigned slot = start[(unsigned)(k[r] >> shift) & 255u] + pos[r];
+        if (base + (size_t)r * CB_THREADS + t < (size_t)n && slot < (unsigned)CB_TILE) sk[slot] = k[r];
+    }
+    __syncthreads();
+    for (unsigned j = t; j < total && j < (unsigned)CB_TILE; j += CB_THREADS) {
+        const unsigned long long key = sk[j];
+        const unsigned d = (unsigned)(key >> shift) & 255u;
+        const size_t dst = (size_t)gbase[d] + (j - start[d]);
+        if (dst < (size_t)n) out[dst] = key;        // always true of a consistent histogram; a guard, not a case
+    }
+}
+
+__global__ __launch_bounds__(CB_THREADS) void cells_records_kernel(const unsigned long long *__restrict__ sorted,
+                                                                   const float *__restrict__ xyz, long long n,
+                                                                   float4 *__restrict__ rec, float4 *__restrict__ aabb,
+                                                                   unsigned char *__restrict__ sticky, unsigned sticky_bytes,
+                                                                   const CellBuildParams *__restrict__ prm)
+{
+    if (prm->bad >= 0) return;
+    const unsigned c = blockIdx.x;
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    long long none = CB_NO_BAD;
+#pragma unroll
+    for (int j = 0; j < CELL_CHUNK / CB_THREADS; ++j) {
+        const size_t i = (size_t)c * CELL_CHUNK + (size_t)j * CB_THREADS + threadIdx.x;
+        const uint32_t id = (uint32_t)sorted[i < (size_t)n ? i : (size_t)n - 1];      // tail: copies of the last point
+        const size_t src = 3 * (size_t)(id < (unsigned long long)n ? id : 0u);         // (a guard: ids are < n)
+        const float p[3] = {xyz[src], xyz[src + 1], xyz[src + 2]};
+        rec[i] = make_float4(p[0], p[1], p[2], __uint_as_float(id));
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = p[k] < lo[k] ? p[k] : lo[k];
+            hi[k] = p[k] > hi[k] ? p[k] : hi[k];
+        }
+    }
+    cb_reduce_box(lo, hi, none);
+    if (threadIdx.x == 0) {
+        aabb[2 * (size_t)c] = make_float4(lo[0], lo[1], lo[2], hi[0]);
+        aabb[2 * (size_t)c + 1] = make_float4(hi[1], hi[2], 0.0f, 0.0f);
+        sticky[c] = 0;
+    }
+    if (c == gridDim.x - 1)
+        for (unsigned j = gridDim.x + threadIdx.x; j < sticky_bytes; j += CB_THREADS) sticky[j] = 0;
+}
+
+}  // namespace
+
+extern "C" size_t read_splat_cells_build_scratch_bytes(int64_t n)
+{
+    if (n < 1 || n > 0xFFFFFFFEll) return 0;
+    return cell_build_layout(n).total;
+}
+
+// Device-side build: read_splat_cells_build_host's blob from a cloud in HBM, stream-ordered, in the caller's scratch.  One
+// device -> host read of the non-finite index and one synchronisation at the end.
+extern "C" int read_splat_cells_build(const float *xyz, int64_t n, void *cells, size_t cells_bytes, void *scratch,
+                                      size_t scratch_bytes, void *stream)
+{
+    READ_CHECK_ARG(xyz && cells && scratch, "read_splat_cells_build: null pointer");
+    READ_CHECK_ARG(n >= 1 && n <= 0xFFFFFFFEll, "read_splat_cells_build: n out of range");
+    const CellOffsets o = cell_offsets(n);
+    READ_CHECK_ARG(cells_bytes >= o.total, "read_splat_cells_build: buffer %zu < %zu bytes", cells_bytes, o.total);
+    const CellBuildLayout s = cell_build_layout(n);
+    READ_CHECK_ARG(scratch_bytes >= s.total, "read_splat_cells_build: scratch %zu < %zu bytes", scratch_bytes, s.total);
+    READ_CHECK_ARG((uintptr_t)cells % 256 == 0 && (uintptr_t)scratch % 256 == 0 && (uintptr_t)xyz % 4 == 0,
+                   "read_splat_cells_build: cells and scratch must be 256-byte aligned");
+    {
+        std::lock_guard<std::mutex> lock(g_ws_mutex);             // as read_splat_cells_invalidate: the blob is rewritten in place
+        g_cells_frames.erase((const char *)cells + o.pts);
+    }
+    hipStream_t st = as_stream(stream);
+    char *sc = (char *)scratch, *blob = (char *)cells;
+    unsigned long long *key_buf[2] = {(unsigned long long *)(sc + s.keys), (unsigned long long *)(blob + o.pts)};
+    unsigned *hist = (unsigned *)(sc + s.hist), *dtot = (unsigned *)(sc + s.dtot);
+    CellBoundsPart *parts = (CellBoundsPart *)(sc + s.parts);
+    CellBuildParams *prm = (CellBuildParams *)(sc + s.params);
+    const unsigned tiles = (unsigned)cb_tiles(n), nc = (unsigned)cells_chunks(n);
+    const int bounds_blocks = (int)std::min<int64_t>(ceil_div64(n, CB_THREADS), CB_BOUNDS_BLOCKS);
+    const unsigned codes_blocks = (unsigned)std::min<int64_t>(ceil_div64(n, CB_THREADS), CB_CODES_BLOCKS);
+
+    hipLaunchKernelGGL(cells_bounds_kernel, dim3((unsigned)bounds_blocks), dim3(CB_THREADS), 0, st, xyz, (long long)n, parts);
+    READ_CHECK_LAUNCH();
+    hipLaunchKernelGGL(cells_finalize_kernel, dim3(1), dim3(CB_THREADS), 0, st, parts, bounds_blocks, (long long)n, (int)nc, prm,
+                       (uint4 *)blob);
+    READ_CHECK_LAUNCH();
+    hipLaunchKernelGGL(cells_codes_kernel, dim3(codes_blocks), dim3(CB_THREADS), 0, st, xyz, (long long)n, prm, key_buf[0]);
+    READ_CHECK_LAUNCH();
+    for (int pass = 0; pass < CB_PASSES; ++pass) {
+        const int shift = 32 + 8 * pass;
+        unsigned long long *src = key_buf[pass & 1], *dst = key_buf[(pass & 1) ^ 1];
+        hipLaunchKernelGGL(cells_hist_kernel, dim3(tiles), dim3(CB_THREADS), 0, st, src, (long long)n, shift, hist, tiles, prm);
+        READ_CHECK_LAUNCH();
+        hipLaunchKernelGGL(cells_scan_kernel, dim3(256), dim3(CB_THREADS), 0, st, hist, tiles, dtot, prm);
+        READ_CHECK_LAUNCH();
+        hipLaunchKernelGGL(cells_scatter_kernel, dim3(tiles), dim3(CB_THREADS), 0, st, src, dst, (long long)n, shift, hist, tiles,
+                           dtot, prm);
+        READ_CHECK_LAUNCH();
+    }
+    static_assert(CB_PASSES % 2 == 0, "the sorted keys must end in the scratch, not in the record region they are gathered into");
+    hipLaunchKernelGGL(cells_records_kernel, dim3(nc), dim3(CB_THREADS), 0, st, key_buf[0], xyz, (long long)n,
+                       (float4 *)(blob + o.pts), (float4 *)(blob + o.aabb), (unsigned char *)(blob + o.sticky),
+                       (unsigned)(o.total - o.sticky), prm);
+    READ_CHECK_LAUNCH();
+    long long bad = -1;
+    READ_CHECK_HIP(hipMemcpyAsync(&bad, &prm->bad, sizeof(bad), hipMemcpyDeviceToHost, st));
+    READ_CHECK_HIP(hipStreamSynchronize(st));
+    READ_CHECK_ARG(bad < 0, "read_splat_cells_build: point %lld is not finite", bad);
     return READ_OK;
 }
 

@@ -24,7 +24,7 @@ class PointCloudRasterizer:
     CELLS_MIN_POINTS = 1 << 20      # below this the plain pass is used (read_splat_forward_cells falls back anyway)
 
     def __init__(self, xyz, device=None, cells=True):
-        """cells: True = build the cell-ordered copy here (host, multi-threaded); False = plain path only; a uint8
+        """cells: True = build the cell-ordered copy here (on the device, from self.xyz); False = plain path only; a uint8
         CUDA tensor = a blob built elsewhere (e.g. by rank 0 and broadcast over RCCL, read_amd/sweep.py)."""
         self.device = device if device is not None else _lib.require_gpu()
         xyz = torch.as_tensor(np.ascontiguousarray(xyz, dtype=np.float32) if not torch.is_tensor(xyz) else xyz)
@@ -34,14 +34,14 @@ class PointCloudRasterizer:
         self.n = int(self.xyz.shape[0])
         self._workspaces = {}
         self._ws = None
-        # cell-ordered copy (Morton-sorted chunks of 1024 points + bounding boxes), built once on the host
+        # cell-ordered copy (Morton-sorted chunks of 1024 points + bounding boxes), built once per cloud on the device
         self.cells = None
         if torch.is_tensor(cells):
             if cells.dtype != torch.uint8 or cells.numel() != _lib.lib().read_splat_cells_bytes(self.n):
                 raise ValueError("cells blob does not belong to a cloud of this size")
             self.cells = cells.to(self.device)
         elif cells and self.n >= self.CELLS_MIN_POINTS:
-            self.cells = torch.from_numpy(build_cells(xyz.detach().cpu().numpy())).to(self.device)
+            self.cells = build_cells_device(self.xyz)
         if self.cells is not None:           # a fresh blob at an address the allocator may have handed out before
             _lib.check(_lib.lib().read_splat_cells_invalidate(self.cells.data_ptr(), self.n), "read_splat_cells_invalidate")
 
@@ -173,6 +173,26 @@ def build_cells(xyz):
     blob = np.empty(nbytes, np.uint8)
     _lib.check(L.read_splat_cells_build_host(xyz.ctypes.data, xyz.shape[0], blob.ctypes.data, nbytes),
                "read_splat_cells_build_host")
+    return blob
+
+
+def build_cells_device(xyz):
+    """Device blob of ``read_splat_cells_build`` for an (N,3) float32 CUDA tensor: a uint8 CUDA tensor, byte for byte the blob of
+    ``build_cells`` (up to the sign of a zero in a box bound).  Its scratch comes from the torch allocator; the call waits for
+    the build on the current stream (it reports a non-finite point as the host builder does)."""
+    if not (torch.is_tensor(xyz) and xyz.is_cuda) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError("build_cells_device takes an (N,3) CUDA tensor")
+    xyz = xyz.detach().to(torch.float32).contiguous()
+    n = int(xyz.shape[0])
+    L = _lib.lib()
+    nbytes, sbytes = L.read_splat_cells_bytes(n), L.read_splat_cells_build_scratch_bytes(n)
+    if nbytes == 0 or sbytes == 0:
+        raise ValueError(f"cannot build cells for {n} points")
+    with torch.cuda.device(xyz.device):
+        blob = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device)
+        scratch = torch.empty(sbytes, dtype=torch.uint8, device=xyz.device)
+        _lib.check(L.read_splat_cells_build(xyz.data_ptr(), n, blob.data_ptr(), nbytes, scratch.data_ptr(), sbytes,
+                                            _lib.stream_ptr()), "read_splat_cells_build")
     return blob
 
 
