@@ -133,7 +133,8 @@ int read_splat_forward(const float *xyz, int64_t n, const float *M_host, int B, 
 int read_splat_hint_next_camera(void *workspace, const float *M_next_host);
 /* Per-kernel durations (ms) of the LAST cell-path frame, HIP events on the launch stream around every launch; needs
  * read_tuning_set("splat_prof", 1) before the frame.  ms5[0] seeds + classification (0 when the previous frame's resolve launch did
- * that work), [1] pass A, [2] bin merge + bounds, [3] pass B, [4] resolve (+ the next frame's seeds / classification).  Synchronises. */
+ * that work), [1] pass A, [2] bin merge + bounds, [3] pass B (+ the object launches of read_splat_forward_objects), [4] resolve (+ the
+ * next frame's seeds / classification).  Synchronises. */
 int read_splat_profile_last(float *ms5);
 size_t read_splat_cells_bytes(int64_t n);
 int read_splat_cells_build_host(const float *xyz_host, int64_t n, void *cells_host, size_t cells_bytes);
@@ -154,6 +155,35 @@ int read_splat_cells_invalidate(const void *cells, int64_t n);
 int read_splat_forward_cells(const float *xyz, void *cells, int64_t n, const float *M_host, int B, int W, int H,
                              int levels, int32_t *const *idx_levels, float *const *depth_levels,
                              void *workspace, size_t workspace_bytes, void *stream);
+
+/* Scene editing (csrc/splat.hip, splat_objects_kernel).  A scene = a static part (label 0) plus objects k = 0..count-1, each with its
+ * own matrix M_k = M_0 @ P_k (P_k maps the object's points, in the cloud's coordinates, to their new place; computed on the host).
+ * Every visible point is projected with its label's matrix by the arithmetic of every pass; per pixel the minimum (depth, ORIGINAL
+ * id) wins, empty pixels are (0, 0.0f), levels are formed as in read_splat_forward.  Index images carry the original ids.
+ *
+ * read_splat_cells_build_ids: read_splat_cells_build of the static part's own xyz (n points, gathered), whose records carry
+ *   ids[i] (device, n entries: the original ids) instead of i.  Same blob otherwise, same scratch, same checks. */
+int read_splat_cells_build_ids(const float *xyz_dev, const int32_t *ids_dev, int64_t n, void *cells_dev, size_t cells_bytes,
+                               void *scratch_dev, size_t scratch_bytes, void *stream);
+typedef struct read_splat_objects {
+    const float *xyz;              /* device, n x 3: every object's points, object after object */
+    const int32_t *ids;            /* device, n: their original ids */
+    int64_t n;
+    int count;
+    const int64_t *begin;          /* host, count + 1: object k = points [begin[k], begin[k+1]); begin[0] = 0, begin[count] = n */
+    const float *M;                /* host, count x 16 row-major: M_k */
+    const unsigned char *visible;  /* host, count entries (0 = hidden, not launched), or NULL = all visible */
+} read_splat_objects;
+/* One camera M_host (= M_0, 16 floats on the host) over the static part (xyz_static / ids_static, n_static points, device; cells =
+ * its blob from read_splat_cells_build_ids or NULL) and the objects.  With cells, n_static >= 2^20 and W % 16 == 0 the static part
+ * takes the cell path (read_splat_hint_next_camera applies to it) and the objects join the key image after its pass B; otherwise
+ * the static part is one more object range with M_0.  Stream-ordered, allocates nothing, no synchronisation; workspace of
+ * read_splat_workspace_bytes(1, W, H).  READ_EINVAL before any device work for null pointers, objs->begin not starting at 0 or
+ * not monotone, begin[count] != n, and W or H not a multiple of 2^(levels-1). */
+int read_splat_forward_objects(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
+                               const float *M_host, int W, int H, int levels, const read_splat_objects *objs,
+                               int32_t *const *idx_levels, float *const *depth_levels, void *workspace, size_t workspace_bytes,
+                               void *stream);
 
 /* Measurement aid for bench.py (roofline.mfma_sustained): one workgroup of four waves per CU, every wave `iters` rounds of 16 independent
  * v_mfma_f32_16x16x4_f32 and nothing else.  scratch: >= 256 floats per CU on the device (never written); *flops receives the number of

@@ -59,6 +59,12 @@ class SplatGlOpts(C.Structure):
                 ("point_sizes", C.c_void_p)]
 
 
+class SplatObjects(C.Structure):
+    """read_splat_objects (include/read_hip.h): the object ranges of one read_splat_forward_objects call."""
+    _fields_ = [("xyz", C.c_void_p), ("ids", C.c_void_p), ("n", C.c_int64), ("count", C.c_int), ("begin", C.c_void_p),
+                ("M", C.c_void_p), ("visible", C.c_void_p)]
+
+
 _vp, _i, _i64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
 _pp = C.POINTER(C.c_void_p)
 
@@ -88,6 +94,8 @@ SIGNATURES = {
     "read_splat_cells_build_scratch_bytes": (_sz, [_i64]),
     "read_splat_cells_build": (_i, [_vp, _i64, _vp, _sz, _vp, _sz, _vp]),
     "read_splat_cells_invalidate": (_i, [_vp, _i64]),
+    "read_splat_cells_build_ids": (_i, [_vp, _vp, _i64, _vp, _sz, _vp, _sz, _vp]),
+    "read_splat_forward_objects": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_forward_cells": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _i, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_hint_next_camera": (_i, [_vp, C.POINTER(_f)]),
     "read_splat_profile_last": (_i, [C.POINTER(_f)]),

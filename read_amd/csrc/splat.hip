@@ -1253,6 +1253,40 @@ __global__ __launch_bounds__(256) void splat_project_gl_kernel(const float *__re
     }
 }
 
+// ---- scene editing: object points drawn with their own matrices (read_splat_forward_objects) --------------------------------
+// A scene = a static part (label 0) and objects k >= 1, each a contiguous range of one compacted array of points with the points'
+// ORIGINAL ids and its own matrix M_k = M_0 @ P_k (computed on the host).  After the static part's passes, every visible object's
+// points are projected with project_one under M_k and folded into the frame's level-0 key image as (depth bits << 32 | original
+// id) — the same keys, the same min; the resolve then forms the levels as for any frame.  Up to OBJ_MAX ranges per launch, their
+// matrices in the kernel arguments; workgroup b works on the range whose first workgroup (a host prefix of block counts) is the
+// last one <= b — a scalar scan of <= OBJ_MAX entries per workgroup, no search per point.
+constexpr int OBJ_MAX = 32;
+struct ObjBatch {
+    float m[OBJ_MAX][16];
+    long long first[OBJ_MAX], last[OBJ_MAX];        // range k = points [first, last) of the compacted arrays
+    int block0[OBJ_MAX + 1];                        // first workgroup of range k; block0[count] = the grid
+    int count;
+};
+
+__global__ __launch_bounds__(256) void splat_objects_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
+                                                            ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys,
+                                                            KeySlots ks)
+{
+    const int b = (int)blockIdx.x;
+    int j = 0;
+    for (int k = 1; k < ob.count; ++k)
+        if (b >= ob.block0[k]) j = k;
+    const long long i = ob.first[j] + (long long)(b - ob.block0[j]) * 256 + threadIdx.x;
+    if (i >= ob.last[j]) return;
+    float d;
+    int xx, yy;
+    const int pix = project_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], W, H, d, xx, yy);
+    if (pix < 0) return;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)ids[i];
+    unsigned long long *k = keys + key_slot(ks, (unsigned)pix);
+    if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
+}
+
 struct ResolveOut {
     int32_t *idx[READ_MAX_LEVELS];
     float *depth[READ_MAX_LEVELS];
@@ -1665,6 +1699,60 @@ StripInfo make_strips(int W)
     return si;
 }
 
+// ---- scene editing: the object launches of a frame ------------------------------------------------------------------------
+struct ObjectsDraw {
+    const float *xyz;                 // device: every object's points, object after object
+    const int32_t *ids;               // device: their original ids
+    const int64_t *begin;             // host, count + 1
+    const float *M;                   // host, count x 16
+    const unsigned char *visible;     // host, count, or NULL (all visible)
+    int count;
+    const float *xyz0;                // the static part as one more range (route without cells); n0 = 0: none
+    const int32_t *ids0;
+    int64_t n0;
+    const float *M0;
+};
+
+int objects_flush(ObjBatch &ob, int &blocks, const float *xyz, const int32_t *ids, int W, int H, unsigned long long *keys,
+                  KeySlots ks, hipStream_t stream)
+{
+    if (ob.count == 0) return READ_OK;
+    ob.block0[ob.count] = blocks;
+    hipLaunchKernelGGL(splat_objects_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys, ks);
+    READ_CHECK_LAUNCH();
+    ob.count = 0;
+    blocks = 0;
+    return READ_OK;
+}
+
+void objects_add(ObjBatch &ob, int &blocks, int64_t first, int64_t last, const float *M)
+{
+    const int k = ob.count++;
+    memcpy(ob.m[k], M, sizeof(ob.m[k]));
+    ob.first[k] = first;
+    ob.last[k] = last;
+    ob.block0[k] = blocks;
+    blocks += (int)ceil_div64(last - first, 256);
+}
+
+// Every visible, non-empty range of `od` into the key image: stream-ordered, OBJ_MAX ranges per launch, no synchronisation.
+int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, KeySlots ks, hipStream_t stream)
+{
+    ObjBatch ob;
+    memset(&ob, 0, sizeof(ob));
+    int blocks = 0, rc;
+    if (od.n0 > 0) {
+        objects_add(ob, blocks, 0, od.n0, od.M0);
+        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, ks, stream)) != READ_OK) return rc;
+    }
+    for (int k = 0; k < od.count; ++k) {
+        if ((od.visible && !od.visible[k]) || od.begin[k + 1] == od.begin[k]) continue;     // hidden or empty: not launched
+        objects_add(ob, blocks, od.begin[k], od.begin[k + 1], od.M + 16 * (size_t)k);
+        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream)) != READ_OK) return rc;
+    }
+    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream);
+}
+
 // ---- per-kernel durations of the LAST cell-path frame (read_tuning_set("splat_prof", 1) + read_splat_profile_last): HIP events
 // on the launch stream around every launch of the frame.  Slots: 0 seeds + classification (0 when the previous frame's resolve
 // launch did that work), 1 pass A, 2 bin merge + bounds, 3 pass B, 4 resolve (+ the next frame's seeds / classification).
@@ -1683,7 +1771,7 @@ int prof_mark(int i, hipStream_t stream)
 }
 
 int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int levels, int32_t *const *idx_levels,
-                float *const *depth_levels, const WsLayout &ws, hipStream_t stream, int b0 = 0)
+                float *const *depth_levels, const WsLayout &ws, hipStream_t stream, int b0 = 0, const ObjectsDraw *objs = nullptr)
 {
     const StripInfo si = make_strips(W);
     Cam1 cam;
@@ -1762,6 +1850,12 @@ int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int leve
     hipLaunchKernelGGL(pass_b, dim3((unsigned)(device_cus() * (g_splat_wgs_b > 0 ? g_splat_wgs_b : g_splat_wgs))), dim3(256), 0, stream, cc, cam, W, H, ws.keys, ws.zimg[fp],
                        (const unsigned short *)ws.hiz, ws.nbx, ws.hdr, next_pos, fp, si, items, stats, ks, bi);
     READ_CHECK_LAUNCH();
+    // ---- scene editing: the objects join the key image before the resolve (profile slot 3 includes them).  The bound image
+    // stays the static part's: an upper bound of the static depths, so also of the merged ones
+    if (objs) {
+        const int rc = objects_launch(*objs, W, H, ws.keys, ks, stream);
+        if (rc != READ_OK) return rc;
+    }
     // ---- resolve; with an announced next camera the same launch prepares the next frame's set
     const bool ahead = h.hinted && g_splat_ahead;
     h.hinted = false;
@@ -2454,7 +2548,8 @@ __global__ __launch_bounds__(CB_THREADS) void cells_records_kernel(const unsigne
                                                                    const float *__restrict__ xyz, long long n,
                                                                    float4 *__restrict__ rec, float4 *__restrict__ aabb,
                                                                    unsigned char *__restrict__ sticky, unsigned sticky_bytes,
-                                                                   const CellBuildParams *__restrict__ prm)
+                                                                   const CellBuildParams *__restrict__ prm,
+                                                                   const int32_t *__restrict__ ids)
 {
     if (prm->bad >= 0) return;
     const unsigned c = blockIdx.x;
@@ -2466,7 +2561,8 @@ __global__ __launch_bounds__(CB_THREADS) void cells_records_kernel(const unsigne
         const uint32_t id = (uint32_t)sorted[i < (size_t)n ? i : (size_t)n - 1];      // tail: copies of the last point
         const size_t src = 3 * (size_t)(id < (unsigned long long)n ? id : 0u);         // (a guard: ids are < n)
         const float p[3] = {xyz[src], xyz[src + 1], xyz[src + 2]};
-        rec[i] = make_float4(p[0], p[1], p[2], __uint_as_float(id));
+        // id-mapped build (read_splat_cells_build_ids): the record carries the caller's id of the point, keys follow it
+        rec[i] = make_float4(p[0], p[1], p[2], __uint_as_float(ids ? (uint32_t)ids[src / 3] : id));
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             lo[k] = p[k] < lo[k] ? p[k] : lo[k];
@@ -2491,19 +2587,20 @@ extern "C" size_t read_splat_cells_build_scratch_bytes(int64_t n)
     return cell_build_layout(n).total;
 }
 
+namespace {
 // Device-side build: read_splat_cells_build_host's blob from a cloud in HBM, stream-ordered, in the caller's scratch.  One
-// device -> host read of the non-finite index and one synchronisation at the end.
-extern "C" int read_splat_cells_build(const float *xyz, int64_t n, void *cells, size_t cells_bytes, void *scratch,
-                                      size_t scratch_bytes, void *stream)
+// device -> host read of the non-finite index and one synchronisation at the end.  ids (device, n entries) or NULL: what the
+// records carry as the point's id (NULL: its index in xyz).
+int cells_build(const float *xyz, const int32_t *ids, int64_t n, void *cells, size_t cells_bytes, void *scratch,
+                size_t scratch_bytes, void *stream, const char *fn)
 {
-    READ_CHECK_ARG(xyz && cells && scratch, "read_splat_cells_build: null pointer");
-    READ_CHECK_ARG(n >= 1 && n <= 0xFFFFFFFEll, "read_splat_cells_build: n out of range");
+    READ_CHECK_ARG(n >= 1 && n <= 0xFFFFFFFEll, "%s: n out of range", fn);
     const CellOffsets o = cell_offsets(n);
-    READ_CHECK_ARG(cells_bytes >= o.total, "read_splat_cells_build: buffer %zu < %zu bytes", cells_bytes, o.total);
+    READ_CHECK_ARG(cells_bytes >= o.total, "%s: buffer %zu < %zu bytes", fn, cells_bytes, o.total);
     const CellBuildLayout s = cell_build_layout(n);
-    READ_CHECK_ARG(scratch_bytes >= s.total, "read_splat_cells_build: scratch %zu < %zu bytes", scratch_bytes, s.total);
+    READ_CHECK_ARG(scratch_bytes >= s.total, "%s: scratch %zu < %zu bytes", fn, scratch_bytes, s.total);
     READ_CHECK_ARG((uintptr_t)cells % 256 == 0 && (uintptr_t)scratch % 256 == 0 && (uintptr_t)xyz % 4 == 0,
-                   "read_splat_cells_build: cells and scratch must be 256-byte aligned");
+                   "%s: cells and scratch must be 256-byte aligned", fn);
     {
         std::lock_guard<std::mutex> lock(g_ws_mutex);             // as read_splat_cells_invalidate: the blob is rewritten in place
         g_cells_frames.erase((const char *)cells + o.pts);
@@ -2539,13 +2636,28 @@ extern "C" int read_splat_cells_build(const float *xyz, int64_t n, void *cells, 
     static_assert(CB_PASSES % 2 == 0, "the sorted keys must end in the scratch, not in the record region they are gathered into");
     hipLaunchKernelGGL(cells_records_kernel, dim3(nc), dim3(CB_THREADS), 0, st, key_buf[0], xyz, (long long)n,
                        (float4 *)(blob + o.pts), (float4 *)(blob + o.aabb), (unsigned char *)(blob + o.sticky),
-                       (unsigned)(o.total - o.sticky), prm);
+                       (unsigned)(o.total - o.sticky), prm, ids);
     READ_CHECK_LAUNCH();
     long long bad = -1;
     READ_CHECK_HIP(hipMemcpyAsync(&bad, &prm->bad, sizeof(bad), hipMemcpyDeviceToHost, st));
     READ_CHECK_HIP(hipStreamSynchronize(st));
-    READ_CHECK_ARG(bad < 0, "read_splat_cells_build: point %lld is not finite", bad);
+    READ_CHECK_ARG(bad < 0, "%s: point %lld is not finite", fn, bad);
     return READ_OK;
+}
+}  // namespace
+
+extern "C" int read_splat_cells_build(const float *xyz, int64_t n, void *cells, size_t cells_bytes, void *scratch,
+                                      size_t scratch_bytes, void *stream)
+{
+    READ_CHECK_ARG(xyz && cells && scratch, "read_splat_cells_build: null pointer");
+    return cells_build(xyz, nullptr, n, cells, cells_bytes, scratch, scratch_bytes, stream, "read_splat_cells_build");
+}
+
+extern "C" int read_splat_cells_build_ids(const float *xyz, const int32_t *ids, int64_t n, void *cells, size_t cells_bytes,
+                                          void *scratch, size_t scratch_bytes, void *stream)
+{
+    READ_CHECK_ARG(xyz && ids && cells && scratch, "read_splat_cells_build_ids: null pointer");
+    return cells_build(xyz, ids, n, cells, cells_bytes, scratch, scratch_bytes, stream, "read_splat_cells_build_ids");
 }
 
 extern "C" int read_splat_profile_last(float *ms5)
@@ -2623,6 +2735,86 @@ extern "C" int read_splat_forward_cells(const float *xyz, void *cells, int64_t n
         if (rc != READ_OK) return rc;
     }
     return READ_OK;
+}
+
+// Scene editing: the static part (label 0, its original ids; through its id-mapped cell blob when the cell path serves it) and
+// the objects of `objs`, one camera.  Every check precedes the first launch.
+extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
+                                          const float *M_host, int W, int H, int levels, const read_splat_objects *objs,
+                                          int32_t *const *idx_levels, float *const *depth_levels, void *ws, size_t ws_bytes,
+                                          void *stream)
+{
+    READ_CHECK_ARG(M_host && objs && ws, "read_splat_forward_objects: null pointer (M_host, objs or workspace)");
+    READ_CHECK_ARG(idx_levels || depth_levels, "read_splat_forward_objects: no outputs requested");
+    READ_CHECK_ARG(n_static >= 0 && n_static <= 0xFFFFFFFEll, "read_splat_forward_objects: n_static out of range");
+    READ_CHECK_ARG(n_static == 0 || (xyz_static && ids_static), "read_splat_forward_objects: null pointer (static xyz or ids)");
+    READ_CHECK_ARG(objs->count >= 0 && objs->n >= 0 && objs->n <= 0xFFFFFFFEll,
+                   "read_splat_forward_objects: objs->count / objs->n out of range");
+    READ_CHECK_ARG(objs->count == 0 || (objs->begin && objs->M), "read_splat_forward_objects: null pointer (objs->begin or objs->M)");
+    READ_CHECK_ARG(objs->n == 0 || (objs->xyz && objs->ids), "read_splat_forward_objects: null pointer (objs->xyz or objs->ids)");
+    if (objs->count > 0) {
+        READ_CHECK_ARG(objs->begin[0] == 0, "read_splat_forward_objects: objs->begin[0] = %lld, not 0", (long long)objs->begin[0]);
+        for (int k = 0; k < objs->count; ++k)
+            READ_CHECK_ARG(objs->begin[k] <= objs->begin[k + 1], "read_splat_forward_objects: objs->begin is not monotone at %d", k);
+        READ_CHECK_ARG(objs->begin[objs->count] == objs->n, "read_splat_forward_objects: objs->begin[count] = %lld != objs->n = %lld",
+                       (long long)objs->begin[objs->count], (long long)objs->n);
+    } else
+        READ_CHECK_ARG(objs->n == 0, "read_splat_forward_objects: objs->begin[count] = 0 != objs->n = %lld", (long long)objs->n);
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "read_splat_forward_objects: levels must be 1..%d", READ_MAX_LEVELS);
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_forward_objects: bad size (%d,%d)", W, H);
+    const int mask = (1 << (levels - 1)) - 1;
+    READ_CHECK_ARG(((W | H) & mask) == 0, "read_splat_forward_objects: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", W, H,
+                   mask + 1);
+    READ_CHECK_ARG((uintptr_t)ws % 256 == 0 && (uintptr_t)cells % 256 == 0,
+                   "read_splat_forward_objects: workspace and cells must be 256-byte aligned");
+    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
+        set_error("read_splat_forward_objects: workspace %zu < %zu bytes", ws_bytes, read_splat_workspace_bytes(1, W, H));
+        return READ_ENOMEM;
+    }
+    ObjectsDraw od;
+    od.xyz = objs->xyz;
+    od.ids = objs->ids;
+    od.begin = objs->begin;
+    od.M = objs->M;
+    od.visible = objs->visible;
+    od.count = objs->count;
+    od.xyz0 = xyz_static;
+    od.ids0 = ids_static;
+    od.n0 = 0;
+    od.M0 = M_host;
+    const WsLayout L = ws_layout(ws, 1, W, H);
+    hipStream_t s = as_stream(stream);
+    if (cells && g_splat_cells && g_splat_mode == MODE_HIZ && n_static >= (1 << 20) && (W & 15) == 0) {
+        // the cell path for the static part (its blob from read_splat_cells_build_ids), the objects after its pass B
+        const CellOffsets o = cell_offsets(n_static);
+        CellCloud cc;
+        cc.hdr = (const CellHeader *)cells;
+        cc.pts = (const float4 *)((const char *)cells + o.pts);
+        cc.aabb = (const float *)((const char *)cells + o.aabb);
+        cc.list_a = (int *)((char *)cells + o.list_a);
+        cc.list_b = (CellEntryB *)((char *)cells + o.list_b);
+        cc.sticky = (unsigned char *)cells + o.sticky;
+        cc.nchunks = (int)cells_chunks(n_static);
+        cc.hdr_n = n_static;
+        cc.sticky_frames = g_splat_sticky;
+        cc.mark_candidates = g_splat_mark && g_splat_sticky > 0;
+        return cells_frame(cc, M_host, W, H, levels, idx_levels, depth_levels, L, s, 0, &od);
+    }
+    // Otherwise the static part is one more range of splat_objects_kernel with M_0 and its explicit ids (never the plain pass,
+    // whose keys and warm start carry implicit ids), and the resolve keeps no seeds
+    {
+        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
+        auto it = g_ws_host.find(ws);
+        if (it != g_ws_host.end()) {
+            it->second.hinted = false;
+            const int rc = ws_drop_prediction(it->second, s);
+            if (rc != READ_OK) return rc;
+        }
+    }
+    od.n0 = n_static;
+    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s);
+    if (rc != READ_OK) return rc;
+    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
 }
 
 extern "C" int read_splat_forward_gl(const float *xyz, int64_t n, const float *M_host, int W, int H,

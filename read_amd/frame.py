@@ -19,7 +19,7 @@ LEVELS = 5          # the reference rasterises and gathers 5 scales; the UNet co
 
 class FrameRenderer:
     def __init__(self, xyz, texture_cn, unet_state, W, H, proj_matrix=None, device=None, levels=LEVELS, cells=True,
-                 frames_in_flight=1):
+                 frames_in_flight=1, object_labels=None):
         """xyz (N,3); texture_cn (C,N) descriptors (PointTexture.texture_[0]); unet_state: state dict (tensors or
         ndarrays) under the reference's names, or an already packed fp32 blob (1-D tensor, e.g. received from rank 0);
         W,H multiples of 16; cells: see PointCloudRasterizer.
@@ -28,12 +28,16 @@ class FrameRenderer:
         call order (the rasteriser warm-starts from the previous call), and runs the UNet of call i on stream i mod F with its
         own plan and feature buffers — the launches of consecutive frames overlap, so the workgroups of one frame fill the
         CUs that the last, partly filled round of the other frame's layer leaves idle.  The returned tensor is then
-        complete on ``frame_done`` (an event; ``sync()`` waits for everything), not on the caller's stream."""
+        complete on ``frame_done`` (an event; ``sync()`` waits for everything), not on the caller's stream.
+
+        object_labels: one label per point for scene editing (PointCloudRasterizer): ``set_object_pose`` /
+        ``set_object_visible`` apply to the frames enqueued after the call, also with frames_in_flight > 1 (the matrices travel in
+        kernel arguments)."""
         self.device = device if device is not None else _lib.require_gpu()
         if W % 16 or H % 16:
             raise ValueError(f"set width {16 * (W // 16)} / height {16 * (H // 16)}")    # READ/gl/nn.py:107-109
         self.W, self.H, self.levels = W, H, levels
-        self.raster = PointCloudRasterizer(xyz, self.device, cells=cells)
+        self.raster = PointCloudRasterizer(xyz, self.device, cells=cells, labels=object_labels)
         if self.raster.n != int(torch.as_tensor(texture_cn).shape[-1]):
             raise ValueError(f"descriptor table has {int(torch.as_tensor(texture_cn).shape[-1])} columns for a cloud of "
                              f"{self.raster.n} points")
@@ -80,6 +84,12 @@ class FrameRenderer:
                         "stream": torch.cuda.Stream(self.device), "ready": torch.cuda.Event(), "done": torch.cuda.Event()}
                 slot["done"].record(torch.cuda.current_stream(self.device))
                 self._slots.append(slot)
+
+    def set_object_pose(self, k, P):
+        self.raster.set_object_pose(k, P)
+
+    def set_object_visible(self, k, flag):
+        self.raster.set_object_visible(k, flag)
 
     def rasterize(self, total_m, next_total=None):
         return self.raster.render(total_m, self.W, self.H, self.levels, out=(self.idx, self.depth), next_total=next_total)

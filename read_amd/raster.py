@@ -23,9 +23,14 @@ class PointCloudRasterizer:
 
     CELLS_MIN_POINTS = 1 << 20      # below this the plain pass is used (read_splat_forward_cells falls back anyway)
 
-    def __init__(self, xyz, device=None, cells=True):
+    def __init__(self, xyz, device=None, cells=True, labels=None):
         """cells: True = build the cell-ordered copy here (on the device, from self.xyz); False = plain path only; a uint8
-        CUDA tensor = a blob built elsewhere (e.g. by rank 0 and broadcast over RCCL, read_amd/sweep.py)."""
+        CUDA tensor = a blob built elsewhere (e.g. by rank 0 and broadcast over RCCL, read_amd/sweep.py).
+
+        labels: None, or one object label per point (ints in [0, MAX_LABEL]; 0 = the static scene) — scene editing: label k >= 1
+        is drawn with M_0 @ P_k (``set_object_pose``) and can be hidden (``set_object_visible``), see ``render``.  The cloud is
+        split once on the device: the static part gets its own id-mapped cell blob, the objects' points are compacted label
+        after label.  Index images keep the original ids.  New labels mean a new rasteriser; poses and visibility never do."""
         self.device = device if device is not None else _lib.require_gpu()
         xyz = torch.as_tensor(np.ascontiguousarray(xyz, dtype=np.float32) if not torch.is_tensor(xyz) else xyz)
         if xyz.dim() != 2 or xyz.shape[1] != 3:
@@ -34,6 +39,12 @@ class PointCloudRasterizer:
         self.n = int(self.xyz.shape[0])
         self._workspaces = {}
         self._ws = None
+        self.labels = None
+        if labels is not None:
+            if torch.is_tensor(cells):
+                raise ValueError("a cloud with object labels builds its own cell blob (the static part's)")
+            self._init_objects(labels, cells)
+            return
         # cell-ordered copy (Morton-sorted chunks of 1024 points + bounding boxes), built once per cloud on the device
         self.cells = None
         if torch.is_tensor(cells):
@@ -44,6 +55,65 @@ class PointCloudRasterizer:
             self.cells = build_cells_device(self.xyz)
         if self.cells is not None:           # a fresh blob at an address the allocator may have handed out before
             _lib.check(_lib.lib().read_splat_cells_invalidate(self.cells.data_ptr(), self.n), "read_splat_cells_invalidate")
+
+    def _init_objects(self, labels, cells):
+        lab = torch.as_tensor(labels)
+        if lab.dim() != 1 or lab.numel() != self.n:
+            raise ValueError(f"labels must hold one entry per point ({self.n}), got shape {tuple(lab.shape)}")
+        static_ids, obj_ids, begin = label_layout(lab.to(self.device))
+        self.labels = lab.to(self.device, torch.int32)
+        self.n_static, self.n_objects = int(static_ids.numel()), len(begin) - 1
+        self._static_ids = static_ids
+        self._static_xyz = self.xyz[static_ids.long()].contiguous()
+        self._obj_ids = obj_ids
+        self._obj_xyz = self.xyz[obj_ids.long()].contiguous()
+        self._begin = begin
+        self._poses = {}                                               # label -> 4x4 float32 (absent: identity)
+        self._visible = np.ones(self.n_objects, np.uint8)
+        self._obj_m = np.zeros((self.n_objects, 16), np.float32)       # M_k of the frame being enqueued (read during the call)
+        self.cells = None
+        if cells and self.n_static >= self.CELLS_MIN_POINTS:
+            self.cells = build_cells_device(self._static_xyz, ids=self._static_ids)
+            _lib.check(_lib.lib().read_splat_cells_invalidate(self.cells.data_ptr(), self.n_static), "read_splat_cells_invalidate")
+        self._objs = _lib.SplatObjects(self._obj_xyz.data_ptr() or None, self._obj_ids.data_ptr() or None, int(obj_ids.numel()),
+                                       self.n_objects, self._begin.ctypes.data, self._obj_m.ctypes.data,
+                                       self._visible.ctypes.data)
+
+    def _object_index(self, k):
+        if self.labels is None:
+            raise ValueError("this rasteriser was built without object labels")
+        k = int(k)
+        if not 1 <= k <= self.n_objects:
+            raise ValueError(f"no object {k}: labels 1..{self.n_objects} (0 is the static scene)")
+        return k - 1
+
+    def set_object_pose(self, k, P):
+        """P (4x4, None = identity) maps object k's points, in the cloud's coordinates, to their new place; applies from the next
+        frame enqueued (the matrices travel in kernel arguments)."""
+        i = self._object_index(k)
+        if P is None:
+            self._poses.pop(i + 1, None)
+        else:
+            P = np.array(P.detach().cpu().numpy() if torch.is_tensor(P) else P, dtype=np.float32).reshape(4, 4)
+            self._poses[i + 1] = P
+
+    def set_object_visible(self, k, flag):
+        self._visible[self._object_index(k)] = 1 if flag else 0
+
+    def object_matrices(self, total_m):
+        """The (K,16) float32 matrices M_k of the objects 1..K for the camera total_m (= M_0)."""
+        M0 = np.asarray(total_m, np.float32).reshape(4, 4)
+        out = np.empty((self.n_objects, 16), np.float32)
+        for i in range(self.n_objects):
+            out[i] = object_matrix(M0, self._poses.get(i + 1)).reshape(16)
+        return out
+
+    def _render_objects(self, M, W, H, levels, idx, dep, ws, stream):
+        self._obj_m[...] = self.object_matrices(M)
+        _lib.check(_lib.lib().read_splat_forward_objects(
+            self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
+            self.cells.data_ptr() if self.cells is not None else None, self.n_static, M.ctypes.data_as(C.POINTER(C.c_float)),
+            W, H, levels, C.byref(self._objs), idx, dep, ws.data_ptr(), ws.numel(), stream), "read_splat_forward_objects")
 
     def _workspace(self, B, W, H):
         """One persistent workspace per (min(B,8), W, H): key images, hi-z bounds and the previous frame's
@@ -67,6 +137,8 @@ class PointCloudRasterizer:
         M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m,
                                  dtype=np.float32).reshape(-1, 16)
         B = M.shape[0]
+        if self.labels is not None and B != 1:
+            raise ValueError("a cloud with object labels renders one camera per call")
         sizes = level_sizes(W, H, levels)
         if out is None:
             idx = [torch.empty((B, h, w), dtype=torch.int32, device=self.device) for (w, h) in sizes]
@@ -83,6 +155,9 @@ class PointCloudRasterizer:
                        "read_splat_hint_next_camera")
         idx_p = _lib.ptr_array([t.data_ptr() for t in idx])
         dep_p = _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
+        if self.labels is not None:
+            self._render_objects(M, W, H, levels, idx_p, dep_p, ws, _lib.stream_ptr())
+            return idx, dep
         _lib.check(L.read_splat_forward_cells(self.xyz.data_ptr(),
                                               self.cells.data_ptr() if self.cells is not None else None, self.n,
                                               M.ctypes.data_as(C.POINTER(C.c_float)), B, W, H, levels, idx_p, dep_p,
@@ -109,6 +184,9 @@ class PointCloudRasterizer:
             st = _lib.stream_ptr() if stream is None else stream
             if next_k is not None and cells_p is not None:
                 hint(ws_p, Mp[next_k])
+            if self.labels is not None:                     # scene editing: the objects' matrices of the current poses
+                self._render_objects(Ms[k], W, H, levels, idx_p, dep_p, ws, st)
+                return
             check(fwd(xyz_p, cells_p, n, Mp[k], 1, W, H, levels, idx_p, dep_p, ws_p, ws_n, st), "read_splat_forward_cells")
         call.keep = keep
         return call
@@ -120,6 +198,8 @@ class PointCloudRasterizer:
         tensor (set_point_discard), drop = (p, seed) seeded drop, perturb = (N,2) clip-space offsets
         (set_point_perturb), perturb_hash = (amp, seed), point_sizes = (N,) per-point sizes (set_point_sizes; they replace
         point_size as in the shader, programs.py:183-187).  -> (idx (1,H,W) int32, depth (1,H,W) fp32 | None)."""
+        if self.labels is not None:
+            raise NotImplementedError("render_gl (GL-twin point options) with object labels")
         M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m,
                                  dtype=np.float32).reshape(-1, 16)
         if M.shape[0] != 1:
@@ -176,14 +256,20 @@ def build_cells(xyz):
     return blob
 
 
-def build_cells_device(xyz):
+def build_cells_device(xyz, ids=None):
     """Device blob of ``read_splat_cells_build`` for an (N,3) float32 CUDA tensor: a uint8 CUDA tensor, byte for byte the blob of
     ``build_cells`` (up to the sign of a zero in a box bound).  Its scratch comes from the torch allocator; the call waits for
-    the build on the current stream (it reports a non-finite point as the host builder does)."""
+    the build on the current stream (it reports a non-finite point as the host builder does).
+    ids: None, or (N,) ids the records carry instead of the point's index (read_splat_cells_build_ids: a subset of a cloud keeps
+    its original ids)."""
     if not (torch.is_tensor(xyz) and xyz.is_cuda) or xyz.dim() != 2 or xyz.shape[1] != 3:
         raise ValueError("build_cells_device takes an (N,3) CUDA tensor")
     xyz = xyz.detach().to(torch.float32).contiguous()
     n = int(xyz.shape[0])
+    if ids is not None:
+        ids = torch.as_tensor(ids).to(xyz.device, torch.int32).contiguous()
+        if ids.numel() != n:
+            raise ValueError(f"ids has {ids.numel()} entries for {n} points")
     L = _lib.lib()
     nbytes, sbytes = L.read_splat_cells_bytes(n), L.read_splat_cells_build_scratch_bytes(n)
     if nbytes == 0 or sbytes == 0:
@@ -191,9 +277,57 @@ def build_cells_device(xyz):
     with torch.cuda.device(xyz.device):
         blob = torch.empty(nbytes, dtype=torch.uint8, device=xyz.device)
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=xyz.device)
-        _lib.check(L.read_splat_cells_build(xyz.data_ptr(), n, blob.data_ptr(), nbytes, scratch.data_ptr(), sbytes,
-                                            _lib.stream_ptr()), "read_splat_cells_build")
+        if ids is None:
+            _lib.check(L.read_splat_cells_build(xyz.data_ptr(), n, blob.data_ptr(), nbytes, scratch.data_ptr(), sbytes,
+                                                _lib.stream_ptr()), "read_splat_cells_build")
+        else:
+            _lib.check(L.read_splat_cells_build_ids(xyz.data_ptr(), ids.data_ptr(), n, blob.data_ptr(), nbytes, scratch.data_ptr(),
+                                                    sbytes, _lib.stream_ptr()), "read_splat_cells_build_ids")
     return blob
+
+
+# ---- scene editing: labels and poses ---------------------------------------------------------------------------------------
+MAX_LABEL = (1 << 16) - 1
+_EYE4 = np.eye(4, dtype=np.float32)
+
+
+def object_matrix(M0, P):
+    """M_k = M_0 @ P_k on the host in float32 — the one helper the product and the tests use.  P None or exactly the identity:
+    M_0 itself (not a product).  Otherwise the row-by-column sums in float32, left to right (j = 0..3), no fused operations."""
+    M0 = np.asarray(M0, np.float32).reshape(4, 4)
+    if P is None:
+        return M0
+    P = np.asarray(P, np.float32).reshape(4, 4)
+    if np.array_equal(P, _EYE4):
+        return M0
+    out = M0[:, 0:1] * P[0:1, :]
+    for j in range(1, 4):
+        out = out + M0[:, j:j + 1] * P[j:j + 1, :]
+    return out.astype(np.float32)
+
+
+def label_layout(labels):
+    """One label per point (0 = static; 1..K objects) -> (static_ids, object_ids, begin): int32 tensors on the labels' device
+    holding the original ids of the static points (ascending) and of the object points, label after label (ascending ids
+    within a label), and begin (host int64, K + 1 entries): object k = object_ids[begin[k-1]:begin[k]].  K = the largest
+    label; a label without points is an empty range."""
+    lab = torch.as_tensor(labels)
+    if lab.dim() != 1:
+        raise ValueError(f"labels must be 1-D, got shape {tuple(lab.shape)}")
+    if lab.dtype.is_floating_point or lab.dtype == torch.bool:
+        raise ValueError(f"labels must be integers, got {lab.dtype}")
+    lab = lab.to(torch.int64)
+    if lab.numel() and (int(lab.min()) < 0 or int(lab.max()) > MAX_LABEL):
+        raise ValueError(f"labels must lie in [0, {MAX_LABEL}]")
+    K = int(lab.max()) if lab.numel() else 0
+    static_ids = torch.nonzero(lab == 0).flatten().to(torch.int32)
+    oids = torch.nonzero(lab > 0).flatten()
+    order = torch.argsort(lab[oids], stable=True)
+    object_ids = oids[order].to(torch.int32)
+    counts = torch.bincount(lab, minlength=K + 1)[1:].cpu().numpy().astype(np.int64)
+    begin = np.zeros(K + 1, np.int64)
+    begin[1:] = np.cumsum(counts)
+    return static_ids, object_ids, begin
 
 
 def index_to_float(idx):

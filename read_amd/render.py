@@ -183,6 +183,9 @@ class Scene:
         self.point_sizes = None           # float (N,) set_point_sizes (programs.py:339-345)
         self.point_drop = None            # (p, seed): seeded drop evaluated on the device
         self.point_perturb_seeded = None  # (amp, seed)
+        self.object_labels = None         # scene editing (extension): int (N,) labels, 0 = static
+        self.object_poses = {}            # label -> 4x4
+        self.object_hidden = set()        # labels not drawn
         self.params = {'mode': (MODE_UV, UV_TYPE_1D), 'draw_points': True, 'flat_color': True, 'point_size': 1,
                        'splat_mode': False}
         if xyz is not None:
@@ -199,8 +202,47 @@ class Scene:
             raise NotImplementedError("uv1d other than the point index (import_model3d's arange) is not supported")
         self.xyz_min, self.xyz_max = self.xyz.min(axis=0), self.xyz.max(axis=0)          # programs.py:334-335
         self.point_discard = self.point_perturb = self.point_sizes = None
+        self.object_labels, self.object_poses, self.object_hidden = None, {}, set()
         self._dev = {}
         self._dirty = True
+
+    def set_object_labels(self, labels):
+        """Extension (not in NNScene): one object label per point (0 = the static scene, k >= 1 = object k), None = no objects.
+        Objects are moved by ``set_object_pose`` and hidden by ``set_object_visible`` without rebuilding anything; new labels
+        rebuild the rasteriser.  The point-id pyramid (OGL.infer's fast path, MultiscaleRender's id tokens) honours the edits;
+        every other token raises NotImplementedError while objects are set."""
+        if labels is not None:
+            labels = np.ascontiguousarray(labels).reshape(-1)
+            if self.xyz is None or labels.shape[0] != self.xyz.shape[0]:
+                raise ValueError(f"labels has {labels.shape[0]} entries for {0 if self.xyz is None else self.xyz.shape[0]} points")
+        self.object_labels = labels
+        self.object_poses, self.object_hidden = {}, set()
+        self._dirty = True
+
+    def set_object_pose(self, k, P):
+        """Extension: P (4x4, None = identity) maps object k's points, in the cloud's coordinates, to their new place; it is
+        applied before the model matrix (M_k = proj @ inv(view) @ model @ P)."""
+        self._require_objects()
+        if self._raster is not None and not self._dirty:
+            self._raster.set_object_pose(k, P)
+        if P is None:
+            self.object_poses.pop(int(k), None)
+        else:
+            self.object_poses[int(k)] = np.array(P, np.float32).reshape(4, 4)
+
+    def set_object_visible(self, k, flag):
+        """Extension: hide (False) or show object k."""
+        self._require_objects()
+        if self._raster is not None and not self._dirty:
+            self._raster.set_object_visible(k, flag)
+        (self.object_hidden.discard if flag else self.object_hidden.add)(int(k))
+
+    def _require_objects(self):
+        if self.object_labels is None:
+            raise ValueError("no object labels set (set_object_labels)")
+
+    def edited(self):
+        return self.object_labels is not None
 
     def set_point_sizes(self, point_sizes):
         """Per-point sizes (READ/gl/programs.py:339-345, scene yaml 'point_sizes'): from now on every token is drawn with the
@@ -283,7 +325,11 @@ class Scene:
         if self._raster is None or self._dirty:
             if self.xyz is None:
                 raise ValueError("scene has no point cloud (set_vertices)")
-            self._raster = PointCloudRasterizer(self.xyz)
+            self._raster = PointCloudRasterizer(self.xyz, labels=self.object_labels)
+            for k, P in self.object_poses.items():
+                self._raster.set_object_pose(k, P)
+            for k in self.object_hidden:
+                self._raster.set_object_visible(k, False)
             self._dirty = False
         return self._raster
 
@@ -321,8 +367,18 @@ class MultiscaleRender:
         scene = self.scene
         W, H = self.ss * self.viewport_size[0], self.ss * self.viewport_size[1]
         out = {}
-        if is_point_id_pyramid(input_format) and not scene.augmented() and W % (1 << (len(fmts) - 1)) == 0 \
-                and H % (1 << (len(fmts) - 1)) == 0:
+        pyramid = is_point_id_pyramid(input_format) and W % (1 << (len(fmts) - 1)) == 0 and H % (1 << (len(fmts) - 1)) == 0
+        if scene.edited() and scene.augmented():
+            raise NotImplementedError("scene objects (set_object_labels) with GL-twin augmentation (point sizes, discard, drop, "
+                                      "perturb)")
+        if scene.edited() and not pyramid:
+            bad = next((f for i, f in enumerate(fmts) if not is_point_id_pyramid(','.join(fmts[:i + 1]))), None)
+            if bad is None:
+                raise NotImplementedError(f"scene objects (set_object_labels) at {W}x{H}: the point-id pyramid needs sizes that "
+                                          f"are multiples of {1 << (len(fmts) - 1)}")
+            raise NotImplementedError(f"token {bad!r} with scene objects (set_object_labels): only the point-id pyramid "
+                                      "honours object poses and visibility")
+        if pyramid and not scene.augmented():
             # the layout of TexturePipeline: one pass over the cloud feeds every scale
             idx, _ = scene.rasterizer().render(scene.total_matrix(), W, H, len(fmts), want_depth=False)
             self.last_index = idx
