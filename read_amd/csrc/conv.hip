@@ -1959,6 +1959,9 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
 // relative rms error 0.9e-7 / 1.8e-7 / 3.1e-7 at K = 32 / 256 / 1024 against 1.1e-7 / 2.8e-7 / 5.9e-7 for the fp32 MFMA chain —
 // the split product is MORE accurate than the fp32 instruction it replaces, from |V| ~ 1e-4 up to the f16 overflow at |V| = 65504,
 // i.e. activations up to ~650 (B^T d B amplifies by at most 100); below ~1e-4 the absolute error floors at ~1e-11.
+// The weight pieces have the same kind of floor: Ul and 2^-11 Uh are f16 numbers with a fixed quantum of 2^-24 below 2^-14, so an entry
+// more than 2^14 below its row's largest keeps an absolute error of 2^-24 / s instead of 2^-22 of itself (tests/conv_ref64.py derives
+// both floors and holds every split-operand kernel to them against float64; measured: profiles/conv_accuracy_fp64.md).
 // The scaled low piece is what makes it two pieces instead of three (bf16 x 3: six MFMAs, 1.5x the weight bytes).
 //
 // Shape: the unit, grid walk, weight ownership (wave w = output channels 8w .. 8w+7, rows 0..7 conv_f, 8..15 conv_m) and the
@@ -5054,7 +5057,7 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream)
         // (the lean UNet blob) must never reach a kernel that reads wpacked as the direct order — a tuning knob changed on a
         // live engine, a 2 GiB tensor or an odd out_cstride can decline the Winograd kernels after the host has packed for them.
         // Checked HERE, for both entry points (read_gated_conv_forward and the UNet executor's direct call).
-        const int family = conv_uses_t3h(d) ? 8 : conv_uses_sc(d) ? 1 : conv_uses_pxh(d) ? 7 : (conv_uses_d3h(d) || conv_uses_d3h_s2(d)) ? 6 : conv_uses_w4h(d) ? 5 : conv_uses_w4(d) ? 4 : conv_uses_wino(d) ? 2 : 0;
+        const int family = conv_uses_sc(d) ? 1 : conv_uses_t3h(d) ? 8 : conv_uses_pxh(d) ? 7 : (conv_uses_d3h(d) || conv_uses_d3h_s2(d)) ? 6 : conv_uses_w4h(d) ? 5 : conv_uses_w4(d) ? 4 : conv_uses_wino(d) ? 2 : 0;
         const bool cfg_wino = d->config >= 0 && d->config < N_CONFIGS && g_configs[d->config].wino;   // forced F(2x2) configs read wpacked_wino
         const bool w16_forced = d->config == -3;
         READ_CHECK_ARG(d->wpacked || family != 0 || cfg_wino || w16_forced,
@@ -5634,8 +5637,8 @@ int conv_kc_for(const read_conv_desc *d)
 extern "C" int read_conv_kernel_family(const read_conv_desc *desc)
 {
     if (!desc) return -1;
+    if (readhip::conv_uses_sc(desc)) return 1;           // the order of the dispatch in launch_gated_conv: the small-Cout kernel first
     if (readhip::conv_uses_t3h(desc)) return 8;
-    if (readhip::conv_uses_sc(desc)) return 1;
     if (readhip::conv_uses_pxh(desc)) return 7;
     if (readhip::conv_uses_d3h(desc) || readhip::conv_uses_d3h_s2(desc)) return 6;
     if (readhip::conv_uses_w4h(desc)) return 5;

@@ -1,0 +1,335 @@
+"""CPU: the NumPy restatements of the split-operand convolution kernels (tests/d3h_ref.py, tests/wino4h_ref.py, with the library's own
+host packers) held to the float64 reference, the derived bounds and the measured caps of tests/conv_ref64.py — on unit-scale,
+checkpoint-like, structured and range-edge inputs — and the DETECTION POWER of those caps: the same arithmetic with one seeded defect
+each must exceed them.  The restatements sum in float64 where the device rounds per MFMA, so the intact models sit well inside the caps;
+what this module establishes is that the inputs are such that correct split arithmetic passes (floors included) and that broken split
+arithmetic does not.  The kernels themselves: tests/test_gpu_conv_accuracy.py."""
+import numpy as np
+import pytest
+
+from tests import conv_ref64 as R64
+from tests.d3h_ref import pack_d1h_blob, pack_d3h_blob, split_conv_model, split_conv_model_taps
+
+
+# ------------------------------------------------------------------------------------------ plumbing
+def im2col(x_chw, k, stride):
+    """-> (outH, outW, k k Cin), index tap * Cin + ci (the order of read_conv_pack_t3h_host), zero padding (k - 1) // 2."""
+    cin, H, W = x_chw.shape
+    pad = (k - 1) // 2
+    oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    xp = np.zeros((cin, H + 2 * pad + stride, W + 2 * pad + stride), np.float32)
+    xp[:, pad:pad + H, pad:pad + W] = x_chw
+    taps = [xp[:, ky:ky + stride * oh:stride, kx:kx + stride * ow:stride] for ky in range(k) for kx in range(k)]
+    return np.ascontiguousarray(np.concatenate(taps, 0).transpose(1, 2, 0))
+
+
+def w_matrix(w):
+    return np.ascontiguousarray(w.transpose(0, 2, 3, 1).reshape(w.shape[0], -1))
+
+
+def split_model(cols, w2, defect=None):
+    """tests/d3h_ref.split_conv_model_taps, copied so that ONE line at a time can be broken (defect = None: the same arithmetic)."""
+    cout, K = w2.shape
+    mx = np.abs(w2.astype(np.float64)).max(axis=1)
+    ex = np.zeros(cout, np.int64)
+    nz = mx > 0
+    ex[nz] = np.clip(15 - np.frexp(mx[nz])[1], -60, 60)
+    if defect == "scale_binade":
+        ex[nz] += 1                                              # the row's largest entry lands in [2^15, 2^16)
+    ws = np.ldexp(w2.astype(np.float64), ex[:, None])
+    with np.errstate(over="ignore", invalid="ignore"):
+        wh = ws.astype(np.float16)
+        r = ws - wh.astype(np.float64)
+        wl = r.astype(np.float16)
+        if defect == "wl_truncated":                             # toward zero instead of to nearest
+            over = np.abs(wl.astype(np.float64)) > np.abs(r)
+            wl = np.where(over, np.nextafter(wl, np.float16(0)), wl)
+        wl = wl.astype(np.float64)
+        whs = (wh * np.float16(2.0 ** -11)).astype(np.float16).astype(np.float64)
+        wh = wh.astype(np.float64)
+        xh = cols.astype(np.float16)
+        if defect == "xl_unscaled":                              # the low piece kept at its own scale: it underflows f16
+            xl = (cols - xh.astype(np.float32)).astype(np.float16).astype(np.float64)
+            whs = wh
+        else:
+            xl = ((cols - xh.astype(np.float32)) * np.float32(2048.0)).astype(np.float16).astype(np.float64)
+        xh = xh.astype(np.float64)
+        t_hl = xl @ whs.T if defect != "drop_wh_xl" else 0.0
+        t_lh = xh @ wl.T if defect != "drop_wl_xh" else 0.0
+        out = t_hl + t_lh + xh @ wh.T
+        return (out * np.ldexp(1.0, -ex)[None, None, :]).astype(np.float32)
+
+
+def run_direct(L, x, k, stride, family, model=split_model, defect=None, cls="a"):
+    """One layer's pre-activations [f | m] through a model -> dict of E, R, the worst err / derived bound, finiteness."""
+    ref = R64.reference(L, x, stride=stride)
+    cols = im2col(x, k, stride)
+    kw = {} if defect is None else {"defect": defect}
+    got = [(model(cols, w_matrix(L["w" + fm]), **kw) + L["b" + fm][None, None, :]).transpose(2, 0, 1) for fm in "fm"]
+    got = np.concatenate(got)
+    finite = bool(np.isfinite(got).all())
+    bound = np.concatenate([R64.preact_bound_direct(L, ref, family, fm) for fm in "fm"])
+    err = np.abs(np.nan_to_num(got.astype(np.float64), nan=1e300, posinf=1e300, neginf=-1e300) - np.concatenate([ref.f, ref.m]))
+    clean = np.nan_to_num(got, nan=3e38, posinf=3e38, neginf=-3e38)
+    e_max, e_rms = R64.measure_linear(clean, ref)
+    r_max, r_rms = R64.measure_linear(R64.oracle_fp32(L, x, stride=stride, linear=True), ref)
+    zero = np.concatenate([ref.Af, ref.Am]) == 0
+    return dict(E_max=e_max, E_rms=e_rms, R_max=r_max, R_rms=r_rms, q=float((err / bound).max()), finite=finite,
+                zero_exact=bool((got[zero] == 0).all()), cls=cls)
+
+
+def inside_caps(s, family):
+    """The two kinds of cap of tests/conv_ref64.py: the derived bound (q <= 1, hard) and the measured one against the oracle's own error
+    (only where the oracle has an error to compare with: R_max >= 1)."""
+    c = R64.measured_cap(family, "linear", s["cls"])
+    ok = s["finite"] and s["q"] <= 1.0 and s["zero_exact"]
+    if s["R_max"] >= 1.0:
+        ok = ok and s["E_rms"] <= c * s["R_rms"] and s["E_max"] <= c * s["R_max"]
+    return ok
+
+
+# the direct families at CPU-sized shapes: (family, cin, cout, k, stride, H, W)
+DIRECT = [("d3h", 64, 32, 3, 1, 9, 21), ("d3h_s2", 32, 32, 3, 2, 10, 14), ("d3h_s2", 32, 32, 4, 2, 10, 14), ("pxh", 96, 40, 1, 1, 7, 13),
+          ("t3h", 8, 32, 3, 1, 9, 21)]
+
+
+def direct_inputs(family, cin, cout, k, stride, H, W):
+    """(class, name, L, x) over classes (a) - (d) of tests/conv_ref64.py."""
+    rng = np.random.default_rng([cin, cout, k, 3])
+    tame = R64.tame_layer(cin, cout, k, 11)
+    yield "a", "unit scale", tame, rng.standard_normal((cin, H, W)).astype(np.float32)
+    Lb, xb = R64.checkpoint_like(cin, cout, k, H, W, 12)
+    yield "b", "checkpoint-like", Lb, xb
+    for amp in (1.0, 2.0 ** -10):
+        for (c, y, x_) in R64.impulse_positions(cin, H, W)[::5]:
+            yield "c", f"impulse {amp:g} at c{c} ({y},{x_})", tame, R64.impulse(cin, H, W, c, y, x_, amp)
+    yield "c", "constant", tame, R64.constant_image(cin, H, W)
+    yield "c", "checkerboard", tame, R64.checkerboard(cin, H, W)
+    for amp in (2.0 ** -14, 1e-6):
+        yield "d", f"small scale {amp:g}", tame, (rng.standard_normal((cin, H, W)) * amp).astype(np.float32)
+
+
+@pytest.mark.parametrize("shape", DIRECT, ids=lambda s: f"{s[0]}-k{s[3]}s{s[4]}")
+def test_direct_split_models_stay_inside_the_caps(shape):
+    """The intact three-piece-pair arithmetic on every class: finite, inside the derived bound |err| <= u (12 + 3 nb + 1) A + floors
+    (tests/conv_ref64.py; on the small-scale cases of class (d) the floors ARE the promise: ~1e-11 absolute per product, not fp32-relative
+    accuracy), inside the measured caps, exact zeros where A = 0."""
+    family = shape[0]
+    for cls, name, L, x in direct_inputs(*shape):
+        s = run_direct(L, x, shape[3], shape[4], family, model=split_conv_model_taps, cls=cls)
+        print("%-7s %s %-34s E_max %8.2f E_rms %7.3f  R_max %8.2f R_rms %7.3f  err/bound %.3f" % (family, cls, name, s["E_max"], s["E_rms"], s["R_max"], s["R_rms"], s["q"]))
+        assert inside_caps(s, family), (family, cls, name, s)
+    # the 3x3 restatement with its own padding and tap loop is the same arithmetic as the im2col form used here
+    if family == "d3h":
+        L, x = R64.checkpoint_like(shape[1], shape[2], 3, shape[5], shape[6], 12)
+        a = split_conv_model(np.ascontiguousarray(x.transpose(1, 2, 0)), L["wf"])
+        b = split_conv_model_taps(im2col(x, 3, 1), w_matrix(L["wf"]))
+        assert float(np.abs(a.astype(np.float64) - b).max()) <= 2 * R64.U * float(R64.reference(L, x).Af.max())
+
+
+# Which classes must catch which defect (direct arithmetic; "a" unit scale, "b" checkpoint-like, "c" impulses / constant /
+# checkerboard, "d" small scales):
+#   drop_wh_xl    the pair (2^-11 wh) xl is lost: up to 2^-11 |w x| per product wherever x is not an f16 number — (a) and (b).  The
+#                 impulses, the constant and the checkerboard of (c) ARE f16 numbers (xl = 0): (c) is blind to this one by construction.
+#   drop_wl_xh    the pair wl xh is lost: up to 2^-11 |w x| per product for every x: (a), (b), and every impulse of (c) (hundreds to
+#                 thousands of units at one pixel).
+#   xl_unscaled   x - xh underflows f16 (quantum 2^-24) instead of being carried at 2^11: an absolute 2^-25 per activation — (b) (the
+#                 channels whose scale is small: E_rms seven times the intact model's, over the measured cap) and (d) (over both).
+#   scale_binade  nothing is lost until an entry reaches 65520: the row of (b) whose largest weight is the fp32 number just below a power
+#                 of two rounds to 2^16 = Inf in f16: (b), non-finite.
+#   wl_truncated  |wh + wl - w s| grows from half an ulp of wl to a whole one: still within the 4 u per operand that the bound must allow
+#                 for round-to-nearest's worst case, so no sum can show it; it is caught where it lives, in the packer:
+#                 test_packers_on_edge_rows holds every stored wl to HALF an ulp of the exact residual, and
+#                 test_truncated_low_piece_breaks_the_packer_property shows truncated pieces breaking exactly that.
+EXPECT = {"drop_wh_xl": {"a", "b"}, "drop_wl_xh": {"a", "b", "c"}, "xl_unscaled": {"b", "d"}, "scale_binade": {"b"}}
+
+
+@pytest.mark.parametrize("defect", sorted(EXPECT))
+def test_seeded_defects_exceed_the_caps(defect):
+    shape = DIRECT[0]
+    caught = {}
+    for cls, name, L, x in direct_inputs(*shape):
+        s = run_direct(L, x, shape[3], shape[4], shape[0], defect=defect, cls=cls)
+        intact = run_direct(L, x, shape[3], shape[4], shape[0], cls=cls)
+        assert inside_caps(intact, shape[0]), (cls, name, intact)                # the copy without a defect is the real arithmetic
+        hit = not inside_caps(s, shape[0])
+        caught.setdefault(cls, []).append((name, hit))
+        print("%-13s %s %-34s E_max %10.2f E_rms %9.3f  R_max %8.2f R_rms %7.3f  err/bound %9.3f  %s" % (
+            defect, cls, name, s["E_max"], s["E_rms"], s["R_max"], s["R_rms"], s["q"], "CAUGHT" if hit else "-"))
+    for cls in EXPECT[defect]:
+        assert any(h for _, h in caught[cls]), f"{defect}: class ({cls}) did not catch it: {caught}"
+    if defect == "drop_wl_xh":
+        assert all(h for n, h in caught["c"] if n.startswith("impulse")), "every impulse must show a lost weight piece"
+
+
+def half_ulp_f16(v):
+    """Half the f16 spacing at |v| (2^-25 in the subnormal range)."""
+    e = np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** -14)))
+    return 2.0 ** (e - 11)
+
+
+def test_truncated_low_piece_breaks_the_packer_property():
+    """wl_truncated of EXPECT: round-to-nearest pieces satisfy |wh + wl - w s| <= half an ulp of wl; truncated ones do not."""
+    L, _ = R64.checkpoint_like(64, 32, 3, 4, 4, 21)
+    w2 = w_matrix(L["wf"]).astype(np.float64)
+    ex = np.round(np.log2(1.0 / R64.row_inv_scale(w2))).astype(np.int64)
+    ws = np.ldexp(w2, ex[:, None])
+    wh = ws.astype(np.float16).astype(np.float64)
+    r = ws - wh
+    rtn = r.astype(np.float16)
+    assert np.all(np.abs(rtn.astype(np.float64) - r) <= half_ulp_f16(r))
+    trunc = np.where(np.abs(rtn.astype(np.float64)) > np.abs(r), np.nextafter(rtn, np.float16(0)), rtn).astype(np.float64)
+    assert np.any(np.abs(trunc - r) > half_ulp_f16(r))
+
+
+# ------------------------------------------------------------------------------------------ the library's packers on the edge rows
+def _halfs(blob, n_inv):
+    return blob[:-n_inv].view(np.float16), blob[-n_inv:]
+
+
+def test_packers_on_edge_rows():
+    """read_conv_pack_dkh_host (3x3, 4x4, 1x1), read_conv_pack_t3h_host and read_conv_pack_w4h_host against the NumPy packers BIT FOR BIT
+    on checkpoint-like layers with the edge rows (all zeros, a single weight, largest |w| a power of two and the fp32 number just below
+    one, fp32 denormals, -0.0), and the properties the arithmetic rests on, from the library's own output: 1 / s as the rule says, every
+    piece finite, hi + lo within half an f16 ulp of the exact residual."""
+    from read_amd import _lib
+    from tests.wino4h_ref import pack_w4h_blob
+    L_ = _lib.lib()
+    for cin, cout in ((64, 40), (32, 32)):
+        L, _ = R64.checkpoint_like(cin, cout, 3, 4, 4, 31)
+        wf, wm = np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"])
+        cp = (cout + 31) // 32 * 32
+        # direct 3x3
+        got = np.zeros(L_.read_conv_dkh_floats(cin, cout, 3), np.float32)
+        assert L_.read_conv_pack_dkh_host(cin, cout, 3, wf.ctypes.data, wm.ctypes.data, got.ctypes.data) == 0
+        want = pack_d3h_blob(wf, wm)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "direct 3x3 packer != model packer on the edge rows"
+        h, inv = _halfs(got, 2 * cp)
+        assert np.isfinite(h.astype(np.float32)).all()
+        assert np.array_equal(inv[:cout], R64.row_inv_scale(wf).astype(np.float32)) and np.array_equal(inv[cp:cp + cout], R64.row_inv_scale(wm).astype(np.float32))
+        assert inv[0] == 1.0 and inv[4] == np.float32(2.0 ** -60)           # the all-zero row; the denormal row at the clamp (s = 2^60)
+        assert inv[2] == np.float32(2.0 ** -17) and inv[3] == np.float32(2.0 ** -18)   # 0.125 = 0.5 x 2^-2: ex = 17; the number just below it: ex = 18
+        # Winograd F(4x4)
+        got = np.zeros(L_.read_conv_w4h_floats(cin, cout), np.float32)
+        assert L_.read_conv_pack_w4h_host(cin, cout, wf.ctypes.data, wm.ctypes.data, got.ctypes.data) == 0
+        want = pack_w4h_blob(wf, wm)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), "Winograd packer != model packer on the edge rows"
+        h, inv = _halfs(got, 2 * cp)
+        assert np.isfinite(h.astype(np.float32)).all()
+        assert np.array_equal(inv[:cout], R64.wino_filter_inv_scale(wf).astype(np.float32))
+        # 1x1
+        w1f, w1m = np.ascontiguousarray(wf[:, :, 0, 0]), np.ascontiguousarray(wm[:, :, 0, 0])
+        got = np.zeros(L_.read_conv_dkh_floats(cin, cout, 1), np.float32)
+        assert L_.read_conv_pack_dkh_host(cin, cout, 1, w1f.ctypes.data, w1m.ctypes.data, got.ctypes.data) == 0
+        assert np.array_equal(got.view(np.uint32), pack_d1h_blob(w1f, w1m).view(np.uint32)), "1x1 packer != model packer on the edge rows"
+    L, _ = R64.checkpoint_like(32, 32, 4, 4, 4, 33)                          # the 4 x 4 / stride-2 operand: the piece property from the library's halfs
+    wf, wm = np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"])
+    got = np.zeros(L_.read_conv_dkh_floats(32, 32, 4), np.float32)
+    assert L_.read_conv_pack_dkh_host(32, 32, 4, wf.ctypes.data, wm.ctypes.data, got.ctypes.data) == 0
+    h, inv = _halfs(got, 64)
+    h = h.reshape(1, 2, 1, 16, 2, 2, 64, 8).astype(np.float64)               # [group][rh][chunk][tap][rb][piece][lane][e]
+    for rh in range(2):
+        for rb in range(2):
+            for i in range(16):
+                co, fm = 16 * rh + 8 * rb + (i & 7), i >> 3
+                w = (wm if fm else wf)[co].astype(np.float64)                # (cin, 4, 4)
+                s = 1.0 / float(inv[32 * fm + co])
+                for kq in range(4):
+                    ws = w[8 * kq:8 * kq + 8].reshape(8, 16).T * s            # (tap, e)
+                    hi, lo = h[0, rh, 0, :, rb, 0, i + 16 * kq], h[0, rh, 0, :, rb, 1, i + 16 * kq]
+                    assert np.all(np.abs(hi - ws) <= half_ulp_f16(ws)) and np.all(np.abs(hi + lo - ws) <= half_ulp_f16(ws - hi))
+    for cin, cout in ((8, 32), (32, 8)):                                      # the implicit-GEMM form of 3x3 weights
+        L, _ = R64.checkpoint_like(cin, cout, 3, 4, 4, 35)
+        wf, wm = np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"])
+        K = (9 * cin + 15) // 16 * 16
+        mat = lambda w: np.concatenate([w_matrix(w), np.zeros((cout, K - 9 * cin), np.float32)], 1)   # noqa: E731
+        got = np.zeros(L_.read_conv_t3h_floats(cin, cout), np.float32)
+        assert L_.read_conv_pack_t3h_host(cin, cout, wf.ctypes.data, wm.ctypes.data, got.ctypes.data) == 0
+        assert np.array_equal(got.view(np.uint32), pack_d1h_blob(mat(wf), mat(wm)).view(np.uint32)), "implicit-GEMM packer != model packer on the edge rows"
+
+
+# ------------------------------------------------------------------------------------------ Winograd
+def run_wino(L, x, halfs_edit=None, cls="a"):
+    """The lane-exact model of gated_conv_wino4h_kernel (tests/wino4h_ref.py) on the LIBRARY's packed operand -> statistics as run_direct;
+    E against the transformed-domain condition term A_w and (EA) against A: that number shows what Winograd costs."""
+    from read_amd import _lib
+    from tests.wino4h_ref import wino4h_conv_model
+    cout, cin = L["wf"].shape[:2]
+    cp = (cout + 31) // 32 * 32
+    wf, wm = np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"])
+    blob = np.zeros(_lib.lib().read_conv_w4h_floats(cin, cout), np.float32)
+    assert _lib.lib().read_conv_pack_w4h_host(cin, cout, wf.ctypes.data, wm.ctypes.data, blob.ctypes.data) == 0
+    halfs = blob[:-2 * cp].view(np.float16).reshape(cp // 32, 4, cin // 32, 36, 2, 64, 8).copy()
+    inv = blob[-2 * cp:].reshape(2, cp).copy()
+    if halfs_edit is not None:
+        halfs_edit(halfs, inv)
+    with np.errstate(over="ignore", invalid="ignore"):
+        f, m = wino4h_conv_model(np.ascontiguousarray(x.transpose(1, 2, 0)), halfs, inv, cin, cout)
+        got = np.concatenate([(f + L["bf"][None, None]).transpose(2, 0, 1), (m + L["bm"][None, None]).transpose(2, 0, 1)])
+    ref = R64.reference(L, x)
+    bf_, Awf = R64.preact_bound_wino(L, x, ref, "f")
+    bm_, Awm = R64.preact_bound_wino(L, x, ref, "m")
+    bound = np.concatenate([bf_, bm_])
+    truth = np.concatenate([ref.f, ref.m])
+    finite = bool(np.isfinite(got).all())
+    err = np.abs(np.nan_to_num(got.astype(np.float64), nan=1e300, posinf=1e300, neginf=-1e300) - truth)
+    Aw = np.concatenate([Awf + np.abs(L["bf"].astype(np.float64))[:, None, None], Awm + np.abs(L["bm"].astype(np.float64))[:, None, None]])
+    clean = np.nan_to_num(got, nan=3e38, posinf=3e38, neginf=-3e38)
+    e_max, e_rms = R64._stats(np.abs(clean.astype(np.float64) - truth), Aw)
+    ea_max, ea_rms = R64.measure_linear(clean, ref)
+    r_max, r_rms = R64.measure_linear(R64.oracle_fp32(L, x, linear=True), ref)
+    return dict(E_max=e_max, E_rms=e_rms, EA_max=ea_max, EA_rms=ea_rms, R_max=r_max, R_rms=r_rms, q=float((err / bound).max()), finite=finite,
+                zero_exact=bool((got[Aw == 0] == 0).all()), cls=cls)
+
+
+def wino_inside_caps(s):
+    c = R64.C_MEASURED["w4h"]["gated"][s["cls"]]            # (the device has no linear Winograd launch to measure)
+    ok = s["finite"] and s["q"] <= 1.0 and s["zero_exact"]
+    if s["R_max"] >= 1.0:                                        # the measured cap: E against A_w, as tests/test_gpu_conv_accuracy.py
+        ok = ok and s["E_rms"] <= c * s["R_rms"] and s["E_max"] <= c * s["R_max"]
+    return ok
+
+
+def wino_inputs(cin, cout, H, W):
+    rng = np.random.default_rng([cin, cout, 5])
+    tame = R64.tame_layer(cin, cout, 3, 41)
+    yield "a", "unit scale", tame, rng.standard_normal((cin, H, W)).astype(np.float32)
+    Lb, xb = R64.checkpoint_like(cin, cout, 3, H, W, 42)
+    yield "b", "checkpoint-like", Lb, xb
+    for amp, (c, y, x_) in ((1.0, (1, 3, 3)), (2.0 ** -10, (31, 5, 6)), (1.0, (2, H - 1, W - 1)), (2.0 ** -10, (0, 8, 8))):
+        yield "c", f"impulse {amp:g} at c{c} ({y},{x_})", tame, R64.impulse(cin, H, W, c, y, x_, amp)
+    yield "c", "constant", tame, R64.constant_image(cin, H, W)
+    yield "d", "range edge 650, rows (0, 0)", tame, R64.wino_range_edge(cin, H, W, rows=(0, 0))
+    yield "d", "range edge 650, rows (1, 5)", tame, R64.wino_range_edge(cin, H, W, rows=(1, 5))
+    yield "d", "small scale 2^-14", tame, (rng.standard_normal((cin, H, W)) * 2.0 ** -14).astype(np.float32)
+
+
+def test_winograd_split_model_stays_inside_the_caps_and_defects_do_not():
+    """The lane-exact Winograd model on classes (a) - (d) (one 8 x 32 unit and a partial one below it, 32 channels): inside the
+    transformed-domain bound of tests/conv_ref64.py (the model's input transform rounds once, the bound allows the kernel's four), finite
+    at the documented range edge (amplitude 650 on the pattern that attains |B^T d B| = 100 x), exact zeros.
+    Defects, on the operand the model consumes: the Ul pieces zeroed (= the pair Ul Vh dropped) — caught on (a), (b) and on every impulse;
+    the row scale one binade up — caught on (b) (the just-below-a-power-of-two row overflows f16)."""
+    cin, cout, H, W = 32, 32, 11, 13
+
+    def drop_ul(halfs, inv):
+        halfs[:, :, :, :, 1] = 0
+
+    def binade(halfs, inv):
+        with np.errstate(over="ignore"):
+            halfs *= np.float16(2.0)
+        inv *= 0.5
+
+    caught = {"drop_ul": {}, "binade": {}}
+    for cls, name, L, x in wino_inputs(cin, cout, H, W):
+        s = run_wino(L, x, cls=cls)
+        print("w4h     %s %-30s E(A_w) max %8.2f rms %7.3f  E(A) max %9.2f rms %8.3f  R_max %7.2f R_rms %6.3f  err/bound %.3f" % (
+            cls, name, s["E_max"], s["E_rms"], s["EA_max"], s["EA_rms"], s["R_max"], s["R_rms"], s["q"]))
+        assert wino_inside_caps(s), (cls, name, s)
+        if name in ("unit scale", "checkpoint-like") or name.startswith("impulse"):
+            for dname, edit in (("drop_ul", drop_ul), ("binade", binade)):
+                d = run_wino(L, x, halfs_edit=edit, cls=cls)
+                caught[dname].setdefault(cls, []).append(not wino_inside_caps(d))
+                print("   %-8s E(A) max %10.2f rms %9.3f  err/bound %9.3f finite %s" % (dname, d["EA_max"], d["EA_rms"], d["q"], d["finite"]))
+    assert any(caught["drop_ul"]["a"]) and any(caught["drop_ul"]["b"]) and all(caught["drop_ul"]["c"]), caught
+    assert any(caught["binade"]["b"]), caught

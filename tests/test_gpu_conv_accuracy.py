@@ -1,0 +1,336 @@
+"""GPU: every split-operand convolution kernel (gated_conv_wino4h_kernel, gated_conv_d3h_kernel, gated_conv_d3h_s2_kernel,
+gated_conv_pxh_kernel and its taps form) against a float64 reference, in units of fp32 round-off, on unit-scale, checkpoint-like,
+structured and range-edge inputs (tests/conv_ref64.py: the measure, the derived bounds with the source lines they count, the
+generators).  Each case is asserted against
+  * the derived bound, elementwise (hard: a case over it is a bug in the kernel or a flaw in the derivation);
+  * the measured cap E <= c R against the torch-fp32 oracle's own error on the same inputs, c per family, launch mode and class from
+    profiles/conv_accuracy_fp64.md (twice the largest measured ratio, rounded up to a power of two) — not where the oracle's error is
+    below one unit (R_max < 1: impulses, where oneDNN is exact);
+  * exactness where no product reaches the output (gamma = 0, an all-zero conv_f row with zero bias): the epilogue constant, ==.
+Every element of every case is measured.  The fp32 kernels (Winograd F(4x4) config -5, one direct fp32 configuration) run on the 3x3
+cases for the printed table only: they are the baseline the split kernels replaced.
+Plus FAM's x1 * x2 launches, the family query against the dispatch order, and one whole network whose residual blocks carry
+checkpoint-like statistics against the float64 network.  Run with -s to see the table; lines start with "ACC|"."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from read_amd.gated_conv import PackedGatedConv, config_names, conv_desc, gated_conv
+from tests import conv_ref64 as R64
+
+pytestmark = pytest.mark.gpu
+
+FAMILY_ID = {"w4h": 5, "d3h": 6, "d3h_s2": 6, "pxh": 7, "t3h": 8}
+FORCE = {"w4h": -7, "d3h": -8, "d3h_s2": -1, "pxh": -10, "t3h": -11}          # stride 2 goes through the automatic choice, family asserted
+DIRECT_FP32 = "k3s1c16_p2q1m4n1f1b2"
+
+
+def _pack(L, src_channels):
+    return PackedGatedConv(L["wf"], L["bf"], L["wm"], L["bm"], L["gamma"], L["beta"], L["mean"], L["var"], src_channels=src_channels)
+
+
+def _nhwc(a_chw):
+    return torch.from_numpy(np.ascontiguousarray(a_chw.transpose(1, 2, 0))).cuda()
+
+
+class Case:
+    def __init__(self, family, cls, name, L, x, stride=1, elu=True, residual=None, mul=None, split=None):
+        self.family, self.cls, self.name, self.L, self.x = family, cls, name, L, x
+        self.stride, self.elu, self.residual, self.mul = stride, elu, residual, mul
+        self.split = split if split is not None else [x.shape[0]]           # channels per source (pxh: concatenated sources)
+        self.k = L["wf"].shape[2]
+        self._ref = None
+
+    def ref(self):
+        if self._ref is None:
+            self._ref = R64.reference(self.L, self.x, stride=self.stride, elu=self.elu, residual=self.residual, mul=self.mul)
+        return self._ref
+
+    def launch(self, config, linear=False):
+        """-> ((C or 2 C, H, W) float32 on the host, kernel family of the launch)."""
+        pk = _pack(self.L, self.split)
+        offs = np.cumsum([0] + self.split)
+        srcs = [(_nhwc(self.x[offs[i]:offs[i + 1]]), 0) for i in range(len(self.split))]
+        kw = dict(stride=self.stride, elu=self.elu, config=config)
+        if linear:
+            kw["linear"] = True
+        else:
+            if self.residual is not None:
+                kw["residual"] = _nhwc(self.residual)
+            if self.mul is not None:
+                kw["mul"] = _nhwc(self.mul)
+        from read_amd import _lib
+        fam = _lib.lib().read_conv_kernel_family(ctypes.byref(conv_desc(pk, srcs, **kw)))
+        out = gated_conv(pk, srcs, **kw)
+        torch.cuda.synchronize()
+        return out.cpu().numpy().transpose(2, 0, 1), fam
+
+
+def _bounds(case, family):
+    """-> (d_f, d_m, B_w): the pre-activation bounds and, for the Winograd family, the condition term B with A_w in the place of A."""
+    ref = case.ref()
+    if family == "w4h":
+        df, Awf = R64.preact_bound_wino(case.L, case.x, ref, "f")
+        dm, Awm = R64.preact_bound_wino(case.L, case.x, ref, "m")
+        Awf = Awf + np.abs(case.L["bf"].astype(np.float64))[:, None, None]
+        Awm = Awm + np.abs(case.L["bm"].astype(np.float64))[:, None, None]
+        Bw = ref.S * (np.abs(ref.dact) * ref.sig * Awf + np.abs(ref.g) * ref.sig * (1.0 - ref.sig) * Awm) + np.abs(ref.y)
+        return df, dm, Bw
+    df, dm = (R64.preact_bound_direct(case.L, ref, family, fm) for fm in "fm")
+    return df, dm, None
+
+
+def check(case, config, linear=False, family=None, rows=None, assert_caps=True):
+    """Launch, measure, print the table line and assert the caps.  family: the split-operand family whose bound applies (None: a
+    comparison kernel, printed only)."""
+    ref = case.ref()
+    got, fam = case.launch(config, linear)
+    ora = R64.oracle_fp32(case.L, case.x, stride=case.stride, elu=case.elu, residual=case.residual, mul=case.mul, linear=linear)
+    finite = bool(np.isfinite(got).all())
+    clean = np.nan_to_num(got, nan=3e38, posinf=3e38, neginf=-3e38)
+    if linear:
+        (e_max, e_rms), (r_max, r_rms) = R64.measure_linear(clean, ref), R64.measure_linear(ora, ref)
+        truth = np.concatenate([ref.f, ref.m])
+    else:
+        (e_max, e_rms), (r_max, r_rms) = R64.measure_gated(clean, ref), R64.measure_gated(ora, ref)
+        truth = ref.y
+    q = float("nan")
+    ea_max, ea_rms = e_max, e_rms
+    if family is not None:
+        df, dm, Bw = _bounds(case, family)
+        bound = np.concatenate([df, dm]) if linear else R64.gated_bound(ref, df, dm)
+        q = float((np.abs(clean.astype(np.float64) - truth) / bound).max())
+        if Bw is not None:
+            # Winograd: no bound in terms of A exists (the transforms amplify).  The asserted statistic is E against the transformed-domain
+            # condition term A_w; E against A is printed as E(A): that number shows what Winograd costs.
+            e_max, e_rms = R64._stats(np.abs(clean.astype(np.float64) - truth), Bw)
+    row = dict(family=family or f"fp32[{fam}]", cls=case.cls, name=case.name, mode="linear" if linear else "gated", config=config, kernel=fam,
+               E_max=e_max, E_rms=e_rms, EA_max=ea_max, EA_rms=ea_rms, R_max=r_max, R_rms=r_rms, q=q, finite=finite)
+    print("ACC| %-8s | %s | %-44s | %-6s | cfg %3d fam %d | E_max %10.2f | E_rms %9.3f | R_max %8.2f | R_rms %7.3f | E/R max %8.2f rms %8.2f | err/bound %6.3f | E(A) max %10.2f rms %9.3f" % (
+        row["family"], case.cls, case.name, row["mode"], config, fam, e_max, e_rms, r_max, r_rms, e_max / max(r_max, 1e-30), e_rms / max(r_rms, 1e-30), q, ea_max, ea_rms))
+    if rows is not None:
+        rows.append(row)
+    if family is None or not assert_caps:
+        return row
+    what = f"{family} ({case.cls}) {case.name} {row['mode']} config {config}"
+    assert fam == FAMILY_ID[family], f"{what}: the launch took kernel family {fam}"
+    assert finite, f"{what}: non-finite output inside the documented range"
+    assert q <= 1.0, f"{what}: {q:.3f} x the derived bound (E_max {e_max:.1f}, E_rms {e_rms:.2f})"
+    if r_max >= 1.0:
+        c = R64.measured_cap(family, row["mode"], case.cls)
+        assert e_rms <= c * r_rms and e_max <= c * r_max, f"{what}: E_max {e_max:.2f} E_rms {e_rms:.3f} against {c} x (R_max {r_max:.2f}, R_rms {r_rms:.3f})"
+    if not linear:
+        mask, cands = R64.constant_outputs(case.L, ref)
+        if mask.any():
+            assert bool((np.equal(got, cands[0]) | np.equal(got, cands[1]))[mask].all()), f"{what}: outputs that no product reaches differ from the epilogue constant"
+    return row
+
+
+# ------------------------------------------------------------------------------------------ the cases
+def _res(rng, cout, H, W):
+    return rng.standard_normal((cout, H, W)).astype(np.float32)
+
+
+def _out_hw(k, stride, H, W):
+    pad = (k - 1) // 2
+    return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+
+SHAPES_A = {  # a subset of the shapes of tests/test_gpu_conv.py: (cin or source list, cout, k, stride, H, W, elu, residual)
+    "w4h": [(128, 128, 3, 1, 9, 17, True, True), (64, 64, 3, 1, 40, 100, False, True), (32, 32, 3, 1, 41, 130, True, False), (96, 96, 3, 1, 14, 37, False, False),
+            (256, 256, 3, 1, 8, 32, True, True)],
+    "d3h": [(128, 128, 3, 1, 9, 17, True, True), (64, 64, 3, 1, 40, 100, False, True), (32, 32, 3, 1, 41, 130, True, False), (32, 64, 3, 1, 19, 45, True, False),
+            (256, 256, 3, 1, 8, 32, False, True), (128, 32, 3, 1, 19, 45, True, False)],
+    "d3h_s2": [(32, 64, 3, 2, 24, 80, True, False), (64, 128, 3, 2, 13, 37, False, False), (128, 256, 3, 2, 22, 46, True, False),
+               (64, 64, 4, 2, 10, 18, True, False), (32, 96, 4, 2, 9, 21, False, False), (256, 128, 4, 2, 22, 76, True, False)],
+    "pxh": [([16], 32, 1, 1, 12, 44, True, False), ([32], 56, 1, 1, 12, 44, True, False), ([8, 56], 64, 1, 1, 12, 44, False, False),
+            ([128, 128], 128, 1, 1, 12, 44, True, True), ([96], 64, 1, 1, 40, 100, True, False), ([8, 248], 256, 1, 1, 12, 44, False, True)],
+    "t3h": [(8, 32, 3, 1, 37, 61, True, False), (8, 16, 3, 1, 22, 76, True, False), (16, 32, 3, 1, 21, 45, True, False), (32, 64, 3, 1, 13, 70, False, False),
+            (8, 32, 3, 1, 1, 40, True, False), (32, 32, 3, 1, 21, 45, True, True)],
+}
+SHAPES_B = {"w4h": [(64, 64, 3, 1, 23, 38), (128, 32, 3, 1, 9, 17)], "d3h": [(64, 64, 3, 1, 23, 38), (128, 32, 3, 1, 9, 17)],
+            "d3h_s2": [(32, 64, 3, 2, 13, 37), (64, 32, 4, 2, 10, 18)], "pxh": [(64, 56, 1, 1, 12, 44), (256, 64, 1, 1, 9, 33)],
+            "t3h": [(8, 32, 3, 1, 21, 45), (32, 32, 3, 1, 13, 37)]}
+SHAPE_C = {"w4h": (64, 32, 3, 1, 13, 37), "d3h": (64, 32, 3, 1, 13, 37), "d3h_s2": (64, 32, 3, 2, 13, 37), "pxh": (64, 32, 1, 1, 13, 37), "t3h": (32, 32, 3, 1, 13, 37)}
+
+
+def cases_a(family):
+    for j, (cin, cout, k, s, H, W, elu, with_res) in enumerate(SHAPES_A[family]):
+        split = cin if isinstance(cin, list) else [cin]
+        c = sum(split)
+        rng = np.random.default_rng([100 + j, c, cout])
+        oh, ow = _out_hw(k, s, H, W)
+        yield Case(family, "a", f"unit scale {split}->{cout} k{k}s{s} {H}x{W}", R64.tame_layer(c, cout, k, 200 + j), rng.standard_normal((c, H, W)).astype(np.float32),
+                   stride=s, elu=elu, residual=_res(rng, cout, oh, ow) if with_res else None, split=split)
+
+
+def cases_b(family):
+    for j, (cin, cout, k, s, H, W) in enumerate(SHAPES_B[family]):
+        L, x = R64.checkpoint_like(cin, cout, k, H, W, 300 + j)
+        rng = np.random.default_rng([300 + j])
+        oh, ow = _out_hw(k, s, H, W)
+        yield Case(family, "b", f"checkpoint-like {cin}->{cout} k{k}s{s} {H}x{W}", L, x, stride=s, elu=j % 2 == 0,
+                   residual=_res(rng, cout, oh, ow) if (j == 1 and family != "d3h_s2") else None)
+
+
+def cases_c(family):
+    cin, cout, k, s, H, W = SHAPE_C[family]
+    L = R64.tame_layer(cin, cout, k, 400)
+    for amp in (1.0, 2.0 ** -10):
+        for (c, y, x_) in R64.impulse_positions(cin, H, W):
+            yield Case(family, "c", f"impulse {amp:g} at c{c} ({y},{x_})", L, R64.impulse(cin, H, W, c, y, x_, amp), stride=s)
+    yield Case(family, "c", "constant 1", L, R64.constant_image(cin, H, W), stride=s)
+    yield Case(family, "c", "checkerboard +-1", L, R64.checkerboard(cin, H, W), stride=s, elu=False)
+
+
+def cases_d(family):
+    cin, cout, k, s, H, W = SHAPE_C[family]
+    L = R64.tame_layer(cin, cout, k, 500)
+    rng = np.random.default_rng([500, cin])
+    if family == "w4h":
+        # the documented range edge: |B^T d B| = 100 x 650 = 65000 < 65504 at frequency (r, r'), on interior tiles of both unit rows
+        for rows, tile in (((0, 0), (1, 1)), ((1, 2), (1, 1)), ((5, 5), (2, 3)), ((2, 5), (2, 7)), ((0, 5), (1, 8))):
+            yield Case(family, "d", f"range edge 650 rows {rows} tile {tile}", L, R64.wino_range_edge(cin, H, W, rows=rows, tile=tile, amp=650.0))
+    for amp, label in ((2.0 ** -14, "2^-14"), (1e-6, "1e-6")):
+        # hi piece subnormal: the kernel promises an absolute floor of ~1e-11 per product here (X_FLOOR of tests/conv_ref64.py, carried
+        # through the sum as conv(1, |w|)), not fp32-relative accuracy; the derived bound contains exactly that floor
+        yield Case(family, "d", f"small scale {label}", L, (rng.standard_normal((cin, H, W)) * amp).astype(np.float32), stride=s)
+
+
+ALL_CLASSES = {"a": cases_a, "b": cases_b, "c": cases_c, "d": cases_d}
+
+
+def run_family(family, rows=None, assert_caps=True):
+    linear_too = family in ("pxh", "t3h")
+    for cls in "abcd":
+        for case in ALL_CLASSES[cls](family):
+            check(case, FORCE[family], family=family, rows=rows, assert_caps=assert_caps)
+            if linear_too:
+                check(case, FORCE[family], linear=True, family=family, rows=rows, assert_caps=assert_caps)
+            if cls in "ab" and FORCE[family] != -1:
+                # the automatic choice: held to the caps of whichever split-operand family it takes, printed otherwise
+                _, fam = case.launch(-1)
+                auto = {5: "w4h", 6: "d3h", 7: "pxh", 8: "t3h"}.get(fam)
+                check(case, -1, family=auto, rows=rows, assert_caps=assert_caps)
+            if cls in "ab" and case.k == 3 and case.stride == 1 and family in ("w4h", "d3h") and case.x.shape[0] % 16 == 0:
+                check(case, -5, family=None, rows=rows)                                      # fp32 Winograd F(4x4): printed only
+                check(case, config_names().index(DIRECT_FP32), family=None, rows=rows)      # fp32 direct: printed only
+
+
+@pytest.mark.parametrize("family", ["w4h", "d3h", "d3h_s2", "pxh", "t3h"])
+def test_split_operand_family_against_fp64(hip, family):
+    run_family(family)
+
+
+def test_fam_multiply_through_the_direct_split_kernel(hip):
+    """FAM's x1 * x2 launch (automatic choice: family 6 with a multiplier): the product is rounded to fp32 before the split, one more u per
+    product in the bound."""
+    for j, c in enumerate((64, 128)):
+        rng = np.random.default_rng([600, c])
+        x1, x2 = rng.standard_normal((c, 12, 40)).astype(np.float32), rng.standard_normal((c, 12, 40)).astype(np.float32)
+        case = Case("d3h", "a", f"FAM x1 * x2 C={c}", R64.tame_layer(c, c, 3, 600 + j), x1, elu=False, residual=x1, mul=x2)
+        check(case, -1, family="d3h")
+    L, x = R64.checkpoint_like(64, 64, 3, 12, 40, 610)
+    x2 = (np.random.default_rng(611).standard_normal(x.shape)).astype(np.float32)
+    check(Case("d3h", "b", "FAM x1 * x2 checkpoint-like C=64", L, x, elu=False, residual=x, mul=x2), -1, family="d3h")
+
+
+def test_family_query_agrees_with_the_dispatch_for_small_cout(hip):
+    """read_conv_kernel_family tests the small-Cout kernel before the implicit-GEMM form, as launch_gated_conv dispatches: with conv_t3h
+    raised to 32 a 32 -> 4 layer still runs (and reports) the vector-pipe kernel, family 1; forced with config -11 it is family 8."""
+    from read_amd import _lib
+    L_ = _lib.lib()
+    L = R64.tame_layer(32, 4, 3, 700)
+    pk = _pack(L, [32])
+    x = torch.randn(128, 160, 32, device="cuda")
+    try:
+        assert L_.read_conv_kernel_family(ctypes.byref(conv_desc(pk, [(x, 0)]))) == 1
+        _lib.check(L_.read_tuning_set(b"conv_t3h", 32))
+        assert L_.read_conv_kernel_family(ctypes.byref(conv_desc(pk, [(x, 0)]))) == 1
+        assert L_.read_conv_kernel_family(ctypes.byref(conv_desc(pk, [(x, 0)], config=-11))) == 8
+        L64 = R64.tame_layer(32, 64, 3, 701)
+        assert L_.read_conv_kernel_family(ctypes.byref(conv_desc(_pack(L64, [32]), [(x, 0)]))) == 8
+    finally:
+        _lib.check(L_.read_tuning_set(b"conv_t3h", 8))
+
+
+# ------------------------------------------------------------------------------------------ the whole network
+def rescale_like_a_checkpoint(state, seed):
+    """A seeded UNet state whose residual blocks x + BC1(BC0(x)) carry checkpoint-like statistics, WITHOUT changing the function:
+      * BC0's output channel c is scaled by b_c = 2^U(-8, 6) through its BatchNorm affine (gamma, beta) and BC1's weights of input channel
+        c by 1 / b_c: BC1 — a 3x3 / stride-1 layer on the Winograd split-operand kernel — sees activations whose channel scales span 2^14
+        against inversely scaled weights (products stay O(1), the f16 pieces do not);
+      * BC1 has no ELU, so its conv_f rows (and bias) are scaled by a_o = 2^U(-6, 3) and the inverse is folded into its running
+        statistics: mean' = a mean, var' + eps = a^2 (var + eps) (var' from 2e-4 to 1e2)."""
+    st = {k: np.array(v, dtype=np.float64 if np.asarray(v).dtype.kind == "f" else None, copy=True) for k, v in state.items()}
+    rng = np.random.default_rng(seed)
+    for blk in ("Encoder", "Decoder"):
+        for i in range(4):
+            for j in range(4):
+                p0, p1 = f"{blk}.{i}.layers.{j}.main.0.block.", f"{blk}.{i}.layers.{j}.main.1.block."
+                c = st[p0 + "norm.weight"].shape[0]
+                b = 2.0 ** rng.uniform(-8, 6, c)
+                st[p0 + "norm.weight"] *= b
+                st[p0 + "norm.bias"] *= b
+                for conv in ("conv_f", "conv_m"):
+                    st[p1 + conv + ".weight"] /= b[None, :, None, None]
+                a = 2.0 ** rng.uniform(-6, 3, c)
+                st[p1 + "conv_f.weight"] *= a[:, None, None, None]
+                st[p1 + "conv_f.bias"] *= a
+                st[p1 + "norm.running_mean"] *= a
+                st[p1 + "norm.running_var"] = a * a * (st[p1 + "norm.running_var"] + R64.EPS) - R64.EPS
+    return {k: (v.astype(np.float32) if v.dtype.kind == "f" else v) for k, v in st.items()}
+
+
+def scale_inner_channel(state, block, c, factor):
+    """The same exchange for one channel of one residual block: BC0's output channel c times `factor`, BC1's weights of that channel divided."""
+    st = dict(state)
+    p0, p1 = block + ".main.0.block.", block + ".main.1.block."
+    for key in ("norm.weight", "norm.bias"):
+        v = st[p0 + key].astype(np.float64)
+        v[c] *= factor
+        st[p0 + key] = v.astype(np.float32)
+    for conv in ("conv_f", "conv_m"):
+        v = st[p1 + conv + ".weight"].astype(np.float64)
+        v[:, c] /= factor
+        st[p1 + conv + ".weight"] = v.astype(np.float32)
+    return st
+
+
+def test_unet_with_checkpoint_like_statistics_against_fp64(hip):
+    """UNetEngine at 96 x 160 on a make_unet_state whose 32 residual blocks were rescaled as above, against unet_torch.unet_forward run in
+    FLOAT64 (state and inputs cast: the restatement takes its dtype from them), at the three network guards of tests/test_gpu_unet.py
+    (MAX_ABS, MIN_PSNR, MAX_REL_RMS).  The input of the Winograd layer Decoder.0.layers.0.main.1, recomputed in float64 from the tap `zb`,
+    is brought to a maximum of 300 by scaling its largest channel (the same function-preserving exchange) and must then exceed 100
+    somewhere and stay below the documented 650: the split kernel's range is exercised, not just its middle."""
+    from oracle import unet_torch
+    from read_amd import synthetic
+    from read_amd.unet import UNetEngine, pack_state
+    from tests.test_gpu_unet import _check_rgb
+    from tests.unet_spec import UNET_SPEC
+    H, W = 96, 160
+    state = rescale_like_a_checkpoint(synthetic.make_unet_state(UNET_SPEC, 9), 17)
+    torch.manual_seed(3)
+    xs = [torch.rand(H >> l, W >> l, 8) for l in range(4)]
+    x64 = [x.permute(2, 0, 1)[None].double() for x in xs]
+    to64 = lambda st: {k: torch.from_numpy(np.asarray(v)).double() for k, v in st.items() if np.asarray(v).dtype.kind == "f"}   # noqa: E731
+    taps = {}
+    with torch.no_grad():
+        unet_torch.unet_forward(to64(state), *x64, taps=taps)
+        inner = unet_torch.basic_conv(to64(state), "Decoder.0.layers.0.main.0", taps["zb"], 3)[0]
+        per_channel = inner.abs().amax(dim=(1, 2))
+        c = int(per_channel.argmax())
+        state = scale_inner_channel(state, "Decoder.0.layers.0", c, 300.0 / float(per_channel[c]))
+        st64 = to64(state)
+        ref = unet_torch.unet_forward(st64, *x64, taps=taps)[0]
+        inner = unet_torch.basic_conv(st64, "Decoder.0.layers.0.main.0", taps["zb"], 3)
+    top = float(inner.abs().max())
+    print("input of Decoder.0.layers.0.main.1: max |x| = %.1f" % top)
+    assert ref.dtype == torch.float64 and 100.0 < top < 650.0, top
+    eng = UNetEngine(torch.from_numpy(pack_state(state)).cuda(), H, W)
+    kinds = [k for (_, _, _, k) in eng.profile(*[x.cuda() for x in xs])]
+    assert kinds.count(5) >= 70, kinds                                              # the residual blocks run on the Winograd split-operand kernel
+    got = eng.forward(*[x.cuda() for x in xs]).permute(2, 0, 1).cpu()
+    _check_rgb(got, ref, "checkpoint-like statistics against fp64")
