@@ -338,7 +338,7 @@ typedef struct read_conv_desc {
                                                i.e. activations below ~650); config = -7 forces it where the shape fits */
     const void *wpacked_d3h;                /* optional: read_conv_pack_d3h_host() output (device): the 3x3 weights themselves as two f16 pieces
                                                per weight + a power-of-two scale per output row.  Gated 3x3 / stride-1 single-source launches
-                                               with Cin % 32 == 0, Cin >= read_tuning("conv_d3h") (default 32, 0 = never) and Cout % 32 == 0
+                                               with Cin % 32 == 0, Cin >= read_tuning("conv_d3h") (default 0 = never: plain launches stay on the Winograd split-operand kernels; FAM's x1 * x2 launches take it through read_tuning("conv_d3h_fam"), default 32) and Cout % 32 == 0
                                                (FAM's mul included) then run as a DIRECT convolution on the f16 matrix cores — all nine
                                                taps, three piece pairs per product, fp32 accumulation: no Winograd transform on either
                                                side, fp32-level results (DESIGN.md 3.3 (a++)); inputs must stay below 65504 in magnitude;
@@ -401,11 +401,24 @@ int read_conv_pack_params_host(int Cout, const float *bf, const float *bm, const
                                const float *beta, const float *mean, const float *var, float eps,
                                float *params_host);
 int read_gated_conv_forward(const read_conv_desc *desc, void *stream);
+/* F(4,3)-by-rows operand of the split-operand 3x3/s1 family (Winograd along x, the three ky taps direct): read_conv_f4x1_floats(Cin, Cout)
+ * = Cin * 18 * 2 * pad32(Cout) + 2 * pad32(Cout) floats (half the F(4x4) order), 0 unless Cin % 32 == 0; order
+ * [group][wave 4][chunk of 32 cin][ky 3][frequency 6][Uh | Ul][lane][8 halfs], then 2 * pad32(Cout) floats 1 / s.
+ * read_gated_conv_forward_f4x1 is read_gated_conv_forward with that operand (device) beside the descriptor, which is frozen at ABI
+ * version 3: a family-5 launch with Cin >= read_tuning("conv_f4x1") (default 32; 0 = never), or config = -12, runs on the
+ * F(4,3)-by-rows kernel; every other launch is unchanged.  desc.wpacked_w4h may stay NULL when only this order was packed: a launch
+ * that would then need the F(4x4) order is refused with READ_EINVAL.  The input transform amplifies by at most 10 (F(4x4): 100), so
+ * the f16 pieces cover activations up to about 6500. */
+size_t read_conv_f4x1_floats(int Cin, int Cout);
+int read_conv_pack_f4x1_host(int Cin, int Cout, const float *wf, const float *wm, void *wpacked_f4x1_host);
+int read_gated_conv_forward_f4x1(const read_conv_desc *desc, const void *wpacked_f4x1, void *stream);
+/* The inverse of read_conv_pack_weights_host: (Cout, Cin, k, k) weights, exact, out of the direct fragment order. */
+int read_conv_unpack_weights_host(int Cin, int Cout, int ksize, int kc, const float *wpacked_host, float *wf, float *wm);
 /* Which kernel family read_gated_conv_forward takes for this (filled) descriptor under the current tuning knobs: 8 = the same kernel as an
  * implicit GEMM over a 3x3 layer with 8 - 32 input channels (reads wpacked_t3h), 7 = 1x1 pixel-lane kernel
  * with split operands on the f16 matrix cores (reads wpacked_d3h of a 1x1 layer), 6 = direct 3x3 with
- * split operands on the f16 matrix cores (reads wpacked_d3h), 5 = Winograd
- * F(4x4,3x3) with split operands on the f16 matrix cores (reads wpacked_w4h), 4 = Winograd F(4x4,3x3) on the fp32 matrix cores
+ * split operands on the f16 matrix cores (reads wpacked_d3h), 5 = the split-operand Winograd family for 3x3 / stride 1 on the f16
+ * matrix cores: F(4x4,3x3) (reads wpacked_w4h) or, through read_gated_conv_forward_f4x1, F(4,3) by rows (reads wpacked_f4x1), 4 = Winograd F(4x4,3x3) on the fp32 matrix cores
  * (reads wpacked_w4), 2 = Winograd F(2x2,3x3) (reads wpacked_wino), 1 = vector-pipe small-Cout kernel (reads
  * wpacked_sc), 0 = direct implicit GEMM (reads wpacked); -1 = NULL.  A host that packs ONE fragment order per layer asks this before packing (set the pointer it intends to fill to any
  * non-NULL value); a launch whose wpacked aliases Winograd fragments it would not read is refused with READ_EINVAL. */
@@ -557,7 +570,12 @@ int read_unet_pack_host(const float *raw_host, float bn_eps, float *packed_host)
  * layers that no launch executes (ConvsOut) carry nothing: 451 MB.  read_unet_create_layout refuses a lean blob (READ_EINVAL)
  * when, under the current tuning state or at a size whose tensors reach 2 GiB, one of those layers would not run on the F(4x4)
  * kernel.  The raw blob is the same for both layouts. */
-enum { READ_UNET_LAYOUT_FULL = 0, READ_UNET_LAYOUT_LEAN = 1 };
+/* The F(4,3)-by-rows order (read_conv_pack_f4x1_host) of the 70 split-operand 3x3/s1 layers, which the default plan runs on that kernel:
+ * LEAN carries it behind each such layer's F(4x4) split operand.  FULL is laid out exactly as before and does not carry it; it carries
+ * every layer's exact weights, so the host derives the order once per blob and hands it to the plan as a side buffer — see
+ * read_unet_set_f4x1 below.  LEAN_W4H is the lean layout without that order: blobs packed before the kernel existed; they, and a FULL
+ * plan without a side buffer, run those layers on the F(4x4) split-operand kernel. */
+enum { READ_UNET_LAYOUT_FULL = 0, READ_UNET_LAYOUT_LEAN = 1, READ_UNET_LAYOUT_LEAN_W4H = 2 };
 size_t read_unet_packed_floats_layout(int layout);
 int read_unet_pack_host_layout(const float *raw_host, float bn_eps, float *packed_host, int layout);
 size_t read_unet_workspace_bytes(int H, int W);
@@ -566,6 +584,13 @@ size_t read_unet_workspace_bytes(int H, int W);
 int read_unet_create(read_unet_t **out, const float *packed, int H, int W, void *ws, size_t ws_bytes);
 int read_unet_create_layout(read_unet_t **out, const float *packed, int H, int W, void *ws, size_t ws_bytes, int layout);
 void read_unet_destroy(read_unet_t *u);
+/* FULL-layout plans: for j = 0, 1, ... while read_unet_f4x1_layer(j, ...) returns 0, the layer's weights are
+ * read_conv_unpack_weights_host(cin, cout, 3, 16, full_blob + w_off, wf, wm) and its order goes to side + side_off
+ * (read_conv_pack_f4x1_host); read_unet_f4x1_floats() floats in all.  read_unet_set_f4x1 gives the device copy (16-byte aligned, must
+ * outlive the handle; NULL takes it away) to a plan created from a FULL blob. */
+size_t read_unet_f4x1_floats(void);
+int read_unet_f4x1_layer(int j, size_t *w_off, size_t *side_off, int *cin, int *cout);
+int read_unet_set_f4x1(read_unet_t *u, const float *side_dev);
 /* x0..x3: NHWC [H>>l][W>>l][8] feature pyramids; rgb: NHWC [H][W][rgb_cstride], channels 0..2
  * written (channel 3 set to 1.0f when rgb_cstride == 4, the viewer's RGBA frame, nn.py:123-124). */
 int read_unet_forward(read_unet_t *u, const float *x0, const float *x1, const float *x2,

@@ -128,6 +128,13 @@ SIGNATURES = {
     "read_conv_dkh_floats": (_sz, [_i, _i, _i]),
     "read_conv_pack_dkh_host": (_i, [_i, _i, _i, _vp, _vp, _vp]),
     "read_gated_conv_forward": (_i, [C.POINTER(ConvDesc), _vp]),
+    "read_conv_f4x1_floats": (_sz, [_i, _i]),
+    "read_conv_unpack_weights_host": (_i, [_i, _i, _i, _i, _vp, _vp, _vp]),
+    "read_unet_f4x1_floats": (_sz, []),
+    "read_unet_f4x1_layer": (_i, [_i, C.POINTER(_sz), C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i)]),
+    "read_unet_set_f4x1": (_i, [_vp, _vp]),
+    "read_conv_pack_f4x1_host": (_i, [_i, _i, _vp, _vp, _vp]),
+    "read_gated_conv_forward_f4x1": (_i, [C.POINTER(ConvDesc), _vp, _vp]),
     "read_conv_kernel_family": (_i, [_vp]),
     "read_conv_sc_floats": (_sz, [_i, _i]),
     "read_conv_pack_sc_host": (_i, [_i, _i, _vp, _vp, _vp]),

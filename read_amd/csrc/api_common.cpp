@@ -64,6 +64,7 @@ void conv_set_abl(int v);
 void conv_set_w4_grid(int v);
 void conv_set_w4(int v);
 void conv_set_w4h(int v);
+void conv_set_f4x1(int v);
 void conv_set_d3h(int v);
 void conv_set_d3h_fam(int v);
 void conv_set_d3h_s2(int v);
@@ -99,7 +100,7 @@ extern "C" int read_debug_set_trace(void *buf, size_t bytes)
 // ("conv_ablate") exist only in builds with -DREAD_DEBUG_KNOBS.
 static const char *const k_tuning_keys[] = {"splat_mode", "splat_stats", "splat_subset", "splat_near", "splat_cells",
                                             "splat_cells_sub", "splat_seeds", "splat_items", "splat_strips", "splat_wgs", "splat_zl2", "splat_lds", "splat_bins", "splat_ahead", "splat_prof", "splat_mark", "splat_cells_batch", "splat_compact", "splat_sticky", "splat_wgs_b", "splat_kslot", "unet_streams", "unet_aff_split", "unet_up_fold", "conv_kc32", "conv_px", "conv_sc", "conv_wino_wgs",
-                                            "conv_wino", "conv_w16", "conv_w4", "conv_w4h", "conv_d3h", "conv_d3h_fam", "conv_d3h_s2", "conv_pxh", "conv_t3h", "conv_w4_grid", "conv_stagger", "conv_wave", "wgrad_wino",
+                                            "conv_wino", "conv_w16", "conv_w4", "conv_w4h", "conv_f4x1", "conv_d3h", "conv_d3h_fam", "conv_d3h_s2", "conv_pxh", "conv_t3h", "conv_w4_grid", "conv_stagger", "conv_wave", "wgrad_wino",
 #ifdef READ_DEBUG_KNOBS
                                             "conv_ablate", "conv_abl", "conv_w4x2", "conv_w4h_waves",
 #endif
@@ -153,6 +154,7 @@ extern "C" int read_tuning_set(const char *key, int value)
     if (!strcmp(key, "conv_d3h_fam")) { readhip::conv_set_d3h_fam(value); return READ_OK; }   // min Cin of FAM (x1 * x2) launches on the direct split-operand kernel (0 = off)
     if (!strcmp(key, "conv_d3h")) { readhip::conv_set_d3h(value); return READ_OK; }           // min Cin on the direct split-operand 3x3 kernel (f16 matrix cores; 0 = off)
     if (!strcmp(key, "conv_w4h")) { readhip::conv_set_w4h(value); return READ_OK; }           // min Cin on the split-operand F(4x4) kernel (f16 matrix cores; 0 = off)
+    if (!strcmp(key, "conv_f4x1")) { readhip::conv_set_f4x1(value); return READ_OK; }         // min Cin of that family's launches on the F(4,3)-by-rows kernel (0 = off)
     if (!strcmp(key, "conv_w4")) { readhip::conv_set_w4(value); return READ_OK; }             // min Cin on the Winograd F(4x4,3x3) kernel (0 = off)
     if (!strcmp(key, "conv_w16")) { readhip::conv_set_w16(value); return READ_OK; }           // wave-autonomous Winograd kernel (0 = row-per-wave)
     if (!strcmp(key, "conv_wino")) { readhip::conv_set_wino(value); return READ_OK; }         // largest Cin on the Winograd kernel (0 = off)

@@ -72,6 +72,7 @@ struct ConvKArgs {
     float *out_gated;
     int blk_h, blk_valid;
     unsigned long long *trace;     // optional timeline: 8 x u64 per workgroup (read_debug_set_trace)
+    const void *wp_f4x1;           // the F(4,3)-by-rows operand as f16 piece pairs + row scales (read_conv_pack_f4x1_host) or null
 };
 
 // Epilogue transcendentals on the hardware v_exp_f32 / v_rcp_f32 (about 1 ulp each): the gate and
@@ -2362,6 +2363,345 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
 }
 
 // ------------------------------------------------------------------------------------------
+// Winograd F(4,3) ALONG X ONLY with split fp32 operands on the f16 matrix cores; the three ky taps are executed directly.
+//
+// Why: the F(4x4) split-operand kernel above is bound by its operand stream, not by a pipe (profiles/r6_w4h_ablation.md): per
+// 32-channel stage its four waves pull 288 KiB of weight fragments through one CU's vector-memory path and every 2 KiB fragment
+// feeds three MFMAs.  The direct kernel below has the same 288 KiB and four times the MFMAs.  This kernel sits between the two:
+//     M[y][f] = sum_ky sum_c U[ky][f][c] V[y + ky - 1][f][c]      V[r] = B^T d_r (the same six-point B^T, along x),
+//     U[ky] = G w[ky][:] (host packer),  Y = A^T M (the same 4 x 6 A^T)
+// 18 fragments of 2 KiB per stage and wave (144 KiB per CU), twelve MFMAs behind each; 96 accumulator registers instead of 144; the
+// input transform multiplies by at most 10 instead of 100, so the f16 range covers activations up to ~6500 (F(4x4): ~650).
+// The split-operand scheme is the one of the kernel above (V = Vh + 2^-11 Vl, U s = Uh + Ul, three piece pairs into one fp32
+// accumulator, 1 / s folded into the epilogue's bias FMAs).
+//
+// Shape: unit, persistent walk, weight ownership (wave w = output channels 8w .. 8w+7, rows 0..7 conv_f, 8..15 conv_m), epar and
+// the gate epilogue are the F(4x4) kernel's.  What differs:
+//   * a 16-tile MFMA column block = 2 image rows x 8 segments of 4 pixels (tile t: row t >> 3, segment t & 7); four blocks per unit
+//     x six frequencies = 24 accumulators;
+//   * A operand: [group][wave][chunk][ky 3][frequency 6][piece Uh | Ul][lane][8 halfs]; consumed frequency-major (the three ky
+//     fragments of a frequency are live together), ring of nine fragments, fetched two frequencies (six fragments) ahead;
+//   * B operand: V[buffer 2][row 10][frequency 6][piece 2][segment 8][slot 4][8 halfs] in LDS = 2 x 61,440 bytes; tap ky of block nb
+//     reads rows 2 nb + ky and 2 nb + ky + 1 — a row-shifted ds_read_b128 of the same image.  Within a frequency the row pairs are
+//     walked in order s = 2 nb + ky = 0 .. 8, so the pair that (nb, ky = 2) and (nb + 1, ky = 0) share is read once: 18 instead of
+//     24 reads per frequency;
+//   * transform thread = (row, segment, channel pair): 1280 items per stage, five per thread (rows 2 i + (w >> 1): wave-uniform);
+//     six buffer_load_dwordx2 per item (columns and rows outside the image carry an out-of-range offset and arrive as zeros), one
+//     bt6, six split stores; the loads run one stage ahead into the registers the transform leaves behind;
+//   * slot swizzle slot = q ^ ((-key) & 3), key = 2 (row & 1) + (segment >> 2): for an even row pair the key is tile >> 2 — the
+//     F(4x4) kernel's — and for an odd pair the same masks permuted among the tile quads, so the four 16-lane groups of
+//     ds_read_b128 still cover all 64 banks; a wave's stores of one (row, frequency, piece) are 64 consecutive dwords;
+//   * the output transform is one lane-local 1-D pass per block (a lane holds all six frequencies of its tile).
+struct F4x1Geom {
+    static constexpr int VFREQ = 256;                          // dwords per (row, frequency): 2 pieces x 8 segments x 64 bytes
+    static constexpr int VROW = 6 * VFREQ;                     // dwords per image row
+    static constexpr int VBUF = 10 * VROW;                     // dwords per V buffer (61,440 bytes)
+    static constexpr int LDS_DWORDS = 2 * VBUF;                // 122,880 bytes
+};
+
+__global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArgs a)
+{
+    using WG = F4x1Geom;
+    __shared__ __attribute__((aligned(16))) unsigned lds[WG::LDS_DWORDS];
+    __shared__ __attribute__((aligned(16))) float epar[6][32];  // the group's epilogue parameters: b_f, -log2e b_m, BN scale, BN shift, 1 / s_f, -log2e / s_m
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const SrcDev s = a.src[0];
+    const int groups = a.CoutPad >> 5, G = gridDim.x;
+    const int g = blockIdx.x % groups;
+    const int n = a.nchunks;                                   // 32-channel chunks
+
+    int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit (8 x 32 pixel block)
+    int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor (raw patches)
+    auto step_tile = [&](int &ty_, int &tx_) {
+        ty_ += a.wino_dby;
+        tx_ += a.wino_dbx;
+        if (tx_ >= a.tiles_x) {
+            tx_ -= a.tiles_x;
+            ++ty_;
+        }
+    };
+
+    // ---- transform role: thread = (segment sg, channel pair cp) of patch rows 2 i + (w >> 1), i = 0 .. 4: the rows are
+    // wave-uniform (their offsets travel in SGPRs), the columns are per lane
+    const int cp = lane & 15, sg = (wv & 1) * 4 + (lane >> 4);
+    constexpr unsigned OOR = 0x80000000u;
+    unsigned xoff[6];                                          // byte offset of patch column c, channel pair cp (a pixel row, chunk 0);
+                                                               // columns outside the image: out of range, the load returns zeros
+    int rowoff[5];                                             // byte offset of item i's image row, clamped into the image ...
+    bool rowok[5];                                             // ... and whether it was inside: a row outside loads zeros
+    const unsigned src_bytes = (unsigned)(a.inH * s.W * s.C) * 4u;
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s.p), 0, src_bytes, 0x00020000);
+    auto set_patch = [&]() {
+        const int y0 = pby * 8 - 1 + (wv >> 1), x0 = pbx * 32 + 4 * sg - 1;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int yy = y0 + 2 * i;
+            rowok[i] = (unsigned)yy < (unsigned)a.inH;
+            const int yc = yy < 0 ? 0 : yy >= a.inH ? a.inH - 1 : yy;
+            rowoff[i] = yc * s.W * s.C * 4;
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) xoff[c] = (unsigned)(x0 + c) < (unsigned)a.inW ? (unsigned)((x0 + c) * s.C + 2 * cp) * 4u : OOR;
+    };
+    auto advance = [&]() {
+        if (++pchunk == n) {
+            pchunk = 0;
+            if (pu + G < a.n_units) {
+                pu += G;
+                step_tile(pby, pbx);
+            }
+            set_patch();
+        }
+    };
+    f32x2 d2[5][6];                                            // the five row segments of the chunk under transform: (channel 2 cp, 2 cp + 1)
+    auto gload = [&](int i, int c) {
+        d2[i][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, rowok[i] ? xoff[c] : OOR, rowoff[i] + pchunk * 128, 0));
+    };
+    // B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1] on six channel pairs
+    auto bt6 = [](f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5) {
+        const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2), f = pk_sub(x3, x1), h = pk_sub(x4, x2);
+        const f32x2 y0 = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
+        const f32x2 y5 = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
+        x0 = y0;
+        x1 = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
+        x2 = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
+        x3 = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
+        x4 = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
+        x5 = y5;
+    };
+    // V store address (dwords) of this thread: + buffer + 2 i rows + frequency * 256 (+ 128: the low piece); the swizzle key
+    // 2 (row & 1) + (segment >> 2) is the wave number for every item
+    const int vwoff = (wv >> 1) * WG::VROW + sg * 16 + (((cp >> 2) ^ ((-wv) & 3)) << 2) + (cp & 3);
+    auto split_store = [&](const f32x2 x, int vb, int i, int fq) {
+        unsigned hi, lo;
+        float r0, r1;
+        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x.x), "v"(x.y));
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x.x));                    // x - f32(hi), exact
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x.y));
+        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
+        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
+        lds[vwoff + vb + 2 * i * WG::VROW + fq * WG::VFREQ] = hi;
+        lds[vwoff + vb + 2 * i * WG::VROW + fq * WG::VFREQ + 128] = lo;
+    };
+    // step k of a chunk's transform, seven per item: the 1-D pass, then six frequencies (split + store); the item's registers are
+    // then refilled with the patch of the chunk after
+    constexpr int T_STEPS = 35;
+    auto t_step = [&](int vb, int k) {
+        const int i = k / 7, j = k % 7;
+        if (j == 0) bt6(d2[i][0], d2[i][1], d2[i][2], d2[i][3], d2[i][4], d2[i][5]);
+        else {
+            split_store(d2[i][j - 1], vb, i, j - 1);
+            if (j == 6) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) gload(i, c);
+            }
+        }
+    };
+
+    // ---- A operand (weights): fragment (chunk, ky, fq), consumed in the order (fq, ky)
+    const char *const wbase = reinterpret_cast<const char *>(a.wp_f4x1) + ((size_t)(g * 4 + wv) * n) * (18 * 2048);
+    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(wbase), 0, (unsigned)n * (18 * 2048), 0x00020000);
+    const unsigned wvoff = lane * 16;
+    constexpr int RW = 9;                                      // ring of three frequencies x three taps, fetched two frequencies ahead
+    u32x4 Wh[RW], Wl[RW];
+    f16x8 Ws[2][3];                                            // 2^-11 Uh, one frequency ahead
+    auto wload = [&](int chunk, int fq, int ky) {
+        const int slot = (fq % 3) * 3 + ky;
+        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048, 0);
+        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048 + 1024, 0);
+    };
+    auto wscale = [&](int fq, int ky) {
+        const _Float16 k = (_Float16)0x1p-11f;
+        Ws[fq & 1][ky] = __builtin_bit_cast(f16x8, Wh[(fq % 3) * 3 + ky]) * f16x8{k, k, k, k, k, k, k, k};
+    };
+    // ---- B operand: row pair s (rows s, s + 1) of frequency fq; ring of three, fetched two pairs ahead
+    const int t16 = lane & 15, kl = lane >> 4;
+    const int vrd_e = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-(t16 >> 2)) & 3)) << 2);
+    const int vrd_o = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-((t16 >> 2) ^ 2)) & 3)) << 2);
+    constexpr int RB = 3;
+    u32x4 Bh[RB], Bl[RB];
+    auto bload = [&](int vb, int idx) {                        // idx = fq * 9 + s
+        const int fq = idx / 9, sp = idx % 9;
+        const int o = vb + sp * WG::VROW + fq * WG::VFREQ + ((sp & 1) ? vrd_o : vrd_e);
+        Bh[idx % RB] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + o, 16));
+        Bl[idx % RB] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + o + 128, 16));
+    };
+
+    f32x4 acc[4][6];
+    const auto out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)(a.outH * a.outW * a.out_cstride) * 4u, 0x00020000);
+    const auto res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.residual ? a.residual : a.out), 0,
+                                                            (unsigned)(a.outH * a.outW * a.Cout) * 4u, 0x00020000);
+    const float *const wsc = reinterpret_cast<const float *>(a.wp_f4x1) + (size_t)n * 1152 * a.CoutPad;      // 1 / s: [f | m][CoutPad]
+    if (tid < 192) {                                           // the group is fixed per workgroup: its epilogue parameters go to LDS once
+        constexpr float L2E = 1.44269504088896341f;
+        const int arr = tid >> 5, c = g * 32 + (tid & 31);
+        const float v = arr < 4 ? a.params[arr * a.CoutPad + c] : wsc[(arr - 4) * a.CoutPad + c];
+        epar[arr][tid & 31] = (arr == 1 || arr == 5) ? v * -L2E : v;
+    }
+
+    // ---- prologue: patch(0) -> registers -> V(0); patch(1) -> registers; the first weight fragments and B operands
+    set_patch();
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) gload(i, c);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) wload(0, j / 3, j % 3);
+    advance();
+#pragma unroll
+    for (int k = 0; k < T_STEPS; ++k) t_step(0, k);
+    advance();
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) wscale(0, ky);
+    __syncthreads();
+    bload(0, 0);
+    bload(0, 1);
+
+    int v_cur = 0, v_nxt = WG::VBUF;
+
+    // One stage = one 32-channel chunk: 216 MFMAs (6 frequencies x 12 (block, tap) pairs x 3 piece pairs); beside them the
+    // transform of chunk + 1 (registers -> v_nxt) and the loads of patch(chunk + 2) into the registers the transform leaves behind.
+    auto stage_body = [&](auto first_tag, int chunk) {
+        constexpr bool FIRST = decltype(first_tag)::value;
+        int nchunk = chunk + 1;                                       // wraps into the next unit (same weights)
+        nchunk = nchunk == n ? 0 : nchunk;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int fq = 0; fq < 6; ++fq)
+#pragma unroll
+            for (int sp = 0; sp < 9; ++sp)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    // the (block, tap) pairs that read row pair sp: odd sp (nb, 1); even sp (nb - 1, 2) and then (nb, 0)
+                    const int nb = (sp & 1) ? sp >> 1 : (sp >> 1) - 1 + q, ky = (sp & 1) ? 1 : q ? 0 : 2;
+                    if (((sp & 1) && q) || nb < 0 || nb > 3) continue;
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) {
+                        // MFMA slot: row pairs 2, 4, 6 carry two (block, tap) pairs, the others one: first slots 0 3 6 12 15 21 24 30 33
+                        const int mb = 3 * sp + 3 * ((sp > 0 ? sp - 1 : 0) / 2);
+                        const int ms = mb + ((!(sp & 1) && q && sp > 0) ? 3 : 0) + pc, m = fq * 36 + ms, idx = fq * 9 + sp;
+                        if (ms == mb) {
+                            // B operands two row pairs ahead.  Before the first one of the next chunk: V(chunk + 1) is complete in
+                            // every wave (last store at slot 138) and every wave has fetched its last B operand of this chunk
+                            if (idx == 52) __syncthreads();
+                            if (idx + 2 < 54) bload(v_cur, idx + 2);
+                            else bload(v_nxt, idx + 2 - 54);
+                        }
+                        const int ws = (fq % 3) * 3 + ky;
+                        const f16x8 av = pc == 0 ? Ws[fq & 1][ky] : __builtin_bit_cast(f16x8, pc == 1 ? Wl[ws] : Wh[ws]);
+                        const f16x8 bv = __builtin_bit_cast(f16x8, pc == 0 ? Bl[idx % RB] : Bh[idx % RB]);
+                        if (FIRST && pc == 0 && ky == 0) {
+                            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+                            acc[nb][fq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, zero, 0, 0, 0);
+                        } else
+                            acc[nb][fq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[nb][fq], 0, 0, 0);
+                        // ---- shadow items
+                        if (ms == 4 || ms == 10 || ms == 16) {                           // weights two frequencies ahead
+                            const int wf = fq + 2, wk = (ms - 4) / 6;
+                            if (wf < 6) wload(chunk, wf, wk);
+                            else wload(nchunk, wf - 6, wk);
+                        } else if (ms == 19 || ms == 25 || ms == 31)
+                            wscale((fq + 1) % 6, (ms - 19) / 6);                         // 2^-11 Uh of the next frequency
+                        if ((m & 3) == 2 && (m >> 2) < T_STEPS) t_step(v_nxt, m >> 2);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+        advance();
+        const int v = v_cur;
+        v_cur = v_nxt;
+        v_nxt = v;
+    };
+
+    for (int u = blockIdx.x; u < a.n_units; u += G) {
+        stage_body(std::true_type{}, 0);
+        for (int chunk = 1; chunk < n; ++chunk) stage_body(std::false_type{}, chunk);
+
+        // ================= unit epilogue (lane-local: the F(4x4) kernel's, with a 1-D output transform) =================
+        __builtin_amdgcn_s_setprio(1);
+        const int cq = (lane >> 4) & 1, hf = lane >> 5;
+        const int c0 = g * 32 + wv * 8 + 4 * cq;
+        const int oy = by * 8 + 4 * hf + (t16 >> 3), ox = bx * 32 + 4 * (t16 & 7);           // this lane finishes rows oy, oy + 2
+        const int cl = wv * 8 + 4 * cq;
+        const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
+        const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
+        const f32x4 isf = *reinterpret_cast<const f32x4 *>(&epar[4][cl]), ism = *reinterpret_cast<const f32x4 *>(&epar[5][cl]);
+        constexpr float LOG2E = 1.44269504088896341f;
+        unsigned rvoff[2][4], ovoff[2][4];
+#pragma unroll
+        for (int py = 0; py < 2; ++py)
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                const bool in = (oy + 2 * py < a.outH) & (ox + px < a.outW) & (c0 < a.Cout);
+                const int pix = (oy + 2 * py) * a.outW + ox + px;
+                rvoff[py][px] = in ? (unsigned)((pix * a.Cout + c0) * 4) : OOR;
+                ovoff[py][px] = in ? (unsigned)((pix * a.out_cstride + c0) * 4) : OOR;
+            }
+        f32x4 rv[2][4];
+#pragma unroll
+        for (int py = 0; py < 2; ++py)
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                rv[py][px] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (a.residual) rv[py][px] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvoff[py][px], 0, 0));
+            }
+        f32x4 Y[4][4];                                                 // [block][pixel of the tile]
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb) {
+            const f32x4 s1 = acc[nb][1] + acc[nb][2], d1 = pk_sub4(acc[nb][1], acc[nb][2]);
+            const f32x4 s2 = acc[nb][3] + acc[nb][4], dd2 = pk_sub4(acc[nb][3], acc[nb][4]);
+            Y[nb][0] = acc[nb][0] + s1 + s2;
+            Y[nb][1] = d1 + 2.0f * dd2;
+            Y[nb][2] = s1 + 4.0f * s2;
+            Y[nb][3] = d1 + 8.0f * dd2 + acc[nb][5];
+        }
+        // lanes 0..31 hold conv_f, lanes 32..63 conv_m of the same channels: after the swap the lower half finishes blocks 0, 1
+        // and the upper half blocks 2, 3, both with f and m of a pixel in one lane
+        f32x4 Yf[2][4], Ym[2][4];
+#pragma unroll
+        for (int py = 0; py < 2; ++py)
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                u32x4 u0 = __builtin_bit_cast(u32x4, Y[py][px]), u1 = __builtin_bit_cast(u32x4, Y[py + 2][px]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
+                    u0[k] = sw[0];
+                    u1[k] = sw[1];
+                }
+                Yf[py][px] = __builtin_bit_cast(f32x4, u0);
+                Ym[py][px] = __builtin_bit_cast(f32x4, u1);
+            }
+#pragma unroll
+        for (int py = 0; py < 2; ++py)
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                f32x4 f = __builtin_elementwise_fma(Yf[py][px], isf, bf);
+                const f32x4 mm = __builtin_elementwise_fma(Ym[py][px], ism, bml);
+                if (a.elu) {
+                    const f32x4 fe = f * LOG2E;
+                    f32x4 e;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = __builtin_amdgcn_exp2f(fe[k]);
+                    e = e + f32x4{-1.0f, -1.0f, -1.0f, -1.0f};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = f[k] > 0.0f ? f[k] : e[k];
+                }
+                f32x4 sg_, t;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) t[k] = __builtin_amdgcn_exp2f(mm[k]);
+                t = t + f32x4{1.0f, 1.0f, 1.0f, 1.0f};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sg_[k] = __builtin_amdgcn_rcpf(t[k]);
+                const f32x4 v = (f * sg_) * sc + sh + rv[py][px];
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[py][px], 0, 0);
+            }
+        step_tile(by, bx);
+        __builtin_amdgcn_s_setprio(0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // DIRECT 3x3 / stride-1 gated convolution with split fp32 operands on the f16 matrix cores (round 6, second kernel of the round).
 //
 // Why: the attribution of the split-operand Winograd kernel above (profiles/r6_w4h_ablation.md) — its MFMAs are a fifth of its launch,
@@ -4467,6 +4807,9 @@ int g_w4x2 = 0;            // debug library only: read_tuning_set("conv_w4x2", 1
 int g_w4 = 32;             // read_tuning_set("conv_w4", min Cin): layers with at least this many channels take the Winograd F(4x4,3x3)
 int g_w4h = 32;            // read_tuning_set("conv_w4h", min Cin): F(4x4) layers with Cin % 32 == 0 and at least this many channels take the split-operand
                            // kernel on the f16 matrix cores when its operand was supplied (0 = never: the fp32 kernel)
+int g_f4x1 = 32;           // read_tuning_set("conv_f4x1", min Cin): launches of the split-operand 3x3/s1 family with at least this many channels take the
+                           // F(4,3)-by-rows kernel (gated_conv_f4x1h_kernel) when its operand was supplied (0 = never: the F(4x4) kernel).  Default 32: alternated with the F(4x4) kernel in one
+                           // process it measured 6 - 11 % faster at every level (profiles/f4x1_ab.md)
 int g_w4h_waves = 4;       // debug library only: read_tuning_set("conv_w4h_waves", 8) = the split-operand kernel with specialised waves (measured slower, round 6)
 int g_d3h = 0;             // read_tuning_set("conv_d3h", min Cin): gated 3x3 / stride-1 layers with whole 32-channel chunks and at least this many channels take the
                            // DIRECT split-operand kernel (f16 matrix cores, all nine taps) when its operand was supplied.  Default 0 (never): on plain
@@ -4614,6 +4957,30 @@ extern "C" int read_conv_pack_weights_host(int Cin, int Cout, int ksize, int kc,
                             const int cout = (nt >> 1) * 32 + (lane & 31);
                             const int cin = chunk * kc + kk * 8 + 4 * (lane >> 5) + j;
                             wpacked_host[o] = cout < Cout ? w[((size_t)cout * Cin + cin) * taps + tap] : 0.0f;
+                        }
+                }
+    return READ_OK;
+}
+
+// The inverse of read_conv_pack_weights_host: the layer's weights (Cout, Cin, k, k), exact, out of its direct fragment order.
+extern "C" int read_conv_unpack_weights_host(int Cin, int Cout, int ksize, int kc, const float *wpacked_host, float *wf, float *wm)
+{
+    READ_CHECK_ARG(wf && wm && wpacked_host, "read_conv_unpack_weights_host: null pointer");
+    READ_CHECK_ARG((ksize == 1 || ksize == 3 || ksize == 4) && (kc == 8 || kc == 16 || (kc == 32 && ksize == 1)) && Cin >= kc && Cin % kc == 0 && Cout >= 1,
+                   "read_conv_unpack_weights_host: bad shape (Cin=%d kc=%d ksize=%d)", Cin, kc, ksize);
+    const int CoutPad = pad32(Cout), NT = CoutPad / 16, KK = kc / 8, taps = ksize * ksize;
+    const int nchunks = Cin / kc;
+    size_t o = 0;
+    for (int chunk = 0; chunk < nchunks; ++chunk)
+        for (int tap = 0; tap < taps; ++tap)
+            for (int kk = 0; kk < KK; ++kk)
+                for (int nt = 0; nt < NT; ++nt) {
+                    float *w = (nt & 1) ? wm : wf;
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int j = 0; j < 4; ++j, ++o) {
+                            const int cout = (nt >> 1) * 32 + (lane & 31);
+                            const int cin = chunk * kc + kk * 8 + 4 * (lane >> 5) + j;
+                            if (cout < Cout) w[((size_t)cout * Cin + cin) * taps + tap] = wpacked_host[o];
                         }
                 }
     return READ_OK;
@@ -4810,6 +5177,66 @@ extern "C" int read_conv_pack_w4h_host(int Cin, int Cout, const float *wf, const
     return READ_OK;
 }
 
+// F(4,3)-by-rows operand of gated_conv_f4x1h_kernel: U[ky] = G w[ky][:] in double (the filter transform along x only), scaled per
+// output ROW by the power of two s that puts max |U s| of the row in [2^14, 2^15), cut into Uh = f16(U s) and Ul = f16(U s - Uh);
+// order [group][wave 4][chunk of 32 cin][ky 3][frequency 6][piece Uh | Ul][lane][8 halfs], lanes as in read_conv_pack_w4h_host; then
+// 2 * CoutPad floats 1 / s ([conv_f rows | conv_m rows]).  Half the bytes of the F(4x4) order: Cin * 18 * pad32(Cout) * 2 halfs.
+extern "C" size_t read_conv_f4x1_floats(int Cin, int Cout)
+{
+    if (Cin < 32 || Cin % 32 || Cout < 1) return 0;
+    return (size_t)Cin * 18 * 2 * pad32(Cout) + 2 * (size_t)pad32(Cout);
+}
+
+extern "C" int read_conv_pack_f4x1_host(int Cin, int Cout, const float *wf, const float *wm, void *out)
+{
+    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_f4x1_host: null pointer");
+    READ_CHECK_ARG(Cin >= 32 && Cin % 32 == 0 && Cout >= 1, "read_conv_pack_f4x1_host: needs Cin %% 32 == 0 (got %d)", Cin);
+    static const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
+                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
+    const int CoutPad = pad32(Cout), nchunks = Cin / 32;
+    unsigned short *h = static_cast<unsigned short *>(out);
+    float *inv = reinterpret_cast<float *>(out) + (size_t)Cin * 18 * 2 * CoutPad;
+    std::vector<double> U((size_t)18 * Cin);                   // [ky][frequency][cin]
+    for (int row = 0; row < 2 * CoutPad; ++row) {               // row = [f | m] x padded output channel
+        const int fm = row / CoutPad, co = row % CoutPad;
+        double mx = 0.0;
+        if (co < Cout)
+            for (int ci = 0; ci < Cin; ++ci) {
+                const float *k = (fm ? wm : wf) + ((size_t)co * Cin + ci) * 9;
+                for (int t = 0; t < 18; ++t) {
+                    double u = 0.0;
+                    for (int b = 0; b < 3; ++b) u += G[t % 6][b] * (double)k[(t / 6) * 3 + b];
+                    U[(size_t)t * Cin + ci] = u;
+                    mx = std::fmax(mx, std::fabs(u));
+                }
+            }
+        else
+            std::fill(U.begin(), U.end(), 0.0);
+        int ex = 0;                                            // s = 2^ex: max |U| s in [2^14, 2^15)
+        if (mx > 0.0 && std::isfinite(mx)) {
+            int e;
+            (void)std::frexp(mx, &e);                          // mx in [2^(e-1), 2^e)
+            ex = 15 - e;
+            if (ex > 60) ex = 60;                              // a row of denormal weights: keep 1 / s an fp32 normal
+            if (ex < -60) ex = -60;
+        }
+        inv[row] = (float)std::ldexp(1.0, -ex);
+        const int g = co / 32, w = (co % 32) / 8, i = (co % 8) + 8 * fm;
+        for (int c = 0; c < nchunks; ++c)
+            for (int t = 0; t < 18; ++t)
+                for (int kq = 0; kq < 4; ++kq)
+                    for (int e = 0; e < 8; ++e) {
+                        const double us = std::ldexp(U[(size_t)t * Cin + 32 * c + 8 * kq + e], ex);
+                        const unsigned short hi = f16_bits_rtn(us), lo = f16_bits_rtn(us - f16_value(hi));
+                        const size_t frag = ((((size_t)(g * 4 + w) * nchunks + c) * 18 + t) * 2) * 512;     // halfs; 512 per piece
+                        const int lane = i + 16 * kq;
+                        h[frag + (size_t)lane * 8 + e] = hi;
+                        h[frag + 512 + (size_t)lane * 8 + e] = lo;
+                    }
+    }
+    return READ_OK;
+}
+
 // Operand of the direct split-operand kernel (gated_conv_d3h_kernel): the 3x3 weights themselves, scaled per output ROW by the power
 // of two s that puts the row's largest |w s| in [2^14, 2^15), cut into wh = f16(w s) and wl = f16(w s - wh); order
 // [group][row half rh 2][chunk of 32 cin][tap 9 = 3 ky + kx][row block rb 2][piece wh | wl][lane][8 halfs], lane (i = lane & 15,
@@ -4976,6 +5403,7 @@ void conv_set_w16(int v) { g_w16 = v != 0; }
 void conv_set_abl(int v) { g_abl = v; }
 void conv_set_w4(int v) { g_w4 = v < 0 ? 0 : v; }
 void conv_set_w4h(int v) { g_w4h = v < 0 ? 0 : v; }
+void conv_set_f4x1(int v) { g_f4x1 = v < 0 ? 0 : v; }
 void conv_set_d3h(int v) { g_d3h = v < 0 ? 0 : v; }
 void conv_set_d3h_fam(int v) { g_d3h_fam = v < 0 ? 0 : v; }
 void conv_set_d3h_s2(int v) { g_d3h_s2 = v < 0 ? 0 : v; }
@@ -5002,6 +5430,7 @@ int conv_get(const char *key, int *value)
     else if (!strcmp(key, "conv_w16")) *value = g_w16;
     else if (!strcmp(key, "conv_w4")) *value = g_w4;
     else if (!strcmp(key, "conv_w4h")) *value = g_w4h;
+    else if (!strcmp(key, "conv_f4x1")) *value = g_f4x1;
     else if (!strcmp(key, "conv_d3h")) *value = g_d3h;
     else if (!strcmp(key, "conv_d3h_fam")) *value = g_d3h_fam;
     else if (!strcmp(key, "conv_d3h_s2")) *value = g_d3h_s2;
@@ -5032,13 +5461,14 @@ void conv_set_trace(void *buf, size_t bytes)
 int conv_uses_wino(const read_conv_desc *d);
 int conv_uses_w4(const read_conv_desc *d);
 int conv_uses_w4h(const read_conv_desc *d);
+int conv_uses_f4x1(const read_conv_desc *d);
 int conv_uses_d3h(const read_conv_desc *d);
 int conv_uses_d3h_s2(const read_conv_desc *d);
 int conv_uses_sc(const read_conv_desc *d);
 int conv_uses_pxh(const read_conv_desc *d);
 int conv_uses_t3h(const read_conv_desc *d);
 
-int launch_gated_conv(const read_conv_desc *d, hipStream_t stream)
+int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *wp_f4x1)
 {
     READ_CHECK_ARG(d, "read_gated_conv_forward: null descriptor");
     READ_CHECK_ARG(d->n_src >= 1 && d->n_src <= READ_CONV_MAX_SRC, "read_gated_conv_forward: n_src must be 1..%d",
@@ -5046,7 +5476,7 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream)
     READ_CHECK_ARG(d->ksize == 1 || d->ksize == 3 || d->ksize == 4, "read_gated_conv_forward: ksize must be 1,3,4");
     READ_CHECK_ARG(d->stride == 1 || d->stride == 2, "read_gated_conv_forward: stride must be 1 or 2");
     READ_CHECK_ARG(d->inH >= 1 && d->inW >= 1 && d->Cout >= 1, "read_gated_conv_forward: bad sizes");
-    READ_CHECK_ARG((d->wpacked || d->wpacked_w4 || d->wpacked_w4h || d->wpacked_d3h || d->wpacked_wino || d->wpacked_t3h) && d->params && d->out, "read_gated_conv_forward: null weights/params/out");
+    READ_CHECK_ARG((d->wpacked || d->wpacked_w4 || d->wpacked_w4h || d->wpacked_d3h || d->wpacked_wino || d->wpacked_t3h || wp_f4x1) && d->params && d->out, "read_gated_conv_forward: null weights/params/out");
     READ_CHECK_ARG(d->out_cstride >= (d->linear ? 2 : 1) * d->Cout, "read_gated_conv_forward: out_cstride too small");
     READ_CHECK_ARG(!d->linear || (!d->residual && !d->fill_pad), "read_gated_conv_forward: linear mode takes no residual / fill");
     READ_CHECK_ARG(!d->mul || d->n_src == 1, "read_gated_conv_forward: mul needs a single source");
@@ -5381,9 +5811,13 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream)
         a.tiles_x = ceil_div(outW, 16);
         const int pairs = (CoutPad + 63) / 64;
         a.n_units = a.tiles_x * ceil_div(outH, 8) * pairs;
-        int dev = 0, n_cu_s = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n_cu_s = prop.multiProcessorCount;
+        static int n_cu_s = 0;
+        if (!n_cu_s) {
+            int dev = 0;
+            hipDeviceProp_t prop;
+            n_cu_s = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
+                      prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        }
         int nwg = a.n_units < n_cu_s ? a.n_units : n_cu_s;
         nwg -= nwg % pairs;
         if (nwg < pairs) nwg = pairs;
@@ -5397,12 +5831,21 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream)
     }
     // Winograd F(4x4,3x3): units of 8 x 32 pixels x 32 channels, one persistent workgroup per CU
     const bool d3h = conv_uses_d3h(d), w4h = !d3h && conv_uses_w4h(d);
+    // ... the F(4,3)-by-rows kernel for the family-5 launches its predicate names, when the caller brought its operand; a caller
+    // without it (a blob packed before the kernel existed) keeps running on the F(4x4) kernel
+    const bool f4x1 = w4h && wp_f4x1 && conv_uses_f4x1(d);
+    READ_CHECK_ARG(d->config != -12 || f4x1, "read_gated_conv_forward: config -12 takes the launches of the split-operand 3x3/s1 family "
+                   "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
+    READ_CHECK_ARG(!w4h || f4x1 || d->wpacked_w4h != wp_f4x1, "read_gated_conv_forward: this launch takes the F(4x4) split-operand kernel "
+                   "and only the F(4,3)-by-rows order was packed");
     if (d3h || w4h || conv_uses_w4(d)) {
         READ_CHECK_ARG((uintptr_t)(d3h ? d->wpacked_d3h : w4h ? d->wpacked_w4h : (const void *)d->wpacked_w4) % 16 == 0,
                        "read_gated_conv_forward: wpacked_w4 / wpacked_w4h / wpacked_d3h misaligned");
         a.wp_d3h = d->wpacked_d3h;
         READ_CHECK_ARG(!d->mul || (uintptr_t)d->mul % 16 == 0, "read_gated_conv_forward: mul misaligned");
         a.wp_w4h = d->wpacked_w4h;
+        a.wp_f4x1 = wp_f4x1;
+        READ_CHECK_ARG(!f4x1 || (uintptr_t)wp_f4x1 % 16 == 0, "read_gated_conv_forward: wpacked_f4x1 misaligned");
         if (w4h || d3h) a.nchunks = Cin / 32;
         a.tiles_x = ceil_div(outW, 32);
         a.n_units = a.tiles_x * ceil_div(outH, 8) * groups;
@@ -5457,6 +5900,11 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream)
             }
 #endif
             hipLaunchKernelGGL(fnd, dim3((unsigned)nwg), dim3(512), 0, stream, a);
+            READ_CHECK_LAUNCH();
+            return READ_OK;
+        }
+        if (f4x1) {
+            hipLaunchKernelGGL(gated_conv_f4x1h_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, a);
             READ_CHECK_LAUNCH();
             return READ_OK;
         }
@@ -5547,7 +5995,7 @@ int conv_uses_w4h(const read_conv_desc *d)
     // (FAM's x1 * x2 stays on the fp32 kernel: the second patch costs the transform thread another 72 registers, and the
     //  variant with a shallower weight ring measured SLOWER than the fp32 kernel — 101 / 79 / 68 us against 77 / 69 / 64 at C = 64 / 128 / 256)
     if (!d->wpacked_w4h || d->linear || d->mul || d->src[0].C % 32 != 0 || d->Cout % 32 != 0) return 0;
-    if (d->config == -7) {
+    if (d->config == -7 || d->config == -12) {                             // -12: the F(4,3)-by-rows kernel of the same family (conv_uses_f4x1)
         read_conv_desc t = *d;
         t.config = -5;
         t.wpacked_w4 = reinterpret_cast<const float *>(d->wpacked_w4h);    // the shape test of the family (any non-null operand)
@@ -5557,6 +6005,14 @@ int conv_uses_w4h(const read_conv_desc *d)
     read_conv_desc t = *d;
     t.wpacked_w4 = reinterpret_cast<const float *>(d->wpacked_w4h);
     return conv_uses_w4(&t);
+}
+
+// ... and of those the launches that take the F(4,3)-by-rows kernel instead of the F(4x4) one: at least conv_f4x1 input channels
+// (config -12 forces it).  Consulted inside the family-5 branch only; both kernels report family 5.
+int conv_uses_f4x1(const read_conv_desc *d)
+{
+    if (!conv_uses_w4h(d)) return 0;
+    return d->config == -12 || (d->config == -1 && g_f4x1 > 0 && d->src[0].C >= g_f4x1);
 }
 
 // the DIRECT split-operand kernel: the same launches (FAM's x1 * x2 included: a multiplication at staging time); config -8 forces it
@@ -5647,11 +6103,23 @@ extern "C" int read_conv_kernel_family(const read_conv_desc *desc)
     return 0;
 }
 
+// The same launch with the F(4,3)-by-rows operand (read_conv_pack_f4x1_host) beside the descriptor: the descriptor struct is
+// frozen at ABI version 3.  A launch of the split-operand 3x3/s1 family that conv_f4x1 (or config -12) names runs on
+// gated_conv_f4x1h_kernel; every other launch behaves exactly as read_gated_conv_forward.  A host that packed ONLY this order leaves
+// wpacked_w4h NULL: the family's shape test then sees this operand, and a launch that would read it as the F(4x4) order is refused.
+extern "C" int read_gated_conv_forward_f4x1(const read_conv_desc *desc, const void *wpacked_f4x1, void *stream)
+{
+    if (!desc || !wpacked_f4x1 || desc->wpacked_w4h) return readhip::launch_gated_conv(desc, as_stream(stream), wpacked_f4x1);
+    read_conv_desc t = *desc;
+    t.wpacked_w4h = wpacked_f4x1;
+    return readhip::launch_gated_conv(&t, as_stream(stream), wpacked_f4x1);
+}
+
 extern "C" int read_gated_conv_forward(const read_conv_desc *desc, void *stream)
 {
     // the fragment-order checks (a NULL or aliased wpacked against the kernel family this launch takes) live in
     // launch_gated_conv: the UNet executor (unet.cpp) calls that directly and must get the same refusal
-    return readhip::launch_gated_conv(desc, as_stream(stream));
+    return readhip::launch_gated_conv(desc, as_stream(stream), nullptr);
 }
 
 // ---- measurement aid (bench.py: roofline.mfma_sustained): the rate the fp32 matrix path delivers when a wave does nothing else.

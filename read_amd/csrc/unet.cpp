@@ -13,10 +13,11 @@
 #include "common.h"
 
 namespace readhip {
-int launch_gated_conv(const read_conv_desc *d, hipStream_t stream);
+int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *wp_f4x1);
 int conv_uses_wino(const read_conv_desc *d);
 int conv_uses_w4(const read_conv_desc *d);
 int conv_uses_w4h(const read_conv_desc *d);
+int conv_uses_f4x1(const read_conv_desc *d);
 int conv_uses_d3h(const read_conv_desc *d);
 int conv_uses_d3h_s2(const read_conv_desc *d);
 }
@@ -39,6 +40,8 @@ struct LayerInfo {
     size_t w4h_off = ~(size_t)0;    // F(4x4) weights split into f16 piece pairs (read_conv_pack_w4h_host) of the w4 layers with Cin % 32 == 0, else NO_WINO
     size_t d3h_off = ~(size_t)0;    // the plain 3x3 weights as f16 piece pairs (read_conv_pack_d3h_host) of the same layers, else NO_WINO
     size_t t3h_off = ~(size_t)0;    // 3x3 / stride-1 layers over the 8-channel pyramid: the implicit-GEMM operand (read_conv_pack_t3h_host), else NO_WINO
+    size_t f4x1_off = ~(size_t)0;   // the F(4,3)-by-rows order (read_conv_pack_f4x1_host) of the w4h layers — the LEAN layout only, else NO_WINO
+    size_t side_off = ~(size_t)0;   // FULL layout: offset of that order in the side buffer (read_unet_set_f4x1), else NO_WINO
 };
 constexpr size_t NO_WINO = ~(size_t)0;
 
@@ -56,7 +59,7 @@ struct DerivedInfo {
 struct Arch {
     std::vector<LayerInfo> layers;
     std::vector<DerivedInfo> derived;
-    size_t raw_floats = 0, packed_floats = 0;
+    size_t raw_floats = 0, packed_floats = 0, side_floats = 0;
     int find_derived(const std::string &p) const
     {
         for (size_t i = 0; i < derived.size(); ++i)
@@ -78,9 +81,14 @@ size_t raw_layer_floats(int cin, int cout, int k) { return 2 * ((size_t)cout * c
 // a layer the F(4x4) kernel takes carries its F(4x4) order ONLY (that kernel runs 73 of the 105 launches; its layers' other three
 // orders were 500 MB nobody touched), the layers no launch executes (ConvsOut) carry nothing; everything else as in FULL.
 // The raw blob (read_unet_raw_floats) is the same for both.
+// The F(4,3)-by-rows order of the split-operand 3x3/s1 layers (gated_conv_f4x1h_kernel, which runs them by default): LEAN carries it
+// behind the F(4x4) split operand of each such layer (both, so read_tuning_set("conv_f4x1", 0) still works on it); FULL is laid out
+// exactly as before — a host derives the order from FULL's direct fragments (exact weights) and hands it over as a side buffer
+// (read_unet_f4x1_layer / read_unet_set_f4x1).  LEAN_W4H is the lean layout without it: blobs packed before the kernel existed.
 Arch build_arch(int layout)
 {
-        const bool lean = layout == READ_UNET_LAYOUT_LEAN;
+        const bool lean = layout == READ_UNET_LAYOUT_LEAN || layout == READ_UNET_LAYOUT_LEAN_W4H;
+        const bool f4x1 = layout == READ_UNET_LAYOUT_LEAN;
         Arch a;
         auto add = [&](const std::string &path, int cin, int cout, int k, int s, int elu, int kc) {
             LayerInfo L{path, cin, cout, k, s, elu, kc, 0, NO_WINO, 0, NO_WINO, NO_WINO, NO_WINO};
@@ -112,6 +120,13 @@ Arch build_arch(int layout)
             if (w4h && !(lean && unused)) {
                 L.w4h_off = a.packed_floats;
                 a.packed_floats += read_conv_w4h_floats(cin, cout);
+                if (f4x1) {
+                    L.f4x1_off = a.packed_floats;
+                    a.packed_floats += read_conv_f4x1_floats(cin, cout);
+                } else if (!lean && !unused) {
+                    L.side_off = a.side_floats;
+                    a.side_floats += read_conv_f4x1_floats(cin, cout);
+                }
             }
             if (d3h && !(lean && (unused || !(fam || d3h_s2)))) {
                 L.d3h_off = a.packed_floats;
@@ -231,8 +246,8 @@ Arch build_arch(int layout)
 
 const Arch &arch(int layout = READ_UNET_LAYOUT_FULL)
 {
-    static const Arch A[2] = {build_arch(READ_UNET_LAYOUT_FULL), build_arch(READ_UNET_LAYOUT_LEAN)};
-    return A[layout == READ_UNET_LAYOUT_LEAN ? 1 : 0];
+    static const Arch A[3] = {build_arch(READ_UNET_LAYOUT_FULL), build_arch(READ_UNET_LAYOUT_LEAN), build_arch(READ_UNET_LAYOUT_LEAN_W4H)};
+    return A[layout >= 0 && layout < 3 ? layout : 0];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -247,6 +262,8 @@ struct Tensor {
 struct Op {
     enum Kind { CONV, UP4 } kind;
     read_conv_desc d;          // CONV
+    const void *wp_f4x1 = nullptr;   // CONV: the F(4,3)-by-rows order of the layer, beside the descriptor (its struct is frozen), or null
+    size_t side_off = ~(size_t)0;    // CONV, FULL layout: where that order lies in the side buffer of read_unet_set_f4x1
     int src_t[READ_CONV_MAX_SRC], mul_t, res_t, out_t;   // tensor ids (for external patching)
     int in_t;                  // UP4
     int pre_t = -1;            // CONV: tensor of the pre-activation addend
@@ -323,7 +340,7 @@ struct Builder {
     };
     struct LayerRef {
         int cin, cout, k, stride, elu;
-        size_t w_off, p_off, wino_off, w16_off, w4_off, sc_off, w4h_off = ~(size_t)0, d3h_off = ~(size_t)0, t3h_off = ~(size_t)0;
+        size_t w_off, p_off, wino_off, w16_off, w4_off, sc_off, w4h_off = ~(size_t)0, d3h_off = ~(size_t)0, t3h_off = ~(size_t)0, f4x1_off = ~(size_t)0, side_off = ~(size_t)0;
     };
 
     // One BasicConv.  srcs = {tensor id, shift}; out tensor must already exist.
@@ -332,7 +349,7 @@ struct Builder {
     {
         const Arch &A = arch(u->layout);
         const LayerInfo &L = A.layers[A.find(path)];
-        emit(path, LayerRef{L.cin, L.cout, L.k, L.stride, L.elu, L.w_off, L.p_off, L.wino_off, L.w16_off, L.w4_off, L.sc_off, L.w4h_off, L.d3h_off, L.t3h_off}, srcs, out_t, mul_t, res_t, 0,
+        emit(path, LayerRef{L.cin, L.cout, L.k, L.stride, L.elu, L.w_off, L.p_off, L.wino_off, L.w16_off, L.w4_off, L.sc_off, L.w4h_off, L.d3h_off, L.t3h_off, L.f4x1_off, L.side_off}, srcs, out_t, mul_t, res_t, 0,
              PreRef());
     }
     // A derived 1x1 layer (DerivedInfo): `linear` ones store the pre-activations [f | m] for a finer level to add,
@@ -385,6 +402,8 @@ struct Builder {
         op.d.wpacked_w4 = L.w4_off != NO_WINO ? u->packed + L.w4_off : nullptr;
         op.d.wpacked_sc = L.sc_off != NO_WINO ? u->packed + L.sc_off : nullptr;
         op.d.wpacked_w4h = L.w4h_off != NO_WINO ? u->packed + L.w4h_off : nullptr;
+        op.wp_f4x1 = L.f4x1_off != NO_WINO ? u->packed + L.f4x1_off : nullptr;
+        op.side_off = L.side_off;
         op.d.wpacked_d3h = L.d3h_off != NO_WINO ? u->packed + L.d3h_off : nullptr;
         op.d.wpacked_t3h = L.t3h_off != NO_WINO ? u->packed + L.t3h_off : nullptr;
         op.d.mul = mul_t >= 0 ? u->tensors[mul_t].p : nullptr;
@@ -619,7 +638,7 @@ int run(read_unet *u, const float *const ext[5], int rgb_cstride, hipStream_t s0
                 d.fill_pad = rgb_cstride > d.Cout;   // RGBA: alpha = 1 (READ/gl/nn.py:124)
                 d.out_fill = 1.0f;
             }
-            const int rc = launch_gated_conv(&d, s);
+            const int rc = launch_gated_conv(&d, s, op.wp_f4x1);
             if (rc != READ_OK) return rc;
         } else {
             const Tensor &I = u->tensors[op.in_t];
@@ -658,7 +677,7 @@ extern "C" size_t read_unet_raw_floats(void) { return arch().raw_floats; }
 extern "C" size_t read_unet_packed_floats(void) { return arch().packed_floats; }
 extern "C" size_t read_unet_packed_floats_layout(int layout)
 {
-    return (layout == READ_UNET_LAYOUT_FULL || layout == READ_UNET_LAYOUT_LEAN) ? arch(layout).packed_floats : 0;
+    return (layout >= READ_UNET_LAYOUT_FULL && layout <= READ_UNET_LAYOUT_LEAN_W4H) ? arch(layout).packed_floats : 0;
 }
 
 extern "C" int read_unet_pack_host(const float *raw, float bn_eps, float *packed)
@@ -669,7 +688,7 @@ extern "C" int read_unet_pack_host(const float *raw, float bn_eps, float *packed
 extern "C" int read_unet_pack_host_layout(const float *raw, float bn_eps, float *packed, int layout)
 {
     READ_CHECK_ARG(raw && packed, "read_unet_pack_host: null pointer");
-    READ_CHECK_ARG(layout == READ_UNET_LAYOUT_FULL || layout == READ_UNET_LAYOUT_LEAN, "read_unet_pack_host: unknown layout %d", layout);
+    READ_CHECK_ARG(layout >= READ_UNET_LAYOUT_FULL && layout <= READ_UNET_LAYOUT_LEAN_W4H, "read_unet_pack_host: unknown layout %d", layout);
     for (const LayerInfo &L : arch(layout).layers) {
         const size_t wn = (size_t)L.cout * L.cin * L.k * L.k;
         const float *wf = raw + L.raw_off, *bf = wf + wn, *wm = bf + L.cout, *bm = wm + wn;
@@ -696,6 +715,10 @@ extern "C" int read_unet_pack_host_layout(const float *raw, float bn_eps, float 
         }
         if (L.w4h_off != NO_WINO) {
             rc = read_conv_pack_w4h_host(L.cin, L.cout, wf, wm, packed + L.w4h_off);
+            if (rc) return rc;
+        }
+        if (L.f4x1_off != NO_WINO) {
+            rc = read_conv_pack_f4x1_host(L.cin, L.cout, wf, wm, packed + L.f4x1_off);
             if (rc) return rc;
         }
         if (L.d3h_off != NO_WINO) {
@@ -755,7 +778,7 @@ extern "C" int read_unet_create(read_unet_t **out, const float *packed, int H, i
 extern "C" int read_unet_create_layout(read_unet_t **out, const float *packed, int H, int W, void *ws, size_t ws_bytes, int layout)
 {
     READ_CHECK_ARG(out && packed && ws, "read_unet_create: null pointer");
-    READ_CHECK_ARG(layout == READ_UNET_LAYOUT_FULL || layout == READ_UNET_LAYOUT_LEAN, "read_unet_create: unknown layout %d", layout);
+    READ_CHECK_ARG(layout >= READ_UNET_LAYOUT_FULL && layout <= READ_UNET_LAYOUT_LEAN_W4H, "read_unet_create: unknown layout %d", layout);
     READ_CHECK_ARG((uintptr_t)packed % 16 == 0 && (uintptr_t)ws % 256 == 0, "read_unet_create: misaligned weights/workspace");
     int rc = check_hw(H, W);
     if (rc) return rc;
@@ -785,6 +808,37 @@ extern "C" int read_unet_create_layout(read_unet_t **out, const float *packed, i
         return READ_EINVAL;
     }
     *out = u;                     // (side streams are created on first use: the plan can be built without a device)
+    return READ_OK;
+}
+
+// The F(4,3)-by-rows orders of a FULL-layout plan.  The FULL blob is laid out as it always was and does not carry them; it does carry
+// every such layer's exact weights (the direct fragment order), so a host derives them once per blob: for j = 0, 1, ... until
+// read_unet_f4x1_layer returns non-zero, read_conv_unpack_weights_host(cin, cout, 3, 16, blob + w_off) -> read_conv_pack_f4x1_host
+// -> side + side_off; read_unet_f4x1_floats() floats in all.  read_unet_set_f4x1 hands the buffer (device memory that outlives the
+// handle) to a plan created from a FULL blob; without it the plan runs those layers on the F(4x4) split-operand kernel.
+extern "C" size_t read_unet_f4x1_floats(void) { return arch(READ_UNET_LAYOUT_FULL).side_floats; }
+
+extern "C" int read_unet_f4x1_layer(int j, size_t *w_off, size_t *side_off, int *cin, int *cout)
+{
+    if (j < 0 || !w_off || !side_off || !cin || !cout) return READ_EINVAL;
+    for (const LayerInfo &L : arch(READ_UNET_LAYOUT_FULL).layers)
+        if (L.side_off != NO_WINO && j-- == 0) {
+            *w_off = L.w_off;
+            *side_off = L.side_off;
+            *cin = L.cin;
+            *cout = L.cout;
+            return READ_OK;
+        }
+    return READ_EINVAL;                                             // past the last layer (no error text: this ends the enumeration)
+}
+
+extern "C" int read_unet_set_f4x1(read_unet_t *u, const float *side)
+{
+    READ_CHECK_ARG(u, "read_unet_set_f4x1: null handle");
+    READ_CHECK_ARG(u->layout == READ_UNET_LAYOUT_FULL, "read_unet_set_f4x1: only a plan of the FULL layout takes a side buffer (LEAN carries the order)");
+    READ_CHECK_ARG((uintptr_t)side % 16 == 0, "read_unet_set_f4x1: misaligned buffer");
+    for (Op &op : u->ops)
+        if (op.kind == Op::CONV && op.side_off != NO_WINO) op.wp_f4x1 = side ? side + op.side_off : nullptr;
     return READ_OK;
 }
 

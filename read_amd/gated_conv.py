@@ -34,7 +34,7 @@ class PackedGatedConv:
                                                 pp.ctypes.data), "read_conv_pack_params_host")
         self.wpacked = torch.from_numpy(wp).to(device)
         self.params = torch.from_numpy(pp).to(device)
-        self.wpacked_wino = self.wpacked_w16 = self.wpacked_w4 = self.wpacked_sc = self.wpacked_w4h = self.wpacked_d3h = self.wpacked_t3h = None
+        self.wpacked_wino = self.wpacked_w16 = self.wpacked_w4 = self.wpacked_sc = self.wpacked_w4h = self.wpacked_f4x1 = self.wpacked_d3h = self.wpacked_t3h = None
         if self.k == 3 and L.read_conv_t3h_floats(self.cin, self.cout):     # 8 - 32 input channels: the implicit-GEMM operand of the split-operand pixel-lane kernel
             t3 = np.empty(L.read_conv_t3h_floats(self.cin, self.cout), np.float32)
             _lib.check(L.read_conv_pack_t3h_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, t3.ctypes.data), "read_conv_pack_t3h_host")
@@ -63,6 +63,10 @@ class PackedGatedConv:
                     _lib.check(L.read_conv_pack_w4h_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, w4h.ctypes.data),
                                "read_conv_pack_w4h_host")
                     self.wpacked_w4h = torch.from_numpy(w4h).to(device)
+                    f4 = np.empty(L.read_conv_f4x1_floats(self.cin, self.cout), np.float32)   # ... and the F(4,3)-by-rows order of the same family
+                    _lib.check(L.read_conv_pack_f4x1_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, f4.ctypes.data),
+                               "read_conv_pack_f4x1_host")
+                    self.wpacked_f4x1 = torch.from_numpy(f4).to(device)
         if self.k in (1, 3, 4) and L.read_conv_dkh_floats(self.cin, self.cout, self.k):  # the plain weights as f16 piece pairs (direct split-operand kernels; 1x1: pixel-lane)
             dkh = np.empty(L.read_conv_dkh_floats(self.cin, self.cout, self.k), np.float32)
             _lib.check(L.read_conv_pack_dkh_host(self.cin, self.cout, self.k, wf.ctypes.data, wm.ctypes.data, dkh.ctypes.data),
@@ -73,6 +77,10 @@ class PackedGatedConv:
 def gated_conv(packed, sources, **kw):
     """One BasicConv launch (read_gated_conv_forward); arguments as conv_desc.  Returns the NHWC output (outH,outW,Cout)."""
     d, out = _desc(packed, sources, **kw)
+    f4 = getattr(packed, "wpacked_f4x1", None)
+    if f4 is not None:                 # the same launch with the F(4,3)-by-rows operand beside the descriptor (conv_f4x1 / config -12 decide)
+        _lib.check(_lib.lib().read_gated_conv_forward_f4x1(C.byref(d), f4.data_ptr(), _lib.stream_ptr()), "read_gated_conv_forward_f4x1")
+        return out
     _lib.check(_lib.lib().read_gated_conv_forward(C.byref(d), _lib.stream_ptr()), "read_gated_conv_forward")
     return out
 

@@ -53,7 +53,8 @@ def raw_blob_from_state(state):
     return blob
 
 
-LAYOUT_FULL, LAYOUT_LEAN = 0, 1      # READ_UNET_LAYOUT_*: every fragment order of every layer (952 MB) / what the default plan reads (451 MB)
+LAYOUT_FULL, LAYOUT_LEAN = 0, 1      # READ_UNET_LAYOUT_*: every fragment order of every layer / what the default plan reads
+LAYOUT_LEAN_W4H = 2                  # the lean layout without the F(4,3)-by-rows order: blobs packed before that kernel existed
 
 
 def default_layout():
@@ -66,7 +67,7 @@ def layout_of(packed):
     """The layout of a packed blob, read off its length."""
     L = _lib.lib()
     n = int(packed.numel() if torch.is_tensor(packed) else packed.size)
-    for layout in (LAYOUT_FULL, LAYOUT_LEAN):
+    for layout in (LAYOUT_FULL, LAYOUT_LEAN, LAYOUT_LEAN_W4H):
         if n == L.read_unet_packed_floats_layout(layout):
             return layout
     raise _lib.ReadHipError(f"a packed UNet blob has {L.read_unet_packed_floats_layout(LAYOUT_FULL)} (full) or "
@@ -79,6 +80,32 @@ def pack_state(state, eps=BN_EPS, layout=LAYOUT_FULL):
     packed = np.zeros(_lib.lib().read_unet_packed_floats_layout(layout), np.float32)     # zeros: the blob has alignment gaps
     _lib.check(_lib.lib().read_unet_pack_host_layout(raw.ctypes.data, eps, packed.ctypes.data, layout), "read_unet_pack_host")
     return packed
+
+
+def f4x1_side_buffer(packed_dev):
+    """The F(4,3)-by-rows orders of a FULL blob's split-operand 3x3/s1 layers (read_unet_set_f4x1): the full layout is laid out as it
+    always was and does not carry them, but it carries every layer's exact weights as direct fragments — unpacked and packed again on
+    the host, once per blob (kept on the tensor), bit for bit what the lean blob carries."""
+    side = getattr(packed_dev, "_read_f4x1_side", None)
+    if side is not None:
+        return side
+    L = _lib.lib()
+    host = np.zeros(L.read_unet_f4x1_floats(), np.float32)
+    w_off, s_off, cin, cout = C.c_size_t(), C.c_size_t(), C.c_int(), C.c_int()
+    j = 0
+    while L.read_unet_f4x1_layer(j, C.byref(w_off), C.byref(s_off), C.byref(cin), C.byref(cout)) == 0:
+        n = L.read_conv_packed_floats(cin.value, cout.value, 3)
+        frag = np.ascontiguousarray(packed_dev[w_off.value:w_off.value + n].cpu().numpy())
+        wf = np.zeros((cout.value, cin.value, 3, 3), np.float32)
+        wm = np.zeros_like(wf)
+        _lib.check(L.read_conv_unpack_weights_host(cin.value, cout.value, 3, 16, frag.ctypes.data, wf.ctypes.data, wm.ctypes.data),
+                   "read_conv_unpack_weights_host")
+        _lib.check(L.read_conv_pack_f4x1_host(cin.value, cout.value, wf.ctypes.data, wm.ctypes.data, host[s_off.value:].ctypes.data),
+                   "read_conv_pack_f4x1_host")
+        j += 1
+    side = torch.from_numpy(host).to(packed_dev.device)
+    packed_dev._read_f4x1_side = side
+    return side
 
 
 class UNetEngine:
@@ -96,6 +123,9 @@ class UNetEngine:
         _lib.check(L.read_unet_create_layout(C.byref(h), packed_dev.data_ptr(), H, W, self.ws.data_ptr(), need, layout_of(packed_dev)),
                    "read_unet_create")
         self.handle = h
+        if layout_of(packed_dev) == LAYOUT_FULL:      # the default plan's F(4,3)-by-rows kernel reads an order the full layout does not carry
+            self.f4x1 = f4x1_side_buffer(packed_dev)
+            _lib.check(L.read_unet_set_f4x1(h, self.f4x1.data_ptr()), "read_unet_set_f4x1")
 
     def __del__(self):
         try:

@@ -1,5 +1,6 @@
 """A/B of the F(4x4) kernels on the four dominant C->C shapes at 1216x352 (run on the GPU box): fp32 matrix cores (config -5)
-against split operands on the f16 matrix cores (config -7), both against the torch-fp32 oracle on the CPU.
+against split operands on the f16 matrix cores (config -7 F(4x4), -8 direct, -12 F(4,3) by rows), all against the torch-fp32
+oracle on the CPU.  --rounds N repeats the alternation of the kernels N times in the same process (keys "... #r").
 
     python tools/w4h_ab.py [--iters 20] [--check 1] [--out gpurun_out/r6_w4h_ab.json]
 """
@@ -24,6 +25,7 @@ def main():
     ap.add_argument("--check", type=int, default=1)
     ap.add_argument("--out", default="")
     ap.add_argument("--levels", default="0,1,2,3")
+    ap.add_argument("--rounds", type=int, default=1, help="times the kernels are alternated per level")
     ap.add_argument("--s2", type=int, default=0, help="1: the three 3x3 / stride-2 layers instead")
     ap.add_argument("--mul", type=int, default=0, help="1: the FAM form x1 + BC(x1 * x2) (the kernels' MUL variants)")
     ap.add_argument("--cfg", type=int, default=-7, help="kernel the probes run on: -7 the Winograd split-operand kernel, -8 the direct one")
@@ -80,8 +82,8 @@ def main():
                 ref = (unet_torch.basic_conv(st, "L", (xc * x2c if a.mul else xc)[None], 3, elu=True)[0] + rc).permute(1, 2, 0)
         from read_amd import _lib as _l
         dbg = bool(os.environ.get("READ_HIP_DEBUG"))                 # the specialised-wave kernel lives in the debug library only
-        for name, cfg in (("fp32", -5), ("f16x3", -7), ("d3h", -8)) + ((("f16x3w8", -7),) if dbg else ()):
-            if cfg == -7 and a.mul:
+        for rnd, (name, cfg) in [(r_, k_) for r_ in range(a.rounds) for k_ in (("fp32", -5), ("f16x3", -7), ("f4x1", -12), ("d3h", -8)) + ((("f16x3w8", -7),) if dbg else ())]:
+            if cfg in (-7, -12) and a.mul:
                 continue                                     # the Winograd split-operand kernel does not take FAM's multiply
             if dbg:
                 _l.check(_l.lib().read_tuning_set(b"conv_w4h_waves", 8 if name.endswith("w8") else 4))
@@ -102,7 +104,7 @@ def main():
                 rec["max_abs"] = float(d.abs().max())
                 rec["psnr_db"] = 10.0 * torch.log10(ref.abs().max().double() ** 2 / mse).item()
                 line += f"   max |diff| vs torch fp32 {rec['max_abs']:.3e}   {rec['psnr_db']:.1f} dB"
-            res[f"C{c} {name}"] = rec
+            res[f"C{c} {name}" + (f" #{rnd}" if a.rounds > 1 else "")] = rec
             print(line, flush=True)
         if a.abl:
             from read_amd import _lib
