@@ -342,7 +342,8 @@ typedef struct read_conv_desc {
                                                (FAM's mul included) then run as a DIRECT convolution on the f16 matrix cores — all nine
                                                taps, three piece pairs per product, fp32 accumulation: no Winograd transform on either
                                                side, fp32-level results (DESIGN.md 3.3 (a++)); inputs must stay below 65504 in magnitude;
-                                               config = -8 forces it where the shape fits.  Takes precedence over wpacked_w4h / wpacked_w4.
+                                               config = -8 forces it where the shape fits.  A launch it takes (those thresholds, or config = -8) does not look at
+                                               wpacked_w4h / wpacked_w4; every other launch of the family goes to them as if this field were NULL.
                                                For a 1x1 / stride-1 layer the same field takes read_conv_pack_dkh_host(Cin, Cout, 1, ...): launches
                                                (gated or linear, concatenated sources, residual, pre-activation addend) with Cin % 16 == 0,
                                                read_tuning("conv_pxh") (default 16, 0 = never) <= Cin <= 256, Cout % 4 == 0 and 16-byte aligned

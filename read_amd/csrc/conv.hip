@@ -20,6 +20,7 @@
 // A k-step of 8 is four MFMAs fed from ONE float4 per operand: lanes <32 carry cin 0..3 of the
 // 8-block, lanes >=32 carry cin 4..7 (the k order inside a step is free as long as A and B agree).
 #include "common.h"
+#include "internal.h"
 
 using namespace readhip;
 
@@ -4720,10 +4721,7 @@ struct ConvConfig {
      gated_conv_kernel<KS, S, KC, P, QG, WM, WN, false, PF, NB>,                                      \
      gated_conv_kernel<KS, S, KC, P, QG, WM, WN, true, PF, NB>}
 #define CFG(KS, S, KC, P, QG, WM, WN, PF) CFGN(KS, S, KC, P, QG, WM, WN, PF, 2)
-#define CFGM(KS, S, KC, P, QG, WM, WN, PF)                                                           \
-    {"k" #KS "s" #S "c" #KC "_p" #P "q" #QG "m" #WM "n" #WN "f" #PF "b2", KS, S, KC, P, QG, WM, WN, PF, 2, \
-     gated_conv_kernel<KS, S, KC, P, QG, WM, WN, false, PF, 2>,                                     \
-     gated_conv_kernel<KS, S, KC, P, QG, WM, WN, true, PF, 2>}
+#define CFGM(KS, S, KC, P, QG, WM, WN, PF) CFGNM(KS, S, KC, P, QG, WM, WN, PF, 2)
 
 #define CFGW(KS, S, KC, P, QG, PF, WGCU)                                                      \
     {"k" #KS "s" #S "c" #KC "_wave_p" #P "q" #QG "f" #PF, KS, S, KC, P, QG, 1, 1, PF, 1,        \
@@ -4796,6 +4794,23 @@ int find_config(int ks, int s, int kc, int P, int QG, int WM, int WN, int PF, in
     return -1;
 }
 
+// read_conv_desc.config below zero: the automatic choice, or a request for one kernel.  CFG_SC, CFG_PX, CFG_PXH, CFG_T3H and
+// CFG_F4X1 are refused where the kernel cannot run the launch; the others fall back to the automatic choice.
+enum ConvForce {
+    CFG_AUTO = -1,
+    CFG_PX = -2,         // fp32 pixel-lane kernel (1x1)
+    CFG_W16 = -3,        // wave-autonomous Winograd F(2x2,3x3)
+    CFG_W4 = -5,         // Winograd F(4x4,3x3), fp32
+    CFG_SC = -6,         // small-Cout vector-pipe kernel
+    CFG_W4H = -7,        // split-operand F(4x4,3x3)
+    CFG_D3H = -8,        // direct split-operand 3x3
+    CFG_D3H_S2 = -9,     // ... at stride 2
+    CFG_PXH = -10,       // split-operand pixel-lane kernel (1x1)
+    CFG_T3H = -11,       // ... as an implicit GEMM over a 3x3 layer with 8 - 32 input channels
+    CFG_F4X1 = -12,      // split-operand F(4,3) by rows
+};
+
+// Tuning knobs (the table g_knobs further down: key, normalisation, debug-only)
 int g_prefer_wave = 1;   // read_tuning_set("conv_wave", 0): workgroup-tiled kernels only
 int g_wino_wgs = 2;        // read_tuning_set("conv_wino_wgs", 1): one persistent Winograd workgroup per CU (A/B with frames in flight)
 int g_conv_px = 1;         // read_tuning_set("conv_px", v): pixel-lane kernel for 1x1 layers — 0 off; 1 / 2 where it measured faster
@@ -4803,31 +4818,32 @@ int g_conv_px = 1;         // read_tuning_set("conv_px", v): pixel-lane kernel f
 int g_kc32 = 1;            // 32-channel chunks for 1x1 layers whose sources are all multiples of 32 (read_tuning_set("conv_kc32", 0): 16)
 int g_use_wino = 1 << 30;  // read_tuning_set("conv_wino", max Cin): Winograd kernel for eligible 3x3 layers (0 = off)
 int g_w4_grid = 0;        // read_tuning_set("conv_w4_grid", 1): F(4x4) launches with the same number of units per workgroup (measured: see profiles)
-int g_w4x2 = 0;            // debug library only: read_tuning_set("conv_w4x2", 1) = the two-waves-per-SIMD F(4x4) kernel (measured slower, round 5)
 int g_w4 = 32;             // read_tuning_set("conv_w4", min Cin): layers with at least this many channels take the Winograd F(4x4,3x3)
 int g_w4h = 32;            // read_tuning_set("conv_w4h", min Cin): F(4x4) layers with Cin % 32 == 0 and at least this many channels take the split-operand
                            // kernel on the f16 matrix cores when its operand was supplied (0 = never: the fp32 kernel)
 int g_f4x1 = 32;           // read_tuning_set("conv_f4x1", min Cin): launches of the split-operand 3x3/s1 family with at least this many channels take the
                            // F(4,3)-by-rows kernel (gated_conv_f4x1h_kernel) when its operand was supplied (0 = never: the F(4x4) kernel).  Default 32: alternated with the F(4x4) kernel in one
                            // process it measured 6 - 11 % faster at every level (profiles/f4x1_ab.md)
-int g_w4h_waves = 4;       // debug library only: read_tuning_set("conv_w4h_waves", 8) = the split-operand kernel with specialised waves (measured slower, round 6)
 int g_d3h = 0;             // read_tuning_set("conv_d3h", min Cin): gated 3x3 / stride-1 layers with whole 32-channel chunks and at least this many channels take the
                            // DIRECT split-operand kernel (f16 matrix cores, all nine taps) when its operand was supplied.  Default 0 (never): on plain
-                           // launches it measured 5 - 15 % slower than the Winograd split-operand kernel (profiles/r6_d3h_ab.md) ...
+                           // launches it measured 5 - 15 % slower than the Winograd split-operand kernel (profiles/r6_d3h_ab.md)
+int g_d3h_fam = 32;        // read_tuning_set("conv_d3h_fam", min Cin): the same threshold for FAM's x1 * x2 launches, which the Winograd split-operand kernel
+                           // does not take: there the direct kernel measured 11 us FASTER per launch than the fp32 kernel, so those run on it (0 = never)
 int g_d3h_s2 = 32;         // read_tuning_set("conv_d3h_s2", min Cin): 3x3 / STRIDE-2 layers on the direct split-operand kernel (0 = never: the fp32 direct kernels)
-int g_d3h_fam = 32;        // read_tuning_set("conv_d3h_fam", min Cin): ... and 11 us FASTER per launch than the fp32 kernel on FAM's x1 * x2 launches, which the
-                           // Winograd split-operand kernel does not take: those run on it (0 = never)
 int g_pxh = 16;            // read_tuning_set("conv_pxh", min Cin): 1x1 / stride-1 layers with Cin % 16 == 0, Cin <= 256 and at least this many input channels take the
                            // split-operand pixel-lane kernel (f16 matrix cores) when their operand (wpacked_d3h of a 1x1 layer) was supplied (0 = never)
 int g_t3h = 8;             // read_tuning_set("conv_t3h", max Cin): 3x3 / stride-1 layers over one source of at most this many channels (8, 16 or 32) take the
                            // split-operand implicit-GEMM form of that kernel when wpacked_t3h was supplied (0 = never)
-int g_sc = 8;              // read_tuning_set("conv_sc", 0): the output layer (Cout <= 4) back on the F(2x2) MFMA kernel instead of the vector pipe; other values: conv_set_sc
-                           // kernel when its weights were supplied (0 = never)
-int g_abl = 0;             // read_tuning_set("conv_abl", bits): attribution probes of the 16x16x4 Winograd kernels (results invalid); -DREAD_DEBUG_KNOBS builds only
+int g_sc = 8;              // read_tuning_set("conv_sc", 0): the output layer (Cout <= 4) back on the F(2x2) MFMA kernel instead of the vector pipe; 8 / 16 / 32: input channels per LDS phase
 int g_w16 = 0;             // read_tuning_set("conv_w16", v): F(2x2,3x3) launches: 0 the row-per-wave kernel (default: measured equal or faster),
                            // 1 the wave-autonomous kernel with the shared input transform
 int g_stagger_ticks = 0;   // read_tuning_set("conv_stagger", ticks of 10 ns)
 int g_ablate = 0;          // read_tuning_set("conv_ablate", bits): attribution probe, results invalid; -DREAD_DEBUG_KNOBS builds only
+#ifdef READ_DEBUG_KNOBS
+int g_abl = 0;             // read_tuning_set("conv_abl", bits): attribution probes of the 16x16x4 Winograd kernels (results invalid); -DREAD_DEBUG_KNOBS builds only
+int g_w4x2 = 0;            // debug library only: read_tuning_set("conv_w4x2", 1) = the two-waves-per-SIMD F(4x4) kernel (measured slower, round 5)
+int g_w4h_waves = 4;       // debug library only: read_tuning_set("conv_w4h_waves", 8) = the split-operand kernel with specialised waves (measured slower, round 6)
+#endif
 
 int find_wave_config(int ks, int s, int kc, int P, int QG)
 {
@@ -4837,6 +4853,17 @@ int find_wave_config(int ks, int s, int kc, int P, int QG)
         if (c.wave && c.KS == ks && c.S == s && c.KC == kc && c.P == P && c.QG == QG) best = i;   // last = deepest prefetch
     }
     return best;
+}
+
+// First entry of the table that fits a layer, -1 where none does; tiled_only: no wave-autonomous and no Winograd entry (the linear
+// epilogue), with_mul: one that has the multiply variant
+int first_fit(int ks, int s, int kc, int groups, bool tiled_only = false, bool with_mul = false)
+{
+    for (int i = 0; i < N_CONFIGS; ++i) {
+        const ConvConfig &k = g_configs[i];
+        if (k.KS == ks && k.S == s && k.KC == kc && groups % (k.WN * k.QG) == 0 && !(tiled_only && (k.wave || k.wino)) && !(with_mul && !k.fn_mul)) return i;
+    }
+    return -1;
 }
 
 // Automatic choice = the measured-best entry per layer family on MI355X at 1216x352
@@ -4872,11 +4899,7 @@ int pick_config(int ks, int s, int kc, int groups, int outH, int outW)
         c = groups == 1 ? find_config(4, 2, 16, 1, 1, 4, 1, 1, 2) : find_config(4, 2, 16, 1, 1, 1, 1, 1, 2);
     }
     if (c >= 0 && groups % (g_configs[c].WN * g_configs[c].QG) == 0) return c;
-    for (int i = 0; i < N_CONFIGS; ++i) {
-        const ConvConfig &k = g_configs[i];
-        if (k.KS == ks && k.S == s && k.KC == kc && groups % (k.WN * k.QG) == 0) return i;
-    }
-    return -1;
+    return first_fit(ks, s, kc, groups);
 }
 
 int pad32(int c) { return (c + 31) / 32 * 32; }
@@ -5394,58 +5417,79 @@ extern "C" int read_conv_pack_params_host(int Cout, const float *bf, const float
 
 namespace readhip {
 
-void conv_set_prefer_wave(int v) { g_prefer_wave = v; }
-void conv_set_stagger(int ticks) { g_stagger_ticks = ticks < 0 ? 0 : ticks; }
-void conv_set_ablate(int bits) { g_ablate = bits; }
-void conv_set_wino(int max_cin) { g_use_wino = max_cin; }
-void conv_set_kc32(int v) { g_kc32 = v; }
-void conv_set_w16(int v) { g_w16 = v != 0; }
-void conv_set_abl(int v) { g_abl = v; }
-void conv_set_w4(int v) { g_w4 = v < 0 ? 0 : v; }
-void conv_set_w4h(int v) { g_w4h = v < 0 ? 0 : v; }
-void conv_set_f4x1(int v) { g_f4x1 = v < 0 ? 0 : v; }
-void conv_set_d3h(int v) { g_d3h = v < 0 ? 0 : v; }
-void conv_set_d3h_fam(int v) { g_d3h_fam = v < 0 ? 0 : v; }
-void conv_set_d3h_s2(int v) { g_d3h_s2 = v < 0 ? 0 : v; }
-void conv_set_pxh(int v) { g_pxh = v < 0 ? 0 : v; }
-void conv_set_t3h(int v) { g_t3h = v < 0 ? 0 : v; }
-void conv_set_w4h_waves(int v) { g_w4h_waves = v == 4 ? 4 : 8; }
-void conv_set_w4_grid(int v) { g_w4_grid = v != 0; }
-void conv_set_wino_wgs(int v) { g_wino_wgs = v <= 1 ? 1 : 2; }
-void conv_set_px(int v) { g_conv_px = v < 0 ? 0 : v > 4 ? 4 : v; }
-void conv_set_w4x2(int v) { g_w4x2 = v != 0; }
-void conv_set_sc(int v) { g_sc = v; }           // 0 off; 8 / 16 / 32 = input channels per LDS phase
+// ---- tuning knobs: one row per "conv_*" key.  read_tuning_set / read_tuning_get / read_tuning_key (api_common.cpp) go through
+// conv_set / conv_get / conv_key; the order of the rows is the order read_tuning_key enumerates them in.
+enum KnobNorm { KN_RAW, KN_NONNEG /* <0 -> 0 */, KN_BOOL /* != 0 */, KN_0_TO_4, KN_1_OR_2 /* <=1 -> 1, else 2 */, KN_4_OR_8 /* 4, else 8 */ };
+
+struct ConvKnob {
+    const char *key;
+    int *value;
+    KnobNorm norm;
+    bool debug_only;     // attribution probes (results invalid) and measured-slower kernels: rows of -DREAD_DEBUG_KNOBS builds only
+};
+
+const ConvKnob g_knobs[] = {
+    {"conv_kc32", &g_kc32, KN_RAW, false},
+    {"conv_px", &g_conv_px, KN_0_TO_4, false},           // pixel-lane kernel for 1x1 layers
+    {"conv_sc", &g_sc, KN_RAW, false},                   // vector-pipe kernel for Cout <= 4: 0 off; 8 / 16 / 32 = input channels per LDS phase
+    {"conv_wino_wgs", &g_wino_wgs, KN_1_OR_2, false},    // persistent Winograd workgroups per CU
+    {"conv_wino", &g_use_wino, KN_RAW, false},           // largest Cin on the Winograd kernel (0 = off)
+    {"conv_w16", &g_w16, KN_BOOL, false},                // wave-autonomous Winograd kernel (0 = row-per-wave)
+    {"conv_w4", &g_w4, KN_NONNEG, false},                // min Cin on the Winograd F(4x4,3x3) kernel (0 = off)
+    {"conv_w4h", &g_w4h, KN_NONNEG, false},              // min Cin on the split-operand F(4x4) kernel (f16 matrix cores; 0 = off)
+    {"conv_f4x1", &g_f4x1, KN_NONNEG, false},            // min Cin of that family's launches on the F(4,3)-by-rows kernel (0 = off)
+    {"conv_d3h", &g_d3h, KN_NONNEG, false},              // min Cin on the direct split-operand 3x3 kernel (f16 matrix cores; 0 = off)
+    {"conv_d3h_fam", &g_d3h_fam, KN_NONNEG, false},      // min Cin of FAM (x1 * x2) launches on the direct split-operand kernel (0 = off)
+    {"conv_d3h_s2", &g_d3h_s2, KN_NONNEG, false},        // min Cin of 3x3 / stride-2 layers on the direct split-operand kernel (0 = off)
+    {"conv_pxh", &g_pxh, KN_NONNEG, false},              // min Cin of 1x1 layers on the split-operand pixel-lane kernel (0 = off)
+    {"conv_t3h", &g_t3h, KN_NONNEG, false},              // max Cin of 3x3 layers on the split-operand implicit-GEMM kernel (0 = off)
+    {"conv_w4_grid", &g_w4_grid, KN_BOOL, false},        // F(4x4): equal units per workgroup
+    {"conv_stagger", &g_stagger_ticks, KN_NONNEG, false},
+    {"conv_wave", &g_prefer_wave, KN_BOOL, false},
+#ifdef READ_DEBUG_KNOBS
+    {"conv_ablate", &g_ablate, KN_RAW, true},
+    {"conv_abl", &g_abl, KN_RAW, true},                  // probes of the 16x16x4 Winograd kernels
+    {"conv_w4x2", &g_w4x2, KN_BOOL, true},               // the two-waves-per-SIMD F(4x4) kernel (measured slower)
+    {"conv_w4h_waves", &g_w4h_waves, KN_4_OR_8, true},   // 8: specialised waves (measured slower); 4: the product kernel
+#endif
+};
+
+static const ConvKnob *find_knob(const char *key)
+{
+    for (const ConvKnob &k : g_knobs)
+        if (!strcmp(key, k.key)) return &k;
+    return nullptr;
+}
+
+int conv_set(const char *key, int v)
+{
+    const ConvKnob *k = find_knob(key);
+    if (!k) return 0;
+    switch (k->norm) {
+    case KN_RAW: break;
+    case KN_NONNEG: v = v < 0 ? 0 : v; break;
+    case KN_BOOL: v = v != 0; break;
+    case KN_0_TO_4: v = v < 0 ? 0 : v > 4 ? 4 : v; break;
+    case KN_1_OR_2: v = v <= 1 ? 1 : 2; break;
+    case KN_4_OR_8: v = v == 4 ? 4 : 8; break;
+    }
+    *k->value = v;
+    return 1;
+}
+
 int conv_get(const char *key, int *value)
 {
-    if (!strcmp(key, "conv_wave")) *value = g_prefer_wave;
-    else if (!strcmp(key, "conv_stagger")) *value = g_stagger_ticks;
-    else if (!strcmp(key, "conv_kc32")) *value = g_kc32;
-    else if (!strcmp(key, "conv_px")) *value = g_conv_px;
-    else if (!strcmp(key, "conv_sc")) *value = g_sc;
-#ifdef READ_DEBUG_KNOBS
-    else if (!strcmp(key, "conv_w4x2")) *value = g_w4x2;
-#endif
-    else if (!strcmp(key, "conv_wino_wgs")) *value = g_wino_wgs;
-    else if (!strcmp(key, "conv_wino")) *value = g_use_wino;
-    else if (!strcmp(key, "conv_w16")) *value = g_w16;
-    else if (!strcmp(key, "conv_w4")) *value = g_w4;
-    else if (!strcmp(key, "conv_w4h")) *value = g_w4h;
-    else if (!strcmp(key, "conv_f4x1")) *value = g_f4x1;
-    else if (!strcmp(key, "conv_d3h")) *value = g_d3h;
-    else if (!strcmp(key, "conv_d3h_fam")) *value = g_d3h_fam;
-    else if (!strcmp(key, "conv_d3h_s2")) *value = g_d3h_s2;
-    else if (!strcmp(key, "conv_pxh")) *value = g_pxh;
-    else if (!strcmp(key, "conv_t3h")) *value = g_t3h;
-#ifdef READ_DEBUG_KNOBS
-    else if (!strcmp(key, "conv_w4h_waves")) *value = g_w4h_waves;
-#endif
-    else if (!strcmp(key, "conv_w4_grid")) *value = g_w4_grid;
-#ifdef READ_DEBUG_KNOBS
-    else if (!strcmp(key, "conv_ablate")) *value = g_ablate;
-    else if (!strcmp(key, "conv_abl")) *value = g_abl;
-#endif
-    else return 0;
-    return 1;
+    const ConvKnob *k = find_knob(key);
+    if (k) *value = *k->value;
+    return k != nullptr;
+}
+
+const char *conv_key(int i, bool debug_only)
+{
+    if (i < 0) return nullptr;
+    for (const ConvKnob &k : g_knobs)
+        if (k.debug_only == debug_only && i-- == 0) return k.key;
+    return nullptr;
 }
 
 static unsigned long long *g_trace = nullptr;
@@ -5456,19 +5500,224 @@ void conv_set_trace(void *buf, size_t bytes)
     g_trace_records = buf ? bytes / 64 : 0;
 }
 
-// Validates a descriptor, builds kernel arguments and launches.  Shared by the single-layer
-// entry point and the UNet executor.
-int conv_uses_wino(const read_conv_desc *d);
-int conv_uses_w4(const read_conv_desc *d);
-int conv_uses_w4h(const read_conv_desc *d);
-int conv_uses_f4x1(const read_conv_desc *d);
-int conv_uses_d3h(const read_conv_desc *d);
-int conv_uses_d3h_s2(const read_conv_desc *d);
-int conv_uses_sc(const read_conv_desc *d);
-int conv_uses_pxh(const read_conv_desc *d);
-int conv_uses_t3h(const read_conv_desc *d);
+// ---- routing: which kernel runs a descriptor under the current knobs.  conv_route is the only place that answers it; the
+// launch, the fragment-order checks, read_conv_kernel_family and the UNet plan (lean-blob check, profile column) all ask it.
 
-int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *wp_f4x1)
+// the automatic choice takes the Winograd kernel for every layer it can run (measured faster on all four levels)
+static int conv_uses_wino(const read_conv_desc *d)
+{
+    return d->config < 0 && g_use_wino && !d->pre && d->ksize == 3 && d->stride == 1 && d->n_src == 1 &&
+           d->src[0].shift == 0 && d->src[0].C % 16 == 0 && d->wpacked_wino && d->src[0].C <= g_use_wino;
+}
+
+// F(4x4,3x3): non-linear 3x3 / stride-1 launches with full 32-channel groups and at least conv_w4 input channels
+static int conv_uses_w4(const read_conv_desc *d)
+{
+    const bool shape = !d->pre && (!d->linear || !d->residual) && d->ksize == 3 && d->stride == 1 && d->n_src == 1 && d->src[0].shift == 0 &&
+                       d->src[0].C % 16 == 0 && d->src[0].C >= 32 && (d->Cout % 32 == 0 || (d->linear && d->Cout % 8 == 0)) && !d->fill_pad && d->wpacked_w4 &&
+                       d->out_cstride % 4 == 0 &&                                                     // 128-bit stores
+                       (long long)d->src[0].srcH * d->src[0].srcW * d->src[0].C * 4 < (1ll << 31) &&  // 32-bit buffer offsets
+                       (long long)d->inH * d->inW * d->out_cstride * 4 < (1ll << 31);
+    return shape && (d->config == CFG_W4 || (d->config == CFG_AUTO && g_w4 > 0 && d->src[0].C >= g_w4));
+}
+
+// the test of the F(4x4) family for a kernel that reads another operand of it (any non-null pointer): its shape and, for an
+// automatic launch of the Winograd split-operand kernels, the family's own threshold too (conv_w4)
+static int conv_w4_shape(const read_conv_desc *d, const void *operand, bool with_threshold = false)
+{
+    read_conv_desc t = *d;
+    if (!with_threshold) t.config = CFG_W4;
+    t.wpacked_w4 = reinterpret_cast<const float *>(operand);
+    return conv_uses_w4(&t);
+}
+
+// ... on the f16 matrix cores with split operands: the gated (non-linear) launches of that family with whole 32-channel chunks whose
+// split operand was supplied (the training path's linear launches stay on the fp32 kernel)
+static int conv_uses_w4h(const read_conv_desc *d)
+{
+    // (FAM's x1 * x2 stays on the fp32 kernel: the second patch costs the transform thread another 72 registers, and the
+    //  variant with a shallower weight ring measured SLOWER than the fp32 kernel — 101 / 79 / 68 us against 77 / 69 / 64 at C = 64 / 128 / 256)
+    if (!d->wpacked_w4h || d->linear || d->mul || d->src[0].C % 32 != 0 || d->Cout % 32 != 0) return 0;
+    const bool forced = d->config == CFG_W4H || d->config == CFG_F4X1;    // the F(4,3)-by-rows kernel belongs to the same family
+    if (!forced && (d->config != CFG_AUTO || g_w4h <= 0 || d->src[0].C < g_w4h)) return 0;
+    return conv_w4_shape(d, d->wpacked_w4h, !forced);
+}
+
+// the DIRECT split-operand kernel: the same launches (FAM's x1 * x2 included: a multiplication at staging time)
+static int conv_uses_d3h(const read_conv_desc *d)
+{
+    if (!d->wpacked_d3h || d->linear || d->src[0].C % 32 != 0 || d->Cout % 32 != 0) return 0;
+    const int min_c = d->mul ? g_d3h_fam : g_d3h;
+    if (!(d->config == CFG_D3H || (d->config == CFG_AUTO && min_c > 0 && d->src[0].C >= min_c))) return 0;
+    return conv_w4_shape(d, d->wpacked_d3h);
+}
+
+// ... and at stride 2 (the encoder's down-sampling layers): gated 3x3 / stride-2 single-source launches with whole 32-channel chunks in and
+// whole 64-channel pairs out, no multiplier / addend / fill
+static int conv_uses_d3h_s2(const read_conv_desc *d)
+{
+    const bool shape = d->wpacked_d3h && !d->linear && !d->mul && !d->pre && !d->fill_pad && (d->ksize == 3 || d->ksize == 4) && d->stride == 2 && d->n_src == 1 &&
+                       d->src[0].shift == 0 && d->src[0].C % 32 == 0 && d->Cout % 32 == 0 && d->out_cstride % 4 == 0 &&
+                       (long long)d->src[0].srcH * d->src[0].srcW * d->src[0].C * 4 < (1ll << 31) &&
+                       (long long)d->inH * d->inW * d->out_cstride * 4 < (1ll << 31);
+    return shape && (d->config == CFG_D3H_S2 || (d->config == CFG_AUTO && g_d3h_s2 > 0 && d->src[0].C >= g_d3h_s2));
+}
+
+// 1x1 / stride-1 layers on the split-operand pixel-lane kernel (gated or linear, any number of sources, residual, nearest pre-activation addend):
+// whole k16 steps, at most 64 KiB of weight fragments per group set, everything 16-byte aligned
+static int conv_uses_pxh(const read_conv_desc *d)
+{
+    if (!d->wpacked_d3h || d->ksize != 1 || d->stride != 1 || d->mul || d->fill_pad || d->n_src < 1 || d->n_src > READ_CONV_MAX_SRC) return 0;
+    if (d->pre && d->pre_bilinear) return 0;                          // the bilinear addend (an option of the plan, off) stays on the fp32 pixel-lane kernel
+    int Cin = 0;
+    for (int i = 0; i < d->n_src; ++i) {
+        if (d->src[i].C < 8 || d->src[i].C % 8 != 0 || (uintptr_t)d->src[i].data % 16 != 0) return 0;
+        Cin += d->src[i].C;
+    }
+    const bool shape = Cin % 16 == 0 && Cin <= 256 && d->Cout % 4 == 0 && d->out_cstride % 4 == 0 && (uintptr_t)d->out % 16 == 0 &&
+                       (uintptr_t)d->params % 16 == 0 && (!d->residual || (uintptr_t)d->residual % 16 == 0) &&
+                       (!d->pre || ((uintptr_t)d->pre % 16 == 0 && d->pre_cstride % 4 == 0 && d->pre_f_off % 4 == 0 && d->pre_m_off % 4 == 0));
+    return shape && (d->config == CFG_PXH || (d->config == CFG_AUTO && g_pxh > 0 && Cin >= g_pxh));
+}
+
+// 3x3 / stride-1 layers over one unshifted source of 8, 16 or 32 channels as an implicit GEMM on the same kernel (k = tap C + channel;
+// read_conv_pack_t3h_host): the layers that read the 8-channel descriptor pyramid by default
+static int conv_uses_t3h(const read_conv_desc *d)
+{
+    if (!d->wpacked_t3h || d->ksize != 3 || d->stride != 1 || d->mul || d->fill_pad || d->pre || d->n_src != 1 || d->src[0].shift != 0) return 0;
+    const int C = d->src[0].C;
+    const bool shape = (C == 8 || C == 16 || C == 32) && d->Cout % 4 == 0 && d->out_cstride % 4 == 0 && (uintptr_t)d->out % 16 == 0 &&
+                       (uintptr_t)d->src[0].data % 16 == 0 && (uintptr_t)d->params % 16 == 0 && (!d->residual || (uintptr_t)d->residual % 16 == 0) &&
+                       (long long)d->inH * d->inW * C * 4 < (1ll << 31);
+    // (automatic choice from 16 K pixels on: at 44 x 152 the fp32 direct kernel measured 11.5 us against 14.2)
+    return shape && (d->config == CFG_T3H || (d->config == CFG_AUTO && g_t3h > 0 && C <= g_t3h && (long long)d->inH * d->inW >= 16384));
+}
+
+// gated 3x3 / stride-1 layers with at most four output channels and 32 input channels (READ's output layer)
+static int conv_uses_sc(const read_conv_desc *d)
+{
+    const bool shape = d->ksize == 3 && d->stride == 1 && d->n_src == 1 && d->src[0].shift == 0 && d->src[0].C == 32 && d->Cout >= 1 &&
+                       d->Cout <= 4 && !d->linear && !d->residual && !d->pre && !d->mul && d->wpacked_sc &&
+                       (d->out_cstride != 4 || (uintptr_t)d->out % 16 == 0) &&
+                       (long long)d->src[0].srcH * d->src[0].srcW * d->src[0].C * 4 < (1ll << 31);
+    return shape && (d->config == CFG_SC || (d->config == CFG_AUTO && g_sc));
+}
+
+static bool conv_sane(const read_conv_desc *d)
+{
+    return d->n_src >= 1 && d->n_src <= READ_CONV_MAX_SRC && (d->ksize == 1 || d->ksize == 3 || d->ksize == 4) && (d->stride == 1 || d->stride == 2);
+}
+
+// 1x1 / stride-1 layers on the fp32 pixel-lane kernel: whenever the layer qualifies and the kernel measured faster, or the addend is bilinear
+static int conv_uses_px(const read_conv_desc *d)
+{
+    if (!conv_sane(d)) return 0;
+    int Cin = 0;
+    // Measured per layer at 1216x352 (profiles/README.md): the pixel-lane kernel wins where the LDS-tiled kernels fall to
+    // 8-channel chunks (SCM tails, cat[x(8), main]) or pad the last channel group (Cout = 56 / 120 / 248), 3-7 us per
+    // layer; on the other 1x1 layers it is level or up to 10 us slower (its four 32-byte segments per pixel line
+    // arrive as separate instructions) — conv_px = 1 takes it only for the former, 3 / 4 for every layer it fits.
+    bool px_pick = d->Cout % 32 != 0 || g_conv_px >= 3;
+    for (int i = 0; i < d->n_src; ++i) {
+        Cin += d->src[i].C;
+        px_pick = px_pick || d->src[i].C % 16 != 0;
+    }
+    const bool fits = d->ksize == 1 && d->stride == 1 && !d->mul && !d->fill_pad && d->Cout % 4 == 0 && d->out_cstride % 4 == 0 &&
+                      (uintptr_t)d->out % 16 == 0 && (uintptr_t)d->params % 16 == 0 && Cin / 8 <= 32 &&
+                      (!d->residual || (uintptr_t)d->residual % 16 == 0) &&
+                      (!d->pre || ((uintptr_t)d->pre % 16 == 0 && d->pre_cstride % 4 == 0 && d->pre_f_off % 4 == 0 && d->pre_m_off % 4 == 0));
+    const bool bil = d->pre && d->pre_bilinear;                    // only this kernel samples the addend bilinearly
+    return fits && (d->config == CFG_PX || (bil && d->config < 0) || (d->config == CFG_AUTO && g_conv_px && px_pick));
+}
+
+// sizes every launcher derives from the descriptor (conv_sane descriptors only)
+struct ConvShape {
+    int Cin, kc;             // input channels of all sources; channel chunk of the tile-table kernels (8, 16 or 32)
+    int outH, outW, CoutPad, groups;
+};
+
+static ConvShape conv_shape(const read_conv_desc *d)
+{
+    ConvShape s;
+    s.Cin = 0;
+    s.kc = 16;
+    bool all32 = d->ksize == 1;
+    for (int i = 0; i < d->n_src; ++i) {
+        s.Cin += d->src[i].C;
+        if (d->src[i].C % 16) s.kc = 8;
+        all32 = all32 && d->src[i].C % 32 == 0;
+    }
+    // 1x1 layers whose sources are all multiples of 32 channels run 32-channel chunks (weights packed with kc = 32)
+    if (all32 && (d->config >= 0 ? (d->config < N_CONFIGS && g_configs[d->config].KC == 32) : g_kc32 != 0)) s.kc = 32;
+    const int pad = (d->ksize - 1) / 2;
+    s.outH = (d->inH + 2 * pad - d->ksize) / d->stride + 1;
+    s.outW = (d->inW + 2 * pad - d->ksize) / d->stride + 1;
+    s.CoutPad = pad32(d->Cout);
+    s.groups = s.CoutPad / 32;
+    return s;
+}
+
+enum ConvKernel { CK_SC, CK_T3H, CK_PXH, CK_PX, CK_D3H_S2, CK_D3H, CK_F4X1, CK_W4H, CK_W4, CK_TABLE };
+
+struct ConvRoute {
+    ConvKernel kernel;
+    // CK_TABLE only:
+    int cfg;             // entry of g_configs (a forced index as it stands), -1 where nothing fits: the launch is refused
+    bool wino_auto;      // the automatic choice took the table's Winograd F(2x2) entry (family 2)
+    bool w16;            // ... and runs it as the wave-autonomous kernel (unless the debug timeline records the launch)
+};
+
+// Precedence = the order of the tests.  wp_f4x1: the F(4,3)-by-rows operand that travels beside the descriptor, or NULL.
+static ConvRoute conv_route(const read_conv_desc *d, const void *wp_f4x1)
+{
+    ConvRoute r = {CK_TABLE, -1, false, false};
+    if (conv_uses_sc(d)) r.kernel = CK_SC;
+    else if (conv_uses_t3h(d)) r.kernel = CK_T3H;
+    else if (conv_uses_pxh(d)) r.kernel = CK_PXH;
+    else if (conv_uses_px(d)) r.kernel = CK_PX;
+    else if (conv_uses_d3h_s2(d)) r.kernel = CK_D3H_S2;
+    else if (conv_uses_d3h(d)) r.kernel = CK_D3H;
+    // ... of that family's launches, those with at least conv_f4x1 input channels take the F(4,3)-by-rows kernel (both report family 5); a
+    // caller without its operand (a blob packed before the kernel existed) keeps running on the F(4x4) kernel
+    else if (conv_uses_w4h(d))
+        r.kernel = wp_f4x1 && (d->config == CFG_F4X1 || (d->config == CFG_AUTO && g_f4x1 > 0 && d->src[0].C >= g_f4x1)) ? CK_F4X1 : CK_W4H;
+    else if (conv_uses_w4(d)) r.kernel = CK_W4;
+    else if (conv_sane(d)) {
+        const ConvShape s = conv_shape(d);
+        r.cfg = d->config;
+        r.wino_auto = conv_uses_wino(d);
+        for (int i = N_CONFIGS - 1; r.wino_auto && i >= 0; --i)
+            if (g_configs[i].wino) r.cfg = i;     // first Winograd entry = the product kernel
+        // linear launches: the plain-convolution epilogue exists in the workgroup-tiled kernels and in the Winograd kernel
+        if (d->linear && r.cfg < 0) r.cfg = first_fit(d->ksize, d->stride, s.kc, s.groups, true, d->mul != nullptr);
+        if (r.cfg < 0) r.cfg = pick_config(d->ksize, d->stride, s.kc, s.groups, s.outH, s.outW);
+        if (d->config < 0 && d->mul && r.cfg >= 0 && !g_configs[r.cfg].fn_mul) {
+            const int m = first_fit(d->ksize, d->stride, s.kc, s.groups, false, true);
+            if (m >= 0) r.cfg = m;
+        }
+        // the wave-autonomous Winograd kernel (same units, same grid) whenever its weight order was supplied; linear launches
+        // (training path) stay on the row-per-wave kernel, which carries the plain-convolution epilogue
+        // ... and, by default, for layers whose last channel group is mostly padding (the 32 -> 3 output layer): its waves without a real
+        // channel skip their MFMAs, the row-per-wave kernel pays for all 32 padded channels
+        const bool mostly_padding = d->Cout <= 8;
+        r.w16 = r.cfg >= 0 && r.cfg < N_CONFIGS && g_configs[r.cfg].wino && !d->linear && d->wpacked_w16 &&
+                (d->config == CFG_W16 || (d->config < 0 && (g_w16 || mostly_padding)));
+    }
+    return r;
+}
+
+// the public family number (read_conv_kernel_family) of a route; the table's Winograd F(2x2) entry reports 2 where the automatic choice took it
+static int route_family(const ConvRoute &r)
+{
+    static const int family[] = {/* CK_SC */ 1, /* CK_T3H */ 8, /* CK_PXH */ 7, /* CK_PX */ 0, /* CK_D3H_S2 */ 6, /* CK_D3H */ 6,
+                                 /* CK_F4X1 */ 5, /* CK_W4H */ 5, /* CK_W4 */ 4, /* CK_TABLE */ 0};
+    return r.wino_auto ? 2 : family[r.kernel];
+}
+
+int conv_family(const read_conv_desc *d) { return route_family(conv_route(d, nullptr)); }
+
+// ---- launch: validate and fill the shared arguments, then one launcher per kernel group
+static int conv_prepare(const read_conv_desc *d, const void *wp_f4x1, ConvKArgs &a, ConvShape &s, ConvRoute &r)
 {
     READ_CHECK_ARG(d, "read_gated_conv_forward: null descriptor");
     READ_CHECK_ARG(d->n_src >= 1 && d->n_src <= READ_CONV_MAX_SRC, "read_gated_conv_forward: n_src must be 1..%d",
@@ -5481,15 +5730,16 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
     READ_CHECK_ARG(!d->linear || (!d->residual && !d->fill_pad), "read_gated_conv_forward: linear mode takes no residual / fill");
     READ_CHECK_ARG(!d->mul || d->n_src == 1, "read_gated_conv_forward: mul needs a single source");
     READ_CHECK_ARG((uintptr_t)d->wpacked % 16 == 0, "read_gated_conv_forward: packed weights misaligned");
+    r = conv_route(d, wp_f4x1);
+    s = conv_shape(d);
     {
         // One fragment order per layer is enough for a host that asked read_conv_kernel_family first; a host that aliases
         // wpacked to its Winograd fragments (training: read_amd/train.py packs ONE order per layer and step) or leaves it NULL
         // (the lean UNet blob) must never reach a kernel that reads wpacked as the direct order — a tuning knob changed on a
         // live engine, a 2 GiB tensor or an odd out_cstride can decline the Winograd kernels after the host has packed for them.
-        // Checked HERE, for both entry points (read_gated_conv_forward and the UNet executor's direct call).
-        const int family = conv_uses_sc(d) ? 1 : conv_uses_t3h(d) ? 8 : conv_uses_pxh(d) ? 7 : (conv_uses_d3h(d) || conv_uses_d3h_s2(d)) ? 6 : conv_uses_w4h(d) ? 5 : conv_uses_w4(d) ? 4 : conv_uses_wino(d) ? 2 : 0;
+        const int family = route_family(r);
         const bool cfg_wino = d->config >= 0 && d->config < N_CONFIGS && g_configs[d->config].wino;   // forced F(2x2) configs read wpacked_wino
-        const bool w16_forced = d->config == -3;
+        const bool w16_forced = d->config == CFG_W16;
         READ_CHECK_ARG(d->wpacked || family != 0 || cfg_wino || w16_forced,
                        "read_gated_conv_forward: this launch takes a direct kernel and wpacked is NULL (fragment order not packed)");
         READ_CHECK_ARG(!d->wpacked || (!((const void *)d->wpacked == (const void *)d->wpacked_w4 && family != 4 && family != 5 && family != 6 && family != 7 && family != 8) &&
@@ -5501,51 +5751,31 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
         READ_CHECK_ARG(family != 1 || d->wpacked_sc, "read_gated_conv_forward: small-Cout launch without wpacked_sc");
     }
 
-    ConvKArgs a;
     memset(&a, 0, sizeof(a));
-    int Cin = 0, kc = 16;
     for (int i = 0; i < d->n_src; ++i) {
-        const read_conv_src &s = d->src[i];
-        READ_CHECK_ARG(s.data && (uintptr_t)s.data % 16 == 0, "read_gated_conv_forward: source %d null or misaligned", i);
-        READ_CHECK_ARG(s.C >= 8 && s.C % 8 == 0, "read_gated_conv_forward: source %d has C=%d (need a multiple of 8)", i, s.C);
-        READ_CHECK_ARG(s.shift >= -4 && s.shift <= 4, "read_gated_conv_forward: shift out of range");
-        READ_CHECK_ARG((long long)s.srcH * s.srcW * s.C < (1ll << 31), "read_gated_conv_forward: source too large");
-        const int needH = s.shift >= 0 ? ((d->inH - 1) << s.shift) + 1 : ((d->inH - 1) >> -s.shift) + 1;
-        const int needW = s.shift >= 0 ? ((d->inW - 1) << s.shift) + 1 : ((d->inW - 1) >> -s.shift) + 1;
-        READ_CHECK_ARG(s.srcH >= needH && s.srcW >= needW, "read_gated_conv_forward: source %d (%dx%d) too small for %dx%d at shift %d",
-                       i, s.srcH, s.srcW, d->inH, d->inW, s.shift);
-        if (s.C % 16) kc = 8;
-        Cin += s.C;
-        a.src[i].p = s.data;
-        a.src[i].C = s.C;
-        a.src[i].H = s.srcH;
-        a.src[i].W = s.srcW;
-        a.src[i].sl = s.shift > 0 ? s.shift : 0;
-        a.src[i].sr = s.shift < 0 ? -s.shift : 0;
+        const read_conv_src &src = d->src[i];
+        READ_CHECK_ARG(src.data && (uintptr_t)src.data % 16 == 0, "read_gated_conv_forward: source %d null or misaligned", i);
+        READ_CHECK_ARG(src.C >= 8 && src.C % 8 == 0, "read_gated_conv_forward: source %d has C=%d (need a multiple of 8)", i, src.C);
+        READ_CHECK_ARG(src.shift >= -4 && src.shift <= 4, "read_gated_conv_forward: shift out of range");
+        READ_CHECK_ARG((long long)src.srcH * src.srcW * src.C < (1ll << 31), "read_gated_conv_forward: source too large");
+        const int needH = src.shift >= 0 ? ((d->inH - 1) << src.shift) + 1 : ((d->inH - 1) >> -src.shift) + 1;
+        const int needW = src.shift >= 0 ? ((d->inW - 1) << src.shift) + 1 : ((d->inW - 1) >> -src.shift) + 1;
+        READ_CHECK_ARG(src.srcH >= needH && src.srcW >= needW, "read_gated_conv_forward: source %d (%dx%d) too small for %dx%d at shift %d",
+                       i, src.srcH, src.srcW, d->inH, d->inW, src.shift);
+        a.src[i] = SrcDev{src.data, src.C, src.srcH, src.srcW, src.shift > 0 ? src.shift : 0, src.shift < 0 ? -src.shift : 0};
     }
     READ_CHECK_ARG(!d->mul || d->src[0].shift == 0, "read_gated_conv_forward: mul needs shift 0");
-    {   // 1x1 layers whose sources are all multiples of 32 channels run 32-channel chunks (weights packed with kc = 32)
-        bool all32 = d->ksize == 1;
-        for (int i = 0; i < d->n_src; ++i) all32 = all32 && d->src[i].C % 32 == 0;
-        if (all32 && (d->config >= 0 ? (d->config < N_CONFIGS && g_configs[d->config].KC == 32) : g_kc32 != 0)) kc = 32;
-    }
-    const int nchunks = Cin / kc;
     a.n_src = d->n_src;
-    const int pad = (d->ksize - 1) / 2;
-    const int outH = (d->inH + 2 * pad - d->ksize) / d->stride + 1;
-    const int outW = (d->inW + 2 * pad - d->ksize) / d->stride + 1;
-    READ_CHECK_ARG(outH >= 1 && outW >= 1, "read_gated_conv_forward: empty output");
-    READ_CHECK_ARG((long long)outH * outW * d->out_cstride * 4 < OOB_LIMIT, "read_gated_conv_forward: output too large");
-    const int CoutPad = pad32(d->Cout), groups = CoutPad / 32;
-    int cfg = d->config;
+    READ_CHECK_ARG(s.outH >= 1 && s.outW >= 1, "read_gated_conv_forward: empty output");
+    READ_CHECK_ARG((long long)s.outH * s.outW * d->out_cstride * 4 < OOB_LIMIT, "read_gated_conv_forward: output too large");
     if (d->pre) {
         READ_CHECK_ARG((uintptr_t)d->pre % 4 == 0 && d->pre_shift >= 0 && d->pre_shift <= 4 && d->pre_f_off >= 0 && d->pre_m_off >= 0 &&
                            d->pre_cstride >= d->pre_f_off + d->Cout && d->pre_cstride >= d->pre_m_off + d->Cout,
                        "read_gated_conv_forward: bad pre-activation addend layout");
-        READ_CHECK_ARG(d->preH >= ((outH - 1) >> d->pre_shift) + 1 && d->preW >= ((outW - 1) >> d->pre_shift) + 1 &&
+        READ_CHECK_ARG(d->preH >= ((s.outH - 1) >> d->pre_shift) + 1 && d->preW >= ((s.outW - 1) >> d->pre_shift) + 1 &&
                            (long long)d->preH * d->preW * d->pre_cstride * 4 < OOB_LIMIT,
                        "read_gated_conv_forward: pre-activation addend %dx%d does not cover the %dx%d output at shift %d", d->preH,
-                       d->preW, outH, outW, d->pre_shift);
+                       d->preW, s.outH, s.outW, d->pre_shift);
         READ_CHECK_ARG(!d->pre_bilinear || (d->pre_shift == 2 && d->ksize == 1 && d->stride == 1),
                        "read_gated_conv_forward: pre_bilinear needs pre_shift 2 on a 1x1 / stride-1 layer");
         a.pre = d->pre;
@@ -5563,15 +5793,16 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
     a.wp_wino = d->wpacked_wino;
     a.wp_w16 = d->wpacked_w16;
     a.wp_w4 = d->wpacked_w4;
+    a.wp_sc = d->wpacked_sc;
     a.params = d->params;
     a.residual = d->residual;
     a.out = d->out;
     a.inH = d->inH;
     a.inW = d->inW;
-    a.outH = outH;
-    a.outW = outW;
+    a.outH = s.outH;
+    a.outW = s.outW;
     a.Cout = d->Cout;
-    a.CoutPad = CoutPad;
+    a.CoutPad = s.CoutPad;
     a.out_cstride = d->out_cstride;
     a.elu = d->elu;
     a.linear = d->linear;
@@ -5579,390 +5810,285 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
     a.fill_pad = d->fill_pad;
     a.out_fill = d->out_fill;
 
-    // ---- at most four output channels, 3x3 / stride 1: the vector-pipe kernel (config -6 forces it)
-    a.wp_sc = d->wpacked_sc;
-    READ_CHECK_ARG(d->config != -6 || conv_uses_sc(d), "read_gated_conv_forward: the small-Cout kernel takes gated 3x3/s1 layers with "
+    // a forced config names a kernel: the launch is refused where the route did not take it (CFG_W16, CFG_W4, CFG_W4H, CFG_D3H and
+    // CFG_D3H_S2 fall back to the automatic choice instead; CFG_F4X1 is checked by its family's launcher and by launch_table)
+    READ_CHECK_ARG(d->config != CFG_SC || r.kernel == CK_SC, "read_gated_conv_forward: the small-Cout kernel takes gated 3x3/s1 layers with "
                    "Cin = 32, Cout <= 4, one unshifted source and wpacked_sc");
-    if (conv_uses_sc(d)) {
-        READ_CHECK_ARG((uintptr_t)d->wpacked_sc % 64 == 0 && (uintptr_t)d->src[0].data % 16 == 0, "read_gated_conv_forward: wpacked_sc / source misaligned");
-        a.tiles_x = ceil_div(outW, 32);
-        const int cph = g_sc & 63;                                 // knob: channels per LDS phase
-        const dim3 grid((unsigned)(a.tiles_x * ceil_div(outH, 8)));
-        const bool c3 = d->Cout <= 3;
-#define SC_LAUNCH(CPH, PPT) \
-        do { if (c3) hipLaunchKernelGGL((gated_conv_smallc_kernel<32, CPH, PPT, 3>), grid, dim3(256), 0, stream, a); \
-             else hipLaunchKernelGGL((gated_conv_smallc_kernel<32, CPH, PPT, 4>), grid, dim3(256), 0, stream, a); } while (0)
-        if (cph == 32) SC_LAUNCH(32, 1);
-        else if (cph == 16) SC_LAUNCH(16, 1);
-        else SC_LAUNCH(8, 1);
-#undef SC_LAUNCH
-        READ_CHECK_LAUNCH();
-        return READ_OK;
-    }
-
-    // ---- 1x1 layers on the f16 matrix cores: the split-operand pixel-lane kernel (config -10 forces it)
-    READ_CHECK_ARG(d->config != -10 || conv_uses_pxh(d), "read_gated_conv_forward: the split-operand pixel-lane kernel takes 1x1/s1 layers with "
+    READ_CHECK_ARG(d->config != CFG_PXH || r.kernel == CK_PXH, "read_gated_conv_forward: the split-operand pixel-lane kernel takes 1x1/s1 layers with "
                    "Cin %% 16 == 0, Cin <= 256, Cout %% 4 == 0, 16-byte aligned tensors and wpacked_d3h");
-    READ_CHECK_ARG(d->config != -11 || conv_uses_t3h(d), "read_gated_conv_forward: the split-operand implicit-GEMM kernel takes 3x3/s1 layers over one "
+    READ_CHECK_ARG(d->config != CFG_T3H || r.kernel == CK_T3H, "read_gated_conv_forward: the split-operand implicit-GEMM kernel takes 3x3/s1 layers over one "
                    "unshifted source of 8, 16 or 32 channels with Cout %% 4 == 0, 16-byte aligned tensors and wpacked_t3h");
-    const bool taps = conv_uses_t3h(d);
-    if (taps || conv_uses_pxh(d)) {
-        READ_CHECK_ARG((uintptr_t)(taps ? d->wpacked_t3h : d->wpacked_d3h) % 16 == 0, "read_gated_conv_forward: wpacked_d3h / wpacked_t3h misaligned");
-        static int n_cu_h = 0;
-        if (!n_cu_h) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            n_cu_h = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                      prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
-        a.wp_d3h = taps ? d->wpacked_t3h : d->wpacked_d3h;
-        const int nsteps = taps ? (9 * Cin + 15) / 16 : Cin / 16;
-        if (taps) a.tiles_y = Cin == 8 ? 3 : Cin == 16 ? 4 : 5;     // log2 of the source's channels
-        const int gw = (groups % 2 == 0 && nsteps <= 8) ? 2 : 1;
-        const size_t lds = (size_t)nsteps * 2 * gw * 2048 + 6 * 32 * gw * sizeof(float);     // <= 64 KiB of fragments + parameters: two workgroups per CU
-        const int gsets = groups / gw;
-        const int per_cu = lds > 78 * 1024 ? 1 : 2;
-        // two pixel tiles per wave as soon as one tile per wave would need a second round of units: a wave's time per unit is the
-        // latency of its activation stream (ring of four steps), the same for one tile or two
-        const long slots = (long)n_cu_h * per_cu / gsets * 4;
-        const int pt = gw == 2 ? 1 : ((long)ceil_div(outH * outW, 32) > (slots > 0 ? slots : 1) ? 2 : 1);
-        a.nchunks = nsteps;
-        a.n_units = ceil_div(outH * outW, 32 * pt);
-        int per_set = (n_cu_h * per_cu) / gsets;
-        const int want = ceil_div(a.n_units, 4);
-        per_set = per_set < 1 ? 1 : per_set;
-        per_set = per_set < want ? per_set : want;
-        per_set = (per_set + 7) / 8 * 8;                             // the kernel's XCD-aware workgroup map
-        const bool fullq = nsteps % 4 == 0;
-        bool uni = true;
-        for (int i = 0; i < d->n_src; ++i) uni = uni && d->src[i].C % 16 == 0;
-        const int shape = gw == 2 ? 0 : pt == 2 ? 1 : 2, vi = taps ? 12 + shape : shape * 4 + (fullq ? 2 : 0) + (uni ? 1 : 0);
-        static const conv_fn fns[15] = {
-            gated_conv_pxh_kernel<1, 2, false, 0>, gated_conv_pxh_kernel<1, 2, false, 1>, gated_conv_pxh_kernel<1, 2, true, 0>, gated_conv_pxh_kernel<1, 2, true, 1>,
-            gated_conv_pxh_kernel<2, 1, false, 0>, gated_conv_pxh_kernel<2, 1, false, 1>, gated_conv_pxh_kernel<2, 1, true, 0>, gated_conv_pxh_kernel<2, 1, true, 1>,
-            gated_conv_pxh_kernel<1, 1, false, 0>, gated_conv_pxh_kernel<1, 1, false, 1>, gated_conv_pxh_kernel<1, 1, true, 0>, gated_conv_pxh_kernel<1, 1, true, 1>,
-            gated_conv_pxh_kernel<1, 2, false, 2>, gated_conv_pxh_kernel<2, 1, false, 2>, gated_conv_pxh_kernel<1, 1, false, 2>};
-        static bool attr_set_h[15] = {false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};
-        if (!attr_set_h[vi]) {                                       // 64 KiB of dynamic LDS at Cin = 256 (74 KiB: 3x3 over 32 channels)
-            READ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fns[vi]), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024));
-            attr_set_h[vi] = true;
-        }
-        hipLaunchKernelGGL(fns[vi], dim3((unsigned)(per_set * gsets)), dim3(256), lds, stream, a);
-        READ_CHECK_LAUNCH();
-        return READ_OK;
-    }
+    READ_CHECK_ARG(d->config != CFG_PX || r.kernel == CK_PX, "read_gated_conv_forward: the pixel-lane kernel takes 1x1/s1 layers with Cin <= 256, "
+                   "Cout %% 4 == 0 and 16-byte aligned tensors");
+    READ_CHECK_ARG(!(d->pre && d->pre_bilinear) || r.kernel == CK_PX, "read_gated_conv_forward: pre_bilinear needs the pixel-lane kernel (1x1/s1, Cin <= 256, "
+                   "Cout %% 4 == 0, 16-byte aligned tensors, automatic config)");
+    return READ_OK;
+}
 
-    // ---- 1x1 layers: the pixel-lane kernel (config -2 forces it, -1 takes it whenever the layer qualifies)
-    {
-        const int nsteps = Cin / 8;
-        const int gw = (groups % 2 == 0 && nsteps <= 16) ? 2 : 1;
-        const bool fits = d->ksize == 1 && d->stride == 1 && !d->mul && !d->fill_pad && d->Cout % 4 == 0 && d->out_cstride % 4 == 0 &&
-                          (uintptr_t)d->out % 16 == 0 && (uintptr_t)d->params % 16 == 0 && nsteps <= 32 &&
-                          (!d->residual || (uintptr_t)d->residual % 16 == 0) &&
-                          (!d->pre || ((uintptr_t)d->pre % 16 == 0 && d->pre_cstride % 4 == 0 && d->pre_f_off % 4 == 0 && d->pre_m_off % 4 == 0));
-        READ_CHECK_ARG(d->config != -2 || fits, "read_gated_conv_forward: the pixel-lane kernel takes 1x1/s1 layers with Cin <= 256, "
-                       "Cout %% 4 == 0 and 16-byte aligned tensors");
-        // Measured per layer at 1216x352 (profiles/README.md): the pixel-lane kernel wins where the LDS-tiled kernels fall to
-        // 8-channel chunks (SCM tails, cat[x(8), main]) or pad the last channel group (Cout = 56 / 120 / 248), 3-7 us per
-        // layer; on the other 1x1 layers it is level or up to 10 us slower (its four 32-byte segments per pixel line
-        // arrive as separate instructions) — conv_px = 1 takes it only for the former, 3 / 4 for every layer it fits.
-        bool px_pick = false;
-        for (int i = 0; i < d->n_src; ++i) px_pick = px_pick || d->src[i].C % 16 != 0;
-        px_pick = px_pick || d->Cout % 32 != 0 || g_conv_px >= 3;
-        const bool bil = d->pre && d->pre_bilinear;                // only this kernel samples the addend bilinearly
-        READ_CHECK_ARG(!bil || (fits && d->config < 0), "read_gated_conv_forward: pre_bilinear needs the pixel-lane kernel (1x1/s1, Cin <= 256, "
-                       "Cout %% 4 == 0, 16-byte aligned tensors, automatic config)");
-        if (d->config == -2 || bil || (d->config == -1 && g_conv_px && fits && px_pick)) {
-            static int n_cu_p = 0;
-            if (!n_cu_p) {
-                int dev = 0;
-                hipDeviceProp_t prop;
-                n_cu_p = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                          prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-            }
-            const bool wide = g_conv_px == 2 || g_conv_px == 4;     // 128 accumulator registers per wave instead of 64
-            const int pt = (gw == 2 ? 1 : 2) * (wide ? 2 : 1);
-            const size_t lds = (size_t)nsteps * 2 * gw * 1024;
-            int per_cu = (int)((160 * 1024) / (lds + 256));
-            const int reg_cap = wide ? 2 : 3;
-            per_cu = per_cu < 1 ? 1 : per_cu > reg_cap ? reg_cap : per_cu;
-            const int gsets = groups / gw;
-            a.nchunks = nsteps;
-            a.n_units = ceil_div(outH * outW, 32 * pt);
-            int per_set = (n_cu_p * per_cu) / gsets;
-            const int want = ceil_div(a.n_units, 4);
-            per_set = per_set < 1 ? 1 : per_set;
-            per_set = per_set < want ? per_set : want;
-            const bool fullq = nsteps % 4 == 0;
-            conv_fn fn = gw == 2 ? (wide ? (fullq ? gated_conv_px_kernel<2, 2, true> : gated_conv_px_kernel<2, 2>)
-                                         : (fullq ? gated_conv_px_kernel<1, 2, true> : gated_conv_px_kernel<1, 2>))
-                                 : (wide ? (fullq ? gated_conv_px_kernel<4, 1, true> : gated_conv_px_kernel<4, 1>)
-                                         : (fullq ? gated_conv_px_kernel<2, 1, true> : gated_conv_px_kernel<2, 1>));
-            static bool attr_set[8] = {false, false, false, false, false, false, false, false};
-            const int vi = (gw == 2 ? 2 : 0) + (wide ? 1 : 0) + (fullq ? 4 : 0);
-            if (!attr_set[vi]) {                                    // 64 KiB of dynamic LDS at Cin = 256
-                READ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-                attr_set[vi] = true;
-            }
-            hipLaunchKernelGGL(fn, dim3((unsigned)(per_set * gsets)), dim3(256), lds, stream, a);
-            READ_CHECK_LAUNCH();
-            return READ_OK;
-        }
+#ifdef READ_DEBUG_KNOBS
+// conv_abl: the attribution-probe variant ABL = g_abl of a kernel (results invalid), or `fn` where no such variant was built
+template <template <int> class K, int... ABL>
+static conv_fn abl_variant(conv_fn fn)
+{
+    ((g_abl == ABL ? (void)(fn = K<ABL>::fn()) : (void)0), ...);
+    return fn;
+}
+template <int N> struct AblW4 { static conv_fn fn() { return gated_conv_wino4_kernel<false, N>; } };
+template <int N> struct AblW4h { static conv_fn fn() { return gated_conv_wino4h_kernel<N>; } };
+template <int N> struct AblW4h2 { static conv_fn fn() { return gated_conv_wino4h2_kernel<N>; } };
+template <int N> struct AblD3h { static conv_fn fn() { return gated_conv_d3h_kernel<false, N>; } };
+template <int N> struct AblW16 { static conv_fn fn() { return gated_conv_wino16s_kernel<false, N>; } };
+#endif
+
+// at most four output channels, 3x3 / stride 1: the vector-pipe kernel
+static int launch_sc(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, hipStream_t stream)
+{
+    READ_CHECK_ARG((uintptr_t)d->wpacked_sc % 64 == 0 && (uintptr_t)d->src[0].data % 16 == 0, "read_gated_conv_forward: wpacked_sc / source misaligned");
+    a.tiles_x = ceil_div(s.outW, 32);
+    const int cph = g_sc & 63;                                 // knob: channels per LDS phase
+    const dim3 grid((unsigned)(a.tiles_x * ceil_div(s.outH, 8)));
+    static const conv_fn fns[3][2] = {{gated_conv_smallc_kernel<32, 8, 1, 3>, gated_conv_smallc_kernel<32, 8, 1, 4>},
+                                      {gated_conv_smallc_kernel<32, 16, 1, 3>, gated_conv_smallc_kernel<32, 16, 1, 4>},
+                                      {gated_conv_smallc_kernel<32, 32, 1, 3>, gated_conv_smallc_kernel<32, 32, 1, 4>}};
+    hipLaunchKernelGGL(fns[cph == 32 ? 2 : cph == 16 ? 1 : 0][d->Cout <= 3 ? 0 : 1], grid, dim3(256), 0, stream, a);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+// The pixel-lane kernels' grid: the CUs' `slots` persistent workgroups shared out over the `gsets` group sets, no more per set than
+// the units ask for (four waves each); dynamic LDS up to `lds_limit` is requested once per kernel
+static int launch_pixel_lane(conv_fn fn, bool &attr_set, int lds_limit, int slots, int gsets, bool xcd_map, size_t lds, hipStream_t stream, const ConvKArgs &a)
+{
+    const int want = ceil_div(a.n_units, 4);
+    int per_set = slots / gsets < 1 ? 1 : slots / gsets;
+    per_set = per_set < want ? per_set : want;
+    if (xcd_map) per_set = (per_set + 7) / 8 * 8;                // the split-operand kernel's XCD-aware workgroup map
+    if (!attr_set) {
+        READ_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit));
+        attr_set = true;
     }
-    if (d->linear) {
-        // the plain-convolution epilogue exists in the workgroup-tiled kernels and in the Winograd kernel
-        READ_CHECK_ARG(cfg < 0 || (cfg < N_CONFIGS && !g_configs[cfg].wave),
-                       "read_gated_conv_forward: linear mode needs a workgroup-tiled or Winograd config");
-        if (cfg < 0 && conv_uses_wino(d))
-            for (int i = N_CONFIGS - 1; i >= 0; --i)
-                if (g_configs[i].wino) cfg = i;
-        for (int i = 0; cfg < 0 && i < N_CONFIGS; ++i) {
-            const ConvConfig &k = g_configs[i];
-            if (!k.wave && !k.wino && k.KS == d->ksize && k.S == d->stride && k.KC == kc && groups % (k.WN * k.QG) == 0 &&
-                (!d->mul || k.fn_mul))
-                cfg = i;
-        }
-    }
-    if (cfg < 0 && conv_uses_wino(d))
-        for (int i = N_CONFIGS - 1; i >= 0; --i)
-            if (g_configs[i].wino) cfg = i;       // first Winograd entry = the product kernel
-    if (cfg < 0) cfg = pick_config(d->ksize, d->stride, kc, groups, outH, outW);
-    if (d->config < 0 && d->mul && cfg >= 0 && !g_configs[cfg].fn_mul)
-        for (int i = 0; i < N_CONFIGS; ++i) {
-            const ConvConfig &k = g_configs[i];
-            if (k.fn_mul && k.KS == d->ksize && k.S == d->stride && k.KC == kc && groups % (k.WN * k.QG) == 0) {
-                cfg = i;
-                break;
-            }
-        }
-    READ_CHECK_ARG(cfg >= 0 && cfg < N_CONFIGS, "read_gated_conv_forward: no kernel for k=%d s=%d kc=%d groups=%d",
-                   d->ksize, d->stride, kc, groups);
-    const ConvConfig &c = g_configs[cfg];
-    READ_CHECK_ARG(c.KS == d->ksize && c.S == d->stride && c.KC == kc && groups % (c.WN * c.QG) == 0,
-                   "read_gated_conv_forward: config %s does not fit k=%d s=%d kc=%d groups=%d", c.name, d->ksize,
-                   d->stride, kc, groups);
-    a.nchunks = nchunks;
-    a.tiles_x = ceil_div(outW, 32);
-    READ_CHECK_ARG(!d->pre || !c.wino, "read_gated_conv_forward: the Winograd kernel takes no pre-activation addend");
-    READ_CHECK_ARG(!d->out_gated || ((c.wino || conv_uses_w4(d)) && d->linear && (uintptr_t)d->out_gated % 16 == 0 && d->block_h >= 0 &&
+    hipLaunchKernelGGL(fn, dim3((unsigned)(per_set * gsets)), dim3(256), lds, stream, a);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+// 1x1 layers (taps: 3x3 layers over 8 - 32 channels as an implicit GEMM) on the f16 matrix cores: the split-operand pixel-lane kernel
+static int launch_pxh(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, bool taps, hipStream_t stream)
+{
+    READ_CHECK_ARG((uintptr_t)(taps ? d->wpacked_t3h : d->wpacked_d3h) % 16 == 0, "read_gated_conv_forward: wpacked_d3h / wpacked_t3h misaligned");
+    const int n_cu = device_cus();
+    a.wp_d3h = taps ? d->wpacked_t3h : d->wpacked_d3h;
+    const int nsteps = taps ? (9 * s.Cin + 15) / 16 : s.Cin / 16;
+    if (taps) a.tiles_y = s.Cin == 8 ? 3 : s.Cin == 16 ? 4 : 5;     // log2 of the source's channels
+    const int gw = (s.groups % 2 == 0 && nsteps <= 8) ? 2 : 1;
+    const size_t lds = (size_t)nsteps * 2 * gw * 2048 + 6 * 32 * gw * sizeof(float);     // <= 64 KiB of fragments + parameters: two workgroups per CU
+    const int gsets = s.groups / gw;
+    const int per_cu = lds > 78 * 1024 ? 1 : 2;
+    // two pixel tiles per wave as soon as one tile per wave would need a second round of units: a wave's time per unit is the
+    // latency of its activation stream (ring of four steps), the same for one tile or two
+    const long slots = (long)n_cu * per_cu / gsets * 4;
+    const int pt = gw == 2 ? 1 : ((long)ceil_div(s.outH * s.outW, 32) > (slots > 0 ? slots : 1) ? 2 : 1);
+    a.nchunks = nsteps;
+    a.n_units = ceil_div(s.outH * s.outW, 32 * pt);
+    const bool fullq = nsteps % 4 == 0;
+    bool uni = true;
+    for (int i = 0; i < d->n_src; ++i) uni = uni && d->src[i].C % 16 == 0;
+    const int shape = gw == 2 ? 0 : pt == 2 ? 1 : 2, vi = taps ? 12 + shape : shape * 4 + (fullq ? 2 : 0) + (uni ? 1 : 0);
+    static const conv_fn fns[15] = {
+        gated_conv_pxh_kernel<1, 2, false, 0>, gated_conv_pxh_kernel<1, 2, false, 1>, gated_conv_pxh_kernel<1, 2, true, 0>, gated_conv_pxh_kernel<1, 2, true, 1>,
+        gated_conv_pxh_kernel<2, 1, false, 0>, gated_conv_pxh_kernel<2, 1, false, 1>, gated_conv_pxh_kernel<2, 1, true, 0>, gated_conv_pxh_kernel<2, 1, true, 1>,
+        gated_conv_pxh_kernel<1, 1, false, 0>, gated_conv_pxh_kernel<1, 1, false, 1>, gated_conv_pxh_kernel<1, 1, true, 0>, gated_conv_pxh_kernel<1, 1, true, 1>,
+        gated_conv_pxh_kernel<1, 2, false, 2>, gated_conv_pxh_kernel<2, 1, false, 2>, gated_conv_pxh_kernel<1, 1, false, 2>};
+    static bool attr_set_h[15] = {false, false, false, false, false, false, false, false, false, false, false, false, false, false, false};
+    // 64 KiB of dynamic LDS at Cin = 256 (74 KiB: 3x3 over 32 channels)
+    return launch_pixel_lane(fns[vi], attr_set_h[vi], 80 * 1024, n_cu * per_cu, gsets, true, lds, stream, a);
+}
+
+// 1x1 layers: the fp32 pixel-lane kernel
+static int launch_px(ConvKArgs &a, const ConvShape &s, hipStream_t stream)
+{
+    const int n_cu = device_cus(), nsteps = s.Cin / 8;
+    const int gw = (s.groups % 2 == 0 && nsteps <= 16) ? 2 : 1;
+    const bool wide = g_conv_px == 2 || g_conv_px == 4;     // 128 accumulator registers per wave instead of 64
+    const int pt = (gw == 2 ? 1 : 2) * (wide ? 2 : 1);
+    const size_t lds = (size_t)nsteps * 2 * gw * 1024;
+    int per_cu = (int)((160 * 1024) / (lds + 256));
+    const int reg_cap = wide ? 2 : 3;
+    per_cu = per_cu < 1 ? 1 : per_cu > reg_cap ? reg_cap : per_cu;
+    const int gsets = s.groups / gw;
+    a.nchunks = nsteps;
+    a.n_units = ceil_div(s.outH * s.outW, 32 * pt);
+    const bool fullq = nsteps % 4 == 0;
+    static const conv_fn fns[8] = {gated_conv_px_kernel<2, 1>, gated_conv_px_kernel<4, 1>, gated_conv_px_kernel<1, 2>, gated_conv_px_kernel<2, 2>,
+                                   gated_conv_px_kernel<2, 1, true>, gated_conv_px_kernel<4, 1, true>, gated_conv_px_kernel<1, 2, true>, gated_conv_px_kernel<2, 2, true>};
+    static bool attr_set[8] = {false, false, false, false, false, false, false, false};
+    const int vi = (gw == 2 ? 2 : 0) + (wide ? 1 : 0) + (fullq ? 4 : 0);
+    return launch_pixel_lane(fns[vi], attr_set[vi], 64 * 1024, n_cu * per_cu, gsets, false, lds, stream, a);      // 64 KiB of dynamic LDS at Cin = 256
+}
+
+// out_gated (the layer's output beside a linear launch's pre-activations) exists in the Winograd kernels' linear epilogue only
+static int take_out_gated(const read_conv_desc *d, bool winograd, ConvKArgs &a)
+{
+    READ_CHECK_ARG(!d->out_gated || (winograd && d->linear && (uintptr_t)d->out_gated % 16 == 0 && d->block_h >= 0 &&
                                      d->valid_h <= d->block_h),
                    "read_gated_conv_forward: out_gated needs a linear launch on the Winograd kernel");
     a.out_gated = d->out_gated;
     a.blk_h = d->block_h;
     a.blk_valid = d->valid_h;
-    const int tiles_y = ceil_div(outH, c.WM * c.P);
+    return READ_OK;
+}
+
+static int refuse_f4x1_config(const read_conv_desc *d, bool f4x1)
+{
+    READ_CHECK_ARG(d->config != CFG_F4X1 || f4x1, "read_gated_conv_forward: config -12 takes the launches of the split-operand 3x3/s1 family "
+                   "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
+    return READ_OK;
+}
+
+// Grid of the persistent Winograd-style kernels: at most `cap` workgroups, a multiple of `groups` so that a workgroup keeps its
+// channel group; also sets the (tile row, tile column) step between a workgroup's units
+static int persistent_grid(ConvKArgs &a, int groups, int cap)
+{
+    int nwg = a.n_units < cap ? a.n_units : cap;
+    nwg -= nwg % groups;
+    if (nwg < groups) nwg = groups;
+    a.wino_dby = (nwg / groups) / a.tiles_x;
+    a.wino_dbx = (nwg / groups) % a.tiles_x;
+    return nwg;
+}
+
+// 3x3 / stride 2 (4x4 / stride 2) on the direct split-operand kernel: units of 8 x 16 output pixels x 64 channels, one persistent workgroup per CU
+static int launch_d3h_s2(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, hipStream_t stream)
+{
+    const int rc = take_out_gated(d, false, a);
+    if (rc != READ_OK) return rc;
+    READ_CHECK_ARG((uintptr_t)d->wpacked_d3h % 16 == 0, "read_gated_conv_forward: wpacked_d3h misaligned");
+    a.wp_d3h = d->wpacked_d3h;
+    a.nchunks = s.Cin / 32;
+    a.tiles_x = ceil_div(s.outW, 16);
+    const int pairs = (s.CoutPad + 63) / 64;
+    a.n_units = a.tiles_x * ceil_div(s.outH, 8) * pairs;
+    const int nwg = persistent_grid(a, pairs, device_cus());
+    if (d->ksize == 4) hipLaunchKernelGGL((gated_conv_d3h_s2_kernel<4>), dim3((unsigned)nwg), dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL((gated_conv_d3h_s2_kernel<3>), dim3((unsigned)nwg), dim3(512), 0, stream, a);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+// The F(4x4) family and the kernels that share its units (8 x 32 pixels x 32 channels, one persistent workgroup per CU): Winograd
+// F(4x4,3x3) in fp32 (CK_W4) or with split operands (CK_W4H), F(4,3) by rows (CK_F4X1), the direct split-operand kernel (CK_D3H)
+static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, ConvKernel kernel, const void *wp_f4x1, hipStream_t stream)
+{
+    const bool d3h = kernel == CK_D3H, f4x1 = kernel == CK_F4X1, w4h = f4x1 || kernel == CK_W4H;
+    int rc = take_out_gated(d, kernel == CK_W4, a);
+    if (rc != READ_OK) return rc;
+    rc = refuse_f4x1_config(d, f4x1);
+    if (rc != READ_OK) return rc;
+    READ_CHECK_ARG(!w4h || f4x1 || d->wpacked_w4h != wp_f4x1, "read_gated_conv_forward: this launch takes the F(4x4) split-operand kernel "
+                   "and only the F(4,3)-by-rows order was packed");
+    READ_CHECK_ARG((uintptr_t)(d3h ? d->wpacked_d3h : w4h ? d->wpacked_w4h : (const void *)d->wpacked_w4) % 16 == 0,
+                   "read_gated_conv_forward: wpacked_w4 / wpacked_w4h / wpacked_d3h misaligned");
+    a.wp_d3h = d->wpacked_d3h;
+    READ_CHECK_ARG(!d->mul || (uintptr_t)d->mul % 16 == 0, "read_gated_conv_forward: mul misaligned");
+    a.wp_w4h = d->wpacked_w4h;
+    a.wp_f4x1 = wp_f4x1;
+    READ_CHECK_ARG(!f4x1 || (uintptr_t)wp_f4x1 % 16 == 0, "read_gated_conv_forward: wpacked_f4x1 misaligned");
+    a.nchunks = (w4h || d3h) ? s.Cin / 32 : s.Cin / s.kc;
+    a.tiles_x = ceil_div(s.outW, 32);
+    a.n_units = a.tiles_x * ceil_div(s.outH, 8) * s.groups;
+    const int n_cu = device_cus(), groups = s.groups;
+    int cap = n_cu;
+    if (g_w4_grid) {                                               // A/B: every workgroup the same number of units
+        const int whole = n_cu - n_cu % groups > 0 ? n_cu - n_cu % groups : groups;
+        cap = ceil_div(ceil_div(a.n_units, ceil_div(a.n_units, whole)), groups) * groups;
+        if (cap > n_cu) cap -= groups;
+    }
+    const int nwg = persistent_grid(a, groups, cap);
+    conv_fn fn = d->linear ? (d->out_gated ? gated_conv_wino4_kernel<false, 0, 1> : gated_conv_wino4_kernel<false, 0, 2>) : d->mul ? gated_conv_wino4_kernel<true> : gated_conv_wino4_kernel<false>;
+    unsigned threads = 256;
+    if (d3h) {
+        fn = d->mul ? gated_conv_d3h_kernel<true> : gated_conv_d3h_kernel<false>;
+        threads = 512;
+    } else if (f4x1) fn = gated_conv_f4x1h_kernel;
+    else if (w4h) fn = gated_conv_wino4h_kernel<>;
+    READ_CHECK_ARG(!d->linear || !d->mul, "read_gated_conv_forward: linear launches take no multiplier");
+#ifdef READ_DEBUG_KNOBS
+    if (g_w4x2 && !d->linear && !d->mul) {   // negative result (see the kernel): eight waves per workgroup, frequencies split over wave pairs
+        fn = gated_conv_wino4x2_kernel;
+        threads = 512;
+    } else if (d3h) {
+        if (!d->mul) fn = abl_variant<AblD3h, 1, 2, 4, 8, 16, 32, 7, 63, 55>(fn);
+    } else if (w4h && !f4x1 && g_w4h_waves == 8) {
+        fn = abl_variant<AblW4h2, 1, 8, 9, 128, 256, 1024, 1033>(gated_conv_wino4h2_kernel<>);
+        threads = 512;
+    } else if (w4h && !f4x1) {
+        fn = abl_variant<AblW4h, 1, 2, 3, 4, 7, 8, 15, 32, 64, 128, 256, 512, 1024, 1007, 2047 - 1024, 544, 2048, 4096, 6144, 40, 8192, 16384, 24576,
+                         32768, 65536, 122880>(fn);
+    } else if (!w4h && !d->mul) {
+        fn = abl_variant<AblW4, 1, 7, 8, 24, 31, 32, 64, 128, 256, 511, 383, 512>(fn);
+    }
+#endif
+    hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(threads), 0, stream, a);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+// an entry of g_configs: the workgroup-tiled and wave-autonomous direct kernels and Winograd F(2x2,3x3)
+static int launch_table(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, const ConvRoute &r, hipStream_t stream)
+{
+    const int groups = s.groups;
+    // the plain-convolution epilogue exists in the workgroup-tiled kernels and in the Winograd kernel
+    READ_CHECK_ARG(!d->linear || d->config < 0 || (d->config < N_CONFIGS && !g_configs[d->config].wave),
+                   "read_gated_conv_forward: linear mode needs a workgroup-tiled or Winograd config");
+    READ_CHECK_ARG(r.cfg >= 0 && r.cfg < N_CONFIGS, "read_gated_conv_forward: no kernel for k=%d s=%d kc=%d groups=%d",
+                   d->ksize, d->stride, s.kc, groups);
+    const ConvConfig &c = g_configs[r.cfg];
+    READ_CHECK_ARG(c.KS == d->ksize && c.S == d->stride && c.KC == s.kc && groups % (c.WN * c.QG) == 0,
+                   "read_gated_conv_forward: config %s does not fit k=%d s=%d kc=%d groups=%d", c.name, d->ksize,
+                   d->stride, s.kc, groups);
+    a.nchunks = s.Cin / s.kc;
+    a.tiles_x = ceil_div(s.outW, 32);
+    READ_CHECK_ARG(!d->pre || !c.wino, "read_gated_conv_forward: the Winograd kernel takes no pre-activation addend");
+    int rc = take_out_gated(d, c.wino != 0, a);
+    if (rc != READ_OK) return rc;
+    const int tiles_y = ceil_div(s.outH, c.WM * c.P);
     dim3 grid((unsigned)(a.tiles_x * tiles_y), (unsigned)(groups / (c.WN * c.QG)));
     a.trace = ((size_t)grid.x * grid.y <= g_trace_records) ? g_trace : nullptr;
     if (c.wino) {
         READ_CHECK_ARG(d->wpacked_wino && (uintptr_t)d->wpacked_wino % 16 == 0, "read_gated_conv_forward: config %s needs wpacked_wino", c.name);
         READ_CHECK_ARG(d->n_src == 1 && d->src[0].shift == 0 && d->src[0].C % 16 == 0,
                        "read_gated_conv_forward: the Winograd kernel takes one un-resampled source with C %% 16 == 0");
-        a.tiles_x = ceil_div(outW, 16);
-        a.n_units = a.tiles_x * ceil_div(outH, 8) * groups;       // unit u = (tile u / groups, group u % groups)
-        static int n_cu_w = 0;
-        if (!n_cu_w) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            n_cu_w = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                      prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
-        int nwg = a.n_units < g_wino_wgs * n_cu_w ? a.n_units : g_wino_wgs * n_cu_w;    // persistent: two workgroups per CU
-        nwg -= nwg % groups;                                          // keeps the group fixed per workgroup
-        if (nwg < groups) nwg = groups;
-        grid = dim3((unsigned)nwg, 1);
-        a.wino_dby = (nwg / groups) / a.tiles_x;
-        a.wino_dbx = (nwg / groups) % a.tiles_x;
+        a.tiles_x = ceil_div(s.outW, 16);
+        a.n_units = a.tiles_x * ceil_div(s.outH, 8) * groups;       // unit u = (tile u / groups, group u % groups)
+        grid = dim3((unsigned)persistent_grid(a, groups, g_wino_wgs * device_cus()), 1);      // two workgroups per CU
         a.trace = ((size_t)grid.x * 4 <= g_trace_records) ? g_trace : nullptr;
     }
     if (c.wave) {
-        // persistent grid: every wave walks units u = wave, wave + n_waves, ...
-        a.tiles_y = ceil_div(outH, c.P);
+        // persistent grid: every wave walks units u = wave, wave + n_waves, ...; all units are P rows
+        // (a balanced tail of 1-row units was tried and measured neutral-to-negative)
+        a.tiles_y = ceil_div(s.outH, c.P);
         a.trace = nullptr;
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                    prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
-        // Balanced schedule: whole rounds of P-row units over all wave slots, the remainder as 1-row
-        // units, so the last round costs about half a unit instead of a full one (the trace of the
-        // workgroup-tiled kernel showed 20 % of a launch spent in a quarter-filled last round).
-        const int ncol = a.tiles_x * (groups / c.QG);
-        const long slots = (long)n_cu * c.wg_per_cu * 4;
-        const long unitsP = (long)ncol * a.tiles_y;
-        // (a balanced tail of 1-row units was tried and measured neutral-to-negative; all units are P rows)
-        (void)slots;
-        (void)unitsP;
-        const int col_split = ncol;
         a.stagger_ticks = g_stagger_ticks;
-        a.col_split = col_split;
-        a.n_full = col_split * a.tiles_y;
-        a.n_units = a.n_full + (ncol - col_split) * outH;
-        const int want = ceil_div(a.n_units, 4), cap = n_cu * c.wg_per_cu;
+        a.col_split = a.tiles_x * (groups / c.QG);
+        a.n_full = a.col_split * a.tiles_y;
+        a.n_units = a.n_full;
+        const int want = ceil_div(a.n_units, 4), cap = device_cus() * c.wg_per_cu;
         grid = dim3((unsigned)(want < cap ? want : cap), 1);
     }
+    rc = refuse_f4x1_config(d, false);
+    if (rc != READ_OK) return rc;
     conv_fn fn = c.fn;
-    // 3x3 / stride 2 on the direct split-operand kernel: units of 8 x 16 output pixels x 64 channels, one persistent workgroup per CU
-    if (conv_uses_d3h_s2(d)) {
-        READ_CHECK_ARG((uintptr_t)d->wpacked_d3h % 16 == 0, "read_gated_conv_forward: wpacked_d3h misaligned");
-        a.wp_d3h = d->wpacked_d3h;
-        a.nchunks = Cin / 32;
-        a.tiles_x = ceil_div(outW, 16);
-        const int pairs = (CoutPad + 63) / 64;
-        a.n_units = a.tiles_x * ceil_div(outH, 8) * pairs;
-        static int n_cu_s = 0;
-        if (!n_cu_s) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            n_cu_s = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                      prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
-        int nwg = a.n_units < n_cu_s ? a.n_units : n_cu_s;
-        nwg -= nwg % pairs;
-        if (nwg < pairs) nwg = pairs;
-        a.wino_dby = (nwg / pairs) / a.tiles_x;
-        a.wino_dbx = (nwg / pairs) % a.tiles_x;
-        a.trace = nullptr;
-        if (d->ksize == 4) hipLaunchKernelGGL((gated_conv_d3h_s2_kernel<4>), dim3((unsigned)nwg), dim3(512), 0, stream, a);
-        else hipLaunchKernelGGL((gated_conv_d3h_s2_kernel<3>), dim3((unsigned)nwg), dim3(512), 0, stream, a);
-        READ_CHECK_LAUNCH();
-        return READ_OK;
-    }
-    // Winograd F(4x4,3x3): units of 8 x 32 pixels x 32 channels, one persistent workgroup per CU
-    const bool d3h = conv_uses_d3h(d), w4h = !d3h && conv_uses_w4h(d);
-    // ... the F(4,3)-by-rows kernel for the family-5 launches its predicate names, when the caller brought its operand; a caller
-    // without it (a blob packed before the kernel existed) keeps running on the F(4x4) kernel
-    const bool f4x1 = w4h && wp_f4x1 && conv_uses_f4x1(d);
-    READ_CHECK_ARG(d->config != -12 || f4x1, "read_gated_conv_forward: config -12 takes the launches of the split-operand 3x3/s1 family "
-                   "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
-    READ_CHECK_ARG(!w4h || f4x1 || d->wpacked_w4h != wp_f4x1, "read_gated_conv_forward: this launch takes the F(4x4) split-operand kernel "
-                   "and only the F(4,3)-by-rows order was packed");
-    if (d3h || w4h || conv_uses_w4(d)) {
-        READ_CHECK_ARG((uintptr_t)(d3h ? d->wpacked_d3h : w4h ? d->wpacked_w4h : (const void *)d->wpacked_w4) % 16 == 0,
-                       "read_gated_conv_forward: wpacked_w4 / wpacked_w4h / wpacked_d3h misaligned");
-        a.wp_d3h = d->wpacked_d3h;
-        READ_CHECK_ARG(!d->mul || (uintptr_t)d->mul % 16 == 0, "read_gated_conv_forward: mul misaligned");
-        a.wp_w4h = d->wpacked_w4h;
-        a.wp_f4x1 = wp_f4x1;
-        READ_CHECK_ARG(!f4x1 || (uintptr_t)wp_f4x1 % 16 == 0, "read_gated_conv_forward: wpacked_f4x1 misaligned");
-        if (w4h || d3h) a.nchunks = Cin / 32;
-        a.tiles_x = ceil_div(outW, 32);
-        a.n_units = a.tiles_x * ceil_div(outH, 8) * groups;
-        static int n_cu_4 = 0;
-        if (!n_cu_4) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            n_cu_4 = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                      prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        }
-        int nwg = a.n_units < n_cu_4 ? a.n_units : n_cu_4;
-        nwg -= nwg % groups;
-        if (g_w4_grid) {                                               // A/B: every workgroup the same number of units
-            const int cap = n_cu_4 - n_cu_4 % groups > 0 ? n_cu_4 - n_cu_4 % groups : groups;
-            nwg = ceil_div(ceil_div(a.n_units, ceil_div(a.n_units, cap)), groups) * groups;
-            if (nwg > n_cu_4) nwg -= groups;
-        }
-        if (nwg < groups) nwg = groups;
-        a.wino_dby = (nwg / groups) / a.tiles_x;
-        a.wino_dbx = (nwg / groups) % a.tiles_x;
-        a.trace = nullptr;
-        conv_fn fn4 = d->linear ? (d->out_gated ? gated_conv_wino4_kernel<false, 0, 1> : gated_conv_wino4_kernel<false, 0, 2>) : d->mul ? gated_conv_wino4_kernel<true> : gated_conv_wino4_kernel<false>;
-        READ_CHECK_ARG(!d->linear || !d->mul, "read_gated_conv_forward: linear launches take no multiplier");
-#ifdef READ_DEBUG_KNOBS
-        if (!d->mul && g_abl) {
-            switch (g_abl) {
-#define READ_ABL_CASE(n) case n: fn4 = gated_conv_wino4_kernel<false, n>; break;
-            READ_ABL_CASE(1) READ_ABL_CASE(7) READ_ABL_CASE(8) READ_ABL_CASE(24) READ_ABL_CASE(31) READ_ABL_CASE(32) READ_ABL_CASE(64)
-            READ_ABL_CASE(128) READ_ABL_CASE(256) READ_ABL_CASE(511) READ_ABL_CASE(383) READ_ABL_CASE(512)
-#undef READ_ABL_CASE
-            default: break;
-            }
-        }
-#endif
-#ifdef READ_DEBUG_KNOBS
-        if (g_w4x2 && !d->linear && !d->mul) {   // negative result (see the kernel): eight waves per workgroup, frequencies split over wave pairs
-            hipLaunchKernelGGL(gated_conv_wino4x2_kernel, dim3((unsigned)nwg), dim3(512), 0, stream, a);
-            READ_CHECK_LAUNCH();
-            return READ_OK;
-        }
-#endif
-        if (d3h) {
-            conv_fn fnd = d->mul ? gated_conv_d3h_kernel<true> : gated_conv_d3h_kernel<false>;
-#ifdef READ_DEBUG_KNOBS
-            if (!d->mul && g_abl) {
-                switch (g_abl) {
-#define READ_ABL_CASE(n) case n: fnd = gated_conv_d3h_kernel<false, n>; break;
-                READ_ABL_CASE(1) READ_ABL_CASE(2) READ_ABL_CASE(4) READ_ABL_CASE(8) READ_ABL_CASE(16) READ_ABL_CASE(32) READ_ABL_CASE(7) READ_ABL_CASE(63) READ_ABL_CASE(55)
-#undef READ_ABL_CASE
-                default: break;
-                }
-            }
-#endif
-            hipLaunchKernelGGL(fnd, dim3((unsigned)nwg), dim3(512), 0, stream, a);
-            READ_CHECK_LAUNCH();
-            return READ_OK;
-        }
-        if (f4x1) {
-            hipLaunchKernelGGL(gated_conv_f4x1h_kernel, dim3((unsigned)nwg), dim3(256), 0, stream, a);
-            READ_CHECK_LAUNCH();
-            return READ_OK;
-        }
-        if (w4h) fn4 = gated_conv_wino4h_kernel<>;
-#ifdef READ_DEBUG_KNOBS
-        if (w4h && g_abl) {
-            switch (g_abl) {
-#define READ_ABL_CASE(n) case n: fn4 = gated_conv_wino4h_kernel<n>; break;
-            READ_ABL_CASE(1) READ_ABL_CASE(2) READ_ABL_CASE(3) READ_ABL_CASE(4) READ_ABL_CASE(7) READ_ABL_CASE(8) READ_ABL_CASE(15) READ_ABL_CASE(32) READ_ABL_CASE(64)
-            READ_ABL_CASE(128) READ_ABL_CASE(256) READ_ABL_CASE(512) READ_ABL_CASE(1024) READ_ABL_CASE(1007) READ_ABL_CASE(2047 - 1024) READ_ABL_CASE(544) READ_ABL_CASE(2048) READ_ABL_CASE(4096) READ_ABL_CASE(6144) READ_ABL_CASE(40) READ_ABL_CASE(8192) READ_ABL_CASE(16384) READ_ABL_CASE(24576) READ_ABL_CASE(32768) READ_ABL_CASE(65536) READ_ABL_CASE(122880)
-#undef READ_ABL_CASE
-            default: break;
-            }
-        }
-#endif
-#ifdef READ_DEBUG_KNOBS
-        if (w4h && g_w4h_waves == 8) {
-            conv_fn fn8 = gated_conv_wino4h2_kernel<>;
-            if (g_abl) {
-                switch (g_abl) {
-#define READ_ABL_CASE(n) case n: fn8 = gated_conv_wino4h2_kernel<n>; break;
-                READ_ABL_CASE(1) READ_ABL_CASE(8) READ_ABL_CASE(9) READ_ABL_CASE(128) READ_ABL_CASE(256) READ_ABL_CASE(1024) READ_ABL_CASE(1033)
-#undef READ_ABL_CASE
-                default: break;
-                }
-            }
-            hipLaunchKernelGGL(fn8, dim3((unsigned)nwg), dim3(512), 0, stream, a);
-            READ_CHECK_LAUNCH();
-            return READ_OK;
-        }
-#endif
-        hipLaunchKernelGGL(fn4, dim3((unsigned)nwg), dim3(256), 0, stream, a);
-        READ_CHECK_LAUNCH();
-        return READ_OK;
-    }
     if (c.wino && a.trace && !d->mul) fn = gated_conv_wino_kernel<true, false>;
     if (d->mul) {
         READ_CHECK_ARG(c.fn_mul, "read_gated_conv_forward: config %s has no multiply variant", c.name);
         READ_CHECK_ARG((uintptr_t)d->mul % 16 == 0, "read_gated_conv_forward: mul misaligned");
         fn = c.fn_mul;
     }
-    // the wave-autonomous Winograd kernel (same units, same grid) whenever its weight order was supplied; linear launches
-    // (training path) stay on the row-per-wave kernel, which carries the plain-convolution epilogue
-    // ... and, by default, for layers whose last channel group is mostly padding (the 32 -> 3 output layer): its waves without a real
-    // channel skip their MFMAs, the row-per-wave kernel pays for all 32 padded channels
-    const bool mostly_padding = d->Cout <= 8;
-    if (c.wino && !d->linear && !a.trace && d->wpacked_w16 && (d->config == -3 || (d->config < 0 && (g_w16 || mostly_padding)))) {
+    if (r.w16 && !a.trace) {
         READ_CHECK_ARG((uintptr_t)d->wpacked_w16 % 16 == 0, "read_gated_conv_forward: wpacked_w16 misaligned");
         fn = d->mul ? gated_conv_wino16s_kernel<true> : gated_conv_wino16s_kernel<false>;
 #ifdef READ_DEBUG_KNOBS
-        if (!d->mul && g_abl) {
-            switch (g_abl) {
-#define READ_ABL_CASE(n) case n: fn = gated_conv_wino16s_kernel<false, n>; break;
-            READ_ABL_CASE(1) READ_ABL_CASE(2) READ_ABL_CASE(4) READ_ABL_CASE(8) READ_ABL_CASE(16) READ_ABL_CASE(32) READ_ABL_CASE(63)
-#undef READ_ABL_CASE
-            default: break;
-            }
-        }
+        if (!d->mul) fn = abl_variant<AblW16, 1, 2, 4, 8, 16, 32, 63>(fn);
 #endif
     }
     hipLaunchKernelGGL(fn, grid, dim3(256), 0, stream, a);
@@ -5970,138 +6096,31 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
     return READ_OK;
 }
 
-// the automatic choice takes the Winograd kernel for every layer it can run (measured faster on all four levels)
-int conv_uses_wino(const read_conv_desc *d)
+int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *wp_f4x1)
 {
-    return d->config < 0 && g_use_wino && !d->pre && d->ksize == 3 && d->stride == 1 && d->n_src == 1 &&
-           d->src[0].shift == 0 && d->src[0].C % 16 == 0 && d->wpacked_wino && d->src[0].C <= g_use_wino;
-}
-
-// F(4x4,3x3): non-linear 3x3 / stride-1 launches with full 32-channel groups and at least conv_w4 input channels (config -5 forces it)
-int conv_uses_w4(const read_conv_desc *d)
-{
-    const bool shape = !d->pre && (!d->linear || !d->residual) && d->ksize == 3 && d->stride == 1 && d->n_src == 1 && d->src[0].shift == 0 &&
-                       d->src[0].C % 16 == 0 && d->src[0].C >= 32 && (d->Cout % 32 == 0 || (d->linear && d->Cout % 8 == 0)) && !d->fill_pad && d->wpacked_w4 &&
-                       d->out_cstride % 4 == 0 &&                                                     // 128-bit stores
-                       (long long)d->src[0].srcH * d->src[0].srcW * d->src[0].C * 4 < (1ll << 31) &&  // 32-bit buffer offsets
-                       (long long)d->inH * d->inW * d->out_cstride * 4 < (1ll << 31);
-    return shape && (d->config == -5 || (d->config == -1 && g_w4 > 0 && d->src[0].C >= g_w4));
-}
-
-// ... on the f16 matrix cores with split operands: the gated (non-linear) launches of that family with whole 32-channel chunks whose
-// split operand was supplied (config -7 forces it; the training path's linear launches stay on the fp32 kernel)
-int conv_uses_w4h(const read_conv_desc *d)
-{
-    // (FAM's x1 * x2 stays on the fp32 kernel: the second patch costs the transform thread another 72 registers, and the
-    //  variant with a shallower weight ring measured SLOWER than the fp32 kernel — 101 / 79 / 68 us against 77 / 69 / 64 at C = 64 / 128 / 256)
-    if (!d->wpacked_w4h || d->linear || d->mul || d->src[0].C % 32 != 0 || d->Cout % 32 != 0) return 0;
-    if (d->config == -7 || d->config == -12) {                             // -12: the F(4,3)-by-rows kernel of the same family (conv_uses_f4x1)
-        read_conv_desc t = *d;
-        t.config = -5;
-        t.wpacked_w4 = reinterpret_cast<const float *>(d->wpacked_w4h);    // the shape test of the family (any non-null operand)
-        return conv_uses_w4(&t);
+    ConvKArgs a;
+    ConvShape s;
+    ConvRoute r;
+    const int rc = conv_prepare(d, wp_f4x1, a, s, r);
+    if (rc != READ_OK) return rc;
+    switch (r.kernel) {
+    case CK_SC: return launch_sc(d, a, s, stream);
+    case CK_T3H:
+    case CK_PXH: return launch_pxh(d, a, s, r.kernel == CK_T3H, stream);
+    case CK_PX: return launch_px(a, s, stream);
+    case CK_D3H_S2: return launch_d3h_s2(d, a, s, stream);
+    case CK_D3H:
+    case CK_F4X1:
+    case CK_W4H:
+    case CK_W4: return launch_w4_family(d, a, s, r.kernel, wp_f4x1, stream);
+    case CK_TABLE: return launch_table(d, a, s, r, stream);
     }
-    if (d->config != -1 || g_w4h <= 0 || d->src[0].C < g_w4h) return 0;
-    read_conv_desc t = *d;
-    t.wpacked_w4 = reinterpret_cast<const float *>(d->wpacked_w4h);
-    return conv_uses_w4(&t);
-}
-
-// ... and of those the launches that take the F(4,3)-by-rows kernel instead of the F(4x4) one: at least conv_f4x1 input channels
-// (config -12 forces it).  Consulted inside the family-5 branch only; both kernels report family 5.
-int conv_uses_f4x1(const read_conv_desc *d)
-{
-    if (!conv_uses_w4h(d)) return 0;
-    return d->config == -12 || (d->config == -1 && g_f4x1 > 0 && d->src[0].C >= g_f4x1);
-}
-
-// the DIRECT split-operand kernel: the same launches (FAM's x1 * x2 included: a multiplication at staging time); config -8 forces it
-int conv_uses_d3h(const read_conv_desc *d)
-{
-    if (!d->wpacked_d3h || d->linear || d->src[0].C % 32 != 0 || d->Cout % 32 != 0) return 0;
-    const int min_c = d->mul ? g_d3h_fam : g_d3h;
-    if (!(d->config == -8 || (d->config == -1 && min_c > 0 && d->src[0].C >= min_c))) return 0;
-    read_conv_desc t = *d;
-    t.config = -5;
-    t.wpacked_w4 = reinterpret_cast<const float *>(d->wpacked_d3h);        // the shape test of the family (any non-null operand)
-    return conv_uses_w4(&t);
-}
-
-// ... and at stride 2 (the encoder's down-sampling layers): gated 3x3 / stride-2 single-source launches with whole 32-channel chunks in and
-// whole 64-channel pairs out, no multiplier / addend / fill (config -9 forces it; read_tuning_set("conv_d3h_s2", 0) switches it off)
-int conv_uses_d3h_s2(const read_conv_desc *d)
-{
-    const bool shape = d->wpacked_d3h && !d->linear && !d->mul && !d->pre && !d->fill_pad && (d->ksize == 3 || d->ksize == 4) && d->stride == 2 && d->n_src == 1 &&
-                       d->src[0].shift == 0 && d->src[0].C % 32 == 0 && d->Cout % 32 == 0 && d->out_cstride % 4 == 0 &&
-                       (long long)d->src[0].srcH * d->src[0].srcW * d->src[0].C * 4 < (1ll << 31) &&
-                       (long long)d->inH * d->inW * d->out_cstride * 4 < (1ll << 31);
-    return shape && (d->config == -9 || (d->config == -1 && g_d3h_s2 > 0 && d->src[0].C >= g_d3h_s2));
-}
-
-// 1x1 / stride-1 layers on the split-operand pixel-lane kernel (gated or linear, any number of sources, residual, nearest pre-activation addend):
-// whole k16 steps, at most 64 KiB of weight fragments per group set, everything 16-byte aligned (config -10 forces it;
-// read_tuning_set("conv_pxh", 0) switches it off)
-int conv_uses_pxh(const read_conv_desc *d)
-{
-    if (!d->wpacked_d3h || d->ksize != 1 || d->stride != 1 || d->mul || d->fill_pad || d->n_src < 1 || d->n_src > READ_CONV_MAX_SRC) return 0;
-    if (d->pre && d->pre_bilinear) return 0;                          // the bilinear addend (an option of the plan, off) stays on the fp32 pixel-lane kernel
-    int Cin = 0;
-    for (int i = 0; i < d->n_src; ++i) {
-        if (d->src[i].C < 8 || d->src[i].C % 8 != 0 || (uintptr_t)d->src[i].data % 16 != 0) return 0;
-        Cin += d->src[i].C;
-    }
-    const bool shape = Cin % 16 == 0 && Cin <= 256 && d->Cout % 4 == 0 && d->out_cstride % 4 == 0 && (uintptr_t)d->out % 16 == 0 &&
-                       (uintptr_t)d->params % 16 == 0 && (!d->residual || (uintptr_t)d->residual % 16 == 0) &&
-                       (!d->pre || ((uintptr_t)d->pre % 16 == 0 && d->pre_cstride % 4 == 0 && d->pre_f_off % 4 == 0 && d->pre_m_off % 4 == 0));
-    return shape && (d->config == -10 || (d->config == -1 && g_pxh > 0 && Cin >= g_pxh));
-}
-
-// 3x3 / stride-1 layers over one unshifted source of 8, 16 or 32 channels as an implicit GEMM on the same kernel (k = tap C + channel;
-// read_conv_pack_t3h_host): the layers that read the 8-channel descriptor pyramid by default (read_tuning_set("conv_t3h", max Cin), 0 = never;
-// config -11 forces it)
-int conv_uses_t3h(const read_conv_desc *d)
-{
-    if (!d->wpacked_t3h || d->ksize != 3 || d->stride != 1 || d->mul || d->fill_pad || d->pre || d->n_src != 1 || d->src[0].shift != 0) return 0;
-    const int C = d->src[0].C;
-    const bool shape = (C == 8 || C == 16 || C == 32) && d->Cout % 4 == 0 && d->out_cstride % 4 == 0 && (uintptr_t)d->out % 16 == 0 &&
-                       (uintptr_t)d->src[0].data % 16 == 0 && (uintptr_t)d->params % 16 == 0 && (!d->residual || (uintptr_t)d->residual % 16 == 0) &&
-                       (long long)d->inH * d->inW * C * 4 < (1ll << 31);
-    // (automatic choice from 16 K pixels on: at 44 x 152 the fp32 direct kernel measured 11.5 us against 14.2)
-    return shape && (d->config == -11 || (d->config == -1 && g_t3h > 0 && C <= g_t3h && (long long)d->inH * d->inW >= 16384));
-}
-
-// gated 3x3 / stride-1 layers with at most four output channels and 32 input channels (READ's output layer)
-int conv_uses_sc(const read_conv_desc *d)
-{
-    const bool shape = d->ksize == 3 && d->stride == 1 && d->n_src == 1 && d->src[0].shift == 0 && d->src[0].C == 32 && d->Cout >= 1 &&
-                       d->Cout <= 4 && !d->linear && !d->residual && !d->pre && !d->mul && d->wpacked_sc &&
-                       (d->out_cstride != 4 || (uintptr_t)d->out % 16 == 0) &&
-                       (long long)d->src[0].srcH * d->src[0].srcW * d->src[0].C * 4 < (1ll << 31);
-    return shape && (d->config == -6 || (d->config == -1 && g_sc));
-}
-
-int conv_kc_for(const read_conv_desc *d)
-{
-    int kc = 16;
-    for (int i = 0; i < d->n_src; ++i)
-        if (d->src[i].C % 16) kc = 8;
-    return kc;
+    return READ_EINVAL;
 }
 
 }  // namespace readhip
 
-extern "C" int read_conv_kernel_family(const read_conv_desc *desc)
-{
-    if (!desc) return -1;
-    if (readhip::conv_uses_sc(desc)) return 1;           // the order of the dispatch in launch_gated_conv: the small-Cout kernel first
-    if (readhip::conv_uses_t3h(desc)) return 8;
-    if (readhip::conv_uses_pxh(desc)) return 7;
-    if (readhip::conv_uses_d3h(desc) || readhip::conv_uses_d3h_s2(desc)) return 6;
-    if (readhip::conv_uses_w4h(desc)) return 5;
-    if (readhip::conv_uses_w4(desc)) return 4;
-    if (readhip::conv_uses_wino(desc)) return 2;
-    return 0;
-}
+extern "C" int read_conv_kernel_family(const read_conv_desc *desc) { return desc ? readhip::conv_family(desc) : -1; }
 
 // The same launch with the F(4,3)-by-rows operand (read_conv_pack_f4x1_host) beside the descriptor: the descriptor struct is
 // frozen at ABI version 3.  A launch of the split-operand 3x3/s1 family that conv_f4x1 (or config -12) names runs on
@@ -6117,8 +6136,6 @@ extern "C" int read_gated_conv_forward_f4x1(const read_conv_desc *desc, const vo
 
 extern "C" int read_gated_conv_forward(const read_conv_desc *desc, void *stream)
 {
-    // the fragment-order checks (a NULL or aliased wpacked against the kernel family this launch takes) live in
-    // launch_gated_conv: the UNet executor (unet.cpp) calls that directly and must get the same refusal
     return readhip::launch_gated_conv(desc, as_stream(stream), nullptr);
 }
 

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "common.h"
+#include "internal.h"
 
 #pragma clang fp contract(off)
 
@@ -1540,18 +1541,6 @@ WsLayout ws_layout(void *ws, int B, int W, int H)
 }
 
 constexpr size_t HIZ_LDS_LIMIT = 150 * 1024;   // of the 160 KiB per CU
-
-int device_cus()
-{
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
-                prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return n_cu;
-}
 
 ResolveOut resolve_out(int b0, int W, int H, int levels, int32_t *const *idx_levels, float *const *depth_levels, int level_base)
 {

@@ -11,16 +11,8 @@
 #include <vector>
 
 #include "common.h"
+#include "internal.h"
 
-namespace readhip {
-int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *wp_f4x1);
-int conv_uses_wino(const read_conv_desc *d);
-int conv_uses_w4(const read_conv_desc *d);
-int conv_uses_w4h(const read_conv_desc *d);
-int conv_uses_f4x1(const read_conv_desc *d);
-int conv_uses_d3h(const read_conv_desc *d);
-int conv_uses_d3h_s2(const read_conv_desc *d);
-}
 using namespace readhip;
 
 namespace {
@@ -799,10 +791,12 @@ extern "C" int read_unet_create_layout(read_unet_t **out, const float *packed, i
     b.build();
     // a lean blob serves exactly the launches the F(4x4) kernel takes under the CURRENT tuning state and at THIS size: a knob
     // that sends such a layer elsewhere (conv_w4), or a tensor of 2 GiB and more, needs the full layout
-    for (const Op &op : u->ops)
-        if (op.kind == Op::CONV && !op.d.wpacked && !conv_uses_w4(&op.d) && !conv_uses_w4h(&op.d) && !conv_uses_d3h(&op.d) && !conv_uses_d3h_s2(&op.d))
+    for (const Op &op : u->ops) {
+        const int family = op.kind == Op::CONV && !op.d.wpacked ? conv_family(&op.d) : 4;
+        if (family < 4 || family > 6)                               // 4, 5, 6: the F(4x4) family and the direct split-operand kernels
             set_error("read_unet_create: layer %s is not run by the F(4x4) kernel here and the lean blob carries no other fragment "
                       "order for it (pack with READ_UNET_LAYOUT_FULL)", op.label.c_str());
+    }
     if (read_last_error()[0]) {   // the builder reports plan inconsistencies through set_error
         delete u;
         return READ_EINVAL;
@@ -889,13 +883,13 @@ extern "C" int read_unet_profile(read_unet_t *u, const float *x0, const float *x
     for (int i = 0; i < n; ++i) {
         READ_CHECK_HIP(hipEventElapsedTime(&ms[i], u->events[i], u->events[i + 1]));
         if (flops) flops[i] = u->ops[i].flops;
-        // 0: other, 1: 3x3/s1 C->C direct, 2: the same through the Winograd kernel (2.25x fewer MFMA flops than `flops`)
-        if (is_conv3x3_s1)
-            // 0: not in the 3x3/s1 C->C family; 1: direct kernel; 2: Winograd F(2x2,3x3); 4: Winograd F(4x4,3x3)
-            //    5: Winograd F(4x4,3x3) with split operands on the f16 matrix cores
-            //    6: direct 3x3 with split operands on the f16 matrix cores
-            is_conv3x3_s1[i] = u->ops[i].is_c3s1 ? (u->ops[i].kind != Op::CONV ? 1 : conv_uses_d3h(&u->ops[i].d) ? 6 : conv_uses_w4h(&u->ops[i].d) ? 5 : conv_uses_w4(&u->ops[i].d) ? 4 :
-                                                     conv_uses_wino(&u->ops[i].d) ? 2 : 1) : 0;
+        // 0: not in the 3x3/s1 C->C family; else the kernel family that runs it (read_conv_kernel_family: 2 Winograd F(2x2,3x3), 4 F(4x4,3x3),
+        //    5 the same with split operands on the f16 matrix cores, 6 direct 3x3 with split operands), 1 for the direct fp32 kernels
+        //    (the Winograd kernels spend 2.25x / 4x fewer MFMA flops than `flops`)
+        if (is_conv3x3_s1) {
+            const int family = u->ops[i].is_c3s1 && u->ops[i].kind == Op::CONV ? conv_family(&u->ops[i].d) : 0;
+            is_conv3x3_s1[i] = u->ops[i].is_c3s1 ? (family ? family : 1) : 0;
+        }
     }
     return READ_OK;
 }
