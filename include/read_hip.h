@@ -253,6 +253,41 @@ int read_gather_forward(const float *rows_nc, int64_t n, int C, int levels,
 int read_gather_forward_ss(const float *rows_nc, int64_t n, int C, int levels, int B,
                            const int32_t *const *idx_levels, const int *h_levels, const int *w_levels, int ss,
                            float *const *feat_levels, int activation, void *stream);
+/*
+ * Scene stitching: several fitted scenes ("parts", 1..READ_STITCH_MAX_PARTS) in one frame.  Every part is rasterised on its own
+ * (read_splat_forward*, camera M_s = M_0 @ P_s) into a pyramid of LOCAL ids and depths; this call merges the pyramids and gathers
+ * from the winner's table, all levels in one launch.  Per level and pixel:
+ *   candidates  every visible part whose pixel is not the empty pattern (idx == 0 and depth bits == 0);
+ *   winner      the candidate with the smallest depth bit pattern (depths are >= 0: an unsigned compare, the order of the
+ *               rasteriser's 64-bit key); ties go to the lowest part number;
+ *   outputs     idx_l[p] = id_base[s] + local id, depth_l[p] = its depth, part_l[p] = s (uint8),
+ *               feat_l[p][:] = act_s(rows_s[local id][:]) (NHWC, C % 4 == 0) — bit for bit the values of read_gather_forward;
+ *   no candidate  idx 0, depth 0.0f, part 255, feat = act_0(rows_0[0]): the "empty pixels sample descriptor 0" rule applied to the
+ *               concatenation of the tables — parts[0] is that table WHETHER OR NOT part 0 is visible.
+ * With id_base[s] = sum of n_t over t < s (hidden parts included, so ids stay stable) and identity placements the result equals
+ * rasterising the concatenated cloud and gathering from the concatenated table.  One departure: a part's local point 0 at depth
+ * bit pattern 0 cannot be told from "empty" and loses.
+ * A HIDDEN part is passed with idx_levels == depth_levels == NULL: it keeps its part number and its id range, nothing of it is read
+ * except, for part 0, the row the no-candidate pixels sample.  (No pyramid of empties has to be allocated or streamed for it.)
+ * Each of the four output tables may be NULL (that output is skipped); without features one lane serves a pixel.  Local ids are
+ * clamped to [0, n) as in read_gather_forward.  Stream-ordered, allocates nothing, no synchronisation.  READ_EINVAL before any
+ * device work for: count outside 1..READ_STITCH_MAX_PARTS, C % 4 != 0, levels outside 1..READ_MAX_LEVELS, a null part table or
+ * count_levels, rows_nc == NULL while features are requested, id_base < 0 or id_base + n > INT32_MAX, all four outputs NULL, a part
+ * with only one of its two pyramids, a null level of a visible part or of a requested output.
+ */
+#define READ_STITCH_MAX_PARTS 8
+typedef struct read_stitch_part {
+    const int32_t *const *idx_levels;   /* host array of `levels` device pointers: this part's index images; NULL = hidden */
+    const float   *const *depth_levels; /* same shape: its depth images */
+    const float *rows_nc;               /* device, n x C; may be NULL when feat_levels is NULL */
+    int64_t n;
+    int32_t id_base;                    /* added to local ids in the merged index image */
+    int activation;                     /* 0 none, 1 sigmoid, 2 tanh */
+} read_stitch_part;
+int read_stitch_gather_forward(const read_stitch_part *parts, int count, int C, int levels,
+                               const int64_t *count_levels,
+                               int32_t *const *idx_levels, float *const *depth_levels,
+                               unsigned char *const *part_levels, float *const *feat_levels, void *stream);
 /* drows[idx_l[p]][c] += dfeat_l[p][c]   (fp32 atomics; drows must be zeroed by the caller). */
 int read_gather_backward(float *drows_nc, int64_t n, int C, int levels,
                          const int32_t *const *idx_levels, const int64_t *count_levels,

@@ -65,6 +65,15 @@ class SplatObjects(C.Structure):
                 ("M", C.c_void_p), ("visible", C.c_void_p)]
 
 
+READ_STITCH_MAX_PARTS = 8
+
+
+class StitchPart(C.Structure):
+    """read_stitch_part (include/read_hip.h): one part of a read_stitch_gather_forward call (idx/depth_levels NULL = hidden)."""
+    _fields_ = [("idx_levels", C.POINTER(C.c_void_p)), ("depth_levels", C.POINTER(C.c_void_p)), ("rows_nc", C.c_void_p),
+                ("n", C.c_int64), ("id_base", C.c_int32), ("activation", C.c_int)]
+
+
 _vp, _i, _i64, _sz, _f = C.c_void_p, C.c_int, C.c_int64, C.c_size_t, C.c_float
 _pp = C.POINTER(C.c_void_p)
 
@@ -108,6 +117,7 @@ SIGNATURES = {
     "read_gather_forward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _i, _vp]),
     "read_gather_forward_ss": (_i, [_vp, _i64, _i, _i, _i, _pp, C.POINTER(_i), C.POINTER(_i), _i, _pp, _i, _vp]),
     "read_gather_backward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _vp]),
+    "read_stitch_gather_forward": (_i, [C.POINTER(StitchPart), _i, _i, _i, C.POINTER(_i64), _pp, _pp, _pp, _pp, _vp]),
     "read_bilinear_down": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
     "read_bilinear_down_backward": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
     "read_conv_packed_floats": (_sz, [_i, _i, _i]),

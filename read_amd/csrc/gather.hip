@@ -7,6 +7,7 @@
 // receive descriptor[0], exactly as the reference (SURVEY.md "Empty pixels sample point 0").
 // Backward = scatter-add of dL/dfeat into the rows (autograd of texture.py:61).
 // HBM-bound: algorithmic bytes = sum_l px_l * (4 + 4C + 4C).
+// Scene stitching (stitch_gather_kernel): the same gather over S parts' pyramids, the nearest part per pixel — 8S + 4C + 4C.
 #include "common.h"
 
 using namespace readhip;
@@ -117,6 +118,68 @@ __global__ __launch_bounds__(256) void gather_forward_ss_kernel(const float *__r
         o.z = wy0 * (wx0 * v[0].z + lx * v[1].z) + ly * (wx0 * v[2].z + lx * v[3].z);
         o.w = wy0 * (wx0 * v[0].w + lx * v[1].w) + ly * (wx0 * v[2].w + lx * v[3].w);
         *reinterpret_cast<float4 *>(tab.feat[l] + pix * C + 4 * q) = o;
+    }
+}
+
+// Scene stitching: up to READ_STITCH_MAX_PARTS pyramids of local ids + depths -> per pixel the visible candidate with the smallest
+// depth bit pattern (ties: the lowest part), its descriptor row from ITS table with ITS activation, and optionally the merged
+// index / depth / part images.  Same item mapping as gather_forward_kernel; the tables travel by value in the kernel arguments.
+struct StitchTable {
+    const int32_t *idx[READ_STITCH_MAX_PARTS][READ_MAX_LEVELS];
+    const float *depth[READ_STITCH_MAX_PARTS][READ_MAX_LEVELS];
+    const float *rows[READ_STITCH_MAX_PARTS];
+    long long n[READ_STITCH_MAX_PARTS];
+    int id_base[READ_STITCH_MAX_PARTS];
+    int act[READ_STITCH_MAX_PARTS];
+    int32_t *out_idx[READ_MAX_LEVELS];        // each output: all levels set, or none (then the flag below is 0)
+    float *out_depth[READ_MAX_LEVELS];
+    unsigned char *out_part[READ_MAX_LEVELS];
+    float *feat[READ_MAX_LEVELS];
+    long long end[READ_MAX_LEVELS];
+    unsigned visible;                         // bit s: part s has a pyramid (a hidden part has none and is never read)
+    int levels, count;
+    int want_idx, want_depth, want_part, want_feat;
+};
+
+__global__ __launch_bounds__(256) void stitch_gather_kernel(StitchTable tab, int C)
+{
+    const int qpp = C >> 2;
+    const long long total = tab.end[tab.levels - 1];
+    for (long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x; item < total;
+         item += (long long)gridDim.x * blockDim.x) {
+        int l = 0;
+        long long base = 0;
+#pragma unroll
+        for (int k = 0; k < READ_MAX_LEVELS - 1; ++k)
+            if (k < tab.levels - 1 && item >= tab.end[k]) { l = k + 1; base = tab.end[k]; }
+        const long long local = item - base;
+        const long long pix = local / qpp;
+        const int q = (int)(local - pix * qpp);
+        // running winner by compare-and-select; the loop over parts is wave-uniform (count and visible are kernel arguments)
+        int win = -1, win_id = 0;
+        unsigned win_d = 0u;
+        for (int s = 0; s < tab.count; ++s) {
+            if (!((tab.visible >> s) & 1u)) continue;
+            const int id = tab.idx[s][l][pix];
+            const unsigned d = __float_as_uint(tab.depth[s][l][pix]);
+            const bool take = ((unsigned)id | d) != 0u && (win < 0 || d < win_d);     // strict <: a tie stays with the lower part
+            win = take ? s : win;
+            win_id = take ? id : win_id;
+            win_d = take ? d : win_d;
+        }
+        const int src = win < 0 ? 0 : win;                                            // no candidate: descriptor 0 of part 0
+        const long long n = tab.n[src];
+        long long id = win_id;
+        id = id < 0 ? 0 : (id >= n ? n - 1 : id);   // defensive clamp; ids come from the rasteriser
+        if (tab.want_feat) {
+            const float4 v = act4(*reinterpret_cast<const float4 *>(tab.rows[src] + id * C + 4 * q), tab.act[src]);
+            *reinterpret_cast<float4 *>(tab.feat[l] + pix * C + 4 * q) = v;
+        }
+        if (q == 0) {
+            if (tab.want_idx) tab.out_idx[l][pix] = win < 0 ? 0 : tab.id_base[src] + (int)id;
+            if (tab.want_depth) tab.out_depth[l][pix] = __uint_as_float(win_d);
+            if (tab.want_part) tab.out_part[l][pix] = (unsigned char)(win < 0 ? 255 : win);
+        }
     }
 }
 
@@ -321,6 +384,72 @@ extern "C" int read_gather_forward_ss(const float *rows_nc, int64_t n, int C, in
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(gather_forward_ss_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), rows_nc,
                        (long long)n, C, tab, ss, activation);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+extern "C" int read_stitch_gather_forward(const read_stitch_part *parts, int count, int C, int levels,
+                                          const int64_t *count_levels, int32_t *const *idx_levels, float *const *depth_levels,
+                                          unsigned char *const *part_levels, float *const *feat_levels, void *stream)
+{
+    const char *who = "read_stitch_gather_forward";
+    READ_CHECK_ARG(count >= 1 && count <= READ_STITCH_MAX_PARTS, "%s: count must be 1..%d parts (got %d)", who,
+                   READ_STITCH_MAX_PARTS, count);
+    READ_CHECK_ARG(C >= 4 && C % 4 == 0 && C <= 64, "%s: C must be a multiple of 4 in [4,64] (got %d)", who, C);
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d (got %d)", who, READ_MAX_LEVELS, levels);
+    READ_CHECK_ARG(parts && count_levels, "%s: null part table", who);
+    READ_CHECK_ARG(idx_levels || depth_levels || part_levels || feat_levels, "%s: no outputs (all four output tables are null)", who);
+    StitchTable tab;
+    memset(&tab, 0, sizeof(tab));
+    for (int s = 0; s < count; ++s) {
+        const read_stitch_part &p = parts[s];
+        READ_CHECK_ARG(!feat_levels || p.rows_nc, "%s: part %d: rows_nc is null while features are requested", who, s);
+        READ_CHECK_ARG(!feat_levels || (uintptr_t)p.rows_nc % 16 == 0, "%s: part %d: rows misaligned", who, s);
+        READ_CHECK_ARG(p.n >= 1, "%s: part %d: empty descriptor table", who, s);
+        READ_CHECK_ARG(p.id_base >= 0 && (int64_t)p.id_base + p.n <= (int64_t)INT32_MAX,
+                       "%s: part %d: id_base %d + n %lld leaves the int32 id range", who, s, p.id_base, (long long)p.n);
+        READ_CHECK_ARG(p.activation >= 0 && p.activation <= 2, "%s: part %d: activation must be 0,1,2", who, s);
+        READ_CHECK_ARG(!p.idx_levels == !p.depth_levels, "%s: part %d: index and depth pyramids go together (both, or both null = hidden)",
+                       who, s);
+        tab.rows[s] = p.rows_nc;
+        tab.n[s] = p.n;
+        tab.id_base[s] = p.id_base;
+        tab.act[s] = p.activation;
+        if (p.idx_levels) tab.visible |= 1u << s;
+    }
+    long long acc = 0;
+    const int Ck = feat_levels ? C : 4;       // without features one lane per pixel
+    const int qpp = Ck / 4;
+    for (int l = 0; l < levels; ++l) {
+        READ_CHECK_ARG(count_levels[l] >= 0, "%s: negative pixel count", who);
+        for (int s = 0; s < count; ++s) {
+            if (!parts[s].idx_levels) continue;
+            READ_CHECK_ARG(count_levels[l] == 0 || (parts[s].idx_levels[l] && parts[s].depth_levels[l]), "%s: part %d: null level %d",
+                           who, s, l);
+            tab.idx[s][l] = parts[s].idx_levels[l];
+            tab.depth[s][l] = parts[s].depth_levels[l];
+        }
+        READ_CHECK_ARG(count_levels[l] == 0 || ((!idx_levels || idx_levels[l]) && (!depth_levels || depth_levels[l]) &&
+                                                (!part_levels || part_levels[l]) && (!feat_levels || feat_levels[l])),
+                       "%s: null output level %d", who, l);
+        READ_CHECK_ARG(!feat_levels || (uintptr_t)feat_levels[l] % 16 == 0, "%s: feat level %d misaligned", who, l);
+        if (idx_levels) tab.out_idx[l] = idx_levels[l];
+        if (depth_levels) tab.out_depth[l] = depth_levels[l];
+        if (part_levels) tab.out_part[l] = part_levels[l];
+        if (feat_levels) tab.feat[l] = feat_levels[l];
+        acc += count_levels[l] * qpp;
+        tab.end[l] = acc;
+    }
+    tab.levels = levels;
+    tab.count = count;
+    tab.want_idx = idx_levels != nullptr;
+    tab.want_depth = depth_levels != nullptr;
+    tab.want_part = part_levels != nullptr;
+    tab.want_feat = feat_levels != nullptr;
+    if (acc == 0) return READ_OK;
+    int64_t blocks = ceil_div64(acc, 256);
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(stitch_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tab, Ck);
     READ_CHECK_LAUNCH();
     return READ_OK;
 }

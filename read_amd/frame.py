@@ -17,6 +17,23 @@ from .unet import LAYOUT_FULL, UNetEngine, default_layout, layout_of, pack_state
 LEVELS = 5          # the reference rasterises and gathers 5 scales; the UNet consumes 4 (unet.py:209-212)
 
 
+def unet_engine(unet_state, device, H, W):
+    """unet_state (see FrameRenderer) -> (packed fp32 blob on the device, its UNetEngine for H x W): what FrameRenderer and
+    StitchedFrameRenderer (read_amd/stitch.py) both start from."""
+    if torch.is_tensor(unet_state):
+        packed = unet_state.to(device, torch.float32).contiguous()       # full or lean: read off its length
+        return packed, UNetEngine(packed, H, W)
+    # the lean blob (451 of 952 MB: the F(4x4) layers carry their F(4x4) order only) unless the plan cannot be served by it
+    packed = torch.from_numpy(pack_state(unet_state, layout=default_layout())).to(device)
+    try:
+        return packed, UNetEngine(packed, H, W)
+    except _lib.ReadHipError:
+        if layout_of(packed) == LAYOUT_FULL:
+            raise
+        packed = torch.from_numpy(pack_state(unet_state, layout=LAYOUT_FULL)).to(device)
+        return packed, UNetEngine(packed, H, W)
+
+
 class FrameRenderer:
     def __init__(self, xyz, texture_cn, unet_state, W, H, proj_matrix=None, device=None, levels=LEVELS, cells=True,
                  frames_in_flight=1, object_labels=None):
@@ -43,19 +60,7 @@ class FrameRenderer:
                              f"{self.raster.n} points")
         tex = torch.as_tensor(texture_cn, dtype=torch.float32).to(self.device).contiguous()
         self.rows = texture_to_rows(tex)
-        if torch.is_tensor(unet_state):
-            self.packed = unet_state.to(self.device, torch.float32).contiguous()       # full or lean: read off its length
-            self.unet = UNetEngine(self.packed, H, W)
-        else:
-            # the lean blob (451 of 952 MB: the F(4x4) layers carry their F(4x4) order only) unless the plan cannot be served by it
-            self.packed = torch.from_numpy(pack_state(unet_state, layout=default_layout())).to(self.device)
-            try:
-                self.unet = UNetEngine(self.packed, H, W)
-            except _lib.ReadHipError:
-                if layout_of(self.packed) == LAYOUT_FULL:
-                    raise
-                self.packed = torch.from_numpy(pack_state(unet_state, layout=LAYOUT_FULL)).to(self.device)
-                self.unet = UNetEngine(self.packed, H, W)
+        self.packed, self.unet = unet_engine(unet_state, self.device, H, W)
         self.proj = None if proj_matrix is None else np.asarray(proj_matrix, np.float32)
         sizes = level_sizes(W, H, levels)
         self.idx = [torch.empty((1, h, w), dtype=torch.int32, device=self.device) for (w, h) in sizes]

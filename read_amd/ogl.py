@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from .render import MultiscaleRender, is_point_id_pyramid
-from .texture import gather_pyramid
+from .texture import gather_pyramid, stitch_gather_pyramid
 
 
 class OGL:
@@ -30,14 +30,16 @@ class OGL:
 
     @classmethod
     def from_model(cls, scene, model, input_format, viewport_size, out_buffer_location='torch', supersampling=1,
-                   temporal_average=False):
+                   temporal_average=False, texture_ids=None):
+        """texture_ids: for a ``render.StitchedScene`` the loaded texture of every part, in part order (default: the model's
+        loaded textures in their order)."""
         self = cls.__new__(cls)
         self._setup(scene, model, input_format, viewport_size, out_buffer_location, supersampling, True, None,
-                    temporal_average)
+                    temporal_average, texture_ids)
         return self
 
     def _setup(self, scene, model, input_format, viewport_size, out_buffer_location, supersampling, gpu, clear_color,
-               temporal_average):
+               temporal_average, texture_ids=None):
         if not gpu:
             raise _lib.ReadHipError("OGL(gpu=False): the render path has no CPU implementation")
         self.gpu = True
@@ -57,12 +59,25 @@ class OGL:
         fmts = input_format.replace(' ', '').split(',')
         self._fast_format = len(fmts) >= 4 and is_point_id_pyramid(input_format)
         self.last_path = None                # 'fast' / 'dict': which branch the last infer() took (asserted by the tests)
+        self.texture_ids = None if texture_ids is None else list(texture_ids)
+        if getattr(scene, 'stitched', False):
+            ids = list(model._loaded_textures) if texture_ids is None else self.texture_ids
+            if len(ids) != len(scene.scenes):
+                raise ValueError(f"{len(ids)} textures for a stitched scene of {len(scene.scenes)} parts")
+            missing = [t for t in ids if str(t) not in self.model._modules]
+            if missing:
+                raise ValueError(f"textures {missing} are not loaded (model.load_textures)")
+            self.texture_ids = ids
+        elif texture_ids is not None:
+            raise ValueError("texture_ids goes with a StitchedScene (one texture per part)")
 
     def infer(self, input_dict=None):
         """-> {'output': H x W x 4 float tensor (RGB + alpha 1), 'net_input': list of NCHW feature maps}; a caller-supplied
         ``input_dict`` (it must carry its own 'id') is rendered as it is and echoed under 'input', as the src tree's
         ``OGL.infer(input_dict)`` does (src/READ/gl/nn.py:115-137)."""
         model = self.model
+        if getattr(self.renderer.scene, 'stitched', False):
+            return self._infer_stitched(input_dict)
         texture = model._modules[str(model._loaded_textures[0])] if model._loaded_textures else model._modules['0']
         fast = (input_dict is None and not model.temporal_average and self._fast_format
                 and not self.renderer.scene.augmented() and hasattr(model.net, 'engine'))
@@ -97,3 +112,36 @@ class OGL:
         if input_dict is not None:
             res['input'] = input_dict
         return res
+
+    def _infer_stitched(self, input_dict):
+        """A StitchedScene: per-part raster with depth -> one stitched gather -> the engine.  Always the fast path; what it does
+        not serve is refused by name."""
+        model, scene = self.model, self.renderer.scene
+        if input_dict is not None:
+            raise NotImplementedError("a caller-supplied input_dict with scene stitching (StitchedScene)")
+        if model.temporal_average:
+            raise NotImplementedError("temporal_average with scene stitching (StitchedScene)")
+        if int(model.ss) > 1:
+            raise NotImplementedError(f"supersampling {int(model.ss)} with scene stitching (StitchedScene)")
+        if scene.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with scene stitching")
+        if not self._fast_format or not hasattr(model.net, 'engine'):
+            raise NotImplementedError(f"input format {self.input_format!r} with scene stitching (StitchedScene): only the point-id "
+                                      "pyramid of at least four scales on the HIP UNet is served")
+        textures = [model._modules[str(t)] for t in self.texture_ids]
+        raster = scene.rasterizer()
+        for s, tex in enumerate(textures):
+            if raster.part(s).n != tex.texture_.shape[-1]:
+                raise ValueError(f"part {s}: descriptor table has {tex.texture_.shape[-1]} points, the part's cloud "
+                                 f"{raster.part(s).n}")
+        self.last_path = 'fast'
+        W, H = self.viewport_size
+        fmts = self.input_format.replace(' ', '').split(',')
+        with torch.set_grad_enabled(False):
+            frames = raster.render(scene.total_matrix(), W, H, len(fmts), next_total=scene.take_next_total_matrix())
+            rows = [t.rows() for t in textures]
+            feats = [torch.empty((1, H >> l, W >> l, rows[0].shape[1]), dtype=torch.float32, device=rows[0].device)
+                     for l in range(len(fmts))]
+            stitch_gather_pyramid(raster.gather_parts(frames, [(r, t.activation) for r, t in zip(rows, textures)]), out=feats)
+            out = model.net.engine(H, W).forward(feats[0][0], feats[1][0], feats[2][0], feats[3][0], channels=4)
+        return {'output': out, 'net_input': [f.permute(0, 3, 1, 2) for f in feats]}

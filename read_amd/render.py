@@ -339,6 +339,110 @@ class Scene:
         return (self.proj_matrix @ view @ self.model_matrix).astype(np.float32)[None]
 
 
+class StitchedScene:
+    """Extension (not in NNScene): several ``Scene`` objects ("parts", 1..8) drawn into one frame — scene stitching
+    (read_amd/stitch.py).  Part s is placed by ``set_part_pose(s, P)`` (M_s = M_0 @ P_s, P None = identity) and hidden or shown by
+    ``set_part_visible``; neither rebuilds anything.  The camera setters fan out to every part, and the frame's camera M_0 is
+    part 0's.  Object edits of a part go through that part's own ``Scene`` (``scenes[s].set_object_pose`` ...).  Merged point ids
+    are id_base[s] + local id, id_base[s] = the point count of the parts before s, hidden ones included."""
+
+    stitched = True
+
+    def __init__(self, scenes, poses=None):
+        scenes = list(scenes)
+        if not 1 <= len(scenes) <= 8:
+            raise ValueError(f"a stitched frame has 1..8 parts, got {len(scenes)}")
+        if poses is not None and len(poses) != len(scenes):
+            raise ValueError(f"poses has {len(poses)} entries for {len(scenes)} parts")
+        self.scenes = scenes
+        self.part_poses = [None] * len(scenes)
+        self.part_hidden = set()
+        self._raster = None
+        for s, P in enumerate(poses or ()):
+            self.set_part_pose(s, P)
+
+    def _index(self, s):
+        s = int(s)
+        if not 0 <= s < len(self.scenes):
+            raise ValueError(f"no part {s}: parts 0..{len(self.scenes) - 1}")
+        return s
+
+    def counts(self):
+        return [0 if sc.xyz is None else int(sc.xyz.shape[0]) for sc in self.scenes]
+
+    def id_base(self):
+        """First merged id of every part: the counts of the parts before it, whether or not they are visible."""
+        c = self.counts()
+        return [sum(c[:s]) for s in range(len(c))]
+
+    def set_part_pose(self, s, P):
+        s = self._index(s)
+        self.part_poses[s] = None if P is None else np.array(P, np.float32).reshape(4, 4)
+        if self._raster is not None:
+            self._raster.set_part_pose(s, self.part_poses[s])
+
+    def set_part_visible(self, s, flag):
+        s = self._index(s)
+        (self.part_hidden.discard if flag else self.part_hidden.add)(s)
+        if self._raster is not None:
+            self._raster.set_part_visible(s, flag)
+
+    def part_visible(self, s):
+        return self._index(s) not in self.part_hidden
+
+    # ---- the camera state of every part moves together ---------------------------------------------------------------------
+    def set_camera_view(self, m):
+        for sc in self.scenes:
+            sc.set_camera_view(m)
+
+    def set_proj_matrix(self, m):
+        for sc in self.scenes:
+            sc.set_proj_matrix(m)
+
+    def set_model_view(self, m):
+        for sc in self.scenes:
+            sc.set_model_view(m)
+
+    def announce_next_camera_view(self, m):
+        for sc in self.scenes:
+            sc.announce_next_camera_view(m)
+
+    def set_use_light(self, use_light):
+        for sc in self.scenes:
+            sc.set_use_light(use_light)
+
+    def total_matrix(self):
+        return self.scenes[0].total_matrix()
+
+    def take_next_total_matrix(self):
+        nxt = [sc.take_next_total_matrix() for sc in self.scenes]          # consumed on every part; the frame's is part 0's
+        return nxt[0]
+
+    def augmented(self):
+        return any(sc.augmented() for sc in self.scenes)
+
+    def edited(self):
+        return any(sc.edited() for sc in self.scenes)
+
+    def delete(self):
+        for sc in self.scenes:
+            sc.delete()
+        self._raster = None
+
+    def rasterizer(self):
+        """The StitchedRasterizer over the parts' own rasterisers, built lazily like ``Scene.rasterizer()`` and rebuilt only when
+        a part rebuilt its own (new vertices, new labels)."""
+        from .stitch import StitchedRasterizer
+        rs = [sc.rasterizer() for sc in self.scenes]
+        if self._raster is None or any(a is not b for a, b in zip(self._raster.parts, rs)):
+            self._raster = StitchedRasterizer(rs)
+            for s, P in enumerate(self.part_poses):
+                self._raster.set_part_pose(s, P)
+            for s in self.part_hidden:
+                self._raster.set_part_visible(s, False)
+        return self._raster
+
+
 class MultiscaleRender:
     """READ/datasets/dynamic.py:50-99 without OpenGL: one HIP pass fills all five scales; the
     result dict maps each input_format token to an (h, w, 3) float tensor with the point id in
@@ -367,6 +471,8 @@ class MultiscaleRender:
         scene = self.scene
         W, H = self.ss * self.viewport_size[0], self.ss * self.viewport_size[1]
         out = {}
+        if getattr(scene, 'stitched', False):
+            return self._render_stitched(scene, input_format, fmts, W, H)
         pyramid = is_point_id_pyramid(input_format) and W % (1 << (len(fmts) - 1)) == 0 and H % (1 << (len(fmts) - 1)) == 0
         if scene.edited() and scene.augmented():
             raise NotImplementedError("scene objects (set_object_labels) with GL-twin augmentation (point sizes, discard, drop, "
@@ -394,6 +500,22 @@ class MultiscaleRender:
             x = self._render_token(cfg, w, h)
             out[fmt] = self._package(x, fmt)
         return out
+
+    def _render_stitched(self, scene, input_format, fmts, W, H):
+        """A StitchedScene: the point-id pyramid of merged global ids; everything else is refused by name."""
+        if self.ss > 1:
+            raise NotImplementedError(f"supersampling {self.ss} with scene stitching (StitchedScene)")
+        if scene.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with scene stitching")
+        if not is_point_id_pyramid(input_format):
+            bad = next(f for i, f in enumerate(fmts) if not is_point_id_pyramid(','.join(fmts[:i + 1])))
+            raise NotImplementedError(f"token {bad!r} with scene stitching (StitchedScene): only the point-id pyramid is merged")
+        if W % (1 << (len(fmts) - 1)) or H % (1 << (len(fmts) - 1)):
+            raise NotImplementedError(f"scene stitching at {W}x{H}: the point-id pyramid needs sizes that are multiples of "
+                                      f"{1 << (len(fmts) - 1)}")
+        idx, _ = scene.rasterizer().render_merged(scene.total_matrix(), W, H, len(fmts), want_depth=False)
+        self.last_index = idx
+        return {fmt: self._package(self._id_image(ids_l[0]), fmt) for fmt, ids_l in zip(fmts, idx)}
 
     # ---- one token = one GL draw of the reference (READ/gl/render.py:52-85) -------------------------------------------
     def _id_image(self, ids):

@@ -60,6 +60,69 @@ def gather_pyramid(rows_nc, idx_levels, activation="none", out=None, ss=1):
     return out
 
 
+def stitch_gather_pyramid(parts, out=None, want_index=False, want_depth=False, want_part=False, want_feat=True, ss=1):
+    """Scene stitching (read_stitch_gather_forward): merge the parts' pyramids and gather from the winner's table, one launch.
+
+    parts: list of ``(rows_nc, idx_levels, depth_levels, id_base, activation)``, 1..8 of them — rows (n_s, C) CUDA tensor (with
+    want_feat=False the part's point count n_s, an int, does as well), int32 local-id maps and fp32 depth maps [(1,h,w)...] of
+    this part's rasteriser (both None = the part is hidden: it keeps its number and its id range, and part 0 still serves the
+    pixels nobody covers), id_base added to its ids in the merged index image, activation 'none' / 'sigmoid' / 'tanh'.
+    out: None, a list of NHWC feature tensors to fill (as gather_pyramid's), or a dict with any of 'feat', 'index', 'depth', 'part'
+    (lists of tensors per level) to fill instead of allocating.
+    -> the feature maps [(1,h,w,C)...] alone when no merged image is requested, otherwise the tuple (features, then the
+    requested ones of: merged index int32, merged depth fp32, part image uint8 (255 = no candidate)), each [(1,h,w)...];
+    features are None with want_feat=False."""
+    if ss > 1:
+        raise NotImplementedError("stitch_gather_pyramid: supersampling (ss > 1) is not supported with stitching")
+    if not 1 <= len(parts) <= _lib.READ_STITCH_MAX_PARTS:
+        raise ValueError(f"a stitched frame has 1..{_lib.READ_STITCH_MAX_PARTS} parts, got {len(parts)}")
+    if not isinstance(out, dict):
+        out = {} if out is None else {'feat': out}
+    shown = next((p for p in parts if p[1] is not None), None)
+    like = shown[1] if shown is not None else next((v for v in out.values() if v is not None), None)
+    if like is None:
+        raise ValueError("every part is hidden and no output buffers were given: the image sizes are unknown")
+    levels = len(like)
+    shapes = [tuple(t.shape[:3]) for t in like]
+    device = like[0].device
+    rows0 = parts[0][0]
+    Cc = int(rows0.shape[1]) if torch.is_tensor(rows0) else 4
+    keep, table = [], (_lib.StitchPart * len(parts))()
+    for s, (rows, idx, dep, id_base, activation) in enumerate(parts):
+        if (idx is None) != (dep is None):
+            raise ValueError(f"part {s}: index and depth pyramids go together (both None = hidden)")
+        if want_feat and (not torch.is_tensor(rows) or int(rows.shape[1]) != Cc):
+            raise ValueError(f"part {s}: descriptor rows missing or not {Cc} channels wide")
+        if idx is not None:
+            if len(idx) != levels or len(dep) != levels or any(tuple(i.shape) != sh or tuple(d.shape) != sh
+                                                               for i, d, sh in zip(idx, dep, shapes)):
+                raise ValueError(f"part {s}: pyramid shapes differ from {shapes}")
+            ip, dp = _lib.ptr_array([i.data_ptr() for i in idx]), _lib.ptr_array([d.data_ptr() for d in dep])
+            keep += [ip, dp]
+            table[s].idx_levels, table[s].depth_levels = ip, dp
+        table[s].rows_nc = rows.data_ptr() if torch.is_tensor(rows) else None
+        table[s].n = int(rows.shape[0]) if torch.is_tensor(rows) else int(rows)
+        table[s].id_base = int(id_base)
+        table[s].activation = _ACT[activation]
+
+    def buffers(name, want, dtype, tail=()):
+        if not want:
+            return None
+        if out.get(name) is None:
+            out[name] = [torch.empty(sh + tail, dtype=dtype, device=device) for sh in shapes]
+        return out[name]
+    feat = buffers('feat', want_feat, torch.float32, (Cc,))
+    index = buffers('index', want_index, torch.int32)
+    depth = buffers('depth', want_depth, torch.float32)
+    part = buffers('part', want_part, torch.uint8)
+    counts = (C.c_int64 * levels)(*[sh[0] * sh[1] * sh[2] for sh in shapes])
+    arr = lambda ts: None if ts is None else _lib.ptr_array([t.data_ptr() for t in ts])
+    _lib.check(_lib.lib().read_stitch_gather_forward(table, len(parts), Cc, levels, counts, arr(index), arr(depth), arr(part),
+                                                     arr(feat), _lib.stream_ptr()), "read_stitch_gather_forward")
+    extra = tuple(x for x, w in ((index, want_index), (depth, want_depth), (part, want_part)) if w)
+    return (feat,) + extra if extra else feat
+
+
 def scatter_pyramid(dfeat_levels, idx_levels, n):
     """Backward of gather_pyramid: -> (N, C) gradient rows (fp32 atomics)."""
     Cc = dfeat_levels[0].shape[-1]
