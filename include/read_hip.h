@@ -185,6 +185,27 @@ int read_splat_forward_objects(const float *xyz_static, const int32_t *ids_stati
                                int32_t *const *idx_levels, float *const *depth_levels, void *workspace, size_t workspace_bytes,
                                void *stream);
 
+/* Panorama camera: cylindrical projection (csrc/splat.hip, splat_pano_kernel; the definition is tests/pano_model.py).  cam_host =
+ * 16 floats on the host (camera.pano_camera): [0..11] three rows applied to (x, y, z, 1) giving c0 = x_c, c1 = P[1,1] y_c and
+ * c3 = -z_c (the forward distance), [12] kx = 2 / hfov_rad, [13] ky = P[1,2], [14] za = P[2,2], [15] zb = P[2,3].  Per point, in
+ * fp32 without fused operations: rho = sqrt(c0 c0 + c3 c3), nx = atan2(c0, c3) kx, ny = c1 / rho - ky, nz = (zb - za rho) / rho,
+ * then pixel and depth as in every pass.  Per pixel the minimum (depth, id) wins, empty pixels are (0, 0.0f), levels are formed
+ * as in read_splat_forward.
+ *
+ * xyz / ids / n (device): the cloud, or a labelled cloud's static part; ids == NULL: the id is the point's index.  objs: NULL, or
+ * the objects of read_splat_forward_objects with objs->M = count x 16 floats in the panorama layout (the rows of object k are
+ * (R4 @ P_k)[:3], R4 = the camera's rows with (0, 0, 0, 1) beneath; the four scalars repeat).  With objs == NULL and ids == NULL
+ * the previous frame's winners warm-start the pass; nothing is culled (a cylinder does not take a box to the hull of its
+ * corners).  Stream-ordered, allocates nothing, no synchronisation; workspace of read_splat_workspace_bytes(1, W, H), left
+ * EMPTY — pinhole and panorama frames may alternate on it.  READ_EINVAL before any device work for null pointers, W or H not a
+ * multiple of 2^(levels-1), non-finite camera entries, kx outside [1/pi, inf), and a malformed objs->begin. */
+int read_splat_forward_pano(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H, int levels,
+                            const read_splat_objects *objs, int32_t *const *idx_levels, float *const *depth_levels,
+                            void *workspace, size_t workspace_bytes, void *stream);
+/* read_splat_project_points under a panorama camera: the same device function as read_splat_forward_pano's pass. */
+int read_splat_pano_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel, float *depth,
+                                   void *stream);
+
 /* Measurement aid for bench.py (roofline.mfma_sustained): one workgroup of four waves per CU, every wave `iters` rounds of 16 independent
  * v_mfma_f32_16x16x4_f32 and nothing else.  scratch: >= 256 floats per CU on the device (never written); *flops receives the number of
  * floating-point operations the launch executes — the caller times the launch on `stream`.  Not on the render path. */

@@ -105,6 +105,8 @@ SIGNATURES = {
     "read_splat_cells_invalidate": (_i, [_vp, _i64]),
     "read_splat_cells_build_ids": (_i, [_vp, _vp, _i64, _vp, _sz, _vp, _sz, _vp]),
     "read_splat_forward_objects": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
+    "read_splat_forward_pano": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
+    "read_splat_pano_project_points": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp]),
     "read_splat_forward_cells": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _i, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_hint_next_camera": (_i, [_vp, C.POINTER(_f)]),
     "read_splat_profile_last": (_i, [C.POINTER(_f)]),

@@ -1288,6 +1288,101 @@ __global__ __launch_bounds__(256) void splat_objects_kernel(const float *__restr
     if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
 }
 
+// ---- panorama camera: cylindrical projection (read_splat_forward_pano) ------------------------------------------------------
+// Only the per-point projection differs from the pinhole; keys, z-test, resolve, gather and UNet are the frame's as ever.  The
+// camera is 16 floats formed on the host (camera.pano_camera): c[0..11] three rows applied to (x, y, z, 1) — c0 = x_c,
+// c1 = P[1,1] y_c, c3 = -z_c —, c[12] = kx = 2 / hfov_rad, c[13] = ky = P[1,2], c[14] = za = P[2,2], c[15] = zb = P[2,3].
+// tests/pano_model.py is the definition; this restates it: fp32, no contraction, sums left to right, IEEE division, correctly
+// rounded square root.  No chunk culling here: a cylinder does not map a box to the hull of its corners.
+//
+// atan2 of the model: t = small / large of (|a|, |b|) by compare-and-select (NaN takes the 'false' side, as NumPy's where),
+// Abramowitz & Stegun 4.4.49 by Horner in t^2, then the octant fix-ups.  The literals are the model's ATAN_COEFFS, bit for bit.
+__device__ __forceinline__ float pano_atan2(float a, float b)
+{
+    const float ax = fabsf(a), az = fabsf(b);
+    const bool swap = ax > az;
+    const float large = swap ? ax : az, small = swap ? az : ax;
+    const float t = large == 0.0f ? 0.0f : small / large;
+    const float s = t * t;
+    float p = 0.0028662257f;
+    p = p * s + -0.0161657367f;
+    p = p * s + 0.0429096138f;
+    p = p * s + -0.0752896400f;
+    p = p * s + 0.1065626393f;
+    p = p * s + -0.1420889944f;
+    p = p * s + 0.1999355085f;
+    p = p * s + -0.3333314528f;
+    p = p * s + 1.0f;
+    float r = p * t;
+    if (swap) r = 1.57079632679489661923f - r;
+    if (b < 0.0f) r = 3.14159265358979323846f - r;
+    return copysignf(r, a);
+}
+
+// One point under one panorama camera; returns the pixel or -1.  rho = 0, NaN and Inf fall out through `inside`.
+__device__ __forceinline__ int project_pano_one(float x, float y, float z, const float *c, int W, int H,
+                                                float &depth, int &xx_out, int &yy_out)
+{
+    const float c0 = c[0] * x + c[1] * y + c[2] * z + c[3] * 1.0f;
+    const float c1 = c[4] * x + c[5] * y + c[6] * z + c[7] * 1.0f;
+    const float c3 = c[8] * x + c[9] * y + c[10] * z + c[11] * 1.0f;
+    const float rho = __builtin_sqrtf(c0 * c0 + c3 * c3);
+    const float theta = pano_atan2(c0, c3);
+    const float nx = theta * c[12];
+    const float ny = c1 / rho - c[13];
+    const float nz = (c[15] - c[14] * rho) / rho;
+    // from here on: the tail of project_one
+    const bool inside = (nx >= -1.0f) & (nx <= 1.0f) & (ny >= -1.0f) & (ny <= 1.0f) &
+                        (nz >= -1.0f) & (nz <= 1.0f);
+    const float u = ((float)W * (nx + 1.0f)) * 0.5f;
+    const float v = ((float)H * (1.0f - ny)) * 0.5f;
+    depth = (nz + 1.0f) * 0.5f;
+    const int xx = (int)u, yy = (int)v;
+    const bool ok = inside & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H);
+    xx_out = xx;
+    yy_out = yy;
+    return ok ? yy * W + xx : -1;
+}
+
+// splat_objects_kernel under panorama cameras: ob.m[k] holds range k's 16 camera floats.  The whole cloud (or a labelled cloud's
+// static part) is one range; ids == NULL: the id is the point's index.
+__global__ __launch_bounds__(256) void splat_pano_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
+                                                         ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys,
+                                                         KeySlots ks)
+{
+    const int b = (int)blockIdx.x;
+    int j = 0;
+    for (int k = 1; k < ob.count; ++k)
+        if (b >= ob.block0[k]) j = k;
+    const long long i = ob.first[j] + (long long)(b - ob.block0[j]) * 256 + threadIdx.x;
+    if (i >= ob.last[j]) return;
+    float d;
+    int xx, yy;
+    const int pix = project_pano_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], W, H, d, xx, yy);
+    if (pix < 0) return;
+    const unsigned id = ids ? (unsigned)ids[i] : (unsigned)i;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | id;
+    unsigned long long *k = keys + key_slot(ks, (unsigned)pix);
+    if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
+}
+
+// Warm start of an unlabelled panorama frame: splat_seed_kernel under the panorama camera.  Last frame's winners (the resolve's
+// keep = 1 image) are folded in first, so the big pass's early-out works from its first wave; seeds are real points: exact.
+__global__ __launch_bounds__(256) void splat_pano_seed_kernel(const float *__restrict__ xyz, long long n, Cam1 cam,
+                                                              int W, int H, unsigned long long *__restrict__ keys,
+                                                              const SplatHeader *hdr, const int *__restrict__ prev_idx)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= W * H || !prev_idx) return;
+    if (!(hdr->valid == 1 && hdr->W == W && hdr->H == H)) return;
+    const int id = prev_idx[p];
+    if (id < 0 || id >= n) return;
+    float d;
+    int xx, yy;
+    const int pix = project_pano_one(xyz[3ll * id], xyz[3ll * id + 1], xyz[3ll * id + 2], cam.m, W, H, d, xx, yy);
+    if (pix >= 0) fold_key_agent(keys + pix, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id);
+}
+
 struct ResolveOut {
     int32_t *idx[READ_MAX_LEVELS];
     float *depth[READ_MAX_LEVELS];
@@ -1703,11 +1798,14 @@ struct ObjectsDraw {
 };
 
 int objects_flush(ObjBatch &ob, int &blocks, const float *xyz, const int32_t *ids, int W, int H, unsigned long long *keys,
-                  KeySlots ks, hipStream_t stream)
+                  KeySlots ks, hipStream_t stream, bool pano = false)
 {
     if (ob.count == 0) return READ_OK;
     ob.block0[ob.count] = blocks;
-    hipLaunchKernelGGL(splat_objects_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys, ks);
+    if (pano)
+        hipLaunchKernelGGL(splat_pano_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys, ks);
+    else
+        hipLaunchKernelGGL(splat_objects_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys, ks);
     READ_CHECK_LAUNCH();
     ob.count = 0;
     blocks = 0;
@@ -1725,21 +1823,22 @@ void objects_add(ObjBatch &ob, int &blocks, int64_t first, int64_t last, const f
 }
 
 // Every visible, non-empty range of `od` into the key image: stream-ordered, OBJ_MAX ranges per launch, no synchronisation.
-int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, KeySlots ks, hipStream_t stream)
+// pano: the matrices are panorama cameras (splat_pano_kernel), and ids0 may be NULL (the static range's ids are its indices).
+int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, KeySlots ks, hipStream_t stream, bool pano = false)
 {
     ObjBatch ob;
     memset(&ob, 0, sizeof(ob));
     int blocks = 0, rc;
     if (od.n0 > 0) {
         objects_add(ob, blocks, 0, od.n0, od.M0);
-        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, ks, stream)) != READ_OK) return rc;
+        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
     }
     for (int k = 0; k < od.count; ++k) {
         if ((od.visible && !od.visible[k]) || od.begin[k + 1] == od.begin[k]) continue;     // hidden or empty: not launched
         objects_add(ob, blocks, od.begin[k], od.begin[k + 1], od.M + 16 * (size_t)k);
-        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream)) != READ_OK) return rc;
+        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
     }
-    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream);
+    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream, pano);
 }
 
 // ---- per-kernel durations of the LAST cell-path frame (read_tuning_set("splat_prof", 1) + read_splat_profile_last): HIP events
@@ -2806,6 +2905,98 @@ extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t
     return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
 }
 
+namespace {
+// the host-side conditions on a panorama camera: 16 finite floats, kx = 2 / hfov_rad with hfov in (0, 2 pi]
+const char *pano_cam_fault(const float *c)
+{
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(c[i])) return "a camera entry is not finite";
+    if (!(c[12] >= (float)(1.0 / 3.14159265358979323846))) return "kx = 2 / hfov_rad must be >= 1 / pi (a field of at most 360 degrees)";
+    return nullptr;
+}
+}  // namespace
+
+// Panorama frame: the whole cloud (objs NULL; the previous frame's winners warm-start it) or a labelled cloud's static part plus
+// its objects (no seeds), one range launch each way, then the resolve every frame ends with.  Every check precedes the first launch.
+extern "C" int read_splat_forward_pano(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H, int levels,
+                                       const read_splat_objects *objs, int32_t *const *idx_levels, float *const *depth_levels,
+                                       void *ws, size_t ws_bytes, void *stream)
+{
+    READ_CHECK_ARG(cam_host && ws, "read_splat_forward_pano: null pointer (cam_host or workspace)");
+    READ_CHECK_ARG(idx_levels || depth_levels, "read_splat_forward_pano: no outputs requested");
+    READ_CHECK_ARG(n >= 0 && n <= 0xFFFFFFFEll, "read_splat_forward_pano: n out of range");
+    READ_CHECK_ARG(n == 0 || xyz, "read_splat_forward_pano: null pointer (xyz)");
+    if (objs) {
+        READ_CHECK_ARG(objs->count >= 0 && objs->n >= 0 && objs->n <= 0xFFFFFFFEll,
+                       "read_splat_forward_pano: objs->count / objs->n out of range");
+        READ_CHECK_ARG(objs->count == 0 || (objs->begin && objs->M), "read_splat_forward_pano: null pointer (objs->begin or objs->M)");
+        READ_CHECK_ARG(objs->n == 0 || (objs->xyz && objs->ids), "read_splat_forward_pano: null pointer (objs->xyz or objs->ids)");
+        if (objs->count > 0) {
+            READ_CHECK_ARG(objs->begin[0] == 0, "read_splat_forward_pano: objs->begin[0] = %lld, not 0", (long long)objs->begin[0]);
+            for (int k = 0; k < objs->count; ++k)
+                READ_CHECK_ARG(objs->begin[k] <= objs->begin[k + 1], "read_splat_forward_pano: objs->begin is not monotone at %d", k);
+            READ_CHECK_ARG(objs->begin[objs->count] == objs->n, "read_splat_forward_pano: objs->begin[count] = %lld != objs->n = %lld",
+                           (long long)objs->begin[objs->count], (long long)objs->n);
+        } else
+            READ_CHECK_ARG(objs->n == 0, "read_splat_forward_pano: objs->begin[count] = 0 != objs->n = %lld", (long long)objs->n);
+    }
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "read_splat_forward_pano: levels must be 1..%d", READ_MAX_LEVELS);
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_forward_pano: bad size (%d,%d)", W, H);
+    const int mask = (1 << (levels - 1)) - 1;
+    READ_CHECK_ARG(((W | H) & mask) == 0, "read_splat_forward_pano: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", W, H,
+                   mask + 1);
+    const char *fault = pano_cam_fault(cam_host);
+    READ_CHECK_ARG(!fault, "read_splat_forward_pano: cam_host: %s", fault);
+    if (objs)
+        for (int k = 0; k < objs->count; ++k) {
+            if ((objs->visible && !objs->visible[k]) || objs->begin[k + 1] == objs->begin[k]) continue;
+            fault = pano_cam_fault(objs->M + 16 * (size_t)k);
+            READ_CHECK_ARG(!fault, "read_splat_forward_pano: objs->M of object %d: %s", k, fault);
+        }
+    READ_CHECK_ARG((uintptr_t)ws % 256 == 0, "read_splat_forward_pano: workspace must be 256-byte aligned");
+    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
+        set_error("read_splat_forward_pano: workspace %zu < %zu bytes", ws_bytes, read_splat_workspace_bytes(1, W, H));
+        return READ_ENOMEM;
+    }
+    const WsLayout L = ws_layout(ws, 1, W, H);
+    hipStream_t s = as_stream(stream);
+    {
+        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
+        auto it = g_ws_host.find(ws);
+        if (it != g_ws_host.end()) {
+            it->second.hinted = false;
+            const int rc = ws_drop_prediction(it->second, s);
+            if (rc != READ_OK) return rc;
+        }
+    }
+    ObjectsDraw od;
+    memset(&od, 0, sizeof(od));
+    if (objs) {
+        od.xyz = objs->xyz;
+        od.ids = objs->ids;
+        od.begin = objs->begin;
+        od.M = objs->M;
+        od.visible = objs->visible;
+        od.count = objs->count;
+    }
+    od.xyz0 = xyz;
+    od.ids0 = ids;
+    od.n0 = n;
+    od.M0 = cam_host;
+    // seeds carry implicit ids: only a cloud drawn whole, with its indices as ids, keeps and uses them
+    const bool seeds = !objs && !ids && n > 0 && g_splat_mode == MODE_HIZ;
+    if (seeds && g_splat_seeds) {
+        Cam1 cam;
+        memcpy(cam.m, cam_host, sizeof(cam.m));
+        hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, xyz, (long long)n, cam, W, H, L.keys,
+                           (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
+        READ_CHECK_LAUNCH();
+    }
+    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s, true);
+    if (rc != READ_OK) return rc;
+    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
+}
+
 extern "C" int read_splat_forward_gl(const float *xyz, int64_t n, const float *M_host, int W, int H,
                                      const read_splat_gl_opts *opts, int32_t *idx, float *depth, void *ws,
                                      size_t ws_bytes, void *stream)
@@ -2877,6 +3068,40 @@ extern "C" int read_splat_project_points(const float *xyz, int64_t n, const floa
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(project_points_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), xyz, (long long)n, cam, W,
                        H, pixel, depth);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+namespace {
+// project_points_kernel under a panorama camera: project_pano_one as the frame's passes use it, without the z-test.
+__global__ __launch_bounds__(256) void pano_project_points_kernel(const float *__restrict__ xyz, long long n, Cam1 cam, int W, int H,
+                                                                  int32_t *__restrict__ pixel, float *__restrict__ depth)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float d;
+        int xx, yy;
+        const int pix = project_pano_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cam.m, W, H, d, xx, yy);
+        pixel[i] = pix;
+        if (depth) depth[i] = d;
+    }
+}
+}  // namespace
+
+extern "C" int read_splat_pano_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel,
+                                              float *depth, void *stream)
+{
+    READ_CHECK_ARG(n >= 0 && (n == 0 || (xyz && pixel)), "read_splat_pano_project_points: null pointer");
+    READ_CHECK_ARG(cam_host, "read_splat_pano_project_points: cam_host is null");
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_pano_project_points: bad W/H (%d,%d)", W, H);
+    const char *fault = pano_cam_fault(cam_host);
+    READ_CHECK_ARG(!fault, "read_splat_pano_project_points: cam_host: %s", fault);
+    if (n == 0) return READ_OK;
+    Cam1 cam;
+    for (int i = 0; i < 16; ++i) cam.m[i] = cam_host[i];
+    long long blocks = ceil_div64(n, 256);
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(pano_project_points_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), xyz, (long long)n, cam,
+                       W, H, pixel, depth);
     READ_CHECK_LAUNCH();
     return READ_OK;
 }

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .camera import level_sizes, total_matrix
+from .camera import level_sizes, pano_camera, total_matrix
 from .raster import PointCloudRasterizer
 from .texture import gather_pyramid, texture_to_rows
 from .unet import LAYOUT_FULL, UNetEngine, default_layout, layout_of, pack_state
@@ -99,6 +99,9 @@ class FrameRenderer:
     def rasterize(self, total_m, next_total=None):
         return self.raster.render(total_m, self.W, self.H, self.levels, out=(self.idx, self.depth), next_total=next_total)
 
+    def rasterize_pano(self, cam):
+        return self.raster.render_pano(cam, self.W, self.H, self.levels, out=(self.idx, self.depth))
+
     def gather(self):
         return gather_pyramid(self.rows, self.idx, out=self.feat)
 
@@ -110,8 +113,15 @@ class FrameRenderer:
     def render_total(self, total_m, out=None, channels=4, next_total=None):
         """total_m = proj @ inv(view) (4x4 fp32) -> (H,W,channels) fp32 frame on the device.
         next_total: the NEXT call's matrix when the caller knows it (PointCloudRasterizer.render): one launch less per frame."""
+        return self._frame(lambda: self.rasterize(total_m, next_total), out, channels)
+
+    def render_pano_total(self, cam, out=None, channels=4):
+        """render_total's twin for a panorama camera (the 16 floats of camera.pano_camera): only the raster step differs."""
+        return self._frame(lambda: self.rasterize_pano(cam), out, channels)
+
+    def _frame(self, rasterize, out, channels):
         if not self._slots:
-            self.rasterize(total_m, next_total)
+            rasterize()
             self.gather()
             return self.refine(out, channels)
         slot = self._slots[self._calls % len(self._slots)]
@@ -124,7 +134,7 @@ class FrameRenderer:
         rs = self._raster_stream
         with torch.cuda.stream(rs):
             rs.wait_event(slot["done"])                  # this slot's features were last read by the frame F calls ago
-            self.rasterize(total_m, next_total)
+            rasterize()
             gather_pyramid(self.rows, self.idx, out=slot["feat"])
             slot["ready"].record(rs)
         us = slot["stream"]
@@ -151,3 +161,12 @@ class FrameRenderer:
         if proj is None:
             raise ValueError("no projection matrix set")
         return self.render_total(total_matrix(proj, view_matrix), out, channels)
+
+    def render_pano(self, view_matrix, hfov_deg, proj_matrix=None, out=None, channels=4):
+        """A panorama (cylindrical) frame with a horizontal field of hfov_deg in (0, 360]: view_matrix camera->world; of the
+        projection matrix only the vertical scale / offset and the depth entries are used (camera.pano_camera).  Object edits
+        apply; frames_in_flight as for ``render_total``."""
+        proj = self.proj if proj_matrix is None else np.asarray(proj_matrix, np.float32)
+        if proj is None:
+            raise ValueError("no projection matrix set")
+        return self.render_pano_total(pano_camera(proj, view_matrix, hfov_deg), out, channels)

@@ -81,6 +81,9 @@ class OGL:
         texture = model._modules[str(model._loaded_textures[0])] if model._loaded_textures else model._modules['0']
         fast = (input_dict is None and not model.temporal_average and self._fast_format
                 and not self.renderer.scene.augmented() and hasattr(model.net, 'engine'))
+        pano = getattr(self.renderer.scene, 'panorama', None) is not None
+        if pano:
+            self._require_pano_fast(input_dict)
         self.last_path = 'fast' if fast else 'dict'
         with torch.set_grad_enabled(False):
             if fast:
@@ -91,8 +94,12 @@ class OGL:
                 if raster.n != texture.texture_.shape[-1]:
                     raise ValueError(f"descriptor table has {texture.texture_.shape[-1]} points, the scene cloud {raster.n}")
                 ss = int(model.ss)                               # supersampling: raster at ss x, reduce in the gather
-                idx, _ = raster.render(scene.total_matrix(), ss * W, ss * H, len(fmts), want_depth=False,
-                                       next_total=scene.take_next_total_matrix())      # Scene.announce_next_camera_view
+                if pano:                                         # Scene.set_panorama: only the raster step differs
+                    scene.take_next_total_matrix()               # an announced next camera is ignored (and consumed)
+                    idx, _ = raster.render_pano(scene.pano_camera(), W, H, len(fmts), want_depth=False)
+                else:
+                    idx, _ = raster.render(scene.total_matrix(), ss * W, ss * H, len(fmts), want_depth=False,
+                                           next_total=scene.take_next_total_matrix())      # Scene.announce_next_camera_view
                 feats = gather_pyramid(texture.rows(), idx, texture.activation, ss=ss)
                 out = model.net.engine(H, W).forward(feats[0][0], feats[1][0], feats[2][0], feats[3][0], channels=4)
                 net_input = [f.permute(0, 3, 1, 2) for f in feats]
@@ -113,10 +120,28 @@ class OGL:
             res['input'] = input_dict
         return res
 
+    def _require_pano_fast(self, input_dict):
+        """A panorama camera (Scene.set_panorama) is drawn on the fast path only; what would leave it is refused by name."""
+        model, scene = self.model, self.renderer.scene
+        if input_dict is not None:
+            raise NotImplementedError("a caller-supplied input_dict with a panorama camera (set_panorama)")
+        if model.temporal_average:
+            raise NotImplementedError("temporal_average with a panorama camera (set_panorama)")
+        if int(model.ss) > 1:
+            raise NotImplementedError(f"supersampling {int(model.ss)} with a panorama camera (set_panorama)")
+        if scene.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with a panorama camera "
+                                      "(set_panorama)")
+        if not self._fast_format or not hasattr(model.net, 'engine'):
+            raise NotImplementedError(f"input format {self.input_format!r} with a panorama camera (set_panorama): only the "
+                                      "point-id pyramid of at least four scales on the HIP UNet is served")
+
     def _infer_stitched(self, input_dict):
         """A StitchedScene: per-part raster with depth -> one stitched gather -> the engine.  Always the fast path; what it does
         not serve is refused by name."""
         model, scene = self.model, self.renderer.scene
+        if scene.panorama is not None:
+            raise NotImplementedError("a panorama camera (set_panorama) on a StitchedScene: stitched frames are pinhole frames")
         if input_dict is not None:
             raise NotImplementedError("a caller-supplied input_dict with scene stitching (StitchedScene)")
         if model.temporal_average:

@@ -164,6 +164,46 @@ class PointCloudRasterizer:
                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_cells")
         return idx, dep
 
+    def pano_object_cameras(self, cam):
+        """The (K,16) float32 panorama cameras of the objects 1..K for the camera ``cam`` (camera.pano_camera): the rows are
+        ``object_matrix(R4, P_k)[:3]``, R4 = cam's three rows with (0, 0, 0, 1) beneath; kx, ky, za, zb repeat."""
+        cam = np.asarray(cam, np.float32).reshape(16)
+        R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
+        out = np.empty((self.n_objects, 16), np.float32)
+        for i in range(self.n_objects):
+            out[i, :12] = object_matrix(R4, self._poses.get(i + 1))[:3].reshape(12)
+            out[i, 12:] = cam[12:]
+        return out
+
+    def render_pano(self, cam, W, H, levels=5, want_depth=True, out=None):
+        """One panorama (cylindrical) frame: ``cam`` = the 16 floats of ``camera.pano_camera`` -> (idx_levels, depth_levels) as
+        ``render`` gives them.  One camera per call; object labels, poses and visibility are honoured.  The whole cloud is read
+        every frame (no chunk culling under a cylinder); without labels the previous frame's winners warm-start the pass.
+        Pinhole and panorama frames may alternate on one rasteriser."""
+        cam = np.ascontiguousarray(cam.detach().cpu().numpy() if torch.is_tensor(cam) else cam, dtype=np.float32).reshape(-1, 16)
+        if cam.shape[0] != 1:
+            raise ValueError("render_pano renders one camera per call")
+        sizes = level_sizes(W, H, levels)
+        if out is None:
+            idx = [torch.empty((1, h, w), dtype=torch.int32, device=self.device) for (w, h) in sizes]
+            dep = [torch.empty((1, h, w), dtype=torch.float32, device=self.device) for (w, h) in sizes] if want_depth else None
+        else:
+            idx, dep = out
+        ws = self._workspace(1, W, H)
+        idx_p = _lib.ptr_array([t.data_ptr() for t in idx])
+        dep_p = _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
+        cam_p = cam.ctypes.data_as(C.POINTER(C.c_float))
+        L = _lib.lib()
+        if self.labels is not None:
+            self._obj_m[...] = self.pano_object_cameras(cam[0])
+            _lib.check(L.read_splat_forward_pano(self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
+                                                 self.n_static, cam_p, W, H, levels, C.byref(self._objs), idx_p, dep_p,
+                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano")
+        else:
+            _lib.check(L.read_splat_forward_pano(self.xyz.data_ptr() or None, None, self.n, cam_p, W, H, levels, None, idx_p,
+                                                 dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano")
+        return idx, dep
+
     def bind(self, W, H, levels, out, totals):
         """A pre-bound frame call for loops that must not be host-bound (benchmark stages): every ctypes argument is built ONCE —
         the outputs ``out`` = (idx levels, depth levels or None) and the list of camera matrices ``totals`` — and
@@ -192,14 +232,17 @@ class PointCloudRasterizer:
         return call
 
     def render_gl(self, total_m, W, H, point_size=1.0, relative=False, min_point_size=1.0, discard=None, drop=None,
-                  perturb=None, perturb_hash=None, want_depth=True, point_sizes=None):
+                  perturb=None, perturb_hash=None, want_depth=True, point_sizes=None, pano=None):
         """ONE level of ONE camera at its own size with the GL twin's point options (read_splat_forward_gl):
         point_size / relative ("pN" / "psN" tokens, READ/gl/programs.py:183-192), discard = bool/uint8 (N,) array or
         tensor (set_point_discard), drop = (p, seed) seeded drop, perturb = (N,2) clip-space offsets
         (set_point_perturb), perturb_hash = (amp, seed), point_sizes = (N,) per-point sizes (set_point_sizes; they replace
-        point_size as in the shader, programs.py:183-187).  -> (idx (1,H,W) int32, depth (1,H,W) fp32 | None)."""
+        point_size as in the shader, programs.py:183-187).  -> (idx (1,H,W) int32, depth (1,H,W) fp32 | None).
+        pano = a panorama camera (camera.pano_camera) is refused: the GL twin is a pinhole."""
         if self.labels is not None:
             raise NotImplementedError("render_gl (GL-twin point options) with object labels")
+        if pano is not None:
+            raise NotImplementedError("render_gl (GL-twin point options) with a panorama camera: render_pano draws 1-px point ids")
         M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m,
                                  dtype=np.float32).reshape(-1, 16)
         if M.shape[0] != 1:

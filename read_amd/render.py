@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .camera import level_sizes, total_matrix
+from .camera import level_sizes, pano_camera, total_matrix
 from .raster import PointCloudRasterizer, index_to_float
 
 
@@ -186,6 +186,7 @@ class Scene:
         self.object_labels = None         # scene editing (extension): int (N,) labels, 0 = static
         self.object_poses = {}            # label -> 4x4
         self.object_hidden = set()        # labels not drawn
+        self.panorama = None              # set_panorama: horizontal field in degrees of the cylindrical camera, None = pinhole
         self.params = {'mode': (MODE_UV, UV_TYPE_1D), 'draw_points': True, 'flat_color': True, 'point_size': 1,
                        'splat_mode': False}
         if xyz is not None:
@@ -291,6 +292,24 @@ class Scene:
 
     def set_proj_matrix(self, m):
         self.proj_matrix = np.asarray(m, np.float32)
+
+    def set_panorama(self, hfov_deg):
+        """Extension (not in NNScene): a cylindrical camera with a horizontal field of hfov_deg in (0, 360] at the current view;
+        None returns to the pinhole.  ``OGL.infer`` stays on its fast path and rasterises with
+        ``PointCloudRasterizer.render_pano``; of the projection matrix only the vertical scale / offset and the depth entries
+        are used (camera.pano_camera).  Object edits apply; an announced next camera is ignored; everything that is not the
+        point-id pyramid on the fast path raises NotImplementedError while a panorama is set."""
+        if hfov_deg is not None and not 0.0 < float(hfov_deg) <= 360.0:
+            raise ValueError(f"hfov_deg must lie in (0, 360], got {hfov_deg!r}")
+        self.panorama = None if hfov_deg is None else float(hfov_deg)
+
+    def pano_camera(self):
+        """The 16 floats of camera.pano_camera for the current view, model and projection matrices (points are taken to the
+        camera by inv(view) @ model, as in ``total_matrix``)."""
+        if self.panorama is None:
+            raise ValueError("no panorama set (set_panorama)")
+        view = np.linalg.inv(self.model_matrix.astype(np.float64)) @ self.view_matrix.astype(np.float64)
+        return pano_camera(self.proj_matrix, view, self.panorama)
 
     def set_use_light(self, use_light):
         if use_light:
@@ -399,6 +418,16 @@ class StitchedScene:
         for sc in self.scenes:
             sc.set_proj_matrix(m)
 
+    def set_panorama(self, hfov_deg):
+        if hfov_deg is not None:
+            raise NotImplementedError("a panorama camera on a StitchedScene: stitched frames are pinhole frames")
+        for sc in self.scenes:
+            sc.set_panorama(None)
+
+    @property
+    def panorama(self):
+        return next((sc.panorama for sc in self.scenes if sc.panorama is not None), None)
+
     def set_model_view(self, m):
         for sc in self.scenes:
             sc.set_model_view(m)
@@ -471,6 +500,10 @@ class MultiscaleRender:
         scene = self.scene
         W, H = self.ss * self.viewport_size[0], self.ss * self.viewport_size[1]
         out = {}
+        if getattr(scene, 'panorama', None) is not None:
+            what = "a StitchedScene" if getattr(scene, 'stitched', False) else "MultiscaleRender (the dict path)"
+            raise NotImplementedError(f"a panorama camera (set_panorama) on {what}: only OGL.infer's fast path and "
+                                      "FrameRenderer.render_pano draw it")
         if getattr(scene, 'stitched', False):
             return self._render_stitched(scene, input_format, fmts, W, H)
         pyramid = is_point_id_pyramid(input_format) and W % (1 << (len(fmts) - 1)) == 0 and H % (1 << (len(fmts) - 1)) == 0
