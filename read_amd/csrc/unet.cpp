@@ -21,52 +21,64 @@ constexpr int BASE = 32;      // base_channel, unet.py:141
 constexpr int NUM_RES = 4;    // num_res, ogl.py:24
 constexpr int IN_CH = READ_DESC_CHANNELS;
 
-struct LayerInfo {
+// A weight order is one packed form of a layer's weights: what one kernel family reads.  One row per order, in the sequence the
+// packed blob carries them; everything below that places, packs or hands out an order walks this table.
+enum Order { DIRECT, WINO, W16, W4, W4H, F4X1, DKH, T3H, SC, N_ORDERS };
+constexpr size_t ABSENT = ~(size_t)0;      // an offset of an order the layer does not carry
+
+template <auto F> size_t floats2(int cin, int cout, int) { return F(cin, cout); }      // size functions and packers without ksize / kc
+template <auto F> int pack2(int cin, int cout, int, int, const float *wf, const float *wm, float *dst) { return F(cin, cout, wf, wm, dst); }
+int pack_dkh(int cin, int cout, int k, int, const float *wf, const float *wm, float *dst) { return read_conv_pack_dkh_host(cin, cout, k, wf, wm, dst); }
+
+const struct OrderRow {
+    const char *name;
+    size_t (*floats)(int cin, int cout, int k);
+    int (*pack)(int cin, int cout, int k, int kc, const float *wf, const float *wm, float *dst);
+    size_t align;                          // of its offset in the blob, in floats
+    const float *read_conv_desc::*field;   // the read_conv_desc pointer it fills (the f16 operands are declared const void *) ...
+    const void *read_conv_desc::*field_h;  // ... both null: the order travels beside the descriptor, whose struct is frozen
+} ORDERS[N_ORDERS] = {
+    {"direct", read_conv_packed_floats, read_conv_pack_weights_host, 1, &read_conv_desc::wpacked, nullptr},
+    {"wino", floats2<read_conv_wino_floats>, pack2<read_conv_pack_wino_host>, 1, &read_conv_desc::wpacked_wino, nullptr},
+    {"w16", floats2<read_conv_wino_floats>, pack2<read_conv_pack_w16_host>, 1, &read_conv_desc::wpacked_w16, nullptr},
+    {"w4", floats2<read_conv_w4_floats>, pack2<read_conv_pack_w4_host>, 1, &read_conv_desc::wpacked_w4, nullptr},
+    {"w4h", floats2<read_conv_w4h_floats>, pack2<read_conv_pack_w4h_host>, 1, nullptr, &read_conv_desc::wpacked_w4h},
+    {"f4x1", floats2<read_conv_f4x1_floats>, pack2<read_conv_pack_f4x1_host>, 1, nullptr, nullptr},
+    {"dkh", read_conv_dkh_floats, pack_dkh, 1, nullptr, &read_conv_desc::wpacked_d3h},
+    {"t3h", floats2<read_conv_t3h_floats>, pack2<read_conv_pack_t3h_host>, 1, nullptr, &read_conv_desc::wpacked_t3h},
+    {"sc", floats2<read_conv_sc_floats>, pack2<read_conv_pack_sc_host>, 16, &read_conv_desc::wpacked_sc, nullptr},   // 64 bytes: scalar loads of 16 dwords
+};
+
+// A convolution of the plan: a BasicConv of the model (LayerInfo) or a 1x1 block cut out of some (DerivedInfo).
+struct ConvInfo {
     std::string path;
     int cin, cout, k, stride, elu, kc;
-    size_t raw_off, w_off, p_off;   // float offsets into the raw / packed blobs
-    size_t wino_off;                // Winograd-transformed weights of 3x3/s1 layers with Cin % 16 == 0, else NO_WINO
-    size_t w16_off;                 // ... in the order of the wave-autonomous Winograd kernel (read_conv_pack_w16_host)
-    size_t w4_off;                  // Winograd F(4x4,3x3) weights of the 3x3/s1 layers with Cin >= 32 and Cout % 32 == 0, else NO_WINO
-    size_t sc_off = ~(size_t)0;     // small-Cout order of the 3x3/s1 layers with Cout <= 4 (the output layer), else NO_WINO
-    size_t w4h_off = ~(size_t)0;    // F(4x4) weights split into f16 piece pairs (read_conv_pack_w4h_host) of the w4 layers with Cin % 32 == 0, else NO_WINO
-    size_t d3h_off = ~(size_t)0;    // the plain 3x3 weights as f16 piece pairs (read_conv_pack_d3h_host) of the same layers, else NO_WINO
-    size_t t3h_off = ~(size_t)0;    // 3x3 / stride-1 layers over the 8-channel pyramid: the implicit-GEMM operand (read_conv_pack_t3h_host), else NO_WINO
-    size_t f4x1_off = ~(size_t)0;   // the F(4,3)-by-rows order (read_conv_pack_f4x1_host) of the w4h layers — the LEAN layout only, else NO_WINO
-    size_t side_off = ~(size_t)0;   // FULL layout: offset of that order in the side buffer (read_unet_set_f4x1), else NO_WINO
+    size_t p_off = 0;                      // float offset of the parameters in the packed blob
+    size_t off[N_ORDERS];                  // ... of each weight order, or ABSENT
+    size_t side_off = ABSENT;              // FULL layout: offset of the F4X1 order in the side buffer (read_unet_set_f4x1), else ABSENT
+    ConvInfo(const std::string &path, int cin, int cout, int k, int stride, int elu, int kc)
+        : path(path), cin(cin), cout(cout), k(k), stride(stride), elu(elu), kc(kc)
+    {
+        for (size_t &o : off) o = ABSENT;
+    }
 };
-constexpr size_t NO_WINO = ~(size_t)0;
+
+struct LayerInfo : ConvInfo {
+    using ConvInfo::ConvInfo;
+    size_t raw_off = 0;                    // float offset into the raw blob
+};
 
 // A 1x1 layer whose weights are a block of existing layers' weights: input channels [ci0, ci0 + cin) of the parts'
 // concatenated input, the parts' output channels stacked.  Used to evaluate the coarse-level inputs of the AFF 1x1
-// convs at their own resolution (a 1x1 conv commutes with the nearest up-sampling of unet.py:239-254).
-struct DerivedInfo {
-    std::string name;
-    int cin, cout, ci0;
-    std::vector<int> parts;         // indices into Arch::layers
-    size_t w_off, p_off;            // packed weights; parameters (zero biases) — gated finals use their part's own p_off
-    size_t h_off = ~(size_t)0;      // the same weights as f16 piece pairs (read_conv_pack_dkh_host, ksize 1: the split-operand pixel-lane kernel)
+// convs at their own resolution (a 1x1 conv commutes with the nearest up-sampling of unet.py:239-254).  Its parameters
+// are zero biases — gated finals use their part's own p_off.
+struct DerivedInfo : ConvInfo {
+    using ConvInfo::ConvInfo;
+    int ci0 = 0;
+    std::vector<int> parts;                // indices into Arch::layers
 };
 
-struct Arch {
-    std::vector<LayerInfo> layers;
-    std::vector<DerivedInfo> derived;
-    size_t raw_floats = 0, packed_floats = 0, side_floats = 0;
-    int find_derived(const std::string &p) const
-    {
-        for (size_t i = 0; i < derived.size(); ++i)
-            if (derived[i].name == p) return (int)i;
-        return -1;
-    }
-    int find(const std::string &p) const
-    {
-        for (size_t i = 0; i < layers.size(); ++i)
-            if (layers[i].path == p) return (int)i;
-        return -1;
-    }
-};
-
-size_t raw_layer_floats(int cin, int cout, int k) { return 2 * ((size_t)cout * cin * k * k + cout) + 4 * (size_t)cout; }
+enum Home { NOWHERE, BLOB, SIDE };
 
 // Layout of the packed blob.  FULL: every fragment order of every layer (direct + both F(2x2) orders + F(4x4) where they exist):
 // any tuning knob can send a layer to any of its kernels — 952 MB for a 121 MB model.  LEAN: what the default plan reads —
@@ -77,67 +89,85 @@ size_t raw_layer_floats(int cin, int cout, int k) { return 2 * ((size_t)cout * c
 // behind the F(4x4) split operand of each such layer (both, so read_tuning_set("conv_f4x1", 0) still works on it); FULL is laid out
 // exactly as before — a host derives the order from FULL's direct fragments (exact weights) and hands it over as a side buffer
 // (read_unet_f4x1_layer / read_unet_set_f4x1).  LEAN_W4H is the lean layout without it: blobs packed before the kernel existed.
+// One rule per order, asked in the blob's sequence: does this convolution carry the order in this layout, and where.
+Home home(Order o, const ConvInfo &L, int layout)
+{
+    const bool lean = layout != READ_UNET_LAYOUT_FULL;
+    const bool k3s1 = L.k == 3 && L.stride == 1;
+    const bool unused = L.path.compare(0, 9, "ConvsOut.") == 0;                  // no launch executes these layers
+    const bool fam = L.path.compare(0, 3, "FAM") == 0;                           // x1 * x2 launches: the DIRECT split-operand kernel takes them
+    const bool wino = k3s1 && L.kc == 16 && L.cin % 16 == 0;
+    const bool w4 = wino && L.cin >= 32 && L.cout % 32 == 0;                     // the F(4x4) family runs the layer by default ...
+    const bool split = w4 && L.cin % 32 == 0;                                    // ... with split operands on the f16 matrix cores
+    const bool s2 = (L.k == 3 || L.k == 4) && L.stride == 2 && L.cin % 32 == 0 && L.cout % 32 == 0;   // down-sampling (3x3) and decoder (4x4) layers: direct split-operand kernel
+    bool in = false;
+    switch (o) {
+    case DIRECT: in = !(lean && (w4 || unused || s2)); break;                    // lean: absent where a split-operand or F(4x4) kernel runs the layer
+    case WINO:
+    case W16: in = wino && !(lean && (w4 || unused)); break;
+    case W4: in = w4 && !(lean && split); break;
+    case W4H: in = split && !fam; break;
+    case F4X1: in = split && !fam && layout != READ_UNET_LAYOUT_LEAN_W4H; break;   // the W4H layers; LEAN_W4H predates the order
+    case DKH:                                                                    // 1x1 layers: the fp32 order stays beside it as the fallback
+        in = (split && (fam || !lean)) || s2 || (L.k == 1 && L.stride == 1 && L.cin <= 256);
+        break;
+    case T3H: in = k3s1 && L.cin == IN_CH; break;                                // over the 8-channel pyramid
+    case SC: in = k3s1 && !(lean && unused); break;                              // Cout <= 4: the output layer
+    default: break;
+    }
+    if (!in || !ORDERS[o].floats(L.cin, L.cout, L.k)) return NOWHERE;            // a size function answers 0 for a shape its kernel does not take
+    // FULL is laid out as it was before F4X1 existed: a host derives that order from the direct fragments into a side buffer
+    return o == F4X1 && !lean ? SIDE : BLOB;
+}
+
+struct Arch {
+    std::vector<LayerInfo> layers;
+    std::vector<DerivedInfo> derived;
+    size_t raw_floats = 0, packed_floats = 0, side_floats = 0;
+    int find_derived(const std::string &p) const
+    {
+        for (size_t i = 0; i < derived.size(); ++i)
+            if (derived[i].path == p) return (int)i;
+        return -1;
+    }
+    int find(const std::string &p) const
+    {
+        for (size_t i = 0; i < layers.size(); ++i)
+            if (layers[i].path == p) return (int)i;
+        return -1;
+    }
+};
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+size_t raw_layer_floats(int cin, int cout, int k) { return 2 * ((size_t)cout * cin * k * k + cout) + 4 * (size_t)cout; }
+
 Arch build_arch(int layout)
 {
-        const bool lean = layout == READ_UNET_LAYOUT_LEAN || layout == READ_UNET_LAYOUT_LEAN_W4H;
-        const bool f4x1 = layout == READ_UNET_LAYOUT_LEAN;
         Arch a;
-        auto add = [&](const std::string &path, int cin, int cout, int k, int s, int elu, int kc) {
-            LayerInfo L{path, cin, cout, k, s, elu, kc, 0, NO_WINO, 0, NO_WINO, NO_WINO, NO_WINO};
-            L.raw_off = a.raw_floats;
-            a.raw_floats += raw_layer_floats(cin, cout, k);
-            const bool wino = k == 3 && s == 1 && kc == 16 && cin % 16 == 0, w4 = wino && cin >= 32 && cout % 32 == 0;
-            const bool unused = path.compare(0, 9, "ConvsOut.") == 0;
-            const bool d3h_s2 = (k == 3 || k == 4) && s == 2 && cin % 32 == 0 && cout % 32 == 0;   // down-sampling (3x3) and decoder (4x4) stride-2 layers: direct split-operand kernel
+        // the blob's sequence: a layer's parameters, then its orders in table order; a derived layer's direct order, parameters, the rest
+        auto params = [&](ConvInfo &L) {
             L.p_off = a.packed_floats;
-            a.packed_floats += read_conv_param_floats(cout);
-            if (!(lean && (w4 || unused || d3h_s2))) {
-                L.w_off = a.packed_floats;
-                a.packed_floats += read_conv_packed_floats(cin, cout, k);
-            }
-            if (wino && !(lean && (w4 || unused))) {
-                L.wino_off = a.packed_floats;
-                a.packed_floats += read_conv_wino_floats(cin, cout);
-                L.w16_off = a.packed_floats;
-                a.packed_floats += read_conv_wino_floats(cin, cout);
-            }
-            // the Winograd split-operand kernel (f16 matrix cores) runs the layer by default — except FAM's x1 * x2 launches, which the
-            // DIRECT split-operand kernel takes
-            const bool fam = path.compare(0, 3, "FAM") == 0;
-            const bool w4h = w4 && cin % 32 == 0 && !fam, d3h = (w4 && cin % 32 == 0) || d3h_s2;
-            if (w4 && !(lean && (unused || w4h || (d3h && fam)))) {
-                L.w4_off = a.packed_floats;
-                a.packed_floats += read_conv_w4_floats(cin, cout);
-            }
-            if (w4h && !(lean && unused)) {
-                L.w4h_off = a.packed_floats;
-                a.packed_floats += read_conv_w4h_floats(cin, cout);
-                if (f4x1) {
-                    L.f4x1_off = a.packed_floats;
-                    a.packed_floats += read_conv_f4x1_floats(cin, cout);
-                } else if (!lean && !unused) {
+            a.packed_floats += read_conv_param_floats(L.cout);
+        };
+        auto place = [&](ConvInfo &L, int first, int last) {
+            for (int o = first; o <= last; ++o) {
+                const Home h = home((Order)o, L, layout);
+                const size_t n = ORDERS[o].floats(L.cin, L.cout, L.k);
+                if (h == BLOB) {
+                    L.off[o] = a.packed_floats = align_up(a.packed_floats, ORDERS[o].align);
+                    a.packed_floats += n;
+                } else if (h == SIDE) {
                     L.side_off = a.side_floats;
-                    a.side_floats += read_conv_f4x1_floats(cin, cout);
+                    a.side_floats += n;
                 }
             }
-            if (d3h && !(lean && (unused || !(fam || d3h_s2)))) {
-                L.d3h_off = a.packed_floats;
-                a.packed_floats += read_conv_dkh_floats(cin, cout, k);
-            }
-            // 1x1 layers: the operand of the split-operand pixel-lane kernel (both layouts: the fp32 order stays beside it as the fallback)
-            if (k == 1 && s == 1 && cin <= 256 && read_conv_dkh_floats(cin, cout, 1)) {
-                L.d3h_off = a.packed_floats;
-                a.packed_floats += read_conv_dkh_floats(cin, cout, 1);
-            }
-            if (k == 3 && s == 1 && cin == IN_CH && read_conv_t3h_floats(cin, cout)) {
-                L.t3h_off = a.packed_floats;
-                a.packed_floats += read_conv_t3h_floats(cin, cout);
-            }
-            if (k == 3 && s == 1 && read_conv_sc_floats(cin, cout) && !(lean && unused)) {
-                a.packed_floats = (a.packed_floats + 15) / 16 * 16;     // 64-byte aligned: scalar loads of 16 dwords
-                L.sc_off = a.packed_floats;
-                a.packed_floats += read_conv_sc_floats(cin, cout);
-            }
+        };
+        auto add = [&](const std::string &path, int cin, int cout, int k, int s, int elu, int kc) {
+            LayerInfo L(path, cin, cout, k, s, elu, kc);
+            L.raw_off = a.raw_floats;
+            a.raw_floats += raw_layer_floats(cin, cout, k);
+            params(L);
+            place(L, DIRECT, SC);
             a.layers.push_back(L);
         };
         // SCM (unet.py:92-106): SCM2 -> 64 planes @1/2, SCM1 -> 128 @1/4, SCM0 -> 256 @1/8
@@ -189,49 +219,32 @@ Arch build_arch(int layout)
         add("FAM1.merge", BASE * 4, BASE * 4, 3, 1, 0, 16);
         add("FAM2.merge", BASE * 2, BASE * 2, 3, 1, 0, 16);
         // AFF first convs split by the level their inputs live at; concat order res1(32) res2(64) res3(128) z(256)
-        auto derive = [&](const std::string &name, int ci0, int cin, std::vector<int> affs) {
-            DerivedInfo D{name, cin, 0, ci0, {}, 0, 0};
-            for (int k : affs) {
-                const int li = a.find("AFFs." + std::to_string(k) + ".conv.0");
-                D.parts.push_back(li);
-                D.cout += a.layers[li].cout;
+        auto derive = [&](const std::string &name, int ci0, int cin, const std::vector<std::string> &layers) {
+            DerivedInfo D(name, cin, 0, 1, 1, a.layers[a.find(layers[0])].elu, 16);
+            D.ci0 = ci0;
+            for (const std::string &l : layers) {
+                D.parts.push_back(a.find(l));
+                D.cout += a.layers[D.parts.back()].cout;
             }
-            D.w_off = a.packed_floats;
-            a.packed_floats += read_conv_packed_floats(cin, D.cout, 1);
-            D.p_off = a.packed_floats;
-            a.packed_floats += read_conv_param_floats(D.cout);
-            if (cin <= 256 && read_conv_dkh_floats(cin, D.cout, 1)) {
-                D.h_off = a.packed_floats;
-                a.packed_floats += read_conv_dkh_floats(cin, D.cout, 1);
-            }
+            place(D, DIRECT, DIRECT);
+            params(D);
+            place(D, DIRECT + 1, SC);
             a.derived.push_back(D);
         };
-        derive("AFFq3", BASE * 7, BASE * 8, {0, 1, 2});   // z    @1/8 -> partial sums of AFF0, AFF1, AFF2
-        derive("AFFq2", BASE * 3, BASE * 4, {0, 1});      // res3 @1/4 -> AFF0, AFF1
-        derive("AFFq1", BASE, BASE * 2, {0});             // res2 @1/2 -> AFF0
-        derive("AFFs.0.conv.0r", 0, BASE, {0});           // what is left at the layer's own level
-        derive("AFFs.1.conv.0r", 0, BASE * 3, {1});
-        derive("AFFs.2.conv.0r", 0, BASE * 7, {2});
+        const std::string aff0 = "AFFs.0.conv.0", aff1 = "AFFs.1.conv.0", aff2 = "AFFs.2.conv.0";
+        derive("AFFq3", BASE * 7, BASE * 8, {aff0, aff1, aff2});   // z    @1/8 -> partial sums of AFF0, AFF1, AFF2
+        derive("AFFq2", BASE * 3, BASE * 4, {aff0, aff1});         // res3 @1/4 -> AFF0, AFF1
+        derive("AFFq1", BASE, BASE * 2, {aff0});                   // res2 @1/2 -> AFF0
+        derive("AFFs.0.conv.0r", 0, BASE, {aff0});                 // what is left at the layer's own level
+        derive("AFFs.1.conv.0r", 0, BASE * 3, {aff1});
+        derive("AFFs.2.conv.0r", 0, BASE * 7, {aff2});
         // Convs.k = 1x1 over cat[Upsample4_bilinear(fe), r] (unet.py:261-262,269-270,277-278): the half that multiplies the up-sampled
         // tensor is applied at ITS level (1/16 of the pixels, `linear`) and enters the gated launch as a bilinear pre-activation addend
-        auto derive_of = [&](const std::string &name, const std::string &layer, int ci0, int cin) {
-            const int li = a.find(layer);
-            DerivedInfo D{name, cin, a.layers[li].cout, ci0, {li}, 0, 0};
-            D.w_off = a.packed_floats;
-            a.packed_floats += read_conv_packed_floats(cin, D.cout, 1);
-            D.p_off = a.packed_floats;
-            a.packed_floats += read_conv_param_floats(D.cout);
-            if (cin <= 256 && read_conv_dkh_floats(cin, D.cout, 1)) {
-                D.h_off = a.packed_floats;
-                a.packed_floats += read_conv_dkh_floats(cin, D.cout, 1);
-            }
-            a.derived.push_back(D);
-        };
         for (int k = 0; k < 3; ++k) {
             const int Cu = (BASE * 4) >> k;                                  // channels of up4(fe) = channels of r
             const std::string L = "Convs." + std::to_string(k);
-            derive_of(L + ".u", L, 0, Cu);
-            derive_of(L + ".r", L, Cu, Cu);
+            derive(L + ".u", 0, Cu, {L});
+            derive(L + ".r", Cu, Cu, {L});
         }
         return a;
 }
@@ -286,8 +299,6 @@ struct read_unet {
 
 namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 int g_unet_aff_split = 1;     // read_tuning_set("unet_aff_split", 0): the AFF first convs as single 480-channel launches
 // read_tuning_set("unet_up_fold", 1): the bilinear x4 up-sampling folded into the Convs.k launches (read_conv_desc.pre_bilinear).
 // Built and measured in round 5 (profiles/r5_up_fold_ab.md): results equal (148 dB either way) and 110 MB per frame less written and
@@ -330,10 +341,6 @@ struct Builder {
     struct PreRef {
         int t = -1, f_off = 0, m_off = 0, shift = 0, bilinear = 0;
     };
-    struct LayerRef {
-        int cin, cout, k, stride, elu;
-        size_t w_off, p_off, wino_off, w16_off, w4_off, sc_off, w4h_off = ~(size_t)0, d3h_off = ~(size_t)0, t3h_off = ~(size_t)0, f4x1_off = ~(size_t)0, side_off = ~(size_t)0;
-    };
 
     // One BasicConv.  srcs = {tensor id, shift}; out tensor must already exist.
     void conv(const std::string &path, std::vector<std::pair<int, int>> srcs, int out_t, int mul_t = -1,
@@ -341,8 +348,7 @@ struct Builder {
     {
         const Arch &A = arch(u->layout);
         const LayerInfo &L = A.layers[A.find(path)];
-        emit(path, LayerRef{L.cin, L.cout, L.k, L.stride, L.elu, L.w_off, L.p_off, L.wino_off, L.w16_off, L.w4_off, L.sc_off, L.w4h_off, L.d3h_off, L.t3h_off, L.f4x1_off, L.side_off}, srcs, out_t, mul_t, res_t, 0,
-             PreRef());
+        emit(L, L.p_off, srcs, out_t, mul_t, res_t, 0, PreRef());
     }
     // A derived 1x1 layer (DerivedInfo): `linear` ones store the pre-activations [f | m] for a finer level to add,
     // gated ones are the AFF layer itself on the inputs of its own level, with the layer's own bias / BatchNorm.
@@ -350,18 +356,16 @@ struct Builder {
     {
         const Arch &A = arch(u->layout);
         const DerivedInfo &D = A.derived[A.find_derived(name)];
-        const LayerInfo &P0 = A.layers[D.parts[0]];
-        emit(name, LayerRef{D.cin, D.cout, 1, 1, P0.elu, D.w_off, linear ? D.p_off : P0.p_off, NO_WINO, NO_WINO, NO_WINO, NO_WINO, NO_WINO, D.h_off}, srcs, out_t, -1, -1,
-             linear, pre);
+        emit(D, linear ? D.p_off : A.layers[D.parts[0]].p_off, srcs, out_t, -1, -1, linear, pre);
     }
 
-    void emit(const std::string &path, const LayerRef &L, const std::vector<std::pair<int, int>> &srcs, int out_t, int mul_t,
-              int res_t, int linear, PreRef pre)
+    void emit(const ConvInfo &L, size_t p_off, const std::vector<std::pair<int, int>> &srcs, int out_t, int mul_t, int res_t, int linear,
+              PreRef pre)
     {
         Op op;
         memset(&op.d, 0, sizeof(op.d));
         op.kind = Op::CONV;
-        op.label = path;
+        op.label = L.path;
         op.mul_t = mul_t;
         op.res_t = res_t;
         op.out_t = out_t;
@@ -387,17 +391,14 @@ struct Builder {
         op.d.ksize = L.k;
         op.d.stride = L.stride;
         op.d.elu = L.elu;
-        op.d.wpacked = L.w_off != NO_WINO ? u->packed + L.w_off : nullptr;      // lean blob: absent where the F(4x4) kernel runs the layer
-        op.d.params = u->packed + L.p_off;
-        op.d.wpacked_wino = L.wino_off != NO_WINO ? u->packed + L.wino_off : nullptr;
-        op.d.wpacked_w16 = L.w16_off != NO_WINO ? u->packed + L.w16_off : nullptr;
-        op.d.wpacked_w4 = L.w4_off != NO_WINO ? u->packed + L.w4_off : nullptr;
-        op.d.wpacked_sc = L.sc_off != NO_WINO ? u->packed + L.sc_off : nullptr;
-        op.d.wpacked_w4h = L.w4h_off != NO_WINO ? u->packed + L.w4h_off : nullptr;
-        op.wp_f4x1 = L.f4x1_off != NO_WINO ? u->packed + L.f4x1_off : nullptr;
+        op.d.params = u->packed + p_off;
+        for (int r = 0; r < N_ORDERS; ++r) {                      // an order the layout does not carry for this layer: a null pointer
+            const float *p = L.off[r] != ABSENT ? u->packed + L.off[r] : nullptr;
+            if (ORDERS[r].field) op.d.*ORDERS[r].field = p;
+            else if (ORDERS[r].field_h) op.d.*ORDERS[r].field_h = p;
+            else op.wp_f4x1 = p;
+        }
         op.side_off = L.side_off;
-        op.d.wpacked_d3h = L.d3h_off != NO_WINO ? u->packed + L.d3h_off : nullptr;
-        op.d.wpacked_t3h = L.t3h_off != NO_WINO ? u->packed + L.t3h_off : nullptr;
         op.d.mul = mul_t >= 0 ? u->tensors[mul_t].p : nullptr;
         op.d.residual = res_t >= 0 ? u->tensors[res_t].p : nullptr;
         op.d.out = o.p;
@@ -417,9 +418,9 @@ struct Builder {
         }
         op.flops = 2.0 * 2.0 * (double)o.H * o.W * L.cout * cin * L.k * L.k;
         op.is_c3s1 = (L.k == 3 && L.stride == 1 && L.cin == L.cout && L.cin >= BASE) ? 1 : 0;
-        if (cin != L.cin) set_error("internal: layer %s expects Cin=%d, plan gives %d", path.c_str(), L.cin, cin);
+        if (cin != L.cin) set_error("internal: layer %s expects Cin=%d, plan gives %d", L.path.c_str(), L.cin, cin);
         if (o.C != (linear ? 2 : 1) * L.cout && o.ext < 0)
-            set_error("internal: layer %s writes %d channels into a %d-channel tensor", path.c_str(), (linear ? 2 : 1) * L.cout, o.C);
+            set_error("internal: layer %s writes %d channels into a %d-channel tensor", L.path.c_str(), (linear ? 2 : 1) * L.cout, o.C);
         op.lane = cur_lane;
         u->tensors[out_t].lane = cur_lane;
         if (cur_lane == 0) {
@@ -681,46 +682,22 @@ extern "C" int read_unet_pack_host_layout(const float *raw, float bn_eps, float 
 {
     READ_CHECK_ARG(raw && packed, "read_unet_pack_host: null pointer");
     READ_CHECK_ARG(layout >= READ_UNET_LAYOUT_FULL && layout <= READ_UNET_LAYOUT_LEAN_W4H, "read_unet_pack_host: unknown layout %d", layout);
+    auto pack = [&](const ConvInfo &L, const float *wf, const float *wm) {
+        for (int o = 0; o < N_ORDERS; ++o)
+            if (L.off[o] != ABSENT) {
+                const int rc = ORDERS[o].pack(L.cin, L.cout, L.k, L.kc, wf, wm, packed + L.off[o]);
+                if (rc) return rc;
+            }
+        return (int)READ_OK;
+    };
     for (const LayerInfo &L : arch(layout).layers) {
         const size_t wn = (size_t)L.cout * L.cin * L.k * L.k;
         const float *wf = raw + L.raw_off, *bf = wf + wn, *wm = bf + L.cout, *bm = wm + wn;
         const float *gamma = bm + L.cout, *beta = gamma + L.cout, *mean = beta + L.cout, *var = mean + L.cout;
         int rc = read_conv_pack_params_host(L.cout, bf, bm, gamma, beta, mean, var, bn_eps, packed + L.p_off);
         if (rc) return rc;
-        if (L.w_off != NO_WINO) {
-            rc = read_conv_pack_weights_host(L.cin, L.cout, L.k, L.kc, wf, wm, packed + L.w_off);
-            if (rc) return rc;
-        }
-        if (L.wino_off != NO_WINO) {
-            rc = read_conv_pack_wino_host(L.cin, L.cout, wf, wm, packed + L.wino_off);
-            if (rc) return rc;
-            rc = read_conv_pack_w16_host(L.cin, L.cout, wf, wm, packed + L.w16_off);
-            if (rc) return rc;
-        }
-        if (L.w4_off != NO_WINO) {
-            rc = read_conv_pack_w4_host(L.cin, L.cout, wf, wm, packed + L.w4_off);
-            if (rc) return rc;
-        }
-        if (L.sc_off != NO_WINO) {
-            rc = read_conv_pack_sc_host(L.cin, L.cout, wf, wm, packed + L.sc_off);
-            if (rc) return rc;
-        }
-        if (L.w4h_off != NO_WINO) {
-            rc = read_conv_pack_w4h_host(L.cin, L.cout, wf, wm, packed + L.w4h_off);
-            if (rc) return rc;
-        }
-        if (L.f4x1_off != NO_WINO) {
-            rc = read_conv_pack_f4x1_host(L.cin, L.cout, wf, wm, packed + L.f4x1_off);
-            if (rc) return rc;
-        }
-        if (L.d3h_off != NO_WINO) {
-            rc = read_conv_pack_dkh_host(L.cin, L.cout, L.k, wf, wm, packed + L.d3h_off);
-            if (rc) return rc;
-        }
-        if (L.t3h_off != NO_WINO) {
-            rc = read_conv_pack_t3h_host(L.cin, L.cout, wf, wm, packed + L.t3h_off);
-            if (rc) return rc;
-        }
+        rc = pack(L, wf, wm);
+        if (rc) return rc;
     }
     const Arch &A = arch(layout);
     for (const DerivedInfo &D : A.derived) {
@@ -736,12 +713,8 @@ extern "C" int read_unet_pack_host_layout(const float *raw, float bn_eps, float 
                 }
             co0 += L.cout;
         }
-        int rc = read_conv_pack_weights_host(D.cin, D.cout, 1, 16, wf.data(), wm.data(), packed + D.w_off);
+        int rc = pack(D, wf.data(), wm.data());
         if (rc) return rc;
-        if (D.h_off != NO_WINO) {
-            rc = read_conv_pack_dkh_host(D.cin, D.cout, 1, wf.data(), wm.data(), packed + D.h_off);
-            if (rc) return rc;
-        }
         rc = read_conv_pack_params_host(D.cout, zero.data(), zero.data(), one.data(), zero.data(), zero.data(), one.data(), 0.0f,
                                         packed + D.p_off);
         if (rc) return rc;
@@ -816,8 +789,8 @@ extern "C" int read_unet_f4x1_layer(int j, size_t *w_off, size_t *side_off, int 
 {
     if (j < 0 || !w_off || !side_off || !cin || !cout) return READ_EINVAL;
     for (const LayerInfo &L : arch(READ_UNET_LAYOUT_FULL).layers)
-        if (L.side_off != NO_WINO && j-- == 0) {
-            *w_off = L.w_off;
+        if (L.side_off != ABSENT && j-- == 0) {
+            *w_off = L.off[DIRECT];
             *side_off = L.side_off;
             *cin = L.cin;
             *cout = L.cout;
@@ -832,7 +805,7 @@ extern "C" int read_unet_set_f4x1(read_unet_t *u, const float *side)
     READ_CHECK_ARG(u->layout == READ_UNET_LAYOUT_FULL, "read_unet_set_f4x1: only a plan of the FULL layout takes a side buffer (LEAN carries the order)");
     READ_CHECK_ARG((uintptr_t)side % 16 == 0, "read_unet_set_f4x1: misaligned buffer");
     for (Op &op : u->ops)
-        if (op.kind == Op::CONV && op.side_off != NO_WINO) op.wp_f4x1 = side ? side + op.side_off : nullptr;
+        if (op.kind == Op::CONV && op.side_off != ABSENT) op.wp_f4x1 = side ? side + op.side_off : nullptr;
     return READ_OK;
 }
 

@@ -15,6 +15,36 @@ def kc_for(src_channels):
     return 8 if any(c % 16 for c in src_channels) else 16
 
 
+def _wino(cin, cout, k):
+    return k == 3 and cin % 16 == 0
+
+
+def _w4(cin, cout, k):
+    return _wino(cin, cout, k) and cout % 32 == 0 and cin >= 32
+
+
+def _w4h(cin, cout, k):
+    return _w4(cin, cout, k) and cin % 32 == 0
+
+
+# The weight orders of one layer, one row each: attribute of PackedGatedConv, whether read_conv_desc has a field of that name, the size
+# function and the packer with the arguments each takes (a packer's are followed by wf, wm, dst), and the rule carried(Cin, Cout, k).
+# A layer carries an order when its rule holds and the size function answers non-zero.  These rules are the single-layer packer's
+# own — every order a kernel could take — not the UNet blob's.
+_CC, _CCK, _CCKK = ("cin", "cout"), ("cin", "cout", "k"), ("cin", "cout", "k", "kc")
+WEIGHT_ORDERS = (
+    ("wpacked", True, "read_conv_packed_floats", _CCK, "read_conv_pack_weights_host", _CCKK, lambda cin, cout, k: True),
+    ("wpacked_wino", True, "read_conv_wino_floats", _CC, "read_conv_pack_wino_host", _CC, _wino),        # Winograd F(2x2,3x3)
+    ("wpacked_w16", True, "read_conv_wino_floats", _CC, "read_conv_pack_w16_host", _CC, _wino),          # ... in the wave-autonomous kernel's order
+    ("wpacked_w4", True, "read_conv_w4_floats", _CC, "read_conv_pack_w4_host", _CC, _w4),                # Winograd F(4x4,3x3)
+    ("wpacked_w4h", True, "read_conv_w4h_floats", _CC, "read_conv_pack_w4h_host", _CC, _w4h),            # ... split into f16 piece pairs
+    ("wpacked_f4x1", False, "read_conv_f4x1_floats", _CC, "read_conv_pack_f4x1_host", _CC, _w4h),        # F(4,3) by rows: travels beside the descriptor
+    ("wpacked_d3h", True, "read_conv_dkh_floats", _CCK, "read_conv_pack_dkh_host", _CCK, lambda cin, cout, k: k in (1, 3, 4)),   # plain weights as f16 piece pairs
+    ("wpacked_t3h", True, "read_conv_t3h_floats", _CC, "read_conv_pack_t3h_host", _CC, lambda cin, cout, k: k == 3),             # 8 - 32 input channels
+    ("wpacked_sc", True, "read_conv_sc_floats", _CC, "read_conv_pack_sc_host", _CC, lambda cin, cout, k: k == 3),                # Cout <= 4
+)
+
+
 class PackedGatedConv:
     """Weights of one BasicConv packed for the MFMA kernel and resident on the device."""
 
@@ -25,53 +55,18 @@ class PackedGatedConv:
         self.cout, self.cin, self.k, _ = wf.shape
         self.kc = kc if kc is not None else kc_for(src_channels if src_channels is not None else [self.cin])
         L = _lib.lib()
-        wp = np.empty(L.read_conv_packed_floats(self.cin, self.cout, self.k), np.float32)
         pp = np.empty(L.read_conv_param_floats(self.cout), np.float32)
-        _lib.check(L.read_conv_pack_weights_host(self.cin, self.cout, self.k, self.kc, wf.ctypes.data, wm.ctypes.data,
-                                                 wp.ctypes.data), "read_conv_pack_weights_host")
         _lib.check(L.read_conv_pack_params_host(self.cout, bf.ctypes.data, bm.ctypes.data, gamma.ctypes.data,
                                                 beta.ctypes.data, mean.ctypes.data, var.ctypes.data, eps,
                                                 pp.ctypes.data), "read_conv_pack_params_host")
-        self.wpacked = torch.from_numpy(wp).to(device)
         self.params = torch.from_numpy(pp).to(device)
-        self.wpacked_wino = self.wpacked_w16 = self.wpacked_w4 = self.wpacked_sc = self.wpacked_w4h = self.wpacked_f4x1 = self.wpacked_d3h = self.wpacked_t3h = None
-        if self.k == 3 and L.read_conv_t3h_floats(self.cin, self.cout):     # 8 - 32 input channels: the implicit-GEMM operand of the split-operand pixel-lane kernel
-            t3 = np.empty(L.read_conv_t3h_floats(self.cin, self.cout), np.float32)
-            _lib.check(L.read_conv_pack_t3h_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, t3.ctypes.data), "read_conv_pack_t3h_host")
-            self.wpacked_t3h = torch.from_numpy(t3).to(device)
-        if self.k == 3 and L.read_conv_sc_floats(self.cin, self.cout):      # small-Cout order for the vector-pipe kernel (Cout <= 4)
-            sc = np.empty(L.read_conv_sc_floats(self.cin, self.cout), np.float32)
-            _lib.check(L.read_conv_pack_sc_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, sc.ctypes.data),
-                       "read_conv_pack_sc_host")
-            self.wpacked_sc = torch.from_numpy(sc).to(device)
-        if self.k == 3 and self.cin % 16 == 0:        # Winograd F(2x2,3x3) operand for the 3x3/s1 kernel variant
-            ww = np.empty(L.read_conv_wino_floats(self.cin, self.cout), np.float32)
-            _lib.check(L.read_conv_pack_wino_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, ww.ctypes.data),
-                       "read_conv_pack_wino_host")
-            self.wpacked_wino = torch.from_numpy(ww).to(device)
-            w16 = np.empty(L.read_conv_wino_floats(self.cin, self.cout), np.float32)
-            _lib.check(L.read_conv_pack_w16_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, w16.ctypes.data),
-                       "read_conv_pack_w16_host")
-            self.wpacked_w16 = torch.from_numpy(w16).to(device)
-            if self.cout % 32 == 0 and self.cin >= 32:
-                w4 = np.empty(L.read_conv_w4_floats(self.cin, self.cout), np.float32)
-                _lib.check(L.read_conv_pack_w4_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, w4.ctypes.data),
-                           "read_conv_pack_w4_host")
-                self.wpacked_w4 = torch.from_numpy(w4).to(device)
-                if self.cin % 32 == 0:            # ... and the same operand split into f16 piece pairs (the f16 matrix cores)
-                    w4h = np.empty(L.read_conv_w4h_floats(self.cin, self.cout), np.float32)
-                    _lib.check(L.read_conv_pack_w4h_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, w4h.ctypes.data),
-                               "read_conv_pack_w4h_host")
-                    self.wpacked_w4h = torch.from_numpy(w4h).to(device)
-                    f4 = np.empty(L.read_conv_f4x1_floats(self.cin, self.cout), np.float32)   # ... and the F(4,3)-by-rows order of the same family
-                    _lib.check(L.read_conv_pack_f4x1_host(self.cin, self.cout, wf.ctypes.data, wm.ctypes.data, f4.ctypes.data),
-                               "read_conv_pack_f4x1_host")
-                    self.wpacked_f4x1 = torch.from_numpy(f4).to(device)
-        if self.k in (1, 3, 4) and L.read_conv_dkh_floats(self.cin, self.cout, self.k):  # the plain weights as f16 piece pairs (direct split-operand kernels; 1x1: pixel-lane)
-            dkh = np.empty(L.read_conv_dkh_floats(self.cin, self.cout, self.k), np.float32)
-            _lib.check(L.read_conv_pack_dkh_host(self.cin, self.cout, self.k, wf.ctypes.data, wm.ctypes.data, dkh.ctypes.data),
-                       "read_conv_pack_dkh_host")
-            self.wpacked_d3h = torch.from_numpy(dkh).to(device)
+        dims = {"cin": self.cin, "cout": self.cout, "k": self.k, "kc": self.kc}
+        for attr, _, size, size_args, packer, pack_args, carried in WEIGHT_ORDERS:
+            n = getattr(L, size)(*(dims[a] for a in size_args)) if carried(self.cin, self.cout, self.k) else 0
+            buf = np.empty(n, np.float32)
+            if n:
+                _lib.check(getattr(L, packer)(*(dims[a] for a in pack_args), wf.ctypes.data, wm.ctypes.data, buf.ctypes.data), packer)
+            setattr(self, attr, torch.from_numpy(buf).to(device) if n else None)
 
 
 def gated_conv(packed, sources, **kw):
@@ -120,19 +115,16 @@ def _desc(packed, sources, stride=1, elu=True, mul=None, residual=None, config=-
     d.inH, d.inW = inH, inW
     d.Cout, d.ksize, d.stride = packed.cout, packed.k, stride
     d.elu = 1 if elu else 0
-    d.wpacked, d.params = packed.wpacked.data_ptr(), packed.params.data_ptr()
+    d.params = packed.params.data_ptr()
     d.residual = residual.data_ptr() if residual is not None else None
     d.out, d.out_cstride = out.data_ptr(), cs
     d.fill_pad = 0 if fill is None else 1
     d.out_fill = 0.0 if fill is None else float(fill)
     d.config = config
-    d.wpacked_wino = packed.wpacked_wino.data_ptr() if packed.wpacked_wino is not None else None
-    d.wpacked_w16 = packed.wpacked_w16.data_ptr() if packed.wpacked_w16 is not None else None
-    d.wpacked_w4 = packed.wpacked_w4.data_ptr() if packed.wpacked_w4 is not None else None
-    d.wpacked_sc = packed.wpacked_sc.data_ptr() if packed.wpacked_sc is not None else None
-    d.wpacked_w4h = packed.wpacked_w4h.data_ptr() if packed.wpacked_w4h is not None else None
-    d.wpacked_d3h = packed.wpacked_d3h.data_ptr() if packed.wpacked_d3h is not None else None
-    d.wpacked_t3h = packed.wpacked_t3h.data_ptr() if getattr(packed, "wpacked_t3h", None) is not None else None
+    for attr, in_desc, *_ in WEIGHT_ORDERS:
+        buf = getattr(packed, attr, None)
+        if in_desc:
+            setattr(d, attr, buf.data_ptr() if buf is not None else None)
     d.linear = 1 if linear else 0
     if pre is not None:
         pt, f_off, m_off, psh = pre[:4]

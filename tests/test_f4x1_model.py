@@ -195,15 +195,13 @@ def test_f4x1_order_in_the_unet_blobs():
     and a host derives the same bits from its direct fragments (read_conv_unpack_weights_host is the exact inverse of the packer);
     the lean layout without the order is still known, by its length."""
     import ctypes as C
-    from read_amd import synthetic
-    from read_amd.unet import LAYOUT_FULL, LAYOUT_LEAN, LAYOUT_LEAN_W4H, layout_of, pack_state
-    from tests.unet_spec import UNET_SPEC
+    from read_amd.unet import LAYOUT_FULL, LAYOUT_LEAN, LAYOUT_LEAN_W4H, layout_of
+    from tests.weight_order_cases import blob
     L = _lib()
     n_side = L.read_unet_f4x1_floats()
     assert L.read_unet_packed_floats_layout(LAYOUT_LEAN) == L.read_unet_packed_floats_layout(LAYOUT_LEAN_W4H) + n_side
     assert L.read_unet_packed_floats_layout(LAYOUT_FULL) == L.read_unet_packed_floats()
-    state = synthetic.make_unet_state(UNET_SPEC, 3)
-    full, lean, old = (pack_state(state, layout=l) for l in (LAYOUT_FULL, LAYOUT_LEAN, LAYOUT_LEAN_W4H))
+    full, lean, old = (blob(l) for l in (LAYOUT_FULL, LAYOUT_LEAN, LAYOUT_LEAN_W4H))     # pack_state(make_unet_state(UNET_SPEC, 3)), shared
     assert layout_of(old) == LAYOUT_LEAN_W4H and layout_of(lean) == LAYOUT_LEAN
     lean_b = lean.tobytes()
     w_off, s_off, cin, cout = C.c_size_t(), C.c_size_t(), C.c_int(), C.c_int()

@@ -239,8 +239,9 @@ def test_lean_packed_layout_is_a_subset_of_the_full_one():
     L = _lib.lib()
     n_full, n_lean = L.read_unet_packed_floats_layout(LAYOUT_FULL), L.read_unet_packed_floats_layout(LAYOUT_LEAN)
     assert n_full == L.read_unet_packed_floats() and 0 < n_lean < 0.5 * n_full and L.read_unet_packed_floats_layout(7) == 0
-    state = synthetic.make_unet_state(UNET_SPEC, 3)
-    full, lean = pack_state(state, layout=LAYOUT_FULL), pack_state(state, layout=LAYOUT_LEAN)
+    from tests.weight_order_cases import BLOB_SEED, blob
+    state = synthetic.make_unet_state(UNET_SPEC, BLOB_SEED)
+    full, lean = blob(LAYOUT_FULL), blob(LAYOUT_LEAN)                        # pack_state(state, layout=...), shared with other tests
     assert full.size == n_full and lean.size == n_lean and np.isfinite(lean).all()
     assert layout_of(full) == LAYOUT_FULL and layout_of(lean) == LAYOUT_LEAN
     with pytest.raises(_lib.ReadHipError):
