@@ -206,6 +206,35 @@ int read_splat_forward_pano(const float *xyz, const int32_t *ids, int64_t n, con
 int read_splat_pano_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel, float *depth,
                                    void *stream);
 
+/* Scene editing, third verb: ADD.  An instance = (a range of one point pool, its own matrix, a visible flag); ranges may repeat and
+ * overlap, so one object (a labelled cluster, or a "foreign" object cut out of another fitted scene and appended to the pool with
+ * ids N, N + 1, ... past the scene's) is drawn as often as it is listed.  Per pixel the minimum of depth bits << 32 | id over every
+ * visible point of every visible instance and of the static part wins; two copies of one point at the same pixel and depth have the
+ * same key.  The list may have any length (32 ranges per launch); hidden and empty instances are not launched.  The definition is
+ * tests/instances_model.py. */
+typedef struct read_splat_instances {
+    const float *xyz; const int32_t *ids; int64_t n;   /* device: the point pool (own objects' points, then foreign ones) */
+    int count;                                         /* instances */
+    const int64_t *first; const int64_t *npts;         /* host, count each: instance i draws pool points [first[i], first[i] + npts[i]) */
+    const float *M;                                    /* host, count x 16: M_i (pinhole) or the panorama layout of read_splat_forward_pano */
+    const unsigned char *visible;                      /* host, count, or NULL */
+} read_splat_instances;
+/* read_splat_forward_objects with an instance list in place of the partition: same routes (cell path for the static part with cells,
+ * n_static >= 2^20 and W % 16 == 0, the instances after its pass B; otherwise the static part is one more range with M_0), same
+ * workspace, stream ordering and read_splat_hint_next_camera behaviour; allocates nothing, no synchronisation.  With the list
+ * first[k] = begin[k], npts[k] = begin[k + 1] - begin[k] the result is read_splat_forward_objects', bit for bit.  READ_EINVAL before
+ * any device work for null pointers, count < 0, a negative first or npts, first + npts > n, and W or H off the pyramid. */
+int read_splat_forward_instances(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
+                                 const float *M_host, int W, int H, int levels, const read_splat_instances *inst,
+                                 int32_t *const *idx_levels, float *const *depth_levels,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+/* read_splat_forward_pano with an instance list (inst must not be NULL; no warm start): xyz / ids / n as there (ids == NULL: the id is
+ * the point's index).  Also refuses non-finite camera entries and kx < 1 / pi, of cam_host and of every instance that is drawn. */
+int read_splat_forward_pano_instances(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host,
+                                      int W, int H, int levels, const read_splat_instances *inst,
+                                      int32_t *const *idx_levels, float *const *depth_levels,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* Measurement aid for bench.py (roofline.mfma_sustained): one workgroup of four waves per CU, every wave `iters` rounds of 16 independent
  * v_mfma_f32_16x16x4_f32 and nothing else.  scratch: >= 256 floats per CU on the device (never written); *flops receives the number of
  * floating-point operations the launch executes — the caller times the launch on `stream`.  Not on the render path. */
@@ -274,6 +303,22 @@ int read_gather_forward(const float *rows_nc, int64_t n, int C, int levels,
 int read_gather_forward_ss(const float *rows_nc, int64_t n, int C, int levels, int B,
                            const int32_t *const *idx_levels, const int *h_levels, const int *w_levels, int ss,
                            float *const *feat_levels, int activation, void *stream);
+/* The gather over several descriptor tables (csrc/gather.hip, gather_tables_kernel; the definition is tests/instances_model.py): an
+ * index image may carry ids of objects that were added to a scene with their own small tables, and the scene's table is never copied
+ * to append them.  Table t of count (1..READ_GATHER_MAX_TABLES) serves ids in [id_base_t, id_base_t + n_t); id_base_0 = 0, bases
+ * ascend, ranges do not overlap (gaps may remain).  feat_l[p][:] = act_t(rows_t[id - id_base_t][:]) with t = the last table whose base
+ * is <= id and the local id clamped to n_t - 1; an id below 0 reads row 0 of table 0.  count = 1: read_gather_forward, bit for bit;
+ * equal activations and no gaps: the plain gather over the concatenated tables, bit for bit.  All levels in one launch; stream-ordered,
+ * allocates nothing, no synchronisation.  READ_EINVAL before any device work for: a null table list or level table, count outside
+ * 1..READ_GATHER_MAX_TABLES, C % 4 != 0, levels outside 1..READ_MAX_LEVELS, null or misaligned rows, n < 1, an activation outside
+ * 0..2, id_base_0 != 0, bases not ascending or ranges overlapping, id_base + n > INT32_MAX, a null level. */
+#define READ_GATHER_MAX_TABLES 8
+typedef struct read_gather_table {
+    const float *rows_nc; int64_t n; int64_t id_base; int activation;
+} read_gather_table;
+int read_gather_forward_tables(const read_gather_table *tables, int count, int C, int levels,
+                               const int32_t *const *idx_levels, const int64_t *count_levels,
+                               float *const *feat_levels, void *stream);
 /*
  * Scene stitching: several fitted scenes ("parts", 1..READ_STITCH_MAX_PARTS) in one frame.  Every part is rasterised on its own
  * (read_splat_forward*, camera M_s = M_0 @ P_s) into a pyramid of LOCAL ids and depths; this call merges the pyramids and gathers

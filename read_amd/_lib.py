@@ -65,6 +65,20 @@ class SplatObjects(C.Structure):
                 ("M", C.c_void_p), ("visible", C.c_void_p)]
 
 
+class SplatInstances(C.Structure):
+    """read_splat_instances (include/read_hip.h): the instance list of one read_splat_forward_instances call."""
+    _fields_ = [("xyz", C.c_void_p), ("ids", C.c_void_p), ("n", C.c_int64), ("count", C.c_int), ("first", C.c_void_p),
+                ("npts", C.c_void_p), ("M", C.c_void_p), ("visible", C.c_void_p)]
+
+
+READ_GATHER_MAX_TABLES = 8
+
+
+class GatherTable(C.Structure):
+    """read_gather_table (include/read_hip.h): one descriptor table of a read_gather_forward_tables call."""
+    _fields_ = [("rows_nc", C.c_void_p), ("n", C.c_int64), ("id_base", C.c_int64), ("activation", C.c_int)]
+
+
 READ_STITCH_MAX_PARTS = 8
 
 
@@ -106,6 +120,8 @@ SIGNATURES = {
     "read_splat_cells_build_ids": (_i, [_vp, _vp, _i64, _vp, _sz, _vp, _sz, _vp]),
     "read_splat_forward_objects": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_forward_pano": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
+    "read_splat_forward_instances": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
+    "read_splat_forward_pano_instances": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_pano_project_points": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp]),
     "read_splat_forward_cells": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _i, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_hint_next_camera": (_i, [_vp, C.POINTER(_f)]),
@@ -118,6 +134,7 @@ SIGNATURES = {
     "read_rows_to_texture": (_i, [_vp, _i64, _i, _vp, _vp]),
     "read_gather_forward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _i, _vp]),
     "read_gather_forward_ss": (_i, [_vp, _i64, _i, _i, _i, _pp, C.POINTER(_i), C.POINTER(_i), _i, _pp, _i, _vp]),
+    "read_gather_forward_tables": (_i, [C.POINTER(GatherTable), _i, _i, _i, _pp, C.POINTER(_i64), _pp, _vp]),
     "read_gather_backward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _vp]),
     "read_stitch_gather_forward": (_i, [C.POINTER(StitchPart), _i, _i, _i, C.POINTER(_i64), _pp, _pp, _pp, _pp, _vp]),
     "read_bilinear_down": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),

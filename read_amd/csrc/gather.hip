@@ -183,6 +183,51 @@ __global__ __launch_bounds__(256) void stitch_gather_kernel(StitchTable tab, int
     }
 }
 
+// The gather over several tables (read_gather_forward_tables): gather_forward_kernel's item mapping, loads and stores; the table list
+// travels by value in the kernel arguments.  Table t serves ids in [base_t, base_t + n_t), bases ascending from 0: the table of an id
+// is the LAST one whose base is <= id — a loop of compare-and-selects with a wave-uniform trip count, no divergent branch; the local id
+// is clamped to [0, n_t) (an id in a gap or past the end reads its table's last row, an id below 0 row 0 of table 0: the plain
+// kernel's defensive clamp, generalised).
+struct GatherTables {
+    const float *rows[READ_GATHER_MAX_TABLES];
+    long long n[READ_GATHER_MAX_TABLES];
+    long long base[READ_GATHER_MAX_TABLES];
+    int act[READ_GATHER_MAX_TABLES];
+    int count;
+};
+
+__global__ __launch_bounds__(256) void gather_tables_kernel(GatherTables tt, int C, LevelTable tab)
+{
+    const int qpp = C >> 2;
+    const long long total = tab.end[tab.levels - 1];
+    for (long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x; item < total;
+         item += (long long)gridDim.x * blockDim.x) {
+        int l = 0;
+        long long base = 0;
+#pragma unroll
+        for (int k = 0; k < READ_MAX_LEVELS - 1; ++k)
+            if (k < tab.levels - 1 && item >= tab.end[k]) { l = k + 1; base = tab.end[k]; }
+        const long long local = item - base;
+        const long long pix = local / qpp;
+        const int q = (int)(local - pix * qpp);
+        const long long gid = tab.idx[l][pix];
+        const float *rows = tt.rows[0];
+        long long n = tt.n[0], b = 0;
+        int act = tt.act[0];
+        for (int t = 1; t < tt.count; ++t) {
+            const bool take = gid >= tt.base[t];
+            rows = take ? tt.rows[t] : rows;
+            n = take ? tt.n[t] : n;
+            b = take ? tt.base[t] : b;
+            act = take ? tt.act[t] : act;
+        }
+        long long id = gid - b;
+        id = id < 0 ? 0 : (id >= n ? n - 1 : id);
+        const float4 v = act4(*reinterpret_cast<const float4 *>(rows + id * C + 4 * q), act);
+        *reinterpret_cast<float4 *>(tab.feat[l] + pix * C + 4 * q) = v;
+    }
+}
+
 // Bilinear down-scale by an integer factor of NCHW planes: torch's F.interpolate(scale_factor = 1 / ss, mode = 'bilinear',
 // align_corners = False) as READ/models/compose.py:162-163 applies it to the concatenated (non-uv extras + texture sample)
 // network inputs.  out[p][oy][ox] = blend of the 4 samples around ((o + 0.5) * ss - 0.5); lane = output pixel of a plane.
@@ -351,6 +396,62 @@ extern "C" int read_gather_forward(const float *rows_nc, int64_t n, int C, int l
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(gather_forward_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), rows_nc,
                        (long long)n, C, tab, activation);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+extern "C" int read_gather_forward_tables(const read_gather_table *tables, int count, int C, int levels,
+                                          const int32_t *const *idx_levels, const int64_t *count_levels,
+                                          float *const *feat_levels, void *stream)
+{
+    const char *who = "read_gather_forward_tables";
+    READ_CHECK_ARG(count >= 1 && count <= READ_GATHER_MAX_TABLES, "%s: count must be 1..%d tables (got %d)", who,
+                   READ_GATHER_MAX_TABLES, count);
+    READ_CHECK_ARG(C >= 4 && C % 4 == 0 && C <= 64, "%s: C must be a multiple of 4 in [4,64] (got %d)", who, C);
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d (got %d)", who, READ_MAX_LEVELS, levels);
+    READ_CHECK_ARG(tables && idx_levels && count_levels && feat_levels, "%s: null table list or level table", who);
+    GatherTables tt;
+    memset(&tt, 0, sizeof(tt));
+    for (int t = 0; t < count; ++t) {
+        const read_gather_table &g = tables[t];
+        READ_CHECK_ARG(g.rows_nc && (uintptr_t)g.rows_nc % 16 == 0, "%s: table %d: rows null or misaligned", who, t);
+        READ_CHECK_ARG(g.n >= 1, "%s: table %d: empty descriptor table", who, t);
+        READ_CHECK_ARG(g.activation >= 0 && g.activation <= 2, "%s: table %d: activation must be 0,1,2", who, t);
+        if (t == 0)
+            READ_CHECK_ARG(g.id_base == 0, "%s: table 0: id_base must be 0 (got %lld)", who, (long long)g.id_base);
+        else {
+            READ_CHECK_ARG(g.id_base > tables[t - 1].id_base, "%s: table %d: id_base %lld does not ascend", who, t,
+                           (long long)g.id_base);
+            READ_CHECK_ARG(g.id_base >= tables[t - 1].id_base + tables[t - 1].n,
+                           "%s: table %d: id_base %lld overlaps the range of table %d, which ends at %lld", who, t,
+                           (long long)g.id_base, t - 1, (long long)(tables[t - 1].id_base + tables[t - 1].n));
+        }
+        READ_CHECK_ARG(g.id_base <= (int64_t)INT32_MAX && g.n <= (int64_t)INT32_MAX && g.id_base + g.n <= (int64_t)INT32_MAX,
+                       "%s: table %d: id_base %lld + n %lld leaves the int32 id range", who, t, (long long)g.id_base, (long long)g.n);
+        tt.rows[t] = g.rows_nc;
+        tt.n[t] = g.n;
+        tt.base[t] = g.id_base;
+        tt.act[t] = g.activation;
+    }
+    tt.count = count;
+    LevelTable tab;
+    memset(&tab, 0, sizeof(tab));
+    long long acc = 0;
+    const int qpp = C / 4;
+    for (int l = 0; l < levels; ++l) {
+        READ_CHECK_ARG(count_levels[l] >= 0, "%s: negative pixel count", who);
+        READ_CHECK_ARG(count_levels[l] == 0 || (idx_levels[l] && feat_levels[l]), "%s: null level %d", who, l);
+        READ_CHECK_ARG((uintptr_t)feat_levels[l] % 16 == 0, "%s: feat level %d misaligned", who, l);
+        tab.idx[l] = idx_levels[l];
+        tab.feat[l] = feat_levels[l];
+        acc += count_levels[l] * qpp;
+        tab.end[l] = acc;
+    }
+    tab.levels = levels;
+    if (acc == 0) return READ_OK;
+    int64_t blocks = ceil_div64(acc, 256);
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(gather_tables_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tt, C, tab);
     READ_CHECK_LAUNCH();
     return READ_OK;
 }

@@ -1787,7 +1787,9 @@ StripInfo make_strips(int W)
 struct ObjectsDraw {
     const float *xyz;                 // device: every object's points, object after object
     const int32_t *ids;               // device: their original ids
-    const int64_t *begin;             // host, count + 1
+    const int64_t *begin;             // host, count + 1: range k = [begin[k], begin[k + 1]) — the partition of read_splat_objects
+    const int64_t *first, *npts;      // host, count each, used instead of begin when first != NULL: range k = [first[k], first[k] +
+                                      // npts[k]) — the instance list of read_splat_instances (ranges may repeat and overlap)
     const float *M;                   // host, count x 16
     const unsigned char *visible;     // host, count, or NULL (all visible)
     int count;
@@ -1834,8 +1836,9 @@ int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys
         if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
     }
     for (int k = 0; k < od.count; ++k) {
-        if ((od.visible && !od.visible[k]) || od.begin[k + 1] == od.begin[k]) continue;     // hidden or empty: not launched
-        objects_add(ob, blocks, od.begin[k], od.begin[k + 1], od.M + 16 * (size_t)k);
+        const int64_t first = od.first ? od.first[k] : od.begin[k], last = od.first ? first + od.npts[k] : od.begin[k + 1];
+        if ((od.visible && !od.visible[k]) || last == first) continue;                      // hidden or empty: not launched
+        objects_add(ob, blocks, first, last, od.M + 16 * (size_t)k);
         if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
     }
     return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream, pano);
@@ -2825,6 +2828,47 @@ extern "C" int read_splat_forward_cells(const float *xyz, void *cells, int64_t n
     return READ_OK;
 }
 
+namespace {
+// The frame of read_splat_forward_objects / read_splat_forward_instances once the arguments are checked: od carries the ranges (a
+// partition or an instance list) and the static part with n0 = 0; the route is chosen here.
+int objects_frame(ObjectsDraw &od, void *cells, int64_t n_static, const float *M_host, int W, int H, int levels,
+                  int32_t *const *idx_levels, float *const *depth_levels, void *ws, hipStream_t s)
+{
+    const WsLayout L = ws_layout(ws, 1, W, H);
+    if (cells && g_splat_cells && g_splat_mode == MODE_HIZ && n_static >= (1 << 20) && (W & 15) == 0) {
+        // the cell path for the static part (its blob from read_splat_cells_build_ids), the objects after its pass B
+        const CellOffsets o = cell_offsets(n_static);
+        CellCloud cc;
+        cc.hdr = (const CellHeader *)cells;
+        cc.pts = (const float4 *)((const char *)cells + o.pts);
+        cc.aabb = (const float *)((const char *)cells + o.aabb);
+        cc.list_a = (int *)((char *)cells + o.list_a);
+        cc.list_b = (CellEntryB *)((char *)cells + o.list_b);
+        cc.sticky = (unsigned char *)cells + o.sticky;
+        cc.nchunks = (int)cells_chunks(n_static);
+        cc.hdr_n = n_static;
+        cc.sticky_frames = g_splat_sticky;
+        cc.mark_candidates = g_splat_mark && g_splat_sticky > 0;
+        return cells_frame(cc, M_host, W, H, levels, idx_levels, depth_levels, L, s, 0, &od);
+    }
+    // Otherwise the static part is one more range of splat_objects_kernel with M_0 and its explicit ids (never the plain pass,
+    // whose keys and warm start carry implicit ids), and the resolve keeps no seeds
+    {
+        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
+        auto it = g_ws_host.find(ws);
+        if (it != g_ws_host.end()) {
+            it->second.hinted = false;
+            const int rc = ws_drop_prediction(it->second, s);
+            if (rc != READ_OK) return rc;
+        }
+    }
+    od.n0 = n_static;
+    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s);
+    if (rc != READ_OK) return rc;
+    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
+}
+}  // namespace
+
 // Scene editing: the static part (label 0, its original ids; through its id-mapped cell blob when the cell path serves it) and
 // the objects of `objs`, one camera.  Every check precedes the first launch.
 extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
@@ -2863,6 +2907,7 @@ extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t
     od.xyz = objs->xyz;
     od.ids = objs->ids;
     od.begin = objs->begin;
+    od.first = od.npts = nullptr;
     od.M = objs->M;
     od.visible = objs->visible;
     od.count = objs->count;
@@ -2870,39 +2915,7 @@ extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t
     od.ids0 = ids_static;
     od.n0 = 0;
     od.M0 = M_host;
-    const WsLayout L = ws_layout(ws, 1, W, H);
-    hipStream_t s = as_stream(stream);
-    if (cells && g_splat_cells && g_splat_mode == MODE_HIZ && n_static >= (1 << 20) && (W & 15) == 0) {
-        // the cell path for the static part (its blob from read_splat_cells_build_ids), the objects after its pass B
-        const CellOffsets o = cell_offsets(n_static);
-        CellCloud cc;
-        cc.hdr = (const CellHeader *)cells;
-        cc.pts = (const float4 *)((const char *)cells + o.pts);
-        cc.aabb = (const float *)((const char *)cells + o.aabb);
-        cc.list_a = (int *)((char *)cells + o.list_a);
-        cc.list_b = (CellEntryB *)((char *)cells + o.list_b);
-        cc.sticky = (unsigned char *)cells + o.sticky;
-        cc.nchunks = (int)cells_chunks(n_static);
-        cc.hdr_n = n_static;
-        cc.sticky_frames = g_splat_sticky;
-        cc.mark_candidates = g_splat_mark && g_splat_sticky > 0;
-        return cells_frame(cc, M_host, W, H, levels, idx_levels, depth_levels, L, s, 0, &od);
-    }
-    // Otherwise the static part is one more range of splat_objects_kernel with M_0 and its explicit ids (never the plain pass,
-    // whose keys and warm start carry implicit ids), and the resolve keeps no seeds
-    {
-        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
-        auto it = g_ws_host.find(ws);
-        if (it != g_ws_host.end()) {
-            it->second.hinted = false;
-            const int rc = ws_drop_prediction(it->second, s);
-            if (rc != READ_OK) return rc;
-        }
-    }
-    od.n0 = n_static;
-    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s);
-    if (rc != READ_OK) return rc;
-    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
+    return objects_frame(od, cells, n_static, M_host, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
 }
 
 namespace {
@@ -2913,6 +2926,32 @@ const char *pano_cam_fault(const float *c)
         if (!std::isfinite(c[i])) return "a camera entry is not finite";
     if (!(c[12] >= (float)(1.0 / 3.14159265358979323846))) return "kx = 2 / hfov_rad must be >= 1 / pi (a field of at most 360 degrees)";
     return nullptr;
+}
+
+// The panorama frame once the arguments are checked: one range launch for the static part, the ranges of od, the resolve.
+int pano_frame(const ObjectsDraw &od, bool seeds, int W, int H, int levels, int32_t *const *idx_levels, float *const *depth_levels,
+               void *ws, hipStream_t s)
+{
+    const WsLayout L = ws_layout(ws, 1, W, H);
+    {
+        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
+        auto it = g_ws_host.find(ws);
+        if (it != g_ws_host.end()) {
+            it->second.hinted = false;
+            const int rc = ws_drop_prediction(it->second, s);
+            if (rc != READ_OK) return rc;
+        }
+    }
+    if (seeds && g_splat_seeds) {
+        Cam1 cam;
+        memcpy(cam.m, od.M0, sizeof(cam.m));
+        hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, W, H, L.keys,
+                           (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
+        READ_CHECK_LAUNCH();
+    }
+    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s, true);
+    if (rc != READ_OK) return rc;
+    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
 }
 }  // namespace
 
@@ -2958,17 +2997,6 @@ extern "C" int read_splat_forward_pano(const float *xyz, const int32_t *ids, int
         set_error("read_splat_forward_pano: workspace %zu < %zu bytes", ws_bytes, read_splat_workspace_bytes(1, W, H));
         return READ_ENOMEM;
     }
-    const WsLayout L = ws_layout(ws, 1, W, H);
-    hipStream_t s = as_stream(stream);
-    {
-        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
-        auto it = g_ws_host.find(ws);
-        if (it != g_ws_host.end()) {
-            it->second.hinted = false;
-            const int rc = ws_drop_prediction(it->second, s);
-            if (rc != READ_OK) return rc;
-        }
-    }
     ObjectsDraw od;
     memset(&od, 0, sizeof(od));
     if (objs) {
@@ -2984,17 +3012,105 @@ extern "C" int read_splat_forward_pano(const float *xyz, const int32_t *ids, int
     od.n0 = n;
     od.M0 = cam_host;
     // seeds carry implicit ids: only a cloud drawn whole, with its indices as ids, keeps and uses them
-    const bool seeds = !objs && !ids && n > 0 && g_splat_mode == MODE_HIZ;
-    if (seeds && g_splat_seeds) {
-        Cam1 cam;
-        memcpy(cam.m, cam_host, sizeof(cam.m));
-        hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, xyz, (long long)n, cam, W, H, L.keys,
-                           (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
-        READ_CHECK_LAUNCH();
+    return pano_frame(od, !objs && !ids && n > 0 && g_splat_mode == MODE_HIZ, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+}
+
+namespace {
+// what both instance entry points ask of a read_splat_instances before any device work
+int check_instances(const char *who, const read_splat_instances *inst)
+{
+    READ_CHECK_ARG(inst->count >= 0, "%s: inst->count = %d is negative", who, inst->count);
+    READ_CHECK_ARG(inst->n >= 0 && inst->n <= 0xFFFFFFFEll, "%s: inst->n out of range", who);
+    READ_CHECK_ARG(inst->count == 0 || (inst->first && inst->npts && inst->M), "%s: null pointer (inst->first, inst->npts or inst->M)", who);
+    READ_CHECK_ARG(inst->n == 0 || (inst->xyz && inst->ids), "%s: null pointer (inst->xyz or inst->ids)", who);
+    for (int i = 0; i < inst->count; ++i) {
+        READ_CHECK_ARG(inst->first[i] >= 0 && inst->npts[i] >= 0, "%s: instance %d: first = %lld, npts = %lld: negative", who, i,
+                       (long long)inst->first[i], (long long)inst->npts[i]);
+        READ_CHECK_ARG(inst->first[i] <= inst->n && inst->npts[i] <= inst->n - inst->first[i],
+                       "%s: instance %d: first + npts = %lld + %lld > inst->n = %lld", who, i, (long long)inst->first[i],
+                       (long long)inst->npts[i], (long long)inst->n);
     }
-    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s, true);
+    return READ_OK;
+}
+
+void instances_draw(ObjectsDraw &od, const read_splat_instances *inst)
+{
+    memset(&od, 0, sizeof(od));
+    od.xyz = inst->xyz;
+    od.ids = inst->ids;
+    od.first = inst->first;
+    od.npts = inst->npts;
+    od.M = inst->M;
+    od.visible = inst->visible;
+    od.count = inst->count;
+}
+}  // namespace
+
+// read_splat_forward_objects over an instance list: the same frame (objects_frame), the ranges explicit.
+extern "C" int read_splat_forward_instances(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
+                                            const float *M_host, int W, int H, int levels, const read_splat_instances *inst,
+                                            int32_t *const *idx_levels, float *const *depth_levels, void *ws, size_t ws_bytes,
+                                            void *stream)
+{
+    const char *who = "read_splat_forward_instances";
+    READ_CHECK_ARG(M_host && inst && ws, "%s: null pointer (M_host, inst or workspace)", who);
+    READ_CHECK_ARG(idx_levels || depth_levels, "%s: no outputs requested", who);
+    READ_CHECK_ARG(n_static >= 0 && n_static <= 0xFFFFFFFEll, "%s: n_static out of range", who);
+    READ_CHECK_ARG(n_static == 0 || (xyz_static && ids_static), "%s: null pointer (static xyz or ids)", who);
+    int rc = check_instances(who, inst);
     if (rc != READ_OK) return rc;
-    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d", who, READ_MAX_LEVELS);
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad size (%d,%d)", who, W, H);
+    const int mask = (1 << (levels - 1)) - 1;
+    READ_CHECK_ARG(((W | H) & mask) == 0, "%s: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", who, W, H, mask + 1);
+    READ_CHECK_ARG((uintptr_t)ws % 256 == 0 && (uintptr_t)cells % 256 == 0, "%s: workspace and cells must be 256-byte aligned", who);
+    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
+        set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, read_splat_workspace_bytes(1, W, H));
+        return READ_ENOMEM;
+    }
+    ObjectsDraw od;
+    instances_draw(od, inst);
+    od.xyz0 = xyz_static;
+    od.ids0 = ids_static;
+    od.M0 = M_host;
+    return objects_frame(od, cells, n_static, M_host, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+}
+
+// read_splat_forward_pano over an instance list (no warm start: the ids are explicit).
+extern "C" int read_splat_forward_pano_instances(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H,
+                                                 int levels, const read_splat_instances *inst, int32_t *const *idx_levels,
+                                                 float *const *depth_levels, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *who = "read_splat_forward_pano_instances";
+    READ_CHECK_ARG(cam_host && inst && ws, "%s: null pointer (cam_host, inst or workspace)", who);
+    READ_CHECK_ARG(idx_levels || depth_levels, "%s: no outputs requested", who);
+    READ_CHECK_ARG(n >= 0 && n <= 0xFFFFFFFEll, "%s: n out of range", who);
+    READ_CHECK_ARG(n == 0 || xyz, "%s: null pointer (xyz)", who);
+    int rc = check_instances(who, inst);
+    if (rc != READ_OK) return rc;
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d", who, READ_MAX_LEVELS);
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad size (%d,%d)", who, W, H);
+    const int mask = (1 << (levels - 1)) - 1;
+    READ_CHECK_ARG(((W | H) & mask) == 0, "%s: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", who, W, H, mask + 1);
+    const char *fault = pano_cam_fault(cam_host);
+    READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
+    for (int i = 0; i < inst->count; ++i) {
+        if ((inst->visible && !inst->visible[i]) || inst->npts[i] == 0) continue;
+        fault = pano_cam_fault(inst->M + 16 * (size_t)i);
+        READ_CHECK_ARG(!fault, "%s: inst->M of instance %d: %s", who, i, fault);
+    }
+    READ_CHECK_ARG((uintptr_t)ws % 256 == 0, "%s: workspace must be 256-byte aligned", who);
+    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
+        set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, read_splat_workspace_bytes(1, W, H));
+        return READ_ENOMEM;
+    }
+    ObjectsDraw od;
+    instances_draw(od, inst);
+    od.xyz0 = xyz;
+    od.ids0 = ids;
+    od.n0 = n;
+    od.M0 = cam_host;
+    return pano_frame(od, false, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
 }
 
 extern "C" int read_splat_forward_gl(const float *xyz, int64_t n, const float *M_host, int W, int H,

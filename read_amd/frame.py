@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from .camera import level_sizes, pano_camera, total_matrix
 from .raster import PointCloudRasterizer
-from .texture import gather_pyramid, texture_to_rows
+from .texture import gather_pyramid, gather_tables_pyramid, texture_to_rows
 from .unet import LAYOUT_FULL, UNetEngine, default_layout, layout_of, pack_state
 
 LEVELS = 5          # the reference rasterises and gathers 5 scales; the UNet consumes 4 (unet.py:209-212)
@@ -60,6 +60,7 @@ class FrameRenderer:
                              f"{self.raster.n} points")
         tex = torch.as_tensor(texture_cn, dtype=torch.float32).to(self.device).contiguous()
         self.rows = texture_to_rows(tex)
+        self.foreign_rows = []           # add_object: (rows (m,C), activation) of every foreign object, in id order
         self.packed, self.unet = unet_engine(unet_state, self.device, H, W)
         self.proj = None if proj_matrix is None else np.asarray(proj_matrix, np.float32)
         sizes = level_sizes(W, H, levels)
@@ -96,14 +97,44 @@ class FrameRenderer:
     def set_object_visible(self, k, flag):
         self.raster.set_object_visible(k, flag)
 
+    def add_object(self, xyz, texture_cn, activation='none'):
+        """A foreign object (PointCloudRasterizer.add_object): (m,3) points and their (C,m) descriptors.  -> k for add_instance."""
+        tex = torch.as_tensor(texture_cn, dtype=torch.float32).to(self.device).contiguous()
+        if tex.dim() != 2 or int(tex.shape[0]) != int(self.rows.shape[1]) or int(tex.shape[1]) != int(np.shape(xyz)[0]):
+            raise ValueError(f"a foreign object of {int(np.shape(xyz)[0])} points takes ({int(self.rows.shape[1])}, m) descriptors, "
+                             f"got {tuple(tex.shape)}")
+        if len(self.foreign_rows) + 2 > _lib.READ_GATHER_MAX_TABLES:
+            raise ValueError(f"the table gather serves {_lib.READ_GATHER_MAX_TABLES - 1} foreign objects")
+        k = self.raster.add_object(xyz)
+        self.foreign_rows.append((texture_to_rows(tex), activation))
+        return k
+
+    def add_instance(self, k, P=None, visible=True):
+        """One more copy of object k from the next frame enqueued (also with frames_in_flight > 1).  -> a handle."""
+        return self.raster.add_instance(k, P, visible)
+
+    def set_instance_pose(self, handle, P):
+        self.raster.set_instance_pose(handle, P)
+
+    def set_instance_visible(self, handle, flag):
+        self.raster.set_instance_visible(handle, flag)
+
+    def remove_instance(self, handle):
+        self.raster.remove_instance(handle)
+
     def rasterize(self, total_m, next_total=None):
         return self.raster.render(total_m, self.W, self.H, self.levels, out=(self.idx, self.depth), next_total=next_total)
 
     def rasterize_pano(self, cam):
         return self.raster.render_pano(cam, self.W, self.H, self.levels, out=(self.idx, self.depth))
 
-    def gather(self):
-        return gather_pyramid(self.rows, self.idx, out=self.feat)
+    def gather(self, out=None):
+        out = self.feat if out is None else out
+        if self.foreign_rows:
+            ranges = self.raster.id_ranges()
+            tables = [(self.rows, 0, 'none')] + [(r, base, act) for (r, act), (base, _) in zip(self.foreign_rows, ranges[1:])]
+            return gather_tables_pyramid(tables, self.idx, out=out)
+        return gather_pyramid(self.rows, self.idx, out=out)
 
     def refine(self, out=None, channels=4):
         f = self.feat
@@ -135,7 +166,7 @@ class FrameRenderer:
         with torch.cuda.stream(rs):
             rs.wait_event(slot["done"])                  # this slot's features were last read by the frame F calls ago
             rasterize()
-            gather_pyramid(self.rows, self.idx, out=slot["feat"])
+            self.gather(slot["feat"])
             slot["ready"].record(rs)
         us = slot["stream"]
         with torch.cuda.stream(us):

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from .render import MultiscaleRender, is_point_id_pyramid
-from .texture import gather_pyramid, stitch_gather_pyramid
+from .texture import gather_pyramid, gather_tables_pyramid, stitch_gather_pyramid
 
 
 class OGL:
@@ -84,6 +84,9 @@ class OGL:
         pano = getattr(self.renderer.scene, 'panorama', None) is not None
         if pano:
             self._require_pano_fast(input_dict)
+        foreign = bool(getattr(self.renderer.scene, 'foreign_objects', None))
+        if foreign:
+            self._require_foreign_fast(input_dict)
         self.last_path = 'fast' if fast else 'dict'
         with torch.set_grad_enabled(False):
             if fast:
@@ -100,7 +103,10 @@ class OGL:
                 else:
                     idx, _ = raster.render(scene.total_matrix(), ss * W, ss * H, len(fmts), want_depth=False,
                                            next_total=scene.take_next_total_matrix())      # Scene.announce_next_camera_view
-                feats = gather_pyramid(texture.rows(), idx, texture.activation, ss=ss)
+                if foreign:                                      # ids >= N live in the foreign objects' own tables
+                    feats = gather_tables_pyramid(scene.gather_tables(texture), idx)
+                else:
+                    feats = gather_pyramid(texture.rows(), idx, texture.activation, ss=ss)
                 out = model.net.engine(H, W).forward(feats[0][0], feats[1][0], feats[2][0], feats[3][0], channels=4)
                 net_input = [f.permute(0, 3, 1, 2) for f in feats]
             else:
@@ -119,6 +125,24 @@ class OGL:
         if input_dict is not None:
             res['input'] = input_dict
         return res
+
+    def _require_foreign_fast(self, input_dict):
+        """Foreign objects (Scene.add_foreign_object) are drawn on the fast path only: the dict path's single-table lookup would see
+        ids >= N.  What would leave the fast path is refused by name."""
+        model, scene = self.model, self.renderer.scene
+        if input_dict is not None:
+            raise NotImplementedError("a caller-supplied input_dict with foreign objects (add_foreign_object)")
+        if model.temporal_average:
+            raise NotImplementedError("temporal_average with foreign objects (add_foreign_object)")
+        if int(model.ss) > 1:
+            raise NotImplementedError(f"supersampling {int(model.ss)} with foreign objects (add_foreign_object): the table gather "
+                                      "has no supersampled form")
+        if scene.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with foreign objects "
+                                      "(add_foreign_object)")
+        if not self._fast_format or not hasattr(model.net, 'engine'):
+            raise NotImplementedError(f"input format {self.input_format!r} with foreign objects (add_foreign_object): only the "
+                                      "point-id pyramid of at least four scales on the HIP UNet is served")
 
     def _require_pano_fast(self, input_dict):
         """A panorama camera (Scene.set_panorama) is drawn on the fast path only; what would leave it is refused by name."""

@@ -30,7 +30,9 @@ class PointCloudRasterizer:
         labels: None, or one object label per point (ints in [0, MAX_LABEL]; 0 = the static scene) — scene editing: label k >= 1
         is drawn with M_0 @ P_k (``set_object_pose``) and can be hidden (``set_object_visible``), see ``render``.  The cloud is
         split once on the device: the static part gets its own id-mapped cell blob, the objects' points are compacted label
-        after label.  Index images keep the original ids.  New labels mean a new rasteriser; poses and visibility never do."""
+        after label.  Index images keep the original ids.  New labels mean a new rasteriser; poses and visibility never do.
+        Objects are ADDED with ``add_instance`` (one more copy of a label) and ``add_object`` (points from elsewhere with ids past
+        the cloud's, also on a cloud without labels); from then on frames go through read_splat_forward_instances."""
         self.device = device if device is not None else _lib.require_gpu()
         xyz = torch.as_tensor(np.ascontiguousarray(xyz, dtype=np.float32) if not torch.is_tensor(xyz) else xyz)
         if xyz.dim() != 2 or xyz.shape[1] != 3:
@@ -40,6 +42,8 @@ class PointCloudRasterizer:
         self._workspaces = {}
         self._ws = None
         self.labels = None
+        self._foreign = []            # add_object: (xyz tensor, id_base) of every foreign object, in order
+        self._inst = None             # None until add_object / add_instance: then {handle: instance}, drawn in handle order
         if labels is not None:
             if torch.is_tensor(cells):
                 raise ValueError("a cloud with object labels builds its own cell blob (the static part's)")
@@ -108,7 +112,134 @@ class PointCloudRasterizer:
             out[i] = object_matrix(M0, self._poses.get(i + 1)).reshape(16)
         return out
 
+    # ---- scene editing, third verb: add ------------------------------------------------------------------------------------
+    def _own_objects(self):
+        return self.n_objects if self.labels is not None else 0
+
+    def _start_instances(self):
+        """The switch from the partition (read_splat_forward_objects) to the instance list: every own label starts with one
+        instance, the object itself, whose pose and flag stay those of set_object_pose / set_object_visible."""
+        if self._inst is not None:
+            return
+        if self.labels is None:       # a cloud without labels: every point is static; the ids the range kernel needs, no xyz copy
+            self._static_xyz, self.n_static = self.xyz, self.n
+            self._static_ids = torch.arange(self.n, dtype=torch.int32, device=self.device)
+            self._poses = {}
+        self._inst = {k - 1: {'k': k, 'own': True} for k in range(1, self._own_objects() + 1)}
+        self._next_handle = self._own_objects()
+        self._rebuild_pool()
+
+    def _rebuild_pool(self):
+        """The point pool of the instance path: the own objects' compacted points, then the foreign objects'; ids alongside."""
+        K = self._own_objects()
+        xyz = [self._obj_xyz] if K else []
+        ids = [self._obj_ids] if K else []
+        ranges = [(int(self._begin[k]), int(self._begin[k + 1] - self._begin[k])) for k in range(K)]
+        at = int(self._begin[K]) if K else 0
+        for fx, base in self._foreign:
+            m = int(fx.shape[0])
+            xyz.append(fx)
+            ids.append(torch.arange(base, base + m, dtype=torch.int32, device=self.device))
+            ranges.append((at, m))
+            at += m
+        self._pool_xyz = torch.cat(xyz).contiguous() if xyz else torch.empty((0, 3), dtype=torch.float32, device=self.device)
+        self._pool_ids = torch.cat(ids).contiguous() if ids else torch.empty(0, dtype=torch.int32, device=self.device)
+        self._ranges = ranges          # object k = pool points [first, first + n) = self._ranges[k - 1]
+
+    def add_object(self, xyz):
+        """A foreign object: m points (m,3) with descriptors of their own (typically a labelled object cut out of another fitted
+        scene).  Uploaded once; its point j carries id id_base + j, id_base = N for the first foreign object, each next one
+        following the previous (``id_ranges``).  -> k, continuing the label numbering.  It starts with no instance."""
+        x = torch.as_tensor(np.ascontiguousarray(xyz, dtype=np.float32) if not torch.is_tensor(xyz) else xyz)
+        if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] < 1:
+            raise ValueError(f"a foreign object is (m,3) points with m >= 1, got {tuple(x.shape)}")
+        base = self.n + sum(int(f.shape[0]) for f, _ in self._foreign)
+        if base + int(x.shape[0]) > _INT32_MAX:
+            raise ValueError(f"ids {base}..{base + int(x.shape[0])} of the new object leave the int32 index image")
+        self._start_instances()
+        self._foreign.append((x.to(device=self.device, dtype=torch.float32).contiguous(), base))
+        self._rebuild_pool()
+        return self._own_objects() + len(self._foreign)
+
+    def id_ranges(self):
+        """[(id_base, n), ...]: the scene's own ids, then every foreign object's — the tables of the gather, in order."""
+        return [(0, self.n)] + [(base, int(f.shape[0])) for f, base in self._foreign]
+
+    def _instance(self, handle):
+        if self._inst is None or handle not in self._inst:
+            raise ValueError(f"no instance {handle!r}")
+        return self._inst[handle]
+
+    def add_instance(self, k, P=None, visible=True):
+        """One more copy of object k (an own label or a foreign object) drawn with M_0 @ P from the next frame enqueued.  Nothing
+        is rebuilt: the list travels in kernel arguments.  -> a handle for the setters and remove_instance."""
+        self._start_instances()
+        k = int(k)
+        if not 1 <= k <= len(self._ranges):
+            raise ValueError(f"no object {k}: objects 1..{len(self._ranges)}")
+        h = self._next_handle
+        self._next_handle += 1
+        self._inst[h] = {'k': k, 'own': False, 'P': _pose44(P), 'visible': bool(visible)}
+        return h
+
+    def set_instance_pose(self, handle, P):
+        inst = self._instance(handle)
+        if inst['own']:
+            self.set_object_pose(inst['k'], P)
+        else:
+            inst['P'] = _pose44(P)
+
+    def set_instance_visible(self, handle, flag):
+        inst = self._instance(handle)
+        if inst['own']:
+            self.set_object_visible(inst['k'], flag)
+        else:
+            inst['visible'] = bool(flag)
+
+    def remove_instance(self, handle):
+        if self._instance(handle)['own']:
+            raise ValueError(f"instance {handle} is object {self._inst[handle]['k']} itself: hide it (set_object_visible)")
+        del self._inst[handle]
+
+    def _instance_list(self):
+        """[(k, P, visible)] of the frame being enqueued, in handle order."""
+        return [(i['k'], self._poses.get(i['k']), bool(self._visible[i['k'] - 1])) if i['own'] else (i['k'], i['P'], i['visible'])
+                for _, i in sorted(self._inst.items())]
+
+    def instance_matrices(self, total_m):
+        """The (I,16) float32 matrices M_i = object_matrix(M_0, P_i) of the instances, in handle order, for the camera total_m."""
+        return object_matrices(total_m, [P for _, P, _ in self._instance_list()]).reshape(-1, 16)
+
+    def pano_instance_cameras(self, cam):
+        """``pano_object_cameras`` per instance: (I,16) panorama cameras in handle order."""
+        cam = np.asarray(cam, np.float32).reshape(16)
+        R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
+        lst = self._instance_list()
+        out = np.empty((len(lst), 16), np.float32)
+        out[:, :12] = object_matrices(R4, [P for _, P, _ in lst])[:, :3].reshape(-1, 12)
+        out[:, 12:] = cam[12:]
+        return out
+
+    def _instances_struct(self, matrices):
+        """The read_splat_instances of this frame; the host arrays it points to are kept on self until the next frame."""
+        lst = self._instance_list()
+        first = np.array([self._ranges[k - 1][0] for k, _, _ in lst], np.int64)
+        npts = np.array([self._ranges[k - 1][1] for k, _, _ in lst], np.int64)
+        vis = np.array([v for _, _, v in lst], np.uint8)
+        M = np.ascontiguousarray(matrices, np.float32)
+        self._inst_host = (first, npts, vis, M)
+        return _lib.SplatInstances(self._pool_xyz.data_ptr() or None, self._pool_ids.data_ptr() or None,
+                                   int(self._pool_ids.numel()), len(lst), first.ctypes.data, npts.ctypes.data, M.ctypes.data,
+                                   vis.ctypes.data)
+
     def _render_objects(self, M, W, H, levels, idx, dep, ws, stream):
+        if self._inst is not None:
+            inst = self._instances_struct(self.instance_matrices(M))
+            _lib.check(_lib.lib().read_splat_forward_instances(
+                self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
+                self.cells.data_ptr() if self.cells is not None else None, self.n_static, M.ctypes.data_as(C.POINTER(C.c_float)),
+                W, H, levels, C.byref(inst), idx, dep, ws.data_ptr(), ws.numel(), stream), "read_splat_forward_instances")
+            return
         self._obj_m[...] = self.object_matrices(M)
         _lib.check(_lib.lib().read_splat_forward_objects(
             self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
@@ -137,8 +268,8 @@ class PointCloudRasterizer:
         M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m,
                                  dtype=np.float32).reshape(-1, 16)
         B = M.shape[0]
-        if self.labels is not None and B != 1:
-            raise ValueError("a cloud with object labels renders one camera per call")
+        if (self.labels is not None or self._inst is not None) and B != 1:
+            raise ValueError("a cloud with object labels or added objects renders one camera per call")
         sizes = level_sizes(W, H, levels)
         if out is None:
             idx = [torch.empty((B, h, w), dtype=torch.int32, device=self.device) for (w, h) in sizes]
@@ -155,7 +286,7 @@ class PointCloudRasterizer:
                        "read_splat_hint_next_camera")
         idx_p = _lib.ptr_array([t.data_ptr() for t in idx])
         dep_p = _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
-        if self.labels is not None:
+        if self.labels is not None or self._inst is not None:
             self._render_objects(M, W, H, levels, idx_p, dep_p, ws, _lib.stream_ptr())
             return idx, dep
         _lib.check(L.read_splat_forward_cells(self.xyz.data_ptr(),
@@ -194,7 +325,15 @@ class PointCloudRasterizer:
         dep_p = _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
         cam_p = cam.ctypes.data_as(C.POINTER(C.c_float))
         L = _lib.lib()
-        if self.labels is not None:
+        if self._inst is not None:
+            inst = self._instances_struct(self.pano_instance_cameras(cam[0]))
+            labelled = self.labels is not None
+            _lib.check(L.read_splat_forward_pano_instances(
+                (self._static_xyz if labelled else self.xyz).data_ptr() or None,
+                (self._static_ids.data_ptr() or None) if labelled else None, self.n_static if labelled else self.n, cam_p, W, H,
+                levels, C.byref(inst), idx_p, dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+                "read_splat_forward_pano_instances")
+        elif self.labels is not None:
             self._obj_m[...] = self.pano_object_cameras(cam[0])
             _lib.check(L.read_splat_forward_pano(self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
                                                  self.n_static, cam_p, W, H, levels, C.byref(self._objs), idx_p, dep_p,
@@ -224,7 +363,7 @@ class PointCloudRasterizer:
             st = _lib.stream_ptr() if stream is None else stream
             if next_k is not None and cells_p is not None:
                 hint(ws_p, Mp[next_k])
-            if self.labels is not None:                     # scene editing: the objects' matrices of the current poses
+            if self.labels is not None or self._inst is not None:      # scene editing: the matrices of the current poses
                 self._render_objects(Ms[k], W, H, levels, idx_p, dep_p, ws, st)
                 return
             check(fwd(xyz_p, cells_p, n, Mp[k], 1, W, H, levels, idx_p, dep_p, ws_p, ws_n, st), "read_splat_forward_cells")
@@ -241,6 +380,8 @@ class PointCloudRasterizer:
         pano = a panorama camera (camera.pano_camera) is refused: the GL twin is a pinhole."""
         if self.labels is not None:
             raise NotImplementedError("render_gl (GL-twin point options) with object labels")
+        if getattr(self, '_inst', None) is not None:
+            raise NotImplementedError("render_gl (GL-twin point options) with added objects or instances (add_object / add_instance)")
         if pano is not None:
             raise NotImplementedError("render_gl (GL-twin point options) with a panorama camera: render_pano draws 1-px point ids")
         M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m,
@@ -332,6 +473,13 @@ def build_cells_device(xyz, ids=None):
 # ---- scene editing: labels and poses ---------------------------------------------------------------------------------------
 MAX_LABEL = (1 << 16) - 1
 _EYE4 = np.eye(4, dtype=np.float32)
+_INT32_MAX = (1 << 31) - 1
+
+
+def _pose44(P):
+    if P is None:
+        return None
+    return np.array(P.detach().cpu().numpy() if torch.is_tensor(P) else P, dtype=np.float32).reshape(4, 4)
 
 
 def object_matrix(M0, P):
@@ -347,6 +495,22 @@ def object_matrix(M0, P):
     for j in range(1, 4):
         out = out + M0[:, j:j + 1] * P[j:j + 1, :]
     return out.astype(np.float32)
+
+
+def object_matrices(M0, poses):
+    """``object_matrix(M0, P)`` for a list of poses in one go -> (n,4,4) float32, bit for bit: the same float32 products and
+    sums in the same order, element by element; None and the exact identity yield M_0 itself."""
+    M0 = np.asarray(M0, np.float32).reshape(4, 4)
+    out = np.empty((len(poses), 4, 4), np.float32)
+    out[:] = M0
+    moved = [i for i, P in enumerate(poses) if P is not None and not np.array_equal(np.asarray(P, np.float32).reshape(4, 4), _EYE4)]
+    if moved:
+        P = np.stack([np.asarray(poses[i], np.float32).reshape(4, 4) for i in moved])
+        acc = M0[None, :, 0:1] * P[:, 0:1, :]
+        for j in range(1, 4):
+            acc = acc + M0[None, :, j:j + 1] * P[:, j:j + 1, :]
+        out[moved] = acc.astype(np.float32)
+    return out
 
 
 def label_layout(labels):

@@ -187,6 +187,9 @@ class Scene:
         self.object_poses = {}            # label -> 4x4
         self.object_hidden = set()        # labels not drawn
         self.panorama = None              # set_panorama: horizontal field in degrees of the cylindrical camera, None = pinhole
+        self.foreign_objects = []         # scene editing, add: [(xyz (m,3), PointTexture)] of add_foreign_object, in order
+        self.instances = {}               # handle -> {'k', 'P', 'visible'} of add_object_instance, replayed into a rebuilt rasteriser
+        self._next_instance = 0
         self.params = {'mode': (MODE_UV, UV_TYPE_1D), 'draw_points': True, 'flat_color': True, 'point_size': 1,
                        'splat_mode': False}
         if xyz is not None:
@@ -204,6 +207,7 @@ class Scene:
         self.xyz_min, self.xyz_max = self.xyz.min(axis=0), self.xyz.max(axis=0)          # programs.py:334-335
         self.point_discard = self.point_perturb = self.point_sizes = None
         self.object_labels, self.object_poses, self.object_hidden = None, {}, set()
+        self.foreign_objects, self.instances = [], {}
         self._dev = {}
         self._dirty = True
 
@@ -216,8 +220,19 @@ class Scene:
             labels = np.ascontiguousarray(labels).reshape(-1)
             if self.xyz is None or labels.shape[0] != self.xyz.shape[0]:
                 raise ValueError(f"labels has {labels.shape[0]} entries for {0 if self.xyz is None else self.xyz.shape[0]} points")
+        K_old = self._own_objects()
         self.object_labels = labels
         self.object_poses, self.object_hidden = {}, set()
+        # foreign objects follow the labels (k = K + 1 + ordinal), so their instances move with them; an instance of an own label
+        # that no longer exists is dropped
+        K = self._own_objects()
+        kept = {}
+        for h, inst in self.instances.items():
+            if inst['k'] > K_old:
+                kept[h] = dict(inst, k=inst['k'] - K_old + K)
+            elif inst['k'] <= K:
+                kept[h] = inst
+        self.instances = kept
         self._dirty = True
 
     def set_object_pose(self, k, P):
@@ -243,7 +258,95 @@ class Scene:
             raise ValueError("no object labels set (set_object_labels)")
 
     def edited(self):
-        return self.object_labels is not None
+        return self.object_labels is not None or bool(self.foreign_objects) or bool(self.instances)
+
+    # ---- scene editing, third verb: add (PointCloudRasterizer.add_object / add_instance) -----------------------------------
+    def _own_objects(self):
+        return 0 if self.object_labels is None or self.object_labels.size == 0 else int(self.object_labels.max())
+
+    def _live_raster(self):
+        return self._raster if self._raster is not None and not self._dirty else None
+
+    def has_foreign(self):
+        return bool(self.foreign_objects)
+
+    def extract_object(self, k):
+        """-> (xyz (m,3) float32, ids (m,) int64) of object k: the points of label k with their ids in this scene — what
+        ``add_foreign_object`` of ANOTHER scene takes, with the rows ``ids`` of this scene's descriptor table as its texture."""
+        self._require_objects()
+        ids = np.flatnonzero(self.object_labels == int(k))
+        if not 1 <= int(k) <= self._own_objects():
+            raise ValueError(f"no object {k}: labels 1..{self._own_objects()}")
+        return self.xyz[ids].copy(), ids
+
+    def add_foreign_object(self, xyz, texture):
+        """Extension: an object that is not part of this cloud — m points with their own descriptors, a ``PointTexture`` of size m
+        (its own activation).  Its ids follow the scene's: id_base = N for the first, each next one after the previous.  -> k,
+        continuing the label numbering (new labels renumber it to follow them).  It is drawn once per ``add_object_instance``."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+        if self.xyz is None:
+            raise ValueError("scene has no point cloud (set_vertices)")
+        if xyz.ndim != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+            raise ValueError(f"a foreign object is (m,3) points with m >= 1, got {xyz.shape}")
+        if not hasattr(texture, 'texture_') or int(texture.texture_.shape[-1]) != xyz.shape[0]:
+            raise ValueError(f"a foreign object of {xyz.shape[0]} points takes a PointTexture of that size")
+        self.foreign_objects.append((xyz, texture))
+        r = self._live_raster()
+        if r is not None:
+            r.add_object(xyz)
+        return self._own_objects() + len(self.foreign_objects)
+
+    def add_object_instance(self, k, P=None, visible=True):
+        """Extension: one more copy of object k (a label, or a foreign object) placed by P (4x4, None = identity; applied before
+        the model matrix, like set_object_pose).  -> a handle.  Nothing is rebuilt."""
+        k = int(k)
+        if not 1 <= k <= self._own_objects() + len(self.foreign_objects):
+            raise ValueError(f"no object {k}: objects 1..{self._own_objects() + len(self.foreign_objects)}")
+        h = self._next_instance
+        self._next_instance += 1
+        inst = {'k': k, 'P': None if P is None else np.array(P, np.float32).reshape(4, 4), 'visible': bool(visible)}
+        r = self._live_raster()
+        if r is not None:
+            inst['raster'] = r.add_instance(k, inst['P'], inst['visible'])
+        self.instances[h] = inst
+        return h
+
+    def _scene_instance(self, handle):
+        if handle not in self.instances:
+            raise ValueError(f"no instance {handle!r}")
+        return self.instances[handle]
+
+    def set_instance_pose(self, handle, P):
+        inst = self._scene_instance(handle)
+        inst['P'] = None if P is None else np.array(P, np.float32).reshape(4, 4)
+        if self._live_raster() is not None:
+            self._raster.set_instance_pose(inst['raster'], inst['P'])
+
+    def set_instance_visible(self, handle, flag):
+        inst = self._scene_instance(handle)
+        inst['visible'] = bool(flag)
+        if self._live_raster() is not None:
+            self._raster.set_instance_visible(inst['raster'], flag)
+
+    def remove_instance(self, handle):
+        inst = self._scene_instance(handle)
+        if self._live_raster() is not None:
+            self._raster.remove_instance(inst['raster'])
+        del self.instances[handle]
+
+    def gather_tables(self, texture):
+        """[(rows, id_base, activation)] for texture.gather_tables_pyramid: the scene's table, then every foreign object's, each
+        checked against the rasteriser's id ranges."""
+        ranges = self.rasterizer().id_ranges()
+        tables = []
+        for t, ((base, n), tex) in enumerate(zip(ranges, [texture] + [f[1] for f in self.foreign_objects])):
+            if int(tex.texture_.shape[-1]) != n:
+                what = "the scene cloud" if t == 0 else f"foreign object {t}"
+                raise ValueError(f"descriptor table {t} has {int(tex.texture_.shape[-1])} points, {what} {n}")
+            if not tex.texture_.is_cuda:
+                tex.cuda()
+            tables.append((tex.rows(), base, tex.activation))
+        return tables
 
     def set_point_sizes(self, point_sizes):
         """Per-point sizes (READ/gl/programs.py:339-345, scene yaml 'point_sizes'): from now on every token is drawn with the
@@ -349,6 +452,10 @@ class Scene:
                 self._raster.set_object_pose(k, P)
             for k in self.object_hidden:
                 self._raster.set_object_visible(k, False)
+            for xyz, _ in self.foreign_objects:
+                self._raster.add_object(xyz)
+            for _, inst in sorted(self.instances.items()):
+                inst['raster'] = self._raster.add_instance(inst['k'], inst['P'], inst['visible'])
             self._dirty = False
         return self._raster
 
@@ -462,6 +569,10 @@ class StitchedScene:
         """The StitchedRasterizer over the parts' own rasterisers, built lazily like ``Scene.rasterizer()`` and rebuilt only when
         a part rebuilt its own (new vertices, new labels)."""
         from .stitch import StitchedRasterizer
+        for s, sc in enumerate(self.scenes):
+            if getattr(sc, 'foreign_objects', None):
+                raise NotImplementedError(f"foreign objects (add_foreign_object) in part {s} of a StitchedScene: the stitched gather "
+                                          "has one descriptor table per part")
         rs = [sc.rasterizer() for sc in self.scenes]
         if self._raster is None or any(a is not b for a, b in zip(self._raster.parts, rs)):
             self._raster = StitchedRasterizer(rs)
@@ -506,9 +617,13 @@ class MultiscaleRender:
                                       "FrameRenderer.render_pano draw it")
         if getattr(scene, 'stitched', False):
             return self._render_stitched(scene, input_format, fmts, W, H)
+        if getattr(scene, 'foreign_objects', None):
+            raise NotImplementedError("foreign objects (add_foreign_object) on MultiscaleRender (the dict path): its id tokens would "
+                                      "carry ids past the scene's descriptor table; only OGL.infer's fast path and FrameRenderer "
+                                      "draw them")
         pyramid = is_point_id_pyramid(input_format) and W % (1 << (len(fmts) - 1)) == 0 and H % (1 << (len(fmts) - 1)) == 0
         if scene.edited() and scene.augmented():
-            raise NotImplementedError("scene objects (set_object_labels) with GL-twin augmentation (point sizes, discard, drop, "
+            raise NotImplementedError("scene objects (set_object_labels, add_object_instance) with GL-twin augmentation (point sizes, discard, drop, "
                                       "perturb)")
         if scene.edited() and not pyramid:
             bad = next((f for i, f in enumerate(fmts) if not is_point_id_pyramid(','.join(fmts[:i + 1]))), None)

@@ -67,7 +67,8 @@ class StitchedRasterizer:
         self.visible = [True] * len(self.parts)
 
     def part(self, s):
-        """Part s's own rasteriser (set_object_pose / set_object_visible of a part with object labels)."""
+        """Part s's own rasteriser (set_object_pose / set_object_visible / add_instance of a part with object labels; foreign
+        objects, add_object, are refused: the stitched gather has one descriptor table per part)."""
         return self.parts[self._index(s)]
 
     def _index(self, s):
@@ -91,6 +92,10 @@ class StitchedRasterizer:
         """-> one entry per part: (idx_levels, depth_levels) of LOCAL ids from that part's rasteriser, or None for a hidden part
         (not rasterised).  out: None or a list of per-part (idx, depth) buffers to fill.  next_total: the next call's camera, when
         known — every part is told object_matrix(next_total, P_s)."""
+        for s, r in enumerate(self.parts):
+            if r._foreign:
+                raise NotImplementedError(f"foreign objects (add_object) in part {s} of a stitched frame: the stitched gather has one "
+                                          "descriptor table per part")
         Ms = self.part_matrices(total_m)
         Mn = None if next_total is None else self.part_matrices(next_total)
         frames = []

@@ -60,6 +60,32 @@ def gather_pyramid(rows_nc, idx_levels, activation="none", out=None, ss=1):
     return out
 
 
+def gather_tables_pyramid(tables, idx_levels, out=None):
+    """The gather over several descriptor tables (read_gather_forward_tables), one launch for all levels.
+
+    tables: [(rows_nc, id_base, activation), ...], 1..8 of them: table t, an (n_t, C) CUDA tensor, serves the ids
+    [id_base_t, id_base_t + n_t) with its own activation; id_base_0 = 0, bases ascend, ranges do not overlap
+    (``PointCloudRasterizer.id_ranges``).  An id below 0 reads row 0 of table 0; an id in no range the last row of the last table
+    whose base is <= id.  -> NHWC feature maps [(B,h,w,C)...] as ``gather_pyramid``'s."""
+    if not 1 <= len(tables) <= _lib.READ_GATHER_MAX_TABLES:
+        raise ValueError(f"the table gather takes 1..{_lib.READ_GATHER_MAX_TABLES} tables, got {len(tables)}")
+    Cc = int(tables[0][0].shape[1])
+    table = (_lib.GatherTable * len(tables))()
+    for t, (rows, id_base, activation) in enumerate(tables):
+        if not torch.is_tensor(rows) or rows.dim() != 2 or int(rows.shape[1]) != Cc or not rows.is_contiguous():
+            raise ValueError(f"table {t}: descriptor rows must be a contiguous (n, {Cc}) tensor")
+        table[t].rows_nc, table[t].n = rows.data_ptr(), int(rows.shape[0])
+        table[t].id_base, table[t].activation = int(id_base), _ACT[activation]
+    levels = len(idx_levels)
+    if out is None:
+        out = [torch.empty(tuple(i.shape) + (Cc,), dtype=torch.float32, device=tables[0][0].device) for i in idx_levels]
+    counts = (C.c_int64 * levels)(*[int(i.numel()) for i in idx_levels])
+    _lib.check(_lib.lib().read_gather_forward_tables(
+        table, len(tables), Cc, levels, _lib.ptr_array([i.data_ptr() for i in idx_levels]), counts,
+        _lib.ptr_array([o.data_ptr() for o in out]), _lib.stream_ptr()), "read_gather_forward_tables")
+    return out
+
+
 def stitch_gather_pyramid(parts, out=None, want_index=False, want_depth=False, want_part=False, want_feat=True, ss=1):
     """Scene stitching (read_stitch_gather_forward): merge the parts' pyramids and gather from the winner's table, one launch.
 
