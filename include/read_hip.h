@@ -283,6 +283,37 @@ int read_index_to_float(const int32_t *idx, int64_t count, float *out, void *str
 int read_splat_project_points(const float *xyz, int64_t n, const float *M_host, int W, int H, int32_t *pixel, float *depth,
                               void *stream);
 
+/* ---------------------------------------------------------------- object selection (extension) */
+
+/* Per-point object labels made on the device: the front end of scene editing.  The contract is tests/select_model.py, held bit
+ * for bit: fp32, sums left to right, no fused operations, a comparison with a NaN is false.  Every pointer is a device pointer
+ * except M_host; no call allocates or synchronises; n == 0 succeeds without a launch; null pointers are refused when n > 0.
+ *
+ * read_select_boxes: boxes = K x 12 floats, each a row-major 3x4 matrix A that maps cloud coordinates to the unit cube; point i is
+ *   inside box k iff |A[4r] x + A[4r+1] y + A[4r+2] z + A[4r+3]| <= 1 for r = 0, 1, 2 (faces inclusive; a non-finite point is
+ *   outside).  labels_out[i] = label_of[k] of the smallest such k, else labels_in[i] (labels_in NULL: 0).  0 <= K <= 1024; K = 0
+ *   copies labels_in or zero-fills.  labels_in may be labels_out. */
+int read_select_boxes(const float *xyz, int64_t n, const float *boxes, const int32_t *label_of, int K, const int32_t *labels_in,
+                      int32_t *labels_out, void *stream);
+/* read_select_near: near[p] for the W*H pixels of a level-0 frame (idx0, depth0 as read_splat_forward writes them) of this cloud
+ *   under the pinhole matrix M_host: +inf where the pixel is empty (idx0 = 0 and the bits of depth0 = 0) or idx0 is no id of the
+ *   cloud, else the clip w (M[12] x + M[13] y + M[14] z + M[15]) of point idx0[p] — for get_proj_matrix projections the metric
+ *   distance along the camera axis.  W * H < 2^31. */
+int read_select_near(const float *xyz, int64_t n, const float *M_host, int W, int H, const int32_t *idx0, const float *depth0,
+                     float *near, void *stream);
+/* read_select_vote: one view's vote into state (one uint32 per point: cand << 16 | hit << 8 | seen, zero before the first view).
+ *   Point i projects as in read_splat_project_points; outside the image nothing changes; with lim = near[pix] * scale + slack,
+ *   unless clip w <= lim nothing changes (occluded); else seen += 1 and, m = mask[pix] (int32 image, values in [0, 65535], 0 = no
+ *   object): m != 0 and cand = 0 -> cand = m, hit = 1; m = cand -> hit += 1.  The candidate is the label of the FIRST view that
+ *   names one.  scale >= 1 and slack >= 0, both finite.  At most 255 views per state: the counters are 8 bits wide and the caller
+ *   counts the views. */
+int read_select_vote(const float *xyz, int64_t n, const float *M_host, int W, int H, const float *near, const int32_t *mask,
+                     float scale, float slack, uint32_t *state, void *stream);
+/* read_select_finish: labels_out[i] = cand iff cand != 0, hit >= min_hits and hit * den >= num * seen; else labels_in[i]
+ *   (labels_in NULL: 0; it may be labels_out).  1 <= min_hits <= 255, den >= 1, 0 <= num <= den. */
+int read_select_finish(const uint32_t *state, int64_t n, int min_hits, int num, int den, const int32_t *labels_in,
+                       int32_t *labels_out, void *stream);
+
 /* ---------------------------------------------------------------- descriptor gather / scatter */
 
 /* (C, N) channel-major texture  ->  N x C row-major rows (and back, for gradients). */

@@ -130,6 +130,10 @@ SIGNATURES = {
     "read_splat_forward_gl": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "read_index_to_float": (_i, [_vp, _i64, _vp, _vp]),
     "read_splat_project_points": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp]),
+    "read_select_boxes": (_i, [_vp, _i64, _vp, _vp, _i, _vp, _vp, _vp]),
+    "read_select_near": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp, _vp]),
+    "read_select_vote": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _f, _f, _vp, _vp]),
+    "read_select_finish": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "read_texture_to_rows": (_i, [_vp, _i64, _i, _vp, _vp]),
     "read_rows_to_texture": (_i, [_vp, _i64, _i, _vp, _vp]),
     "read_gather_forward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _i, _vp]),

@@ -459,10 +459,59 @@ class Scene:
             self._dirty = False
         return self._raster
 
-    def total_matrix(self):
-        # clip = P * inv(cam->world) * model * x   (programs.py:121-125 with column vectors)
-        view = np.linalg.inv(self.view_matrix.astype(np.float32))
+    def total_matrix(self, view_matrix=None):
+        # clip = P * inv(cam->world) * model * x   (programs.py:121-125 with column vectors); view_matrix: another camera -> world
+        # pose in place of the scene's
+        view = np.linalg.inv((self.view_matrix if view_matrix is None else np.asarray(view_matrix, np.float32)).astype(np.float32))
         return (self.proj_matrix @ view @ self.model_matrix).astype(np.float32)[None]
+
+    # ---- object selection: where the labels come from (read_amd/select.py) --------------------------------
+    def _selected(self, labels):
+        from . import select
+        n = select.counts(labels)
+        self.set_object_labels(labels.cpu().numpy())
+        return n
+
+    def select_boxes(self, boxes, label_of=None, keep=False):
+        """Extension: label the cloud on the device from K <= 1024 oriented boxes (``select.box_matrix``; (K,12) or (K,3,4)) — box k
+        gives label_of[k] (default k + 1), the first box that contains a point wins, faces inclusive — and hand the result to
+        ``set_object_labels``.  keep: start from the current labels instead of 0 (label 0 then carves points back into the static
+        scene).  -> points per label (host int64, index = label)."""
+        from . import select
+        if self.xyz is None:
+            raise ValueError("scene has no point cloud (set_vertices)")
+        return self._selected(select.label_boxes(self.device_array('xyz'), boxes, label_of,
+                                                 self.object_labels if keep else None))
+
+    def select_masks(self, view_matrices, masks, viewport_size, rel=0.05, slack=0.0, min_hits=1, ratio=(1, 2), keep=False):
+        """Extension: label the cloud on the device from 2-D label images (``masks[v]``: (H,W) ints, 0 = no object) seen from the
+        camera -> world poses ``view_matrices[v]`` with the scene's projection and model matrices, viewport_size = (W, H), at most
+        255 views.  Each view renders level 0 of the UNEDITED cloud, keeps the points within near * (1 + rel) + slack of their
+        pixel's winner and votes (``select.MaskVotes``: the candidate is the label of the first view that names one); the result
+        goes to ``set_object_labels``.  keep: points without a label keep their current one.  -> points per label."""
+        from . import select
+        if self.xyz is None:
+            raise ValueError("scene has no point cloud (set_vertices)")
+        if self.panorama is not None:
+            raise NotImplementedError("a panorama camera (set_panorama) with select_masks: the occlusion window compares clip w, "
+                                      "which is no depth under the cylindrical camera; select from pinhole views")
+        if self.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with select_masks: the views are "
+                                      "level-0 frames of the plain cloud")
+        if len(view_matrices) != len(masks):
+            raise ValueError(f"{len(view_matrices)} view matrices for {len(masks)} masks")
+        W, H = int(viewport_size[0]), int(viewport_size[1])
+        votes = select.MaskVotes(self.device_array('xyz'))
+        # the frames must carry the cloud's own ids under one matrix: the live rasteriser while nothing is edited, else a temporary
+        # unlabelled one
+        raster = self.rasterizer() if not self.edited() else PointCloudRasterizer(self.xyz)
+        for view, mask in zip(view_matrices, masks):
+            M = self.total_matrix(view)[0]
+            idx, dep = raster.render(M, W, H, 1)
+            votes.add_view(M, W, H, idx[0], dep[0], mask, rel, slack)
+        labels = votes.labels(min_hits, ratio, self.object_labels if keep else None)
+        del raster
+        return self._selected(labels)
 
 
 class StitchedScene:
@@ -549,6 +598,14 @@ class StitchedScene:
 
     def total_matrix(self):
         return self.scenes[0].total_matrix()
+
+    def select_boxes(self, *args, **kwargs):
+        raise NotImplementedError("select_boxes on a StitchedScene: labels belong to a part; select on the parts "
+                                  "(scenes[s].select_boxes)")
+
+    def select_masks(self, *args, **kwargs):
+        raise NotImplementedError("select_masks on a StitchedScene: labels belong to a part; select on the parts "
+                                  "(scenes[s].select_masks)")
 
     def take_next_total_matrix(self):
         nxt = [sc.take_next_total_matrix() for sc in self.scenes]          # consumed on every part; the frame's is part 0's
