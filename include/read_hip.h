@@ -644,7 +644,11 @@ int read_bn_param_grads(int Cout, const float *sums, const float *mean, const fl
  * read_gate_backward_bn: read_gate_backward through that BatchNorm: two passes (sums of dy and dy * g, then
  * dg = gamma r (dy - mean(dy) - xhat mean(dy xhat))) per group; sums[groups][4][Cout] as read_gate_backward per group, so
  * read_bn_param_grads_groups(Cout, groups, sums, stat, ...) gives db_f, db_m, dgamma, dbeta (accumulating, summed over the
- * groups); abc = groups * 3 * Cout floats of scratch. */
+ * groups); abc = groups * 3 * Cout floats of scratch.
+ * Numerical range of read_gate_backward(_bn) / read_bn_param_grads(_groups) (profiles/train_accuracy_fp64.md): sums row 3 is sum dy * g, NOT centred, so dgamma = (S3 - mean S2) r and
+ * dg = A dy + B + C g cancel when a channel's |mean| is large against its standard deviation: the cost is about half of |mean| / std in units of
+ * u r sum |dy| |g - mean| in dgamma and a quarter of it in units of dg's condition term (u = 2^-24; measured up to 118 and 66 at
+ * |mean| / std = 2^8, 1536 pixels); read_bn_train_forward's y = g scale + (beta - mean scale) carries an absolute error of about u |mean| scale. */
 int read_bn_train_forward(float *g_to_y, int64_t pixels, int C, int W, int block_h, int valid_h, int groups, const float *gamma,
                           const float *beta, float eps, float momentum, float *running_mean, float *running_var, float *stat,
                           float *scale_shift, double *scratch, void *stream);

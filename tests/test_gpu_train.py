@@ -2,7 +2,10 @@
 the functional restatement of the reference's modules): per-layer gradients of every BasicConv flavour, the bilinear x4
 adjoint, the Huber loss, the full UNet backward on a crop, the sparse descriptor RMSprop against torch.optim.RMSprop, and
 one whole optimisation step through TexturePipeline.  Stated tolerance: gradients rtol 1e-4 of the largest gradient entry of
-the tensor (fp32, different summation orders; wgrad sums ~10^4..10^5 products per weight)."""
+the tensor (fp32, different summation orders; wgrad sums ~10^4..10^5 products per weight).
+This file stays the END-TO-END parity test (autograd through GatedConvFn / UNet.backward, the UNet's own geometry).  What each kernel
+costs per element — every C entry point called directly, float64 references, derived bounds, the shapes and value ranges where the
+kernels can go wrong — lives in tests/test_gpu_train_accuracy.py (tests/train_ref64.py, profiles/train_accuracy_fp64.md)."""
 import os
 
 import numpy as np
