@@ -1643,6 +1643,16 @@ int ws_drop_prediction(WsHost &h, hipStream_t stream)
     return READ_OK;
 }
 
+// a frame that is not the cell path's: a prediction pending on this workspace (and its announcement) is not for this call
+int ws_forget_prediction(void *ws, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lock(g_ws_mutex);
+    auto it = g_ws_host.find(ws);
+    if (it == g_ws_host.end()) return READ_OK;
+    it->second.hinted = false;
+    return ws_drop_prediction(it->second, stream);
+}
+
 // ---- plain path ------------------------------------------------------------------------------------------------------
 int project_and_resolve(const float *xyz, int64_t n, const float *M_host, int B, int W, int H, int levels,
                         int32_t *const *idx_levels, float *const *depth_levels, int level_base,
@@ -1723,9 +1733,7 @@ StripInfo make_strips(int W)
 struct ObjectsDraw {
     const float *xyz;                 // device: every object's points, object after object
     const int32_t *ids;               // device: their original ids
-    const int64_t *begin;             // host, count + 1: range k = [begin[k], begin[k + 1]) — the partition of read_splat_objects
-    const int64_t *first, *npts;      // host, count each, used instead of begin when first != NULL: range k = [first[k], first[k] +
-                                      // npts[k]) — the instance list of read_splat_instances (ranges may repeat and overlap)
+    const int64_t *first, *npts;      // host, count each: range k = [first[k], first[k] + npts[k]) (ranges may repeat and overlap)
     const float *M;                   // host, count x 16
     const unsigned char *visible;     // host, count, or NULL (all visible)
     int count;
@@ -1772,7 +1780,7 @@ int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys
         if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
     }
     for (int k = 0; k < od.count; ++k) {
-        const int64_t first = od.first ? od.first[k] : od.begin[k], last = od.first ? first + od.npts[k] : od.begin[k + 1];
+        const int64_t first = od.first[k], last = first + od.npts[k];
         if ((od.visible && !od.visible[k]) || last == first) continue;                      // hidden or empty: not launched
         objects_add(ob, blocks, first, last, od.M + 16 * (size_t)k);
         if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
@@ -2035,15 +2043,7 @@ extern "C" int read_splat_forward(const float *xyz, int64_t n, const float *M_ho
     }
     const WsLayout L = ws_layout(ws, B, W, H);
     hipStream_t s = as_stream(stream);
-    {
-        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
-        auto it = g_ws_host.find(ws);
-        if (it != g_ws_host.end()) {
-            it->second.hinted = false;
-            const int rc = ws_drop_prediction(it->second, s);
-            if (rc != READ_OK) return rc;
-        }
-    }
+    if (const int rc = ws_forget_prediction(ws, s); rc != READ_OK) return rc;
     const int mask = (1 << (levels - 1)) - 1;
     if (((W | H) & mask) == 0) {
         // pyramid identity holds (App. A.4): one pass over the points feeds every level
@@ -2719,6 +2719,26 @@ extern "C" int read_splat_cells_invalidate(const void *cells, int64_t n)
     return READ_OK;
 }
 
+namespace {
+// the device pointers into a cell blob of n points, and the knobs a frame over it reads
+CellCloud cell_cloud(void *cells, int64_t n)
+{
+    const CellOffsets o = cell_offsets(n);
+    CellCloud cc;
+    cc.hdr = (const CellHeader *)cells;
+    cc.pts = (const float4 *)((const char *)cells + o.pts);
+    cc.aabb = (const float *)((const char *)cells + o.aabb);
+    cc.list_a = (int *)((char *)cells + o.list_a);
+    cc.list_b = (CellEntryB *)((char *)cells + o.list_b);
+    cc.sticky = (unsigned char *)cells + o.sticky;
+    cc.nchunks = (int)cells_chunks(n);
+    cc.hdr_n = n;
+    cc.sticky_frames = g_splat_sticky;
+    cc.mark_candidates = g_splat_mark && g_splat_sticky > 0;
+    return cc;
+}
+}  // namespace
+
 extern "C" int read_splat_forward_cells(const float *xyz, void *cells, int64_t n, const float *M_host, int B,
                                         int W, int H, int levels, int32_t *const *idx_levels,
                                         float *const *depth_levels, void *ws, size_t ws_bytes, void *stream)
@@ -2740,18 +2760,7 @@ extern "C" int read_splat_forward_cells(const float *xyz, void *cells, int64_t n
         set_error("read_splat_forward_cells: workspace %zu < %zu bytes", ws_bytes, read_splat_workspace_bytes(B, W, H));
         return READ_ENOMEM;
     }
-    const CellOffsets o = cell_offsets(n);
-    CellCloud cc;
-    cc.hdr = (const CellHeader *)cells;
-    cc.pts = (const float4 *)((const char *)cells + o.pts);
-    cc.aabb = (const float *)((const char *)cells + o.aabb);
-    cc.list_a = (int *)((char *)cells + o.list_a);
-    cc.list_b = (CellEntryB *)((char *)cells + o.list_b);
-    cc.sticky = (unsigned char *)cells + o.sticky;
-    cc.nchunks = (int)cells_chunks(n);
-    cc.hdr_n = n;
-    cc.sticky_frames = g_splat_sticky;
-    cc.mark_candidates = g_splat_mark && g_splat_sticky > 0;
+    const CellCloud cc = cell_cloud(cells, n);
     const WsLayout L = ws_layout(ws, B, W, H);
     // A batch of cameras (the training step's 8 crops, MyRender) = B cell-path frames, one after the other through the same workspace
     // state: each reads only what its chunk lists keep (the plain pass read the whole cloud once per 8 cameras AND projected every
@@ -2764,195 +2773,26 @@ extern "C" int read_splat_forward_cells(const float *xyz, void *cells, int64_t n
     return READ_OK;
 }
 
+// ---- scene editing: the edited frame ------------------------------------------------------------------------------------------
+// One frame behind four symbols: a static part plus a list of point ranges, each with its matrix and visible flag.  The symbols
+// differ in the camera (pinhole / panorama) and in how the caller writes the ranges down (a partition or the list itself).
+// Every check precedes the first launch.
 namespace {
-// The frame of read_splat_forward_objects / read_splat_forward_instances once the arguments are checked: od carries the ranges (a
-// partition or an instance list) and the static part with n0 = 0; the route is chosen here.
-int objects_frame(ObjectsDraw &od, void *cells, int64_t n_static, const float *M_host, int W, int H, int levels,
-                  int32_t *const *idx_levels, float *const *depth_levels, void *ws, hipStream_t s)
+// what a read_splat_objects must be: `count` consecutive ranges that tile its n points
+int check_partition(const char *who, const read_splat_objects *objs)
 {
-    const WsLayout L = ws_layout(ws, 1, W, H);
-    if (cells && g_splat_cells && g_splat_mode == MODE_HIZ && n_static >= (1 << 20) && (W & 15) == 0) {
-        // the cell path for the static part (its blob from read_splat_cells_build_ids), the objects after its pass B
-        const CellOffsets o = cell_offsets(n_static);
-        CellCloud cc;
-        cc.hdr = (const CellHeader *)cells;
-        cc.pts = (const float4 *)((const char *)cells + o.pts);
-        cc.aabb = (const float *)((const char *)cells + o.aabb);
-        cc.list_a = (int *)((char *)cells + o.list_a);
-        cc.list_b = (CellEntryB *)((char *)cells + o.list_b);
-        cc.sticky = (unsigned char *)cells + o.sticky;
-        cc.nchunks = (int)cells_chunks(n_static);
-        cc.hdr_n = n_static;
-        cc.sticky_frames = g_splat_sticky;
-        cc.mark_candidates = g_splat_mark && g_splat_sticky > 0;
-        return cells_frame(cc, M_host, W, H, levels, idx_levels, depth_levels, L, s, 0, &od);
-    }
-    // Otherwise the static part is one more range of splat_objects_kernel with M_0 and its explicit ids (never the plain pass,
-    // whose keys and warm start carry implicit ids), and the resolve keeps no seeds
-    {
-        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
-        auto it = g_ws_host.find(ws);
-        if (it != g_ws_host.end()) {
-            it->second.hinted = false;
-            const int rc = ws_drop_prediction(it->second, s);
-            if (rc != READ_OK) return rc;
-        }
-    }
-    od.n0 = n_static;
-    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s);
-    if (rc != READ_OK) return rc;
-    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
-}
-}  // namespace
-
-// Scene editing: the static part (label 0, its original ids; through its id-mapped cell blob when the cell path serves it) and
-// the objects of `objs`, one camera.  Every check precedes the first launch.
-extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
-                                          const float *M_host, int W, int H, int levels, const read_splat_objects *objs,
-                                          int32_t *const *idx_levels, float *const *depth_levels, void *ws, size_t ws_bytes,
-                                          void *stream)
-{
-    READ_CHECK_ARG(M_host && objs && ws, "read_splat_forward_objects: null pointer (M_host, objs or workspace)");
-    READ_CHECK_ARG(idx_levels || depth_levels, "read_splat_forward_objects: no outputs requested");
-    READ_CHECK_ARG(n_static >= 0 && n_static <= 0xFFFFFFFEll, "read_splat_forward_objects: n_static out of range");
-    READ_CHECK_ARG(n_static == 0 || (xyz_static && ids_static), "read_splat_forward_objects: null pointer (static xyz or ids)");
-    READ_CHECK_ARG(objs->count >= 0 && objs->n >= 0 && objs->n <= 0xFFFFFFFEll,
-                   "read_splat_forward_objects: objs->count / objs->n out of range");
-    READ_CHECK_ARG(objs->count == 0 || (objs->begin && objs->M), "read_splat_forward_objects: null pointer (objs->begin or objs->M)");
-    READ_CHECK_ARG(objs->n == 0 || (objs->xyz && objs->ids), "read_splat_forward_objects: null pointer (objs->xyz or objs->ids)");
-    if (objs->count > 0) {
-        READ_CHECK_ARG(objs->begin[0] == 0, "read_splat_forward_objects: objs->begin[0] = %lld, not 0", (long long)objs->begin[0]);
-        for (int k = 0; k < objs->count; ++k)
-            READ_CHECK_ARG(objs->begin[k] <= objs->begin[k + 1], "read_splat_forward_objects: objs->begin is not monotone at %d", k);
-        READ_CHECK_ARG(objs->begin[objs->count] == objs->n, "read_splat_forward_objects: objs->begin[count] = %lld != objs->n = %lld",
-                       (long long)objs->begin[objs->count], (long long)objs->n);
-    } else
-        READ_CHECK_ARG(objs->n == 0, "read_splat_forward_objects: objs->begin[count] = 0 != objs->n = %lld", (long long)objs->n);
-    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "read_splat_forward_objects: levels must be 1..%d", READ_MAX_LEVELS);
-    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_forward_objects: bad size (%d,%d)", W, H);
-    const int mask = (1 << (levels - 1)) - 1;
-    READ_CHECK_ARG(((W | H) & mask) == 0, "read_splat_forward_objects: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", W, H,
-                   mask + 1);
-    READ_CHECK_ARG((uintptr_t)ws % 256 == 0 && (uintptr_t)cells % 256 == 0,
-                   "read_splat_forward_objects: workspace and cells must be 256-byte aligned");
-    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
-        set_error("read_splat_forward_objects: workspace %zu < %zu bytes", ws_bytes, read_splat_workspace_bytes(1, W, H));
-        return READ_ENOMEM;
-    }
-    ObjectsDraw od;
-    od.xyz = objs->xyz;
-    od.ids = objs->ids;
-    od.begin = objs->begin;
-    od.first = od.npts = nullptr;
-    od.M = objs->M;
-    od.visible = objs->visible;
-    od.count = objs->count;
-    od.xyz0 = xyz_static;
-    od.ids0 = ids_static;
-    od.n0 = 0;
-    od.M0 = M_host;
-    return objects_frame(od, cells, n_static, M_host, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+    READ_CHECK_ARG(objs->count >= 0 && objs->n >= 0 && objs->n <= 0xFFFFFFFEll, "%s: objs->count / objs->n out of range", who);
+    READ_CHECK_ARG(objs->count == 0 || (objs->begin && objs->M), "%s: null pointer (objs->begin or objs->M)", who);
+    READ_CHECK_ARG(objs->n == 0 || (objs->xyz && objs->ids), "%s: null pointer (objs->xyz or objs->ids)", who);
+    if (objs->count > 0) READ_CHECK_ARG(objs->begin[0] == 0, "%s: objs->begin[0] = %lld, not 0", who, (long long)objs->begin[0]);
+    for (int k = 0; k < objs->count; ++k)
+        READ_CHECK_ARG(objs->begin[k] <= objs->begin[k + 1], "%s: objs->begin is not monotone at %d", who, k);
+    const int64_t end = objs->count > 0 ? objs->begin[objs->count] : 0;
+    READ_CHECK_ARG(end == objs->n, "%s: objs->begin[count] = %lld != objs->n = %lld", who, (long long)end, (long long)objs->n);
+    return READ_OK;
 }
 
-namespace {
-// the host-side conditions on a panorama camera: 16 finite floats, kx = 2 / hfov_rad with hfov in (0, 2 pi]
-const char *pano_cam_fault(const float *c)
-{
-    for (int i = 0; i < 16; ++i)
-        if (!std::isfinite(c[i])) return "a camera entry is not finite";
-    if (!(c[12] >= (float)(1.0 / 3.14159265358979323846))) return "kx = 2 / hfov_rad must be >= 1 / pi (a field of at most 360 degrees)";
-    return nullptr;
-}
-
-// The panorama frame once the arguments are checked: one range launch for the static part, the ranges of od, the resolve.
-int pano_frame(const ObjectsDraw &od, bool seeds, int W, int H, int levels, int32_t *const *idx_levels, float *const *depth_levels,
-               void *ws, hipStream_t s)
-{
-    const WsLayout L = ws_layout(ws, 1, W, H);
-    {
-        std::lock_guard<std::mutex> lock(g_ws_mutex);             // a cell-path prediction pending on this workspace is not for this call
-        auto it = g_ws_host.find(ws);
-        if (it != g_ws_host.end()) {
-            it->second.hinted = false;
-            const int rc = ws_drop_prediction(it->second, s);
-            if (rc != READ_OK) return rc;
-        }
-    }
-    if (seeds && g_splat_seeds) {
-        Cam1 cam;
-        memcpy(cam.m, od.M0, sizeof(cam.m));
-        hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, W, H, L.keys,
-                           (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
-        READ_CHECK_LAUNCH();
-    }
-    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s, true);
-    if (rc != READ_OK) return rc;
-    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
-}
-}  // namespace
-
-// Panorama frame: the whole cloud (objs NULL; the previous frame's winners warm-start it) or a labelled cloud's static part plus
-// its objects (no seeds), one range launch each way, then the resolve every frame ends with.  Every check precedes the first launch.
-extern "C" int read_splat_forward_pano(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H, int levels,
-                                       const read_splat_objects *objs, int32_t *const *idx_levels, float *const *depth_levels,
-                                       void *ws, size_t ws_bytes, void *stream)
-{
-    READ_CHECK_ARG(cam_host && ws, "read_splat_forward_pano: null pointer (cam_host or workspace)");
-    READ_CHECK_ARG(idx_levels || depth_levels, "read_splat_forward_pano: no outputs requested");
-    READ_CHECK_ARG(n >= 0 && n <= 0xFFFFFFFEll, "read_splat_forward_pano: n out of range");
-    READ_CHECK_ARG(n == 0 || xyz, "read_splat_forward_pano: null pointer (xyz)");
-    if (objs) {
-        READ_CHECK_ARG(objs->count >= 0 && objs->n >= 0 && objs->n <= 0xFFFFFFFEll,
-                       "read_splat_forward_pano: objs->count / objs->n out of range");
-        READ_CHECK_ARG(objs->count == 0 || (objs->begin && objs->M), "read_splat_forward_pano: null pointer (objs->begin or objs->M)");
-        READ_CHECK_ARG(objs->n == 0 || (objs->xyz && objs->ids), "read_splat_forward_pano: null pointer (objs->xyz or objs->ids)");
-        if (objs->count > 0) {
-            READ_CHECK_ARG(objs->begin[0] == 0, "read_splat_forward_pano: objs->begin[0] = %lld, not 0", (long long)objs->begin[0]);
-            for (int k = 0; k < objs->count; ++k)
-                READ_CHECK_ARG(objs->begin[k] <= objs->begin[k + 1], "read_splat_forward_pano: objs->begin is not monotone at %d", k);
-            READ_CHECK_ARG(objs->begin[objs->count] == objs->n, "read_splat_forward_pano: objs->begin[count] = %lld != objs->n = %lld",
-                           (long long)objs->begin[objs->count], (long long)objs->n);
-        } else
-            READ_CHECK_ARG(objs->n == 0, "read_splat_forward_pano: objs->begin[count] = 0 != objs->n = %lld", (long long)objs->n);
-    }
-    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "read_splat_forward_pano: levels must be 1..%d", READ_MAX_LEVELS);
-    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_forward_pano: bad size (%d,%d)", W, H);
-    const int mask = (1 << (levels - 1)) - 1;
-    READ_CHECK_ARG(((W | H) & mask) == 0, "read_splat_forward_pano: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", W, H,
-                   mask + 1);
-    const char *fault = pano_cam_fault(cam_host);
-    READ_CHECK_ARG(!fault, "read_splat_forward_pano: cam_host: %s", fault);
-    if (objs)
-        for (int k = 0; k < objs->count; ++k) {
-            if ((objs->visible && !objs->visible[k]) || objs->begin[k + 1] == objs->begin[k]) continue;
-            fault = pano_cam_fault(objs->M + 16 * (size_t)k);
-            READ_CHECK_ARG(!fault, "read_splat_forward_pano: objs->M of object %d: %s", k, fault);
-        }
-    READ_CHECK_ARG((uintptr_t)ws % 256 == 0, "read_splat_forward_pano: workspace must be 256-byte aligned");
-    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
-        set_error("read_splat_forward_pano: workspace %zu < %zu bytes", ws_bytes, read_splat_workspace_bytes(1, W, H));
-        return READ_ENOMEM;
-    }
-    ObjectsDraw od;
-    memset(&od, 0, sizeof(od));
-    if (objs) {
-        od.xyz = objs->xyz;
-        od.ids = objs->ids;
-        od.begin = objs->begin;
-        od.M = objs->M;
-        od.visible = objs->visible;
-        od.count = objs->count;
-    }
-    od.xyz0 = xyz;
-    od.ids0 = ids;
-    od.n0 = n;
-    od.M0 = cam_host;
-    // seeds carry implicit ids: only a cloud drawn whole, with its indices as ids, keeps and uses them
-    return pano_frame(od, !objs && !ids && n > 0 && g_splat_mode == MODE_HIZ, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
-}
-
-namespace {
-// what both instance entry points ask of a read_splat_instances before any device work
+// what a read_splat_instances must be: ranges inside its n points (they may repeat and overlap)
 int check_instances(const char *who, const read_splat_instances *inst)
 {
     READ_CHECK_ARG(inst->count >= 0, "%s: inst->count = %d is negative", who, inst->count);
@@ -2969,9 +2809,9 @@ int check_instances(const char *who, const read_splat_instances *inst)
     return READ_OK;
 }
 
-void instances_draw(ObjectsDraw &od, const read_splat_instances *inst)
+ObjectsDraw instances_draw(const read_splat_instances *inst)
 {
-    memset(&od, 0, sizeof(od));
+    ObjectsDraw od{};
     od.xyz = inst->xyz;
     od.ids = inst->ids;
     od.first = inst->first;
@@ -2979,10 +2819,162 @@ void instances_draw(ObjectsDraw &od, const read_splat_instances *inst)
     od.M = inst->M;
     od.visible = inst->visible;
     od.count = inst->count;
+    return od;
+}
+
+// a checked partition (NULL: no ranges) as the list: first / npts live in `ranges` for the length of the call
+ObjectsDraw partition_draw(const read_splat_objects *objs, std::vector<int64_t> &ranges)
+{
+    ObjectsDraw od{};
+    if (!objs) return od;
+    ranges.resize(2 * (size_t)objs->count);
+    int64_t *first = ranges.data(), *npts = first + objs->count;
+    for (int k = 0; k < objs->count; ++k) {
+        first[k] = objs->begin[k];
+        npts[k] = objs->begin[k + 1] - objs->begin[k];
+    }
+    od.xyz = objs->xyz;
+    od.ids = objs->ids;
+    od.first = first;
+    od.npts = npts;
+    od.M = objs->M;
+    od.visible = objs->visible;
+    od.count = objs->count;
+    return od;
+}
+
+// the host-side conditions on a panorama camera: 16 finite floats, kx = 2 / hfov_rad with hfov in (0, 2 pi]
+const char *pano_cam_fault(const float *c)
+{
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite(c[i])) return "a camera entry is not finite";
+    if (!(c[12] >= (float)(1.0 / 3.14159265358979323846))) return "kx = 2 / hfov_rad must be >= 1 / pi (a field of at most 360 degrees)";
+    return nullptr;
+}
+
+// the frame's camera and the camera of every range that will be launched (a partition's or a list's: one of the two, or neither)
+int check_pano_cameras(const char *who, const float *cam_host, const read_splat_objects *objs, const read_splat_instances *inst)
+{
+    const char *fault = pano_cam_fault(cam_host);
+    READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
+    const int count = objs ? objs->count : inst ? inst->count : 0;
+    const float *M = objs ? objs->M : inst ? inst->M : nullptr;
+    const unsigned char *visible = objs ? objs->visible : inst ? inst->visible : nullptr;
+    for (int k = 0; k < count; ++k) {
+        if ((visible && !visible[k]) || (objs ? objs->begin[k + 1] == objs->begin[k] : inst->npts[k] == 0)) continue;
+        fault = pano_cam_fault(M + 16 * (size_t)k);
+        READ_CHECK_ARG(!fault, "%s: %s %d: %s", who, objs ? "objs->M of object" : "inst->M of instance", k, fault);
+    }
+    return READ_OK;
+}
+
+// What the four entry points ask of their arguments, in one order: outputs, the static part, the ranges (objs or inst, whichever
+// the symbol takes; both NULL: none), the pyramid, the cameras of a panorama, alignment, workspace size.  cam_host != NULL: a
+// panorama frame, whose static part may come without ids (its indices are its ids) and has no cell blob.
+int check_frame_args(const char *who, const float *cam_host, const float *xyz, const int32_t *ids, const void *cells, int64_t n,
+                     const read_splat_objects *objs, const read_splat_instances *inst, int W, int H, int levels,
+                     int32_t *const *idx_levels, float *const *depth_levels, const void *ws, size_t ws_bytes)
+{
+    const bool pano = cam_host != nullptr;
+    int rc = READ_OK;
+    READ_CHECK_ARG(idx_levels || depth_levels, "%s: no outputs requested", who);
+    READ_CHECK_ARG(n >= 0 && n <= 0xFFFFFFFEll, "%s: %s out of range", who, pano ? "n" : "n_static");
+    READ_CHECK_ARG(n == 0 || (xyz && (ids || pano)), "%s: null pointer (%s)", who, pano ? "xyz" : "static xyz or ids");
+    if (objs && (rc = check_partition(who, objs)) != READ_OK) return rc;
+    if (inst && (rc = check_instances(who, inst)) != READ_OK) return rc;
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d", who, READ_MAX_LEVELS);
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad size (%d,%d)", who, W, H);
+    const int mask = (1 << (levels - 1)) - 1;
+    READ_CHECK_ARG(((W | H) & mask) == 0, "%s: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", who, W, H, mask + 1);
+    if (pano && (rc = check_pano_cameras(who, cam_host, objs, inst)) != READ_OK) return rc;
+    READ_CHECK_ARG((uintptr_t)ws % 256 == 0 && (uintptr_t)cells % 256 == 0, "%s: workspace %smust be 256-byte aligned", who,
+                   pano ? "" : "and cells ");
+    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
+        set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, read_splat_workspace_bytes(1, W, H));
+        return READ_ENOMEM;
+    }
+    return READ_OK;
+}
+
+// The pinhole frame once the arguments are checked: od carries the ranges; the route of the static part is chosen here.
+int objects_frame(ObjectsDraw od, const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
+                  const float *M_host, int W, int H, int levels, int32_t *const *idx_levels, float *const *depth_levels, void *ws,
+                  hipStream_t s)
+{
+    const WsLayout L = ws_layout(ws, 1, W, H);
+    od.xyz0 = xyz_static;
+    od.ids0 = ids_static;
+    od.M0 = M_host;
+    // the cell path for the static part (its blob from read_splat_cells_build_ids), the objects after its pass B
+    if (cells && g_splat_cells && g_splat_mode == MODE_HIZ && n_static >= (1 << 20) && (W & 15) == 0)
+        return cells_frame(cell_cloud(cells, n_static), M_host, W, H, levels, idx_levels, depth_levels, L, s, 0, &od);
+    // Otherwise the static part is one more range of splat_objects_kernel with M_0 and its explicit ids (never the plain pass,
+    // whose keys and warm start carry implicit ids), and the resolve keeps no seeds
+    if (const int rc = ws_forget_prediction(ws, s); rc != READ_OK) return rc;
+    od.n0 = n_static;
+    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s);
+    if (rc != READ_OK) return rc;
+    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
+}
+
+// The panorama frame once the arguments are checked: one range launch for the static part, the ranges of od, the resolve.
+// Seeds carry implicit ids: only a cloud drawn whole, with its indices as ids, keeps and uses them.
+int pano_frame(ObjectsDraw od, const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, bool whole, int W, int H,
+               int levels, int32_t *const *idx_levels, float *const *depth_levels, void *ws, hipStream_t s)
+{
+    const WsLayout L = ws_layout(ws, 1, W, H);
+    const bool seeds = whole && !ids && n > 0 && g_splat_mode == MODE_HIZ;
+    od.xyz0 = xyz;
+    od.ids0 = ids;
+    od.n0 = n;
+    od.M0 = cam_host;
+    if (const int rc = ws_forget_prediction(ws, s); rc != READ_OK) return rc;
+    if (seeds && g_splat_seeds) {
+        Cam1 cam;
+        memcpy(cam.m, od.M0, sizeof(cam.m));
+        hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, W, H, L.keys,
+                           (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
+        READ_CHECK_LAUNCH();
+    }
+    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s, true);
+    if (rc != READ_OK) return rc;
+    return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
 }
 }  // namespace
 
-// read_splat_forward_objects over an instance list: the same frame (objects_frame), the ranges explicit.
+// Pinhole, a partition: the static part (label 0, its original ids; through its id-mapped cell blob when the cell path serves it)
+// and the objects of `objs`, one camera.
+extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
+                                          const float *M_host, int W, int H, int levels, const read_splat_objects *objs,
+                                          int32_t *const *idx_levels, float *const *depth_levels, void *ws, size_t ws_bytes,
+                                          void *stream)
+{
+    const char *who = "read_splat_forward_objects";
+    READ_CHECK_ARG(M_host && objs && ws, "%s: null pointer (M_host, objs or workspace)", who);
+    const int rc = check_frame_args(who, nullptr, xyz_static, ids_static, cells, n_static, objs, nullptr, W, H, levels, idx_levels,
+                                    depth_levels, ws, ws_bytes);
+    if (rc != READ_OK) return rc;
+    std::vector<int64_t> ranges;
+    return objects_frame(partition_draw(objs, ranges), xyz_static, ids_static, cells, n_static, M_host, W, H, levels, idx_levels,
+                         depth_levels, ws, as_stream(stream));
+}
+
+// Panorama: the whole cloud (objs NULL; the previous frame's winners warm-start it) or a labelled cloud's static part plus its
+// objects as a partition (no seeds).
+extern "C" int read_splat_forward_pano(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H, int levels,
+                                       const read_splat_objects *objs, int32_t *const *idx_levels, float *const *depth_levels,
+                                       void *ws, size_t ws_bytes, void *stream)
+{
+    const char *who = "read_splat_forward_pano";
+    READ_CHECK_ARG(cam_host && ws, "%s: null pointer (cam_host or workspace)", who);
+    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, objs, nullptr, W, H, levels, idx_levels, depth_levels, ws,
+                                    ws_bytes);
+    if (rc != READ_OK) return rc;
+    std::vector<int64_t> ranges;
+    return pano_frame(partition_draw(objs, ranges), xyz, ids, n, cam_host, !objs, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+}
+
+// Pinhole, the list itself.
 extern "C" int read_splat_forward_instances(const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
                                             const float *M_host, int W, int H, int levels, const read_splat_instances *inst,
                                             int32_t *const *idx_levels, float *const *depth_levels, void *ws, size_t ws_bytes,
@@ -2990,63 +2982,24 @@ extern "C" int read_splat_forward_instances(const float *xyz_static, const int32
 {
     const char *who = "read_splat_forward_instances";
     READ_CHECK_ARG(M_host && inst && ws, "%s: null pointer (M_host, inst or workspace)", who);
-    READ_CHECK_ARG(idx_levels || depth_levels, "%s: no outputs requested", who);
-    READ_CHECK_ARG(n_static >= 0 && n_static <= 0xFFFFFFFEll, "%s: n_static out of range", who);
-    READ_CHECK_ARG(n_static == 0 || (xyz_static && ids_static), "%s: null pointer (static xyz or ids)", who);
-    int rc = check_instances(who, inst);
+    const int rc = check_frame_args(who, nullptr, xyz_static, ids_static, cells, n_static, nullptr, inst, W, H, levels, idx_levels,
+                                    depth_levels, ws, ws_bytes);
     if (rc != READ_OK) return rc;
-    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d", who, READ_MAX_LEVELS);
-    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad size (%d,%d)", who, W, H);
-    const int mask = (1 << (levels - 1)) - 1;
-    READ_CHECK_ARG(((W | H) & mask) == 0, "%s: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", who, W, H, mask + 1);
-    READ_CHECK_ARG((uintptr_t)ws % 256 == 0 && (uintptr_t)cells % 256 == 0, "%s: workspace and cells must be 256-byte aligned", who);
-    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
-        set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, read_splat_workspace_bytes(1, W, H));
-        return READ_ENOMEM;
-    }
-    ObjectsDraw od;
-    instances_draw(od, inst);
-    od.xyz0 = xyz_static;
-    od.ids0 = ids_static;
-    od.M0 = M_host;
-    return objects_frame(od, cells, n_static, M_host, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+    return objects_frame(instances_draw(inst), xyz_static, ids_static, cells, n_static, M_host, W, H, levels, idx_levels,
+                         depth_levels, ws, as_stream(stream));
 }
 
-// read_splat_forward_pano over an instance list (no warm start: the ids are explicit).
+// Panorama, the list itself (no warm start: the ids are explicit).
 extern "C" int read_splat_forward_pano_instances(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H,
                                                  int levels, const read_splat_instances *inst, int32_t *const *idx_levels,
                                                  float *const *depth_levels, void *ws, size_t ws_bytes, void *stream)
 {
     const char *who = "read_splat_forward_pano_instances";
     READ_CHECK_ARG(cam_host && inst && ws, "%s: null pointer (cam_host, inst or workspace)", who);
-    READ_CHECK_ARG(idx_levels || depth_levels, "%s: no outputs requested", who);
-    READ_CHECK_ARG(n >= 0 && n <= 0xFFFFFFFEll, "%s: n out of range", who);
-    READ_CHECK_ARG(n == 0 || xyz, "%s: null pointer (xyz)", who);
-    int rc = check_instances(who, inst);
+    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, nullptr, inst, W, H, levels, idx_levels, depth_levels, ws,
+                                    ws_bytes);
     if (rc != READ_OK) return rc;
-    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d", who, READ_MAX_LEVELS);
-    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad size (%d,%d)", who, W, H);
-    const int mask = (1 << (levels - 1)) - 1;
-    READ_CHECK_ARG(((W | H) & mask) == 0, "%s: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", who, W, H, mask + 1);
-    const char *fault = pano_cam_fault(cam_host);
-    READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
-    for (int i = 0; i < inst->count; ++i) {
-        if ((inst->visible && !inst->visible[i]) || inst->npts[i] == 0) continue;
-        fault = pano_cam_fault(inst->M + 16 * (size_t)i);
-        READ_CHECK_ARG(!fault, "%s: inst->M of instance %d: %s", who, i, fault);
-    }
-    READ_CHECK_ARG((uintptr_t)ws % 256 == 0, "%s: workspace must be 256-byte aligned", who);
-    if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
-        set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, read_splat_workspace_bytes(1, W, H));
-        return READ_ENOMEM;
-    }
-    ObjectsDraw od;
-    instances_draw(od, inst);
-    od.xyz0 = xyz;
-    od.ids0 = ids;
-    od.n0 = n;
-    od.M0 = cam_host;
-    return pano_frame(od, false, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+    return pano_frame(instances_draw(inst), xyz, ids, n, cam_host, false, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
 }
 
 extern "C" int read_splat_forward_gl(const float *xyz, int64_t n, const float *M_host, int W, int H,

@@ -83,10 +83,10 @@ class OGL:
                 and not self.renderer.scene.augmented() and hasattr(model.net, 'engine'))
         pano = getattr(self.renderer.scene, 'panorama', None) is not None
         if pano:
-            self._require_pano_fast(input_dict)
+            self._require_fast("a panorama camera (set_panorama)", input_dict)
         foreign = bool(getattr(self.renderer.scene, 'foreign_objects', None))
         if foreign:
-            self._require_foreign_fast(input_dict)
+            self._require_fast("foreign objects (add_foreign_object)", input_dict, ": the table gather has no supersampled form")
         self.last_path = 'fast' if fast else 'dict'
         with torch.set_grad_enabled(False):
             if fast:
@@ -126,39 +126,21 @@ class OGL:
             res['input'] = input_dict
         return res
 
-    def _require_foreign_fast(self, input_dict):
-        """Foreign objects (Scene.add_foreign_object) are drawn on the fast path only: the dict path's single-table lookup would see
-        ids >= N.  What would leave the fast path is refused by name."""
+    def _require_fast(self, what, input_dict, ss_note=''):
+        """``what`` — foreign objects, a panorama camera, scene stitching — is drawn on the fast path only (for foreign objects:
+        the dict path's single-table lookup would see ids >= N).  What would leave the fast path is refused by name."""
         model, scene = self.model, self.renderer.scene
         if input_dict is not None:
-            raise NotImplementedError("a caller-supplied input_dict with foreign objects (add_foreign_object)")
+            raise NotImplementedError(f"a caller-supplied input_dict with {what}")
         if model.temporal_average:
-            raise NotImplementedError("temporal_average with foreign objects (add_foreign_object)")
+            raise NotImplementedError(f"temporal_average with {what}")
         if int(model.ss) > 1:
-            raise NotImplementedError(f"supersampling {int(model.ss)} with foreign objects (add_foreign_object): the table gather "
-                                      "has no supersampled form")
+            raise NotImplementedError(f"supersampling {int(model.ss)} with {what}{ss_note}")
         if scene.augmented():
-            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with foreign objects "
-                                      "(add_foreign_object)")
+            raise NotImplementedError(f"GL-twin augmentation (point sizes, discard, drop, perturb) with {what}")
         if not self._fast_format or not hasattr(model.net, 'engine'):
-            raise NotImplementedError(f"input format {self.input_format!r} with foreign objects (add_foreign_object): only the "
-                                      "point-id pyramid of at least four scales on the HIP UNet is served")
-
-    def _require_pano_fast(self, input_dict):
-        """A panorama camera (Scene.set_panorama) is drawn on the fast path only; what would leave it is refused by name."""
-        model, scene = self.model, self.renderer.scene
-        if input_dict is not None:
-            raise NotImplementedError("a caller-supplied input_dict with a panorama camera (set_panorama)")
-        if model.temporal_average:
-            raise NotImplementedError("temporal_average with a panorama camera (set_panorama)")
-        if int(model.ss) > 1:
-            raise NotImplementedError(f"supersampling {int(model.ss)} with a panorama camera (set_panorama)")
-        if scene.augmented():
-            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with a panorama camera "
-                                      "(set_panorama)")
-        if not self._fast_format or not hasattr(model.net, 'engine'):
-            raise NotImplementedError(f"input format {self.input_format!r} with a panorama camera (set_panorama): only the "
-                                      "point-id pyramid of at least four scales on the HIP UNet is served")
+            raise NotImplementedError(f"input format {self.input_format!r} with {what}: only the point-id pyramid of at least four "
+                                      "scales on the HIP UNet is served")
 
     def _infer_stitched(self, input_dict):
         """A StitchedScene: per-part raster with depth -> one stitched gather -> the engine.  Always the fast path; what it does
@@ -166,17 +148,7 @@ class OGL:
         model, scene = self.model, self.renderer.scene
         if scene.panorama is not None:
             raise NotImplementedError("a panorama camera (set_panorama) on a StitchedScene: stitched frames are pinhole frames")
-        if input_dict is not None:
-            raise NotImplementedError("a caller-supplied input_dict with scene stitching (StitchedScene)")
-        if model.temporal_average:
-            raise NotImplementedError("temporal_average with scene stitching (StitchedScene)")
-        if int(model.ss) > 1:
-            raise NotImplementedError(f"supersampling {int(model.ss)} with scene stitching (StitchedScene)")
-        if scene.augmented():
-            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with scene stitching")
-        if not self._fast_format or not hasattr(model.net, 'engine'):
-            raise NotImplementedError(f"input format {self.input_format!r} with scene stitching (StitchedScene): only the point-id "
-                                      "pyramid of at least four scales on the HIP UNet is served")
+        self._require_fast("scene stitching (StitchedScene)", input_dict)
         textures = [model._modules[str(t)] for t in self.texture_ids]
         raster = scene.rasterizer()
         for s, tex in enumerate(textures):

@@ -32,7 +32,12 @@ class PointCloudRasterizer:
         split once on the device: the static part gets its own id-mapped cell blob, the objects' points are compacted label
         after label.  Index images keep the original ids.  New labels mean a new rasteriser; poses and visibility never do.
         Objects are ADDED with ``add_instance`` (one more copy of a label) and ``add_object`` (points from elsewhere with ids past
-        the cloud's, also on a cloud without labels); from then on frames go through read_splat_forward_instances."""
+        the cloud's, also on a cloud without labels).
+
+        A rasteriser is either plain (``_inst is None``: the whole cloud, read_splat_forward_cells) or a range list (``_inst`` =
+        {handle: instance}: a static part plus ranges of a point pool, each with its pose and visible flag, drawn in handle order
+        by read_splat_forward_instances).  A labelled cloud is a range list from the start — label k is instance k - 1 — and a
+        plain cloud becomes one at its first ``add_object`` / ``add_instance``."""
         self.device = device if device is not None else _lib.require_gpu()
         xyz = torch.as_tensor(np.ascontiguousarray(xyz, dtype=np.float32) if not torch.is_tensor(xyz) else xyz)
         if xyz.dim() != 2 or xyz.shape[1] != 3:
@@ -43,7 +48,7 @@ class PointCloudRasterizer:
         self._ws = None
         self.labels = None
         self._foreign = []            # add_object: (xyz tensor, id_base) of every foreign object, in order
-        self._inst = None             # None until add_object / add_instance: then {handle: instance}, drawn in handle order
+        self._inst = None             # None: a plain cloud; else {handle: instance}, drawn in handle order
         if labels is not None:
             if torch.is_tensor(cells):
                 raise ValueError("a cloud with object labels builds its own cell blob (the static part's)")
@@ -69,19 +74,21 @@ class PointCloudRasterizer:
         self.n_static, self.n_objects = int(static_ids.numel()), len(begin) - 1
         self._static_ids = static_ids
         self._static_xyz = self.xyz[static_ids.long()].contiguous()
-        self._obj_ids = obj_ids
-        self._obj_xyz = self.xyz[obj_ids.long()].contiguous()
-        self._begin = begin
-        self._poses = {}                                               # label -> 4x4 float32 (absent: identity)
-        self._visible = np.ones(self.n_objects, np.uint8)
-        self._obj_m = np.zeros((self.n_objects, 16), np.float32)       # M_k of the frame being enqueued (read during the call)
         self.cells = None
         if cells and self.n_static >= self.CELLS_MIN_POINTS:
             self.cells = build_cells_device(self._static_xyz, ids=self._static_ids)
             _lib.check(_lib.lib().read_splat_cells_invalidate(self.cells.data_ptr(), self.n_static), "read_splat_cells_invalidate")
-        self._objs = _lib.SplatObjects(self._obj_xyz.data_ptr() or None, self._obj_ids.data_ptr() or None, int(obj_ids.numel()),
-                                       self.n_objects, self._begin.ctypes.data, self._obj_m.ctypes.data,
-                                       self._visible.ctypes.data)
+        self._start_ranges(self.xyz[obj_ids.long()].contiguous(), obj_ids, begin)
+
+    def _start_ranges(self, own_xyz, own_ids, begin):
+        """The range list of a cloud whose K = len(begin) - 1 own objects are the compacted points own_xyz / own_ids, object k at
+        [begin[k-1], begin[k]): each starts as one instance, the object itself (handle k - 1, identity pose, visible)."""
+        b = begin.tolist()
+        self._own_xyz, self._own_ids = own_xyz, own_ids
+        self._own_ranges = [(b[k], b[k + 1] - b[k]) for k in range(len(b) - 1)]
+        self._inst = {k: {'k': k + 1, 'own': True, 'P': None, 'visible': True} for k in range(len(b) - 1)}
+        self._next_handle = len(b) - 1
+        self._rebuild_pool()
 
     def _object_index(self, k):
         if self.labels is None:
@@ -94,48 +101,27 @@ class PointCloudRasterizer:
     def set_object_pose(self, k, P):
         """P (4x4, None = identity) maps object k's points, in the cloud's coordinates, to their new place; applies from the next
         frame enqueued (the matrices travel in kernel arguments)."""
-        i = self._object_index(k)
-        if P is None:
-            self._poses.pop(i + 1, None)
-        else:
-            P = np.array(P.detach().cpu().numpy() if torch.is_tensor(P) else P, dtype=np.float32).reshape(4, 4)
-            self._poses[i + 1] = P
+        self._inst[self._object_index(k)]['P'] = _pose44(P)     # object k itself is instance k - 1
 
     def set_object_visible(self, k, flag):
-        self._visible[self._object_index(k)] = 1 if flag else 0
-
-    def object_matrices(self, total_m):
-        """The (K,16) float32 matrices M_k of the objects 1..K for the camera total_m (= M_0)."""
-        M0 = np.asarray(total_m, np.float32).reshape(4, 4)
-        out = np.empty((self.n_objects, 16), np.float32)
-        for i in range(self.n_objects):
-            out[i] = object_matrix(M0, self._poses.get(i + 1)).reshape(16)
-        return out
+        self._inst[self._object_index(k)]['visible'] = bool(flag)
 
     # ---- scene editing, third verb: add ------------------------------------------------------------------------------------
-    def _own_objects(self):
-        return self.n_objects if self.labels is not None else 0
-
-    def _start_instances(self):
-        """The switch from the partition (read_splat_forward_objects) to the instance list: every own label starts with one
-        instance, the object itself, whose pose and flag stay those of set_object_pose / set_object_visible."""
-        if self._inst is not None:
-            return
-        if self.labels is None:       # a cloud without labels: every point is static; the ids the range kernel needs, no xyz copy
+    def _as_range_list(self):
+        """A plain cloud at its first add_object / add_instance: every point is static — the ids the range kernel needs, no copy
+        of the positions — and there is no own object."""
+        if self._inst is None:
             self._static_xyz, self.n_static = self.xyz, self.n
             self._static_ids = torch.arange(self.n, dtype=torch.int32, device=self.device)
-            self._poses = {}
-        self._inst = {k - 1: {'k': k, 'own': True} for k in range(1, self._own_objects() + 1)}
-        self._next_handle = self._own_objects()
-        self._rebuild_pool()
+            self._start_ranges(None, None, np.zeros(1, np.int64))
 
     def _rebuild_pool(self):
-        """The point pool of the instance path: the own objects' compacted points, then the foreign objects'; ids alongside."""
-        K = self._own_objects()
-        xyz = [self._obj_xyz] if K else []
-        ids = [self._obj_ids] if K else []
-        ranges = [(int(self._begin[k]), int(self._begin[k + 1] - self._begin[k])) for k in range(K)]
-        at = int(self._begin[K]) if K else 0
+        """The point pool the ranges index: the own objects' compacted points, then the foreign objects'; ids alongside."""
+        K = len(self._own_ranges)
+        xyz = [self._own_xyz] if K else []
+        ids = [self._own_ids] if K else []
+        ranges = list(self._own_ranges)
+        at = sum(self._own_ranges[-1]) if K else 0
         for fx, base in self._foreign:
             m = int(fx.shape[0])
             xyz.append(fx)
@@ -156,10 +142,10 @@ class PointCloudRasterizer:
         base = self.n + sum(int(f.shape[0]) for f, _ in self._foreign)
         if base + int(x.shape[0]) > _INT32_MAX:
             raise ValueError(f"ids {base}..{base + int(x.shape[0])} of the new object leave the int32 index image")
-        self._start_instances()
+        self._as_range_list()
         self._foreign.append((x.to(device=self.device, dtype=torch.float32).contiguous(), base))
         self._rebuild_pool()
-        return self._own_objects() + len(self._foreign)
+        return len(self._ranges)
 
     def id_ranges(self):
         """[(id_base, n), ...]: the scene's own ids, then every foreign object's — the tables of the gather, in order."""
@@ -173,7 +159,7 @@ class PointCloudRasterizer:
     def add_instance(self, k, P=None, visible=True):
         """One more copy of object k (an own label or a foreign object) drawn with M_0 @ P from the next frame enqueued.  Nothing
         is rebuilt: the list travels in kernel arguments.  -> a handle for the setters and remove_instance."""
-        self._start_instances()
+        self._as_range_list()
         k = int(k)
         if not 1 <= k <= len(self._ranges):
             raise ValueError(f"no object {k}: objects 1..{len(self._ranges)}")
@@ -183,18 +169,10 @@ class PointCloudRasterizer:
         return h
 
     def set_instance_pose(self, handle, P):
-        inst = self._instance(handle)
-        if inst['own']:
-            self.set_object_pose(inst['k'], P)
-        else:
-            inst['P'] = _pose44(P)
+        self._instance(handle)['P'] = _pose44(P)
 
     def set_instance_visible(self, handle, flag):
-        inst = self._instance(handle)
-        if inst['own']:
-            self.set_object_visible(inst['k'], flag)
-        else:
-            inst['visible'] = bool(flag)
+        self._instance(handle)['visible'] = bool(flag)
 
     def remove_instance(self, handle):
         if self._instance(handle)['own']:
@@ -202,16 +180,16 @@ class PointCloudRasterizer:
         del self._inst[handle]
 
     def _instance_list(self):
-        """[(k, P, visible)] of the frame being enqueued, in handle order."""
-        return [(i['k'], self._poses.get(i['k']), bool(self._visible[i['k'] - 1])) if i['own'] else (i['k'], i['P'], i['visible'])
-                for _, i in sorted(self._inst.items())]
+        """[(k, P, visible)] of the frame being enqueued, in handle order (handles only grow, so that is the dict's order)."""
+        return [(i['k'], i['P'], i['visible']) for i in self._inst.values()]
 
     def instance_matrices(self, total_m):
         """The (I,16) float32 matrices M_i = object_matrix(M_0, P_i) of the instances, in handle order, for the camera total_m."""
         return object_matrices(total_m, [P for _, P, _ in self._instance_list()]).reshape(-1, 16)
 
     def pano_instance_cameras(self, cam):
-        """``pano_object_cameras`` per instance: (I,16) panorama cameras in handle order."""
+        """The (I,16) float32 panorama cameras of the instances, in handle order, for the camera ``cam`` (camera.pano_camera): the
+        rows are ``object_matrix(R4, P_i)[:3]``, R4 = cam's three rows with (0, 0, 0, 1) beneath; kx, ky, za, zb repeat."""
         cam = np.asarray(cam, np.float32).reshape(16)
         R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
         lst = self._instance_list()
@@ -221,7 +199,8 @@ class PointCloudRasterizer:
         return out
 
     def _instances_struct(self, matrices):
-        """The read_splat_instances of this frame; the host arrays it points to are kept on self until the next frame."""
+        """The read_splat_instances of this frame: its host arrays (first, npts, visible, M) are built here and kept on self
+        until the next frame."""
         lst = self._instance_list()
         first = np.array([self._ranges[k - 1][0] for k, _, _ in lst], np.int64)
         npts = np.array([self._ranges[k - 1][1] for k, _, _ in lst], np.int64)
@@ -232,19 +211,23 @@ class PointCloudRasterizer:
                                    int(self._pool_ids.numel()), len(lst), first.ctypes.data, npts.ctypes.data, M.ctypes.data,
                                    vis.ctypes.data)
 
-    def _render_objects(self, M, W, H, levels, idx, dep, ws, stream):
-        if self._inst is not None:
-            inst = self._instances_struct(self.instance_matrices(M))
-            _lib.check(_lib.lib().read_splat_forward_instances(
-                self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
-                self.cells.data_ptr() if self.cells is not None else None, self.n_static, M.ctypes.data_as(C.POINTER(C.c_float)),
-                W, H, levels, C.byref(inst), idx, dep, ws.data_ptr(), ws.numel(), stream), "read_splat_forward_instances")
-            return
-        self._obj_m[...] = self.object_matrices(M)
-        _lib.check(_lib.lib().read_splat_forward_objects(
+    def _render_ranges(self, M, W, H, levels, idx, dep, ws, stream):
+        inst = self._instances_struct(self.instance_matrices(M))
+        _lib.check(_lib.lib().read_splat_forward_instances(
             self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
             self.cells.data_ptr() if self.cells is not None else None, self.n_static, M.ctypes.data_as(C.POINTER(C.c_float)),
-            W, H, levels, C.byref(self._objs), idx, dep, ws.data_ptr(), ws.numel(), stream), "read_splat_forward_objects")
+            W, H, levels, C.byref(inst), idx, dep, ws.data_ptr(), ws.numel(), stream), "read_splat_forward_instances")
+
+    def _outputs(self, B, W, H, levels, want_depth, out):
+        """The level lists (idx, depth | None) of a frame — fresh ones, or the caller's ``out`` — and the host arrays of their
+        device pointers."""
+        if out is None:
+            sizes = level_sizes(W, H, levels)
+            idx = [torch.empty((B, h, w), dtype=torch.int32, device=self.device) for (w, h) in sizes]
+            dep = [torch.empty((B, h, w), dtype=torch.float32, device=self.device) for (w, h) in sizes] if want_depth else None
+        else:
+            idx, dep = out
+        return (idx, dep) + _level_ptrs(idx, dep)
 
     def _workspace(self, B, W, H):
         """One persistent workspace per (min(B,8), W, H): key images, hi-z bounds and the previous frame's
@@ -265,29 +248,19 @@ class PointCloudRasterizer:
         next_total: the matrix the NEXT call at this size will use, when the caller knows it (a sweep, a trajectory replay): this
         frame's last launch then also prepares the next frame's chunk lists and depth seeds (read_splat_hint_next_camera —
         4 dependent launches per frame instead of 5; results identical, a wrong announcement only costs two small memsets)."""
-        M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m,
-                                 dtype=np.float32).reshape(-1, 16)
+        M = _host_f32(total_m).reshape(-1, 16)
         B = M.shape[0]
-        if (self.labels is not None or self._inst is not None) and B != 1:
+        if self._inst is not None and B != 1:
             raise ValueError("a cloud with object labels or added objects renders one camera per call")
-        sizes = level_sizes(W, H, levels)
-        if out is None:
-            idx = [torch.empty((B, h, w), dtype=torch.int32, device=self.device) for (w, h) in sizes]
-            dep = [torch.empty((B, h, w), dtype=torch.float32, device=self.device) for (w, h) in sizes] \
-                if want_depth else None
-        else:
-            idx, dep = out
+        idx, dep, idx_p, dep_p = self._outputs(B, W, H, levels, want_depth, out)
         ws = self._workspace(B, W, H)
         L = _lib.lib()
         if next_total is not None and B == 1 and self.cells is not None:
-            Mn = np.ascontiguousarray(next_total.detach().cpu().numpy() if torch.is_tensor(next_total) else next_total,
-                                      dtype=np.float32).reshape(-1, 16)
+            Mn = _host_f32(next_total).reshape(-1, 16)
             _lib.check(L.read_splat_hint_next_camera(ws.data_ptr(), Mn.ctypes.data_as(C.POINTER(C.c_float))),
                        "read_splat_hint_next_camera")
-        idx_p = _lib.ptr_array([t.data_ptr() for t in idx])
-        dep_p = _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
-        if self.labels is not None or self._inst is not None:
-            self._render_objects(M, W, H, levels, idx_p, dep_p, ws, _lib.stream_ptr())
+        if self._inst is not None:
+            self._render_ranges(M, W, H, levels, idx_p, dep_p, ws, _lib.stream_ptr())
             return idx, dep
         _lib.check(L.read_splat_forward_cells(self.xyz.data_ptr(),
                                               self.cells.data_ptr() if self.cells is not None else None, self.n,
@@ -295,49 +268,25 @@ class PointCloudRasterizer:
                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_cells")
         return idx, dep
 
-    def pano_object_cameras(self, cam):
-        """The (K,16) float32 panorama cameras of the objects 1..K for the camera ``cam`` (camera.pano_camera): the rows are
-        ``object_matrix(R4, P_k)[:3]``, R4 = cam's three rows with (0, 0, 0, 1) beneath; kx, ky, za, zb repeat."""
-        cam = np.asarray(cam, np.float32).reshape(16)
-        R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
-        out = np.empty((self.n_objects, 16), np.float32)
-        for i in range(self.n_objects):
-            out[i, :12] = object_matrix(R4, self._poses.get(i + 1))[:3].reshape(12)
-            out[i, 12:] = cam[12:]
-        return out
-
     def render_pano(self, cam, W, H, levels=5, want_depth=True, out=None):
         """One panorama (cylindrical) frame: ``cam`` = the 16 floats of ``camera.pano_camera`` -> (idx_levels, depth_levels) as
         ``render`` gives them.  One camera per call; object labels, poses and visibility are honoured.  The whole cloud is read
         every frame (no chunk culling under a cylinder); without labels the previous frame's winners warm-start the pass.
         Pinhole and panorama frames may alternate on one rasteriser."""
-        cam = np.ascontiguousarray(cam.detach().cpu().numpy() if torch.is_tensor(cam) else cam, dtype=np.float32).reshape(-1, 16)
+        cam = _host_f32(cam).reshape(-1, 16)
         if cam.shape[0] != 1:
             raise ValueError("render_pano renders one camera per call")
-        sizes = level_sizes(W, H, levels)
-        if out is None:
-            idx = [torch.empty((1, h, w), dtype=torch.int32, device=self.device) for (w, h) in sizes]
-            dep = [torch.empty((1, h, w), dtype=torch.float32, device=self.device) for (w, h) in sizes] if want_depth else None
-        else:
-            idx, dep = out
+        idx, dep, idx_p, dep_p = self._outputs(1, W, H, levels, want_depth, out)
         ws = self._workspace(1, W, H)
-        idx_p = _lib.ptr_array([t.data_ptr() for t in idx])
-        dep_p = _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
         cam_p = cam.ctypes.data_as(C.POINTER(C.c_float))
         L = _lib.lib()
         if self._inst is not None:
             inst = self._instances_struct(self.pano_instance_cameras(cam[0]))
-            labelled = self.labels is not None
+            # a cloud without labels is static as a whole: its points' indices are their ids, and none are passed
+            ids = (self._static_ids.data_ptr() or None) if self.labels is not None else None
             _lib.check(L.read_splat_forward_pano_instances(
-                (self._static_xyz if labelled else self.xyz).data_ptr() or None,
-                (self._static_ids.data_ptr() or None) if labelled else None, self.n_static if labelled else self.n, cam_p, W, H,
-                levels, C.byref(inst), idx_p, dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
-                "read_splat_forward_pano_instances")
-        elif self.labels is not None:
-            self._obj_m[...] = self.pano_object_cameras(cam[0])
-            _lib.check(L.read_splat_forward_pano(self._static_xyz.data_ptr() or None, self._static_ids.data_ptr() or None,
-                                                 self.n_static, cam_p, W, H, levels, C.byref(self._objs), idx_p, dep_p,
-                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano")
+                self._static_xyz.data_ptr() or None, ids, self.n_static, cam_p, W, H, levels, C.byref(inst), idx_p, dep_p,
+                ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano_instances")
         else:
             _lib.check(L.read_splat_forward_pano(self.xyz.data_ptr() or None, None, self.n, cam_p, W, H, levels, None, idx_p,
                                                  dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano")
@@ -351,10 +300,9 @@ class PointCloudRasterizer:
         idx, dep = out
         ws = self._workspace(1, W, H)
         L = _lib.lib()
-        Ms = [np.ascontiguousarray(t.detach().cpu().numpy() if torch.is_tensor(t) else t, dtype=np.float32).reshape(16) for t in totals]
+        Ms = [_host_f32(t).reshape(16) for t in totals]
         Mp = [m.ctypes.data_as(C.POINTER(C.c_float)) for m in Ms]
-        idx_p = _lib.ptr_array([t.data_ptr() for t in idx])
-        dep_p = _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
+        idx_p, dep_p = _level_ptrs(idx, dep)
         xyz_p, cells_p, ws_p, ws_n = self.xyz.data_ptr(), self.cells.data_ptr() if self.cells is not None else None, ws.data_ptr(), ws.numel()
         fwd, hint, n, check = L.read_splat_forward_cells, L.read_splat_hint_next_camera, self.n, _lib.check
         keep = (Ms, idx, dep, ws)
@@ -363,8 +311,8 @@ class PointCloudRasterizer:
             st = _lib.stream_ptr() if stream is None else stream
             if next_k is not None and cells_p is not None:
                 hint(ws_p, Mp[next_k])
-            if self.labels is not None or self._inst is not None:      # scene editing: the matrices of the current poses
-                self._render_objects(Ms[k], W, H, levels, idx_p, dep_p, ws, st)
+            if self._inst is not None:                                 # scene editing: the matrices of the current poses
+                self._render_ranges(Ms[k], W, H, levels, idx_p, dep_p, ws, st)
                 return
             check(fwd(xyz_p, cells_p, n, Mp[k], 1, W, H, levels, idx_p, dep_p, ws_p, ws_n, st), "read_splat_forward_cells")
         call.keep = keep
@@ -384,8 +332,7 @@ class PointCloudRasterizer:
             raise NotImplementedError("render_gl (GL-twin point options) with added objects or instances (add_object / add_instance)")
         if pano is not None:
             raise NotImplementedError("render_gl (GL-twin point options) with a panorama camera: render_pano draws 1-px point ids")
-        M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m,
-                                 dtype=np.float32).reshape(-1, 16)
+        M = _host_f32(total_m).reshape(-1, 16)
         if M.shape[0] != 1:
             raise ValueError("render_gl renders one camera per call")
         o = _lib.SplatGlOpts(float(point_size), int(bool(relative)), float(min_point_size), None, 0, 0, None, 0.0, 0, None)
@@ -476,10 +423,20 @@ _EYE4 = np.eye(4, dtype=np.float32)
 _INT32_MAX = (1 << 31) - 1
 
 
+def _level_ptrs(idx, dep):
+    """The host arrays of device pointers a frame call takes for its index and depth levels (depth may be None)."""
+    return _lib.ptr_array([t.data_ptr() for t in idx]), _lib.ptr_array([t.data_ptr() for t in dep]) if dep is not None else None
+
+
+def _host_f32(a):
+    """A host array or a tensor (any device) -> a contiguous float32 numpy array; the input itself where it already is one."""
+    return np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype=np.float32)
+
+
 def _pose44(P):
-    if P is None:
-        return None
-    return np.array(P.detach().cpu().numpy() if torch.is_tensor(P) else P, dtype=np.float32).reshape(4, 4)
+    """A pose as the rasteriser keeps it: None (the identity), or a 4x4 float32 array of its own (a copy: the caller may go on
+    writing to what it passed)."""
+    return None if P is None else np.array(_host_f32(P)).reshape(4, 4)
 
 
 def object_matrix(M0, P):

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from .camera import level_sizes, total_matrix
 from .frame import LEVELS, unet_engine
-from .raster import PointCloudRasterizer, object_matrix
+from .raster import PointCloudRasterizer, _host_f32, object_matrix
 from .texture import _ACT, stitch_gather_pyramid, texture_to_rows
 
 MAX_PARTS = _lib.READ_STITCH_MAX_PARTS
@@ -33,13 +33,11 @@ def id_bases(counts):
 
 
 def _pose(P):
-    if P is None:
-        return None
-    return np.array(P.detach().cpu().numpy() if torch.is_tensor(P) else P, dtype=np.float32).reshape(4, 4)
+    return None if P is None else np.array(_host_f32(P)).reshape(4, 4)
 
 
 def _one_camera(total_m):
-    M = np.ascontiguousarray(total_m.detach().cpu().numpy() if torch.is_tensor(total_m) else total_m, dtype=np.float32)
+    M = _host_f32(total_m)
     if M.size != 16:
         raise ValueError("a stitched frame renders one camera per call")
     return M.reshape(4, 4)

@@ -5,6 +5,7 @@ M_i = object_matrix(M_0, P_i); per pixel the minimum of depth bits << 32 | id wi
 instance and the static part; a foreign object's ids follow the scene's.  The oracle is oracle.raster_multiscale per instance,
 merged on the key.  Every comparison of index and depth images is exact (torch.equal on the ids and on the depth bit patterns, all
 5 levels)."""
+import ctypes as C
 import functools
 
 import numpy as np
@@ -13,10 +14,11 @@ import torch
 
 import oracle
 from oracle import unet_torch
-from read_amd import camera, synthetic
+from read_amd import _lib, camera, synthetic
+from read_amd.camera import level_sizes
 from read_amd.frame import FrameRenderer
 from read_amd.ogl import OGL
-from read_amd.raster import PointCloudRasterizer
+from read_amd.raster import PointCloudRasterizer, build_cells_device, label_layout, object_matrix
 from read_amd.render import Scene
 from read_amd.stitch import StitchedRasterizer
 from read_amd.texture import PointTexture, gather_pyramid, gather_tables_pyramid
@@ -116,16 +118,60 @@ def _instance_list(r):
 
 
 # ---- 1. the partition listed once equals read_splat_forward_objects, both routes --------------------------------------------------
+class _ForwardObjects:
+    """read_splat_forward_objects called directly, as a C caller would: the partition of ``label_layout`` in a hand-built
+    read_splat_objects, a cell blob of the static part when it is large enough, a workspace of its own."""
+
+    def __init__(self, xyz, labels, W, H):
+        L, dev = _lib.lib(), torch.device("cuda")
+        pts = torch.from_numpy(xyz).to(dev)
+        self.static_ids, self.obj_ids, self.begin = label_layout(torch.from_numpy(labels).to(dev))
+        self.static_xyz = pts[self.static_ids.long()].contiguous()
+        self.obj_xyz = pts[self.obj_ids.long()].contiguous()
+        self.n_static, self.K = int(self.static_ids.numel()), len(self.begin) - 1
+        self.cells = None
+        if self.n_static >= (1 << 20):
+            self.cells = build_cells_device(self.static_xyz, ids=self.static_ids)
+            _lib.check(L.read_splat_cells_invalidate(self.cells.data_ptr(), self.n_static), "read_splat_cells_invalidate")
+        self.W, self.H = W, H
+        self.ws = torch.empty(L.read_splat_workspace_bytes(1, W, H), dtype=torch.uint8, device=dev)
+        _lib.check(L.read_splat_workspace_init(self.ws.data_ptr(), self.ws.numel(), _lib.stream_ptr()), "read_splat_workspace_init")
+        self.M = np.zeros((self.K, 16), np.float32)
+        self.visible = np.ones(self.K, np.uint8)
+        self.objs = _lib.SplatObjects(self.obj_xyz.data_ptr(), self.obj_ids.data_ptr(), int(self.obj_ids.numel()), self.K,
+                                      self.begin.ctypes.data, self.M.ctypes.data, self.visible.ctypes.data)
+
+    def render(self, M0, poses, hidden, next_total):
+        L = _lib.lib()
+        M0 = np.ascontiguousarray(M0, np.float32).reshape(4, 4)
+        for k in range(1, self.K + 1):
+            self.M[k - 1] = object_matrix(M0, poses.get(k)).reshape(16)
+            self.visible[k - 1] = 0 if k in hidden else 1
+        sizes = level_sizes(self.W, self.H, LEVELS)
+        idx = [torch.empty((1, h, w), dtype=torch.int32, device="cuda") for (w, h) in sizes]
+        dep = [torch.empty((1, h, w), dtype=torch.float32, device="cuda") for (w, h) in sizes]
+        if self.cells is not None:                               # the announcement PointCloudRasterizer.render makes
+            Mn = np.ascontiguousarray(next_total, np.float32).reshape(16)
+            _lib.check(L.read_splat_hint_next_camera(self.ws.data_ptr(), Mn.ctypes.data_as(C.POINTER(C.c_float))),
+                       "read_splat_hint_next_camera")
+        _lib.check(L.read_splat_forward_objects(
+            self.static_xyz.data_ptr(), self.static_ids.data_ptr(), self.cells.data_ptr() if self.cells is not None else None,
+            self.n_static, M0.ctypes.data_as(C.POINTER(C.c_float)), self.W, self.H, LEVELS, C.byref(self.objs),
+            _lib.ptr_array([t.data_ptr() for t in idx]), _lib.ptr_array([t.data_ptr() for t in dep]), self.ws.data_ptr(),
+            self.ws.numel(), _lib.stream_ptr()), "read_splat_forward_objects")
+        return idx, dep
+
+
 @pytest.mark.parametrize("cloud", ["street", "cloud200k"])
 def test_partition_listed_once_equals_forward_objects(hip, cloud):
     xyz, labels = _cloud(cloud)
     proj = synthetic.make_proj(W, H)
-    old = PointCloudRasterizer(xyz, labels=labels)
-    new = PointCloudRasterizer(xyz, labels=labels)
-    new.remove_instance(new.add_instance(1))                  # switches to the instance list; what is left is every label once
-    assert new._inst is not None and old._inst is None and len(new._inst) == 6
+    old = _ForwardObjects(xyz, labels, W, H)
+    new = PointCloudRasterizer(xyz, labels=labels)              # a range list from the constructor on: every label once
+    assert new._inst is not None and len(new._inst) == 6
     street = cloud == "street"
     assert (new.cells is not None) == street and (new.n_static >= (1 << 20)) == street
+    assert (old.cells is not None) == street and old.n_static == new.n_static and old.K == 6
     views = [synthetic.sweep_pose(10 + 2 * f) for f in range(4)]
     totals = [camera.total_matrix(proj, v)[0] for v in views]
     for f in range(3):
@@ -133,12 +179,12 @@ def test_partition_listed_once_equals_forward_objects(hip, cloud):
         poses = {1: translation(camera_space_target(views[f], proj, -0.5 + 0.4 * f, 6.0) - c[1]), 2: about(c[2], rot_z(0.3 * f), (0.1, 0, 0)),
                  3: translation(camera_space_target(views[f], proj, 0.0, 10.0, behind=True) - c[3]), 4: None,
                  5: translation(camera_space_target(views[f], proj, -1.0, 20.0) - c[5]), 6: about(c[6], rot_z(-0.2), (0, 0.05 * f, 0))}
-        for r in (old, new):
-            for k, P in poses.items():
-                r.set_object_pose(k, P)
-            r.set_object_visible(4, f != 1)
-            r.set_object_visible(6, f == 1)
-        a = copy(old.render(totals[f], W, H, LEVELS, next_total=totals[f + 1]))      # announced: consecutive frames still match
+        for k, P in poses.items():
+            new.set_object_pose(k, P)
+        new.set_object_visible(4, f != 1)
+        new.set_object_visible(6, f == 1)
+        hidden = ({4} if f == 1 else set()) | (set() if f == 1 else {6})
+        a = old.render(totals[f], poses, hidden, totals[f + 1])                       # announced: consecutive frames still match
         b = new.render(totals[f], W, H, LEVELS, next_total=totals[f + 1])
         assert_same(b, a, f"{cloud} frame {f}")
         if f == 0:

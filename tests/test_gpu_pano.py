@@ -12,7 +12,7 @@ from oracle import unet_torch
 from read_amd import _lib, camera, synthetic
 from read_amd.frame import FrameRenderer
 from read_amd.ogl import OGL
-from read_amd.raster import PointCloudRasterizer
+from read_amd.raster import PointCloudRasterizer, label_layout, object_matrix
 from read_amd.render import MultiscaleRender, Scene, StitchedScene
 from read_amd.unet import weight_spec
 from tests import pano_cases as pc
@@ -180,6 +180,47 @@ def test_labels_moved_hidden_and_empty(hip):
     r.set_object_pose(2, None)
     plain = PointCloudRasterizer(xyz).render_pano(cam, W, H, LEVELS)
     assert_frame(*r.render_pano(cam, W, H, LEVELS), [t.cpu().numpy() for t in plain[0]], [t.cpu().numpy() for t in plain[1]], "identity")
+
+
+def test_forward_pano_partition_equals_the_rasteriser(hip):
+    """read_splat_forward_pano with a hand-built read_splat_objects (the partition of ``label_layout``), as a C caller would
+    pass it, against the rasteriser's own frame of the same labelled cloud (a range list through
+    read_splat_forward_pano_instances) and against the model: one object moved, one hidden."""
+    W, H, n = 256, 64, 200_000
+    xyz = pc.ring_cloud(n, 15, dup=1000)
+    labels = pc.labels_for(n, 5, n_objects=3, share=0.1)
+    cam = camera.pano_camera(pc.proj(W, H), pc.pose(yaw=-15.0, pitch=4.0, roll=-7.0, t=(0.2, 0.1, -0.3)), 360.0)
+    poses = {2: (pc.translation((2.0, -0.5, 1.5)) @ pc.rot(1, -25.0)).astype(np.float32)}
+    r = PointCloudRasterizer(xyz, labels=labels)
+    assert r._inst is not None and len(r._inst) == 3
+    r.set_object_pose(2, poses[2])
+    r.set_object_visible(3, False)
+    got = r.render_pano(cam, W, H, LEVELS)
+    # the C caller's side: static part, compacted objects, begin, one panorama camera per object, flags; a workspace of its own
+    dev = torch.device("cuda")
+    pts = torch.from_numpy(xyz).to(dev)
+    static_ids, obj_ids, begin = label_layout(torch.from_numpy(labels).to(dev))
+    static_xyz, obj_xyz = pts[static_ids.long()].contiguous(), pts[obj_ids.long()].contiguous()
+    R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
+    Ms = np.empty((3, 16), np.float32)
+    for k in range(1, 4):
+        Ms[k - 1, :12] = object_matrix(R4, poses.get(k))[:3].reshape(12)
+        Ms[k - 1, 12:] = cam[12:]
+    visible = np.array([1, 1, 0], np.uint8)
+    objs = _lib.SplatObjects(obj_xyz.data_ptr(), obj_ids.data_ptr(), int(obj_ids.numel()), 3, begin.ctypes.data, Ms.ctypes.data,
+                             visible.ctypes.data)
+    ws = torch.empty(hip.read_splat_workspace_bytes(1, W, H), dtype=torch.uint8, device=dev)
+    _lib.check(hip.read_splat_workspace_init(ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_workspace_init")
+    idx = [torch.empty_like(t) for t in got[0]]
+    dep = [torch.empty_like(t) for t in got[1]]
+    _lib.check(hip.read_splat_forward_pano(
+        static_xyz.data_ptr(), static_ids.data_ptr(), int(static_ids.numel()), cam.ctypes.data_as(C.POINTER(C.c_float)), W, H, LEVELS,
+        C.byref(objs), _lib.ptr_array([t.data_ptr() for t in idx]), _lib.ptr_array([t.data_ptr() for t in dep]), ws.data_ptr(),
+        ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano")
+    assert_frame(idx, dep, [t.cpu().numpy() for t in got[0]], [t.cpu().numpy() for t in got[1]], "partition vs range list")
+    keys = pm.labelled_keys(xyz, labels, cam, poses, {3}, W, H)
+    assert_frame(idx, dep, *pm.pyramid_of(keys, W, H, LEVELS), "model")
+    assert not np.array_equal(keys, pm.labelled_keys(xyz, labels, cam, {}, set(), W, H))          # the move and the hiding show
 
 
 # ---- FrameRenderer ---------------------------------------------------------------------------------------------------------------

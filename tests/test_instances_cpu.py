@@ -310,6 +310,50 @@ def test_object_matrices_equal_object_matrix_bit_for_bit():
     assert object_matrices(M0, []).shape == (0, 4, 4)
 
 
+def test_labelled_rasteriser_lists_its_partition():
+    """The partition equals the list at the host level: a labelled rasteriser's read_splat_instances holds range k of
+    ``label_layout`` with M_k = object_matrix(M_0, P_k) and the flag set for label k + 1 — a label without points and an identity
+    pose included.  Host arrays only: the state is what the constructor leaves, on CPU tensors."""
+    import torch
+    from read_amd.raster import PointCloudRasterizer, label_layout, object_matrix
+    rng = np.random.default_rng(8)
+    labels = rng.integers(0, 6, 400).astype(np.int32)
+    labels[labels == 3] = 0                                                     # label 3 has no points
+    static_ids, obj_ids, begin = label_layout(labels)
+    K = len(begin) - 1
+    assert K == 5 and begin[3] == begin[2]
+    r = PointCloudRasterizer.__new__(PointCloudRasterizer)
+    r.device, r.labels, r.n_objects, r._foreign = torch.device("cpu"), torch.from_numpy(labels), K, []
+    r._start_ranges(torch.from_numpy(rng.standard_normal((obj_ids.numel(), 3)).astype(np.float32)), obj_ids, begin)
+    assert sorted(r._inst) == list(range(K))
+    poses = {1: _translation((0.4, 0.1, -0.2)), 2: np.eye(4), 3: rng.standard_normal((4, 4)), 4: None,
+             5: torch.from_numpy(rng.standard_normal((4, 4)).astype(np.float32))}
+    for k, P in poses.items():
+        r.set_object_pose(k, P)
+    r.set_object_visible(2, False)
+    r.set_object_visible(5, False)
+    r.set_object_visible(5, True)
+    M0 = rng.standard_normal((4, 4)).astype(np.float32)
+    s = r._instances_struct(r.instance_matrices(M0))
+    assert s.count == K and s.n == obj_ids.numel() and s.xyz == r._pool_xyz.data_ptr() and s.ids == r._pool_ids.data_ptr()
+    host = lambda p, ct, shape: np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), shape)
+    assert np.array_equal(host(s.first, C.c_int64, (K,)), begin[:-1])
+    assert np.array_equal(host(s.npts, C.c_int64, (K,)), begin[1:] - begin[:-1])
+    assert host(s.visible, C.c_uint8, (K,)).tolist() == [1, 0, 1, 1, 1]
+    M = host(s.M, C.c_float, (K, 4, 4))
+    for k in range(1, K + 1):
+        Pk = poses[k].numpy() if torch.is_tensor(poses[k]) else poses[k]
+        assert np.array_equal(M[k - 1].view(np.uint32), object_matrix(M0, Pk).view(np.uint32)), k
+    assert np.array_equal(M[1].view(np.uint32), M0.view(np.uint32)) and np.array_equal(M[3].view(np.uint32), M0.view(np.uint32))
+    assert torch.equal(r._pool_ids, obj_ids)
+    # the setters of the own instances are the object's setters: one pose and one flag per object
+    r.set_instance_pose(0, None)
+    r.set_instance_visible(1, True)
+    assert [(k, P is None, v) for k, P, v in r._instance_list()][:2] == [(1, True, True), (2, False, True)]
+    with pytest.raises(ValueError, match="itself"):
+        r.remove_instance(2)
+
+
 # ---- the table gather model ------------------------------------------------------------------------------------------------------
 def test_table_gather_model():
     rng = np.random.default_rng(3)
