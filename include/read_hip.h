@@ -57,9 +57,8 @@ int read_device_arch(char *name, int len);
  *   "splat_mode"      plain path: 7 (default) warm start + LDS hierarchical-Z, 1 = agent-scope atomics + early-z only
  *   "splat_cells"     0: ignore the cell-ordered copy (plain path everywhere)
  *   "splat_seeds"     0: no warm start from the previous frame
- *   "splat_near"      striped path: expected points per pixel in front of the pass-A split distance (default 12)
+ *   "splat_near"      cell path: expected points per pixel in front of the pass-A split distance (default 12)
  *   "splat_cells_sub" cell path: every n-th chunk joins pass A (default 0 = only on a workspace's first frame, every 32nd; rounds 2-4: 32)
- *   "splat_items"     striped path: work items per 1024-point chunk (1, 2, 4)
  *   "splat_subset"    plain path: bootstrap pass over every n-th chunk (default 8)
  *   "splat_stats"     debug counters in the workspace header
  *   "conv_wino"       largest Cin that takes the Winograd F(2x2,3x3) kernel (0 = direct implicit-GEMM kernels everywhere)
@@ -69,7 +68,6 @@ int read_device_arch(char *name, int len);
  *                     (default 1) classifications, wherever it lies — on surface-like scenes the chunks beyond the near split that hold
  *                     front points then run banded and binned in pass A instead of surviving pass B's bound test every frame
  *                     (street scene 81.7 -> 70.9 us per frame; volumetric slab unchanged); 0: only pass B's survivors are promoted
- *   "splat_compact"   1 (default): pass A compacts the candidates of a 256-point round into dense lanes before binning them; 0: rounds 2-4
  *   "splat_cells_batch" 1 (default): a batch of cameras runs as B cell-path frames; 0: the plain pass over the whole cloud
  *   "splat_prof"      1: HIP events around every launch of a cell-path frame (read_splat_profile_last); 0 (default)
  *   "splat_ahead"     1 (default): with an announced next camera (read_splat_hint_next_camera) a cell-path frame's resolve launch

@@ -20,38 +20,34 @@ int conv_get(const char *key, int *value);
 const char *conv_key(int i, bool debug_only);
 void conv_set_trace(void *buf, size_t bytes);
 
-// splat.hip
-int splat_set_mode(int m);
-void splat_set_subset(int v);
-void splat_set_stats(int v);
-void splat_set_near(int v);
-void splat_set_cells(int v);
-void splat_set_seeds(int v);
-void splat_set_cells_sub(int v);
-void splat_set_items(int v);
-void splat_set_strips(int v);
-void splat_set_wgs(int v);
-void splat_set_zl2(int v);
-void splat_set_lds(int v);
-void splat_set_bins(int v);
-void splat_set_ahead(int v);
-void splat_set_prof(int v);
-void splat_set_mark(int v);
-void splat_set_cells_batch(int v);
-void splat_set_compact(int v);
-void splat_set_wgs_b(int v);
-void splat_set_sticky(int v);
-void splat_set_kslot(int v);
+// One row of a module's table of tuning keys; the order of the rows is the order read_tuning_key enumerates them in.
+enum TuneNorm {
+    TN_RAW,
+    TN_FLAG,      // != 0
+    TN_CLAMP,     // into [lo, hi]
+    TN_POW2,      // into [lo, hi] (powers of two), then down to a power of two
+    TN_EITHER     // lo or hi; anything else is refused
+};
+struct TuneRow {
+    const char *key;
+    int *value;
+    TuneNorm norm;
+    int lo, hi;
+};
+// api_common.cpp: 1 = key known and the normalised value stored, 0 = no such key in the table, READ_EINVAL = value refused
+int tune_set(const TuneRow *rows, int n, const char *key, int value);
+int tune_get(const TuneRow *rows, int n, const char *key, int *value);
+const char *tune_key(const TuneRow *rows, int n, int i);       // NULL past the end
+
+// splat.hip, unet.cpp, train.hip: the "splat_*" / "unet_*" / "wgrad_wino" keys, as conv_set / conv_get / conv_key above
+int splat_set(const char *key, int value);
 int splat_get(const char *key, int *value);
-
-// unet.cpp
-void unet_set_streams(int v);
-void unet_set_aff_split(int v);
-void unet_set_up_fold(int v);
+const char *splat_key(int i);
+int unet_set(const char *key, int value);
 int unet_get(const char *key, int *value);
-
-// train.hip
-void train_set_wgrad_wino(int v);
+const char *unet_key(int i);
+int train_set(const char *key, int value);
 int train_get(const char *key, int *value);
+const char *train_key(int i);
 
 }  // namespace readhip

@@ -77,19 +77,6 @@ __device__ __forceinline__ void fold_key_agent(unsigned long long *k, unsigned l
 {
     __hip_atomic_fetch_min(k, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// Where pixel p's key lives in the key image of the striped path.  Mode 0: slot p.  Mode 1: slot 8 p (one key per 64 bytes).
-// Mode 2: slot (p * odd) mod 2^k, a bijection that scatters neighbouring pixels over the whole image — the memory-side atomic
-// units serialise atomics that hit the same line / channel, and the candidates of a round are Morton neighbours, i.e.
-// pixels of a few adjacent 128-byte lines (read_tuning_set("splat_kslot", m); measured in profiles/README.md).
-struct KeySlots {
-    int mode;
-    unsigned mask;           // 2^k - 1 >= W*H - 1 (mode 2)
-};
-__device__ __forceinline__ unsigned key_slot(const KeySlots ks, unsigned pix)
-{
-    return ks.mode == 0 ? pix : (ks.mode == 1 ? pix << 3 : (pix * 0x9E3779B1u) & ks.mask);
-}
-
 // Far bounds are stored as 16 bits: the upper half (bfloat16, truncated = rounded DOWN) of e = fl(1 - d_max).  Depth
 // is d = 1 - O(znear / z), so e keeps 8 mantissa bits of the DISTANCE (0.4 %) where a half-precision d would resolve
 // only ~5 m at 30 m.  Reject iff fl(1 - d) < bound: rounding is monotonic, so fl(1 - d) < fl(1 - d_max) implies
@@ -548,9 +535,9 @@ __global__ __launch_bounds__(256) void cells_seed_classify_kernel(CellCloud cc, 
     seed_block(cc, cam.m, W, H, zimg, pos_img, (int)blockIdx.x);
 }
 
-// `rounds` x 256 consecutive points of one chunk for one wave and one strip: zimg early-z, then atomic min on the key +
-// plain stores of the new bound and of the point's position (next frame's seed).  The records of round r+1 are loaded
-// before round r is processed (one HBM round trip per chunk instead of one per round on the critical path).
+// 256 consecutive points of one chunk (a quarter of it) for one wave and one strip: zimg early-z, then atomic min on the key +
+// plain stores of the new bound and of the point's position (next frame's seed).  The records of the wave's NEXT call are
+// loaded before this call's are processed (q, next_first).
 //
 // LDS (template flag): the candidates of a round are first folded into a 256-slot hash table in LDS that belongs to the
 // wave (slot = hash(pixel); ds_cmpst claims it, ds_min_u64 keeps the smallest key), and only the table's survivors go to
@@ -580,7 +567,6 @@ struct BinInfo {
     unsigned *count;           // per (tile, sub-bin), minus one
     int cap, tiles_x;
     float inv_w;               // 1 / W (exact row of a pixel index: (pix + 0.5) * inv_w, W * H <= 2^20)
-    int compact;               // splat_compact: a round's candidates are compacted into dense lanes before they are binned
 };
 
 // NC candidates per lane (valid bit k of `valid`): records into the bins; pos[k] = position of the point (next frame's seed)
@@ -671,174 +657,168 @@ __device__ __forceinline__ void emit_binned(const BinInfo &bi, const int (&pix)[
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");          // the lists are reused by the next batch
 }
 
-template <bool STATS, bool ZL2, bool LDS, bool BIN>
-__device__ __forceinline__ void strip_points(const CellCloud &cc, const float *M, int W, int H, int xlo, int xhi,
-                                             unsigned long long *keys, unsigned *zimg, int *next, int first, int rounds,
+template <bool STATS, bool LDS, bool BIN>
+__device__ __forceinline__ void strip_points(const CellCloud &cc, const float *M, int W, int H,
+                                             unsigned long long *keys, unsigned *zimg, int *next, int first,
                                              int lane, unsigned &st_in, unsigned &st_atomics, unsigned *tag,
-                                             unsigned long long *hkey, int *hpos, const KeySlots ks, bool use_lds,
+                                             unsigned long long *hkey, int *hpos, bool use_lds,
                                              const BinInfo &bi, unsigned *wl_tile, unsigned *wl_cnt, int sub,
-                                             float4 (&q)[4], int next_first, uint4 *cq = nullptr)
+                                             float4 (&q)[4], int next_first, uint4 *cq)
 {
-    // q holds the first 256 records of this call (loaded by the caller: point_records); on return it holds the first 256 of
-    // the caller's NEXT call (next_first, -1 = none) — their loads run under this call's bound reads and slot reservations
+    // q holds the 256 records of this call (loaded by the caller); on return it holds the 256 of the caller's NEXT call
+    // (next_first, -1 = none) — their loads run under this call's bound reads and slot reservations
     float4 qn[4];
-    for (int r = 0; r < rounds; ++r) {
-        // 256 points: lane l takes records base + l + 64 k (each load instruction = 1 KiB contiguous)
-        const int base = first + r * 256 + lane;
-        if (r + 1 < rounds) {
+    // 256 points: lane l takes records base + 64 k (each load instruction = 1 KiB contiguous)
+    const int base = first + lane;
+    if (next_first >= 0) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) qn[k] = cc.pts[base + 256 + 64 * k];
-        } else if (next_first >= 0) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) qn[k] = cc.pts[next_first + lane + 64 * k];
-        }
-        int pix[4], px[4], py[4];
-        unsigned dbits[4], bound[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float d;
-            pix[k] = project_one(q[k].x, q[k].y, q[k].z, M, W, H, d, px[k], py[k]);
-            if (px[k] < xlo || px[k] >= xhi) pix[k] = -1;
-            dbits[k] = __float_as_uint(d);
-            if (STATS && pix[k] >= 0) st_in++;
-        }
-        // early-z against the bound image (L1 / this XCD's L2; a stale bound is only ever LARGER)
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            bound[k] = pix[k] < 0 ? 0u
-                       : ZL2 ? __hip_atomic_load(zimg + pix[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)   // sc1: L2, not L1
-                             : zimg[pix[k]];
-        // Candidates = points at or in front of their pixel's bound (ties pass: the key's id part breaks them).  Kept as
-        // bit masks over the four points of a lane and handled in straight-line stages — the first version walked a
-        // per-point if-chain through all of it and the compiler shuffled the four 64-bit keys between branch arms
-        // (385 of the loop's 1370 VALU instructions were moves; the pass is VALU-issue bound).
-        unsigned long long key[4];
-        unsigned cand = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            key[k] = ((unsigned long long)dbits[k] << 32) | __float_as_uint(q[k].w);
-            cand |= (pix[k] >= 0 && dbits[k] <= bound[k] ? 1u : 0u) << k;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (((cand >> k) & 1u) && dbits[k] < bound[k]) zimg[pix[k]] = dbits[k];
-        // A chunk one of whose points reached a bound holds front points.  Beyond the near split (list B) such a chunk survives the
-        // bound test of EVERY frame and is run by ONE workgroup at pass B's tail; marked, the next splat_sticky classifications list
-        // it in A, where it is banded, binned and spread over the grid (surface scenes: far facades hold front points)
-        if (cc.mark_candidates && __ballot(cand != 0u) && lane == 0) cc.sticky[(unsigned)(first + r * 256) / CELL_CHUNK] = (unsigned char)cc.sticky_frames;
-        unsigned direct = cand;                                    // candidates that go to memory (bins / atomics) themselves
-        if (LDS && use_lds) {                                      // wave-uniform: dense chunk, fold into the wave's table first
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (!((cand >> k) & 1u)) continue;
-                unsigned h = ((unsigned)pix[k] * 2654435761u) >> 24;
-                bool placed = false;
-#pragma unroll
-                for (int probe = 0; probe < 2 && !placed; ++probe, h = (h + 1) & (LDS_SLOTS - 1)) {
-                    const unsigned old = atomicCAS(tag + h, 0u, (unsigned)pix[k] + 1u);
-                    if (old == 0u || old == (unsigned)pix[k] + 1u) {
-                        if (key[k] < atomicMin(hkey + h, key[k])) hpos[h] = base + 64 * k;
-                        placed = true;
-                    }
-                }
-                if (placed) direct &= ~(1u << k);
-            }
-        }
-        // Round 5: the ~12 % of a round's 256 points that reach a bound are COMPACTED into dense lanes before they are binned (BIN):
-        // the code behind the bound test then runs once for up to 64 candidates instead of four times, masked, over the four point
-        // slots of every lane (pass A is bound by the number of vector instructions it issues).  Ranks are prefix
-        // counts over the four ballots; the candidates travel through a wave-private queue in LDS (pixel, position, key).
-        bool compacted = false;
-        if (BIN && cq) {
-            unsigned long long mk[4];
-            int rank[4], tot = 0;
-            const unsigned long long lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                mk[k] = __ballot((direct >> k) & 1u);
-                rank[k] = tot + __builtin_popcountll(mk[k] & lt_mask);
-                tot += __builtin_popcountll(mk[k]);
-            }
-            if (tot <= 64) {                                           // wave-uniform
-                compacted = true;
-                if (tot) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        if ((direct >> k) & 1u)
-                            cq[rank[k]] = make_uint4((unsigned)pix[k], (unsigned)(base + 64 * k), (unsigned)key[k], (unsigned)(key[k] >> 32));
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // the wave's own queue: LDS operations complete in order
-                    const unsigned v = lane < tot ? 1u : 0u;
-                    const uint4 c = cq[lane < tot ? lane : 0];
-                    const int p1[1] = {(int)c.x};
-                    int y1[1], x1[1];
-                    y1[0] = (int)(((float)p1[0] + 0.5f) * bi.inv_w);           // exact for W * H <= 2^20 (as in the table flush below)
-                    x1[0] = p1[0] - y1[0] * W;
-                    const unsigned long long k1[1] = {((unsigned long long)c.w << 32) | c.z};
-                    if (v) next[p1[0]] = (int)c.y;                             // a front point of this pixel: next frame's seed
-                    if (STATS) st_atomics += v;
-                    emit_binned<1>(bi, p1, x1, y1, k1, v, keys, lane, wl_tile, wl_cnt, sub);
-                    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // the queue is free again before the next round writes it
-                }
-            }
-        }
-        if (!compacted) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if ((direct >> k) & 1u) {
-                    next[pix[k]] = base + 64 * k;                      // a front point of this pixel: next frame's seed
-                    if (!BIN) __hip_atomic_fetch_min(keys + key_slot(ks, (unsigned)pix[k]), key[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (STATS) st_atomics++;
-                }
-            if (BIN && __ballot(direct != 0u)) emit_binned<4>(bi, pix, px, py, key, direct, keys, lane, wl_tile, wl_cnt, sub);
-        }
-        if (LDS && use_lds) {
-            // the wave's own table: its LDS operations complete in program order, no barrier needed
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            unsigned flush = 0;
-#pragma unroll
-            for (int j = 0; j < LDS_SLOTS / 64; ++j) {
-                const int sl = lane + 64 * j;
-                const unsigned t = tag[sl];
-                pix[j] = (int)t - 1;
-                key[j] = hkey[sl];
-                py[j] = (int)(((float)pix[j] + 0.5f) * bi.inv_w);  // exact for W * H <= 2^20 (BIN only; unused otherwise)
-                px[j] = pix[j] - py[j] * W;
-                if (t) {
-                    flush |= 1u << j;
-                    if (!BIN) __hip_atomic_fetch_min(keys + key_slot(ks, t - 1u), key[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    next[t - 1u] = hpos[sl];
-                    tag[sl] = 0u;
-                    hkey[sl] = ~0ull;
-                    if (STATS) st_atomics++;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-            if (BIN && __ballot(flush != 0u)) emit_binned<4>(bi, pix, px, py, key, flush, keys, lane, wl_tile, wl_cnt, sub);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) q[k] = qn[k];
+        for (int k = 0; k < 4; ++k) qn[k] = cc.pts[next_first + lane + 64 * k];
     }
+    int pix[4], px[4], py[4];
+    unsigned dbits[4], bound[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float d;
+        pix[k] = project_one(q[k].x, q[k].y, q[k].z, M, W, H, d, px[k], py[k]);
+        dbits[k] = __float_as_uint(d);
+        if (STATS && pix[k] >= 0) st_in++;
+    }
+    // early-z against the bound image (L1 / this XCD's L2; a stale bound is only ever LARGER)
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        bound[k] = pix[k] < 0 ? 0u : zimg[pix[k]];
+    // Candidates = points at or in front of their pixel's bound (ties pass: the key's id part breaks them).  Kept as
+    // bit masks over the four points of a lane and handled in straight-line stages — the first version walked a
+    // per-point if-chain through all of it and the compiler shuffled the four 64-bit keys between branch arms
+    // (385 of the loop's 1370 VALU instructions were moves; the pass is VALU-issue bound).
+    unsigned long long key[4];
+    unsigned cand = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        key[k] = ((unsigned long long)dbits[k] << 32) | __float_as_uint(q[k].w);
+        cand |= (pix[k] >= 0 && dbits[k] <= bound[k] ? 1u : 0u) << k;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (((cand >> k) & 1u) && dbits[k] < bound[k]) zimg[pix[k]] = dbits[k];
+    // A chunk one of whose points reached a bound holds front points.  Beyond the near split (list B) such a chunk survives the
+    // bound test of EVERY frame and is run by ONE workgroup at pass B's tail; marked, the next splat_sticky classifications list
+    // it in A, where it is banded, binned and spread over the grid (surface scenes: far facades hold front points)
+    if (cc.mark_candidates && __ballot(cand != 0u) && lane == 0) cc.sticky[(unsigned)first / CELL_CHUNK] = (unsigned char)cc.sticky_frames;
+    unsigned direct = cand;                                    // candidates that go to memory (bins / atomics) themselves
+    if (LDS && use_lds) {                                      // wave-uniform: dense chunk, fold into the wave's table first
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!((cand >> k) & 1u)) continue;
+            unsigned h = ((unsigned)pix[k] * 2654435761u) >> 24;
+            bool placed = false;
+#pragma unroll
+            for (int probe = 0; probe < 2 && !placed; ++probe, h = (h + 1) & (LDS_SLOTS - 1)) {
+                const unsigned old = atomicCAS(tag + h, 0u, (unsigned)pix[k] + 1u);
+                if (old == 0u || old == (unsigned)pix[k] + 1u) {
+                    if (key[k] < atomicMin(hkey + h, key[k])) hpos[h] = base + 64 * k;
+                    placed = true;
+                }
+            }
+            if (placed) direct &= ~(1u << k);
+        }
+    }
+    // The ~12 % of the 256 points that reach a bound are COMPACTED into dense lanes before they are binned (BIN):
+    // the code behind the bound test then runs once for up to 64 candidates instead of four times, masked, over the four point
+    // slots of every lane (pass A is bound by the number of vector instructions it issues).  Ranks are prefix
+    // counts over the four ballots; the candidates travel through a wave-private queue in LDS (pixel, position, key).
+    // More than 64 of them (a cold first frame: every bound is "none") take the four masked point slots per lane below.
+    bool compacted = false;
+    if (BIN) {
+        unsigned long long mk[4];
+        int rank[4], tot = 0;
+        const unsigned long long lt_mask = (1ull << lane) - 1ull;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            mk[k] = __ballot((direct >> k) & 1u);
+            rank[k] = tot + __builtin_popcountll(mk[k] & lt_mask);
+            tot += __builtin_popcountll(mk[k]);
+        }
+        if (tot <= 64) {                                           // wave-uniform
+            compacted = true;
+            if (tot) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if ((direct >> k) & 1u)
+                        cq[rank[k]] = make_uint4((unsigned)pix[k], (unsigned)(base + 64 * k), (unsigned)key[k], (unsigned)(key[k] >> 32));
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // the wave's own queue: LDS operations complete in order
+                const unsigned v = lane < tot ? 1u : 0u;
+                const uint4 c = cq[lane < tot ? lane : 0];
+                const int p1[1] = {(int)c.x};
+                int y1[1], x1[1];
+                y1[0] = (int)(((float)p1[0] + 0.5f) * bi.inv_w);           // exact for W * H <= 2^20 (as in the table flush below)
+                x1[0] = p1[0] - y1[0] * W;
+                const unsigned long long k1[1] = {((unsigned long long)c.w << 32) | c.z};
+                if (v) next[p1[0]] = (int)c.y;                             // a front point of this pixel: next frame's seed
+                if (STATS) st_atomics += v;
+                emit_binned<1>(bi, p1, x1, y1, k1, v, keys, lane, wl_tile, wl_cnt, sub);
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");     // the queue is free again before the next call writes it
+            }
+        }
+    }
+    if (!compacted) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if ((direct >> k) & 1u) {
+                next[pix[k]] = base + 64 * k;                      // a front point of this pixel: next frame's seed
+                if (!BIN) __hip_atomic_fetch_min(keys + pix[k], key[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (STATS) st_atomics++;
+            }
+        if (BIN && __ballot(direct != 0u)) emit_binned<4>(bi, pix, px, py, key, direct, keys, lane, wl_tile, wl_cnt, sub);
+    }
+    if (LDS && use_lds) {
+        // the wave's own table: its LDS operations complete in program order, no barrier needed
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        unsigned flush = 0;
+#pragma unroll
+        for (int j = 0; j < LDS_SLOTS / 64; ++j) {
+            const int sl = lane + 64 * j;
+            const unsigned t = tag[sl];
+            pix[j] = (int)t - 1;
+            key[j] = hkey[sl];
+            py[j] = (int)(((float)pix[j] + 0.5f) * bi.inv_w);  // exact for W * H <= 2^20 (BIN only; unused otherwise)
+            px[j] = pix[j] - py[j] * W;
+            if (t) {
+                flush |= 1u << j;
+                if (!BIN) __hip_atomic_fetch_min(keys + (t - 1u), key[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                next[t - 1u] = hpos[sl];
+                tag[sl] = 0u;
+                hkey[sl] = ~0ull;
+                if (STATS) st_atomics++;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        if (BIN && __ballot(flush != 0u)) emit_binned<4>(bi, pix, px, py, key, flush, keys, lane, wl_tile, wl_cnt, sub);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = qn[k];
 }
 
-// Pass A: an item = 1024 / sub_items consecutive points of one list-A chunk, for one wave and one strip.
-// Pass B: four list-B entries in flight per wave: the hi-Z bounds of their rectangles (inside the strip) are loaded together,
+// Pass A: an item = a quarter (256 consecutive points) of one list-A chunk, for one wave and one strip.
+// Pass B: EPW list-B entries in flight per wave: the hi-Z bounds of their rectangles are loaded together,
 // then reduced; chunks that survive are processed like pass-A chunks.
-template <bool PASS_B, bool STATS, bool ZL2, bool LDS, bool BIN>
+constexpr int ITEMS_PER_CHUNK = CELL_CHUNK / 256;
+template <bool PASS_B, bool STATS, bool LDS, bool BIN>
 __global__ __launch_bounds__(256) void cells_pass_kernel(CellCloud cc, Cam1 cam, int W, int H,
                                                          unsigned long long *keys, unsigned *zimg,
                                                          const unsigned short *__restrict__ hiz_g, int nbx, void *hdr_v,
-                                                         int *next, int cset, StripInfo si, int sub_items,
-                                                         unsigned long long *stats, KeySlots ks, BinInfo bi)
+                                                         int *next, int cset, StripInfo si,
+                                                         unsigned long long *stats, BinInfo bi)
 {
     __shared__ unsigned s_tag[LDS ? 4 * LDS_SLOTS : 1];
     __shared__ unsigned long long s_key[LDS ? 4 * LDS_SLOTS : 1];
     __shared__ int s_pos[LDS ? 4 * LDS_SLOTS : 1];
     __shared__ unsigned s_wl[BIN ? 4 * 128 : 1];                     // per wave: 64 tiles + 64 counts / bases (emit_binned)
-    __shared__ uint4 s_cq[BIN ? 4 * 64 : 1];                         // per wave: the compacted candidates of a round (strip_points)
+    __shared__ uint4 s_cq[BIN ? 4 * 64 : 1];                         // per wave: the compacted candidates of an item (strip_points)
     __shared__ int s_surv[PASS_B ? 2 * 24 : 1];                      // pass B: the workgroup's surviving list entries of one round
     __shared__ int s_nsurv[2];
     unsigned *wl_tile = s_wl + (BIN ? (threadIdx.x >> 6) * 128 : 0), *wl_cnt = wl_tile + (BIN ? 64 : 0);
-    uint4 *cq = (BIN && bi.compact) ? s_cq + (threadIdx.x >> 6) * 64 : nullptr;
+    uint4 *cq = s_cq + (BIN ? (threadIdx.x >> 6) * 64 : 0);
     const float *M = cam.m;                                         // (`next`: the seed image this frame's front points go to)
     const int lane = threadIdx.x & 63;
     unsigned *tag = s_tag + (LDS ? (threadIdx.x >> 6) * LDS_SLOTS : 0);
@@ -862,31 +842,29 @@ __global__ __launch_bounds__(256) void cells_pass_kernel(CellCloud cc, Cam1 cam,
     const int n_waves = n_wg * (int)(blockDim.x >> 6);
     const int wave = __builtin_amdgcn_readfirstlane(wg_in_strip * (int)(blockDim.x >> 6) + (int)(threadIdx.x >> 6));
     const StripCounters *sc = strip_counters(hdr_v, cset, s);
-    const int xlo = 0, xhi = W;                                     // a chunk is processed whole by the strip that lists it
-    float4 q[4];
+    float4 q[4];                                                    // (a chunk is processed whole by the strip that lists it)
     if (!PASS_B) {
-        const int rounds = 4 / sub_items;
         int n_items = 0;
-        for (int b = 0; b < A_BANDS; ++b) n_items += sc->nA[b] * sub_items;
+        for (int b = 0; b < A_BANDS; ++b) n_items += sc->nA[b] * ITEMS_PER_CHUNK;
         // Items are pipelined over three iterations of the walk: the list entry of item i+2 and the point records of item
         // i+1 are in flight while item i is tested — a wave's item is otherwise a chain of four dependent memory round trips
         // (entry, records, bounds, slot reservation) with nothing of its own to overlap them.
-        int band = 0, band_first = 0, band_items = sc->nA[0] * sub_items;      // items [band_first, band_first + band_items)
+        int band = 0, band_first = 0, band_items = sc->nA[0] * ITEMS_PER_CHUNK;   // items [band_first, band_first + band_items)
         auto entry_of = [&](int t, int &part) {                                  // t only grows: the cursor moves forward
             while (t >= band_first + band_items) {
                 band_first += band_items;
                 ++band;
-                band_items = sc->nA[band] * sub_items;
+                band_items = sc->nA[band] * ITEMS_PER_CHUNK;
             }
-            const int tl = t - band_first, li = tl / sub_items;
-            part = tl - li * sub_items;
+            const int tl = t - band_first, li = tl / ITEMS_PER_CHUNK;
+            part = tl - li * ITEMS_PER_CHUNK;
             return cc.list_a[((size_t)s * A_BANDS + band) * cc.nchunks + li];
         };
         int part0 = 0, part1 = 0, part2 = 0, e0 = 0, e1 = 0, e2 = 0;
         if (wave < n_items) e0 = entry_of(wave, part0);
         if (wave + n_waves < n_items) e1 = entry_of(wave + n_waves, part1);
         if (wave < n_items) {
-            const int first0 = (__builtin_amdgcn_readfirstlane(e0) & 0x7fffffff) * CELL_CHUNK + part0 * rounds * 256;
+            const int first0 = (__builtin_amdgcn_readfirstlane(e0) & 0x7fffffff) * CELL_CHUNK + part0 * 256;
 #pragma unroll
             for (int k = 0; k < 4; ++k) q[k] = cc.pts[first0 + lane + 64 * k];
         }
@@ -895,11 +873,10 @@ __global__ __launch_bounds__(256) void cells_pass_kernel(CellCloud cc, Cam1 cam,
             const int entry = __builtin_amdgcn_readfirstlane(e0);
             const int chunk = entry & 0x7fffffff;
             const int next_first = t + n_waves < n_items
-                                       ? (__builtin_amdgcn_readfirstlane(e1) & 0x7fffffff) * CELL_CHUNK + part1 * rounds * 256 : -1;
+                                       ? (__builtin_amdgcn_readfirstlane(e1) & 0x7fffffff) * CELL_CHUNK + part1 * 256 : -1;
             ++n_run;
-            strip_points<STATS, ZL2, LDS, BIN>(cc, M, W, H, xlo, xhi, keys, zimg, next, chunk * CELL_CHUNK + part0 * rounds * 256,
-                                               rounds, lane, st_in, st_atomics, tag, hkey, hpos, ks, entry < 0, bi, wl_tile, wl_cnt,
-                                               wave & (BIN_SUB - 1), q, next_first, cq);
+            strip_points<STATS, LDS, BIN>(cc, M, W, H, keys, zimg, next, chunk * CELL_CHUNK + part0 * 256, lane, st_in, st_atomics,
+                                          tag, hkey, hpos, entry < 0, bi, wl_tile, wl_cnt, wave & (BIN_SUB - 1), q, next_first, cq);
             e0 = e1;
             part0 = part1;
             e1 = e2;
@@ -989,8 +966,8 @@ __global__ __launch_bounds__(256) void cells_pass_kernel(CellCloud cc, Cam1 cam,
                 const int first = (entry & 0x7fffffff) * CELL_CHUNK + (item & 3) * 256;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) q[k] = cc.pts[first + lane + 64 * k];
-                strip_points<STATS, ZL2, LDS, BIN>(cc, M, W, H, xlo, xhi, keys, zimg, next, first, 1, lane, st_in, st_atomics, tag, hkey,
-                                                   hpos, ks, entry < 0, bi, wl_tile, wl_cnt, wave & (BIN_SUB - 1), q, -1);
+                strip_points<STATS, LDS, BIN>(cc, M, W, H, keys, zimg, next, first, lane, st_in, st_atomics, tag, hkey,
+                                              hpos, entry < 0, bi, wl_tile, wl_cnt, wave & (BIN_SUB - 1), q, -1, cq);
             }
             __syncthreads();
         }
@@ -1014,8 +991,7 @@ __global__ __launch_bounds__(256) void cells_pass_kernel(CellCloud cc, Cam1 cam,
 // pixel is still empty; and zimg is set to the exact current depths (the racy stores of pass A may have left a larger
 // value than the minimum), so pass B's early-z is exact.
 __global__ __launch_bounds__(256) void cells_hiz_kernel(const unsigned long long *__restrict__ keys, unsigned *__restrict__ zimg,
-                                                        int W, int H, int nbx, int nby, unsigned short *__restrict__ hiz,
-                                                        KeySlots ks)
+                                                        int W, int H, int nbx, int nby, unsigned short *__restrict__ hiz)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nbx * nby) return;
@@ -1025,20 +1001,13 @@ __global__ __launch_bounds__(256) void cells_hiz_kernel(const unsigned long long
     for (int dy = 0; dy < 4; ++dy)
         if (by * 4 + dy < H) {                                  // W % 16 == 0: the block's 4 columns exist
             const long long off = (long long)(by * 4 + dy) * W + bx * 4;
+            const ulonglong2 k01 = *reinterpret_cast<const ulonglong2 *>(keys + off);
+            const ulonglong2 k23 = *reinterpret_cast<const ulonglong2 *>(keys + off + 2);
             uint4 z;
-            if (ks.mode == 0) {
-                const ulonglong2 k01 = *reinterpret_cast<const ulonglong2 *>(keys + off);
-                const ulonglong2 k23 = *reinterpret_cast<const ulonglong2 *>(keys + off + 2);
-                z.x = (unsigned)(k01.x >> 32);                  // EMPTY -> 0xffffffff = "none"
-                z.y = (unsigned)(k01.y >> 32);
-                z.z = (unsigned)(k23.x >> 32);
-                z.w = (unsigned)(k23.y >> 32);
-            } else {
-                z.x = (unsigned)(keys[key_slot(ks, (unsigned)off)] >> 32);
-                z.y = (unsigned)(keys[key_slot(ks, (unsigned)off + 1)] >> 32);
-                z.z = (unsigned)(keys[key_slot(ks, (unsigned)off + 2)] >> 32);
-                z.w = (unsigned)(keys[key_slot(ks, (unsigned)off + 3)] >> 32);
-            }
+            z.x = (unsigned)(k01.x >> 32);                      // EMPTY -> 0xffffffff = "none"
+            z.y = (unsigned)(k01.y >> 32);
+            z.z = (unsigned)(k23.x >> 32);
+            z.w = (unsigned)(k23.y >> 32);
             *reinterpret_cast<uint4 *>(zimg + off) = z;
             m = max(max(m, z.x), max(max(z.y, z.z), z.w));
         }
@@ -1206,8 +1175,7 @@ struct ObjBatch {
 };
 
 __global__ __launch_bounds__(256) void splat_objects_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
-                                                            ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys,
-                                                            KeySlots ks)
+                                                            ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys)
 {
     const int b = (int)blockIdx.x;
     int j = 0;
@@ -1220,7 +1188,7 @@ __global__ __launch_bounds__(256) void splat_objects_kernel(const float *__restr
     const int pix = project_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], W, H, d, xx, yy);
     if (pix < 0) return;
     const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)ids[i];
-    unsigned long long *k = keys + key_slot(ks, (unsigned)pix);
+    unsigned long long *k = keys + pix;
     if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
 }
 
@@ -1283,8 +1251,7 @@ __device__ __forceinline__ int project_pano_one(float x, float y, float z, const
 // splat_objects_kernel under panorama cameras: ob.m[k] holds range k's 16 camera floats.  The whole cloud (or a labelled cloud's
 // static part) is one range; ids == NULL: the id is the point's index.
 __global__ __launch_bounds__(256) void splat_pano_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
-                                                         ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys,
-                                                         KeySlots ks)
+                                                         ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys)
 {
     const int b = (int)blockIdx.x;
     int j = 0;
@@ -1298,7 +1265,7 @@ __global__ __launch_bounds__(256) void splat_pano_kernel(const float *__restrict
     if (pix < 0) return;
     const unsigned id = ids ? (unsigned)ids[i] : (unsigned)i;
     const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | id;
-    unsigned long long *k = keys + key_slot(ks, (unsigned)pix);
+    unsigned long long *k = keys + pix;
     if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
 }
 
@@ -1343,7 +1310,7 @@ __device__ __forceinline__ unsigned long long kmin(unsigned long long a, unsigne
 __device__ __forceinline__ void resolve_tile(unsigned long long *__restrict__ keys, int W, int H,
                                              int levels, const ResolveOut &out, int tiles_x,
                                              int *__restrict__ prev_idx,
-                                             void *hdr_v, int keep, unsigned *__restrict__ zimg, int cset, const KeySlots &ks,
+                                             void *hdr_v, int keep, unsigned *__restrict__ zimg, int cset,
                                              const int blk, const int cam)
 {
     __shared__ unsigned long long s1[256], s2[64], s3[16];
@@ -1363,9 +1330,8 @@ __device__ __forceinline__ void resolve_tile(unsigned long long *__restrict__ ke
             unsigned long long v = EMPTY_KEY;
             if (x < W && y < H) {
                 const long long off = (long long)y * W + x;
-                const long long slot = keep == 2 ? (long long)key_slot(ks, (unsigned)off) : off;
-                v = kc[slot];
-                kc[slot] = EMPTY_KEY;                // leave the workspace clean for the next frame
+                v = kc[off];
+                kc[off] = EMPTY_KEY;                 // leave the workspace clean for the next frame
                 emit(out, 0, cam * npx0 + off, v);
                 if (keep == 1) prev_idx[off] = v == EMPTY_KEY ? -1 : (int)(unsigned)(v & 0xffffffffull);   // next frame's seeds
                 if (keep == 2) zimg[off] = 0xffffffffu;       // "no bound"
@@ -1430,9 +1396,9 @@ __device__ __forceinline__ void resolve_tile(unsigned long long *__restrict__ ke
 __global__ __launch_bounds__(256) void splat_resolve_kernel(unsigned long long *__restrict__ keys, int W, int H,
                                                             int levels, ResolveOut out, int tiles_x,
                                                             int tiles_y, int *__restrict__ prev_idx,
-                                                            void *hdr_v, int keep, unsigned *__restrict__ zimg, int cset, KeySlots ks)
+                                                            void *hdr_v, int keep, unsigned *__restrict__ zimg, int cset)
 {
-    resolve_tile(keys, W, H, levels, out, tiles_x, prev_idx, hdr_v, keep, zimg, cset, ks, (int)blockIdx.x, (int)blockIdx.y);
+    resolve_tile(keys, W, H, levels, out, tiles_x, prev_idx, hdr_v, keep, zimg, cset, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // The resolve launch of a cell-path frame whose caller has announced the NEXT camera (read_splat_hint_next_camera): next to the
@@ -1450,7 +1416,7 @@ struct NextFrame {
 };
 __global__ __launch_bounds__(256) void cells_resolve_next_kernel(unsigned long long *__restrict__ keys, int W, int H,
                                                                  int levels, ResolveOut out, int tiles_x, int res_blocks,
-                                                                 void *hdr_v, unsigned *__restrict__ zimg, int cset, KeySlots ks,
+                                                                 void *hdr_v, unsigned *__restrict__ zimg, int cset,
                                                                  CellCloud cc, NextFrame nx, StripInfo si)
 {
     // dispatch order = block order: the classification blocks first — theirs is the longest dependent chain of the launch (box ->
@@ -1461,7 +1427,7 @@ __global__ __launch_bounds__(256) void cells_resolve_next_kernel(unsigned long l
         return;
     }
     if (b < nx.class_blocks + res_blocks) {
-        resolve_tile(keys, W, H, levels, out, tiles_x, nullptr, hdr_v, 2, zimg, cset, ks, b - nx.class_blocks, 0);
+        resolve_tile(keys, W, H, levels, out, tiles_x, nullptr, hdr_v, 2, zimg, cset, b - nx.class_blocks, 0);
         return;
     }
     if (nx.use_seeds) seed_block(cc, nx.cam.m, W, H, nx.zimg, nx.pos_img, b - res_blocks - nx.class_blocks);
@@ -1496,14 +1462,9 @@ int g_splat_near = 12;         // cell path: pass A takes chunks nearer than the
 int g_splat_cells = 1;         // 0: ignore the cell-ordered copy (A/B)
 int g_splat_cells_sub = 0;     // list A also takes every n-th chunk (a first bound where nothing is near); 0: only on a workspace's first frame (every 32nd)
 int g_splat_seeds = 1;         // 0: no warm start from the previous frame's front points (A/B)
-int g_splat_items = 4;         // work items per chunk in the striped passes (1, 2 or 4): 0.101 / 0.101 / 0.097 ms per frame
-int g_splat_zl2 = 0;            // 1: early-z loads bypass the L1 (sc1); measured slower (0.107 vs 0.101 ms)
-int g_splat_kslot = 0;          // key-image layout of the striped path: 0 linear, 1 one key per 64 B, 2 scattered (key_slot):
-                                // pass A 60.7 / 66.0 / 61.9 us — the atomics do not serialise on neighbouring lines, their NUMBER is the cost
 int g_splat_lds = 1;            // 1: per-wave LDS hash table in front of the memory-side atomics (strip_points)
 int g_splat_wgs = 4;            // workgroups per CU of the striped passes: 0.0996 / 0.0936 / 0.0893 / 0.0927 / 0.0923 ms at 2 / 3 / 4 / 6 / 8
                                 // (fewer waves = more rounds per wave = finer front-to-back order over the depth bands)
-int g_splat_compact = 1;        // 1: pass A compacts a round's candidates before binning them (strip_points); 0: four masked point slots per lane
 int g_splat_cells_batch = 1;    // 1: a batch of cameras runs as B cell-path frames; 0: the plain pass over the whole cloud (rounds 1-4)
 int g_splat_wgs_b = 0;          // workgroups per CU of pass B (0: as pass A, splat_wgs)
 int g_splat_mark = 1;           // 1: every chunk one of whose points reaches a depth bound is listed in A for the next splat_sticky classifications
@@ -1516,9 +1477,11 @@ int g_splat_strips = 1;         // column strips of the striped passes (1, 2, 4 
                                // Morton order (pass A 61.5 / 75.5 / 70 us at 8 / 2 / 1: fewer atomics with exact bounds); with the
                                // depth bands ONE global list wins — global front-to-back order and perfect balance: bench
                                // 0.0866 / 0.0867 / 0.0951 ms at 1 / 2 / 8 strips, street scene 0.099 vs 0.138 ms at 1 vs 8
+                               // (re-measured on whole laps, profiles/raster_knobs_refactor.md: 2 strips no longer lose to 1 — it stays a knob)
 
 // Workspace layout (fixed by the (B, W, H) it was sized for; one workspace serves one such triple):
-//   [header 4096 B][key images: min(B,8) x W*H x 8 B][hi-z bounds: ceil(W/4)*ceil(H/4) x 4 B][seed image 0: W*H x 4 B]
+//   [header 8192 B][key images: 8 x W*H x 8 B, min(B,8) of them in use, the rest is slack][hi-z bounds: ceil(W/4)*ceil(H/4) x 4 B]
+//   [seed image 0: W*H x 4 B]
 //   [seed image 1: W*H x 4 B][zimg 0, zimg 1: W*H x 4 B each, depth upper bounds of the cell path, 0xffffffff = none]
 struct WsLayout {
     void *hdr;
@@ -1529,7 +1492,6 @@ struct WsLayout {
     unsigned *bin_count;       // striped path, binned pass A: per 32x32 tile, minus one
     uint4 *bin_recs;           // tiles x bin_cap records
     int bin_cap, bin_tiles_x, bin_tiles;
-    size_t key_slots;
     int nbx, nby;
     size_t total;
 };
@@ -1542,8 +1504,8 @@ WsLayout ws_layout(void *ws, int B, int W, int H)
     L.hdr = p;
     size_t off = HEADER_BYTES;
     L.keys = (unsigned long long *)(p + off);
-    L.key_slots = (size_t)(nb < 8 ? 8 : nb) * W * H;            // >= 8 W H: room for the scattered key layouts of the striped path
-    off += L.key_slots * sizeof(unsigned long long);
+    // always 8 W H slots: nb key images and slack (the size read_splat_workspace_bytes has always answered for this triple)
+    off += (size_t)(nb < 8 ? 8 : nb) * W * H * sizeof(unsigned long long);
     off = (off + 255) / 256 * 256;
     L.nbx = ceil_div(W, 4);
     L.nby = ceil_div(H, 4);
@@ -1588,12 +1550,12 @@ ResolveOut resolve_out(int b0, int W, int H, int levels, int32_t *const *idx_lev
 // cset: the frame's counter set / bound image (cell path, keep == 2)
 int resolve_launch(unsigned long long *keys, int nb, int b0, int W, int H, int levels, int32_t *const *idx_levels,
                    float *const *depth_levels, int level_base, const WsLayout &ws, int keep, hipStream_t stream,
-                   KeySlots ks = KeySlots{0, 0}, int cset = 0)
+                   int cset = 0)
 {
     const ResolveOut out = resolve_out(b0, W, H, levels, idx_levels, depth_levels, level_base);
     const int tiles_x = ceil_div(W, 32), tiles_y = ceil_div(H, 32);
     hipLaunchKernelGGL(splat_resolve_kernel, dim3(tiles_x * tiles_y, nb), dim3(256), 0, stream, keys, W, H,
-                       levels, out, tiles_x, tiles_y, ws.prev[0], ws.hdr, keep, ws.zimg[cset], cset, ks);
+                       levels, out, tiles_x, tiles_y, ws.prev[0], ws.hdr, keep, ws.zimg[cset], cset);
     READ_CHECK_LAUNCH();
     return READ_OK;
 }
@@ -1744,14 +1706,14 @@ struct ObjectsDraw {
 };
 
 int objects_flush(ObjBatch &ob, int &blocks, const float *xyz, const int32_t *ids, int W, int H, unsigned long long *keys,
-                  KeySlots ks, hipStream_t stream, bool pano = false)
+                  hipStream_t stream, bool pano = false)
 {
     if (ob.count == 0) return READ_OK;
     ob.block0[ob.count] = blocks;
     if (pano)
-        hipLaunchKernelGGL(splat_pano_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys, ks);
+        hipLaunchKernelGGL(splat_pano_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys);
     else
-        hipLaunchKernelGGL(splat_objects_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys, ks);
+        hipLaunchKernelGGL(splat_objects_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys);
     READ_CHECK_LAUNCH();
     ob.count = 0;
     blocks = 0;
@@ -1770,22 +1732,22 @@ void objects_add(ObjBatch &ob, int &blocks, int64_t first, int64_t last, const f
 
 // Every visible, non-empty range of `od` into the key image: stream-ordered, OBJ_MAX ranges per launch, no synchronisation.
 // pano: the matrices are panorama cameras (splat_pano_kernel), and ids0 may be NULL (the static range's ids are its indices).
-int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, KeySlots ks, hipStream_t stream, bool pano = false)
+int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, hipStream_t stream, bool pano = false)
 {
     ObjBatch ob;
     memset(&ob, 0, sizeof(ob));
     int blocks = 0, rc;
     if (od.n0 > 0) {
         objects_add(ob, blocks, 0, od.n0, od.M0);
-        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
+        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, stream, pano)) != READ_OK) return rc;
     }
     for (int k = 0; k < od.count; ++k) {
         const int64_t first = od.first[k], last = first + od.npts[k];
         if ((od.visible && !od.visible[k]) || last == first) continue;                      // hidden or empty: not launched
         objects_add(ob, blocks, first, last, od.M + 16 * (size_t)k);
-        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream, pano)) != READ_OK) return rc;
+        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano)) != READ_OK) return rc;
     }
-    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, ks, stream, pano);
+    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano);
 }
 
 // ---- per-kernel durations of the LAST cell-path frame (read_tuning_set("splat_prof", 1) + read_splat_profile_last): HIP events
@@ -1840,15 +1802,8 @@ int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int leve
     }
     int *const next_pos = ws.prev[fp ^ 1];            // the seed image this frame's passes write: the next frame's (set fp ^ 1) seeds
     const unsigned grid = (unsigned)(device_cus() * g_splat_wgs);
-    const int items = g_splat_items;
-    KeySlots ks;
-    ks.mode = g_splat_kslot;
-    ks.mask = 1;
-    while (ks.mask < (unsigned)(W * H)) ks.mask <<= 1;
-    ks.mask -= 1;
-    if (ks.mode == 2 && (size_t)ks.mask + 1 > ws.key_slots) ks.mode = 0;      // (a workspace of this size always has 8 W H slots)
-    // bins need the linear key layout and exact pixel rows from (pix + 0.5) / W in fp32
-    const bool bins = g_splat_bins && ks.mode == 0 && (long long)W * H <= (1ll << 20);
+    // bins need exact pixel rows from (pix + 0.5) / W in fp32
+    const bool bins = g_splat_bins && (long long)W * H <= (1ll << 20);
     BinInfo bi;
     memset(&bi, 0, sizeof(bi));
     if (bins) {
@@ -1857,20 +1812,20 @@ int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int leve
         bi.cap = ws.bin_cap;
         bi.tiles_x = ws.bin_tiles_x;
         bi.inv_w = 1.0f / (float)W;
-        bi.compact = g_splat_compact;
     }
-    auto pass_a = bins ? (stats ? (g_splat_lds ? cells_pass_kernel<false, true, false, true, true> : cells_pass_kernel<false, true, false, false, true>)
-                          : g_splat_zl2 ? cells_pass_kernel<false, false, true, false, true>
-                          : g_splat_lds ? cells_pass_kernel<false, false, false, true, true> : cells_pass_kernel<false, false, false, false, true>)
-                  : stats ? (g_splat_lds ? cells_pass_kernel<false, true, false, true, false> : cells_pass_kernel<false, true, false, false, false>)
-                  : g_splat_zl2 ? cells_pass_kernel<false, false, true, false, false>
-                  : g_splat_lds ? cells_pass_kernel<false, false, false, true, false> : cells_pass_kernel<false, false, false, false, false>;
-    auto pass_b = stats ? (g_splat_lds ? cells_pass_kernel<true, true, false, true, false> : cells_pass_kernel<true, true, false, false, false>)
-                  : g_splat_zl2 ? cells_pass_kernel<true, false, true, false, false>
-                  : g_splat_lds ? cells_pass_kernel<true, false, false, true, false> : cells_pass_kernel<true, false, false, false, false>;
+    // cells_pass_kernel<PASS_B, STATS, LDS, BIN> by [pass][stats][lds][bins]; pass B never bins
+    using PassKernel = decltype(&cells_pass_kernel<false, false, false, false>);
+    static const PassKernel k_pass[2][2][2][2] = {
+        {{{cells_pass_kernel<false, false, false, false>, cells_pass_kernel<false, false, false, true>},
+          {cells_pass_kernel<false, false, true, false>, cells_pass_kernel<false, false, true, true>}},
+         {{cells_pass_kernel<false, true, false, false>, cells_pass_kernel<false, true, false, true>},
+          {cells_pass_kernel<false, true, true, false>, cells_pass_kernel<false, true, true, true>}}},
+        {{{cells_pass_kernel<true, false, false, false>, nullptr}, {cells_pass_kernel<true, false, true, false>, nullptr}},
+         {{cells_pass_kernel<true, true, false, false>, nullptr}, {cells_pass_kernel<true, true, true, false>, nullptr}}}};
+    const PassKernel pass_a = k_pass[0][stats != nullptr][g_splat_lds][bins], pass_b = k_pass[1][stats != nullptr][g_splat_lds][0];
     if (prof_mark(1, stream) != READ_OK) return READ_EHIP;
     hipLaunchKernelGGL(pass_a, dim3(grid), dim3(256), 0, stream, cc, cam, W, H, ws.keys, ws.zimg[fp],
-                       (const unsigned short *)ws.hiz, ws.nbx, ws.hdr, next_pos, fp, si, items, stats, ks, bi);
+                       (const unsigned short *)ws.hiz, ws.nbx, ws.hdr, next_pos, fp, si, stats, bi);
     READ_CHECK_LAUNCH();
     if (prof_mark(2, stream) != READ_OK) return READ_EHIP;
     if (bins)
@@ -1878,17 +1833,17 @@ int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int leve
                            ws.nbx, ws.hiz, bi);
     else
         hipLaunchKernelGGL(cells_hiz_kernel, dim3(ceil_div(ws.nbx * ws.nby, 256)), dim3(256), 0, stream,
-                           (const unsigned long long *)ws.keys, ws.zimg[fp], W, H, ws.nbx, ws.nby, ws.hiz, ks);
+                           (const unsigned long long *)ws.keys, ws.zimg[fp], W, H, ws.nbx, ws.nby, ws.hiz);
     READ_CHECK_LAUNCH();
     bi.recs = nullptr;
     if (prof_mark(3, stream) != READ_OK) return READ_EHIP;
     hipLaunchKernelGGL(pass_b, dim3((unsigned)(device_cus() * (g_splat_wgs_b > 0 ? g_splat_wgs_b : g_splat_wgs))), dim3(256), 0, stream, cc, cam, W, H, ws.keys, ws.zimg[fp],
-                       (const unsigned short *)ws.hiz, ws.nbx, ws.hdr, next_pos, fp, si, items, stats, ks, bi);
+                       (const unsigned short *)ws.hiz, ws.nbx, ws.hdr, next_pos, fp, si, stats, bi);
     READ_CHECK_LAUNCH();
     // ---- scene editing: the objects join the key image before the resolve (profile slot 3 includes them).  The bound image
     // stays the static part's: an upper bound of the static depths, so also of the merged ones
     if (objs) {
-        const int rc = objects_launch(*objs, W, H, ws.keys, ks, stream);
+        const int rc = objects_launch(*objs, W, H, ws.keys, stream);
         if (rc != READ_OK) return rc;
     }
     // ---- resolve; with an announced next camera the same launch prepares the next frame's set
@@ -1897,7 +1852,7 @@ int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int leve
     h.frame += 1;
     if (prof_mark(4, stream) != READ_OK) return READ_EHIP;
     if (!ahead) {
-        const int rc = resolve_launch(ws.keys, 1, b0, W, H, levels, idx_levels, depth_levels, 0, ws, 2, stream, ks, fp);
+        const int rc = resolve_launch(ws.keys, 1, b0, W, H, levels, idx_levels, depth_levels, 0, ws, 2, stream, fp);
         if (rc == READ_OK && prof_mark(5, stream) == READ_OK) g_prof_valid = g_splat_prof != 0;
         return rc;
     }
@@ -1913,7 +1868,7 @@ int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int leve
     const ResolveOut out = resolve_out(b0, W, H, levels, idx_levels, depth_levels, 0);
     const int tiles_x = ceil_div(W, 32), res_blocks = tiles_x * ceil_div(H, 32);
     hipLaunchKernelGGL(cells_resolve_next_kernel, dim3((unsigned)(res_blocks + class_blocks + (g_splat_seeds ? seed_blocks : 0))), dim3(256),
-                       0, stream, ws.keys, W, H, levels, out, tiles_x, res_blocks, ws.hdr, ws.zimg[fp], fp, ks, cc, nx, si);
+                       0, stream, ws.keys, W, H, levels, out, tiles_x, res_blocks, ws.hdr, ws.zimg[fp], fp, cc, nx, si);
     READ_CHECK_LAUNCH();
     h.pred = true;
     memcpy(h.pm, h.hint, sizeof(h.pm));
@@ -1942,59 +1897,38 @@ extern "C" size_t read_splat_workspace_bytes(int B, int W, int H)
 }
 
 namespace readhip {
-void splat_set_subset(int v) { g_splat_subset = v < 0 ? 0 : v; }
-void splat_set_stats(int v) { g_splat_stats = v; }
-int splat_set_mode(int m)
+// The "splat_*" tuning keys, one row each (read_tuning_set / read_tuning_get / read_tuning_key, api_common.cpp).
+constexpr int ANY = 0x7fffffff;
+const TuneRow k_splat_knobs[] = {
+    {"splat_mode", &g_splat_mode, TN_EITHER, MODE_AGENT, MODE_HIZ},
+    {"splat_stats", &g_splat_stats, TN_RAW, 0, 0},
+    {"splat_subset", &g_splat_subset, TN_CLAMP, 0, ANY},
+    {"splat_near", &g_splat_near, TN_CLAMP, 1, ANY},
+    {"splat_cells", &g_splat_cells, TN_RAW, 0, 0},
+    {"splat_cells_sub", &g_splat_cells_sub, TN_CLAMP, 0, ANY},
+    {"splat_seeds", &g_splat_seeds, TN_RAW, 0, 0},
+    {"splat_strips", &g_splat_strips, TN_POW2, 1, MAX_STRIPS},
+    {"splat_wgs", &g_splat_wgs, TN_CLAMP, 1, 16},
+    {"splat_lds", &g_splat_lds, TN_FLAG, 0, 0},
+    {"splat_bins", &g_splat_bins, TN_FLAG, 0, 0},
+    {"splat_ahead", &g_splat_ahead, TN_FLAG, 0, 0},
+    {"splat_prof", &g_splat_prof, TN_FLAG, 0, 0},
+    {"splat_mark", &g_splat_mark, TN_FLAG, 0, 0},
+    {"splat_cells_batch", &g_splat_cells_batch, TN_FLAG, 0, 0},
+    {"splat_sticky", &g_splat_sticky, TN_CLAMP, 0, 200},
+    {"splat_wgs_b", &g_splat_wgs_b, TN_CLAMP, 0, 16},
+};
+constexpr int N_SPLAT_KNOBS = sizeof(k_splat_knobs) / sizeof(k_splat_knobs[0]);
+
+int splat_set(const char *key, int v)
 {
-    if (m != MODE_AGENT && m != MODE_HIZ) return READ_EINVAL;
-    g_splat_mode = m;
-    return READ_OK;
+    const int rc = tune_set(k_splat_knobs, N_SPLAT_KNOBS, key, v);
+    if (rc < 0) set_error("read_tuning_set: splat_mode must be 1 (agent atomics) or 7 (warm start + hi-z)");     // the one row that refuses
+    return rc;
 }
-void splat_set_near(int v) { g_splat_near = v < 1 ? 1 : v; }
-void splat_set_cells(int v) { g_splat_cells = v; }
-void splat_set_seeds(int v) { g_splat_seeds = v; }
-void splat_set_cells_sub(int v) { g_splat_cells_sub = v < 0 ? 0 : v; }
-void splat_set_items(int v) { g_splat_items = v >= 4 ? 4 : (v >= 2 ? 2 : 1); }
-void splat_set_zl2(int v) { g_splat_zl2 = v != 0; }
-void splat_set_lds(int v) { g_splat_lds = v != 0; }
-void splat_set_bins(int v) { g_splat_bins = v != 0; }
-void splat_set_ahead(int v) { g_splat_ahead = v != 0; }
-void splat_set_mark(int v) { g_splat_mark = v != 0; }
-void splat_set_cells_batch(int v) { g_splat_cells_batch = v != 0; }
-void splat_set_compact(int v) { g_splat_compact = v != 0; }
-void splat_set_wgs_b(int v) { g_splat_wgs_b = v < 0 ? 0 : (v > 16 ? 16 : v); }
-void splat_set_sticky(int v) { g_splat_sticky = v < 0 ? 0 : (v > 200 ? 200 : v); }
-void splat_set_prof(int v) { g_splat_prof = v != 0; }
-void splat_set_kslot(int v) { g_splat_kslot = v < 0 ? 0 : (v > 2 ? 2 : v); }
-void splat_set_wgs(int v) { g_splat_wgs = v < 1 ? 1 : (v > 16 ? 16 : v); }
-void splat_set_strips(int v) { g_splat_strips = v >= 8 ? 8 : (v >= 4 ? 4 : (v >= 2 ? 2 : 1)); }
-int splat_get(const char *key, int *value)
-{
-    if (!strcmp(key, "splat_mode")) *value = g_splat_mode;
-    else if (!strcmp(key, "splat_subset")) *value = g_splat_subset;
-    else if (!strcmp(key, "splat_stats")) *value = g_splat_stats;
-    else if (!strcmp(key, "splat_near")) *value = g_splat_near;
-    else if (!strcmp(key, "splat_cells")) *value = g_splat_cells;
-    else if (!strcmp(key, "splat_seeds")) *value = g_splat_seeds;
-    else if (!strcmp(key, "splat_cells_sub")) *value = g_splat_cells_sub;
-    else if (!strcmp(key, "splat_items")) *value = g_splat_items;
-    else if (!strcmp(key, "splat_strips")) *value = g_splat_strips;
-    else if (!strcmp(key, "splat_wgs")) *value = g_splat_wgs;
-    else if (!strcmp(key, "splat_zl2")) *value = g_splat_zl2;
-    else if (!strcmp(key, "splat_lds")) *value = g_splat_lds;
-    else if (!strcmp(key, "splat_bins")) *value = g_splat_bins;
-    else if (!strcmp(key, "splat_ahead")) *value = g_splat_ahead;
-    else if (!strcmp(key, "splat_mark")) *value = g_splat_mark;
-    else if (!strcmp(key, "splat_cells_batch")) *value = g_splat_cells_batch;
-    else if (!strcmp(key, "splat_compact")) *value = g_splat_compact;
-    else if (!strcmp(key, "splat_wgs_b")) *value = g_splat_wgs_b;
-    else if (!strcmp(key, "splat_sticky")) *value = g_splat_sticky;
-    else if (!strcmp(key, "splat_prof")) *value = g_splat_prof;
-    else if (!strcmp(key, "splat_kslot")) *value = g_splat_kslot;
-    else return 0;
-    return 1;
-}
-}
+int splat_get(const char *key, int *value) { return tune_get(k_splat_knobs, N_SPLAT_KNOBS, key, value); }
+const char *splat_key(int i) { return tune_key(k_splat_knobs, N_SPLAT_KNOBS, i); }
+}  // namespace readhip
 
 __global__ __launch_bounds__(256) void splat_header_clear_kernel(int *hdr)
 {
@@ -2912,7 +2846,7 @@ int objects_frame(ObjectsDraw od, const float *xyz_static, const int32_t *ids_st
     // whose keys and warm start carry implicit ids), and the resolve keeps no seeds
     if (const int rc = ws_forget_prediction(ws, s); rc != READ_OK) return rc;
     od.n0 = n_static;
-    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s);
+    const int rc = objects_launch(od, W, H, L.keys, s);
     if (rc != READ_OK) return rc;
     return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
 }
@@ -2936,7 +2870,7 @@ int pano_frame(ObjectsDraw od, const float *xyz, const int32_t *ids, int64_t n, 
                            (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
         READ_CHECK_LAUNCH();
     }
-    const int rc = objects_launch(od, W, H, L.keys, KeySlots{0, 0}, s, true);
+    const int rc = objects_launch(od, W, H, L.keys, s, true);
     if (rc != READ_OK) return rc;
     return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
 }

@@ -13,6 +13,7 @@
 // trains with (configs/train_example.yaml: eval_in_train: True, train.py:271-277).
 // Weights change every optimizer step, so the MFMA fragment orders are produced on the device (pack_*_kernel).
 #include "common.h"
+#include "internal.h"
 
 using namespace readhip;
 
@@ -1436,12 +1437,10 @@ extern "C" int read_conv_dgrad_generic(const float *dfm, int outH, int outW, int
 
 namespace readhip {
 int g_wgrad_wino = 1;     // read_tuning_set("wgrad_wino", 0): 3x3 / stride-1 weight gradients back on the direct kernel
-void train_set_wgrad_wino(int v) { g_wgrad_wino = v; }
-int train_get(const char *key, int *value)
-{
-    if (!strcmp(key, "wgrad_wino")) { *value = g_wgrad_wino; return 1; }
-    return 0;
-}
+static const TuneRow k_train_knobs[] = {{"wgrad_wino", &g_wgrad_wino, TN_RAW, 0, 0}};
+int train_set(const char *key, int v) { return tune_set(k_train_knobs, 1, key, v); }
+int train_get(const char *key, int *value) { return tune_get(k_train_knobs, 1, key, value); }
+const char *train_key(int i) { return tune_key(k_train_knobs, 1, i); }
 }  // namespace readhip
 
 namespace {

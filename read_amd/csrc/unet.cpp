@@ -905,15 +905,13 @@ extern "C" const float *read_unet_debug_tensor(read_unet_t *u, const char *name,
 }
 
 namespace readhip {
-void unet_set_streams(int v) { g_unet_streams = v; }
-void unet_set_aff_split(int v) { g_unet_aff_split = v; }
-void unet_set_up_fold(int v) { g_unet_up_fold = v; }
-int unet_get(const char *key, int *value)
-{
-    if (!strcmp(key, "unet_streams")) *value = g_unet_streams;
-    else if (!strcmp(key, "unet_aff_split")) *value = g_unet_aff_split;
-    else if (!strcmp(key, "unet_up_fold")) *value = g_unet_up_fold;
-    else return 0;
-    return 1;
-}
+static const TuneRow k_unet_knobs[] = {
+    {"unet_streams", &g_unet_streams, TN_RAW, 0, 0},          // 0: SCM chains on the caller's stream
+    {"unet_aff_split", &g_unet_aff_split, TN_FLAG, 0, 0},     // 0: AFF first convs as single 480-channel launches (plans created afterwards)
+    {"unet_up_fold", &g_unet_up_fold, TN_FLAG, 0, 0},         // 0: Upsample4(bilinear) as a separate pass and Convs.k over the concat (plans created afterwards)
+};
+constexpr int N_UNET_KNOBS = sizeof(k_unet_knobs) / sizeof(k_unet_knobs[0]);
+int unet_set(const char *key, int v) { return tune_set(k_unet_knobs, N_UNET_KNOBS, key, v); }
+int unet_get(const char *key, int *value) { return tune_get(k_unet_knobs, N_UNET_KNOBS, key, value); }
+const char *unet_key(int i) { return tune_key(k_unet_knobs, N_UNET_KNOBS, i); }
 }

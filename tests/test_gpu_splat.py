@@ -190,7 +190,6 @@ def test_announced_next_camera_is_exact_whatever_comes_next(hip):
         for mark, sticky in ((0, 8), (1, 1), (1, 8), (1, 0), (0, 0)):
             _lib.check(L.read_tuning_set(b"splat_mark", mark))
             _lib.check(L.read_tuning_set(b"splat_sticky", sticky))
-            _lib.check(L.read_tuning_set(b"splat_compact", sticky & 1))          # candidates compacted before binning / four masked slots
             seq = [60, 61, 62, 63, 64, 180, 181, 64, 65]
             for i, k in enumerate(seq):
                 _exact(r, xyz, proj, k, W, H, nxt=seq[i + 1] if (i + 1 < len(seq) and i % 3 != 2) else None, what=f"mark={mark} sticky={sticky}")
@@ -199,7 +198,6 @@ def test_announced_next_camera_is_exact_whatever_comes_next(hip):
         _lib.check(L.read_tuning_set(b"splat_ahead", 1))
         _lib.check(L.read_tuning_set(b"splat_mark", 1))
         _lib.check(L.read_tuning_set(b"splat_sticky", 1))
-        _lib.check(L.read_tuning_set(b"splat_compact", 1))
 
 
 def test_camera_plane_sides_of_the_chunk_boxes(hip):
@@ -309,10 +307,10 @@ def test_cell_ordered_passes_are_exact_for_hard_cameras(hip):
                     assert np.array_equal(dep[l][0].cpu().numpy().view(np.uint32), od[l].view(np.uint32))
     finally:
         _lib.check(L.read_tuning_set(b"splat_near", 12))
-    # work-item granularity of the striped passes, no warm start, every 32nd chunk in pass A on every frame (rounds 2-4)
+    # no warm start, every 32nd chunk in pass A on every frame (rounds 2-4), column strips, no LDS table, no bins
     try:
-        for key, val in ((b"splat_items", 2), (b"splat_items", 1), (b"splat_seeds", 0), (b"splat_cells_sub", 32), (b"splat_strips", 8),
-                         (b"splat_strips", 2), (b"splat_zl2", 1), (b"splat_lds", 0), (b"splat_kslot", 1), (b"splat_kslot", 2), (b"splat_bins", 0)):
+        for key, val in ((b"splat_seeds", 0), (b"splat_cells_sub", 32), (b"splat_strips", 8),
+                         (b"splat_strips", 2), (b"splat_lds", 0), (b"splat_bins", 0)):
             _lib.check(L.read_tuning_set(key, val))
             for k in (1, 2, 5):
                 M = camera.total_matrix(proj, poses[k])
@@ -321,10 +319,10 @@ def test_cell_ordered_passes_are_exact_for_hard_cameras(hip):
                 for l in range(5):
                     assert np.array_equal(idx[l][0].cpu().numpy(), oi[l]), f"{key} {val} pose {k} level {l}"
                     assert np.array_equal(dep[l][0].cpu().numpy().view(np.uint32), od[l].view(np.uint32))
-            for k_, v_ in ((b"splat_items", 4), (b"splat_seeds", 1), (b"splat_cells_sub", 0), (b"splat_strips", 1), (b"splat_zl2", 0), (b"splat_lds", 1), (b"splat_kslot", 0), (b"splat_bins", 1)):
+            for k_, v_ in ((b"splat_seeds", 1), (b"splat_cells_sub", 0), (b"splat_strips", 1), (b"splat_lds", 1), (b"splat_bins", 1)):
                 _lib.check(L.read_tuning_set(k_, v_))
     finally:
-        for k_, v_ in ((b"splat_items", 4), (b"splat_seeds", 1), (b"splat_cells_sub", 0), (b"splat_strips", 1), (b"splat_zl2", 0), (b"splat_lds", 1), (b"splat_kslot", 0), (b"splat_bins", 1)):
+        for k_, v_ in ((b"splat_seeds", 1), (b"splat_cells_sub", 0), (b"splat_strips", 1), (b"splat_lds", 1), (b"splat_bins", 1)):
             _lib.check(L.read_tuning_set(k_, v_))
     # large world coordinates: the same cloud and camera moved 5 km away (projection rounding grows ~100x)
     off = np.array([5000.0, -3000.0, 4000.0], np.float32)

@@ -167,7 +167,7 @@ def test_rasteriser_pass_a_keeps_five_waves_per_simd(tmp_path_factory):
     of dependent round trips is the number of resident waves (profiles/r5_pass_a_pipe_ab.md) — 512 registers / 5 waves = 102, the
     allocation granule is 8."""
     asm = _asm("splat.hip", tmp_path_factory)
-    name, body = _function(asm, "cells_pass_kernelILb0ELb0ELb0ELb1ELb1E")
+    name, body = _function(asm, "cells_pass_kernelILb0ELb0ELb1ELb1E")
     assert _meta(asm, name, "private_seg_size") == 0, "scratch in pass A"
     assert _meta(asm, name, "num_vgpr") + _meta(asm, name, "num_agpr") <= 96, "pass A no longer fits five waves per SIMD"
     assert "global_atomic_add" in body and "ds_write" in body           # the bin reservation and the candidate queue are in this kernel

@@ -14,19 +14,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from read_amd import _lib, camera, synthetic          # noqa: E402
 from read_amd.raster import PointCloudRasterizer      # noqa: E402
 
-DEFAULTS = {"splat_mode": 7, "splat_cells": 1, "splat_seeds": 1, "splat_near": 12, "splat_cells_sub": 0, "splat_items": 4,
-            "splat_subset": 8, "splat_strips": 1, "splat_zl2": 0, "splat_wgs": 4, "splat_lds": 1, "splat_kslot": 0}
+DEFAULTS = {"splat_mode": 7, "splat_cells": 1, "splat_seeds": 1, "splat_near": 12, "splat_cells_sub": 0,
+            "splat_subset": 8, "splat_strips": 1, "splat_wgs": 4, "splat_lds": 1}
 VARIANTS = [
     ("default: striped cell-ordered passes, zimg early-z, warm start", {}),
     ("no LDS table in front of the atomics", {"splat_lds": 0}),
     ("8 workgroups per CU", {"splat_wgs": 8}),
-    ("scattered key image", {"splat_kslot": 2}),
-    ("early-z loads from L2 (sc1)", {"splat_zl2": 1}),
     ("4 strips", {"splat_strips": 4}),
     ("2 strips", {"splat_strips": 2}),
     ("8 strips (XCD affinity of the bound image)", {"splat_strips": 8}),
-    ("items per chunk 2", {"splat_items": 2}),
-    ("items per chunk 1", {"splat_items": 1}),
     ("near split 6 points/pixel", {"splat_near": 6}),
     ("near split 24 points/pixel", {"splat_near": 24}),
     ("near split 48 points/pixel", {"splat_near": 48}),
