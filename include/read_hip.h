@@ -52,8 +52,8 @@ int read_abi_version(void);
 /* Fills name[0..len) with the gfx arch of the current device ("gfx950"); READ_EHIP without a GPU. */
 int read_device_arch(char *name, int len);
 
-/* Measurement knobs (A/B runs on the GPU box).  Every knob of the release library selects between implementations
- * that produce the SAME results (the attribution probes with invalid results exist only in -DREAD_DEBUG_KNOBS builds):
+/* Measurement knobs (A/B runs on the GPU box).  Every knob selects between implementations that produce the SAME results, in
+ * every build of the library (-DREAD_DEBUG_KNOBS adds entry points, no key):
  *   "splat_mode"      plain path: 7 (default) warm start + LDS hierarchical-Z, 1 = agent-scope atomics + early-z only
  *   "splat_cells"     0: ignore the cell-ordered copy (plain path everywhere)
  *   "splat_seeds"     0: no warm start from the previous frame

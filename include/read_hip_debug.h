@@ -1,6 +1,7 @@
 /* read_hip_debug.h — entry points of the DEBUG build of the library only (libreadhip_debug.so: python -m read_amd.build --debug,
  * -DREAD_DEBUG_KNOBS).  Measurement probes and the kernel timeline used by tools/ (issue_probe.py, operand_probe.py,
- * mfma_probe.py, trace_conv.py); none of them is exported by libreadhip.so, the product. */
+ * mfma_probe.py, trace_conv.py); none of them is exported by libreadhip.so, the product.  The debug build adds these entry points
+ * and nothing else: the same tuning keys, the same kernels, no kernel variant whose results are invalid. */
 #ifndef READ_HIP_DEBUG_H
 #define READ_HIP_DEBUG_H
 #include "read_hip.h"

@@ -2,8 +2,8 @@
 
     python -m read_amd.build [--force] [--debug]
 
---debug builds read_amd/libreadhip_debug.so with -DREAD_DEBUG_KNOBS: the same library plus the attribution probes whose results
-are invalid (read_tuning_set "conv_ablate", "conv_abl").  Only tools/ load it (READ_HIP_DEBUG=1); it is never the product.
+--debug builds read_amd/libreadhip_debug.so with -DREAD_DEBUG_KNOBS: the same library plus the entry points of read_hip_debug.h
+(the measurement probes of csrc/probe.hip and the conv kernels' timeline).  Only tools/ load it (READ_HIP_DEBUG=1); it is never the product.
 
 hipcc cross-compiles without a GPU; the resulting read_amd/libreadhip.so travels with the
 tree to the GPU box (it is git-ignored, never pip-installed).

@@ -56,9 +56,8 @@ extern "C" int read_debug_set_trace(void *buf, size_t bytes)
 }
 #endif
 
-// Tuning knobs for A/B measurements on the GPU box (not needed in production).  Every knob of the release library
-// selects between implementations that produce the SAME results; the attribution probes whose results are invalid
-// ("conv_ablate") exist only in builds with -DREAD_DEBUG_KNOBS.
+// Tuning knobs for A/B measurements on the GPU box (not needed in production).  Every knob selects between implementations
+// that produce the SAME results, in the release library and in builds with -DREAD_DEBUG_KNOBS alike.
 // Each module keeps its keys in one table (internal.h); read_tuning_key enumerates the tables in the order of k_key.
 namespace readhip {
 static const TuneRow *find_row(const TuneRow *rows, int n, const char *key)
@@ -91,9 +90,7 @@ const char *tune_key(const TuneRow *rows, int n, int i) { return i >= 0 && i < n
 
 static int (*const k_set[])(const char *, int) = {splat_set, unet_set, conv_set, train_set};
 static int (*const k_get[])(const char *, int *) = {splat_get, unet_get, conv_get, train_get};
-// read_tuning_key: the splat keys, the unet keys, the release rows of the conv table, "wgrad_wino", then the conv table's debug-only rows
-static const char *(*const k_key[])(int) = {splat_key, unet_key, [](int i) { return conv_key(i, false); }, train_key,
-                                            [](int i) { return conv_key(i, true); }};
+static const char *(*const k_key[])(int) = {splat_key, unet_key, conv_key, train_key};
 }  // namespace readhip
 
 extern "C" int read_tuning_set(const char *key, int value)

@@ -19,6 +19,8 @@
 // B[k=l>>5][j=l&31]; D[i][j] sits in lane (j + 32*((i>>2)&1)), register (i&3) + 4*(i>>3).
 // A k-step of 8 is four MFMAs fed from ONE float4 per operand: lanes <32 carry cin 0..3 of the
 // 8-block, lanes >=32 carry cin 4..7 (the k order inside a step is free as long as A and B agree).
+#include <limits.h>
+
 #include "common.h"
 #include "internal.h"
 
@@ -53,8 +55,6 @@ struct ConvKArgs {
     int Cout, CoutPad, out_cstride;
     int nchunks, tiles_x, n_src;
     int tiles_y, n_units;          // wave-autonomous kernel: units = (group set, x tile, y tile)
-    int ablate;                    // debug ablation bits: 1 no epilogue loads/stores, 2 no A restaging, 4 B loads pinned to
-                                   //   step 0, 8 no MFMAs (results invalid; tools/ablate_conv.py)
     int stagger_ticks;             //   start delay (10 ns ticks) of waves in odd hardware slots: de-phases SIMD partners
     int n_full, col_split;         //   units [0,n_full) are P-row units of columns [0,col_split); the rest are
                                    //   1-row units of the remaining (group set, x tile) columns (balanced tail)
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void gated_conv_kernel(const ConvKArgs a)
     const int abase = ((wm * P) * S * TL::IW + (lane & 31) * S) * TL::PS + 4 * (lane >> 5);
 
     for (int chunk = 0; chunk < a.nchunks; ++chunk) {
-        const bool more = chunk + 1 < a.nchunks && !(a.ablate & 2);
+        const bool more = chunk + 1 < a.nchunks;
         if (more) gload();
         const float *buf = lds + (NBUF == 2 ? (chunk & 1) * TL::BUF : 0);
         const int step0 = chunk * SPC;
@@ -343,8 +343,7 @@ __global__ __launch_bounds__(256) void gated_conv_kernel(const ConvKArgs a)
                 const int opix = oy * a.outW + ox;
                 ooff[rr] = (in & c_st) ? (opix * a.out_cstride + c) * 4 : OOB;
                 const int roff = (in & c_ok) ? (opix * a.Cout + c) * 4 : OOB;
-                rv[rr] = (a.ablate & 1) ? 0.0f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, roff, 0, 0));
-                if ((a.ablate & 1) && !(in && oy == 0 && ox == 0)) ooff[rr] = OOB;      // one store per tile keeps the math live
+                rv[rr] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rrsrc, roff, 0, 0));
                 pf[rr] = pm[rr] = 0.0f;
                 if (a.pre) {
                     const int poff = (in & c_ok) ? (((oy >> a.pre_shift) * a.pre_W + (ox >> a.pre_shift)) * a.pre_cstride + c) * 4 : OOB;
@@ -1103,7 +1102,7 @@ struct Wino16sGeom {
     static constexpr int LDS_FLOATS = 2 * BUF + 3 * VBUF + 4;  // two raw buffers, three V buffers, a dummy float4 slot
 };
 
-template <bool MUL, int ABL = 0>
+template <bool MUL>
 __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKArgs a)
 {
     using WG = Wino16sGeom;
@@ -1292,7 +1291,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKA
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     const int m = fl * 8 + e * 2 + b;
-                    const float4 wv4 = Wq[(ABL & 2) ? 0 : (fl & 3)], vv4 = Bq[(ABL & 4) ? 0 : bs][(ABL & 4) ? 0 : b];
+                    const float4 wv4 = Wq[fl & 3], vv4 = Bq[bs][b];
                     const float we = e == 0 ? wv4.x : e == 1 ? wv4.y : e == 2 ? wv4.z : wv4.w;
                     const float ve = e == 0 ? vv4.x : e == 1 ? vv4.y : e == 2 ? vv4.z : vv4.w;
                     if (FIRST && e == 0) {
@@ -1302,15 +1301,15 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKA
                         acc[b][arow][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(we, ve, acc[b][arow][j], 0, 0, 0);
                     // ---- shadow items
                     const int mm = e * 2 + b;                                        // position inside this frequency's 8 MFMAs
-                    if (!(ABL & 4) && mm < 2) {                                      // B operands two frequencies ahead
+                    if (mm < 2) {                                                    // B operands two frequencies ahead
                         if (fl + 2 < 8) bload1((fl + 2) & 3, v_cur, fl + 2, mm);
                         else bload1((fl + 2) & 3, v_nxt, fl + 2 - 8, mm);           // next stage (stored before this stage's barrier)
                     }
-                    if (!(ABL & 2) && mm == 2) {                                     // weights three frequencies ahead
+                    if (mm == 2) {                                                   // weights three frequencies ahead
                         if (fl + 3 < 8) wload1((fl + 3) & 3, stage, fl + 3);
                         else wload1((fl + 3) & 3, nstage, fl + 3 - 8);
                     }
-                    if (!(ABL & 32)) {                                               // the next stage's share of B^T d B
+                    {                                                                // the next stage's share of B^T d B
                         // program order = step order (the steps recycle registers); every arithmetic step sits at least 8 MFMAs
                         // behind the LDS reads it consumes, everything is stored before the barrier at m = 39
                         constexpr int at[T_STEPS] = {2, 3, 4, 5, 12, 13, 14, 15, 15, 16, 16, 17, 23, 24, 24, 25, 26, 27, 28, 29};
@@ -1318,16 +1317,14 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKA
                         for (int k2 = 0; k2 < T_STEPS; ++k2)
                             if (at[k2] == m) t_step(traw, narow, v_nxt, k2);
                     }
-                    if (!(ABL & 8)) {
-                        if (P == 0 && m >= 28 && m - 28 < WG::NI) lwrite1(m - 28, raw_nxt);        // raw(chunk + 1): registers -> LDS
-                        if (P == 1 && m >= 50 && m - 50 < WG::NI) gload1(m - 50);                  // raw(chunk + 2) -> registers
-                    }
-                    if (m == 39 && !(ABL & 16)) __syncthreads();                     // V of the next stage (and raw(chunk + 1)) complete
+                    if (P == 0 && m >= 28 && m - 28 < WG::NI) lwrite1(m - 28, raw_nxt);            // raw(chunk + 1): registers -> LDS
+                    if (P == 1 && m >= 50 && m - 50 < WG::NI) gload1(m - 50);                      // raw(chunk + 2) -> registers
+                    if (m == 39) __syncthreads();                                    // V of the next stage (and raw(chunk + 1)) complete
                     __builtin_amdgcn_sched_barrier(0);
                 }
         }
         if (P == 1) {
-            if (!(ABL & 8)) st_ok = okmask;
+            st_ok = okmask;
             advance();
             const int o = raw_cur;
             raw_cur = raw_nxt;
@@ -1376,18 +1373,6 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKA
         for (int chunk = 1; chunk < n; ++chunk) {
             stage_body(std::false_type{}, std::integral_constant<int, 0>{}, chunk);
             stage_body(std::false_type{}, std::integral_constant<int, 1>{}, chunk);
-        }
-        if (ABL & 1) {                                                 // keep the accumulators live with one store per wave
-            f32x4 ssum = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int aa = 0; aa < 4; ++aa)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ssum += acc[b][aa][j];
-            if (ssum[0] + ssum[1] + ssum[2] + ssum[3] == 12345.678f) a.out[lane] = ssum[0];
-            step_tile(by, bx);
-            continue;
         }
         // ================= unit epilogue (lane-local) =================
         // D layout of v_mfma_f32_16x16x4_f32: lane (t = lane & 15, q = lane >> 4), register r = MFMA row 4q + r:
@@ -1539,13 +1524,10 @@ struct Wino4Geom {
     static constexpr int LDS_FLOATS = 2 * BUF + 2 * VBUF + 4;  // two raw buffers, two V buffers, a dummy float4 slot (128 KiB)
 };
 
-// ABL (attribution probes, results invalid; -DREAD_DEBUG_KNOBS builds only, read_tuning_set("conv_abl")): 1 no transform
-// arithmetic, 2 no transform LDS reads, 4 no transform LDS writes, 8 no raw-patch global loads, 16 no raw-patch LDS writes,
-// 32 weights loaded once, 64 B operands loaded once, 128 no epilogue, 256 no barrier
 // LIN: the training path's linear launches — 1: pre-activations + gated output (forward), 2: pre-activations only (dgrad) —
 // separate instantiations, so that every kernel's unit loop keeps ONE path through its epilogue (the waitcnt bookkeeping of hipcc merges every path at the loop
 // header: with the dgrad's early `continue` in the same function every unit started with s_waitcnt vmcnt(0))
-template <bool MUL, int ABL = 0, int LIN = 0>
+template <bool MUL, int LIN = 0>
 __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArgs a)
 {
     using WG = Wino4Geom;
@@ -1622,10 +1604,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
     // time of scalar ones beside the MFMAs (tools/issue_probe.py), so the transform is written for v_pk_*: 96 instructions instead
     // of 168 on the pipe the MFMAs run on.
     f32x2 d2[6][3];
-    if (ABL) {
-#pragma unroll
-        for (int i = 0; i < 18; ++i) d2[i / 3][i % 3] = f32x2{1.0f + tid, 2.0f + tid};
-    }
     // 1-D transform with B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]:
     // down the rows, two columns at a time: 14 packed operations
     auto bt6v = [](f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5) {
@@ -1663,20 +1641,18 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
     auto t_step = [&](const float *raw, int vb, int k) {
         if (k < 0) {
             const int e = k + 36, r = e / 6, c = e % 6;
-            if (!(ABL & 2)) d2[r][c >> 1][c & 1] = raw[rbase + (r * WG::IW + c) * WG::PS];
+            d2[r][c >> 1][c & 1] = raw[rbase + (r * WG::IW + c) * WG::PS];
         } else if (k < 21) {
             const int c = k - 18;
-            if (!(ABL & 1)) bt6v(d2[0][c], d2[1][c], d2[2][c], d2[3][c], d2[4][c], d2[5][c]);
+            bt6v(d2[0][c], d2[1][c], d2[2][c], d2[3][c], d2[4][c], d2[5][c]);
         } else if (k < 27) {
             const int r = k - 21;
-            if (!(ABL & 1)) bt6row(d2[r][0], d2[r][1], d2[r][2]);
+            bt6row(d2[r][0], d2[r][1], d2[r][2]);
         } else {
             const int r = (k - 27) / 3, j = (k - 27) % 3;             // pair j of row r holds frequencies (0, 5), (1, 2), (3, 4) of that row
             const int f0 = r * 6 + (j == 0 ? 0 : j == 1 ? 1 : 3), f1 = r * 6 + (j == 0 ? 5 : j == 1 ? 2 : 4);
-            if (!(ABL & 4)) {
-                lds[vwoff + vb + f0 * 256] = d2[r][j].x;
-                lds[vwoff + vb + f1 * 256] = d2[r][j].y;
-            }
+            lds[vwoff + vb + f0 * 256] = d2[r][j].x;
+            lds[vwoff + vb + f1 * 256] = d2[r][j].y;
         }
     };
     constexpr int T_FIRST = -36, T_STEPS = 45;
@@ -1689,7 +1665,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
     const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(wbase), 0, (unsigned)n * (36 * 1024), 0x00020000);
     const unsigned wvoff = lane * 16;
     float4 Wq[12];
-    constexpr int WLEAD = (ABL & 512) ? 6 : 10;                // frequencies ahead (probe 512: the sensitivity to that distance)
+    constexpr int WLEAD = 10;                                  // frequencies ahead
     auto wload1 = [&](int slot, int chunk, int fq) {
         Wq[slot] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, (chunk * 36 + fq) * 1024, 0));
     };
@@ -1761,8 +1737,8 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
                         acc[fq] = __builtin_amdgcn_mfma_f32_16x16x4f32(we, ve, acc[fq], 0, 0, 0);
                     // ---- shadow items
                     const int mm = e * 2 + sidx;                                     // position inside this pair's 8 MFMAs
-                    if (!(ABL & 64) && mm < 2 && 2 * pr + 4 + mm < 36) bload1((2 * pr + 4 + mm) % 6, v_cur, 2 * pr + 4 + mm);   // B operands 4 ahead
-                    if (!(ABL & 32) && (mm == 2 || mm == 6)) {                       // weights 10 frequencies ahead
+                    if (mm < 2 && 2 * pr + 4 + mm < 36) bload1((2 * pr + 4 + mm) % 6, v_cur, 2 * pr + 4 + mm);   // B operands 4 ahead
+                    if (mm == 2 || mm == 6) {                                        // weights 10 frequencies ahead
                         const int wf = 2 * pr + WLEAD + (mm == 6);
                         if (wf < 36) wload1(wf % 12, chunk, wf);
                         else wload1(wf % 12, nchunk, wf - 36);
@@ -1771,18 +1747,16 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
                     if (m < 36) t_step(traw, v_nxt, m - 36);
                     if (m >= 44 && m < 53) t_step(traw, v_nxt, 18 + (m - 44));
                     if (m >= 58 && m < 94 && !(m & 1)) t_step(traw, v_nxt, 27 + ((m - 58) >> 1));
-                    if (!(ABL & 16) && m >= 96 && m - 96 < WG::NI) lwrite1(m - 96, raw_cur);        // raw(chunk + 2): registers -> LDS
-                    if (!(ABL & 8) && m >= 104 && m - 104 < WG::NI) gload1(m - 104);               // raw(chunk + 3) -> registers
+                    if (m >= 96 && m - 96 < WG::NI) lwrite1(m - 96, raw_cur);        // raw(chunk + 2): registers -> LDS
+                    if (m >= 104 && m - 104 < WG::NI) gload1(m - 104);               // raw(chunk + 3) -> registers
                     // The stage's barrier, eight MFMAs BEFORE its end: V(chunk + 1) and raw(chunk + 2) are complete in every
                     // wave (last LDS write at m = 101), every wave has fetched its last B operand of this chunk (m = 121), and
                     // the first B operands of the next chunk travel under the remaining MFMAs (frequencies 34, 35: ring slots
                     // 4, 5) instead of behind the barrier
                     if (m == BAR_M) {
-                        if (!(ABL & 256)) __syncthreads();
-                        if (!(ABL & 64)) {
+                        __syncthreads();
 #pragma unroll
-                            for (int j = 0; j < 4; ++j) bload1(j, v_nxt, j);
-                        }
+                        for (int j = 0; j < 4; ++j) bload1(j, v_nxt, j);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -1806,15 +1780,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
         const int cq = (lane >> 4) & 1, hf = lane >> 5;
         const int c0 = g * 32 + wv * 8 + 4 * cq;
         const int oy = by * 8 + 4 * (t16 >> 3) + 2 * hf, ox = bx * 32 + 4 * (t16 & 7);           // this lane finishes rows oy, oy + 1
-        if (ABL & 128) {                                               // keep the accumulators live with one store per lane
-            f32x4 sum = acc[0];
-#pragma unroll
-            for (int i = 1; i < 36; ++i) sum += acc[i];
-            if (oy < a.outH && ox < a.outW) *reinterpret_cast<f32x4 *>(a.out + ((size_t)oy * a.outW + ox) * a.out_cstride + c0) = sum;
-            step_tile(by, bx);
-            __builtin_amdgcn_s_setprio(0);
-            continue;
-        }
         const f32x4 bf = *reinterpret_cast<const f32x4 *>(a.params + c0);
         const f32x4 bm = *reinterpret_cast<const f32x4 *>(a.params + a.CoutPad + c0);
         const f32x4 sc = *reinterpret_cast<const f32x4 *>(a.params + 2 * a.CoutPad + c0);
@@ -1935,14 +1900,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
         step_tile(by, bx);
         __builtin_amdgcn_s_setprio(0);
     }
-    if (ABL && a.nchunks == -12345) {                                  // never true: keeps the probes' dead values alive
-        float sink = 0.f;
-#pragma unroll
-        for (int i = 0; i < 18; ++i) sink += d2[i / 3][i % 3].x + d2[i / 3][i % 3].y;
-#pragma unroll
-        for (int i = 0; i < WG::NI; ++i) sink += st[i].x + st[i].y + st[i].z + st[i].w;
-        a.out[tid] = sink;
-    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1989,11 +1946,6 @@ struct Wino4hGeom {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-// ABL (attribution probes, results invalid; -DREAD_DEBUG_KNOBS builds only, read_tuning_set("conv_abl")): 1 no transform arithmetic,
-// 2 no split arithmetic, 4 no V stores, 8 no patch loads, 32 weights loaded once, 64 B operands loaded once, 128 no epilogue,
-// 256 no barrier, 512 no 2^-11 Uh products, 1024 no MFMAs, 2048 / 4096 patch / weight loads from one cache-resident address,
-// epilogue: 8192 no residual loads, 16384 one store instead of eight, 32768 no exp / rcp, 65536 no output transform
-template <int ABL = 0>
 __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKArgs a)
 {
     using WG = Wino4hGeom;
@@ -2058,11 +2010,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
     };
     f32x2 d2[6][6];                                            // the patch of the chunk under transform: (channel 2 cp, 2 cp + 1)
     auto gload = [&](int r, int c) {
-        if (ABL & 8) return;
-        if (ABL & 2048) {                                      // every patch load from the tensor's first 128 bytes: the instruction without its miss
-            d2[r][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, cp * 8u, 0, 0));
-            return;
-        }
         d2[r][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, xoff[c], rowoff[r] + pchunk * 128, 0));
     };
     // 1-D transform with B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1] on six
@@ -2083,22 +2030,11 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
     auto split_store = [&](const f32x2 x, int vb, int fq) {
         unsigned hi, lo;
         float r0, r1;
-        if (ABL & 2) {
-            if (!(ABL & 4)) {
-                lds[vwoff + vb + fq * WG::VFREQ] = __builtin_bit_cast(unsigned, x.x);
-                lds[vwoff + vb + fq * WG::VFREQ + 256] = __builtin_bit_cast(unsigned, x.y);
-            }
-            return;
-        }
         asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x.x), "v"(x.y));
         asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x.x));                    // x - f32(hi), exact
         asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x.y));
         const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
         asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
-        if (ABL & 4) {
-            asm volatile("" :: "v"(hi), "v"(lo));
-            return;
-        }
         lds[vwoff + vb + fq * WG::VFREQ] = hi;
         lds[vwoff + vb + fq * WG::VFREQ + 256] = lo;
     };
@@ -2111,12 +2047,11 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
 #pragma unroll
                 for (int r = 0; r < 6; ++r) d2[r][k] = d2[r][k] * f32x2{rmask_d[r], rmask_d[r]};
             }
-            if (!(ABL & 1)) bt6(d2[0][k], d2[1][k], d2[2][k], d2[3][k], d2[4][k], d2[5][k]);
+            bt6(d2[0][k], d2[1][k], d2[2][k], d2[3][k], d2[4][k], d2[5][k]);
         } else {
             const int r = (k - 6) / 7, j = (k - 6) % 7;
-            if (j == 0) {
-                if (!(ABL & 1)) bt6(d2[r][0], d2[r][1], d2[r][2], d2[r][3], d2[r][4], d2[r][5]);
-            }
+            if (j == 0)
+                bt6(d2[r][0], d2[r][1], d2[r][2], d2[r][3], d2[r][4], d2[r][5]);
             else {
                 split_store(d2[r][j - 1], vb, r * 6 + j - 1);
                 if (j == 6 && reload) {
@@ -2135,11 +2070,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
     u32x4 Wh[RW], Wl[RW];
     f16x8 Ws[4];                                               // 2^-11 Uh, one frequency pair ahead
     auto wload = [&](int slot, int chunk, int fq) {
-        if (ABL & 4096) {                                      // every weight load from one 2 KiB fragment: the instruction without its L2 traffic
-            Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, 0, 0);
-            Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, 1024, 0);
-            return;
-        }
         Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, (chunk * 36 + fq) * 2048, 0);
         Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, (chunk * 36 + fq) * 2048 + 1024, 0);
     };
@@ -2205,17 +2135,14 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
 #pragma unroll
             for (int j = 0; j < 6; ++j) {
                 const int fq = 2 * pr + (j & 1), pc = j >> 1, m = pr * 6 + j;
-                if (m == BAR_M && !(ABL & 256)) {
+                if (m == BAR_M) {
                     // V(chunk + 1) is complete in every wave (last store at slot 94) and every wave has fetched its last B
                     // operand of this chunk (slot 97); the first B operands of the next chunk travel under the last six MFMAs
                     __syncthreads();
                 }
                 const f16x8 av = pc == 0 ? Ws[fq % 4] : __builtin_bit_cast(f16x8, pc == 1 ? Wl[fq % RW] : Wh[fq % RW]);
                 const f16x8 bv = __builtin_bit_cast(f16x8, pc == 0 ? Bl[fq % RB] : Bh[fq % RB]);
-                if (ABL & 1024) {
-                    if (FIRST && pc == 0) acc[fq] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (pc == 2) asm volatile("" :: "v"(av), "v"(bv));
-                } else if (FIRST && pc == 0) {
+                if (FIRST && pc == 0) {
                     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                     acc[fq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, zero, 0, 0, 0);
                 } else
@@ -2223,15 +2150,13 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
                 // ---- shadow items
                 if (j < 2) {                                                         // B operands one frequency pair ahead
                     const int bf = 2 * pr + 2 + j;
-                    if (ABL & 64) {
-                    } else if (bf < 36) bload(bf % RB, v_cur, bf);
+                    if (bf < 36) bload(bf % RB, v_cur, bf);
                     else bload(bf % RB, v_nxt, bf - 36);
                 } else if (j < 4) {                                                  // weights WLEAD frequencies ahead
                     const int wf = 2 * pr + WLEAD + (j - 2);
-                    if (ABL & 32) {
-                    } else if (wf < 36) wload(wf % RW, chunk, wf);
+                    if (wf < 36) wload(wf % RW, chunk, wf);
                     else wload(wf % RW, nchunk, wf - 36);
-                } else if (!(ABL & 512))
+                } else
                     wscale((2 * pr + 2 + (j - 4)) % 36);                              // 2^-11 Uh of the next frequency pair
                 if (!(m & 1) && (m >> 1) < T_STEPS) t_step(v_nxt, m >> 1, true);
                 __builtin_amdgcn_sched_barrier(0);
@@ -2251,15 +2176,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
         const int cq = (lane >> 4) & 1, hf = lane >> 5;
         const int c0 = g * 32 + wv * 8 + 4 * cq;
         const int oy = by * 8 + 4 * (t16 >> 3) + 2 * hf, ox = bx * 32 + 4 * (t16 & 7);           // this lane finishes rows oy, oy + 1
-        if (ABL & 128) {                                               // keep the accumulators live with one store per lane
-            f32x4 sum = acc[0];
-#pragma unroll
-            for (int i = 1; i < 36; ++i) sum += acc[i];
-            if (oy < a.outH && ox < a.outW) *reinterpret_cast<f32x4 *>(a.out + ((size_t)oy * a.outW + ox) * a.out_cstride + c0) = sum;
-            step_tile(by, bx);
-            __builtin_amdgcn_s_setprio(0);
-            continue;
-        }
         const int cl = wv * 8 + 4 * cq;
         const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
         const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
@@ -2281,14 +2197,11 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
                 rv[py][px] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (a.residual && !(ABL & 8192))
+                if (a.residual)
                     rv[py][px] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvoff[py][px], 0, 0));
             }
         f32x4 Y[4][4];
-        if (ABL & 65536) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) Y[i >> 2][i & 3] = acc[i] + acc[16 + i] + acc[20 + i];
-        } else {
+        {
             f32x4 R[4][6];
 #pragma unroll
             for (int nu = 0; nu < 6; ++nu) {
@@ -2334,32 +2247,22 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
                     const f32x4 fe = f * LOG2E;
                     f32x4 e;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) e[k] = (ABL & 32768) ? fe[k] * 0.5f : __builtin_amdgcn_exp2f(fe[k]);
+                    for (int k = 0; k < 4; ++k) e[k] = __builtin_amdgcn_exp2f(fe[k]);
                     e = e + f32x4{-1.0f, -1.0f, -1.0f, -1.0f};
 #pragma unroll
                     for (int k = 0; k < 4; ++k) f[k] = f[k] > 0.0f ? f[k] : e[k];
                 }
                 f32x4 sg, t;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) t[k] = (ABL & 32768) ? mm[k] * 0.25f : __builtin_amdgcn_exp2f(mm[k]);
+                for (int k = 0; k < 4; ++k) t[k] = __builtin_amdgcn_exp2f(mm[k]);
                 t = t + f32x4{1.0f, 1.0f, 1.0f, 1.0f};
 #pragma unroll
-                for (int k = 0; k < 4; ++k) sg[k] = (ABL & 32768) ? t[k] * 0.125f : __builtin_amdgcn_rcpf(t[k]);
+                for (int k = 0; k < 4; ++k) sg[k] = __builtin_amdgcn_rcpf(t[k]);
                 const f32x4 v = (f * sg) * sc + sh + rv[py][px];
-                if ((ABL & 16384) && (py | px)) {
-                    asm volatile("" :: "v"(v));
-                    continue;
-                }
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[py][px], 0, 0);
             }
         step_tile(by, bx);
         __builtin_amdgcn_s_setprio(0);
-    }
-    if (ABL && a.nchunks == -12345) {                                  // never true: keeps the probes' dead values alive
-        float sink = 0.f;
-#pragma unroll
-        for (int i = 0; i < 36; ++i) sink += d2[i / 6][i % 6].x + d2[i / 6][i % 6].y;
-        a.out[tid] = sink;
     }
 }
 
@@ -2732,9 +2635,7 @@ struct D3hGeom {
     static constexpr int NE = NPIX * 8, NI = (NE + 511) / 512; // float4 of a patch chunk: 2720 -> 6 per thread?  (8 float4 per pixel)
 };
 
-// ABL (attribution probes, results invalid; debug library): 1 no patch staging, 2 weights loaded once, 4 B operands read once, 8 no epilogue,
-// 16 no barrier, 32 no 2^-11 wh products
-template <bool MUL, int ABL = 0>
+template <bool MUL>
 __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs a)
 {
     using DG = D3hGeom;
@@ -2964,14 +2865,14 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
             for (int pb = 0; pb < 4; ++pb) {
                 const int m = tap * 4 + pb, cur = m & 1;
                 // ---- loads for later: B operands of the next block (the first block of the next stage waits for the barrier)
-                if (m + 1 < 36 && !(ABL & 4)) bload(cur ^ 1, x_cur, (m + 1) >> 2, (m + 1) & 3);
-                if (pb == 0 && !(ABL & 2)) {                                            // weights two taps ahead
+                if (m + 1 < 36) bload(cur ^ 1, x_cur, (m + 1) >> 2, (m + 1) & 3);
+                if (pb == 0) {                                                          // weights two taps ahead
                     if (tap + 2 < 9) wload((tap + 2) % 3, chunk, tap + 2);
                     else wload((tap + 2) % 3, nchunk, tap + 2 - 9);
                 }
                 // the next chunk's patch: registers -> pieces -> the other buffer, one float4 per block from tap 2 on
-                if (m >= 8 && m - 8 < DG::NI && !(ABL & 1)) lwrite1(m - 8, x_nxt);
-                if (pb == 3 && tap < 8 && !(ABL & 32)) ascale(tap + 1);                 // its wh arrived a tap ago (slot (tap + 1) % 3)
+                if (m >= 8 && m - 8 < DG::NI) lwrite1(m - 8, x_nxt);
+                if (pb == 3 && tap < 8) ascale(tap + 1);                                // its wh arrived a tap ago (slot (tap + 1) % 3)
                 const f16x8 bh = __builtin_bit_cast(f16x8, Bh[cur]), bl = __builtin_bit_cast(f16x8, Bl[cur]);
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb) acc[rb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(As[tap & 1][rb], bl, acc[rb][pb], 0, 0, 0);
@@ -2984,27 +2885,21 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (!(ABL & 32)) ascale(0);                             // tap 0 of the next stage (nine taps: the parity ring restarts)
+        ascale(0);                                              // tap 0 of the next stage (nine taps: the parity ring restarts)
         advance();
-        if (!(ABL & 1)) gload();                                // the patch after next: a whole stage to land
-        if (!(ABL & 16)) __syncthreads();                       // X[x_nxt] complete, X[x_cur] free
+        gload();                                                // the patch after next: a whole stage to land
+        __syncthreads();                                        // X[x_nxt] complete, X[x_cur] free
         const int t_ = x_cur;
         x_cur = x_nxt;
         x_nxt = t_;
-        if (!(ABL & 4)) bload(0, x_cur, 0, 0);                  // first block of the next stage (the last stage of all reads a valid buffer)
+        bload(0, x_cur, 0, 0);                                  // first block of the next stage (the last stage of all reads a valid buffer)
     };
 
     for (int u = blockIdx.x; u < a.n_units; u += G) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i >> 2][i & 3] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int chunk = 0; chunk < n; ++chunk) stage(chunk);
-        if (ABL & 8) {
-            f32x4 sum = acc[0][0];
-#pragma unroll
-            for (int i = 1; i < 8; ++i) sum += acc[i >> 2][i & 3];
-            if (sum[0] == 12345.678f) a.out[tid] = sum[1] + sum[2] + sum[3];
-        } else
-            epilogue();
+        epilogue();
         step_tile(by, bx);
     }
 }
@@ -3026,9 +2921,8 @@ struct D3hS2Geom {
     static constexpr int NE = NPIX * 8, NI = (NE + 511) / 512; // 4488 / 4896 float4 of a patch chunk: 9 / 10 per thread
 };
 
-// ABL: as gated_conv_d3h_kernel
 // KS = 4: the decoder's 4 x 4 / stride-2 layers (pad 1): sixteen taps, the same four planes (row / column offsets 0, 1)
-template <int KS = 3, int ABL = 0>
+template <int KS = 3>
 __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKArgs a)
 {
     using DG = D3hS2Geom<KS>;
@@ -3258,14 +3152,14 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
             for (int pb = 0; pb < 4; ++pb) {
                 const int m = tap * 4 + pb, cur = m & 1;
                 // ---- loads for later: B operands of the next block (the first block of the next stage waits for the barrier)
-                if (m + 1 < 4 * NT && !(ABL & 4)) bload(cur ^ 1, x_cur, (m + 1) >> 2, (m + 1) & 3);
-                if (pb == 0 && !(ABL & 2)) {                                            // weights two taps ahead
+                if (m + 1 < 4 * NT) bload(cur ^ 1, x_cur, (m + 1) >> 2, (m + 1) & 3);
+                if (pb == 0) {                                                          // weights two taps ahead
                     if (tap + 2 < NT) wload((tap + 2) % RING, chunk, tap + 2);
                     else wload((tap + 2) % RING, nchunk, tap + 2 - NT);
                 }
                 // the next chunk's patch: registers -> pieces -> the other buffer, one float4 per block from tap 2 on
-                if (m >= 8 && m - 8 < DG::NI && !(ABL & 1)) lwrite1(m - 8, x_nxt);
-                if (pb == 3 && tap < NT - 1 && !(ABL & 32)) ascale(tap + 1);                 // its wh arrived a tap ago (slot (tap + 1) % 3)
+                if (m >= 8 && m - 8 < DG::NI) lwrite1(m - 8, x_nxt);
+                if (pb == 3 && tap < NT - 1) ascale(tap + 1);                           // its wh arrived a tap ago (slot (tap + 1) % 3)
                 const f16x8 bh = __builtin_bit_cast(f16x8, Bh[cur]), bl = __builtin_bit_cast(f16x8, Bl[cur]);
 #pragma unroll
                 for (int rb = 0; rb < 2; ++rb) acc[rb][pb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(As[tap & 1][rb], bl, acc[rb][pb], 0, 0, 0);
@@ -3278,14 +3172,14 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        if (!(ABL & 32)) ascale(0);                             // tap 0 of the next stage (nine taps: the parity ring restarts)
+        ascale(0);                                              // tap 0 of the next stage (nine taps: the parity ring restarts)
         advance();
-        if (!(ABL & 1)) gload();                                // the patch after next: a whole stage to land
-        if (!(ABL & 16)) __syncthreads();                       // X[x_nxt] complete, X[x_cur] free
+        gload();                                                // the patch after next: a whole stage to land
+        __syncthreads();                                        // X[x_nxt] complete, X[x_cur] free
         const int t_ = x_cur;
         x_cur = x_nxt;
         x_nxt = t_;
-        if (!(ABL & 4)) bload(0, x_cur, 0, 0);                  // first block of the next stage (the last stage of all reads a valid buffer)
+        bload(0, x_cur, 0, 0);                                  // first block of the next stage (the last stage of all reads a valid buffer)
     };
 
     // a layer with an odd number of 32-channel groups (feat_extract.4: 64 -> 32): the waves of the pair's missing half stage patches and
@@ -3310,727 +3204,10 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i >> 2][i & 3] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int chunk = 0; chunk < n; ++chunk) stage(chunk);
-        if (ABL & 8) {
-            f32x4 sum = acc[0][0];
-#pragma unroll
-            for (int i = 1; i < 8; ++i) sum += acc[i >> 2][i & 3];
-            if (sum[0] == 12345.678f) a.out[tid] = sum[1] + sum[2] + sum[3];
-        } else
-            epilogue();
+        epilogue();
         step_tile(by, bx);
     }
 }
-
-
-// ------------------------------------------------------------------------------------------
-// NEGATIVE RESULT, kept in the DEBUG library only (-DREAD_DEBUG_KNOBS, read_tuning_set("conv_w4h_waves", 8)): the split-operand
-// kernel above cut into SPECIALISED waves — eight per workgroup, two per SIMD: waves 0..3 multiply (MFMA stream, weight ring,
-// B operands, epilogue), waves 4..7 produce (patch loads, input transform, split, V stores).  Same arithmetic, operands, LDS layout
-// and unit walk; results bit-identical to the four-wave kernel (tests/test_gpu_conv.py runs both when the debug library is loaded).
-// Why it was tried (profiles/r6_w4h_ablation.md): in the four-wave kernel the MFMAs alone take 9 us of a 44 us launch at C = 256 and
-// everything else ADDS to them — a wave alone on its SIMD issues in order, its loads return in order (a weight fragment requested
-// behind a patch load waits for that load's miss), the transform's 350 vector instructions sit between its MFMAs.  Two waves with
-// different jobs on a SIMD overlap by construction and have separate vmcnt.
-// MEASURED (round 6, tools/w4h_ab.py): 65.6 / 70.3 / 54.7 / 48.5 us per launch at C = 32 / 64 / 128 / 256 against 59.8 / 52.9 / 47.4 / 44.2
-// for the four-wave kernel — SLOWER at every level.  The probes say why: the multiplying waves ALONE (producers switched off) take
-// 35.5 us at C = 256.  At two waves per SIMD a wave has 256 registers; 144 are accumulators, which leaves a six-frequency weight
-// ring fetched four ahead: 8 KiB in flight per wave, 32 KiB per CU, and an L2 hit under this load takes ~0.5 us — the weight stream
-// (288 KiB per 32 input channels and unit) then runs at 65 GB/s per CU = 4.4 us per stage, where the four-wave kernel (nine-frequency
-// ring, six ahead, 48 KiB in flight per CU) is not weight-bound.  Specialisation trades the issue serialisation for a shallower
-// prefetch, and on this machine the prefetch depth is worth more.  It is therefore not part of libreadhip.so.
-// ------------------------------------------------------------------------------------------
-#ifdef READ_DEBUG_KNOBS
-template <int ABL = 0>
-__global__ __launch_bounds__(512, 1) void gated_conv_wino4h2_kernel(const ConvKArgs a)
-{
-    using WG = Wino4hGeom;
-    __shared__ __attribute__((aligned(16))) unsigned lds[WG::LDS_DWORDS];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const SrcDev s = a.src[0];
-    const int groups = a.CoutPad >> 5, G = gridDim.x;
-    const int g = blockIdx.x % groups;
-    const int n = a.nchunks;                                   // 32-channel chunks
-    constexpr unsigned OOR = 0x80000000u;
-    constexpr int BAR_M = 102;                                 // multiplying waves: the stage's barrier in front of frequency pair 17
-
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
-
-    if (wv >= 4) {
-        // =============================== producing waves: patch -> registers -> B^T d B -> f16 pieces -> V ===============================
-        const int tw = wv - 4;
-        const int cp = lane & 15, tl = tw * 4 + (lane >> 4);
-        int pby = (blockIdx.x / groups) / a.tiles_x, pbx = (blockIdx.x / groups) % a.tiles_x, pu = blockIdx.x, pchunk = 0;
-        unsigned xoff[6];
-        int rowoff[6];
-        float rmask[6], rmask_d[6];
-        bool rclamp = false, rclamp_d = false;
-        const unsigned src_bytes = (unsigned)(a.inH * s.W * s.C) * 4u;
-        const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s.p), 0, src_bytes, 0x00020000);
-        auto set_patch = [&]() {
-            const int y0 = pby * 8 + 4 * (tw >> 1) - 1, x0 = pbx * 32 + 4 * (tl & 7) - 1;
-            rclamp = false;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-                const int yy = y0 + r;
-                const bool ok = (unsigned)yy < (unsigned)a.inH;
-                const int yc = yy < 0 ? 0 : yy >= a.inH ? a.inH - 1 : yy;
-                rowoff[r] = yc * s.W * s.C * 4;
-                rmask[r] = ok ? 1.0f : 0.0f;
-                rclamp = rclamp || !ok;
-            }
-#pragma unroll
-            for (int c = 0; c < 6; ++c) xoff[c] = (unsigned)(x0 + c) < (unsigned)a.inW ? (unsigned)((x0 + c) * s.C + 2 * cp) * 4u : OOR;
-        };
-        auto advance = [&]() {
-#pragma unroll
-            for (int r = 0; r < 6; ++r) rmask_d[r] = rmask[r];
-            rclamp_d = rclamp;
-            if (++pchunk == n) {
-                pchunk = 0;
-                if (pu + G < a.n_units) {
-                    pu += G;
-                    step_tile(pby, pbx);
-                }
-                set_patch();
-            }
-        };
-        f32x2 d2[6][6];
-        auto gload_all = [&]() {
-            if (ABL & 8) return;
-#pragma unroll
-            for (int r = 0; r < 6; ++r)
-#pragma unroll
-                for (int c = 0; c < 6; ++c) {
-                    d2[r][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, xoff[c], rowoff[r] + pchunk * 128, 0));
-                }
-        };
-        auto bt6 = [](f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5) {
-            const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2), f = pk_sub(x3, x1), h = pk_sub(x4, x2);
-            const f32x2 y0 = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
-            const f32x2 y5 = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
-            x0 = y0;
-            x1 = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
-            x2 = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
-            x3 = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
-            x4 = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
-            x5 = y5;
-        };
-        const int vwoff = tl * 16 + (((cp >> 2) ^ ((-tw) & 3)) << 2) + (cp & 3);
-        auto split_store = [&](const f32x2 x, int vb, int fq) {
-            unsigned hi, lo;
-            float r0, r1;
-            asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x.x), "v"(x.y));
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x.x));
-            asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x.y));
-            const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
-            asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
-            lds[vwoff + vb + fq * WG::VFREQ] = hi;
-            lds[vwoff + vb + fq * WG::VFREQ + 256] = lo;
-        };
-        auto transform = [&](int vb) {
-            if (ABL & 1) return;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                if (rclamp_d) {
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) d2[r][c] = d2[r][c] * f32x2{rmask_d[r], rmask_d[r]};
-                }
-                bt6(d2[0][c], d2[1][c], d2[2][c], d2[3][c], d2[4][c], d2[5][c]);
-            }
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-                bt6(d2[r][0], d2[r][1], d2[r][2], d2[r][3], d2[r][4], d2[r][5]);
-#pragma unroll
-                for (int c = 0; c < 6; ++c) split_store(d2[r][c], vb, r * 6 + c);
-            }
-        };
-        // prologue: patch(0) -> V(0); patch(1) on its way
-        set_patch();
-        gload_all();
-        advance();
-        transform(0);
-        gload_all();
-        advance();
-        __syncthreads();                                       // P: V(0) complete
-        int v_nxt = WG::VBUF;
-        for (int u = blockIdx.x; u < a.n_units; u += G)
-            for (int chunk = 0; chunk < n; ++chunk) {
-                transform(v_nxt);                              // chunk + 1 (of this or of the next unit) -> the other buffer
-                gload_all();                                   // chunk + 2: a whole stage to land
-                advance();
-                v_nxt = WG::VBUF - v_nxt;
-                if (!(ABL & 256)) __syncthreads();             // S: V(chunk + 1) complete; V(chunk) free
-            }
-        return;
-    }
-
-    // =============================== multiplying waves ===============================
-    int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;
-    const char *const wbase = reinterpret_cast<const char *>(a.wp_w4h) + ((size_t)(g * 4 + wv) * n) * (36 * 2048);
-    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(wbase), 0, (unsigned)n * (36 * 2048), 0x00020000);
-    const unsigned wvoff = lane * 16;
-    constexpr int RW = 6, WLEAD = 4;                           // ring of six frequencies, fetched four ahead
-    u32x4 Wh[RW], Wl[RW];
-    f16x8 Ws[2];                                               // 2^-11 Uh of the next frequency pair
-    auto wload = [&](int slot, int chunk, int fq) {
-        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, (chunk * 36 + fq) * 2048, 0);
-        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, (chunk * 36 + fq) * 2048 + 1024, 0);
-    };
-    auto wscale = [&](int fq) {
-        const _Float16 k = (_Float16)0x1p-11f;
-        Ws[fq % 2] = __builtin_bit_cast(f16x8, Wh[fq % RW]) * f16x8{k, k, k, k, k, k, k, k};
-    };
-    const int t16 = lane & 15, kl = lane >> 4;
-    const int vrd = t16 * 16 + ((kl ^ ((-(t16 >> 2)) & 3)) << 2);
-    constexpr int RB = 4;
-    u32x4 Bh[RB], Bl[RB];
-    auto bload = [&](int slot, int vb, int fq) {
-        Bh[slot] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + vb + fq * WG::VFREQ + vrd, 16));
-        Bl[slot] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + vb + fq * WG::VFREQ + 256 + vrd, 16));
-    };
-    f32x4 acc[36];
-    const auto out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)(a.outH * a.outW * a.out_cstride) * 4u, 0x00020000);
-    const auto res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.residual ? a.residual : a.out), 0,
-                                                            (unsigned)(a.outH * a.outW * a.Cout) * 4u, 0x00020000);
-    const float *const wsc = reinterpret_cast<const float *>(a.wp_w4h) + (size_t)n * 2304 * a.CoutPad;
-    int v_cur = 0, v_nxt = WG::VBUF;
-
-    // One stage = one 32-channel chunk = 108 MFMAs.  LAST: the unit's last chunk — nothing of the next unit is prefetched (its
-    // rings would have to live through the epilogue: no registers for that at two waves per SIMD)
-    auto stage_body = [&](auto first_tag, auto last_tag, int chunk) {
-        constexpr bool FIRST = decltype(first_tag)::value, LAST = decltype(last_tag)::value;
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int pr = 0; pr < 18; ++pr)
-#pragma unroll
-            for (int j = 0; j < 6; ++j) {
-                const int fq = 2 * pr + (j & 1), pc = j >> 1, m = pr * 6 + j;
-                if (m == BAR_M && !(ABL & 256)) __syncthreads();
-                const f16x8 av = pc == 0 ? Ws[fq % 2] : __builtin_bit_cast(f16x8, pc == 1 ? Wl[fq % RW] : Wh[fq % RW]);
-                const f16x8 bv = __builtin_bit_cast(f16x8, pc == 0 ? Bl[fq % RB] : Bh[fq % RB]);
-                if (ABL & 1024) {
-                    if (FIRST && pc == 0) acc[fq] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (pc == 2) asm volatile("" :: "v"(av), "v"(bv));
-                } else if (FIRST && pc == 0) {
-                    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                    acc[fq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, zero, 0, 0, 0);
-                } else
-                    acc[fq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[fq], 0, 0, 0);
-                if (j < 2) {                                                         // B operands one frequency pair ahead
-                    const int bf = 2 * pr + 2 + j;
-                    if (bf < 36) bload(bf % RB, v_cur, bf);
-                    else if (!LAST) bload(bf % RB, v_nxt, bf - 36);
-                } else if (j < 4) {                                                  // weights WLEAD frequencies ahead
-                    const int wf = 2 * pr + WLEAD + (j - 2);
-                    if (wf < 36) wload(wf % RW, chunk, wf);
-                    else if (!LAST) wload(wf % RW, chunk + 1, wf - 36);
-                } else {                                                             // 2^-11 Uh of the next frequency pair
-                    const int sf = 2 * pr + 2 + (j - 4);
-                    if (sf < 36 || !LAST) wscale(sf % 36);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        const int v = v_cur;
-        v_cur = v_nxt;
-        v_nxt = v;
-    };
-
-    __syncthreads();                                           // P
-    for (int u = blockIdx.x; u < a.n_units; u += G) {
-        // prime the rings (first unit: behind the prologue barrier; later units: behind the epilogue)
-#pragma unroll
-        for (int j = 0; j < WLEAD; ++j) wload(j, 0, j);
-        bload(0, v_cur, 0);
-        bload(1, v_cur, 1);
-        wscale(0);
-        wscale(1);
-        if (n == 1) stage_body(std::true_type{}, std::true_type{}, 0);
-        else {
-            stage_body(std::true_type{}, std::false_type{}, 0);
-            for (int chunk = 1; chunk < n - 1; ++chunk) stage_body(std::false_type{}, std::false_type{}, chunk);
-            stage_body(std::false_type{}, std::true_type{}, n - 1);
-        }
-
-        // ================= unit epilogue: two tile rows (p, p + 2) at a time =================
-        __builtin_amdgcn_s_setprio(1);
-        const int cq = (lane >> 4) & 1, hf = lane >> 5;
-        const int c0 = g * 32 + wv * 8 + 4 * cq;
-        const int oy = by * 8 + 4 * (t16 >> 3) + 2 * hf, ox = bx * 32 + 4 * (t16 & 7);
-        if (ABL & 128) {
-            f32x4 sum = acc[0];
-#pragma unroll
-            for (int i = 1; i < 36; ++i) sum += acc[i];
-            if (oy < a.outH && ox < a.outW) *reinterpret_cast<f32x4 *>(a.out + ((size_t)oy * a.outW + ox) * a.out_cstride + c0) = sum;
-            step_tile(by, bx);
-            __builtin_amdgcn_s_setprio(0);
-            continue;
-        }
-        const f32x4 bf = *reinterpret_cast<const f32x4 *>(a.params + c0);
-        const f32x4 sc = *reinterpret_cast<const f32x4 *>(a.params + 2 * a.CoutPad + c0);
-        const f32x4 sh = *reinterpret_cast<const f32x4 *>(a.params + 3 * a.CoutPad + c0);
-        const f32x4 isf = *reinterpret_cast<const f32x4 *>(wsc + c0);
-        constexpr float LOG2E = 1.44269504088896341f;
-        const f32x4 ism = *reinterpret_cast<const f32x4 *>(wsc + a.CoutPad + c0) * -LOG2E;
-        const f32x4 bml = *reinterpret_cast<const f32x4 *>(a.params + a.CoutPad + c0) * -LOG2E;
-#pragma unroll
-        for (int py = 0; py < 2; ++py) {
-            unsigned rvoff[4], ovoff[4];
-            f32x4 rv[4];
-#pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                const bool in = (oy + py < a.outH) & (ox + px < a.outW) & (c0 < a.Cout);
-                const int pix = (oy + py) * a.outW + ox + px;
-                rvoff[px] = in ? (unsigned)((pix * a.Cout + c0) * 4) : OOR;
-                ovoff[px] = in ? (unsigned)((pix * a.out_cstride + c0) * 4) : OOR;
-                rv[px] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (a.residual) rv[px] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvoff[px], 0, 0));
-            }
-            // rows p = py and p + 2 of A^T M:  p = 0: a0 + s1 + s2 | p = 2: s1 + 4 s2   (s = sums of frequency rows 1,2 / 3,4)
-            //                                  p = 1: d1 + 2 d2    | p = 3: d1 + 8 d2 + a5  (d = differences)
-            f32x4 Ra[6], Rb[6];
-#pragma unroll
-            for (int nu = 0; nu < 6; ++nu) {
-                if (py == 0) {
-                    const f32x4 s1 = acc[6 + nu] + acc[12 + nu], s2 = acc[18 + nu] + acc[24 + nu];
-                    Ra[nu] = acc[nu] + s1 + s2;
-                    Rb[nu] = s1 + 4.0f * s2;
-                } else {
-                    const f32x4 d1 = pk_sub4(acc[6 + nu], acc[12 + nu]), dd2 = pk_sub4(acc[18 + nu], acc[24 + nu]);
-                    Ra[nu] = d1 + 2.0f * dd2;
-                    Rb[nu] = d1 + 8.0f * dd2 + acc[30 + nu];
-                }
-            }
-#pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                // column px of (A^T M) A for both rows
-                f32x4 ya, yb;
-                if (px == 0) {
-                    ya = Ra[0] + (Ra[1] + Ra[2]) + (Ra[3] + Ra[4]);
-                    yb = Rb[0] + (Rb[1] + Rb[2]) + (Rb[3] + Rb[4]);
-                } else if (px == 1) {
-                    ya = pk_sub4(Ra[1], Ra[2]) + 2.0f * pk_sub4(Ra[3], Ra[4]);
-                    yb = pk_sub4(Rb[1], Rb[2]) + 2.0f * pk_sub4(Rb[3], Rb[4]);
-                } else if (px == 2) {
-                    ya = (Ra[1] + Ra[2]) + 4.0f * (Ra[3] + Ra[4]);
-                    yb = (Rb[1] + Rb[2]) + 4.0f * (Rb[3] + Rb[4]);
-                } else {
-                    ya = pk_sub4(Ra[1], Ra[2]) + 8.0f * pk_sub4(Ra[3], Ra[4]) + Ra[5];
-                    yb = pk_sub4(Rb[1], Rb[2]) + 8.0f * pk_sub4(Rb[3], Rb[4]) + Rb[5];
-                }
-                // lanes 0..31 hold conv_f, lanes 32..63 conv_m: after the exchange the lower half-wave owns tile row py, the upper
-                // half row py + 2, f in one register and m in the other
-                u32x4 u0 = __builtin_bit_cast(u32x4, ya), u1 = __builtin_bit_cast(u32x4, yb);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                    u0[k] = sw[0];
-                    u1[k] = sw[1];
-                }
-                f32x4 f = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u0), isf, bf);
-                const f32x4 mm = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u1), ism, bml);
-                if (a.elu) {
-                    const f32x4 fe = f * LOG2E;
-                    f32x4 e;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) e[k] = __builtin_amdgcn_exp2f(fe[k]);
-                    e = e + f32x4{-1.0f, -1.0f, -1.0f, -1.0f};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) f[k] = f[k] > 0.0f ? f[k] : e[k];
-                }
-                f32x4 sg, t;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) t[k] = __builtin_amdgcn_exp2f(mm[k]);
-                t = t + f32x4{1.0f, 1.0f, 1.0f, 1.0f};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) sg[k] = __builtin_amdgcn_rcpf(t[k]);
-                const f32x4 v = (f * sg) * sc + sh + rv[px];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[px], 0, 0);
-            }
-        }
-        step_tile(by, bx);
-        __builtin_amdgcn_s_setprio(0);
-    }
-}
-
-#endif  // READ_DEBUG_KNOBS
-
-// ------------------------------------------------------------------------------------------
-// NEGATIVE RESULT, kept in the DEBUG library only (-DREAD_DEBUG_KNOBS, read_tuning_set("conv_w4x2", 1)): the F(4x4,3x3) kernel
-// above cut for TWO waves per SIMD.  Why it was tried (DESIGN.md 12.1 d): one wave per SIMD issues a vector instruction every
-// 5.2 cycles, two waves one every 2.6 (tools/valu_probe.py), and a VALU instruction behind an fp32 MFMA costs 4 - 11.5 cycles with
-// one wave per SIMD against 1.4 - 2.5 with two (tools/issue_probe.py).  The accumulators do not shrink with the tile (36
-// frequencies x a 16 x 16 MFMA block), so the cut is over FREQUENCIES: eight waves per workgroup, wave (co = w & 3, fh = w >> 2) owns
-// output channels 8 co .. 8 co + 7 and frequency rows 3 fh .. 3 fh + 2 of the 6 x 6 grid — 18 frequencies, 72 accumulators, the SAME
-// weight blob and the same V buffer; input transform by halves (each half reads the whole 6 x 6 patch), output transform by halves
-// with a hand-over of partial row sums between the wave pair through LDS (message counters, no workgroup barrier).
-// MEASURED in round 5 (profiles/r5_w4x2_ab.json, tools/w4x2_ab.py; results equal to the kernel above within 7e-6, parity test
-// green): 73.2 / 67.7 / 62.5 / 61.1 us per launch at C = 32 / 64 / 128 / 256 against 71.2 / 66.1 / 59.4 / 56.0 for the one-wave
-// kernel, 214.6 against 220.8 frames/s in bench.py — SLOWER at every level.  The reason is structural, not a tuning state: the
-// split halves the cost of a vector instruction and doubles their number (each wave still reads the whole 6 x 6 patch, runs its own
-// operand rings and address bookkeeping: ~345 non-MFMA instructions per 72 MFMAs and wave, i.e. 690 per SIMD and stage against ~300),
-// and the hand-over adds a dependent LDS round trip per unit.  It is therefore not part of libreadhip.so.
-// ------------------------------------------------------------------------------------------
-#ifdef READ_DEBUG_KNOBS
-__global__ __launch_bounds__(512, 1) void gated_conv_wino4x2_kernel(const ConvKArgs a)
-{
-    using WG = Wino4Geom;
-    constexpr int NI = (WG::NE + 511) / 512;                   // 1360 float4 of a raw chunk over 512 threads: 3 each
-    constexpr int XCH = WG::LDS_FLOATS, XW = 4 * 64 * 4;       // exchange area: 4 float4 slots x 64 lanes per wave (4 KiB)
-    __shared__ __attribute__((aligned(16))) float lds[WG::LDS_FLOATS + 8 * XW];
-    __shared__ int xflag[16];                                  // [w]: messages written by wave w; [8 + w]: messages of its partner wave w has read
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), co = wv & 3, fh = wv >> 2;
-    const SrcDev s = a.src[0];
-    const int groups = a.CoutPad >> 5, G = gridDim.x;
-    const int g = blockIdx.x % groups;
-    const int n = a.nchunks;
-    if (tid < 16) xflag[tid] = 0;
-
-    int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit (8 x 32 pixel block)
-    int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor (raw patches)
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
-    int loff[NI];
-    unsigned rel[NI], aoff[NI];
-    constexpr unsigned OOR = 0x80000000u;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-        const int e = tid + i * 512, q = e % 4, pix = e / 4;
-        loff[i] = e < WG::NE ? (pix / WG::IW) * WG::RS + (pix % WG::IW) * WG::PS + 4 * q : WG::KC;   // else: pixel 0's pad floats
-        rel[i] = (unsigned)(((pix / WG::IW) * s.W + pix % WG::IW) * s.C + 4 * q) * 4u;
-    }
-    const unsigned src_bytes = (unsigned)(a.inH * s.W * s.C) * 4u;
-    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s.p), 0, src_bytes, 0x00020000);
-    auto set_patch = [&]() {
-        const int y0 = pby * 8 - 1, x0 = pbx * 32 - 1;
-        const unsigned base = (unsigned)((y0 * s.W + x0) * s.C) * 4u;          // may wrap: only lanes inside the image use it
-#pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            const int e = tid + i * 512, pix = e / 4, ppy = pix / WG::IW, ppx = pix % WG::IW;
-            const bool ok = (e < WG::NE) & (ppy >= -y0) & (ppy < a.inH - y0) & (ppx >= -x0) & (ppx < a.inW - x0);
-            aoff[i] = ok ? base + rel[i] : OOR;
-        }
-    };
-    auto advance = [&]() {
-        if (++pchunk == n) {
-            pchunk = 0;
-            if (pu + G < a.n_units) {
-                pu += G;
-                step_tile(pby, pbx);
-            }
-            set_patch();
-        }
-    };
-    float4 st[NI];
-    auto gload1 = [&](int i) {
-        st[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, aoff[i], pchunk * (WG::KC * 4), 0));
-    };
-    auto lwrite1 = [&](int i, int obuf) {
-        *reinterpret_cast<float4 *>(__builtin_assume_aligned(lds + obuf + loff[i], 16)) = st[i];
-    };
-
-    // ---- transform role: thread = (input channel c16 of the chunk, tile tl, frequency-row half = fh of its wave)
-    const int c16 = tid & 15, tl = (tid >> 4) & 15;
-    const int rbase = ((4 * (tl >> 3)) * WG::IW + 4 * (tl & 7)) * WG::PS + c16;
-    const int vwoff = WG::V0 + tl * 16 + ((c16 >> 2) ^ ((tl >> 1) & 3)) * 4 + (c16 & 3);
-    f32x2 d2[6][3];                                            // the patch as column pairs; after the column step rows 0..2 hold B^T d rows 3 fh ..
-    // the half-specific arithmetic takes the half as a compile-time tag: the caller branches ONCE per stage (wave-uniform), so
-    // that no branch sits between the MFMAs
-    auto bt3v = [&](auto half, int c) {                        // rows 3 fh .. 3 fh + 2 of B^T applied down column pair c
-        const f32x2 x0 = d2[0][c], x1 = d2[1][c], x2 = d2[2][c], x3 = d2[3][c], x4 = d2[4][c], x5 = d2[5][c];
-        if constexpr (decltype(half)::value == 0) {
-            const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2);
-            d2[0][c] = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
-            d2[1][c] = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
-            d2[2][c] = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
-        } else {
-            const f32x2 f = pk_sub(x3, x1), h = pk_sub(x4, x2);
-            d2[0][c] = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
-            d2[1][c] = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
-            d2[2][c] = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
-        }
-    };
-    const f32x2 KA = {4.0f, -5.0f}, KB = {2.0f, 0.0f};
-    auto bt6row = [&](f32x2 &P0, f32x2 &P1, f32x2 &P2) {        // as in the kernel above: (x0,x1)(x2,x3)(x4,x5) -> (y0,y5)(y1,y2)(y3,y4)
-        f32x2 T, Y05, QU, PR, Y12, Y34, F2, H2;
-        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(T) : "v"(P0), "v"(KA), "v"(P2));
-        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(Y05) : "v"(P1), "v"(KA), "v"(T));
-        asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(QU) : "v"(P0), "v"(P1));
-        asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(PR) : "v"(P2), "v"(P1));
-        asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,1] neg_lo:[0,1] neg_hi:[1,0]" : "=v"(F2) : "v"(P1), "v"(P0));
-        asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(H2) : "v"(P2), "v"(P1));
-        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "=v"(Y12) : "v"(QU), "v"(KA), "v"(PR));
-        asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]" : "=v"(Y34) : "v"(F2), "v"(KB), "v"(H2));
-        P0 = Y05;
-        P1 = Y12;
-        P2 = Y34;
-    };
-    // step k of the next chunk's transform: -36..-1 reads, 18..20 column pairs, 21..23 rows, 24..32 stores (two each)
-    auto t_step = [&](auto half, const float *raw, int vb, int k) {
-        if (k < 0) {
-            const int e = k + 36, r = e / 6, c = e % 6;
-            d2[r][c >> 1][c & 1] = raw[rbase + (r * WG::IW + c) * WG::PS];
-        } else if (k < 21) {
-            bt3v(half, k - 18);
-        } else if (k < 24) {
-            const int r = k - 21;
-            bt6row(d2[r][0], d2[r][1], d2[r][2]);
-        } else {
-            const int r = (k - 24) / 3, j = (k - 24) % 3;             // pair j of local row r holds frequencies (0, 5), (1, 2), (3, 4) of row 3 fh + r
-            const int f0 = (3 * fh + r) * 6 + (j == 0 ? 0 : j == 1 ? 1 : 3), f1 = (3 * fh + r) * 6 + (j == 0 ? 5 : j == 1 ? 2 : 4);
-            lds[vwoff + vb + f0 * 256] = d2[r][j].x;
-            lds[vwoff + vb + f1 * 256] = d2[r][j].y;
-        }
-    };
-    constexpr int T_FIRST = -36, T_STEPS = 33;
-    constexpr int BAR_M = 63;                                  // MFMA slot of the per-stage barrier (of 72)
-
-    // ---- A operand: the same blob as the kernel above; this wave's half of its octet's fragments.  Ring of 6 (18 % 6 == 0: a
-    // frequency keeps its slot across chunks), fetched 4 ahead (a ring of 9 / 7 ahead spilled: 256 registers per wave at 2 waves per SIMD)
-    const float *const wbase = a.wp_w4 + ((size_t)(g * 4 + co) * n) * (36 * 256);
-    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(wbase), 0, (unsigned)n * (36 * 1024), 0x00020000);
-    const unsigned wvoff = lane * 16;
-    float4 Wq[6];
-    constexpr int WLEAD = 4;
-    auto wload1 = [&](int slot, int chunk, int fql) {
-        Wq[slot] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, (chunk * 36 + 18 * fh + fql) * 1024, 0));
-    };
-    // ---- B operand: Vbuf[frequency][tile t16][slot]; ring of 6, fetched 4 ahead
-    const int t16 = lane & 15, kl = lane >> 4;
-    const int vlane = t16 * 16 + 4 * (kl ^ ((t16 >> 1) & 3));
-    float4 Bq[6];
-    auto bload1 = [&](int slot, int vb, int fql) {
-        Bq[slot] = *reinterpret_cast<const float4 *>(__builtin_assume_aligned(lds + WG::V0 + vb + (18 * fh + fql) * 256 + vlane, 16));
-    };
-
-    f32x4 acc[18];
-    const auto out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)(a.outH * a.outW * a.out_cstride) * 4u, 0x00020000);
-    const auto res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.residual ? a.residual : a.out), 0,
-                                                            (unsigned)(a.outH * a.outW * a.Cout) * 4u, 0x00020000);
-
-    // ---- prologue: raw(0), raw(1) -> LDS, raw(2) -> registers, this half's V(0), the first weight fragments and B operands
-    set_patch();
-#pragma unroll
-    for (int i = 0; i < NI; ++i) gload1(i);
-#pragma unroll
-    for (int j = 0; j < WLEAD; ++j) wload1(j, 0, j);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) lwrite1(i, 0);
-    advance();
-#pragma unroll
-    for (int i = 0; i < NI; ++i) gload1(i);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) lwrite1(i, WG::BUF);
-    advance();
-#pragma unroll
-    for (int i = 0; i < NI; ++i) gload1(i);
-    advance();
-    __syncthreads();
-    if (fh == 0) {
-#pragma unroll
-        for (int k = T_FIRST; k < T_STEPS; ++k)
-            if (k < 0 || k >= 18) t_step(std::integral_constant<int, 0>{}, lds, 0, k);
-    } else {
-#pragma unroll
-        for (int k = T_FIRST; k < T_STEPS; ++k)
-            if (k < 0 || k >= 18) t_step(std::integral_constant<int, 1>{}, lds, 0, k);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; ++j) bload1(j, 0, j);
-
-    int raw_cur = 0, raw_nxt = WG::BUF;
-    int v_cur = 0, v_nxt = WG::VBUF;
-    int n_msg = 0;                                             // messages this wave has sent (two per unit)
-
-    auto stage_body = [&](auto first_tag, auto half, int chunk) {
-        constexpr bool FIRST = decltype(first_tag)::value;
-        int nchunk = chunk + 1;
-        nchunk = nchunk == n ? 0 : nchunk;
-        const float *traw = lds + raw_nxt;
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int pr = 0; pr < 9; ++pr)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int sidx = 0; sidx < 2; ++sidx) {
-                    const int fq = 2 * pr + sidx, m = pr * 8 + e * 2 + sidx;
-                    const float4 wv4 = Wq[fq % 6], vv4 = Bq[fq % 6];
-                    const float we = e == 0 ? wv4.x : e == 1 ? wv4.y : e == 2 ? wv4.z : wv4.w;
-                    const float ve = e == 0 ? vv4.x : e == 1 ? vv4.y : e == 2 ? vv4.z : vv4.w;
-                    if (FIRST && e == 0) {
-                        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                        acc[fq] = __builtin_amdgcn_mfma_f32_16x16x4f32(we, ve, zero, 0, 0, 0);
-                    } else
-                        acc[fq] = __builtin_amdgcn_mfma_f32_16x16x4f32(we, ve, acc[fq], 0, 0, 0);
-                    // ---- shadow items
-                    const int mm = e * 2 + sidx;
-                    if (mm < 2 && 2 * pr + 4 + mm < 18) bload1((2 * pr + 4 + mm) % 6, v_cur, 2 * pr + 4 + mm);       // B operands 4 ahead
-                    if (mm == 2 || mm == 6) {                                                                        // weights 4 frequencies ahead
-                        const int wf = 2 * pr + WLEAD + (mm == 6);
-                        if (wf < 18) wload1(wf % 6, chunk, wf);
-                        else wload1(wf % 6, nchunk, wf - 18);
-                    }
-                    if (m < 36) t_step(half, traw, v_nxt, m - 36);                                    // the next chunk's transform: reads ...
-                    if (m >= 38 && m < 44 && !(m & 1)) t_step(half, traw, v_nxt, 18 + ((m - 38) >> 1));   // ... column pairs ...
-                    if (m >= 44 && m < 50 && !(m & 1)) t_step(half, traw, v_nxt, 21 + ((m - 44) >> 1));   // ... rows ...
-                    if (m >= 50 && m < 59) t_step(half, traw, v_nxt, 24 + (m - 50));                  // ... stores
-                    if (m >= 59 && m - 59 < NI) lwrite1(m - 59, raw_cur);                        // raw(chunk + 2): registers -> LDS
-                    if (m > BAR_M && m - (BAR_M + 1) < NI) gload1(m - (BAR_M + 1));              // raw(chunk + 3) -> registers
-                    if (m == BAR_M) {                                                            // V(chunk + 1) and raw(chunk + 2) complete in every wave
-                        __syncthreads();
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) bload1(j, v_nxt, j);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-        advance();
-        const int o = raw_cur;
-        raw_cur = raw_nxt;
-        raw_nxt = o;
-        const int v = v_cur;
-        v_cur = v_nxt;
-        v_nxt = v;
-    };
-
-    float *const xme = lds + XCH + wv * XW + lane * 4;
-    const float *const xpa = lds + XCH + (wv ^ 4) * XW + lane * 4;
-    for (int u = blockIdx.x; u < a.n_units; u += G) {
-        if (fh == 0) {
-            stage_body(std::true_type{}, std::integral_constant<int, 0>{}, 0);
-            for (int chunk = 1; chunk < n; ++chunk) stage_body(std::false_type{}, std::integral_constant<int, 0>{}, chunk);
-        } else {
-            stage_body(std::true_type{}, std::integral_constant<int, 1>{}, 0);
-            for (int chunk = 1; chunk < n; ++chunk) stage_body(std::false_type{}, std::integral_constant<int, 1>{}, chunk);
-        }
-
-        // ================= unit epilogue =================
-        const int cq = (lane >> 4) & 1, hf = lane >> 5;
-        const int c0 = g * 32 + co * 8 + 4 * cq;
-        const int oy = by * 8 + 4 * (t16 >> 3) + 2 * fh + hf, ox = bx * 32 + 4 * (t16 & 7);     // this lane finishes ONE row of its tile
-        const f32x4 bf = *reinterpret_cast<const f32x4 *>(a.params + c0);
-        const f32x4 bm = *reinterpret_cast<const f32x4 *>(a.params + a.CoutPad + c0);
-        const f32x4 sc = *reinterpret_cast<const f32x4 *>(a.params + 2 * a.CoutPad + c0);
-        const f32x4 sh = *reinterpret_cast<const f32x4 *>(a.params + 3 * a.CoutPad + c0);
-        unsigned rvoff[4], ovoff[4];
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            const bool in = (oy < a.outH) & (ox + px < a.outW) & (c0 < a.Cout);
-            const int pix = oy * a.outW + ox + px;
-            rvoff[px] = in ? (unsigned)((pix * a.Cout + c0) * 4) : OOR;
-            ovoff[px] = in ? (unsigned)((pix * a.out_cstride + c0) * 4) : OOR;
-        }
-        f32x4 rv[4];
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-            rv[px] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (a.residual) rv[px] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvoff[px], 0, 0));
-        }
-        // column pass, local to a frequency row: T[r][q] from M[r][0..5] (acc[6 r + nu])
-        f32x4 T[3][4];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const f32x4 s1 = acc[6 * r + 1] + acc[6 * r + 2], d1 = pk_sub4(acc[6 * r + 1], acc[6 * r + 2]);
-            const f32x4 s2 = acc[6 * r + 3] + acc[6 * r + 4], dd = pk_sub4(acc[6 * r + 3], acc[6 * r + 4]);
-            T[r][0] = acc[6 * r] + s1 + s2;
-            T[r][1] = d1 + 2.0f * dd;
-            T[r][2] = s1 + 4.0f * s2;
-            T[r][3] = d1 + 8.0f * dd + acc[6 * r + 5];
-        }
-        // row pass, this half's three rows of A^T = [1 1 1 | 1 1 0; 0 1 -1 | 2 -2 0; 0 1 1 | 4 4 0; 0 1 -1 | 8 -8 1]: partial sums of
-        // all four output rows; `keep` = rows 2 fh, 2 fh + 1, `give` = the partner's rows
-        f32x4 keep[2][4], give[2][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (fh == 0) {
-                const f32x4 sm = T[1][q] + T[2][q], df = pk_sub4(T[1][q], T[2][q]);
-                keep[0][q] = T[0][q] + sm;
-                keep[1][q] = df;
-                give[0][q] = sm;
-                give[1][q] = df;
-            } else {
-                const f32x4 sm = T[0][q] + T[1][q], df = pk_sub4(T[0][q], T[1][q]);
-                give[0][q] = sm;
-                give[1][q] = 2.0f * df;
-                keep[0][q] = 4.0f * sm;
-                keep[1][q] = 8.0f * df + T[2][q];
-            }
-        }
-        // exchange with the partner wave, two rounds of four float4 per lane (columns 0, 1 then 2, 3)
-#pragma unroll
-        for (int round = 0; round < 2; ++round) {
-            const int seq = n_msg + round + 1;
-            while (__hip_atomic_load(&xflag[8 + (wv ^ 4)], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq - 1) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-            for (int o = 0; o < 2; ++o)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    *reinterpret_cast<f32x4 *>(__builtin_assume_aligned(xme + (o * 2 + j) * 256, 16)) = give[o][2 * round + j];
-            __hip_atomic_store(&xflag[wv], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            while (__hip_atomic_load(&xflag[wv ^ 4], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq) __builtin_amdgcn_s_sleep(1);
-#pragma unroll
-            for (int o = 0; o < 2; ++o)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    keep[o][2 * round + j] += *reinterpret_cast<const f32x4 *>(__builtin_assume_aligned(xpa + (o * 2 + j) * 256, 16));
-            __hip_atomic_store(&xflag[8 + wv], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        n_msg += 2;
-        __builtin_amdgcn_s_setprio(1);                          // only now: a wave polling its partner's counter must not outrank the partner on their SIMD
-        // lanes 0..31 hold conv_f, lanes 32..63 conv_m: exchange the two rows so that the lower half-wave owns row 2 fh and the upper
-        // half row 2 fh + 1, f in one register and m in the other
-        {
-            constexpr float LOG2E = 1.44269504088896341f;
-#pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                u32x4 u0 = __builtin_bit_cast(u32x4, keep[0][px]), u1 = __builtin_bit_cast(u32x4, keep[1][px]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                    u0[k] = sw[0];
-                    u1[k] = sw[1];
-                }
-                f32x4 f = __builtin_bit_cast(f32x4, u0) + bf;
-                const f32x4 mm = (__builtin_bit_cast(f32x4, u1) + bm) * -LOG2E;
-                if (a.elu) {
-                    const f32x4 fe = f * LOG2E;
-                    f32x4 e;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) e[k] = __builtin_amdgcn_exp2f(fe[k]);
-                    e = e + f32x4{-1.0f, -1.0f, -1.0f, -1.0f};
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) f[k] = f[k] > 0.0f ? f[k] : e[k];
-                }
-                f32x4 sg, t;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) t[k] = __builtin_amdgcn_exp2f(mm[k]);
-                t = t + f32x4{1.0f, 1.0f, 1.0f, 1.0f};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) sg[k] = __builtin_amdgcn_rcpf(t[k]);
-                const f32x4 v = (f * sg) * sc + sh + rv[px];
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[px], 0, 0);
-            }
-        }
-        step_tile(by, bx);
-        __builtin_amdgcn_s_setprio(0);
-    }
-}
-#endif  // READ_DEBUG_KNOBS
 
 // ------------------------------------------------------------------------------------------
 // 3x3 / stride-1 layers with at most FOUR output channels on the vector pipe (READ's output layer, feat_extract.5: 32 -> 3).
@@ -4418,14 +3595,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_pxh_kernel(const ConvKArgs 
     // XCD instead of once per group set (gridDim.x = per_set x gsets with per_set a multiple of 8)
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int gs = slot % gsets, wgi = (slot / gsets) * 8 + xcd;     // channel-group set of this workgroup; its index among the set's workgroups
-#if defined(PXH_ABL)                 // attribution probes (results invalid): 1 no epilogue memory traffic, 2 activation loads from one resident line per lane,
-    constexpr int abl = PXH_ABL;     //   4 no MFMAs, 16 no weight copy.  Compile-time in variant builds (tools/pxh_probe.py), run-time in the debug library
-#elif defined(READ_DEBUG_KNOBS)
-    const int abl = a.ablate;
-#else
-    constexpr int abl = 0;
-#endif
-    if (!(abl & 16)) {
+    {
         // the set's fragments: T consecutive 2 KiB blocks per k16 step.  Eight 16-byte loads per thread in flight, then their stores
         // (one load, one store at a time cost a memory round trip per KiB: 16 round trips for 64 KiB)
         const int NT = a.CoutPad >> 4;                               // 32-row tiles of the layer: (f, m) per group
@@ -4534,7 +3704,6 @@ __global__ __launch_bounds__(256, 2) void gated_conv_pxh_kernel(const ConvKArgs 
             for (int pt = 0; pt < PT; ++pt) {
                 const int sy = (ly[pt] << sl) >> sr, sx = (lx[pt] << sl) >> sr;
                 const float4 *q = reinterpret_cast<const float4 *>(p + (sy * sW + sx) * sC + coff);
-                if (abl & 2) q = reinterpret_cast<const float4 *>(p + lane * 8);
                 ring[slot][pt][0] = q[0];
                 ring[slot][pt][1] = q[1];
             }
@@ -4599,19 +3768,6 @@ __global__ __launch_bounds__(256, 2) void gated_conv_pxh_kernel(const ConvKArgs 
                     f16x8 as[T];
 #pragma unroll
                     for (int t = 0; t < T; ++t) as[t] = __builtin_bit_cast(f16x8, wh[t]) * f16x8{k11, k11, k11, k11, k11, k11, k11, k11};
-                    if (abl & 4) {
-#pragma unroll
-                        for (int pt = 0; pt < PT; ++pt)
-#pragma unroll
-                            for (int t = 0; t < T; ++t) {
-                                acc[pt][t][0] += __builtin_bit_cast(float, bl[pt][0] ^ bh[pt][1] ^ wl[t][0]);
-                                acc[pt][t][1] += __builtin_bit_cast(float, bl[pt][2] ^ bh[pt][3] ^ __builtin_bit_cast(u32x4, as[t])[1]);
-                                acc[pt][t][2] += __builtin_bit_cast(float, bl[pt][1] ^ bh[pt][0] ^ wh[t][2]);
-                                acc[pt][t][3] += __builtin_bit_cast(float, bl[pt][3] ^ bh[pt][2] ^ wh[t][3]);
-                            }
-                        load_step(e);
-                        continue;
-                    }
 #pragma unroll
                     for (int pt = 0; pt < PT; ++pt)
 #pragma unroll
@@ -4670,8 +3826,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_pxh_kernel(const ConvKArgs 
                         m += am[qd];
                     }
                     const bool ok = p_ok && c0 < a.Cout;
-                    float *op = a.out + (size_t)pc * a.out_cstride + (c0 < a.Cout ? c0 : 0);
-                    if (abl & 1) op = a.out + lane * 4;
+                    float *const op = a.out + (size_t)pc * a.out_cstride + (c0 < a.Cout ? c0 : 0);
                     if (a.linear) {
                         if (ok) {
                             *reinterpret_cast<f32x4 *>(op) = f;
@@ -4690,7 +3845,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_pxh_kernel(const ConvKArgs 
 #pragma unroll
                     for (int k = 0; k < 4; ++k) sg[k] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(mm[k]));
                     f32x4 v = (f * sg) * *reinterpret_cast<const f32x4 *>(&epar[2 * EP + cl]) + *reinterpret_cast<const f32x4 *>(&epar[3 * EP + cl]);
-                    if (quad_res) v += *reinterpret_cast<const f32x4 *>(a.residual + (abl & 1 ? (size_t)lane * 4 : (size_t)pc * a.Cout + cc));
+                    if (quad_res) v += *reinterpret_cast<const f32x4 *>(a.residual + (size_t)pc * a.Cout + cc);
                     if (ok) *reinterpret_cast<f32x4 *>(op) = v;
                 }
             }
@@ -4810,7 +3965,7 @@ enum ConvForce {
     CFG_F4X1 = -12,      // split-operand F(4,3) by rows
 };
 
-// Tuning knobs (the table g_knobs further down: key, normalisation, debug-only)
+// Tuning knobs (the table g_knobs further down: key, normalisation)
 int g_prefer_wave = 1;   // read_tuning_set("conv_wave", 0): workgroup-tiled kernels only
 int g_wino_wgs = 2;        // read_tuning_set("conv_wino_wgs", 1): one persistent Winograd workgroup per CU (A/B with frames in flight)
 int g_conv_px = 1;         // read_tuning_set("conv_px", v): pixel-lane kernel for 1x1 layers — 0 off; 1 / 2 where it measured faster
@@ -4838,12 +3993,6 @@ int g_sc = 8;              // read_tuning_set("conv_sc", 0): the output layer (C
 int g_w16 = 0;             // read_tuning_set("conv_w16", v): F(2x2,3x3) launches: 0 the row-per-wave kernel (default: measured equal or faster),
                            // 1 the wave-autonomous kernel with the shared input transform
 int g_stagger_ticks = 0;   // read_tuning_set("conv_stagger", ticks of 10 ns)
-int g_ablate = 0;          // read_tuning_set("conv_ablate", bits): attribution probe, results invalid; -DREAD_DEBUG_KNOBS builds only
-#ifdef READ_DEBUG_KNOBS
-int g_abl = 0;             // read_tuning_set("conv_abl", bits): attribution probes of the 16x16x4 Winograd kernels (results invalid); -DREAD_DEBUG_KNOBS builds only
-int g_w4x2 = 0;            // debug library only: read_tuning_set("conv_w4x2", 1) = the two-waves-per-SIMD F(4x4) kernel (measured slower, round 5)
-int g_w4h_waves = 4;       // debug library only: read_tuning_set("conv_w4h_waves", 8) = the split-operand kernel with specialised waves (measured slower, round 6)
-#endif
 
 int find_wave_config(int ks, int s, int kc, int P, int QG)
 {
@@ -5419,78 +4568,30 @@ namespace readhip {
 
 // ---- tuning knobs: one row per "conv_*" key.  read_tuning_set / read_tuning_get / read_tuning_key (api_common.cpp) go through
 // conv_set / conv_get / conv_key; the order of the rows is the order read_tuning_key enumerates them in.
-enum KnobNorm { KN_RAW, KN_NONNEG /* <0 -> 0 */, KN_BOOL /* != 0 */, KN_0_TO_4, KN_1_OR_2 /* <=1 -> 1, else 2 */, KN_4_OR_8 /* 4, else 8 */ };
-
-struct ConvKnob {
-    const char *key;
-    int *value;
-    KnobNorm norm;
-    bool debug_only;     // attribution probes (results invalid) and measured-slower kernels: rows of -DREAD_DEBUG_KNOBS builds only
+const TuneRow g_knobs[] = {
+    {"conv_kc32", &g_kc32, TN_RAW, 0, 0},
+    {"conv_px", &g_conv_px, TN_CLAMP, 0, 4},                 // pixel-lane kernel for 1x1 layers
+    {"conv_sc", &g_sc, TN_RAW, 0, 0},                        // vector-pipe kernel for Cout <= 4: 0 off; 8 / 16 / 32 = input channels per LDS phase
+    {"conv_wino_wgs", &g_wino_wgs, TN_CLAMP, 1, 2},          // persistent Winograd workgroups per CU
+    {"conv_wino", &g_use_wino, TN_RAW, 0, 0},                // largest Cin on the Winograd kernel (0 = off)
+    {"conv_w16", &g_w16, TN_FLAG, 0, 0},                     // wave-autonomous Winograd kernel (0 = row-per-wave)
+    {"conv_w4", &g_w4, TN_CLAMP, 0, INT_MAX},                // min Cin on the Winograd F(4x4,3x3) kernel (0 = off)
+    {"conv_w4h", &g_w4h, TN_CLAMP, 0, INT_MAX},              // min Cin on the split-operand F(4x4) kernel (f16 matrix cores; 0 = off)
+    {"conv_f4x1", &g_f4x1, TN_CLAMP, 0, INT_MAX},            // min Cin of that family's launches on the F(4,3)-by-rows kernel (0 = off)
+    {"conv_d3h", &g_d3h, TN_CLAMP, 0, INT_MAX},              // min Cin on the direct split-operand 3x3 kernel (f16 matrix cores; 0 = off)
+    {"conv_d3h_fam", &g_d3h_fam, TN_CLAMP, 0, INT_MAX},      // min Cin of FAM (x1 * x2) launches on the direct split-operand kernel (0 = off)
+    {"conv_d3h_s2", &g_d3h_s2, TN_CLAMP, 0, INT_MAX},        // min Cin of 3x3 / stride-2 layers on the direct split-operand kernel (0 = off)
+    {"conv_pxh", &g_pxh, TN_CLAMP, 0, INT_MAX},              // min Cin of 1x1 layers on the split-operand pixel-lane kernel (0 = off)
+    {"conv_t3h", &g_t3h, TN_CLAMP, 0, INT_MAX},              // max Cin of 3x3 layers on the split-operand implicit-GEMM kernel (0 = off)
+    {"conv_w4_grid", &g_w4_grid, TN_FLAG, 0, 0},             // F(4x4): equal units per workgroup
+    {"conv_stagger", &g_stagger_ticks, TN_CLAMP, 0, INT_MAX},
+    {"conv_wave", &g_prefer_wave, TN_FLAG, 0, 0},
 };
+constexpr int N_CONV_KNOBS = sizeof(g_knobs) / sizeof(g_knobs[0]);
 
-const ConvKnob g_knobs[] = {
-    {"conv_kc32", &g_kc32, KN_RAW, false},
-    {"conv_px", &g_conv_px, KN_0_TO_4, false},           // pixel-lane kernel for 1x1 layers
-    {"conv_sc", &g_sc, KN_RAW, false},                   // vector-pipe kernel for Cout <= 4: 0 off; 8 / 16 / 32 = input channels per LDS phase
-    {"conv_wino_wgs", &g_wino_wgs, KN_1_OR_2, false},    // persistent Winograd workgroups per CU
-    {"conv_wino", &g_use_wino, KN_RAW, false},           // largest Cin on the Winograd kernel (0 = off)
-    {"conv_w16", &g_w16, KN_BOOL, false},                // wave-autonomous Winograd kernel (0 = row-per-wave)
-    {"conv_w4", &g_w4, KN_NONNEG, false},                // min Cin on the Winograd F(4x4,3x3) kernel (0 = off)
-    {"conv_w4h", &g_w4h, KN_NONNEG, false},              // min Cin on the split-operand F(4x4) kernel (f16 matrix cores; 0 = off)
-    {"conv_f4x1", &g_f4x1, KN_NONNEG, false},            // min Cin of that family's launches on the F(4,3)-by-rows kernel (0 = off)
-    {"conv_d3h", &g_d3h, KN_NONNEG, false},              // min Cin on the direct split-operand 3x3 kernel (f16 matrix cores; 0 = off)
-    {"conv_d3h_fam", &g_d3h_fam, KN_NONNEG, false},      // min Cin of FAM (x1 * x2) launches on the direct split-operand kernel (0 = off)
-    {"conv_d3h_s2", &g_d3h_s2, KN_NONNEG, false},        // min Cin of 3x3 / stride-2 layers on the direct split-operand kernel (0 = off)
-    {"conv_pxh", &g_pxh, KN_NONNEG, false},              // min Cin of 1x1 layers on the split-operand pixel-lane kernel (0 = off)
-    {"conv_t3h", &g_t3h, KN_NONNEG, false},              // max Cin of 3x3 layers on the split-operand implicit-GEMM kernel (0 = off)
-    {"conv_w4_grid", &g_w4_grid, KN_BOOL, false},        // F(4x4): equal units per workgroup
-    {"conv_stagger", &g_stagger_ticks, KN_NONNEG, false},
-    {"conv_wave", &g_prefer_wave, KN_BOOL, false},
-#ifdef READ_DEBUG_KNOBS
-    {"conv_ablate", &g_ablate, KN_RAW, true},
-    {"conv_abl", &g_abl, KN_RAW, true},                  // probes of the 16x16x4 Winograd kernels
-    {"conv_w4x2", &g_w4x2, KN_BOOL, true},               // the two-waves-per-SIMD F(4x4) kernel (measured slower)
-    {"conv_w4h_waves", &g_w4h_waves, KN_4_OR_8, true},   // 8: specialised waves (measured slower); 4: the product kernel
-#endif
-};
-
-static const ConvKnob *find_knob(const char *key)
-{
-    for (const ConvKnob &k : g_knobs)
-        if (!strcmp(key, k.key)) return &k;
-    return nullptr;
-}
-
-int conv_set(const char *key, int v)
-{
-    const ConvKnob *k = find_knob(key);
-    if (!k) return 0;
-    switch (k->norm) {
-    case KN_RAW: break;
-    case KN_NONNEG: v = v < 0 ? 0 : v; break;
-    case KN_BOOL: v = v != 0; break;
-    case KN_0_TO_4: v = v < 0 ? 0 : v > 4 ? 4 : v; break;
-    case KN_1_OR_2: v = v <= 1 ? 1 : 2; break;
-    case KN_4_OR_8: v = v == 4 ? 4 : 8; break;
-    }
-    *k->value = v;
-    return 1;
-}
-
-int conv_get(const char *key, int *value)
-{
-    const ConvKnob *k = find_knob(key);
-    if (k) *value = *k->value;
-    return k != nullptr;
-}
-
-const char *conv_key(int i, bool debug_only)
-{
-    if (i < 0) return nullptr;
-    for (const ConvKnob &k : g_knobs)
-        if (k.debug_only == debug_only && i-- == 0) return k.key;
-    return nullptr;
-}
+int conv_set(const char *key, int v) { return tune_set(g_knobs, N_CONV_KNOBS, key, v); }
+int conv_get(const char *key, int *value) { return tune_get(g_knobs, N_CONV_KNOBS, key, value); }
+const char *conv_key(int i) { return tune_key(g_knobs, N_CONV_KNOBS, i); }
 
 static unsigned long long *g_trace = nullptr;
 static size_t g_trace_records = 0;
@@ -5806,7 +4907,6 @@ static int conv_prepare(const read_conv_desc *d, const void *wp_f4x1, ConvKArgs 
     a.out_cstride = d->out_cstride;
     a.elu = d->elu;
     a.linear = d->linear;
-    a.ablate = g_ablate;
     a.fill_pad = d->fill_pad;
     a.out_fill = d->out_fill;
 
@@ -5824,21 +4924,6 @@ static int conv_prepare(const read_conv_desc *d, const void *wp_f4x1, ConvKArgs 
                    "Cout %% 4 == 0, 16-byte aligned tensors, automatic config)");
     return READ_OK;
 }
-
-#ifdef READ_DEBUG_KNOBS
-// conv_abl: the attribution-probe variant ABL = g_abl of a kernel (results invalid), or `fn` where no such variant was built
-template <template <int> class K, int... ABL>
-static conv_fn abl_variant(conv_fn fn)
-{
-    ((g_abl == ABL ? (void)(fn = K<ABL>::fn()) : (void)0), ...);
-    return fn;
-}
-template <int N> struct AblW4 { static conv_fn fn() { return gated_conv_wino4_kernel<false, N>; } };
-template <int N> struct AblW4h { static conv_fn fn() { return gated_conv_wino4h_kernel<N>; } };
-template <int N> struct AblW4h2 { static conv_fn fn() { return gated_conv_wino4h2_kernel<N>; } };
-template <int N> struct AblD3h { static conv_fn fn() { return gated_conv_d3h_kernel<false, N>; } };
-template <int N> struct AblW16 { static conv_fn fn() { return gated_conv_wino16s_kernel<false, N>; } };
-#endif
 
 // at most four output channels, 3x3 / stride 1: the vector-pipe kernel
 static int launch_sc(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, hipStream_t stream)
@@ -6004,30 +5089,14 @@ static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvSha
         if (cap > n_cu) cap -= groups;
     }
     const int nwg = persistent_grid(a, groups, cap);
-    conv_fn fn = d->linear ? (d->out_gated ? gated_conv_wino4_kernel<false, 0, 1> : gated_conv_wino4_kernel<false, 0, 2>) : d->mul ? gated_conv_wino4_kernel<true> : gated_conv_wino4_kernel<false>;
+    conv_fn fn = d->linear ? (d->out_gated ? gated_conv_wino4_kernel<false, 1> : gated_conv_wino4_kernel<false, 2>) : d->mul ? gated_conv_wino4_kernel<true> : gated_conv_wino4_kernel<false>;
     unsigned threads = 256;
     if (d3h) {
         fn = d->mul ? gated_conv_d3h_kernel<true> : gated_conv_d3h_kernel<false>;
         threads = 512;
     } else if (f4x1) fn = gated_conv_f4x1h_kernel;
-    else if (w4h) fn = gated_conv_wino4h_kernel<>;
+    else if (w4h) fn = gated_conv_wino4h_kernel;
     READ_CHECK_ARG(!d->linear || !d->mul, "read_gated_conv_forward: linear launches take no multiplier");
-#ifdef READ_DEBUG_KNOBS
-    if (g_w4x2 && !d->linear && !d->mul) {   // negative result (see the kernel): eight waves per workgroup, frequencies split over wave pairs
-        fn = gated_conv_wino4x2_kernel;
-        threads = 512;
-    } else if (d3h) {
-        if (!d->mul) fn = abl_variant<AblD3h, 1, 2, 4, 8, 16, 32, 7, 63, 55>(fn);
-    } else if (w4h && !f4x1 && g_w4h_waves == 8) {
-        fn = abl_variant<AblW4h2, 1, 8, 9, 128, 256, 1024, 1033>(gated_conv_wino4h2_kernel<>);
-        threads = 512;
-    } else if (w4h && !f4x1) {
-        fn = abl_variant<AblW4h, 1, 2, 3, 4, 7, 8, 15, 32, 64, 128, 256, 512, 1024, 1007, 2047 - 1024, 544, 2048, 4096, 6144, 40, 8192, 16384, 24576,
-                         32768, 65536, 122880>(fn);
-    } else if (!w4h && !d->mul) {
-        fn = abl_variant<AblW4, 1, 7, 8, 24, 31, 32, 64, 128, 256, 511, 383, 512>(fn);
-    }
-#endif
     hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(threads), 0, stream, a);
     READ_CHECK_LAUNCH();
     return READ_OK;
@@ -6087,9 +5156,6 @@ static int launch_table(const read_conv_desc *d, ConvKArgs &a, const ConvShape &
     if (r.w16 && !a.trace) {
         READ_CHECK_ARG((uintptr_t)d->wpacked_w16 % 16 == 0, "read_gated_conv_forward: wpacked_w16 misaligned");
         fn = d->mul ? gated_conv_wino16s_kernel<true> : gated_conv_wino16s_kernel<false>;
-#ifdef READ_DEBUG_KNOBS
-        if (!d->mul) fn = abl_variant<AblW16, 1, 2, 4, 8, 16, 32, 63>(fn);
-#endif
     }
     hipLaunchKernelGGL(fn, grid, dim3(256), 0, stream, a);
     READ_CHECK_LAUNCH();

@@ -13,11 +13,6 @@ int device_cus();
 int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *wp_f4x1);
 // The public family number (read_conv_kernel_family) of the kernel this descriptor runs on under the current knobs.
 int conv_family(const read_conv_desc *d);
-// The "conv_*" tuning knobs, one table: 1 = key known (conv_set stores the normalised value), 0 = not a conv key of this build.
-int conv_set(const char *key, int value);
-int conv_get(const char *key, int *value);
-// i-th key of the table's release rows (debug_only = false) or of its -DREAD_DEBUG_KNOBS rows; NULL past the end
-const char *conv_key(int i, bool debug_only);
 void conv_set_trace(void *buf, size_t bytes);
 
 // One row of a module's table of tuning keys; the order of the rows is the order read_tuning_key enumerates them in.
@@ -39,13 +34,16 @@ int tune_set(const TuneRow *rows, int n, const char *key, int value);
 int tune_get(const TuneRow *rows, int n, const char *key, int *value);
 const char *tune_key(const TuneRow *rows, int n, int i);       // NULL past the end
 
-// splat.hip, unet.cpp, train.hip: the "splat_*" / "unet_*" / "wgrad_wino" keys, as conv_set / conv_get / conv_key above
+// splat.hip, unet.cpp, conv.hip, train.hip: the "splat_*" / "unet_*" / "conv_*" / "wgrad_wino" keys, each through tune_set / tune_get / tune_key
 int splat_set(const char *key, int value);
 int splat_get(const char *key, int *value);
 const char *splat_key(int i);
 int unet_set(const char *key, int value);
 int unet_get(const char *key, int *value);
 const char *unet_key(int i);
+int conv_set(const char *key, int value);
+int conv_get(const char *key, int *value);
+const char *conv_key(int i);
 int train_set(const char *key, int value);
 int train_get(const char *key, int *value);
 const char *train_key(int i);

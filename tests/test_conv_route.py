@@ -101,15 +101,14 @@ def test_launch_outcomes_match_the_parent(rec):
 def test_tuning_keys_and_normalisation_match_the_parent(rec):
     _defaults_guard()
     L = _lib.lib()
-    debug = bool(os.environ.get("READ_HIP_DEBUG"))
     keys = rc.tuning_keys(_lib)
-    assert keys == rec["tuning_keys"] + (list(rc.DEBUG_ONLY_KEYS) if debug else [])
+    assert keys == rec["tuning_keys"]
     assert rec["knob_values"] == list(rc.KNOB_VALUES)
     table = rc.knob_table(_lib)
-    assert {k: v for k, v in table.items() if k not in rc.DEBUG_ONLY_KEYS} == rec["knobs"]
+    assert table == rec["knobs"]
     assert rc.knob_table(_lib) == table                              # ... and the defaults came back
     v = C.c_int()
-    for key in ("conv_nope", "conv_", "") + (() if debug else rc.DEBUG_ONLY_KEYS):
+    for key in ("conv_nope", "conv_", "") + rc.RETIRED_KEYS:
         assert L.read_tuning_set(key.encode(), 1) == -22
         assert L.read_last_error().decode() == f"read_tuning_set: unknown key '{key}'"
         assert L.read_tuning_get(key.encode(), C.byref(v)) == -22

@@ -50,7 +50,7 @@ def conv_asm(tmp_path_factory):
 
 
 def test_f4_inference_kernels_keep_the_cross_unit_pipeline(conv_asm):
-    for variant in ("gated_conv_wino4_kernelILb0ELi0ELi0E", "gated_conv_wino4_kernelILb1ELi0ELi0E"):
+    for variant in ("gated_conv_wino4_kernelILb0ELi0EEEv", "gated_conv_wino4_kernelILb1ELi0EEEv"):
         name, body = _function(conv_asm, variant)
         assert _meta(conv_asm, name, "private_seg_size") == 0, "scratch in the F(4x4) kernel"
         assert _meta(conv_asm, name, "num_vgpr") == 256 and _meta(conv_asm, name, "num_agpr") >= 144
@@ -68,7 +68,7 @@ def test_split_operand_f4_kernel_keeps_its_registers_and_pipeline(conv_asm):
     scratch (a denser transform cadence once flipped hipcc's allocation to 256 + 22 registers and 1.4 KB of scratch: 720 us per
     launch instead of 60), 108 MFMAs per stage instance, the patch loads and both operand rings inside the stage, a unit loop
     that does not drain the memory pipeline — and the specialised-wave variant (measured slower) is not in the product."""
-    for variant in ("gated_conv_wino4h_kernelILi0E",):
+    for variant in ("gated_conv_wino4h_kernelENS",):
         name, body = _function(conv_asm, variant)
         assert _meta(conv_asm, name, "private_seg_size") == 0, "scratch in the split-operand F(4x4) kernel"
         assert _meta(conv_asm, name, "num_vgpr") == 256 and _meta(conv_asm, name, "num_agpr") >= 144
@@ -87,7 +87,7 @@ def test_direct_split_operand_kernel_fits_two_waves_per_simd(conv_asm):
     """gated_conv_d3h_kernel (round 6): eight waves per workgroup = two per SIMD, so at most 256 registers per wave, no scratch; 216 MFMAs
     per stage (9 taps x 4 pixel blocks x 2 row blocks x 3 piece pairs); the weight loads stay ahead of their use (hipcc sinks an
     unpinned load to its first use: the first version waited vmcnt(0) behind every tap's loads)."""
-    for variant in ("gated_conv_d3h_kernelILb0ELi0E", "gated_conv_d3h_kernelILb1ELi0E"):
+    for variant in ("gated_conv_d3h_kernelILb0EEEv", "gated_conv_d3h_kernelILb1EEEv"):
         name, body = _function(conv_asm, variant)
         assert _meta(conv_asm, name, "private_seg_size") == 0, "scratch in the direct split-operand kernel"
         assert _meta(conv_asm, name, "num_vgpr") + _meta(conv_asm, name, "num_agpr") <= 256
@@ -99,7 +99,7 @@ def test_direct_split_operand_kernel_fits_two_waves_per_simd(conv_asm):
 
 
 def test_training_kernels_count_their_loads(conv_asm, tmp_path_factory):
-    for variant in ("gated_conv_wino4_kernelILb0ELi0ELi1E", "gated_conv_wino4_kernelILb0ELi0ELi2E"):
+    for variant in ("gated_conv_wino4_kernelILb0ELi1EEEv", "gated_conv_wino4_kernelILb0ELi2EEEv"):
         name, body = _function(conv_asm, variant)
         lines = body.split("\n")
         head = "\n".join(lines[[i for i, l in enumerate(lines) if "Loop Header: Depth=1" in l][0]:][:12])
@@ -148,18 +148,36 @@ def test_winograd_wgrad_kernel_fits_two_waves_per_simd(train_asm):
 
 def test_two_waves_per_simd_f4_kernel_is_not_in_the_product(conv_asm):
     """Round 5 ran the frequency-split two-waves-per-SIMD F(4x4) kernel: results equal, 3-9 % slower at every level
-    (profiles/r5_w4x2_ab.json, DESIGN.md 12.1 d).  It lives on in the debug library only (-DREAD_DEBUG_KNOBS) as the record of
-    the experiment; the product's device code does not contain it and the release library does not know its knob."""
+    (profiles/r5_w4x2_ab.json, DESIGN.md 12.1 d).  The kernel was removed from the sources once the verdict was written down; the
+    product's device code does not contain it and no library knows its knob."""
     assert "gated_conv_wino4x2_kernel" not in conv_asm
     from read_amd import _lib
-    if not os.environ.get("READ_HIP_DEBUG"):
-        L = _lib.lib()
-        assert L.read_tuning_set(b"conv_w4x2", 1) != 0
-        keys, i = [], 0
-        while L.read_tuning_key(i):
-            keys.append(L.read_tuning_key(i).decode())
-            i += 1
-        assert "conv_w4x2" not in keys and "conv_w4" in keys
+    L = _lib.lib()
+    assert L.read_tuning_set(b"conv_w4x2", 1) != 0
+    keys, i = [], 0
+    while L.read_tuning_key(i):
+        keys.append(L.read_tuning_key(i).decode())
+        i += 1
+    assert "conv_w4x2" not in keys and "conv_w4" in keys
+
+
+def test_release_conv_kernels_are_instantiated_once_per_variant(conv_asm):
+    """The gated-conv kernels of the release library, counted in its assembly: every instantiation is one the dispatcher can launch,
+    and none carries a probe parameter (the attribution probes were template parameters once: each probe value was another copy of
+    the kernel).  The template arguments left are the variants the product runs: MUL, LIN, KS."""
+    names = re.findall(r"^(_Z\S*gated_conv_\w*kernel\S*):\s*;", conv_asm, flags=re.M)
+    per_kernel = {}
+    for n in names:
+        k = re.search(r"(gated_conv_\w*kernel)", n).group(1)
+        per_kernel.setdefault(k, []).append(n)
+    want = {"gated_conv_wino4_kernel": 4, "gated_conv_wino4h_kernel": 1, "gated_conv_d3h_kernel": 2, "gated_conv_d3h_s2_kernel": 2,
+            "gated_conv_wino16s_kernel": 2, "gated_conv_f4x1h_kernel": 1}
+    assert {k: len(per_kernel[k]) for k in want} == want
+    assert len(per_kernel) == 12 and len(names) == 91
+    args = {k: sorted(re.search(r"kernel(?:I(\w+?)E)?Ev?NS_", n).group(1) or "" for n in per_kernel[k]) for k in want}
+    assert args == {"gated_conv_wino4_kernel": ["Lb0ELi0E", "Lb0ELi1E", "Lb0ELi2E", "Lb1ELi0E"], "gated_conv_wino4h_kernel": [""],
+                    "gated_conv_d3h_kernel": ["Lb0E", "Lb1E"], "gated_conv_d3h_s2_kernel": ["Li3E", "Li4E"],
+                    "gated_conv_wino16s_kernel": ["Lb0E", "Lb1E"], "gated_conv_f4x1h_kernel": [""]}
 
 
 def test_rasteriser_pass_a_keeps_five_waves_per_simd(tmp_path_factory):

@@ -1,9 +1,8 @@
 """A/B of the Winograd kernels on the four dominant UNet shapes (run on the GPU box): "old" = F(2x2,3x3) row-per-wave kernel
 (32x32x2 MFMA, cross-wave LDS epilogue), "new" = F(2x2,3x3) wave-autonomous kernel with the shared input transform (16x16x4 MFMA,
-in-lane epilogue), "f4" = F(4x4,3x3).  --abl lists attribution variants of the f4 / new kernels (the -DREAD_DEBUG_KNOBS library:
-python -m read_amd.build --debug, then READ_HIP_DEBUG=1).
+in-lane epilogue), "f4" = F(4x4,3x3).
 
-    python tools/ab_wino.py [--iters 20] [--kernels old,new,f4] [--abl 1,7,24,...] [--tune key=value,...]
+    python tools/ab_wino.py [--iters 20] [--kernels old,new,f4] [--tune key=value,...]
 """
 import argparse
 import json
@@ -26,7 +25,6 @@ def main():
     ap.add_argument("--tune", default="")
     ap.add_argument("--out", default="gpurun_out/ab_wino.json")
     ap.add_argument("--kernels", default="old,new,f4")
-    ap.add_argument("--abl", default="", help="attribution probes of the f4 / new kernels (READ_HIP_DEBUG=1 library): comma list of bit sets")
     a = ap.parse_args()
     if a.tune:
         for kv in a.tune.split(","):
@@ -63,20 +61,6 @@ def main():
                    "frac_of_157.3": fl / gain / ms / 1e9 / 157.3}
             print(rec, flush=True)
             res.append(rec)
-            for bits in [int(v) for v in a.abl.split(",") if v] if name in ("f4", "new") else []:
-                _lib.check(_lib.lib().read_tuning_set(b"conv_abl", bits))
-                for _ in range(2):
-                    gated_conv(pk, [(x, 0)], elu=True, residual=r, config=cfg, out=out)
-                e0.record()
-                for _ in range(a.iters):
-                    gated_conv(pk, [(x, 0)], elu=True, residual=r, config=cfg, out=out)
-                e1.record()
-                e1.synchronize()
-                _lib.check(_lib.lib().read_tuning_set(b"conv_abl", 0))
-                rec = {"shape": label, "kernel": name, "abl": bits, "us": 1e3 * e0.elapsed_time(e1) / a.iters}
-                print(rec, flush=True)
-                res.append(rec)
-            gated_conv(pk, [(x, 0)], elu=True, residual=r, config=cfg, out=out)
         for other in ("new", "f4"):
             if "old" in outs and other in outs:
                 d = (outs["old"] - outs[other]).abs().max().item()

@@ -1,7 +1,6 @@
 """The 1x1 layers of the plan on the split-operand pixel-lane kernel (config -10) against the fp32 kernels' automatic choice
-(conv_pxh = 0), one launch at a time, us per launch and effective GB/s (input + output + addend + residual bytes) — and, with the
-debug library (READ_HIP_DEBUG=1), the kernel's attribution probes (read_tuning_set("conv_ablate", bits): 1 no epilogue memory
-traffic, 2 activation loads from one resident line per lane, 4 no MFMAs, 16 no weight copy; results invalid).  Run on the GPU box."""
+(conv_pxh = 0), one launch at a time, us per launch and effective GB/s (input + output + addend + residual bytes).  Run on the
+GPU box."""
 import json
 import os
 import sys
@@ -33,7 +32,6 @@ SHAPES = [
     ("SCM0.main.3 128->248 @L3", [(128, 0)], 248, 3, None, False),
     ("SCM0.conv 256->256 @L3 (8+248)", [(8, 0), (248, 0)], 256, 3, None, False),
 ]
-debug = os.environ.get("READ_HIP_DEBUG") == "1"
 L = _lib.lib()
 rows = []
 for (label, srcs, cout, lvl, pre, linear) in SHAPES:
@@ -70,13 +68,7 @@ for (label, srcs, cout, lvl, pre, linear) in SHAPES:
     _lib.check(L.read_tuning_set(b"conv_pxh", 0))
     row["fp32_auto_us"] = timed(-1)
     _lib.check(L.read_tuning_set(b"conv_pxh", 16))
-    if debug:
-        for bits in (1, 2, 4, 16, 3, 7, 23):
-            _lib.check(L.read_tuning_set(b"conv_ablate", bits))
-            row[f"abl{bits}_us"] = timed(-10)
-        _lib.check(L.read_tuning_set(b"conv_ablate", 0))
     rows.append(row)
-    print("%-34s %6.1f MB  pxh %6.1f us (%5.0f GB/s)  fp32 %6.1f us  " % (label, row["MB"], row["pxh_us"], nbytes / row["pxh_us"] / 1e3, row["fp32_auto_us"]) +
-          "  ".join("%s %.1f" % (k[:-3], v) for k, v in row.items() if k.startswith("abl")), flush=True)
+    print("%-34s %6.1f MB  pxh %6.1f us (%5.0f GB/s)  fp32 %6.1f us" % (label, row["MB"], row["pxh_us"], nbytes / row["pxh_us"] / 1e3, row["fp32_auto_us"]), flush=True)
 if len(sys.argv) > 1:
     json.dump(rows, open(sys.argv[1], "w"), indent=1)

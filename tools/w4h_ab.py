@@ -28,9 +28,6 @@ def main():
     ap.add_argument("--rounds", type=int, default=1, help="times the kernels are alternated per level")
     ap.add_argument("--s2", type=int, default=0, help="1: the three 3x3 / stride-2 layers instead")
     ap.add_argument("--mul", type=int, default=0, help="1: the FAM form x1 + BC(x1 * x2) (the kernels' MUL variants)")
-    ap.add_argument("--cfg", type=int, default=-7, help="kernel the probes run on: -7 the Winograd split-operand kernel, -8 the direct one")
-    ap.add_argument("--waves", type=int, default=4, help="kernel the probes run on: 4 (the product kernel) / 8 specialised waves")
-    ap.add_argument("--abl", default="", help="comma list of conv_abl probe values for the split-operand kernel (READ_HIP_DEBUG=1; results invalid)")
     a = ap.parse_args()
     res = {}
     torch.manual_seed(0)
@@ -80,13 +77,9 @@ def main():
         if a.check:
             with torch.no_grad():
                 ref = (unet_torch.basic_conv(st, "L", (xc * x2c if a.mul else xc)[None], 3, elu=True)[0] + rc).permute(1, 2, 0)
-        from read_amd import _lib as _l
-        dbg = bool(os.environ.get("READ_HIP_DEBUG"))                 # the specialised-wave kernel lives in the debug library only
-        for rnd, (name, cfg) in [(r_, k_) for r_ in range(a.rounds) for k_ in (("fp32", -5), ("f16x3", -7), ("f4x1", -12), ("d3h", -8)) + ((("f16x3w8", -7),) if dbg else ())]:
+        for rnd, (name, cfg) in [(r_, k_) for r_ in range(a.rounds) for k_ in (("fp32", -5), ("f16x3", -7), ("f4x1", -12), ("d3h", -8))]:
             if cfg in (-7, -12) and a.mul:
                 continue                                     # the Winograd split-operand kernel does not take FAM's multiply
-            if dbg:
-                _l.check(_l.lib().read_tuning_set(b"conv_w4h_waves", 8 if name.endswith("w8") else 4))
             for _ in range(3):
                 gated_conv(pk, [(x, 0)], elu=True, residual=r, config=cfg, out=out, mul=x2)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -106,24 +99,6 @@ def main():
                 line += f"   max |diff| vs torch fp32 {rec['max_abs']:.3e}   {rec['psnr_db']:.1f} dB"
             res[f"C{c} {name}" + (f" #{rnd}" if a.rounds > 1 else "")] = rec
             print(line, flush=True)
-        if a.abl:
-            from read_amd import _lib
-            if a.cfg == -7:
-                _lib.check(_lib.lib().read_tuning_set(b"conv_w4h_waves", a.waves))
-            for v in [int(t) for t in a.abl.split(",")]:
-                _lib.check(_lib.lib().read_tuning_set(b"conv_abl", v))
-                for _ in range(3):
-                    gated_conv(pk, [(x, 0)], elu=True, residual=r, config=a.cfg, out=out, mul=x2)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(a.iters):
-                    gated_conv(pk, [(x, 0)], elu=True, residual=r, config=a.cfg, out=out, mul=x2)
-                e1.record()
-                e1.synchronize()
-                us = e0.elapsed_time(e1) / a.iters * 1e3
-                res[f"C{c} f16x3 abl {v}"] = {"us": us}
-                print(f"C={c:3d} f16x3 probe {v:5d} {us:8.2f} us", flush=True)
-            _lib.check(_lib.lib().read_tuning_set(b"conv_abl", 0))
     if a.out:
         with open(a.out, "w") as fh:
             json.dump(res, fh, indent=1)
