@@ -32,6 +32,32 @@ roundings per pass, two passes: 4 u against |B^T| |d| |B^T|^T (not |V|: the patt
 A_in = |A^T| (sum_c |U_c| . (|B^T| |d_c| |B^T|^T)) |A^T|^T.  Output transform (R / Y of the epilogue): the longest path is three
 additions per pass (R[0] = acc + s1 + s2; the factors 2, 4, 8 are exact): 6 u A_w.  Then the fma with 1 / s and the bias: 1.
     |got_f - f|  <=  u ((12 + 3 Cin / 32 + 6) A_w + 4 A_in + |f|)  +  floors in the transformed domain  +  TINY
+F(4,3) by rows (gated_conv_f4x1h_kernel, family "f4x1"): Winograd along x only, the three ky taps direct.  With the patch columns
+4 t - 1 .. 4 t + 4 of segment t:  V[r] = B^T d_r,  U[ky] = G w[ky][:],  M[y][fq] = sum_ky sum_c U[ky][fq][c] V[y + ky - 1][fq][c],
+Y = A^T M, and the absolute-value images  A_w = |A^T| (sum_ky sum_c |U| . |V|),  A_in = the same with |B^T| |d| in the place of |V|.
+  * input transform, the lambda `bt6`: every output is an add followed by an fma (x1 = fma(q, -4, p), x3 = fma(f, 2, h), ...) or two
+    fmas (y0, y5) = 2 roundings, ONE pass: 2 u against |B^T| |d|, carried through the sum as 2 u A_in;
+  * split operands, `split_store` (hi = v_cvt_pk_f16_f32, the residual by v_fma_mix_f32 is exact, times 2048, v_cvt_pk_f16_f32) and
+    read_conv_pack_f4x1_host (hi = f16_bits_rtn(us), lo = f16_bits_rtn(us - hi)); the three piece pairs of `stage_body` (pc = 0: Ws x Bl,
+    pc = 1: Wl x Bh, pc = 2: Wh x Bh): 12 u |U| |V| per product, as above;
+  * accumulation, `stage_body`: per 32-channel chunk and frequency an accumulator acc[nb][fq] takes 3 taps x 3 piece pairs = 9
+    v_mfma_f32_16x16x32_f16, one rounding each, partial sums bounded by the frequency's share of A_w: 9 (Cin / 32) u A_w;
+  * output transform, the unit epilogue: Y[nb][0] = acc[0] + s1 + s2 with s1 = acc[1] + acc[2], s2 = acc[3] + acc[4] — three additions
+    on the longest path, as Y[nb][3] = d1 + 8 dd2 + acc[5] (8 dd2 is exact, or fused): 3 u A_w;
+  * f = fma(Yf, isf, bf): 1 u |f|.
+The floors are the Winograd kernel's, in the 1-D transformed domain (V1 = |A^T| sum_ky sum_c |V|, U1 = |A^T| sum_ky sum_c |U| over the
+taps whose row is inside the image: a row outside loads zeros, and zero has no pieces to lose) — with one term more.  The 4 u allowed
+for the dropped pair Ul (2^-11 Vl) assume |V - Vh| <= 2^-11 |V|.  Where Vh is SUBNORMAL (|V| < 2^-14) the residual is bounded by the
+f16 quantum instead, |V - Vh| <= 2^-25 absolute, so the dropped pair is up to 2^-11 |U| 2^-25 = X_FLOOR |U| per product however small
+V is: of the size of the Vl floor itself.  In general |Ul| 2^-11 |Vl| <= 2^-11 |U| (2^-11 |V| + 2^-25): the relative part is in the
+12 u, the absolute part doubles the X_FLOOR term.  (On activations of 1e-6 the NumPy model of this kernel still reaches 0.88 of the
+bound.  That is not a floor: the worst element has f = b_f + 1e-6-sized products, u |f| is 0.92 of its bound and 2 X_FLOOR U1 0.06,
+and the one rounding of fma(Yf, isf, bf) is half an ulp of f, which IS u |f| for f just above a power of two.  The term is tight by
+nature; the other families hide it under (12 + 3 nb + 1) u A with |b| inside A.)
+    |got_f - f|  <=  u ((12 + 9 Cin / 32 + 3) A_w + 2 A_in + |f|)  +  W_FLOOR V1 / s  +  2 X_FLOOR U1  +  TINY
+s: one power of two per output row over all (ky, frequency, cin), `mx` of read_conv_pack_f4x1_host (f4x1_filter_inv_scale).
+Range: the largest row sum of |B^T| is 10 (rows 0, 1, 2, 5): |V| <= 10 max |x|, finite in f16 up to max |x| = 6550 (65500 rounds to
+65504, the last finite f16; 65600 rounds to Inf).  f4x1_range_edge attains it.
 Gate epilogue (the `epilogue` lambdas of the kernels: mm = fma(acc_m, -log2e / s, -log2e b_m), t = v_exp_f32(mm) + 1, sg = v_rcp_f32(t),
 fe = f log2e, e = v_exp_f32(fe) - 1, v = (f sg) sc + sh + res; v_exp_f32 / v_rcp_f32 1 ulp = 2 u):
   d_sigma <= sigma (1 - sigma) (d_m + u (3 A_m + 2))  +  3 u sigma        (rounded log2e constant, the rounded product log2e b_m and the
@@ -63,7 +89,8 @@ SECOND_ORDER = 1.0 + 2.0 ** -10
 # seeds, not by a factor.  Winograd (w4h): E against A_w (module docstring).  The d3h / d3h_s2 / w4h kernels have no linear launches;
 # the NumPy restatements of their pre-activations (tests/test_conv_accuracy_cpu.py) are held to the pxh kernel's linear row — the same
 # three-piece-pair arithmetic, measured without an epilogue.
-C_MEASURED = {"d3h": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}}, "d3h_s2": {"gated": {"a": 4.0, "b": 8.0, "c": 16.0, "d": 8.0}}, "pxh": {"gated": {"a": 4.0, "b": 4.0, "c": 8.0, "d": 4.0}, "linear": {"a": 4.0, "b": 2.0, "c": 2.0, "d": 1.0}}, "t3h": {"gated": {"a": 4.0, "b": 2.0, "c": 16.0, "d": 8.0}, "linear": {"a": 4.0, "b": 8.0, "c": 2.0, "d": 2.0}}, "w4h": {"gated": {"a": 1.0, "b": 8.0, "c": 16.0, "d": 8.0}}}
+C_MEASURED = {"d3h": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}}, "d3h_s2": {"gated": {"a": 4.0, "b": 8.0, "c": 16.0, "d": 8.0}}, "pxh": {"gated": {"a": 4.0, "b": 4.0, "c": 8.0, "d": 4.0}, "linear": {"a": 4.0, "b": 2.0, "c": 2.0, "d": 1.0}}, "t3h": {"gated": {"a": 4.0, "b": 2.0, "c": 16.0, "d": 8.0}, "linear": {"a": 4.0, "b": 8.0, "c": 2.0, "d": 2.0}}, "w4h": {"gated": {"a": 1.0, "b": 8.0, "c": 16.0, "d": 8.0}},
+              "f4x1": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}}}      # f4x1: E against A_w, as w4h
 
 
 def measured_cap(family, mode, cls):
@@ -74,12 +101,13 @@ def measured_cap(family, mode, cls):
 def k_blocks(family, cin, k):
     """MFMA k-blocks per output element: gated_conv_d3h_kernel / _s2 run one v_mfma_f32_16x16x32_f16 triple per (tap, 32-channel chunk)
     (`stage`: 9 taps x 4 pixel blocks, three MFMAs each); gated_conv_pxh_kernel one v_mfma_f32_32x32x16_f16 triple per k16 step of
-    K = taps Cin padded to 16 (read_conv_pack_t3h_host); the Winograd kernel one triple per 32-channel chunk and frequency."""
+    K = taps Cin padded to 16 (read_conv_pack_t3h_host); the Winograd kernel one triple per 32-channel chunk and frequency; the
+    F(4,3)-by-rows kernel three triples (one per ky tap) per 32-channel chunk and frequency: its bound counts 9 per block."""
     if family in ("d3h", "d3h_s2"):
         return k * k * cin // 32
     if family in ("pxh", "t3h"):
         return (k * k * cin + 15) // 16
-    if family == "w4h":
+    if family in ("w4h", "f4x1"):
         return cin // 32
     raise ValueError(family)
 
@@ -200,13 +228,19 @@ def wino_terms(L, x, which):
     ix = (4 * np.arange(tx))[:, None] + np.arange(6)[None]
     d = xp[:, iy[:, None, :, None], ix[None, :, None, :]]                                        # (C, ty, tx, 6, 6)
     B64, A64 = BT.astype(np.float64), AT.astype(np.float64)
-    V = np.abs(np.einsum("ia,ctuab,jb->tuijc", B64, d, B64))
-    Vin = np.einsum("ia,ctuab,jb->tuijc", np.abs(B64), np.abs(d), np.abs(B64))
-    Uabs = np.abs(np.einsum("ia,ocab,jb->ijco", G, w, G))
+    V = np.abs(np.einsum("ia,ctuab,jb->tuijc", B64, d, B64, optimize=True))
+    Vin = np.einsum("ia,ctuab,jb->tuijc", np.abs(B64), np.abs(d), np.abs(B64), optimize=True)
+    Uabs = np.ascontiguousarray(np.abs(np.einsum("ia,ocab,jb->ijco", G, w, G)))
+
+    def per_frequency(Vt):                                                                       # sum_c |V_c| |U_c|: one matrix product per frequency
+        Vf = np.ascontiguousarray(Vt.transpose(2, 3, 0, 1, 4)).reshape(6, 6, ty * tx, cin)
+        M = np.stack([np.stack([Vf[i, j] @ Uabs[i, j] for j in range(6)]) for i in range(6)])
+        return M.reshape(6, 6, ty, tx, cout).transpose(2, 3, 0, 1, 4)
+
     out = []
-    for M in (np.einsum("tuijc,ijco->tuijo", V, Uabs), np.einsum("tuijc,ijco->tuijo", Vin, Uabs),
+    for M in (per_frequency(V), per_frequency(Vin),
               np.repeat(V.sum(-1)[..., None], cout, -1), np.repeat(Uabs.sum(2)[None, None], ty, 0).repeat(tx, 1)):
-        Y = np.einsum("pi,tuijo,qj->otpuq", np.abs(A64), M, np.abs(A64)).reshape(cout, 4 * ty, 4 * tx)
+        Y = np.einsum("pi,tuijo,qj->otpuq", np.abs(A64), M, np.abs(A64), optimize=True).reshape(cout, 4 * ty, 4 * tx)
         out.append(Y[:, :H, :W])
     return out
 
@@ -223,6 +257,56 @@ def preact_bound_wino(L, x, ref, which):
     inv_s = wino_filter_inv_scale(w)[:, None, None]
     val = np.abs(ref.f if which == "f" else ref.m)
     return U * (n * Aw + 4 * Ain + val) + W_FLOOR * inv_s * V1 + X_FLOOR * U1 + TINY, Aw
+
+
+def _f4x1_images(x):
+    """-> (|V|, |B^T| |d|), each (6, H + 2, segments, Cin): the transformed rows of the zero-padded image, row index y + 1."""
+    cin, H, W = x.shape
+    nt = (W + 3) // 4
+    xp = np.zeros((H + 2, 4 * nt + 2, cin))
+    xp[1:H + 1, 1:W + 1] = np.asarray(x, np.float64).transpose(1, 2, 0)
+    d = np.stack([xp[:, j:j + 4 * nt:4] for j in range(6)]).reshape(6, -1)                       # [patch column 4 t - 1 + j][(row, segment, cin)]
+    B64 = BT.astype(np.float64)
+    return np.abs(B64 @ d).reshape(6, H + 2, nt, cin), (np.abs(B64) @ np.abs(d)).reshape(6, H + 2, nt, cin)
+
+
+def f4x1_terms(L, x, which):
+    """The 1-D analogue of wino_terms for gated_conv_f4x1h_kernel -> (A_w, A_in, V1, U1), each (Cout, H, W), float64, bias not included
+    (module docstring, "F(4,3) by rows").  Every contraction over cin is one matrix product per (frequency, ky)."""
+    w = np.asarray(L["w" + which], np.float64)
+    cout, cin = w.shape[:2]
+    _, H, W = x.shape
+    nt = (W + 3) // 4
+    Uabs = np.ascontiguousarray(np.abs(np.einsum("fb,ocab->faco", G.astype(np.float64), w)))      # [fq][ky][cin][co]
+    absAT = np.abs(AT).astype(np.float64)
+    inside = np.array([[0 <= y + ky - 1 < H for ky in range(3)] for y in range(H)], np.float64)   # (y, ky): the tap's row is in the image
+    out = []
+    V, Vin = _f4x1_images(x)
+    for img in (V, Vin):
+        M = np.stack([sum(img[fq, ky:ky + H].reshape(H * nt, cin) @ Uabs[fq, ky] for ky in range(3)) for fq in range(6)])   # (fq, (y, t), co)
+        out.append(np.einsum("pf,fno->onp", absAT, M).reshape(cout, H, 4 * nt)[:, :, :W])
+    X1 = sum(V[:, ky:ky + H].sum(axis=3) for ky in range(3))                                      # (fq, y, t)
+    V1 = np.einsum("pf,fyt->ytp", absAT, X1).reshape(H, 4 * nt)[:, :W]
+    out.append(np.broadcast_to(V1[None], (cout, H, W)).copy())
+    U1 = np.einsum("pf,yk,fko->oyp", absAT, inside, Uabs.sum(axis=2))                             # (co, y, pixel of the segment)
+    out.append(np.tile(U1, (1, 1, nt))[:, :, :W])
+    return out
+
+
+def f4x1_filter_inv_scale(w):
+    """1 / s of read_conv_pack_f4x1_host: one scale per output row over all (ky, frequency, cin) of U[ky] = G w[ky][:]."""
+    Uf = np.einsum("fb,ocab->oafc", G.astype(np.float64), np.asarray(w, np.float64))
+    return row_inv_scale(Uf)
+
+
+def preact_bound_f4x1(L, x, ref, which):
+    """-> (|got - f| or |got - m| <= this, elementwise; A_w) for gated_conv_f4x1h_kernel (module docstring, "F(4,3) by rows")."""
+    Aw, Ain, V1, U1 = f4x1_terms(L, x, which)
+    w = L["w" + which]
+    n = 12 + 9 * k_blocks("f4x1", w.shape[1], 3) + 3
+    inv_s = f4x1_filter_inv_scale(w)[:, None, None]
+    val = np.abs(ref.f if which == "f" else ref.m)
+    return U * (n * Aw + 2 * Ain + val) + W_FLOOR * inv_s * V1 + 2 * X_FLOOR * U1 + TINY, Aw
 
 
 def gated_bound(ref, df, dm):
@@ -330,6 +414,18 @@ def impulse_positions(cin, H, W):
     return pos
 
 
+def impulse_positions_f4x1(cin, H, W):
+    """impulse_positions plus what the geometry of gated_conv_f4x1h_kernel adds (units of 8 rows x 32 columns = 8 segments of 4): the
+    unit seam in x (columns 31, 32, 33) inside a unit's rows, the halo rows of a unit (7, 8) at that seam, and every column of the last
+    partial segment.  A list of its own: the cases of the other families do not change."""
+    pos = list(impulse_positions(cin, H, W))
+    seam = [x_ for x_ in (31, 32, 33) if x_ < W]
+    pos += [(1 % cin, min(3, H - 1), x_) for x_ in seam]
+    pos += [(1 % cin, y, x_) for y in (7, 8) if y < H for x_ in seam]
+    pos += [(3 % cin, H // 2, x_) for x_ in range(4 * ((W - 1) // 4), W)]
+    return list(dict.fromkeys(pos))
+
+
 def constant_image(cin, H, W, value=1.0):
     return np.full((cin, H, W), value, np.float32)
 
@@ -347,4 +443,14 @@ def wino_range_edge(cin, H, W, rows=(0, 0), tile=(1, 1), amp=650.0):
     x = np.zeros((cin, H, W), np.float32)
     y0, x0 = 4 * tile[0] - 1, 4 * tile[1] - 1
     x[:, y0:y0 + 6, x0:x0 + 6] = pat[None]
+    return x
+
+
+def f4x1_range_edge(cin, H, W, row=0, segment=1, amp=6550.0):
+    """Class (d) of the F(4,3)-by-rows kernel: sign(BT[row]) amp on the six patch columns 4 t - 1 .. 4 t + 4 of segment t, every image
+    row and channel, the rest zero: |B^T d| = 10 amp at frequency `row` (rows of absolute sum 10: 0, 1, 2, 5).  At amp = 6550 the
+    transformed value is 65500, which rounds to 65504, the last finite f16."""
+    assert np.abs(BT[row]).sum() == 10 and 4 * segment - 1 >= 0 and 4 * segment + 4 < W
+    x = np.zeros((cin, H, W), np.float32)
+    x[:, :, 4 * segment - 1:4 * segment + 5] = (np.sign(BT[row]).astype(np.float32) * np.float32(amp))[None, None, :]
     return x

@@ -1,5 +1,5 @@
-"""CPU: the NumPy restatements of the split-operand convolution kernels (tests/d3h_ref.py, tests/wino4h_ref.py, with the library's own
-host packers) held to the float64 reference, the derived bounds and the measured caps of tests/conv_ref64.py — on unit-scale,
+"""CPU: the NumPy restatements of the split-operand convolution kernels (tests/d3h_ref.py, tests/wino4h_ref.py, the F(4,3)-by-rows
+model of tests/test_f4x1_model.py, with the library's own host packers) held to the float64 reference, the derived bounds and the measured caps of tests/conv_ref64.py — on unit-scale,
 checkpoint-like, structured and range-edge inputs — and the DETECTION POWER of those caps: the same arithmetic with one seeded defect
 each must exceed them.  The restatements sum in float64 where the device rounds per MFMA, so the intact models sit well inside the caps;
 what this module establishes is that the inputs are such that correct split arithmetic passes (floors included) and that broken split
@@ -191,8 +191,11 @@ def test_packers_on_edge_rows():
     """read_conv_pack_dkh_host (3x3, 4x4, 1x1), read_conv_pack_t3h_host and read_conv_pack_w4h_host against the NumPy packers BIT FOR BIT
     on checkpoint-like layers with the edge rows (all zeros, a single weight, largest |w| a power of two and the fp32 number just below
     one, fp32 denormals, -0.0), and the properties the arithmetic rests on, from the library's own output: 1 / s as the rule says, every
-    piece finite, hi + lo within half an f16 ulp of the exact residual."""
+    piece finite, hi + lo within half an f16 ulp of the exact residual.  read_conv_pack_f4x1_host has no NumPy packer beside it: its
+    output is decoded (tests/test_f4x1_model.decode_rows) and held to the same properties against G w in float64."""
     from read_amd import _lib
+    from tests import test_f4x1_model as F4
+    from tests.wino4_ref import G
     from tests.wino4h_ref import pack_w4h_blob
     L_ = _lib.lib()
     for cin, cout in ((64, 40), (32, 32)):
@@ -217,6 +220,20 @@ def test_packers_on_edge_rows():
         h, inv = _halfs(got, 2 * cp)
         assert np.isfinite(h.astype(np.float32)).all()
         assert np.array_equal(inv[:cout], R64.wino_filter_inv_scale(wf).astype(np.float32))
+        # F(4,3) by rows
+        halfs, inv = F4.pack_f4x1(wf, wm)
+        assert inv.shape == (2, cp) and np.isfinite(halfs.astype(np.float32)).all()
+        Uh, Ul = F4.decode_rows(halfs, cin, cp)
+        for fm, w in enumerate((wf, wm)):
+            assert np.array_equal(inv[fm, :cout], R64.f4x1_filter_inv_scale(w).astype(np.float32)), "1 / s of the F(4,3)-by-rows packer"
+            z, dn = (0, 4) if fm == 0 else (8, 12)                            # the all-zero row; the denormal row at the clamp (s = 2^60)
+            assert inv[fm, z] == 1.0 and inv[fm, dn] == np.float32(2.0 ** -60)
+            w64 = w.astype(np.float64).transpose(0, 2, 1, 3)                  # (co, ky, cin, kx)
+            Us = sum(G[None, None, :, None, b] * w64[:, :, None, :, b] for b in range(3)) / inv[fm, :cout].astype(np.float64)[:, None, None, None]
+            hi, lo = Uh[fm, :cout], Ul[fm, :cout]                             # (co, ky, frequency, cin)
+            assert np.abs(Us).max() < 2.0 ** 15 and np.isfinite(hi).all() and np.isfinite(lo).all()
+            assert np.all(np.abs(hi - Us) <= half_ulp_f16(Us)) and np.all(np.abs(hi + lo - Us) <= half_ulp_f16(Us - hi)), "pieces of the F(4,3)-by-rows packer"
+            assert not Uh[fm, cout:].any() and not Ul[fm, cout:].any() and np.all(inv[fm, cout:] == 1.0)     # padded rows: zero, scale 1
         # 1x1
         w1f, w1m = np.ascontiguousarray(wf[:, :, 0, 0]), np.ascontiguousarray(wm[:, :, 0, 0])
         got = np.zeros(L_.read_conv_dkh_floats(cin, cout, 1), np.float32)
@@ -333,3 +350,134 @@ def test_winograd_split_model_stays_inside_the_caps_and_defects_do_not():
                 print("   %-8s E(A) max %10.2f rms %9.3f  err/bound %9.3f finite %s" % (dname, d["EA_max"], d["EA_rms"], d["q"], d["finite"]))
     assert any(caught["drop_ul"]["a"]) and any(caught["drop_ul"]["b"]) and all(caught["drop_ul"]["c"]), caught
     assert any(caught["binade"]["b"]), caught
+
+
+# ------------------------------------------------------------------------------------------ F(4,3) by rows
+def run_f4x1(L, x, halfs_edit=None, cls="a"):
+    """The NumPy model of gated_conv_f4x1h_kernel (tests/test_f4x1_model.f4x1_conv_model) on the LIBRARY's packed operand -> statistics as
+    run_wino: E against the transformed-domain condition term A_w, (EA) against A; `got` = [f | m] for the checks that look at elements."""
+    from tests import test_f4x1_model as F4
+    cout, cin = L["wf"].shape[:2]
+    halfs, inv = F4.pack_f4x1(np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"]))
+    halfs, inv = halfs.copy(), inv.copy()
+    if halfs_edit is not None:
+        halfs_edit(halfs, inv)
+    with np.errstate(over="ignore", invalid="ignore"):
+        Uh, Ul = F4.decode_rows(halfs, cin, inv.shape[1])
+        f, m = F4.f4x1_conv_model(np.ascontiguousarray(x.transpose(1, 2, 0)), Uh, Ul, inv, cout)
+        got = np.concatenate([(f + L["bf"][None, None]).transpose(2, 0, 1), (m + L["bm"][None, None]).transpose(2, 0, 1)])
+    ref = R64.reference(L, x)
+    bf_, Awf = R64.preact_bound_f4x1(L, x, ref, "f")
+    bm_, Awm = R64.preact_bound_f4x1(L, x, ref, "m")
+    bound = np.concatenate([bf_, bm_])
+    truth = np.concatenate([ref.f, ref.m])
+    finite = bool(np.isfinite(got).all())
+    err = np.abs(np.nan_to_num(got.astype(np.float64), nan=1e300, posinf=1e300, neginf=-1e300) - truth)
+    Aw = np.concatenate([Awf + np.abs(L["bf"].astype(np.float64))[:, None, None], Awm + np.abs(L["bm"].astype(np.float64))[:, None, None]])
+    clean = np.nan_to_num(got, nan=3e38, posinf=3e38, neginf=-3e38)
+    e_max, e_rms = R64._stats(np.abs(clean.astype(np.float64) - truth), Aw)
+    ea_max, ea_rms = R64.measure_linear(clean, ref)
+    r_max, r_rms = R64.measure_linear(R64.oracle_fp32(L, x, linear=True), ref)
+    return dict(E_max=e_max, E_rms=e_rms, EA_max=ea_max, EA_rms=ea_rms, R_max=r_max, R_rms=r_rms, q=float((err / bound).max()), finite=finite,
+                zero_exact=bool((got[Aw == 0] == 0).all()), cls=cls, got=got)
+
+
+def f4x1_inside_caps(s):
+    """Finite, inside preact_bound_f4x1, exact zeros where A_w + |b| = 0, and inside the linear caps this file uses for models
+    (measured_cap falls back to the pxh kernel's linear row for a family without linear launches)."""
+    return inside_caps(s, "f4x1")
+
+
+F4X1_SHAPE = (32, 32, 11, 37)        # one full 8 x 32 unit, partial units to the right (5 columns, a last segment of 1) and below (3 rows)
+
+
+def f4x1_inputs(cin, cout, H, W):
+    rng = np.random.default_rng([cin, cout, 7])
+    tame = R64.tame_layer(cin, cout, 3, 51)
+    yield "a", "unit scale", tame, rng.standard_normal((cin, H, W)).astype(np.float32)
+    Lb, xb = R64.checkpoint_like(cin, cout, 3, H, W, 52)
+    yield "b", "checkpoint-like", Lb, xb
+    base = R64.impulse_positions(cin, H, W)
+    own = [p for p in R64.impulse_positions_f4x1(cin, H, W) if p not in base]           # the seam, the halo rows, the last partial segment
+    for amp in (1.0, 2.0 ** -10):
+        for (c, y, x_) in base[::5] + own:
+            yield "c", f"impulse {amp:g} at c{c} ({y},{x_})", tame, R64.impulse(cin, H, W, c, y, x_, amp)
+    yield "c", "constant", tame, R64.constant_image(cin, H, W)
+    yield "c", "checkerboard", tame, R64.checkerboard(cin, H, W)
+    yield "d", "range edge 6550, row 1, segment 3", tame, R64.f4x1_range_edge(cin, H, W, row=1, segment=3)
+    yield "d", "range edge 6550, row 5, segment 8", tame, R64.f4x1_range_edge(cin, H, W, row=5, segment=8)      # the last full segment, right of the seam
+    for amp, label in ((2.0 ** -14, "2^-14"), (1e-6, "1e-6")):
+        yield "d", f"small scale {label}", tame, (rng.standard_normal((cin, H, W)) * amp).astype(np.float32)
+
+
+def test_f4x1_model_stays_inside_the_caps():
+    """The intact arithmetic of gated_conv_f4x1h_kernel on classes (a) - (d): finite (at amplitude 6550 on the pattern that attains
+    |B^T d| = 10 x), inside preact_bound_f4x1, inside the linear caps, exact zeros where A_w + |b| = 0."""
+    for cls, name, L, x in f4x1_inputs(*F4X1_SHAPE):
+        s = run_f4x1(L, x, cls=cls)
+        print("f4x1    %s %-36s E(A_w) max %8.2f rms %7.3f  E(A) max %9.2f rms %8.3f  R_max %7.2f R_rms %6.3f  err/bound %.3f" % (
+            cls, name, s["E_max"], s["E_rms"], s["EA_max"], s["EA_rms"], s["R_max"], s["R_rms"], s["q"]))
+        assert s["finite"], (cls, name)
+        assert s["q"] <= 1.0, (cls, name, s["q"])
+        assert s["zero_exact"], (cls, name)
+        assert f4x1_inside_caps(s), (cls, name, {k: v for k, v in s.items() if k != "got"})
+
+
+def _f4x1_drop_ul(halfs, inv):
+    halfs[:, :, :, :, :, 1] = 0                                  # = the pair Ul Vh dropped
+
+
+def _f4x1_binade(halfs, inv):
+    with np.errstate(over="ignore"):
+        halfs *= np.float16(2.0)                                 # the row's largest entry lands in [2^15, 2^16)
+    inv *= 0.5
+
+
+def _f4x1_no_ky0(halfs, inv):
+    halfs[:, :, :, 0] = 0                                        # the fragments of tap ky = 0: the row above never reaches the output
+
+
+# Which classes must catch which defect of the operand the model consumes:
+#   drop_ul  up to 2^-11 |U V| per product for every V: (a), (b), and EVERY impulse of (c);
+#   binade   nothing is lost until an entry reaches 65520: the row of (b) whose largest weight is the fp32 number just below a power of two
+#            (its G[5] w = w at frequency 5) rounds to 2^16 = Inf in f16: (b), non-finite;
+#   no_ky0   a third of the taps: every class.  On an impulse at (y, x) it is visible EXACTLY: the output row y + 1 sees the impulse
+#            through tap ky = 0 alone, so the broken model returns the bias there, bit for bit, where the reference does not — for the
+#            impulses on row 7 that is row 8, the top row of the unit below.
+F4X1_DEFECTS = {"drop_ul": (_f4x1_drop_ul, {"a", "b", "c"}), "binade": (_f4x1_binade, {"b"}), "no_ky0": (_f4x1_no_ky0, {"a", "b", "c", "d"})}
+
+
+@pytest.mark.parametrize("defect", sorted(F4X1_DEFECTS))
+def test_f4x1_seeded_defects_exceed_the_caps(defect):
+    edit, classes = F4X1_DEFECTS[defect]
+    cin, cout, H, W = F4X1_SHAPE
+    caught = {}
+    for cls, name, L, x in f4x1_inputs(*F4X1_SHAPE):
+        s = run_f4x1(L, x, halfs_edit=edit, cls=cls)
+        hit = not f4x1_inside_caps(s)
+        caught.setdefault(cls, []).append((name, hit))
+        print("%-8s %s %-36s E(A) max %10.2f rms %9.3f  err/bound %9.3f finite %s  %s" % (defect, cls, name, s["EA_max"], s["EA_rms"], s["q"], s["finite"], "CAUGHT" if hit else "-"))
+        if defect == "binade" and cls == "b":
+            assert not s["finite"], "the row just below a power of two must overflow f16 one binade up"
+        if defect == "no_ky0" and name.startswith("impulse"):
+            y = int(name.split("(")[1].split(",")[0])
+            if y + 1 < H:
+                ref = R64.reference(L, x)
+                row = s["got"][:cout, y + 1]
+                assert np.array_equal(row, np.broadcast_to(L["bf"][:, None], row.shape)) and np.any(ref.f[:, y + 1] != L["bf"].astype(np.float64)[:, None]), name
+    for cls in classes:
+        assert any(h for _, h in caught[cls]), f"{defect}: class ({cls}) did not catch it: {caught}"
+    if defect in ("drop_ul", "no_ky0"):
+        # (an impulse on the last image row reaches no output through tap ky = 0: nothing to lose there)
+        assert all(h for n, h in caught["c"] if n.startswith("impulse") and (defect == "drop_ul" or int(n.split("(")[1].split(",")[0]) + 1 < H)), caught["c"]
+
+
+def test_f4x1_model_overflows_just_past_the_documented_range():
+    """Written to fail the finiteness check: amplitude 6560 on the range-edge pattern gives |B^T d| = 65600, which rounds to Inf in f16 —
+    so the 6550 cases of the tests above and of tests/test_gpu_conv_accuracy.py really sit on the edge."""
+    cin, cout, H, W = F4X1_SHAPE
+    tame = R64.tame_layer(cin, cout, 3, 51)
+    for row, segment in ((1, 3), (5, 8)):
+        assert run_f4x1(tame, R64.f4x1_range_edge(cin, H, W, row=row, segment=segment, amp=6550.0), cls="d")["finite"]
+        s = run_f4x1(tame, R64.f4x1_range_edge(cin, H, W, row=row, segment=segment, amp=6560.0), cls="d")
+        assert not s["finite"] and not f4x1_inside_caps(s), (row, segment)

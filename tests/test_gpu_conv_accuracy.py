@@ -1,5 +1,5 @@
-"""GPU: every split-operand convolution kernel (gated_conv_wino4h_kernel, gated_conv_d3h_kernel, gated_conv_d3h_s2_kernel,
-gated_conv_pxh_kernel and its taps form) against a float64 reference, in units of fp32 round-off, on unit-scale, checkpoint-like,
+"""GPU: every split-operand convolution kernel (gated_conv_wino4h_kernel, gated_conv_f4x1h_kernel, gated_conv_d3h_kernel,
+gated_conv_d3h_s2_kernel, gated_conv_pxh_kernel and its taps form) against a float64 reference, in units of fp32 round-off, on unit-scale, checkpoint-like,
 structured and range-edge inputs (tests/conv_ref64.py: the measure, the derived bounds with the source lines they count, the
 generators).  Each case is asserted against
   * the derived bound, elementwise (hard: a case over it is a bug in the kernel or a flaw in the derivation);
@@ -9,8 +9,11 @@ generators).  Each case is asserted against
   * exactness where no product reaches the output (gamma = 0, an all-zero conv_f row with zero bias): the epilogue constant, ==.
 Every element of every case is measured.  The fp32 kernels (Winograd F(4x4) config -5, one direct fp32 configuration) run on the 3x3
 cases for the printed table only: they are the baseline the split kernels replaced.
-Plus FAM's x1 * x2 launches, the family query against the dispatch order, and one whole network whose residual blocks carry
-checkpoint-like statistics against the float64 network.  Run with -s to see the table; lines start with "ACC|"."""
+An automatic launch (config -1) of the 3x3 / stride-1 family is attributed BY ITS BITS — the F(4x4) and the F(4,3)-by-rows kernel both
+report family 5 — and held to the bound and cap of the kernel that ran.
+Plus the persistent walk (shapes with more units than the device has compute units, impulses in a workgroup's second and third unit),
+FAM's x1 * x2 launches, the family query against the dispatch order, the loud failure past the documented range, and one whole network
+whose residual blocks carry checkpoint-like statistics against the float64 network.  Run with -s to see the table; lines start with "ACC|"."""
 import ctypes
 
 import numpy as np
@@ -22,8 +25,8 @@ from tests import conv_ref64 as R64
 
 pytestmark = pytest.mark.gpu
 
-FAMILY_ID = {"w4h": 5, "d3h": 6, "d3h_s2": 6, "pxh": 7, "t3h": 8}
-FORCE = {"w4h": -7, "d3h": -8, "d3h_s2": -1, "pxh": -10, "t3h": -11}          # stride 2 goes through the automatic choice, family asserted
+FAMILY_ID = {"w4h": 5, "f4x1": 5, "d3h": 6, "d3h_s2": 6, "pxh": 7, "t3h": 8}
+FORCE = {"w4h": -7, "f4x1": -12, "d3h": -8, "d3h_s2": -1, "pxh": -10, "t3h": -11}          # stride 2 goes through the automatic choice, family asserted
 DIRECT_FP32 = "k3s1c16_p2q1m4n1f1b2"
 
 
@@ -42,6 +45,7 @@ class Case:
         self.split = split if split is not None else [x.shape[0]]           # channels per source (pxh: concatenated sources)
         self.k = L["wf"].shape[2]
         self._ref = None
+        self._bounds = {}
 
     def ref(self):
         if self._ref is None:
@@ -70,16 +74,20 @@ class Case:
 
 def _bounds(case, family):
     """-> (d_f, d_m, B_w): the pre-activation bounds and, for the Winograd family, the condition term B with A_w in the place of A."""
-    ref = case.ref()
-    if family == "w4h":
-        df, Awf = R64.preact_bound_wino(case.L, case.x, ref, "f")
-        dm, Awm = R64.preact_bound_wino(case.L, case.x, ref, "m")
-        Awf = Awf + np.abs(case.L["bf"].astype(np.float64))[:, None, None]
-        Awm = Awm + np.abs(case.L["bm"].astype(np.float64))[:, None, None]
-        Bw = ref.S * (np.abs(ref.dact) * ref.sig * Awf + np.abs(ref.g) * ref.sig * (1.0 - ref.sig) * Awm) + np.abs(ref.y)
-        return df, dm, Bw
-    df, dm = (R64.preact_bound_direct(case.L, ref, family, fm) for fm in "fm")
-    return df, dm, None
+    if family not in case._bounds:
+        ref = case.ref()
+        if family in ("w4h", "f4x1"):
+            preact = R64.preact_bound_wino if family == "w4h" else R64.preact_bound_f4x1
+            df, Awf = preact(case.L, case.x, ref, "f")
+            dm, Awm = preact(case.L, case.x, ref, "m")
+            Awf = Awf + np.abs(case.L["bf"].astype(np.float64))[:, None, None]
+            Awm = Awm + np.abs(case.L["bm"].astype(np.float64))[:, None, None]
+            Bw = ref.S * (np.abs(ref.dact) * ref.sig * Awf + np.abs(ref.g) * ref.sig * (1.0 - ref.sig) * Awm) + np.abs(ref.y)
+            case._bounds[family] = (df, dm, Bw)
+        else:
+            df, dm = (R64.preact_bound_direct(case.L, ref, family, fm) for fm in "fm")
+            case._bounds[family] = (df, dm, None)
+    return case._bounds[family]
 
 
 def check(case, config, linear=False, family=None, rows=None, assert_caps=True):
@@ -141,6 +149,9 @@ def _out_hw(k, stride, H, W):
 SHAPES_A = {  # a subset of the shapes of tests/test_gpu_conv.py: (cin or source list, cout, k, stride, H, W, elu, residual)
     "w4h": [(128, 128, 3, 1, 9, 17, True, True), (64, 64, 3, 1, 40, 100, False, True), (32, 32, 3, 1, 41, 130, True, False), (96, 96, 3, 1, 14, 37, False, False),
             (256, 256, 3, 1, 8, 32, True, True)],
+    # f4x1: ragged 8 x 32 units and 4-pixel segments on all four borders (widths 4 k + 1 .. 4 k + 3, heights 8 k + 1 .. 8 k + 7), a single pixel
+    "f4x1": [(32, 32, 3, 1, 41, 130, True, False), (64, 64, 3, 1, 13, 37, True, False), (128, 128, 3, 1, 9, 17, True, True), (256, 256, 3, 1, 11, 35, True, False),
+             (96, 96, 3, 1, 23, 70, False, False), (160, 160, 3, 1, 3, 65, True, False), (64, 64, 3, 1, 1, 1, True, False)],
     "d3h": [(128, 128, 3, 1, 9, 17, True, True), (64, 64, 3, 1, 40, 100, False, True), (32, 32, 3, 1, 41, 130, True, False), (32, 64, 3, 1, 19, 45, True, False),
             (256, 256, 3, 1, 8, 32, False, True), (128, 32, 3, 1, 19, 45, True, False)],
     "d3h_s2": [(32, 64, 3, 2, 24, 80, True, False), (64, 128, 3, 2, 13, 37, False, False), (128, 256, 3, 2, 22, 46, True, False),
@@ -150,10 +161,10 @@ SHAPES_A = {  # a subset of the shapes of tests/test_gpu_conv.py: (cin or source
     "t3h": [(8, 32, 3, 1, 37, 61, True, False), (8, 16, 3, 1, 22, 76, True, False), (16, 32, 3, 1, 21, 45, True, False), (32, 64, 3, 1, 13, 70, False, False),
             (8, 32, 3, 1, 1, 40, True, False), (32, 32, 3, 1, 21, 45, True, True)],
 }
-SHAPES_B = {"w4h": [(64, 64, 3, 1, 23, 38), (128, 32, 3, 1, 9, 17)], "d3h": [(64, 64, 3, 1, 23, 38), (128, 32, 3, 1, 9, 17)],
+SHAPES_B = {"w4h": [(64, 64, 3, 1, 23, 38), (128, 32, 3, 1, 9, 17)], "f4x1": [(64, 64, 3, 1, 23, 38), (128, 32, 3, 1, 9, 17)], "d3h": [(64, 64, 3, 1, 23, 38), (128, 32, 3, 1, 9, 17)],
             "d3h_s2": [(32, 64, 3, 2, 13, 37), (64, 32, 4, 2, 10, 18)], "pxh": [(64, 56, 1, 1, 12, 44), (256, 64, 1, 1, 9, 33)],
             "t3h": [(8, 32, 3, 1, 21, 45), (32, 32, 3, 1, 13, 37)]}
-SHAPE_C = {"w4h": (64, 32, 3, 1, 13, 37), "d3h": (64, 32, 3, 1, 13, 37), "d3h_s2": (64, 32, 3, 2, 13, 37), "pxh": (64, 32, 1, 1, 13, 37), "t3h": (32, 32, 3, 1, 13, 37)}
+SHAPE_C = {"w4h": (64, 32, 3, 1, 13, 37), "f4x1": (64, 32, 3, 1, 13, 37), "d3h": (64, 32, 3, 1, 13, 37), "d3h_s2": (64, 32, 3, 2, 13, 37), "pxh": (64, 32, 1, 1, 13, 37), "t3h": (32, 32, 3, 1, 13, 37)}
 
 
 def cases_a(family):
@@ -179,7 +190,7 @@ def cases_c(family):
     cin, cout, k, s, H, W = SHAPE_C[family]
     L = R64.tame_layer(cin, cout, k, 400)
     for amp in (1.0, 2.0 ** -10):
-        for (c, y, x_) in R64.impulse_positions(cin, H, W):
+        for (c, y, x_) in (R64.impulse_positions_f4x1 if family == "f4x1" else R64.impulse_positions)(cin, H, W):
             yield Case(family, "c", f"impulse {amp:g} at c{c} ({y},{x_})", L, R64.impulse(cin, H, W, c, y, x_, amp), stride=s)
     yield Case(family, "c", "constant 1", L, R64.constant_image(cin, H, W), stride=s)
     yield Case(family, "c", "checkerboard +-1", L, R64.checkerboard(cin, H, W), stride=s, elu=False)
@@ -193,6 +204,12 @@ def cases_d(family):
         # the documented range edge: |B^T d B| = 100 x 650 = 65000 < 65504 at frequency (r, r'), on interior tiles of both unit rows
         for rows, tile in (((0, 0), (1, 1)), ((1, 2), (1, 1)), ((5, 5), (2, 3)), ((2, 5), (2, 7)), ((0, 5), (1, 8))):
             yield Case(family, "d", f"range edge 650 rows {rows} tile {tile}", L, R64.wino_range_edge(cin, H, W, rows=rows, tile=tile, amp=650.0))
+    if family == "f4x1":
+        # the documented range edge: |B^T d| = 10 x 6550 = 65500, which rounds to 65504, at frequency `row`, on every image row of an interior
+        # segment and of the last full one (right of the unit seam at x = 32)
+        for row in (0, 1, 2, 5):
+            for segment in (3, W // 4 - 1):
+                yield Case(family, "d", f"range edge 6550 row {row} segment {segment}", L, R64.f4x1_range_edge(cin, H, W, row=row, segment=segment, amp=6550.0))
     for amp, label in ((2.0 ** -14, "2^-14"), (1e-6, "1e-6")):
         # hi piece subnormal: the kernel promises an absolute floor of ~1e-11 per product here (X_FLOOR of tests/conv_ref64.py, carried
         # through the sum as conv(1, |w|)), not fp32-relative accuracy; the derived bound contains exactly that floor
@@ -202,26 +219,114 @@ def cases_d(family):
 ALL_CLASSES = {"a": cases_a, "b": cases_b, "c": cases_c, "d": cases_d}
 
 
-def run_family(family, rows=None, assert_caps=True):
+def _same_bits(a, b):
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def attribute_auto(case):
+    """The split-operand family an automatic launch (config -1) of this case runs on, or None.  The F(4x4) kernel and the F(4,3)-by-rows
+    kernel both report family 5: the launch is attributed by its BITS — equal to the forced launch of one and different from the
+    other's (different arithmetic: tests/test_gpu_conv_f4x1.test_f4x1_dispatch)."""
+    got, fam = case.launch(-1)
+    if fam != 5:
+        return {6: "d3h", 7: "pxh", 8: "t3h"}.get(fam)
+    as_f4x1, as_w4h = (_same_bits(got, case.launch(FORCE[f])[0]) for f in ("f4x1", "w4h"))
+    assert as_f4x1 != as_w4h, f"{case.name}: an automatic family-5 launch equals {'both' if as_f4x1 else 'neither'} of config -12 and config -7"
+    return "f4x1" if as_f4x1 else "w4h"
+
+
+def run_family(family, rows=None, assert_caps=True, classes="abcd"):
     linear_too = family in ("pxh", "t3h")
-    for cls in "abcd":
+    for cls in classes:
         for case in ALL_CLASSES[cls](family):
             check(case, FORCE[family], family=family, rows=rows, assert_caps=assert_caps)
             if linear_too:
                 check(case, FORCE[family], linear=True, family=family, rows=rows, assert_caps=assert_caps)
             if cls in "ab" and FORCE[family] != -1:
-                # the automatic choice: held to the caps of whichever split-operand family it takes, printed otherwise
-                _, fam = case.launch(-1)
-                auto = {5: "w4h", 6: "d3h", 7: "pxh", 8: "t3h"}.get(fam)
-                check(case, -1, family=auto, rows=rows, assert_caps=assert_caps)
+                # the automatic choice: held to the bound and caps of whichever split-operand kernel it takes, printed otherwise
+                check(case, -1, family=attribute_auto(case), rows=rows, assert_caps=assert_caps)
             if cls in "ab" and case.k == 3 and case.stride == 1 and family in ("w4h", "d3h") and case.x.shape[0] % 16 == 0:
                 check(case, -5, family=None, rows=rows)                                      # fp32 Winograd F(4x4): printed only
                 check(case, config_names().index(DIRECT_FP32), family=None, rows=rows)      # fp32 direct: printed only
 
 
-@pytest.mark.parametrize("family", ["w4h", "d3h", "d3h_s2", "pxh", "t3h"])
+@pytest.mark.parametrize("family", ["w4h", "f4x1", "d3h", "d3h_s2", "pxh", "t3h"])
 def test_split_operand_family_against_fp64(hip, family):
     run_family(family)
+
+
+# ------------------------------------------------------------------------------------------ the persistent walk
+# The kernels of the 8 x 32-unit family run one workgroup per compute unit, each walking units u = blockIdx, blockIdx + grid, ... with
+# grid = min(n_units, CUs) rounded down to a multiple of the Cout / 32 channel groups (persistent_grid of read_amd/csrc/conv.hip; unit u =
+# tile u / groups, group u % groups).  The walk has state of its own — step_tile with its single wrap in x, a prefetch cursor that runs
+# ahead into the next unit, V buffers whose parity across units depends on whether Cin / 32 is odd, weight rings that keep turning — and
+# only a shape with MORE units than compute units reaches it.  (C, H, W): 261 / 513 / 258 / 261 / 264 units on 256 CUs.
+WALK_SHAPES = [(32, 72, 900),       # one chunk: the V parity flips per unit; some workgroups walk two units
+               (32, 150, 860),      # one workgroup walks three
+               (64, 24, 1376),      # two groups
+               (96, 20, 920),       # three groups, grid 255, an odd chunk count
+               (256, 20, 330)]      # eight groups
+
+
+def walk_grid(c, H, W):
+    """-> (n_units, grid, groups, tiles_x): the rule above, restated from the device's compute-unit count and the shape."""
+    groups, tiles_x = (c + 31) // 32, (W + 31) // 32
+    n_units = tiles_x * ((H + 7) // 8) * groups
+    grid = min(n_units, torch.cuda.get_device_properties(0).multi_processor_count)
+    grid = max(grid - grid % groups, groups)
+    return n_units, grid, groups, tiles_x
+
+
+_WALK_CASES = {}
+
+
+def walk_cases(shape):
+    """-> the class (a) case and the class (c) case (one image with two impulses) of one walk shape, built once and shared by the
+    families that run it (only the latest shape is kept: the references of 10^5 pixels are large); asserts the conditions that make
+    them walk."""
+    if shape in _WALK_CASES:
+        return _WALK_CASES[shape]
+    _WALK_CASES.clear()
+    c, H, W = shape
+    n_units, grid, groups, tiles_x = walk_grid(c, H, W)
+    assert n_units > grid, f"{c} x {H}x{W}: {n_units} units on a grid of {grid}: no workgroup walks a second unit on this device"
+    t0 = (grid + groups - 1) // groups                                       # the first tile all of whose units have index >= grid
+    spots = [(1 % c, min(8 * (t0 // tiles_x) + 3, H - 1), min(32 * (t0 % tiles_x) + 17, W - 1)), (c - 1, H - 1, W - 1)]
+    x = np.zeros((c, H, W), np.float32)
+    for (ch, y, x_) in spots:
+        unit = ((y // 8) * tiles_x + x_ // 32) * groups
+        assert unit >= grid, f"the impulse at ({y},{x_}) lies in units {unit} .. {unit + groups - 1}, the grid is {grid}"
+        x[ch, y, x_] = 1.0
+    rng = np.random.default_rng([800, c, H, W])
+    L = R64.tame_layer(c, c, 3, 800)
+    tag = f"walk {n_units} / {grid}: {c} {H}x{W}"
+    _WALK_CASES[shape] = [Case("walk", "a", f"{tag} unit scale", L, rng.standard_normal((c, H, W)).astype(np.float32), residual=_res(rng, c, H, W)),
+                          Case("walk", "c", f"{tag} impulses at " + " ".join(f"c{ch} ({y},{x_})" for (ch, y, x_) in spots), L, x)]
+    return _WALK_CASES[shape]
+
+
+WALK_RUNS = [(shape, family) for shape in WALK_SHAPES for family in (("f4x1", "w4h", "d3h") if shape in ((32, 72, 900), (256, 20, 330)) else ("f4x1",))]
+
+
+@pytest.mark.parametrize("shape,family", WALK_RUNS, ids=lambda v: v if isinstance(v, str) else "%dx%dx%d" % v)
+def test_persistent_walk_against_fp64(hip, shape, family):
+    """Unit-scale inputs (class (a)) and two impulses (class (c)) on shapes with more units than the device has compute units: one
+    impulse in the first tile that only a workgroup's SECOND unit reaches, one in the last unit (partial on every shape but 24 x 1376).
+    Held to the derived bound and to the caps of classes (a) / (c) of the family, as every other case; config -12 on every shape, -7
+    and -8 on two of them (no other kernel-level float64 case walks a second unit for those kernels either).  A device with more compute
+    units than a shape has units FAILS here: the shapes must then grow, not the test pass without walking."""
+    for case in walk_cases(shape):
+        check(case, FORCE[family], family=family)
+
+
+def test_f4x1_fails_loudly_past_its_range(hip):
+    """Activations of ~2e4 (normal x 2e4; |B^T d| far beyond 65504, the documented range ends at 6550 — module docstring of
+    tests/conv_ref64.py): the F(4,3)-by-rows kernel returns Inf / NaN, never a plausible wrong number, as
+    tests/test_gpu_conv.test_winograd_f4_split_operand_kernel asserts for the F(4x4) kernel."""
+    L = R64.tame_layer(64, 64, 3, 78)
+    x = (np.random.default_rng(78).standard_normal((64, 24, 40)) * 2.0e4).astype(np.float32)
+    got, fam = Case("f4x1", "d", "normal x 2e4", L, x).launch(FORCE["f4x1"])
+    assert fam == 5 and not np.isfinite(got).all(), "overflow of the f16 pieces must not pass silently"
 
 
 def test_fam_multiply_through_the_direct_split_kernel(hip):
@@ -304,33 +409,43 @@ def test_unet_with_checkpoint_like_statistics_against_fp64(hip):
     FLOAT64 (state and inputs cast: the restatement takes its dtype from them), at the three network guards of tests/test_gpu_unet.py
     (MAX_ABS, MIN_PSNR, MAX_REL_RMS).  The input of the Winograd layer Decoder.0.layers.0.main.1, recomputed in float64 from the tap `zb`,
     is brought to a maximum of 300 by scaling its largest channel (the same function-preserving exchange) and must then exceed 100
-    somewhere and stay below the documented 650: the split kernel's range is exercised, not just its middle."""
+    somewhere and stay below the documented 650: the split kernel's range is exercised, not just its middle.
+    Second pass: the same exchange to a maximum of 3000 — inside the F(4,3)-by-rows kernel's documented ~6500 and outside F(4x4)'s 650 —
+    with the engine's default plan, after asserting that this plan is what it names: conv_f4x1 = 32 and the engine holds the
+    F(4,3)-by-rows side buffer.  The same three guards."""
     from oracle import unet_torch
-    from read_amd import synthetic
+    from read_amd import _lib, synthetic
     from read_amd.unet import UNetEngine, pack_state
     from tests.test_gpu_unet import _check_rgb
     from tests.unet_spec import UNET_SPEC
     H, W = 96, 160
-    state = rescale_like_a_checkpoint(synthetic.make_unet_state(UNET_SPEC, 9), 17)
+    base = rescale_like_a_checkpoint(synthetic.make_unet_state(UNET_SPEC, 9), 17)
     torch.manual_seed(3)
     xs = [torch.rand(H >> l, W >> l, 8) for l in range(4)]
     x64 = [x.permute(2, 0, 1)[None].double() for x in xs]
     to64 = lambda st: {k: torch.from_numpy(np.asarray(v)).double() for k, v in st.items() if np.asarray(v).dtype.kind == "f"}   # noqa: E731
     taps = {}
     with torch.no_grad():
-        unet_torch.unet_forward(to64(state), *x64, taps=taps)
-        inner = unet_torch.basic_conv(to64(state), "Decoder.0.layers.0.main.0", taps["zb"], 3)[0]
-        per_channel = inner.abs().amax(dim=(1, 2))
-        c = int(per_channel.argmax())
-        state = scale_inner_channel(state, "Decoder.0.layers.0", c, 300.0 / float(per_channel[c]))
-        st64 = to64(state)
-        ref = unet_torch.unet_forward(st64, *x64, taps=taps)[0]
-        inner = unet_torch.basic_conv(st64, "Decoder.0.layers.0.main.0", taps["zb"], 3)
-    top = float(inner.abs().max())
-    print("input of Decoder.0.layers.0.main.1: max |x| = %.1f" % top)
-    assert ref.dtype == torch.float64 and 100.0 < top < 650.0, top
-    eng = UNetEngine(torch.from_numpy(pack_state(state)).cuda(), H, W)
-    kinds = [k for (_, _, _, k) in eng.profile(*[x.cuda() for x in xs])]
-    assert kinds.count(5) >= 70, kinds                                              # the residual blocks run on the Winograd split-operand kernel
-    got = eng.forward(*[x.cuda() for x in xs]).permute(2, 0, 1).cpu()
-    _check_rgb(got, ref, "checkpoint-like statistics against fp64")
+        unet_torch.unet_forward(to64(base), *x64, taps=taps)
+        inner = unet_torch.basic_conv(to64(base), "Decoder.0.layers.0.main.0", taps["zb"], 3)[0]
+    per_channel = inner.abs().amax(dim=(1, 2))
+    c = int(per_channel.argmax())
+    L_ = _lib.lib()
+    for target, lo, hi in ((300.0, 100.0, 650.0), (3000.0, 1000.0, 6500.0)):
+        state = scale_inner_channel(base, "Decoder.0.layers.0", c, target / float(per_channel[c]))
+        with torch.no_grad():
+            st64 = to64(state)
+            ref = unet_torch.unet_forward(st64, *x64, taps=taps)[0]
+            top = float(unet_torch.basic_conv(st64, "Decoder.0.layers.0.main.0", taps["zb"], 3).abs().max())
+        print("input of Decoder.0.layers.0.main.1: max |x| = %.1f" % top)
+        assert ref.dtype == torch.float64 and lo < top < hi, top
+        eng = UNetEngine(torch.from_numpy(pack_state(state)).cuda(), H, W)
+        if target > 650.0:                                                          # the pass is about the F(4,3)-by-rows kernel: the default plan must run it
+            knob = ctypes.c_int(-1)
+            _lib.check(L_.read_tuning_get(b"conv_f4x1", ctypes.byref(knob)))
+            assert knob.value == 32, knob.value
+            assert getattr(eng, "f4x1", None) is not None and eng.f4x1.is_cuda and eng.f4x1.numel() == L_.read_unet_f4x1_floats()
+        kinds = [k for (_, _, _, k) in eng.profile(*[x.cuda() for x in xs])]
+        assert kinds.count(5) >= 70, kinds                                          # the residual blocks run on the Winograd split-operand kernels
+        got = eng.forward(*[x.cuda() for x in xs]).permute(2, 0, 1).cpu()
+        _check_rgb(got, ref, "checkpoint-like statistics against fp64, inner maximum %g" % target)

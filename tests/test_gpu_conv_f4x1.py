@@ -47,7 +47,11 @@ def _case(c, H, W, seed, amp=1.0, residual=True):
 
 
 # the four C -> C shapes of the network at an eighth of its 1216 x 352 frame per side, and odd sizes that clip the 8 x 32 units and the 1 x 4
-# tiles on all four borders (one unit, several units per workgroup, a single pixel, widths 4 k + 1 .. 4 k + 3)
+# tiles on all four borders (one unit, several units side by side and below each other, a single pixel, widths 4 k + 1 .. 4 k + 3).  Every
+# workgroup runs ONE unit here: the grid is min(units, compute units) rounded down to a multiple of the channel groups, and the largest
+# entry has 32 units.  The persistent walk (a workgroup's second and third unit) is run by shape in
+# tests/test_gpu_conv_accuracy.py::test_persistent_walk_against_fp64, and the kernel is held to a float64 reference and its derived bound
+# there (family "f4x1" of test_split_operand_family_against_fp64); the checks below are parity, dispatch and plumbing.
 SHAPES = [(32, 44, 152), (64, 22, 76), (128, 11, 38), (256, 6, 19), (32, 41, 130), (64, 13, 37), (128, 9, 17), (256, 11, 35), (96, 23, 70),
           (160, 3, 65), (64, 1, 1), (32, 5, 3), (32, 64, 96)]
 
