@@ -564,13 +564,13 @@ int read_bilinear_up4(const float *in, int inH, int inW, int C, float *out, void
 /* ---------------------------------------------------------------- training step (csrc/train.hip)
  * Backward of one BasicConv, y = BN_eval(act(f) * sigmoid(m)) with [f | m] = conv_{f|m}(x) + b (READ/models/unet.py:44-53 under
  * torch.autograd in src/train.py:132-203); BatchNorm as the eval-mode affine map (configs/train_example.yaml eval_in_train).
- *   forward (training)  read_conv_pack_params_device + read_conv_pack_weights_device, read_gated_conv_forward with
+ *   forward (training)  a READ_PACK_PARAMS and a mode-0 fragment job (read_pack_job below), read_gated_conv_forward with
  *                       desc.linear = 1 -> pre-activations [pixels][2*Cout], read_gate_forward -> y
  *   backward            read_gate_backward: dy, [f|m] -> dfm [pixels][2*Cp] (Cp = Cout rounded up to 8; df | dm) and the
  *                       per-channel sums S[4][Cout] += {sum df, sum dm, sum dy, sum dy*g} (ACCUMULATED: the caller zero-fills S —
  *                       one fill for all layers of a step; read_gate_backward_bn clears its own); read_bn_param_grads turns them
  *                       into db_f, db_m, dgamma, dbeta (accumulating);
- *                       dgrad: stride 1 -> read_conv_pack_dgrad_device + read_gated_conv_forward(linear = 1) over dfm with
+ *                       dgrad: stride 1 -> a mode-1 fragment job + read_gated_conv_forward(linear = 1) over dfm with
  *                       Cout := Cin/2, zero biases (the same MFMA kernel with flipped, transposed weights);
  *                       stride 2 -> read_conv_dgrad_generic;
  *                       read_conv_wgrad: x, dfm -> dW_f, dW_m in the PyTorch layout (Cout, Cin, k, k), MFMA, split over
@@ -578,38 +578,29 @@ int read_bilinear_up4(const float *in, int inH, int inW, int C, float *out, void
  *                       images of whole 4 x 4 tiles are summed in the Winograd F(4x4,3x3) domain (dg = G^T [sum over tiles of
  *                       (B^T d B) . (A dY A^T)] G: a quarter of the multiplications; read_tuning_set("wgrad_wino", 0): direct
  *                       kernel); read_conv_wgrad_family says which: 4 or 0. */
-int read_conv_pack_params_device(int Cout, const float *bf, const float *bm, const float *gamma, const float *beta,
-                                 const float *mean, const float *var, float eps, float *params, void *stream);
-int read_conv_pack_weights_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm, float *wpacked,
-                                  void *stream);
-/* Winograd fragments (3x3 / stride 1, Cin % 16 == 0) of the layer's own weights and of its dgrad weights, produced on the
- * device: with desc.wpacked_wino set, linear-mode launches of eligible layers take the Winograd kernel too. */
-int read_conv_pack_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino, void *stream);
-size_t read_conv_dgrad_wino_floats(int Cin, int Cout);
-int read_conv_pack_dgrad_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino, void *stream);
-/* ... and the Winograd F(4x4,3x3) fragments (read_conv_pack_w4_host's order; desc.wpacked_w4): linear-mode launches of layers
- * with Cin >= 32 and Cout % 32 == 0 (the dgrad's virtual layer: 2 * pad8(Cout) input and Cin / 2 gated output channels) then run
- * on the F(4x4) kernel, which stores the pre-activations and — with desc.out_gated — the gated output in the same pass. */
-int read_conv_pack_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream);
-size_t read_conv_dgrad_w4_floats(int Cin, int Cout);
-int read_conv_pack_dgrad_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream);
-size_t read_conv_dgrad_packed_floats(int Cin, int Cout, int ksize);
-int read_conv_pack_dgrad_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm, float *wpacked,
-                                void *stream);
-/* All packing jobs of a training step in ONE launch.  The optimizer changes every weight every step, so a step re-packs the
- * parameter block, the forward fragments and the dgrad fragments of every layer: the entry points above are one launch each
- * (297 per step for READ's UNet).  A host that knows its layers builds a table of jobs ONCE (the tensors keep their addresses
- * across optimizer steps), uploads it, and calls read_conv_pack_batch once per step.
- *   kind READ_PACK_PARAMS: out[4 * pad32(Cout)] = bias_f, bias_m, bn scale, bn shift   (read_conv_pack_params_device)
- *        READ_PACK_DIRECT / _WINO / _W4: the fragment order of read_conv_pack_weights_device / _wino_device / _w4_device;
- *        mode 1 = the layer's dgrad fragments (read_conv_pack_dgrad_device / _dgrad_wino_device / _dgrad_w4_device).
- * read_conv_pack_job_prepare (host) validates a job and fills Cp / total / nblocks; the caller then sets first_block to the
- * running sum of nblocks and passes the grand total as total_blocks. */
+/* Packing on the device.  The optimizer changes every weight every step, so a step re-packs the parameter block, the forward
+ * fragments and the dgrad fragments of every layer (294 jobs for READ's UNet).  ONE job type describes them all:
+ *   kind READ_PACK_PARAMS: out[4 * pad32(Cout)] = bias_f, bias_m, bn scale, bn shift   (read_conv_pack_params_host's block)
+ *        READ_PACK_DIRECT: the direct fragment order of read_conv_pack_weights_host (ksize 1 / 3 / 4, chunk kc)
+ *        READ_PACK_WINO / READ_PACK_W4: the Winograd F(2x2,3x3) / F(4x4,3x3) orders of read_conv_pack_wino_host / _w4_host
+ *        (3x3 / stride 1, Cin % 16 == 0; desc.wpacked_wino / desc.wpacked_w4: linear-mode launches of eligible layers then take
+ *        those kernels, the F(4x4) one where Cin >= 32 and Cout % 8 == 0, storing the pre-activations and — with desc.out_gated —
+ *        the gated output in the same pass)
+ *   mode 0: the layer's own weights; mode 1: its dgrad as a convolution over d[f|m] — the virtual layer with 2 * pad8(Cout)
+ *        input and Cin / 2 gated output channels, weights flipped and transposed (Cin even; sizes: read_conv_dgrad_*_floats).
+ * read_conv_pack_job_prepare (host) is the one place that validates a job (READ_EINVAL and a message otherwise) and fills
+ * Cp / total / nblocks.  Two ways to run jobs:
+ *   read_conv_pack_job(job_host, stream): prepare, then ONE launch with the job passed by value (a direct-order job on its own is
+ *        spread over more workgroups than the nblocks it takes in a table; the packer is grid-strided, the output the same);
+ *   read_conv_pack_batch: every job of a step in ONE launch.  A host that knows its layers builds the table ONCE (the tensors keep
+ *        their addresses across optimizer steps): prepare each job, set first_block to the running sum of nblocks, upload the table
+ *        and pass the grand total as total_blocks, once per step.
+ * The read_conv_pack_*_device entry points are read_conv_pack_job with the job filled from their arguments. */
 enum { READ_PACK_PARAMS = 0, READ_PACK_DIRECT = 1, READ_PACK_WINO = 2, READ_PACK_W4 = 3 };
 typedef struct read_pack_job {
     int kind, mode;                         /* mode: 0 the layer's own weights, 1 its dgrad */
-    int Cin, Cout, ksize, kc;               /* kc: channel chunk of the direct order (8 / 16 / 32) */
-    int Cp, first_block, nblocks;           /* derived (prepare) / prefix sum (caller) */
+    int Cin, Cout, ksize, kc;               /* kc: channel chunk of the direct order (8 / 16; 32 for a 1x1 layer's own weights) */
+    int Cp, first_block, nblocks;           /* derived (prepare) / prefix sum (caller, read_conv_pack_batch only) */
     float eps;                              /* params job: BatchNorm epsilon */
     const float *wf, *wm;                   /* (Cout, Cin, k, k) conv_f / conv_m weights */
     const float *bf, *bm, *gamma, *beta, *mean, *var;   /* params job (bf / bm may be NULL) */
@@ -617,7 +608,21 @@ typedef struct read_pack_job {
     long long total;                        /* floats written (derived) */
 } read_pack_job;
 int read_conv_pack_job_prepare(read_pack_job *job);
+int read_conv_pack_job(read_pack_job *job_host, void *stream);
 int read_conv_pack_batch(const read_pack_job *jobs_dev, int njobs, int total_blocks, void *stream);
+int read_conv_pack_params_device(int Cout, const float *bf, const float *bm, const float *gamma, const float *beta,
+                                 const float *mean, const float *var, float eps, float *params, void *stream);
+int read_conv_pack_weights_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm, float *wpacked,
+                                  void *stream);
+int read_conv_pack_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino, void *stream);
+int read_conv_pack_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream);
+size_t read_conv_dgrad_packed_floats(int Cin, int Cout, int ksize);
+size_t read_conv_dgrad_wino_floats(int Cin, int Cout);
+size_t read_conv_dgrad_w4_floats(int Cin, int Cout);
+int read_conv_pack_dgrad_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm, float *wpacked,
+                                void *stream);
+int read_conv_pack_dgrad_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino, void *stream);
+int read_conv_pack_dgrad_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream);
 /* A training batch is ONE tall image: the items stacked vertically, block_h rows per item of which the first valid_h are
  * the item and the rest a separator that stays zero in every activation — it is the zero padding between neighbours, so the
  * convolutions need no batch dimension and one launch covers the batch.  The gate kernels keep the separators zero (forward)

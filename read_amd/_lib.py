@@ -42,7 +42,7 @@ class ConvDesc(C.Structure):
 
 
 class PackJob(C.Structure):
-    """read_pack_job (include/read_hip.h): one entry of read_conv_pack_batch's table."""
+    """read_pack_job (include/read_hip.h): one packing job, for read_conv_pack_job or as an entry of read_conv_pack_batch's table."""
     _fields_ = [("kind", C.c_int), ("mode", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("ksize", C.c_int), ("kc", C.c_int),
                 ("Cp", C.c_int), ("first_block", C.c_int), ("nblocks", C.c_int), ("eps", C.c_float),
                 ("wf", C.c_void_p), ("wm", C.c_void_p), ("bf", C.c_void_p), ("bm", C.c_void_p), ("gamma", C.c_void_p),
@@ -172,6 +172,7 @@ SIGNATURES = {
     "read_conv_sc_floats": (_sz, [_i, _i]),
     "read_conv_pack_sc_host": (_i, [_i, _i, _vp, _vp, _vp]),
     "read_conv_pack_job_prepare": (_i, [C.POINTER(PackJob)]),
+    "read_conv_pack_job": (_i, [C.POINTER(PackJob), _vp]),
     "read_conv_pack_batch": (_i, [_vp, _i, _i, _vp]),
     "read_conv_config_count": (_i, []),
     "read_conv_config_name": (C.c_char_p, [_i]),

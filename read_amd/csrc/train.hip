@@ -7,11 +7,11 @@
 //                       gate_forward_kernel                   -> y
 //   backward            gate_backward_kernel   dy, [f|m] -> d[f|m] (channel-padded) + per-channel sums for db_f, db_m, dgamma, dbeta
 //                       dgrad                  d[f|m] -> dx: for stride-1 layers the SAME MFMA convolution kernel with flipped,
-//                                              transposed weights (pack_dgrad_weights_kernel + linear = 1); stride 2: dgrad_generic_kernel
+//                                              transposed weights (a mode-1 packing job + linear = 1); stride 2: dgrad_generic_kernel
 //                       wgrad_mfma_kernel      x, d[f|m] -> dW_f, dW_m on the matrix cores (pixels are the reduction dimension)
 // BatchNorm is the eval-mode affine map (running statistics frozen, gamma/beta trained) — the configuration the reference
 // trains with (configs/train_example.yaml: eval_in_train: True, train.py:271-277).
-// Weights change every optimizer step, so the MFMA fragment orders are produced on the device (pack_*_kernel).
+// Weights change every optimizer step, so the MFMA fragment orders are produced on the device (pack_batch_kernel / pack_job_kernel).
 #include "common.h"
 #include "internal.h"
 
@@ -43,11 +43,6 @@ __device__ __forceinline__ void pack_params_body(int c, int Cout, int CoutPad, c
     out[CoutPad + c] = ok && bm ? bm[c] : 0.0f;
     out[2 * CoutPad + c] = sc;
     out[3 * CoutPad + c] = ok ? beta[c] - mean[c] * sc : 0.0f;
-}
-__global__ void pack_params_kernel(int Cout, int CoutPad, const float *bf, const float *bm, const float *gamma,
-                                   const float *beta, const float *mean, const float *var, float eps, float *out)
-{
-    pack_params_body(blockIdx.x * blockDim.x + threadIdx.x, Cout, CoutPad, bf, bm, gamma, beta, mean, var, eps, out);
 }
 
 // Direct-kernel fragment order of read_conv_pack_weights_host: [chunk][tap][k8][tile(f,m)][lane][4].
@@ -83,14 +78,9 @@ __device__ __forceinline__ void pack_weights_body(int bid, int nblk, int mode, i
         out[o] = v;
     }
 }
-__global__ void pack_weights_kernel(int mode, int Cin, int Cout, int ksize, int kc, int Cp, const float *wf, const float *wm,
-                                    float *out, long long total)
-{
-    pack_weights_body((int)blockIdx.x, (int)gridDim.x, mode, Cin, Cout, ksize, kc, Cp, wf, wm, out, total);
-}
 
 // The 3x3 kernel of the (virtual) layer's (cout, cin) pair, or null where the pair does not exist.  mode 0: the layer's own weights;
-// mode 1: dgrad as a convolution over d[f|m] (pack_weights_kernel): flipped, transposed.
+// mode 1: dgrad as a convolution over d[f|m] (pack_weights_body): flipped, transposed.
 __device__ __forceinline__ const float *w3x3_of(int mode, int Cin, int Cout, int Cp, const float *wf, const float *wm, int fm, int co,
                                                 int ci, int CoutV)
 {
@@ -135,10 +125,6 @@ __device__ __forceinline__ void pack_wino_body(int bid, int mode, int Cin, int C
         }
     }
 }
-__global__ __launch_bounds__(256) void pack_wino_kernel(int mode, int Cin, int Cout, int Cp, const float *wf, const float *wm, float *out)
-{
-    pack_wino_body((int)blockIdx.x, mode, Cin, Cout, Cp, wf, wm, out);
-}
 
 // Winograd F(4x4,3x3) fragment order of read_conv_pack_w4_host: U = G g G^T (6 x 6, evaluated in double, rounded once) per
 // (cout, cin) pair, [group][wave 4][chunk of 16 cin][frequency 6 xi + nu][lane][e]; lane (i = lane & 15, kl = lane >> 4) =
@@ -177,9 +163,28 @@ __device__ __forceinline__ void pack_w4_body(int bid, int mode, int Cin, int Cou
         for (int nu = 0; nu < 6; ++nu) o[(xi * 6 + nu) * 256] = (float)u[nu];
     }
 }
-__global__ __launch_bounds__(256) void pack_w4_kernel(int mode, int Cin, int Cout, int Cp, const float *wf, const float *wm, float *out)
+
+// Block `bid` of a packing job: the ONE road into the packer bodies, for a job of the step's table (pack_batch_kernel) and for a
+// job launched on its own (pack_job_kernel).
+__device__ __forceinline__ void pack_job_body(const read_pack_job &j, int bid)
 {
-    pack_w4_body((int)blockIdx.x, mode, Cin, Cout, Cp, wf, wm, out);
+    switch (j.kind) {
+    case READ_PACK_PARAMS:
+        pack_params_body(bid * 256 + (int)threadIdx.x, j.Cout, (j.Cout + 31) / 32 * 32, j.bf, j.bm, j.gamma, j.beta, j.mean, j.var, j.eps,
+                         j.out);
+        break;
+    case READ_PACK_DIRECT:
+        pack_weights_body(bid, j.nblocks, j.mode, j.Cin, j.Cout, j.ksize, j.kc, j.Cp, j.wf, j.wm, j.out, j.total);
+        break;
+    case READ_PACK_WINO:
+        pack_wino_body(bid, j.mode, j.Cin, j.Cout, j.Cp, j.wf, j.wm, j.out);
+        break;
+    case READ_PACK_W4:
+        pack_w4_body(bid, j.mode, j.Cin, j.Cout, j.Cp, j.wf, j.wm, j.out);
+        break;
+    default:
+        break;
+    }
 }
 
 // Every packing job of a training step in ONE launch (read_conv_pack_batch): a step re-packs the parameter block, the forward
@@ -202,24 +207,11 @@ __global__ __launch_bounds__(256) void pack_batch_kernel(const read_pack_job *__
     const read_pack_job j = jobs[s_job];
     const int bid = (int)blockIdx.x - j.first_block;
     if (bid >= j.nblocks) return;
-    switch (j.kind) {
-    case READ_PACK_PARAMS:
-        pack_params_body(bid * 256 + (int)threadIdx.x, j.Cout, (j.Cout + 31) / 32 * 32, j.bf, j.bm, j.gamma, j.beta, j.mean, j.var, j.eps,
-                         j.out);
-        break;
-    case READ_PACK_DIRECT:
-        pack_weights_body(bid, j.nblocks, j.mode, j.Cin, j.Cout, j.ksize, j.kc, j.Cp, j.wf, j.wm, j.out, j.total);
-        break;
-    case READ_PACK_WINO:
-        pack_wino_body(bid, j.mode, j.Cin, j.Cout, j.Cp, j.wf, j.wm, j.out);
-        break;
-    case READ_PACK_W4:
-        pack_w4_body(bid, j.mode, j.Cin, j.Cout, j.Cp, j.wf, j.wm, j.out);
-        break;
-    default:
-        break;
-    }
+    pack_job_body(j, bid);
 }
+
+// One job on its own (read_conv_pack_job): the job travels by value in the kernel arguments, nblocks workgroups of 256.
+__global__ __launch_bounds__(256) void pack_job_kernel(const read_pack_job j) { pack_job_body(j, (int)blockIdx.x); }
 
 // weights for dgrad_generic_kernel: [tap][co' in 2*Cp][ci]  (ci contiguous)
 __global__ void pack_dgrad_generic_kernel(int Cin, int Cout, int taps, int Cp, const float *wf, const float *wm, float *out,
@@ -1132,116 +1124,13 @@ __global__ __launch_bounds__(256) void rmsprop_sparse_kernel(float *__restrict__
 // ---------------------------------------------------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------------------------------------------------
-extern "C" int read_conv_pack_params_device(int Cout, const float *bf, const float *bm, const float *gamma, const float *beta,
-                                            const float *mean, const float *var, float eps, float *params, void *stream)
-{
-    READ_CHECK_ARG(Cout >= 1 && gamma && beta && mean && var && params, "read_conv_pack_params_device: null pointer");
-    const int CoutPad = (Cout + 31) / 32 * 32;
-    hipLaunchKernelGGL(pack_params_kernel, dim3(ceil_div(CoutPad, 64)), dim3(64), 0, as_stream(stream), Cout, CoutPad, bf, bm,
-                       gamma, beta, mean, var, eps, params);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
-}
-
-extern "C" int read_conv_pack_weights_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm,
-                                             float *wpacked, void *stream)
-{
-    READ_CHECK_ARG(wf && wm && wpacked, "read_conv_pack_weights_device: null pointer");
-    READ_CHECK_ARG(ksize == 1 || ksize == 3 || ksize == 4, "read_conv_pack_weights_device: ksize must be 1, 3 or 4");
-    READ_CHECK_ARG((kc == 8 || kc == 16 || (kc == 32 && ksize == 1)) && Cin >= kc && Cin % kc == 0,
-                   "read_conv_pack_weights_device: Cin=%d is not a multiple of kc=%d", Cin, kc);
-    const long long total = (long long)read_conv_packed_floats(Cin, Cout, ksize);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), 0, Cin, Cout, ksize, kc, 0,
-                       wf, wm, wpacked, total);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
-}
-
-extern "C" int read_conv_pack_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino, void *stream)
-{
-    READ_CHECK_ARG(wf && wm && wpacked_wino, "read_conv_pack_wino_device: null pointer");
-    READ_CHECK_ARG(Cin >= 16 && Cin % 16 == 0 && Cout >= 1, "read_conv_pack_wino_device: needs Cin %% 16 == 0 (got %d)", Cin);
-    const long long total = (long long)read_conv_wino_floats(Cin, Cout);
-    hipLaunchKernelGGL(pack_wino_kernel, dim3((unsigned)(total / (32 * 256))), dim3(256), 0, as_stream(stream), 0, Cin, Cout, 0, wf, wm,
-                       wpacked_wino);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
-}
-
-extern "C" size_t read_conv_dgrad_wino_floats(int Cin, int Cout)
-{
-    if (Cin < 2 || Cin % 2 || Cout < 1) return 0;
-    return read_conv_wino_floats(2 * ((Cout + 7) / 8 * 8), Cin / 2);
-}
-
-extern "C" int read_conv_pack_dgrad_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino,
-                                                void *stream)
-{
-    READ_CHECK_ARG(wf && wm && wpacked_wino, "read_conv_pack_dgrad_wino_device: null pointer");
-    READ_CHECK_ARG(Cin >= 2 && Cin % 2 == 0 && Cout >= 1, "read_conv_pack_dgrad_wino_device: Cin must be even");
-    const int Cp = (Cout + 7) / 8 * 8;
-    const long long total = (long long)read_conv_dgrad_wino_floats(Cin, Cout);
-    hipLaunchKernelGGL(pack_wino_kernel, dim3((unsigned)(total / (32 * 256))), dim3(256), 0, as_stream(stream), 1, Cin, Cout, Cp, wf, wm,
-                       wpacked_wino);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
-}
-
-extern "C" int read_conv_pack_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream)
-{
-    READ_CHECK_ARG(wf && wm && wpacked_w4, "read_conv_pack_w4_device: null pointer");
-    READ_CHECK_ARG(Cin >= 16 && Cin % 16 == 0 && Cout >= 1, "read_conv_pack_w4_device: needs Cin %% 16 == 0 (got %d)", Cin);
-    const long long total = (long long)read_conv_w4_floats(Cin, Cout);
-    hipLaunchKernelGGL(pack_w4_kernel, dim3((unsigned)(total / (36 * 256))), dim3(256), 0, as_stream(stream), 0, Cin, Cout, 0, wf, wm, wpacked_w4);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
-}
-
-extern "C" size_t read_conv_dgrad_w4_floats(int Cin, int Cout)
-{
-    if (Cin < 2 || Cin % 2 || Cout < 1) return 0;
-    return read_conv_w4_floats(2 * ((Cout + 7) / 8 * 8), Cin / 2);
-}
-
-extern "C" int read_conv_pack_dgrad_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream)
-{
-    READ_CHECK_ARG(wf && wm && wpacked_w4, "read_conv_pack_dgrad_w4_device: null pointer");
-    READ_CHECK_ARG(Cin >= 2 && Cin % 2 == 0 && Cout >= 1, "read_conv_pack_dgrad_w4_device: Cin must be even");
-    const int Cp = (Cout + 7) / 8 * 8;
-    const long long total = (long long)read_conv_dgrad_w4_floats(Cin, Cout);
-    hipLaunchKernelGGL(pack_w4_kernel, dim3((unsigned)(total / (36 * 256))), dim3(256), 0, as_stream(stream), 1, Cin, Cout, Cp, wf, wm, wpacked_w4);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
-}
-
-extern "C" size_t read_conv_dgrad_packed_floats(int Cin, int Cout, int ksize)
-{
-    if (Cin < 2 || Cin % 2 || Cout < 1) return 0;
-    const int Cp = (Cout + 7) / 8 * 8;
-    return read_conv_packed_floats(2 * Cp, Cin / 2, ksize);
-}
-
-extern "C" int read_conv_pack_dgrad_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm,
-                                           float *wpacked, void *stream)
-{
-    READ_CHECK_ARG(wf && wm && wpacked, "read_conv_pack_dgrad_device: null pointer");
-    READ_CHECK_ARG(Cin >= 2 && Cin % 2 == 0, "read_conv_pack_dgrad_device: Cin must be even");
-    const int Cp = (Cout + 7) / 8 * 8;
-    READ_CHECK_ARG((kc == 8 || kc == 16) && (2 * Cp) % kc == 0, "read_conv_pack_dgrad_device: 2*pad8(Cout)=%d is not a multiple of kc=%d",
-                   2 * Cp, kc);
-    const long long total = (long long)read_conv_dgrad_packed_floats(Cin, Cout, ksize);
-    hipLaunchKernelGGL(pack_weights_kernel, dim3(grid_for(total)), dim3(256), 0, as_stream(stream), 1, Cin, Cout, ksize, kc, Cp,
-                       wf, wm, wpacked, total);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
-}
-
 // Fills the derived fields of a packing job (Cp, total, nblocks) from its kind / mode / shape; first_block stays the caller's.
+// The ONE place that validates a packing job and sizes its launch, whichever entry point it came through.
 extern "C" int read_conv_pack_job_prepare(read_pack_job *job)
 {
     READ_CHECK_ARG(job, "read_conv_pack_job_prepare: null job");
     read_pack_job &j = *job;
-    READ_CHECK_ARG(j.Cout >= 1 && j.out, "read_conv_pack_job_prepare: bad job (Cout %d)", j.Cout);
+    READ_CHECK_ARG(j.Cout >= 1 && j.out, "read_conv_pack_job_prepare: null output or bad job (Cout %d)", j.Cout);
     j.Cp = (j.Cout + 7) / 8 * 8;
     if (j.kind == READ_PACK_PARAMS) {
         READ_CHECK_ARG(j.gamma && j.beta && j.mean && j.var, "read_conv_pack_job_prepare: params job needs gamma / beta / mean / var");
@@ -1249,14 +1138,17 @@ extern "C" int read_conv_pack_job_prepare(read_pack_job *job)
         j.nblocks = ((j.Cout + 31) / 32 * 32 + 255) / 256;
         return READ_OK;
     }
-    READ_CHECK_ARG(j.wf && j.wm && j.Cin >= 2 && (j.mode == 0 || j.Cin % 2 == 0), "read_conv_pack_job_prepare: bad weights job");
+    READ_CHECK_ARG(j.wf && j.wm, "read_conv_pack_job_prepare: null weights");
+    READ_CHECK_ARG(j.Cin >= 2 && (j.mode == 0 || j.Cin % 2 == 0), "read_conv_pack_job_prepare: bad weights job (Cin %d; a dgrad needs it even)",
+                   j.Cin);
     const int CinV = j.mode ? 2 * j.Cp : j.Cin, CoutV = j.mode ? j.Cin / 2 : j.Cout;
     if (j.kind == READ_PACK_DIRECT) {
         READ_CHECK_ARG(j.ksize == 1 || j.ksize == 3 || j.ksize == 4, "read_conv_pack_job_prepare: ksize must be 1, 3 or 4");
-        READ_CHECK_ARG((j.kc == 8 || j.kc == 16 || (j.kc == 32 && j.ksize == 1)) && CinV % j.kc == 0,
+        // (the 32-channel chunk exists for 1x1 forward launches only: read_conv_pack_weights_host)
+        READ_CHECK_ARG((j.kc == 8 || j.kc == 16 || (j.kc == 32 && j.ksize == 1 && j.mode == 0)) && CinV % j.kc == 0,
                        "read_conv_pack_job_prepare: %d input channels are not a multiple of kc=%d", CinV, j.kc);
         j.total = (long long)read_conv_packed_floats(CinV, CoutV, j.ksize);
-        const long long b = (j.total + 256 * 8 - 1) / (256 * 8);
+        const long long b = (j.total + 256 * 8 - 1) / (256 * 8);               // pack_weights_body is grid-strided: any count is right
         j.nblocks = (int)(b < 1 ? 1 : (b > 64 ? 64 : b));
     } else if (j.kind == READ_PACK_WINO) {
         READ_CHECK_ARG(CinV % 16 == 0, "read_conv_pack_job_prepare: Winograd fragments need Cin %% 16 == 0 (got %d)", CinV);
@@ -1270,6 +1162,89 @@ extern "C" int read_conv_pack_job_prepare(read_pack_job *job)
         READ_CHECK_ARG(false, "read_conv_pack_job_prepare: unknown kind %d", j.kind);
     }
     return READ_OK;
+}
+
+extern "C" int read_conv_pack_job(read_pack_job *job_host, void *stream)
+{
+    const int rc = read_conv_pack_job_prepare(job_host);
+    if (rc != READ_OK) return rc;
+    read_pack_job j = *job_host;
+    // A direct-order job on its own has the chip to itself: one element per thread, as the single launch always had (prepare's count,
+    // at most 64 workgroups, is sized for a table whose jobs share one launch).  pack_weights_body is grid-strided: same output.
+    if (j.kind == READ_PACK_DIRECT) j.nblocks = grid_for(j.total);
+    hipLaunchKernelGGL(pack_job_kernel, dim3((unsigned)j.nblocks), dim3(256), 0, as_stream(stream), j);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+// The single-job entry points of the ABI: fill a job, read_conv_pack_job.
+static int pack_weights_job(int kind, int mode, int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm, float *out, void *stream)
+{
+    read_pack_job j = {};
+    j.kind = kind, j.mode = mode, j.Cin = Cin, j.Cout = Cout, j.ksize = ksize, j.kc = kc;
+    j.wf = wf, j.wm = wm, j.out = out;
+    return read_conv_pack_job(&j, stream);
+}
+
+extern "C" int read_conv_pack_params_device(int Cout, const float *bf, const float *bm, const float *gamma, const float *beta,
+                                            const float *mean, const float *var, float eps, float *params, void *stream)
+{
+    read_pack_job j = {};
+    j.kind = READ_PACK_PARAMS, j.Cout = Cout, j.eps = eps;
+    j.bf = bf, j.bm = bm, j.gamma = gamma, j.beta = beta, j.mean = mean, j.var = var, j.out = params;
+    return read_conv_pack_job(&j, stream);
+}
+
+extern "C" int read_conv_pack_weights_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm,
+                                             float *wpacked, void *stream)
+{
+    return pack_weights_job(READ_PACK_DIRECT, 0, Cin, Cout, ksize, kc, wf, wm, wpacked, stream);
+}
+
+extern "C" int read_conv_pack_dgrad_device(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm,
+                                           float *wpacked, void *stream)
+{
+    return pack_weights_job(READ_PACK_DIRECT, 1, Cin, Cout, ksize, kc, wf, wm, wpacked, stream);
+}
+
+extern "C" int read_conv_pack_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino, void *stream)
+{
+    return pack_weights_job(READ_PACK_WINO, 0, Cin, Cout, 3, 16, wf, wm, wpacked_wino, stream);
+}
+
+extern "C" int read_conv_pack_dgrad_wino_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_wino,
+                                                void *stream)
+{
+    return pack_weights_job(READ_PACK_WINO, 1, Cin, Cout, 3, 16, wf, wm, wpacked_wino, stream);
+}
+
+extern "C" int read_conv_pack_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream)
+{
+    return pack_weights_job(READ_PACK_W4, 0, Cin, Cout, 3, 16, wf, wm, wpacked_w4, stream);
+}
+
+extern "C" int read_conv_pack_dgrad_w4_device(int Cin, int Cout, const float *wf, const float *wm, float *wpacked_w4, void *stream)
+{
+    return pack_weights_job(READ_PACK_W4, 1, Cin, Cout, 3, 16, wf, wm, wpacked_w4, stream);
+}
+
+// Sizes of the dgrad's fragment orders: those of its virtual layer, 2 * pad8(Cout) input and Cin / 2 gated output channels.
+extern "C" size_t read_conv_dgrad_packed_floats(int Cin, int Cout, int ksize)
+{
+    if (Cin < 2 || Cin % 2 || Cout < 1) return 0;
+    return read_conv_packed_floats(2 * ((Cout + 7) / 8 * 8), Cin / 2, ksize);
+}
+
+extern "C" size_t read_conv_dgrad_wino_floats(int Cin, int Cout)
+{
+    if (Cin < 2 || Cin % 2 || Cout < 1) return 0;
+    return read_conv_wino_floats(2 * ((Cout + 7) / 8 * 8), Cin / 2);
+}
+
+extern "C" size_t read_conv_dgrad_w4_floats(int Cin, int Cout)
+{
+    if (Cin < 2 || Cin % 2 || Cout < 1) return 0;
+    return read_conv_w4_floats(2 * ((Cout + 7) / 8 * 8), Cin / 2);
 }
 
 extern "C" int read_conv_pack_batch(const read_pack_job *jobs_dev, int njobs, int total_blocks, void *stream)

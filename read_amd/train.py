@@ -14,6 +14,10 @@ HIP kernels of csrc/train.hip + csrc/conv.hip:
   SparseDescriptorRMSprop   RMSprop over the descriptor rows a step touched (the reference sweeps all N rows: 960 MB of
                              gradient + state at 30 M points every step)
 
+Routing lives in ONE place: ``layer_route`` says which fragment orders a layer's launches read (forward, dgrad, polyphase),
+``dgrad_method`` which dgrad runs it; both are pure.  ``_layer_jobs`` turns a route into the layer's packing jobs — the step's
+``_PackPlan`` runs all of them in one launch, the per-layer path (``_packed_for`` / ``_pack_dgrad``) the same jobs one by one.
+
 The graph around the convolutions (torch.cat, nearest resampling, FAM's product, residual adds) is expressed with torch
 tensor ops on the device so that autograd does the bookkeeping of the 99-layer graph; every FLOP-carrying node is HIP.
 BatchNorm: with the net in ``.eval()`` (configs/train_example.yaml ``eval_in_train: True``; train.py:271-277) it is the
@@ -24,6 +28,7 @@ layer normalises with the statistics of the batch and moves its running buffers 
 import ctypes as C
 import os
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -38,16 +43,62 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
-def _kc_for(cin):
+# -----------------------------------------------------------------------------------------------------------------------
+# One route per layer: which fragment orders its launches read, and which dgrad runs it
+# -----------------------------------------------------------------------------------------------------------------------
+class LayerRoute(NamedTuple):
+    """What a layer's training launches read, decided ONCE from its shape and the module switches (layer_route).  Kinds are the
+    packing kinds of read_pack_job (_lib.PACK_DIRECT / PACK_WINO / PACK_W4); ONE fragment order per layer, direction and step: the
+    Winograd order where that kernel runs the launch (3x3 / stride 1), the direct order everywhere else — packing both cost 64 us
+    per layer and step for fragments nobody read."""
+    cin: int
+    cout: int
+    k: int
+    stride: int
+    fwd: int                 # forward fragments (the layer's own weights, mode 0) ...
+    fwd_kc: int              # ... and the channel chunk of the direct order (16 with the Winograd orders)
+    dgrad: Optional[int]     # dgrad fragments (flipped / transposed, mode 1); None: the dgrad is no convolution launch over them
+    dgrad_kc: int
+    poly: Optional[int]      # fragments of the four polyphase pseudo-layers (_poly_fragments); None: no polyphase dgrad
+
+
+def layer_route(cin, cout, k, stride):
+    """The route of a (cin -> cout, k x k, stride) layer under USE_WINOGRAD / USE_W4.  Pure: no library call, no tensor."""
     if cin % 8:
         raise ValueError(f"the HIP convolution needs input channels in multiples of 8 (got {cin})")
-    return 16 if cin % 16 == 0 else 8
+
+    def wino_kind(c_in, c_out):
+        # F(4x4,3x3) for the layers that kernel takes in linear mode (csrc/conv.hip conv_uses_w4): at least two 16-channel chunks,
+        # output channels in multiples of 8 (the dgrad of a 32-channel layer is a 64 -> 16 + 16 virtual layer: half a group; a
+        # padded last group is masked); F(2x2,3x3) for the rest
+        return _lib.PACK_W4 if USE_W4 and c_in % 16 == 0 and c_in >= 32 and c_out % 8 == 0 else _lib.PACK_WINO
+
+    virtual = (2 * ((cout + 7) // 8 * 8), cin // 2)         # the dgrad's virtual layer: 2 * cp -> cin / 2 gated channels (always % 16)
+    if USE_WINOGRAD and k == 3 and stride == 1 and cin % 16 == 0:
+        fwd, fwd_kc = wino_kind(cin, cout), 16
+    else:
+        fwd, fwd_kc = _lib.PACK_DIRECT, 16 if cin % 16 == 0 else 8
+    dgrad = None
+    if stride == 1 or (stride == 2 and k == 3):              # 3x3 / stride 2: the stride-1 dgrad over the zero-dilated d[f|m]
+        dgrad = wino_kind(*virtual) if USE_WINOGRAD and k == 3 else _lib.PACK_DIRECT   # the stride-1 dgrad of a 3x3 layer always runs on that kernel
+    poly = wino_kind(*virtual) if USE_WINOGRAD and stride == 2 and k in (3, 4) and cin % 16 == 0 else None
+    return LayerRoute(cin, cout, k, stride, fwd, fwd_kc, dgrad, 16, poly)
 
 
-def _w4_fits(cin, cout):
-    """Layers the Winograd F(4x4,3x3) kernel takes in linear mode (csrc/conv.hip conv_uses_w4): at least two 16-channel chunks,
-    output channels in multiples of 8 (the dgrad of a 32-channel layer is a 64 -> 16 + 16 virtual layer: half a group)."""
-    return USE_W4 and cin % 16 == 0 and cin >= 32 and cout % 8 == 0       # linear launches: a padded last group is masked
+def dgrad_method(route, H, W, capturing=False, polyphase=None):
+    """How the input gradient of a layer over an (H, W) input is computed (_dgrad runs it):
+      'conv'     stride 1: the convolution kernel over d[f|m] with the layer's dgrad fragments
+      'poly'     stride 2, even H and W: four 3x3 / stride-1 dgrads, one per pixel parity (_poly_fragments) — not inside a captured
+                 step, whose retained backward graph is walked again after the weights have changed
+      'dilated'  3x3 / stride 2, even H and W: 'conv' over the zero-dilated d[f|m]
+      'generic'  the vector kernel (read_conv_dgrad_generic)
+    polyphase: POLYPHASE_DGRAD unless given.  Pure, like layer_route."""
+    if route.stride == 1:
+        return 'conv'
+    even = H % 2 == 0 and W % 2 == 0
+    if (POLYPHASE_DGRAD if polyphase is None else polyphase) and route.poly is not None and even and not capturing:
+        return 'poly'
+    return 'dilated' if route.dgrad is not None and even else 'generic'
 
 
 def _linear_conv(x, cin, wpacked, params, cout, k, stride, out, wino=None, gated=None, w4=False):
@@ -84,9 +135,9 @@ FLOP_LOG = None
 
 
 # packed copies of a layer's weights, reused by every image of a batch (weights only change at optimizer steps, which bump
-# the parameters' _version): key = id of the conv_f weight -> (versions, params block, forward fragments, dgrad fragments)
+# the parameters' _version): key = id of the conv_f weight -> _PackEntry
 _PACK_CACHE = {}
-USE_W4 = True                # ... and through the F(4x4,3x3) kernel where its units fit (cin >= 32, cout % 32 == 0)
+USE_W4 = True                # ... and through the F(4x4,3x3) kernel where its units fit (cin >= 32, cout % 8 == 0; layer_route)
 USE_WINOGRAD = True          # 3x3 / stride-1 layers with cin % 16 == 0: forward pre-activations and dgrad through the Winograd kernel
 
 
@@ -150,103 +201,145 @@ def _zero_params(n, dev):
     return z
 
 
-def _pack_version(wf, bf, wm, bm, gamma, beta, mean, var, identity_bn):
+def _pack_version(route, ts, identity_bn):
+    wf, bf, wm, bm = ts[:4]
     if identity_bn:
-        return tuple(t._version for t in (wf, bf, wm, bm)) + (wf.data_ptr(), wm.data_ptr(), 'identity')
-    return tuple(t._version for t in (wf, bf, wm, bm, gamma, beta, mean, var)) + (wf.data_ptr(), wm.data_ptr())
+        return tuple(t._version for t in (wf, bf, wm, bm)) + (wf.data_ptr(), wm.data_ptr(), 'identity', route)
+    return tuple(t._version for t in ts) + (wf.data_ptr(), wm.data_ptr(), route)
 
 
-def _packed_for(wf, bf, wm, bm, gamma, beta, mean, var, cin, cout, k, identity_bn=False, stride=1):
-    """identity_bn (batch-statistics mode): the params block carries the two biases and scale 1 / shift 0 — the launch then
-    stores g = act(f) * sigmoid(m) itself and read_bn_train_forward normalises it."""
-    L = _lib.lib()
-    st = _lib.stream_ptr()
-    ver = _pack_version(wf, bf, wm, bm, gamma, beta, mean, var, identity_bn)
-    # While a HIP graph is being captured (GraphedTrainStep) every layer packs afresh: the packing launches must be PART of
-    # the graph — it is replayed after every optimizer step — and a cache hit would freeze the fragments of the capture step in.
-    capturing = torch.cuda.is_current_stream_capturing()
-    hit = None if capturing else _PACK_CACHE.get(id(wf))
-    if hit is not None and hit[6]() is not wf:              # the id was recycled by another tensor: not this layer's entry
-        hit = None
-    if hit is not None and hit[0] == ver:
-        if hit[4] is not None:                              # None: the step's pack plan filled it on this stream, into buffers it keeps
-            cur = torch.cuda.current_stream()
-            cur.wait_event(hit[4])                          # packed on another item's stream
-            hit[1].record_stream(cur)
-            hit[2].record_stream(cur)
-            if hit[5] is not None:
-                hit[5].record_stream(cur)
-        return hit
-    dev = wf.device
-    params = torch.empty(L.read_conv_param_floats(cout), dtype=torch.float32, device=dev)
-    if identity_bn:
-        one, zero = _const_vec(cout, 1.0, dev), _const_vec(cout, 0.0, dev)
-        _lib.check(L.read_conv_pack_params_device(cout, _ptr(bf.detach()), _ptr(bm.detach()), one.data_ptr(), zero.data_ptr(),
-                                                  zero.data_ptr(), one.data_ptr(), 0.0, params.data_ptr(), st))      # 1 / sqrt(1 + 0) = 1
-    else:
-        _lib.check(L.read_conv_pack_params_device(cout, _ptr(bf.detach()), _ptr(bm.detach()), _ptr(gamma.detach()),
-                                                  _ptr(beta.detach()), _ptr(mean), _ptr(var), BN_EPS, params.data_ptr(), st))
-    wf_c, wm_c = wf.detach().contiguous(), wm.detach().contiguous()
-    # ONE fragment order per layer and step: the Winograd order where that kernel runs the layer (3x3 / stride 1), the direct
-    # order everywhere else — packing both cost 64 us per layer and step for fragments nobody read
-    wp = wino = None
-    if k == 3 and stride == 1 and cin % 16 == 0 and USE_WINOGRAD:
-        if _w4_fits(cin, cout):
-            wino = torch.empty(L.read_conv_w4_floats(cin, cout), dtype=torch.float32, device=dev)
-            _lib.check(L.read_conv_pack_w4_device(cin, cout, wf_c.data_ptr(), wm_c.data_ptr(), wino.data_ptr(), st))
-        else:
-            wino = torch.empty(L.read_conv_wino_floats(cin, cout), dtype=torch.float32, device=dev)
-            _lib.check(L.read_conv_pack_wino_device(cin, cout, wf_c.data_ptr(), wm_c.data_ptr(), wino.data_ptr(), st))
-        wp = wino                                             # read_conv_desc.wpacked must point somewhere; it is not read
-    else:
-        wp = torch.empty(L.read_conv_packed_floats(cin, cout, k), dtype=torch.float32, device=dev)
-        _lib.check(L.read_conv_pack_weights_device(cin, cout, k, _kc_for(cin), wf_c.data_ptr(), wm_c.data_ptr(), wp.data_ptr(), st))
-    ev = None
-    if not capturing:             # an event recorded inside a capture must never be waited on from outside it (see backward)
-        ev = torch.cuda.Event()
-        ev.record()
+class _PackEntry:
+    """The packed copies of ONE layer: what _PACK_CACHE holds, what a GatedConvFn node keeps (ctx.pack), what the pack plan fills."""
+    __slots__ = ("version", "route", "params", "fwd", "dgrad", "dgrad_event", "event", "ref")
+
+    def __init__(self, version=None, route=None, params=None, fwd=None, dgrad=None, event=None):
+        self.version, self.route = version, route           # _pack_version of the tensors packed; LayerRoute
+        self.params, self.fwd = params, fwd                 # parameter block; forward fragments in the order route.fwd
+        self.dgrad, self.dgrad_event = dgrad, None          # dgrad fragments in the order route.dgrad (None: not packed) + their event
+        self.event = event                                  # params / fwd are packed; None: by the step's pack plan or inside a capture
+        self.ref = None                                     # weakref of the conv_f weight the cache key is the id of (_cache_put)
+
+    @property
+    def wino(self):          # the forward fragments where they are in a Winograd order (read_conv_desc.wpacked_wino / _w4), else None
+        return self.fwd if self.route.fwd != _lib.PACK_DIRECT else None
+
+
+def _cache_put(wf, entry):
+    """entry becomes the cache entry of the parameter wf and dies with it: ONE finalizer per parameter object, however many
+    versions of it pass through the cache."""
     key = id(wf)
     old = _PACK_CACHE.get(key)
-    if old is not None and old[6]() is wf:
-        ref = old[6]                                          # same parameter, new version: keep its finalizer's handle
+    if old is not None and old.ref() is wf:
+        entry.ref = old.ref                                   # same parameter, new version: keep its finalizer's handle
     else:
-        ref = weakref.ref(wf)
-        weakref.finalize(wf, _drop_pack, key, ref)            # the entry dies with its parameter
-    entry = [ver, params, wp, None, ev, wino, ref]
-    if not capturing:                                         # a captured entry lives in the graph's memory pool, not in the cache
-        _PACK_CACHE[key] = entry
-    return entry
+        entry.ref = weakref.ref(wf)
+        weakref.finalize(wf, _drop_pack, key, entry.ref)      # the entry dies with its parameter
+    _PACK_CACHE[key] = entry
 
 
 def _drop_pack(key, ref):
     e = _PACK_CACHE.get(key)
-    if e is not None and e[6] is ref:
+    if e is not None and e.ref is ref:
         del _PACK_CACHE[key]
 
 
-def _pack_dgrad(entry, wf, wm, cin, cout, k):
-    """Flipped / transposed fragments of the layer for its dgrad (direct and, for 3x3, Winograd) on the current stream."""
-    L = _lib.lib()
-    st = _lib.stream_ptr()
+# -----------------------------------------------------------------------------------------------------------------------
+# One job builder: a layer's packing jobs, for the step's one batch launch and for the per-layer launches alike
+# -----------------------------------------------------------------------------------------------------------------------
+_FRAGMENT_FLOATS = {(_lib.PACK_DIRECT, 0): "read_conv_packed_floats", (_lib.PACK_DIRECT, 1): "read_conv_dgrad_packed_floats",
+                    (_lib.PACK_WINO, 0): "read_conv_wino_floats", (_lib.PACK_WINO, 1): "read_conv_dgrad_wino_floats",
+                    (_lib.PACK_W4, 0): "read_conv_w4_floats", (_lib.PACK_W4, 1): "read_conv_dgrad_w4_floats"}
+
+
+def _fragment_floats(kind, mode, cin, cout, k):
+    size = getattr(_lib.lib(), _FRAGMENT_FLOATS[(kind, mode)])
+    return size(cin, cout, k) if kind == _lib.PACK_DIRECT else size(cin, cout)
+
+
+def _job(kind, mode, cin, cout, k, kc, out, wf=None, wm=None, par=None, eps=BN_EPS):
+    """One validated read_pack_job (include/read_hip.h) writing `out`; par = (bf, bm, gamma, beta, mean, var) of a params job."""
+    j = _lib.PackJob()
+    j.kind, j.mode, j.Cin, j.Cout, j.ksize, j.kc, j.eps = kind, mode, cin, cout, k, kc, eps
+    j.out = out.data_ptr()
+    if wf is not None:
+        j.wf, j.wm = wf.data_ptr(), wm.data_ptr()
+    if par is not None:
+        j.bf, j.bm, j.gamma, j.beta, j.mean, j.var = (_ptr(t) for t in par)
+    _lib.check(_lib.lib().read_conv_pack_job_prepare(C.byref(j)), "read_conv_pack_job_prepare")
+    return j
+
+
+def _layer_jobs(route, wf, wm, ts=None, identity_bn=False, fwd=True, dgrad=True):
+    """The packing jobs of one layer with the tensors they fill, in the order params, fwd, dgrad: {name: (PackJob, out)}.
+    wf, wm: the contiguous weights; ts: the layer's eight tensors for the parameter block (None: no params job).
+    identity_bn (batch-statistics mode): the params block carries the two biases and scale 1 / shift 0 — the launch then
+    stores g = act(f) * sigmoid(m) itself and read_bn_train_forward normalises it."""
     dev = wf.device
-    wf_c, wm_c = wf.detach().contiguous(), wm.detach().contiguous()
-    wdw = None
-    if k == 3 and USE_WINOGRAD:                                      # the virtual input has 2 * cp channels: always % 16
-        if _w4_fits(2 * ((cout + 7) // 8 * 8), cin // 2):            # the virtual layer: 2 * cp -> cin / 2 gated channels
-            wdw = torch.empty(L.read_conv_dgrad_w4_floats(cin, cout), dtype=torch.float32, device=dev)
-            _lib.check(L.read_conv_pack_dgrad_w4_device(cin, cout, wf_c.data_ptr(), wm_c.data_ptr(), wdw.data_ptr(), st))
-        else:
-            wdw = torch.empty(L.read_conv_dgrad_wino_floats(cin, cout), dtype=torch.float32, device=dev)
-            _lib.check(L.read_conv_pack_dgrad_wino_device(cin, cout, wf_c.data_ptr(), wm_c.data_ptr(), wdw.data_ptr(), st))
-        wd = wdw                                                     # the stride-1 dgrad of a 3x3 layer always runs on that kernel
-    else:
-        wd = torch.empty(L.read_conv_dgrad_packed_floats(cin, cout, k), dtype=torch.float32, device=dev)
-        _lib.check(L.read_conv_pack_dgrad_device(cin, cout, k, 16, wf_c.data_ptr(), wm_c.data_ptr(), wd.data_ptr(), st))
+    cin, cout, k = route.cin, route.cout, route.k
+    jobs = {}
+    if ts is not None:
+        _wf, bf, _wm, bm, gamma, beta, mean, var = ts
+        eps = BN_EPS
+        if identity_bn:
+            one, zero = _const_vec(cout, 1.0, dev), _const_vec(cout, 0.0, dev)
+            gamma, beta, mean, var, eps = one, zero, zero, one, 0.0       # scale = 1 / sqrt(1 + 0)
+        out = torch.empty(_lib.lib().read_conv_param_floats(cout), dtype=torch.float32, device=dev)
+        jobs['params'] = (_job(_lib.PACK_PARAMS, 0, cin, cout, k, 0, out, par=(bf, bm, gamma, beta, mean, var), eps=eps), out)
+    for name, want, kind, kc in (('fwd', fwd, route.fwd, route.fwd_kc), ('dgrad', dgrad, route.dgrad, route.dgrad_kc)):
+        if want and kind is not None:
+            mode = int(name == 'dgrad')
+            out = torch.empty(_fragment_floats(kind, mode, cin, cout, k), dtype=torch.float32, device=dev)
+            jobs[name] = (_job(kind, mode, cin, cout, k, kc, out, wf, wm), out)
+    return jobs
+
+
+def _launch_jobs(jobs):
+    """One launch per job on the current stream: the path of a captured step, of a standalone GatedConvFn and of weights the step's
+    plan does not take."""
+    L, st = _lib.lib(), _lib.stream_ptr()
+    for j in jobs:
+        _lib.check(L.read_conv_pack_job(C.byref(j), st), "read_conv_pack_job")
+
+
+def _packed_for(route, ts, identity_bn=False):
+    """The layer's entry with the parameter block and the forward fragments of its CURRENT tensors ts = (wf, bf, wm, bm, gamma, beta,
+    running mean, running var), from the cache or packed now."""
+    wf, wm = ts[0], ts[2]
+    ver = _pack_version(route, ts, identity_bn)
+    # While a HIP graph is being captured (GraphedTrainStep) every layer packs afresh: the packing launches must be PART of
+    # the graph — it is replayed after every optimizer step — and a cache hit would freeze the fragments of the capture step in.
+    capturing = torch.cuda.is_current_stream_capturing()
+    hit = None if capturing else _PACK_CACHE.get(id(wf))
+    if hit is not None and hit.ref() is not wf:             # the id was recycled by another tensor: not this layer's entry
+        hit = None
+    if hit is not None and hit.version == ver:
+        if hit.event is not None:                           # None: the step's pack plan filled it on this stream, into buffers it keeps
+            cur = torch.cuda.current_stream()
+            cur.wait_event(hit.event)                       # packed on another item's stream
+            hit.params.record_stream(cur)
+            hit.fwd.record_stream(cur)
+        return hit
+    jobs = _layer_jobs(route, wf.detach().contiguous(), wm.detach().contiguous(), ts, identity_bn, dgrad=False)
+    _launch_jobs(j for j, _out in jobs.values())
+    ev = None
+    if not capturing:             # an event recorded inside a capture must never be waited on from outside it (see backward)
+        ev = torch.cuda.Event()
+        ev.record()
+    entry = _PackEntry(ver, route, jobs['params'][1], jobs['fwd'][1], event=ev)
+    if not capturing:                                         # a captured entry lives in the graph's memory pool, not in the cache
+        _cache_put(wf, entry)
+    return entry
+
+
+def _pack_dgrad(entry, wf, wm):
+    """Flipped / transposed fragments of the layer for its dgrad (direct or, for 3x3, Winograd) on the current stream."""
+    jobs = _layer_jobs(entry.route, wf.detach().contiguous(), wm.detach().contiguous(), fwd=False)
+    _launch_jobs(j for j, _out in jobs.values())
     ev = None
     if not torch.cuda.is_current_stream_capturing():
         ev = torch.cuda.Event()
         ev.record()
-    entry[3] = (wd, ev, wdw)
+    entry.dgrad, entry.dgrad_event = jobs['dgrad'][1], ev
 
 
 # -----------------------------------------------------------------------------------------------------------------------
@@ -258,24 +351,32 @@ def _pack_dgrad(entry, wf, wm, cin, cout, k):
 # each axis.  Four launches of the F(4x4,3x3) kernel on a quarter of the pixels replace the generic vector kernel (690 us per
 # layer, three layers on the critical path of the backward pass).
 POLYPHASE_DGRAD = os.environ.get("READ_AMD_POLYPHASE", "1") != "0"
-_POLY = {}                   # id(conv_f weight) -> (versions, fragments [4][n], w4 flag)
+_POLY = {}                   # id(conv_f weight) -> _PolyEntry
 _POLY_SEL = {}               # device -> index tensors of the four parities
 
 
-def _poly_fragments(wf, wm, cin, cout, k=4):
-    """k = 3 (stride 2, pad 1) the same way: dx[2 u] = W1 dy[u], dx[2 u + 1] = W2 dy[u] + W0 dy[u + 1] — pseudo-weights
+class _PolyEntry(NamedTuple):
+    version: tuple
+    frags: torch.Tensor      # [4][n]: the fragments of the four pseudo-layers, parity 2 py + px
+    event: torch.cuda.Event
+    stream: int              # the stream they were packed on
+
+
+def _poly_fragments(wf, wm, route):
+    """-> fragments [4][n] in the order route.poly, one row per pixel parity.
+    k = 3 (stride 2, pad 1) the same way: dx[2 u] = W1 dy[u], dx[2 u + 1] = W2 dy[u] + W0 dy[u + 1] — pseudo-weights
     [0, W1, 0] / [W0, W2, 0]; instead of the stride-1 dgrad over a zero-dilated d[f|m] (4x the pixels, 3/4 of them zeros)."""
-    L = _lib.lib()
+    cin, cout, k = route.cin, route.cout, route.k
     key = id(wf)
-    ver = (wf._version, wm._version, wf.data_ptr(), wm.data_ptr())
+    ver = (wf._version, wm._version, wf.data_ptr(), wm.data_ptr(), route)
     capturing = torch.cuda.is_current_stream_capturing()
     hit = None if capturing else _POLY.get(key)
-    if hit is not None and hit[0] == ver:
+    if hit is not None and hit.version == ver:
         cur = torch.cuda.current_stream(wf.device)
-        if hit[3] is not None and hit[4] != cur.cuda_stream:      # packed on another stream (e.g. a graph capture's warm-up)
-            cur.wait_event(hit[3])
-            hit[1].record_stream(cur)
-        return hit[:3]
+        if hit.stream != cur.cuda_stream:                         # packed on another stream (e.g. a graph capture's warm-up)
+            cur.wait_event(hit.event)
+            hit.frags.record_stream(cur)
+        return hit.frags
     dev = wf.device
     sel = _POLY_SEL.get((dev, k))
     if sel is None:                                                            # parity -> source tap of the pseudo taps (k: the zero tap)
@@ -283,19 +384,16 @@ def _poly_fragments(wf, wm, cin, cout, k=4):
         sel = _POLY_SEL[(dev, k)] = (taps[[0, 0, 1, 1]][:, :, None], taps[[0, 1, 0, 1]][:, None, :])
     w5 = torch.nn.functional.pad(torch.stack((wf.detach(), wm.detach())), (0, 1, 0, 1))      # (2, cout, cin, k + 1, k + 1)
     wp = w5[:, :, :, sel[0], sel[1]].permute(3, 0, 1, 2, 4, 5).contiguous()                    # (parity 2 py + px, f|m, cout, cin, 3, 3)
-    w4 = _w4_fits(2 * ((cout + 7) // 8 * 8), cin // 2)
-    n = L.read_conv_dgrad_w4_floats(cin, cout) if w4 else L.read_conv_dgrad_wino_floats(cin, cout)
-    buf = torch.empty((4, n), dtype=torch.float32, device=dev)
-    pack = L.read_conv_pack_dgrad_w4_device if w4 else L.read_conv_pack_dgrad_wino_device
-    for par in range(4):
-        _lib.check(pack(cin, cout, wp[par, 0].data_ptr(), wp[par, 1].data_ptr(), buf[par].data_ptr(), _lib.stream_ptr()))
+    buf = torch.empty((4, _fragment_floats(route.poly, 1, cin, cout, 3)), dtype=torch.float32, device=dev)
+    # the dgrad jobs of four 3x3 pseudo-layers, one launch each
+    _launch_jobs(_job(route.poly, 1, cin, cout, 3, route.dgrad_kc, buf[par], wp[par, 0], wp[par, 1]) for par in range(4))
     if not capturing:
         ev = torch.cuda.Event()
         ev.record()
         if key not in _POLY:
             weakref.finalize(wf, _POLY.pop, key, None)
-        _POLY[key] = (ver, buf, w4, ev, torch.cuda.current_stream(dev).cuda_stream)
-    return (ver, buf, w4)
+        _POLY[key] = _PolyEntry(ver, buf, ev, torch.cuda.current_stream(dev).cuda_stream)
+    return buf
 
 
 # -----------------------------------------------------------------------------------------------------------------------
@@ -321,24 +419,10 @@ class _PackPlan:
 
     def __init__(self, net, identity_bn):
         from .unet import layer_table
-        L = _lib.lib()
         dev = next(net.parameters()).device
         self.identity_bn = bool(identity_bn)
-        self.layers = []            # (tensors of the layer, cache entry pieces)
-        jobs = []
-
-        def job(kind, mode, cin, cout, k, kc, out, wf=None, wm=None, par=None):
-            j = _lib.PackJob()
-            j.kind, j.mode, j.Cin, j.Cout, j.ksize, j.kc, j.eps = kind, mode, cin, cout, k, kc, BN_EPS
-            j.out = out.data_ptr()
-            if wf is not None:
-                j.wf, j.wm = wf.data_ptr(), wm.data_ptr()
-            if par is not None:
-                j.bf, j.bm, j.gamma, j.beta, j.mean, j.var = (t.data_ptr() if t is not None else None for t in par)
-            _lib.check(L.read_conv_pack_job_prepare(C.byref(j)), "read_conv_pack_job_prepare")
-            jobs.append(j)
-
-        f32 = dict(dtype=torch.float32, device=dev)
+        self.layers = []            # (tensors of the layer, its _PackEntry: the buffers the jobs fill)
+        self.jobs = []              # (layer path, PackJob) in table order
         for (path, cin, cout, k, stride, _elu) in layer_table():
             if path.startswith("ConvsOut."):                 # in the state dict, never executed (unet.py:181-186)
                 continue
@@ -347,63 +431,28 @@ class _PackPlan:
                 node = node._modules[p_]
             b = node.block
             n = b['norm']
-            wf, bf, wm, bm = b['conv_f'].weight, b['conv_f'].bias, b['conv_m'].weight, b['conv_m'].bias
-            if not (wf.is_contiguous() and wm.is_contiguous()):
+            ts = (b['conv_f'].weight, b['conv_f'].bias, b['conv_m'].weight, b['conv_m'].bias, n.weight, n.bias, n.running_mean,
+                  n.running_var)
+            if not (ts[0].is_contiguous() and ts[2].is_contiguous()):
                 raise _NotBatchPackable("non-contiguous weights")
-            # parameter block
-            params = torch.empty(L.read_conv_param_floats(cout), **f32)
-            if self.identity_bn:
-                one, zero = _const_vec(cout, 1.0, dev), _const_vec(cout, 0.0, dev)
-                par = (bf, bm, one, zero, zero, one)
-            else:
-                par = (bf, bm, n.weight, n.bias, n.running_mean, n.running_var)
-            job(_lib.PACK_PARAMS, 0, cin, cout, k, 0, params, par=par)
-            if self.identity_bn:
-                jobs[-1].eps = 0.0                           # scale = 1 / sqrt(1 + 0)
-            # forward fragments: ONE order per layer, the one the launch takes (as _packed_for)
-            wino = None
-            if k == 3 and stride == 1 and cin % 16 == 0 and USE_WINOGRAD:
-                if _w4_fits(cin, cout):
-                    wino = torch.empty(L.read_conv_w4_floats(cin, cout), **f32)
-                    job(_lib.PACK_W4, 0, cin, cout, 3, 16, wino, wf, wm)
-                else:
-                    wino = torch.empty(L.read_conv_wino_floats(cin, cout), **f32)
-                    job(_lib.PACK_WINO, 0, cin, cout, 3, 16, wino, wf, wm)
-                wp = wino
-            else:
-                wp = torch.empty(L.read_conv_packed_floats(cin, cout, k), **f32)
-                job(_lib.PACK_DIRECT, 0, cin, cout, k, _kc_for(cin), wp, wf, wm)
-            # dgrad fragments (as _pack_dgrad) for the layers whose dgrad is a convolution launch
-            dg = None
-            if stride == 1 or (stride == 2 and k == 3):
-                cp = (cout + 7) // 8 * 8
-                if k == 3 and USE_WINOGRAD:
-                    if _w4_fits(2 * cp, cin // 2):
-                        wdw = torch.empty(L.read_conv_dgrad_w4_floats(cin, cout), **f32)
-                        job(_lib.PACK_W4, 1, cin, cout, 3, 16, wdw, wf, wm)
-                    else:
-                        wdw = torch.empty(L.read_conv_dgrad_wino_floats(cin, cout), **f32)
-                        job(_lib.PACK_WINO, 1, cin, cout, 3, 16, wdw, wf, wm)
-                    dg = (wdw, None, wdw)
-                else:
-                    wd = torch.empty(L.read_conv_dgrad_packed_floats(cin, cout, k), **f32)
-                    job(_lib.PACK_DIRECT, 1, cin, cout, k, 16, wd, wf, wm)
-                    dg = (wd, None, None)
-            self.layers.append(((wf, bf, wm, bm, n.weight, n.bias, n.running_mean, n.running_var), params, wp, dg, wino,
-                                (cin, cout, k, stride)))
+            route = layer_route(cin, cout, k, stride)
+            jobs = _layer_jobs(route, ts[0], ts[2], ts, self.identity_bn)
+            out = {name: o for name, (_j, o) in jobs.items()}
+            self.layers.append((ts, _PackEntry(None, route, out['params'], out['fwd'], out.get('dgrad'))))
+            self.jobs += [(path, j) for j, _o in jobs.values()]
         first = 0
-        for j in jobs:
+        for _path, j in self.jobs:
             j.first_block = first
             first += j.nblocks
-        self.total_blocks, self.njobs = first, len(jobs)
-        table = (_lib.PackJob * len(jobs))(*jobs)
+        self.total_blocks, self.njobs = first, len(self.jobs)
+        table = (_lib.PackJob * self.njobs)(*(j for _path, j in self.jobs))
         self.table = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
         self.signature = None
         self.stream = self.event = None
 
     def refresh(self):
         """Pack every layer with its current weights — one launch — unless nothing changed since the last one."""
-        sig = tuple(t._version for ts in self.layers for t in ts[0])
+        sig = tuple(t._version for ts, _entry in self.layers for t in ts)
         cur = torch.cuda.current_stream()
         if sig == self.signature:
             if self.event is not None and cur != self.stream and not torch.cuda.is_current_stream_capturing():
@@ -416,24 +465,22 @@ class _PackPlan:
         if not torch.cuda.is_current_stream_capturing():
             self.event = torch.cuda.Event()
             self.event.record(cur)
-        for (ts, params, wp, dg, wino, _shape) in self.layers:
-            wf = ts[0]
-            key = id(wf)
-            old = _PACK_CACHE.get(key)
-            if old is not None and old[6]() is wf:
-                ref = old[6]
-            else:
-                ref = weakref.ref(wf)
-                weakref.finalize(wf, _drop_pack, key, ref)
-            _PACK_CACHE[key] = [_pack_version(*ts, self.identity_bn), params, wp, dg, None, wino, ref]
+        for ts, entry in self.layers:                     # the per-layer cache then hits for every layer (entry.event stays None)
+            entry.version = _pack_version(entry.route, ts, self.identity_bn)
+            _cache_put(ts[0], entry)
+
+
+def _net_tensors(net):
+    """The net's parameters and buffers, listed once: their addresses key what is built per net (pack plans, captured steps)."""
+    ts = net.__dict__.get('_flat_tensors')
+    if ts is None:
+        ts = net.__dict__['_flat_tensors'] = list(net.parameters()) + list(net.buffers())
+    return ts
 
 
 def _pack_plan(net, identity_bn):
     """The net's plan for this BatchNorm mode; rebuilt when a tensor has moved (.cuda() / .to() / a new parameter object)."""
-    ts = net.__dict__.get('_flat_tensors')
-    if ts is None:
-        ts = net.__dict__['_flat_tensors'] = list(net.parameters()) + list(net.buffers())
-    key = (bool(identity_bn), hash(tuple(t.data_ptr() for t in ts)), USE_W4, USE_WINOGRAD)
+    key = (bool(identity_bn), hash(tuple(t.data_ptr() for t in _net_tensors(net))), USE_W4, USE_WINOGRAD)
     plans = net.__dict__.setdefault('_pack_plans', {})
     if key in plans:
         return plans[key]
@@ -468,6 +515,55 @@ class _GradArena:
         return self.buf[off:off + n]
 
 
+def _dgrad(method, route, dfm, H, W, wf, wm, entry=None, live=None, out=None):
+    """d[f|m] (Ho, Wo, 2 * pad8(cout)) -> dx (H, W, cin) by `method` (dgrad_method): the input gradient of GatedConvFn.backward, and
+    what tests/test_gpu_train_accuracy.py drives method by method.  wf, wm: the contiguous weights; entry: the layer's _PackEntry —
+    its dgrad fragments are packed here when nobody has yet; live: the parameter objects the polyphase fragments are cached under
+    (wf, wm themselves when not given); out: write dx here."""
+    L = _lib.lib()
+    dev = dfm.device
+    cin, cout, k = route.cin, route.cout, route.k
+    Ho, Wo = int(dfm.shape[0]), int(dfm.shape[1])
+    cp = (cout + 7) // 8 * 8
+    dx = out if out is not None else torch.empty((H, W, cin), dtype=torch.float32, device=dev)
+    if method == 'poly':
+        # four 3x3 / stride-1 dgrads over the half-resolution d[f|m], one per pixel parity of dx (_poly_fragments)
+        frags = _poly_fragments(*(live or (wf, wm)), route)            # of the CURRENT weights (cache: packed in forward)
+        zero = _zero_params(L.read_conv_param_floats(cin // 2), dev)
+        for par in range(4):
+            dxp = torch.empty((Ho, Wo, cin), dtype=torch.float32, device=dev)
+            _linear_conv(dfm, 2 * cp, frags[par], zero, cin // 2, 3, 1, dxp, wino=frags[par], w4=route.poly == _lib.PACK_W4)
+            dx[par >> 1::2, par & 1::2] = dxp
+    elif method in ('conv', 'dilated'):
+        # dgrad = the same MFMA convolution over d[f|m] with flipped, transposed weights; the two "gate halves" of
+        # the kernel's output tile are simply the two halves of the input channels.  A 3x3 / stride-2 layer is the
+        # stride-1 layer sampled at the even positions, so its dgrad is the stride-1 dgrad of d[f|m] spread onto the
+        # even positions of a zero image — 4x the necessary MFMAs, still 7x faster than the generic VALU kernel
+        # (1.34 ms per layer) because it runs on the Winograd kernel.
+        d_in = dfm
+        if method == 'dilated':
+            d_in = torch.zeros((H, W, 2 * cp), dtype=torch.float32, device=dev)
+            d_in[::2, ::2] = dfm
+        if entry is None:
+            entry = _PackEntry(route=route)
+        if entry.dgrad is None:
+            _pack_dgrad(entry, wf, wm)
+        wd, ev = entry.dgrad, entry.dgrad_event
+        wdw = wd if route.dgrad != _lib.PACK_DIRECT else None
+        if ev is not None:                   # None: packed by the step's forward HIP graph, ordered by the replay itself
+            torch.cuda.current_stream().wait_event(ev)
+            wd.record_stream(torch.cuda.current_stream())
+        zero = _zero_params(L.read_conv_param_floats(cin // 2), dev)
+        _linear_conv(d_in, 2 * cp, wd, zero, cin // 2, k, 1, dx, wino=wdw, w4=route.dgrad == _lib.PACK_W4)
+    else:
+        if FLOP_LOG is not None:
+            FLOP_LOG.append(("dgrad_valu", 2.0 * Ho * Wo * cin * 2 * cout * k * k, 0))
+        ws = torch.empty(L.read_conv_dgrad_generic_floats(cin, cout, k), dtype=torch.float32, device=dev)
+        _lib.check(L.read_conv_dgrad_generic(dfm.data_ptr(), Ho, Wo, cin, cout, k, route.stride, wf.data_ptr(), wm.data_ptr(),
+                                             ws.data_ptr(), H, W, dx.data_ptr(), _lib.stream_ptr()))
+    return dx
+
+
 class GatedConvFn(torch.autograd.Function):
     """y = BN_eval(act(conv_f(x) + b_f) * sigmoid(conv_m(x) + b_m)) for ONE image, x (H,W,Cin) NHWC -> (Ho,Wo,Cout)."""
 
@@ -482,23 +578,24 @@ class GatedConvFn(torch.autograd.Function):
         Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
         dev = x.device
         wf_c, wm_c = wf.detach().contiguous(), wm.detach().contiguous()
-        entry = _packed_for(wf, bf, wm, bm, gamma, beta, mean, var, cin, cout, k, identity_bn=bn_train, stride=stride)
-        params, wp = entry[1], entry[2]
-        ctx.pack = entry
-        # the dgrad's fragments too, now: in the backward pass the wgrad kernels of the layers above fill the chip from their side
-        # stream and a small packing launch between two dgrads waits 200 us for its turn (10 us here)
+        route = layer_route(cin, cout, k, stride)
+        entry = _packed_for(route, (wf, bf, wm, bm, gamma, beta, mean, var), identity_bn=bn_train)
+        params, wp = entry.params, entry.fwd
+        ctx.pack, ctx.route = entry, route
+        capturing = torch.cuda.is_current_stream_capturing()
         # stride-2 layers: dgrad as four stride-1 dgrads, one per pixel parity (_poly_fragments) — not inside a captured step, whose
         # retained backward graph is walked again after the weights have changed (the dilated / generic paths stay there)
-        poly = (POLYPHASE_DGRAD and USE_WINOGRAD and stride == 2 and k in (3, 4) and H % 2 == 0 and W % 2 == 0 and cin % 16 == 0
-                and not torch.cuda.is_current_stream_capturing())
-        ctx.poly = poly
+        ctx.method = method = dgrad_method(route, H, W, capturing)
         # a captured step's backward (walked eagerly over the retained graph, on the capture's stream) keeps its weight gradients on
         # that one stream: the side-stream hand-over is only exercised, and only verified, in the per-layer path
-        ctx.side = WGRAD_SIDE_STREAM and not torch.cuda.is_current_stream_capturing()
-        if entry[3] is None and x.requires_grad and (stride == 1 or (stride == 2 and k == 3 and H % 2 == 0 and W % 2 == 0 and not poly)):
-            _pack_dgrad(entry, wf, wm, cin, cout, k)
-        if poly and x.requires_grad:
-            _poly_fragments(wf, wm, cin, cout, k)            # now, for the same reason
+        ctx.side = WGRAD_SIDE_STREAM and not capturing
+        # the dgrad's fragments too, now: in the backward pass the wgrad kernels of the layers above fill the chip from their side
+        # stream and a small packing launch between two dgrads waits 200 us for its turn (10 us here)
+        if x.requires_grad:
+            if method in ('conv', 'dilated') and entry.dgrad is None:
+                _pack_dgrad(entry, wf, wm)
+            elif method == 'poly':
+                _poly_fragments(wf, wm, route)
         side = _SIDE.get(dev)
         if side is not None:
             side[1] = False          # a backward pass that died before its join callback ran must not mute the next one's
@@ -507,9 +604,9 @@ class GatedConvFn(torch.autograd.Function):
         # a batch is one tall image of nb stacked items; separator rows (block geometry at THIS layer's output scale) stay zero
         bh = Ho // nb if nb > 1 else 0
         vh = bh * v_num // v_den
-        wino = entry[5]
+        wino = entry.wino
         # the Winograd kernel writes the gated output next to the pre-activations; the other kernels leave it to the gate pass
-        _linear_conv(x, cin, wp, params, cout, k, stride, fm, wino=wino, gated=(y, elu, bh, vh), w4=_w4_fits(cin, cout))
+        _linear_conv(x, cin, wp, params, cout, k, stride, fm, wino=wino, gated=(y, elu, bh, vh), w4=route.fwd == _lib.PACK_W4)
         if wino is None:
             _lib.check(L.read_gate_forward(fm.data_ptr(), Ho * Wo, cout, params.data_ptr(), int(elu), None, y.data_ptr(), Wo, bh, vh, st))
         stat, groups = None, 1
@@ -596,43 +693,10 @@ class GatedConvFn(torch.autograd.Function):
                                              dbm.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), st))
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty((H, W, cin), dtype=torch.float32, device=dev)
-            poly = ctx.poly and ctx.wrefs[0]() is not None and ctx.wrefs[1]() is not None
-            dilated = not poly and stride == 2 and k == 3 and H % 2 == 0 and W % 2 == 0
-            if poly:
-                # four 3x3 / stride-1 dgrads over the half-resolution d[f|m], one per pixel parity of dx (_poly_fragments)
-                _, frags, w4 = _poly_fragments(ctx.wrefs[0](), ctx.wrefs[1](), cin, cout, k)  # of the CURRENT weights (cache: packed in forward)
-                zero = _zero_params(L.read_conv_param_floats(cin // 2), dev)
-                for par in range(4):
-                    dxp = torch.empty((Ho, Wo, cin), dtype=torch.float32, device=dev)
-                    _linear_conv(dfm, 2 * cp, frags[par], zero, cin // 2, 3, 1, dxp, wino=frags[par], w4=w4)
-                    dx[par >> 1::2, par & 1::2] = dxp
-            elif stride == 1 or dilated:
-                # dgrad = the same MFMA convolution over d[f|m] with flipped, transposed weights; the two "gate halves" of
-                # the kernel's output tile are simply the two halves of the input channels.  A 3x3 / stride-2 layer is the
-                # stride-1 layer sampled at the even positions, so its dgrad is the stride-1 dgrad of d[f|m] spread onto the
-                # even positions of a zero image — 4x the necessary MFMAs, still 7x faster than the generic VALU kernel
-                # (1.34 ms per layer) because it runs on the Winograd kernel.
-                d_in = dfm
-                if dilated:
-                    d_in = torch.zeros((H, W, 2 * cp), dtype=torch.float32, device=dev)
-                    d_in[::2, ::2] = dfm
-                if ctx.pack[3] is None:
-                    _pack_dgrad(ctx.pack, wf, wm, cin, cout, k)
-                wd, ev, wdw = ctx.pack[3]
-                if ev is not None:                   # None: packed by the step's forward HIP graph, ordered by the replay itself
-                    torch.cuda.current_stream().wait_event(ev)
-                    wd.record_stream(torch.cuda.current_stream())
-                    if wdw is not None:
-                        wdw.record_stream(torch.cuda.current_stream())
-                zero = _zero_params(L.read_conv_param_floats(cin // 2), dev)
-                _linear_conv(d_in, 2 * cp, wd, zero, cin // 2, k, 1, dx, wino=wdw, w4=_w4_fits(2 * cp, cin // 2))
-            else:
-                if FLOP_LOG is not None:
-                    FLOP_LOG.append(("dgrad_valu", 2.0 * Ho * Wo * cin * 2 * cout * k * k, 0))
-                ws = torch.empty(L.read_conv_dgrad_generic_floats(cin, cout, k), dtype=torch.float32, device=dev)
-                _lib.check(L.read_conv_dgrad_generic(dfm.data_ptr(), Ho, Wo, cin, cout, k, stride, wf.data_ptr(), wm.data_ptr(),
-                                                     ws.data_ptr(), H, W, dx.data_ptr(), st))
+            method, live = ctx.method, (ctx.wrefs[0](), ctx.wrefs[1]())
+            if method == 'poly' and (live[0] is None or live[1] is None):      # the parameters are gone: from the weights the context holds
+                method = dgrad_method(ctx.route, H, W, polyphase=False)
+            dx = _dgrad(method, ctx.route, dfm, H, W, wf, wm, ctx.pack, live)
         if not want_w:                                                      # frozen net: nobody asked for weight gradients
             return dx, None, dbf, None, dbm, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None
         if FLOP_LOG is not None:
@@ -902,9 +966,7 @@ class _GraphedStep:
 
 
 def _graph_key(net, xs, per_item):
-    ts = net.__dict__.get('_flat_tensors')
-    if ts is None:
-        ts = net.__dict__['_flat_tensors'] = list(net.parameters()) + list(net.buffers())
+    ts = _net_tensors(net)
     return (tuple(tuple(x.shape) for x in xs), tuple(bool(x.requires_grad) for x in xs), bool(net.training), bool(per_item),
             hash(tuple(t.data_ptr() for t in ts)), hash(tuple(bool(t.requires_grad) for t in ts)))
 

@@ -702,22 +702,25 @@ def test_pack_plan_equals_the_per_layer_packers_and_follows_the_optimizer(hip):
         plan = T._PackPlan(net, identity)
         plan.refresh()
         torch.cuda.synchronize()
-        assert len(plan.layers) == 99 and plan.njobs == 99 * 2 + sum(1 for l in plan.layers if l[3] is not None)
-        for (ts, params, wp, dg, wino, (cin, cout, k, stride)) in plan.layers:
-            wf, bf, wm, bm, gamma, beta, mean, var = ts
+        assert len(plan.layers) == 99 and plan.njobs == 99 * 2 + sum(1 for _ts, e in plan.layers if e.dgrad is not None)
+        for ts, planned in plan.layers:
+            wf, wm, route = ts[0], ts[2], planned.route
             T._PACK_CACHE.pop(id(wf), None)                                   # force the per-layer path
-            ref = T._packed_for(wf, bf, wm, bm, gamma, beta, mean, var, cin, cout, k, identity_bn=identity, stride=stride)
-            assert torch.equal(ref[1], params), ("parameter block", cin, cout, k, stride)
-            assert (ref[5] is None) == (wino is None) and torch.equal(ref[2], wp), ("forward fragments", cin, cout, k, stride)
-            if dg is not None:
-                T._pack_dgrad(ref, wf, wm, cin, cout, k)
-                assert torch.equal(ref[3][0], dg[0]), ("dgrad fragments", cin, cout, k, stride)
+            ref = T._packed_for(route, ts, identity_bn=identity)
+            assert ref is not planned and ref.route == route
+            assert torch.equal(ref.params, planned.params), ("parameter block", route)
+            assert (ref.wino is None) == (planned.wino is None) and torch.equal(ref.fwd, planned.fwd), ("forward fragments", route)
+            assert (planned.dgrad is None) == (route.dgrad is None)
+            if planned.dgrad is not None:
+                T._pack_dgrad(ref, wf, wm)
+                assert torch.equal(ref.dgrad, planned.dgrad), ("dgrad fragments", route)
             T._PACK_CACHE.pop(id(wf), None)
     # a fused Adam step: versions bumped by _DeviceAdam, so the plan's signature changes and the refresh repacks
     net.eval()
     plan = T._pack_plan(net, False)
     plan.refresh()
-    before = plan.layers[0][2].clone()
+    _ts, first = plan.layers[0]
+    before = first.fwd.clone()
     opt = _DeviceAdam(net.parameters(), lr=1e-2)
     xs = [torch.rand(1, 8, 32 >> l, 48 >> l, device="cuda") for l in range(4)]
     net(*xs).sum().backward()
@@ -725,7 +728,7 @@ def test_pack_plan_equals_the_per_layer_packers_and_follows_the_optimizer(hip):
     opt.step()
     assert opt.param_groups[0]['fused'] is True and opt._step_supports_amp_scaling
     plan.refresh()
-    assert plan.signature != sig and not torch.equal(plan.layers[0][2], before)
+    assert plan.signature != sig and not torch.equal(first.fwd, before)
 
 
 def test_model_and_loss_under_dataparallel_on_one_gpu(hip):

@@ -500,46 +500,33 @@ def test_generic_input_gradient(hip):
 
 
 # ------------------------------------------------------------------------------------------ input gradient through the convolution kernels
-def _conv_dgrad(dfm_h, wf_h, wm_h, cin, cout, k, stride, H, W, branch):
-    """The three non-generic branches of read_amd.train.GatedConvFn.backward, driven with a chosen d[f|m] through the same private
-    helpers: "s1" stride 1, "dilated" 3x3 / stride 2 as the stride-1 dgrad of the zero-dilated d[f|m], "poly" one 3x3 / stride-1 dgrad
-    per pixel parity.  -> dx (H, W, cin) on the host."""
+_METHOD = {"s1": "conv", "dilated": "dilated", "poly": "poly"}
+
+
+def _conv_dgrad(dfm_h, wf_h, wm_h, route, H, W, branch):
+    """The three non-generic methods of read_amd.train.GatedConvFn.backward, driven with a chosen d[f|m] through the helper the backward
+    pass itself calls (train._dgrad): "s1" stride 1, "dilated" 3x3 / stride 2 as the stride-1 dgrad of the zero-dilated d[f|m], "poly" one
+    3x3 / stride-1 dgrad per pixel parity.  The case names the method; the route function must offer it for this layer (under graph
+    capture for "dilated", which the polyphase method otherwise precedes).  -> dx (H, W, cin) on the host."""
     from read_amd import train
-    L = _lib.lib()
-    cp = T.pad8(cout)
+    assert train.dgrad_method(route, H, W, capturing=branch == "dilated", polyphase=True) == _METHOD[branch], (branch, route)
     dfm, wf, wm = _dev(dfm_h), _dev(wf_h), _dev(wm_h)
-    dx = torch.full((H, W, cin), 7.0, device="cuda")
-    zero = train._zero_params(L.read_conv_param_floats(cin // 2), dfm.device)
-    if branch == "poly":
-        _, frags, w4 = train._poly_fragments(wf, wm, cin, cout, k)
-        Ho, Wo = dfm.shape[:2]
-        for par in range(4):
-            dxp = torch.empty((Ho, Wo, cin), dtype=torch.float32, device="cuda")
-            train._linear_conv(dfm, 2 * cp, frags[par], zero, cin // 2, 3, 1, dxp, wino=frags[par], w4=w4)
-            dx[par >> 1::2, par & 1::2] = dxp
-    else:
-        d_in = dfm
-        if branch == "dilated":
-            d_in = torch.zeros((H, W, 2 * cp), dtype=torch.float32, device="cuda")
-            d_in[::2, ::2] = dfm
-        entry = [None] * 7
-        train._pack_dgrad(entry, wf, wm, cin, cout, k)
-        wd, _ev, wdw = entry[3]
-        train._linear_conv(d_in, 2 * cp, wd, zero, cin // 2, k, 1, dx, wino=wdw, w4=train._w4_fits(2 * cp, cin // 2))
+    dx = torch.full((H, W, route.cin), 7.0, device="cuda")
+    assert train._dgrad(_METHOD[branch], route, dfm, H, W, wf, wm, out=dx) is dx
     return _host(dx)
 
 
-def _conv_family(k, cout, cin):
-    from read_amd import train
-    if k != 3 or not train.USE_WINOGRAD:
-        return "direct"
-    return "w4" if train._w4_fits(2 * T.pad8(cout), cin // 2) else "w2"
+def _conv_family(route, branch):
+    """The kernel family of the fragments the method reads, as the route function decides it."""
+    kind = route.poly if branch == "poly" else route.dgrad
+    return {_lib.PACK_DIRECT: "direct", _lib.PACK_WINO: "w2", _lib.PACK_W4: "w4"}[kind]
 
 
 def test_input_gradient_through_the_convolution_kernels(hip):
     """Stride 1 (k1, k3; 2 pad8(Cout) = 16, 48, 80, 112, 128 virtual input channels), dilated 3x3 / stride 2, polyphase k3 / k4: the fp32
     convolution kernels in linear mode over d[f|m] with flipped, transposed weights.  cond = sum |d| |w|; the Winograd launches are held
     to the transformed-domain term A_w (asserted), E against cond is printed as E(A)."""
+    from read_amd import train
     rng = np.random.default_rng(37)
     cin = 32
     cases = [("s1", k, 1, cout, hw) for k in (1, 3) for cout in (3, 20, 40, 56, 64) for hw in ((9, 21), (12, 20))]
@@ -552,9 +539,10 @@ def test_input_gradient_through_the_convolution_kernels(hip):
             w = [(rng.standard_normal((cout, cin, k, k)) * sw[None, :, None, None] / np.sqrt(cin * k * k)).astype(f32) for _ in range(2)]
             d = (rng.standard_normal((oh, ow, 2 * cout)) * sd).astype(f32)
             dfm = _dfm(d[:, :, :cout], d[:, :, cout:], cout)
-            got = _conv_dgrad(dfm, w[0], w[1], cin, cout, k, stride, H, W, branch)
+            route = train.layer_route(cin, cout, k, stride)
+            got = _conv_dgrad(dfm, w[0], w[1], route, H, W, branch)
             ref, cond = T.dgrad_ref(dfm, cout, w[0], w[1], k, stride, H, W)
-            fam = _conv_family(3 if branch != "s1" else k, cout, cin)
+            fam = _conv_family(route, branch)
             name = f"{branch} {cin}->{cout} k{k} s{stride} {H}x{W} [{fam}]"
             yard = {"torch": T.dgrad_torch32(dfm, cout, w[0], w[1], k, stride, H, W), "seq": T.dgrad_seq32(dfm, cout, w[0], w[1], k, stride, H, W)}
             if fam == "direct":
