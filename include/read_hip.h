@@ -312,6 +312,64 @@ int read_select_vote(const float *xyz, int64_t n, const float *M_host, int W, in
 int read_select_finish(const uint32_t *state, int64_t n, int min_hits, int num, int den, const int32_t *labels_in,
                        int32_t *labels_out, void *stream);
 
+/* ---------------------------------------------------------------- frame annotations (extension) */
+
+/* What drew each pixel of an edited frame, and per-instance 2-D boxes: the back end of scene editing (csrc/annotate.hip).  The
+ * contract is tests/annotate_model.py, held bit for bit.  The frame is a LEVEL-0 pinhole frame of read_splat_forward_instances
+ * (idx0, depth0), the tables describe the instance list it was drawn with — same pool, same matrices M_i, bit for bit.
+ *
+ * Per pixel p: empty (idx0 = 0 and the bits of depth0 = 0) -> obj = inst = -1.  Otherwise id = idx0[p]: for 0 <= id < n the object is
+ * k = labels[id] (labels NULL: 0) and the point xyz[id]; for id in foreign range f, [id_base_f, id_base_f + n_f), the object is
+ * k = K_own + 1 + f and the point pool_xyz[pool_first_f + id - id_base_f].  k = 0: obj = 0, inst = -1.  k >= 1: obj = k and inst =
+ * value[i] of the FIRST instance i in list order that is visible, draws object k and under whose M_i the point projects
+ * (read_splat_project_points' device function) to pixel p with depth bits equal to depth0[p]'s; none: inst = -1 and *unmatched += 1.
+ * An id no range holds, or a label outside [0, K_own]: obj = inst = -1 and *unmatched += 1.  On a frame and list that belong together
+ * *unmatched is 0.
+ *
+ * stats[i][0..11] (int32) of instance i, by list position: vis_px = pixels instance i won; vx0, vy0, vx1, vy1 = their inclusive box;
+ * in_pts = how many of its points project inside the image; ax0, ay0, ax1, ay1 = the inclusive box of those points' pixels (the
+ * amodal box, clipped to the image); near_bits = the smallest depth bit pattern among them; n_pts = npts[i].  An empty minimum is
+ * INT32_MAX, an empty maximum -1; a hidden instance keeps n_pts and is otherwise empty.  Integer min / max / add: order-free.
+ *
+ * The instance table is passed twice: on the HOST for the checks and the extents walk (32 ranges per launch, matrices in kernel
+ * arguments, hidden and empty instances not launched), and on the DEVICE for the pixel pass, where a pixel walks only the instances of
+ * its own object: d_obj_begin[k - 1] .. d_obj_begin[k] index d_obj_list, the list positions of object k's instances, ascending
+ * (K = K_own + n_foreign objects, d_obj_begin has K + 1 entries, d_obj_list has `count`).  The caller keeps the two in step. */
+#define READ_ANNOTATE_STATS 12
+typedef struct read_annotate_foreign {
+    int64_t id_base, n, pool_first;        /* ids [id_base, id_base + n) are pool points [pool_first, pool_first + n) */
+} read_annotate_foreign;
+typedef struct read_annotate_args {
+    const float *xyz; int64_t n;           /* device: the scene cloud, n x 3 */
+    const int32_t *labels;                 /* device, n, or NULL = every point static */
+    int K_own;                             /* own objects: labels lie in [0, K_own] */
+    int n_foreign;                         /* 0 .. READ_GATHER_MAX_TABLES - 1 */
+    const read_annotate_foreign *foreign;  /* host, n_foreign: id bases ascend from n without overlap */
+    const float *pool_xyz; int64_t pool_n; /* device: the point pool of read_splat_instances */
+    int count;                             /* instances I */
+    const int64_t *first; const int64_t *npts;   /* host, count each */
+    const int32_t *obj;                    /* host, count: the object (1..K) instance i draws */
+    const float *M;                        /* host, count x 16: M_i */
+    const unsigned char *visible;          /* host, count, or NULL = all visible */
+    const float *d_M;                      /* device, count x 16: the same matrices */
+    const int32_t *d_visible;              /* device, count: 0 = hidden */
+    const int32_t *d_value;                /* device, count: what inst[p] shows for instance i (the caller's handle) */
+    const int32_t *d_npts;                 /* device, count: npts as int32 */
+    const int32_t *d_obj_begin;            /* device, K + 1 */
+    const int32_t *d_obj_list;             /* device, count */
+    const int32_t *idx0; const float *depth0; int W, H;      /* device: the level-0 frame */
+    int32_t *out_obj, *out_inst;           /* device, W * H each */
+    int32_t *stats;                        /* device, count x READ_ANNOTATE_STATS */
+    int32_t *unmatched;                    /* device, 1 */
+} read_annotate_args;
+/* Stream-ordered, allocates nothing, no synchronisation: one init launch (the statistics rows and *unmatched), the pixel pass (16 B
+ * per pixel), ceil(drawn / 32) extents launches (12 B per drawn point).  count = 0: obj from the labels and inst = -1, no instance
+ * walk, no table read.  READ_EINVAL with a message, before any device work, for: null pointers with work to do, W or H < 1 or
+ * W * H >= 2^31, n, K_own, count or pool_n below 0 (pool_n above INT32_MAX), n_foreign outside 0 .. READ_GATHER_MAX_TABLES - 1, an
+ * object number outside [1, K], foreign bases that do not ascend from n (or overlap, or pass INT32_MAX, or leave the pool), a
+ * negative first or npts, first + npts past the pool. */
+int read_annotate_frame(const read_annotate_args *args, void *stream);
+
 /* ---------------------------------------------------------------- descriptor gather / scatter */
 
 /* (C, N) channel-major texture  ->  N x C row-major rows (and back, for gradients). */

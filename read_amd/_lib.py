@@ -79,6 +79,25 @@ class GatherTable(C.Structure):
     _fields_ = [("rows_nc", C.c_void_p), ("n", C.c_int64), ("id_base", C.c_int64), ("activation", C.c_int)]
 
 
+READ_ANNOTATE_STATS = 12
+
+
+class AnnotateForeign(C.Structure):
+    """read_annotate_foreign (include/read_hip.h): ids [id_base, id_base + n) are pool points [pool_first, pool_first + n)."""
+    _fields_ = [("id_base", C.c_int64), ("n", C.c_int64), ("pool_first", C.c_int64)]
+
+
+class AnnotateArgs(C.Structure):
+    """read_annotate_args (include/read_hip.h): one read_annotate_frame call."""
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_int64), ("labels", C.c_void_p), ("K_own", C.c_int), ("n_foreign", C.c_int),
+                ("foreign", C.POINTER(AnnotateForeign)), ("pool_xyz", C.c_void_p), ("pool_n", C.c_int64), ("count", C.c_int),
+                ("first", C.c_void_p), ("npts", C.c_void_p), ("obj", C.c_void_p), ("M", C.c_void_p), ("visible", C.c_void_p),
+                ("d_M", C.c_void_p), ("d_visible", C.c_void_p), ("d_value", C.c_void_p), ("d_npts", C.c_void_p),
+                ("d_obj_begin", C.c_void_p), ("d_obj_list", C.c_void_p),
+                ("idx0", C.c_void_p), ("depth0", C.c_void_p), ("W", C.c_int), ("H", C.c_int),
+                ("out_obj", C.c_void_p), ("out_inst", C.c_void_p), ("stats", C.c_void_p), ("unmatched", C.c_void_p)]
+
+
 READ_STITCH_MAX_PARTS = 8
 
 
@@ -134,6 +153,7 @@ SIGNATURES = {
     "read_select_near": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp, _vp]),
     "read_select_vote": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _f, _f, _vp, _vp]),
     "read_select_finish": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    "read_annotate_frame": (_i, [C.POINTER(AnnotateArgs), _vp]),
     "read_texture_to_rows": (_i, [_vp, _i64, _i, _vp, _vp]),
     "read_rows_to_texture": (_i, [_vp, _i64, _i, _vp, _vp]),
     "read_gather_forward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _i, _vp]),

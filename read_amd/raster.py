@@ -218,6 +218,27 @@ class PointCloudRasterizer:
             self.cells.data_ptr() if self.cells is not None else None, self.n_static, M.ctypes.data_as(C.POINTER(C.c_float)),
             W, H, levels, C.byref(inst), idx, dep, ws.data_ptr(), ws.numel(), stream), "read_splat_forward_instances")
 
+    def annotate(self, total_m, W, H, idx0, depth0):
+        """Frame annotations (read_amd/annotate.py) of the level-0 frame (idx0, depth0) that ``render(total_m, W,
+        H, ...)`` wrote with the CURRENT instance list: -> ``Annotation`` — per pixel the object and the handle of the instance
+        that drew it, per instance the visible and amodal boxes, counts and nearest depth.  The matrices are the same host
+        arithmetic as the frame's (``instance_matrices``), so the bits agree.  Stream-ordered; ``Annotation.check()`` tells
+        whether frame and list belonged together."""
+        from . import annotate as ann
+        M0 = _host_f32(total_m).reshape(-1, 16)
+        if M0.shape[0] != 1:
+            raise NotImplementedError(f"more than one camera ({M0.shape[0]}) with annotate: an edited frame has one")
+        if self._inst is None:                                   # a plain cloud: every pixel is static or empty
+            return ann.annotate_frame(self.xyz, None, 0, [], self.xyz[:0], [], [], [], np.zeros((0, 16), np.float32), [], [],
+                                      W, H, idx0, depth0)
+        lst = self._instance_list()
+        K_own = len(self._own_ranges)
+        foreign = [(base, int(f.shape[0]), self._ranges[K_own + j][0]) for j, (f, base) in enumerate(self._foreign)]
+        return ann.annotate_frame(self.xyz, self.labels, K_own, foreign, self._pool_xyz,
+                                  [self._ranges[k - 1][0] for k, _, _ in lst], [self._ranges[k - 1][1] for k, _, _ in lst],
+                                  [k for k, _, _ in lst], self.instance_matrices(M0[0]), [v for _, _, v in lst],
+                                  list(self._inst.keys()), W, H, idx0, depth0)
+
     def _outputs(self, B, W, H, levels, want_depth, out):
         """The level lists (idx, depth | None) of a frame — fresh ones, or the caller's ``out`` — and the host arrays of their
         device pointers."""

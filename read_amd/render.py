@@ -514,6 +514,34 @@ class Scene:
         return self._selected(labels)
 
 
+    # ---- frame annotations: what drew each pixel (read_amd/annotate.py) ------------------------------------
+    def annotation_handle(self, handle):
+        """The value ``Annotation.instances`` / ``.handles`` carry for the instance ``add_object_instance`` returned ``handle`` for
+        (the live rasteriser's own handle).  Object k itself — the labelled points where they are — is k - 1."""
+        self.rasterizer()
+        return self._scene_instance(handle)['raster']
+
+    def annotate_frame(self, viewport_size):
+        """Extension: render level 0 with depth of the current camera and edits through the live rasteriser and annotate it -> an
+        ``annotate.Annotation``: per pixel the object and the instance that drew it, per instance boxes and counts.  Pinhole
+        frames of the 1-px point-id raster only."""
+        if self.xyz is None:
+            raise ValueError("scene has no point cloud (set_vertices)")
+        if self.panorama is not None:
+            raise NotImplementedError("a panorama camera (set_panorama) with annotate_frame: the instance match re-projects with the "
+                                      "pinhole projection")
+        if self.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with annotate_frame: annotations "
+                                      "describe the 1-px point-id frame")
+        W, H = int(viewport_size[0]), int(viewport_size[1])
+        raster = self.rasterizer()
+        M = self.total_matrix()
+        if M.shape[0] != 1:
+            raise NotImplementedError("more than one camera with annotate_frame")
+        idx, dep = raster.render(M, W, H, 1)
+        return raster.annotate(M[0], W, H, idx[0], dep[0])
+
+
 class StitchedScene:
     """Extension (not in NNScene): several ``Scene`` objects ("parts", 1..8) drawn into one frame — scene stitching
     (read_amd/stitch.py).  Part s is placed by ``set_part_pose(s, P)`` (M_s = M_0 @ P_s, P None = identity) and hidden or shown by
@@ -598,6 +626,10 @@ class StitchedScene:
 
     def total_matrix(self):
         return self.scenes[0].total_matrix()
+
+    def annotate_frame(self, *args, **kwargs):
+        raise NotImplementedError("annotate_frame on a StitchedScene: instances belong to a part and the merged frame carries "
+                                  "stitched ids; annotate the parts' own frames")
 
     def select_boxes(self, *args, **kwargs):
         raise NotImplementedError("select_boxes on a StitchedScene: labels belong to a part; select on the parts "
