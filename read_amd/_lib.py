@@ -188,6 +188,7 @@ SIGNATURES = {
     "read_unet_set_f4x1": (_i, [_vp, _vp]),
     "read_conv_pack_f4x1_host": (_i, [_i, _i, _vp, _vp, _vp]),
     "read_gated_conv_forward_f4x1": (_i, [C.POINTER(ConvDesc), _vp, _vp]),
+    "read_conv_f4x1_pair_occupancy": (_i, []),
     "read_conv_kernel_family": (_i, [_vp]),
     "read_conv_sc_floats": (_sz, [_i, _i]),
     "read_conv_pack_sc_host": (_i, [_i, _i, _vp, _vp, _vp]),

@@ -2606,6 +2606,309 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
 }
 
 // ------------------------------------------------------------------------------------------
+// The F(4,3)-by-rows kernel above for TWO resident workgroups per CU (config -13).
+//
+// Why: gated_conv_f4x1h_kernel is short of concurrency, not of a pipe: 122,880 bytes of LDS and more than 400 registers make it
+// one workgroup per CU and one wave per SIMD, so every exposed patch miss, weight fetch and epilogue instruction stalls the only
+// wave its SIMD has.  This kernel halves both (one V image, at most 256 registers) and leaves the overlap to the hardware: while one
+// workgroup transforms, waits for its patch or gates a unit, its partner on the same SIMDs issues MFMAs.
+//
+// Same unit, operand (wp_f4x1), walk, group map, epar, transform, split and epilogue arithmetic as the kernel above, and per
+// accumulator the same order of MFMAs (chunk, tap ky 0..2 as the row pairs arrive, piece pair 0..2): the output equals that kernel's
+// bit for bit (tests/test_gpu_conv_f4x1_pair.py).  What differs is the schedule of a chunk:
+//     barrier -> transform (registers -> V) -> barrier -> 216 MFMAs -> [unit epilogue ->] patch loads of the next chunk
+//   * one V image: the transform of chunk + 1 cannot run beside the MFMAs of chunk, so there is no 35-step shadow schedule;
+//   * the 60 patch registers are dead during the MFMA phase and share their space with the operand rings: the patch of the next
+//     chunk is requested behind the last MFMA, that of the next unit behind the epilogue;
+//   * weight ring of two frequencies (six fragments), fetched one frequency ahead within a chunk, the first frequency under the
+//     transform; one fragment of 2^-11 Uh, formed per (block, tap) pair behind the first MFMA of the pair before;
+//   * one stage instance: the accumulators are cleared in front of a unit instead of by a first-stage copy of the 216 MFMAs.
+// The symbol deliberately does not match gated_conv_*kernel: tests/test_isa_guards.py counts the kernels of that pattern.
+__global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs a)
+{
+    using WG = F4x1Geom;
+    __shared__ __attribute__((aligned(16))) unsigned lds[WG::VBUF];                          // one V image: 61,440 bytes
+    __shared__ __attribute__((aligned(16))) float epar[6][32];  // the group's epilogue parameters: b_f, -log2e b_m, BN scale, BN shift, 1 / s_f, -log2e / s_m
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const SrcDev s = a.src[0];
+    const int groups = a.CoutPad >> 5, G = gridDim.x;
+    const int g = blockIdx.x % groups;
+    const int n = a.nchunks;                                   // 32-channel chunks
+
+    int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit (8 x 32 pixel block)
+    int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // patch cursor: one chunk ahead
+    auto step_tile = [&](int &ty_, int &tx_) {
+        ty_ += a.wino_dby;
+        tx_ += a.wino_dbx;
+        if (tx_ >= a.tiles_x) {
+            tx_ -= a.tiles_x;
+            ++ty_;
+        }
+    };
+
+    // ---- transform role (the kernel above's): thread = (segment sg, channel pair cp) of patch rows 2 i + (w >> 1), i = 0 .. 4
+    const int cp = lane & 15, sg = (wv & 1) * 4 + (lane >> 4);
+    constexpr unsigned OOR = 0x80000000u;
+    unsigned xoff[6];
+    int rowoff[5];
+    bool rowok[5];
+    const unsigned src_bytes = (unsigned)(a.inH * s.W * s.C) * 4u;
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s.p), 0, src_bytes, 0x00020000);
+    auto set_patch = [&]() {
+        const int y0 = pby * 8 - 1 + (wv >> 1), x0 = pbx * 32 + 4 * sg - 1;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int yy = y0 + 2 * i;
+            rowok[i] = (unsigned)yy < (unsigned)a.inH;
+            const int yc = yy < 0 ? 0 : yy >= a.inH ? a.inH - 1 : yy;
+            rowoff[i] = yc * s.W * s.C * 4;
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) xoff[c] = (unsigned)(x0 + c) < (unsigned)a.inW ? (unsigned)((x0 + c) * s.C + 2 * cp) * 4u : OOR;
+    };
+    auto advance = [&]() {
+        if (++pchunk == n) {
+            pchunk = 0;
+            if (pu + G < a.n_units) {
+                pu += G;
+                step_tile(pby, pbx);
+            }
+            set_patch();
+        }
+    };
+    f32x2 d2[5][6];                                            // the five row segments of the chunk under transform: (channel 2 cp, 2 cp + 1)
+    // a row outside the image reads through a descriptor of no records (zeros): the rows are wave-uniform, so the choice costs scalar
+    // instructions where a per-lane offset select would cost 30 vector registers
+    const auto rsrc_none = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s.p), 0, 0, 0x00020000);
+    auto gload_patch = [&]() {
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+#pragma unroll
+            for (int c = 0; c < 6; ++c)
+                d2[i][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rowok[i] ? rsrc : rsrc_none, xoff[c], rowoff[i] + pchunk * 128, 0));
+    };
+    auto bt6 = [](f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5) {
+        const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2), f = pk_sub(x3, x1), h = pk_sub(x4, x2);
+        const f32x2 y0 = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
+        const f32x2 y5 = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
+        x0 = y0;
+        x1 = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
+        x2 = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
+        x3 = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
+        x4 = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
+        x5 = y5;
+    };
+    const int vwoff = (wv >> 1) * WG::VROW + sg * 16 + (((cp >> 2) ^ ((-wv) & 3)) << 2) + (cp & 3);
+    auto split_store = [&](const f32x2 x, int i, int fq) {
+        unsigned hi, lo;
+        float r0, r1;
+        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x.x), "v"(x.y));
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x.x));                    // x - f32(hi), exact
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x.y));
+        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
+        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
+        lds[vwoff + 2 * i * WG::VROW + fq * WG::VFREQ] = hi;
+        lds[vwoff + 2 * i * WG::VROW + fq * WG::VFREQ + 128] = lo;
+    };
+
+    // ---- A operand (weights): fragment (chunk, ky, fq), consumed in the order (fq, ky); ring of two frequencies
+    const char *const wbase = reinterpret_cast<const char *>(a.wp_f4x1) + ((size_t)(g * 4 + wv) * n) * (18 * 2048);
+    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(wbase), 0, (unsigned)n * (18 * 2048), 0x00020000);
+    const unsigned wvoff = lane * 16;
+    constexpr int RW = 6;
+    u32x4 Wh[RW], Wl[RW];
+    f16x8 Ws;                                                  // 2^-11 Uh of the (block, tap) pair that comes next
+    auto wload = [&](int chunk, int fq, int ky) {
+        const int slot = (fq & 1) * 3 + ky;
+        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048, 0);
+        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048 + 1024, 0);
+    };
+    auto wscale = [&](int fq, int ky) {
+        const _Float16 k = (_Float16)0x1p-11f;
+        Ws = __builtin_bit_cast(f16x8, Wh[(fq & 1) * 3 + ky]) * f16x8{k, k, k, k, k, k, k, k};
+    };
+    // ---- B operand: row pair s (rows s, s + 1) of frequency fq; ring of three, fetched two pairs ahead
+    const int t16 = lane & 15, kl = lane >> 4;
+    const int vrd_e = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-(t16 >> 2)) & 3)) << 2);
+    const int vrd_o = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-((t16 >> 2) ^ 2)) & 3)) << 2);
+    constexpr int RB = 3;
+    u32x4 Bh[RB], Bl[RB];
+    auto bload = [&](int idx) {                                // idx = fq * 9 + s
+        const int fq = idx / 9, sp = idx % 9;
+        const int o = sp * WG::VROW + fq * WG::VFREQ + ((sp & 1) ? vrd_o : vrd_e);
+        Bh[idx % RB] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + o, 16));
+        Bl[idx % RB] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + o + 128, 16));
+    };
+
+    f32x4 acc[4][6];
+    const auto out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)(a.outH * a.outW * a.out_cstride) * 4u, 0x00020000);
+    const auto res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.residual ? a.residual : a.out), 0,
+                                                            (unsigned)(a.outH * a.outW * a.Cout) * 4u, 0x00020000);
+    const float *const wsc = reinterpret_cast<const float *>(a.wp_f4x1) + (size_t)n * 1152 * a.CoutPad;      // 1 / s: [f | m][CoutPad]
+    if (tid < 192) {                                           // the group is fixed per workgroup: its epilogue parameters go to LDS once
+        constexpr float L2E = 1.44269504088896341f;
+        const int arr = tid >> 5, c = g * 32 + (tid & 31);
+        const float v = arr < 4 ? a.params[arr * a.CoutPad + c] : wsc[(arr - 4) * a.CoutPad + c];
+        epar[arr][tid & 31] = (arr == 1 || arr == 5) ? v * -L2E : v;
+    }
+
+    // ---- prologue: patch(0) -> registers
+    set_patch();
+    gload_patch();
+
+    // One stage = one 32-channel chunk: the transform of its patch into V, then 216 MFMAs (6 frequencies x 12 (block, tap) pairs x
+    // 3 piece pairs) in the order of the kernel above, then the loads of the next chunk's patch.
+    auto stage_body = [&](int chunk) {
+        __syncthreads();                                              // every wave has fetched its last B operand of the image before
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) wload(chunk, 0, ky);           // the first frequency's fragments travel under the transform
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            bt6(d2[i][0], d2[i][1], d2[i][2], d2[i][3], d2[i][4], d2[i][5]);
+#pragma unroll
+            for (int fq = 0; fq < 6; ++fq) split_store(d2[i][fq], i, fq);
+        }
+        __syncthreads();                                              // V(chunk) is complete
+        bload(0);
+        bload(1);
+        wscale(0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int fq = 0; fq < 6; ++fq)
+#pragma unroll
+            for (int sp = 0; sp < 9; ++sp)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    // the (block, tap) pairs that read row pair sp: odd sp (nb, 1); even sp (nb - 1, 2) and then (nb, 0)
+                    const int nb = (sp & 1) ? sp >> 1 : (sp >> 1) - 1 + q, ky = (sp & 1) ? 1 : q ? 0 : 2;
+                    if (((sp & 1) && q) || nb < 0 || nb > 3) continue;
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) {
+                        // MFMA slot: row pairs 2, 4, 6 carry two (block, tap) pairs, the others one: first slots 0 3 6 12 15 21 24 30 33
+                        const int mb = 3 * sp + 3 * ((sp > 0 ? sp - 1 : 0) / 2);
+                        const int ms = mb + ((!(sp & 1) && q && sp > 0) ? 3 : 0) + pc, idx = fq * 9 + sp;
+                        if (ms == mb && idx + 2 < 54) bload(idx + 2);                    // B operands two row pairs ahead
+                        const int ws = (fq & 1) * 3 + ky;
+                        const f16x8 av = pc == 0 ? Ws : __builtin_bit_cast(f16x8, pc == 1 ? Wl[ws] : Wh[ws]);
+                        const f16x8 bv = __builtin_bit_cast(f16x8, pc == 0 ? Bl[idx % RB] : Bh[idx % RB]);
+                        acc[nb][fq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[nb][fq], 0, 0, 0);
+                        // ---- shadow items
+                        // (at the last frequency nothing is ahead: the ring is empty while the next patch is loaded and transformed)
+                        if (fq < 5 && (ms == 5 || ms == 11 || ms == 17)) wload(chunk, fq + 1, (ms - 5) / 6);      // weights one frequency ahead
+                        if (pc == 1) {                                                   // 2^-11 Uh of the next pair: the taps come in the order 0 1 2 0 1 2 ...
+                            if (ms < 33) wscale(fq, (ms / 3 + 1) % 3);
+                            else if (fq < 5) wscale(fq + 1, 0);
+                        }                         // 2^-11 Uh of the next frequency: tap ky's last use was slot 27 + 3 ky
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+    };
+
+    for (int u = blockIdx.x; u < a.n_units; u += G) {
+        // cleared where they live, in the accumulation file (the constraint also makes the compiler split the 256 registers of a wave
+        // into vector and accumulation halves instead of taking all of them as vector registers)
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+            for (int fq = 0; fq < 6; ++fq) asm volatile("v_accvgpr_write_b32 %0, 0\n\tv_accvgpr_write_b32 %1, 0\n\tv_accvgpr_write_b32 %2, 0\n\tv_accvgpr_write_b32 %3, 0"
+                                                        : "=a"(acc[nb][fq][0]), "=a"(acc[nb][fq][1]), "=a"(acc[nb][fq][2]), "=a"(acc[nb][fq][3]));
+        for (int chunk = 0; chunk < n; ++chunk) {
+            stage_body(chunk);
+            if (chunk + 1 < n) {                                       // the next chunk's patch, into the registers the transform left
+                advance();
+                gload_patch();
+            }
+        }
+
+        // ================= unit epilogue: the kernel above's, expression for expression =================
+        // the lane number once more, opaque to the compiler: it would otherwise move everything below that depends on the lane alone in
+        // front of the unit loop and hold it in vector registers across the stages, which have none to spare
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int e16 = ln & 15, cq = (ln >> 4) & 1, hf = ln >> 5;
+        const int c0 = g * 32 + wv * 8 + 4 * cq;
+        const int oy = by * 8 + 4 * hf + (e16 >> 3), ox = bx * 32 + 4 * (e16 & 7);           // this lane finishes rows oy, oy + 2
+        const int cl = wv * 8 + 4 * cq;
+        const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
+        const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
+        const f32x4 isf = *reinterpret_cast<const f32x4 *>(&epar[4][cl]), ism = *reinterpret_cast<const f32x4 *>(&epar[5][cl]);
+        constexpr float LOG2E = 1.44269504088896341f;
+        asm volatile("s_nop 15\n\ts_nop 3");                            // the last MFMA's result, read below through an asm the hazard checker does not see
+#pragma unroll
+        for (int py = 0; py < 2; ++py) {
+            unsigned rvoff[4], ovoff[4];
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                const bool in = (oy + 2 * py < a.outH) & (ox + px < a.outW) & (c0 < a.Cout);
+                const int pix = (oy + 2 * py) * a.outW + ox + px;
+                rvoff[px] = in ? (unsigned)((pix * a.Cout + c0) * 4) : OOR;
+                ovoff[px] = in ? (unsigned)((pix * a.out_cstride + c0) * 4) : OOR;
+            }
+            f32x4 rv[4];
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                rv[px] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (a.residual) rv[px] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvoff[px], 0, 0));
+            }
+            f32x4 Y[2][4];                                             // blocks py and py + 2: [block][pixel of the tile]
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                // one block's six accumulators out of the accumulation file at a time: left to itself the compiler copies all 96
+                // registers behind the chunk loop, which the 128 vector registers of this kernel do not hold
+                f32x4 m[6];
+#pragma unroll
+                for (int fq = 0; fq < 6; ++fq)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(m[fq][k]) : "a"(acc[py + 2 * h][fq][k]));
+                const f32x4 s1 = m[1] + m[2], d1 = pk_sub4(m[1], m[2]);
+                const f32x4 s2 = m[3] + m[4], dd2 = pk_sub4(m[3], m[4]);
+                Y[h][0] = m[0] + s1 + s2;
+                Y[h][1] = d1 + 2.0f * dd2;
+                Y[h][2] = s1 + 4.0f * s2;
+                Y[h][3] = d1 + 8.0f * dd2 + m[5];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            // lanes 0..31 hold conv_f, lanes 32..63 conv_m of the same channels: after the swap the lower half finishes blocks 0, 1
+            // and the upper half blocks 2, 3, both with f and m of a pixel in one lane
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                u32x4 u0 = __builtin_bit_cast(u32x4, Y[0][px]), u1 = __builtin_bit_cast(u32x4, Y[1][px]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
+                    u0[k] = sw[0];
+                    u1[k] = sw[1];
+                }
+                f32x4 f = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u0), isf, bf);
+                const f32x4 mm = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u1), ism, bml);
+                if (a.elu) {
+                    const f32x4 fe = f * LOG2E;
+                    f32x4 e;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = __builtin_amdgcn_exp2f(fe[k]);
+                    e = e + f32x4{-1.0f, -1.0f, -1.0f, -1.0f};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = f[k] > 0.0f ? f[k] : e[k];
+                }
+                f32x4 sg_, t;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) t[k] = __builtin_amdgcn_exp2f(mm[k]);
+                t = t + f32x4{1.0f, 1.0f, 1.0f, 1.0f};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sg_[k] = __builtin_amdgcn_rcpf(t[k]);
+                const f32x4 v = (f * sg_) * sc + sh + rv[px];
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[px], 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        step_tile(by, bx);
+        advance();                                                     // the next unit's first patch (the last unit: its own again)
+        gload_patch();
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // DIRECT 3x3 / stride-1 gated convolution with split fp32 operands on the f16 matrix cores (round 6, second kernel of the round).
 //
 // Why: the attribution of the split-operand Winograd kernel above (profiles/r6_w4h_ablation.md) — its MFMAs are a fifth of its launch,
@@ -3950,7 +4253,7 @@ int find_config(int ks, int s, int kc, int P, int QG, int WM, int WN, int PF, in
 }
 
 // read_conv_desc.config below zero: the automatic choice, or a request for one kernel.  CFG_SC, CFG_PX, CFG_PXH, CFG_T3H and
-// CFG_F4X1 are refused where the kernel cannot run the launch; the others fall back to the automatic choice.
+// CFG_F4X1 / CFG_F4X1_PAIR are refused where the kernel cannot run the launch; the others fall back to the automatic choice.
 enum ConvForce {
     CFG_AUTO = -1,
     CFG_PX = -2,         // fp32 pixel-lane kernel (1x1)
@@ -3962,7 +4265,8 @@ enum ConvForce {
     CFG_D3H_S2 = -9,     // ... at stride 2
     CFG_PXH = -10,       // split-operand pixel-lane kernel (1x1)
     CFG_T3H = -11,       // ... as an implicit GEMM over a 3x3 layer with 8 - 32 input channels
-    CFG_F4X1 = -12,      // split-operand F(4,3) by rows
+    CFG_F4X1 = -12,      // split-operand F(4,3) by rows, one workgroup per CU (gated_conv_f4x1h_kernel)
+    CFG_F4X1_PAIR = -13, // ... two resident workgroups per CU (f4x1_pair_conv_kernel): accepted exactly where -12 is
 };
 
 // Tuning knobs (the table g_knobs further down: key, normalisation)
@@ -4639,7 +4943,7 @@ static int conv_uses_w4h(const read_conv_desc *d)
     // (FAM's x1 * x2 stays on the fp32 kernel: the second patch costs the transform thread another 72 registers, and the
     //  variant with a shallower weight ring measured SLOWER than the fp32 kernel — 101 / 79 / 68 us against 77 / 69 / 64 at C = 64 / 128 / 256)
     if (!d->wpacked_w4h || d->linear || d->mul || d->src[0].C % 32 != 0 || d->Cout % 32 != 0) return 0;
-    const bool forced = d->config == CFG_W4H || d->config == CFG_F4X1;    // the F(4,3)-by-rows kernel belongs to the same family
+    const bool forced = d->config == CFG_W4H || d->config == CFG_F4X1 || d->config == CFG_F4X1_PAIR;    // the F(4,3)-by-rows kernels belong to the same family
     if (!forced && (d->config != CFG_AUTO || g_w4h <= 0 || d->src[0].C < g_w4h)) return 0;
     return conv_w4_shape(d, d->wpacked_w4h, !forced);
 }
@@ -4758,7 +5062,7 @@ static ConvShape conv_shape(const read_conv_desc *d)
     return s;
 }
 
-enum ConvKernel { CK_SC, CK_T3H, CK_PXH, CK_PX, CK_D3H_S2, CK_D3H, CK_F4X1, CK_W4H, CK_W4, CK_TABLE };
+enum ConvKernel { CK_SC, CK_T3H, CK_PXH, CK_PX, CK_D3H_S2, CK_D3H, CK_F4X1, CK_F4X1_PAIR, CK_W4H, CK_W4, CK_TABLE };
 
 struct ConvRoute {
     ConvKernel kernel;
@@ -4767,6 +5071,19 @@ struct ConvRoute {
     bool wino_auto;      // the automatic choice took the table's Winograd F(2x2) entry (family 2)
     bool w16;            // ... and runs it as the wave-autonomous kernel (unless the debug timeline records the launch)
 };
+
+// Units of the F(4x4) family's launches: 8 x 32 output pixels x 32 output channels
+static int w4_units(const ConvShape &s) { return ceil_div(s.outW, 32) * ceil_div(s.outH, 8) * s.groups; }
+
+// Which automatic F(4,3)-by-rows launches run as two workgroups per CU (f4x1_pair_conv_kernel) instead of one
+// (gated_conv_f4x1h_kernel); the results are the same bits.  Level by level from the A/B of profiles/f4x1_pair_ab.md (1216 x 352, the
+// kernels alternated in one process; a level moves only if its slowest pair cell beats the fastest single cell and the gain in means
+// exceeds the single kernel's round-to-round spread):
+//   * n_units > n_cu: with at most one unit per CU no two workgroups share a CU and nothing can overlap (C = 256: 240 units, the pair
+//     kernel measured 4 - 6 us SLOWER per launch: its chunk schedule without a partner);
+//   * Cin = 32 (one chunk per unit, 1672 units) gained 3.4 - 4.8 us per launch and Cin = 128 (four chunks, 440 units) 2.4 - 2.6 us;
+//   * Cin = 64 (two chunks, 836 units) gained 0.3 - 1.3 us, inside the spread: it stays; widths in between were not measured and stay too.
+static bool f4x1_pair_auto(int Cin, int n_units, int n_cu) { return n_units > n_cu && (Cin == 32 || Cin == 128); }
 
 // Precedence = the order of the tests.  wp_f4x1: the F(4,3)-by-rows operand that travels beside the descriptor, or NULL.
 static ConvRoute conv_route(const read_conv_desc *d, const void *wp_f4x1)
@@ -4780,8 +5097,14 @@ static ConvRoute conv_route(const read_conv_desc *d, const void *wp_f4x1)
     else if (conv_uses_d3h(d)) r.kernel = CK_D3H;
     // ... of that family's launches, those with at least conv_f4x1 input channels take the F(4,3)-by-rows kernel (both report family 5); a
     // caller without its operand (a blob packed before the kernel existed) keeps running on the F(4x4) kernel
-    else if (conv_uses_w4h(d))
-        r.kernel = wp_f4x1 && (d->config == CFG_F4X1 || (d->config == CFG_AUTO && g_f4x1 > 0 && d->src[0].C >= g_f4x1)) ? CK_F4X1 : CK_W4H;
+    // ... and of those the automatic choice sends the shapes of f4x1_pair_auto to the two-workgroups-per-CU form of the kernel (same bits)
+    else if (conv_uses_w4h(d)) {
+        const bool forced = d->config == CFG_F4X1 || d->config == CFG_F4X1_PAIR;
+        const bool f4x1 = wp_f4x1 && (forced || (d->config == CFG_AUTO && g_f4x1 > 0 && d->src[0].C >= g_f4x1));
+        const bool pair = f4x1 && (d->config == CFG_F4X1_PAIR ||
+                                   (d->config == CFG_AUTO && f4x1_pair_auto(d->src[0].C, w4_units(conv_shape(d)), device_cus())));
+        r.kernel = !f4x1 ? CK_W4H : pair ? CK_F4X1_PAIR : CK_F4X1;
+    }
     else if (conv_uses_w4(d)) r.kernel = CK_W4;
     else if (conv_sane(d)) {
         const ConvShape s = conv_shape(d);
@@ -4811,7 +5134,7 @@ static ConvRoute conv_route(const read_conv_desc *d, const void *wp_f4x1)
 static int route_family(const ConvRoute &r)
 {
     static const int family[] = {/* CK_SC */ 1, /* CK_T3H */ 8, /* CK_PXH */ 7, /* CK_PX */ 0, /* CK_D3H_S2 */ 6, /* CK_D3H */ 6,
-                                 /* CK_F4X1 */ 5, /* CK_W4H */ 5, /* CK_W4 */ 4, /* CK_TABLE */ 0};
+                                 /* CK_F4X1 */ 5, /* CK_F4X1_PAIR */ 5, /* CK_W4H */ 5, /* CK_W4 */ 4, /* CK_TABLE */ 0};
     return r.wino_auto ? 2 : family[r.kernel];
 }
 
@@ -5027,6 +5350,8 @@ static int refuse_f4x1_config(const read_conv_desc *d, bool f4x1)
 {
     READ_CHECK_ARG(d->config != CFG_F4X1 || f4x1, "read_gated_conv_forward: config -12 takes the launches of the split-operand 3x3/s1 family "
                    "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
+    READ_CHECK_ARG(d->config != CFG_F4X1_PAIR || f4x1, "read_gated_conv_forward: config -13 takes the launches of the split-operand 3x3/s1 family "
+                   "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
     return READ_OK;
 }
 
@@ -5064,7 +5389,7 @@ static int launch_d3h_s2(const read_conv_desc *d, ConvKArgs &a, const ConvShape 
 // F(4x4,3x3) in fp32 (CK_W4) or with split operands (CK_W4H), F(4,3) by rows (CK_F4X1), the direct split-operand kernel (CK_D3H)
 static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, ConvKernel kernel, const void *wp_f4x1, hipStream_t stream)
 {
-    const bool d3h = kernel == CK_D3H, f4x1 = kernel == CK_F4X1, w4h = f4x1 || kernel == CK_W4H;
+    const bool d3h = kernel == CK_D3H, pair = kernel == CK_F4X1_PAIR, f4x1 = pair || kernel == CK_F4X1, w4h = f4x1 || kernel == CK_W4H;
     int rc = take_out_gated(d, kernel == CK_W4, a);
     if (rc != READ_OK) return rc;
     rc = refuse_f4x1_config(d, f4x1);
@@ -5080,8 +5405,8 @@ static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvSha
     READ_CHECK_ARG(!f4x1 || (uintptr_t)wp_f4x1 % 16 == 0, "read_gated_conv_forward: wpacked_f4x1 misaligned");
     a.nchunks = (w4h || d3h) ? s.Cin / 32 : s.Cin / s.kc;
     a.tiles_x = ceil_div(s.outW, 32);
-    a.n_units = a.tiles_x * ceil_div(s.outH, 8) * s.groups;
-    const int n_cu = device_cus(), groups = s.groups;
+    a.n_units = w4_units(s);
+    const int n_cu = (pair ? 2 : 1) * device_cus(), groups = s.groups;      // resident workgroups: the pair kernel has two per CU
     int cap = n_cu;
     if (g_w4_grid) {                                               // A/B: every workgroup the same number of units
         const int whole = n_cu - n_cu % groups > 0 ? n_cu - n_cu % groups : groups;
@@ -5094,7 +5419,8 @@ static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvSha
     if (d3h) {
         fn = d->mul ? gated_conv_d3h_kernel<true> : gated_conv_d3h_kernel<false>;
         threads = 512;
-    } else if (f4x1) fn = gated_conv_f4x1h_kernel;
+    } else if (pair) fn = f4x1_pair_conv_kernel;
+    else if (f4x1) fn = gated_conv_f4x1h_kernel;
     else if (w4h) fn = gated_conv_wino4h_kernel;
     READ_CHECK_ARG(!d->linear || !d->mul, "read_gated_conv_forward: linear launches take no multiplier");
     hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(threads), 0, stream, a);
@@ -5162,6 +5488,13 @@ static int launch_table(const read_conv_desc *d, ConvKArgs &a, const ConvShape &
     return READ_OK;
 }
 
+// resident workgroups per CU the runtime grants f4x1_pair_conv_kernel (2 by design: 62,208 bytes of LDS, at most 256 registers); -1: the query failed
+int f4x1_pair_occupancy()
+{
+    int n = 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f4x1_pair_conv_kernel, 256, 0) == hipSuccess ? n : -1;
+}
+
 int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *wp_f4x1)
 {
     ConvKArgs a;
@@ -5177,6 +5510,7 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
     case CK_D3H_S2: return launch_d3h_s2(d, a, s, stream);
     case CK_D3H:
     case CK_F4X1:
+    case CK_F4X1_PAIR:
     case CK_W4H:
     case CK_W4: return launch_w4_family(d, a, s, r.kernel, wp_f4x1, stream);
     case CK_TABLE: return launch_table(d, a, s, r, stream);
@@ -5186,11 +5520,13 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
 
 }  // namespace readhip
 
+extern "C" int read_conv_f4x1_pair_occupancy(void) { return readhip::f4x1_pair_occupancy(); }
+
 extern "C" int read_conv_kernel_family(const read_conv_desc *desc) { return desc ? readhip::conv_family(desc) : -1; }
 
 // The same launch with the F(4,3)-by-rows operand (read_conv_pack_f4x1_host) beside the descriptor: the descriptor struct is
-// frozen at ABI version 3.  A launch of the split-operand 3x3/s1 family that conv_f4x1 (or config -12) names runs on
-// gated_conv_f4x1h_kernel; every other launch behaves exactly as read_gated_conv_forward.  A host that packed ONLY this order leaves
+// frozen at ABI version 3.  A launch of the split-operand 3x3/s1 family that conv_f4x1 (or config -12 / -13) names runs on
+// gated_conv_f4x1h_kernel or, two workgroups per CU, on f4x1_pair_conv_kernel (config -13; f4x1_pair_auto); every other launch behaves exactly as read_gated_conv_forward.  A host that packed ONLY this order leaves
 // wpacked_w4h NULL: the family's shape test then sees this operand, and a launch that would read it as the F(4x4) order is refused.
 extern "C" int read_gated_conv_forward_f4x1(const read_conv_desc *desc, const void *wpacked_f4x1, void *stream)
 {
