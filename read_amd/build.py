@@ -18,7 +18,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libreadhip.so")
-SOURCES = ["api_common.cpp", "splat.hip", "select.hip", "annotate.hip", "gather.hip", "conv.hip", "train.hip", "unet.cpp"]
+SOURCES = ["api_common.cpp", "splat.hip", "select.hip", "annotate.hip", "gather.hip", "conv.hip", "conv_pack.cpp", "train.hip", "unet.cpp"]
 DEBUG_SOURCES = ["probe.hip"]        # measurement probes (read_hip_debug.h): libreadhip_debug.so only, never the product
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-x", "hip",

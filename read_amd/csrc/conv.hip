@@ -664,6 +664,30 @@ __device__ __forceinline__ float4 load_f4(const char *sbase, unsigned voff)
     return *reinterpret_cast<const float4 *>(sbase + voff);
 }
 
+// The unit walk of every persistent kernel below: a workgroup's next unit is (wino_dby, wino_dbx) tiles on, wrapping at the row's end.
+__device__ __forceinline__ void step_tile(const ConvKArgs &a, int &ty, int &tx)
+{
+    ty += a.wino_dby;
+    tx += a.wino_dbx;
+    if (tx >= a.tiles_x) {
+        tx -= a.tiles_x;
+        ++ty;
+    }
+}
+
+// The prefetch cursor (chunk pchunk of unit pu at tile (pby, pbx)) one chunk on; behind a unit's last chunk on to the workgroup's next
+// unit, past the last unit that one again.  True: the cursor changed unit, the patch addresses are to be set again.
+__device__ __forceinline__ bool cursor_advance(const ConvKArgs &a, int n, int G, int &pchunk, int &pu, int &pby, int &pbx)
+{
+    if (++pchunk != n) return false;
+    pchunk = 0;
+    if (pu + G < a.n_units) {
+        pu += G;
+        step_tile(a, pby, pbx);
+    }
+    return true;
+}
+
 template <bool TRACE, bool MUL>
 __global__ __launch_bounds__(256, 2) void gated_conv_wino_kernel(const ConvKArgs a)
 {
@@ -683,14 +707,6 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino_kernel(const ConvKArgs
     // ---- units: u = blockIdx.x + k G  ->  tile u / groups = (by, bx), advanced by (wino_dby, wino_dbx) per step
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
 
     // ---- input patch staging.  Lane constants: LDS slot and byte offset of its float4s relative to the patch
     // origin; per unit only the scalar origin and the inside-the-image mask change.  Outside pixels load the
@@ -726,7 +742,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino_kernel(const ConvKArgs
             pchunk = 0;
             if (pu + G < a.n_units) {
                 pu += G;
-                step_tile(pby, pbx);
+                step_tile(a, pby, pbx);
             }
             set_patch();
         }
@@ -1026,7 +1042,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino_kernel(const ConvKArgs
                     }
                 }
         }
-        step_tile(by, bx);
+        step_tile(a, by, bx);
         __builtin_amdgcn_s_setprio(0);
         if (TRACE) t_ep[0] += __builtin_amdgcn_s_memrealtime() - t_e0;
     }
@@ -1065,6 +1081,85 @@ __device__ __forceinline__ f32x4 pk_sub4(f32x4 a, f32x4 b)
 {
     const f32x2 lo = pk_sub(a.lo, b.lo), hi = pk_sub(a.hi, b.hi);
     return f32x4{lo.x, lo.y, hi.x, hi.y};
+}
+
+// ------------------------------------------------------------------------------------------
+// Blocks that the Winograd F(4x4) and split-operand kernels below share.  Each is defined once, so "the same arithmetic as the
+// kernel above" holds by construction; tools/isa_diff.py shows that a kernel built from them is the code it was before.
+// ------------------------------------------------------------------------------------------
+// The six-point input transform, in place on six channel pairs (14 packed operations):
+// B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
+__device__ __forceinline__ void bt6(f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5)
+{
+    const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2), f = pk_sub(x3, x1), h = pk_sub(x4, x2);
+    const f32x2 y0 = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
+    const f32x2 y5 = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
+    x0 = y0;
+    x1 = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
+    x2 = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
+    x3 = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
+    x4 = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
+    x5 = y5;
+}
+
+// The 4 x 6 output transform A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1] on six accumulators
+__device__ __forceinline__ void at6(const f32x4 (&m)[6], f32x4 (&y)[4])
+{
+    const f32x4 s1 = m[1] + m[2], d1 = pk_sub4(m[1], m[2]);
+    const f32x4 s2 = m[3] + m[4], dd2 = pk_sub4(m[3], m[4]);
+    y[0] = m[0] + s1 + s2;
+    y[1] = d1 + 2.0f * dd2;
+    y[2] = s1 + 4.0f * s2;
+    y[3] = d1 + 8.0f * dd2 + m[5];
+}
+
+// fp32 pair (x, y) -> hi = (f16(x), f16(y)) and lo = (f16(2^11 (x - hi.x)), f16(2^11 (y - hi.y))): x = hi + 2^-11 lo to ~2^-22 relative
+__device__ __forceinline__ void split_hl(float x, float y, unsigned &hi, unsigned &lo)
+{
+    float r0, r1;
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x), "v"(y));
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x));                    // x - f32(hi), exact
+    asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(y));
+    const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
+    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
+}
+
+// A 32-channel group's epilogue parameters in LDS: b_f, -log2e b_m, BN scale, BN shift, 1 / s_f, -log2e / s_m (wsc: the operand's
+// row scales 1 / s, [f | m][CoutPad]); written once per workgroup by threads 0 .. 191, read back four channels at a time
+__device__ __forceinline__ void epar_load(float (&epar)[6][32], const ConvKArgs &a, const float *wsc, int g, int tid)
+{
+    if (tid < 192) {
+        constexpr float L2E = 1.44269504088896341f;
+        const int arr = tid >> 5, c = g * 32 + (tid & 31);
+        const float v = arr < 4 ? a.params[arr * a.CoutPad + c] : wsc[(arr - 4) * a.CoutPad + c];
+        epar[arr][tid & 31] = (arr == 1 || arr == 5) ? v * -L2E : v;
+    }
+}
+struct EpiPar {
+    f32x4 bf, bml, sc, sh, isf, ism;
+};
+template <int N>
+__device__ __forceinline__ EpiPar epar_read(const float (&epar)[6][N], int cl)
+{
+    return {*reinterpret_cast<const f32x4 *>(&epar[0][cl]), *reinterpret_cast<const f32x4 *>(&epar[1][cl]),
+            *reinterpret_cast<const f32x4 *>(&epar[2][cl]), *reinterpret_cast<const f32x4 *>(&epar[3][cl]),
+            *reinterpret_cast<const f32x4 *>(&epar[4][cl]), *reinterpret_cast<const f32x4 *>(&epar[5][cl])};
+}
+
+// Lanes 0..31 hold conv_f and lanes 32..63 conv_m of the same channels: after the exchange the lower half-wave holds f and m of the
+// pixels of y0 and the upper half those of y1, f in one register and m in the other (whole-vector bit casts: with __builtin_bit_cast of
+// single vector ELEMENTS this hipcc folds the four swaps into one)
+__device__ __forceinline__ void fm_swap(const f32x4 y0, const f32x4 y1, f32x4 &f, f32x4 &m)
+{
+    u32x4 u0 = __builtin_bit_cast(u32x4, y0), u1 = __builtin_bit_cast(u32x4, y1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
+        u0[k] = sw[0];
+        u1[k] = sw[1];
+    }
+    f = __builtin_bit_cast(f32x4, u0);
+    m = __builtin_bit_cast(f32x4, u1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1116,14 +1211,6 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKA
 
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor (raw patches)
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
 
     // ---- raw patch staging (global -> registers -> LDS), two buffers
     int loff[WG::NI];
@@ -1156,7 +1243,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKA
             pchunk = 0;
             if (pu + G < a.n_units) {
                 pu += G;
-                step_tile(pby, pbx);
+                step_tile(a, pby, pbx);
             }
             set_patch();
         }
@@ -1488,7 +1575,7 @@ __global__ __launch_bounds__(256, 2) void gated_conv_wino16s_kernel(const ConvKA
                     }
                 }
         }
-        step_tile(by, bx);
+        step_tile(a, by, bx);
         __builtin_amdgcn_s_setprio(0);
     }
 }
@@ -1541,14 +1628,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
 
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit (8 x 32 pixel block)
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor (raw patches)
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
 
     // ---- raw patch staging (global -> registers -> LDS), two buffers.  Buffer loads: a lane whose pixel lies outside the image
     // (or whose element does not exist: 1360 float4 over 6 x 256 lanes) carries an out-of-range offset and the hardware returns
@@ -1580,7 +1659,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
             pchunk = 0;
             if (pu + G < a.n_units) {
                 pu += G;
-                step_tile(pby, pbx);
+                step_tile(a, pby, pbx);
             }
             set_patch();
         }
@@ -1844,7 +1923,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
                 }
         }
         if constexpr (LIN == 2) {                                      // dgrad: nothing to gate
-            step_tile(by, bx);
+            step_tile(a, by, bx);
             __builtin_amdgcn_s_setprio(0);
             continue;
         }
@@ -1854,17 +1933,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
 #pragma unroll
         for (int py = 0; py < 2; ++py)
 #pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                u32x4 u0 = __builtin_bit_cast(u32x4, Y[py][px]), u1 = __builtin_bit_cast(u32x4, Y[py + 2][px]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                    u0[k] = sw[0];
-                    u1[k] = sw[1];
-                }
-                Yf[py][px] = __builtin_bit_cast(f32x4, u0);
-                Ym[py][px] = __builtin_bit_cast(f32x4, u1);
-            }
+            for (int px = 0; px < 4; ++px) fm_swap(Y[py][px], Y[py + 2][px], Yf[py][px], Ym[py][px]);
         {
             constexpr float LOG2E = 1.44269504088896341f;
 #pragma unroll
@@ -1897,7 +1966,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4_kernel(const ConvKArg
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[py][px], 0, 0);
                 }
         }
-        step_tile(by, bx);
+        step_tile(a, by, bx);
         __builtin_amdgcn_s_setprio(0);
     }
 }
@@ -1960,14 +2029,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
 
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit (8 x 32 pixel block)
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor (raw patches)
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
 
     // ---- transform role: thread = (tile tl, channel pair cp of the 32-channel chunk); wave w = tiles 4w .. 4w+3 (one tile row of
     // the unit per wave: the patch ROWS are wave-uniform — their offsets travel in SGPRs — the patch COLUMNS are per lane)
@@ -1999,42 +2060,17 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
 #pragma unroll
         for (int r = 0; r < 6; ++r) rmask_d[r] = rmask[r];     // the patch just loaded is the next one to be transformed
         rclamp_d = rclamp;
-        if (++pchunk == n) {
-            pchunk = 0;
-            if (pu + G < a.n_units) {
-                pu += G;
-                step_tile(pby, pbx);
-            }
-            set_patch();
-        }
+        if (cursor_advance(a, n, G, pchunk, pu, pby, pbx)) set_patch();
     };
     f32x2 d2[6][6];                                            // the patch of the chunk under transform: (channel 2 cp, 2 cp + 1)
     auto gload = [&](int r, int c) {
         d2[r][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, xoff[c], rowoff[r] + pchunk * 128, 0));
     };
-    // 1-D transform with B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1] on six
-    // channel pairs: 14 packed operations
-    auto bt6 = [](f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5) {
-        const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2), f = pk_sub(x3, x1), h = pk_sub(x4, x2);
-        const f32x2 y0 = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
-        const f32x2 y5 = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
-        x0 = y0;
-        x1 = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
-        x2 = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
-        x3 = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
-        x4 = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
-        x5 = y5;
-    };
     // V store address (dwords) of this thread: + buffer + frequency * 512 (+ 256: the low piece)
     const int vwoff = tl * 16 + (((cp >> 2) ^ ((-wv) & 3)) << 2) + (cp & 3);
     auto split_store = [&](const f32x2 x, int vb, int fq) {
         unsigned hi, lo;
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x.x), "v"(x.y));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x.x));                    // x - f32(hi), exact
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x.y));
-        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
+        split_hl(x.x, x.y, hi, lo);
         lds[vwoff + vb + fq * WG::VFREQ] = hi;
         lds[vwoff + vb + fq * WG::VFREQ + 256] = lo;
     };
@@ -2095,12 +2131,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
     // the group is fixed per workgroup: its epilogue parameters go to LDS once.  (Loaded from global memory in every unit's epilogue
     // they queued behind the next unit's weight and patch loads, already in flight, and the epilogue waited for those: loads return in
     // order.  Measured on one box, old / new library alternating: 64.9 / 55.3 / 49.2 / 47.3 -> 64.0 / 52.4 / 48.5 / 47.3 us at C = 32 .. 256.)
-    if (tid < 192) {
-        constexpr float L2E = 1.44269504088896341f;
-        const int arr = tid >> 5, c = g * 32 + (tid & 31);
-        const float v = arr < 4 ? a.params[arr * a.CoutPad + c] : wsc[(arr - 4) * a.CoutPad + c];
-        epar[arr][tid & 31] = (arr == 1 || arr == 5) ? v * -L2E : v;
-    }
+    epar_load(epar, a, wsc, g, tid);
 
     // ---- prologue: patch(0) -> registers -> V(0); patch(1) -> registers; the first weight fragments and B operands
     set_patch();
@@ -2177,9 +2208,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
         const int c0 = g * 32 + wv * 8 + 4 * cq;
         const int oy = by * 8 + 4 * (t16 >> 3) + 2 * hf, ox = bx * 32 + 4 * (t16 & 7);           // this lane finishes rows oy, oy + 1
         const int cl = wv * 8 + 4 * cq;
-        const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
-        const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
-        const f32x4 isf = *reinterpret_cast<const f32x4 *>(&epar[4][cl]), ism = *reinterpret_cast<const f32x4 *>(&epar[5][cl]);
+        const auto [bf, bml, sc, sh, isf, ism] = epar_read(epar, cl);
         constexpr float LOG2E = 1.44269504088896341f;
         unsigned rvoff[2][4], ovoff[2][4];
 #pragma unroll
@@ -2226,17 +2255,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
 #pragma unroll
         for (int py = 0; py < 2; ++py)
 #pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                u32x4 u0 = __builtin_bit_cast(u32x4, Y[py][px]), u1 = __builtin_bit_cast(u32x4, Y[py + 2][px]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                    u0[k] = sw[0];
-                    u1[k] = sw[1];
-                }
-                Yf[py][px] = __builtin_bit_cast(f32x4, u0);
-                Ym[py][px] = __builtin_bit_cast(f32x4, u1);
-            }
+            for (int px = 0; px < 4; ++px) fm_swap(Y[py][px], Y[py + 2][px], Yf[py][px], Ym[py][px]);
 #pragma unroll
         for (int py = 0; py < 2; ++py)
 #pragma unroll
@@ -2261,7 +2280,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_wino4h_kernel(const ConvKAr
                 const f32x4 v = (f * sg) * sc + sh + rv[py][px];
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[py][px], 0, 0);
             }
-        step_tile(by, bx);
+        step_tile(a, by, bx);
         __builtin_amdgcn_s_setprio(0);
     }
 }
@@ -2301,6 +2320,41 @@ struct F4x1Geom {
     static constexpr int VROW = 6 * VFREQ;                     // dwords per image row
     static constexpr int VBUF = 10 * VROW;                     // dwords per V buffer (61,440 bytes)
     static constexpr int LDS_DWORDS = 2 * VBUF;                // 122,880 bytes
+
+    // ---- What gated_conv_f4x1h_kernel and f4x1_pair_conv_kernel share beside the blocks above: thread roles, addresses and the order of
+    // a chunk's MFMAs.  The two kernels differ in their schedule only, so one's output equals the other's bit for bit.
+
+    // V store address (dwords) of the transform thread: + 2 i rows + frequency * VFREQ (+ 128: the low piece); the swizzle key
+    // 2 (row & 1) + (segment >> 2) is the wave number for every item
+    static __device__ __forceinline__ int v_store_off(int wv, int sg, int cp)
+    {
+        return (wv >> 1) * VROW + sg * 16 + (((cp >> 2) ^ ((-wv) & 3)) << 2) + (cp & 3);
+    }
+    // V read address (dwords) of MFMA lane (t16 = lane & 15, kl = lane >> 4) inside a row pair, for even and odd pairs
+    static __device__ __forceinline__ int v_read_off(int t16, int kl, int odd)
+    {
+        return (t16 >> 3) * VROW + (t16 & 7) * 16 + ((kl ^ ((-((t16 >> 2) ^ (2 * odd))) & 3)) << 2);
+    }
+    // A operand: wave wv of group g owns W_BYTES per chunk; fragment (chunk, ky, fq) = Uh, then Ul 1024 bytes on.  Behind all groups:
+    // the row scales 1 / s, [f | m][CoutPad]
+    static constexpr int W_BYTES = 18 * 2048;
+    static __device__ __forceinline__ const char *w_base(const ConvKArgs &a, int g, int wv, int n)
+    {
+        return reinterpret_cast<const char *>(a.wp_f4x1) + ((size_t)(g * 4 + wv) * n) * W_BYTES;
+    }
+    static __device__ __forceinline__ int w_frag(int chunk, int fq, int ky) { return ((chunk * 3 + ky) * 6 + fq) * 2048; }
+    static __device__ __forceinline__ const float *row_scales(const ConvKArgs &a, int n)
+    {
+        return reinterpret_cast<const float *>(a.wp_f4x1) + (size_t)n * 1152 * a.CoutPad;
+    }
+    // The MFMAs of a frequency, in the order the row pairs sp = 0 .. 8 arrive: odd sp feeds (block nb, tap 1); even sp feeds
+    // (nb - 1, tap 2) and then (q = 1) (nb, tap 0).  live: the pair exists.  Slots: row pairs 2, 4, 6 carry two (block, tap) pairs, the
+    // others one, three piece pairs each: first slots 0 3 6 12 15 21 24 30 33
+    static __device__ __forceinline__ constexpr int pair_nb(int sp, int q) { return (sp & 1) ? sp >> 1 : (sp >> 1) - 1 + q; }
+    static __device__ __forceinline__ constexpr int pair_ky(int sp, int q) { return (sp & 1) ? 1 : q ? 0 : 2; }
+    static __device__ __forceinline__ constexpr bool pair_live(int sp, int q) { return !(((sp & 1) && q) || pair_nb(sp, q) < 0 || pair_nb(sp, q) > 3); }
+    static __device__ __forceinline__ constexpr int slot_first(int sp) { return 3 * sp + 3 * ((sp > 0 ? sp - 1 : 0) / 2); }
+    static __device__ __forceinline__ constexpr int slot(int sp, int q, int pc) { return slot_first(sp) + ((!(sp & 1) && q && sp > 0) ? 3 : 0) + pc; }
 };
 
 __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArgs a)
@@ -2317,14 +2371,6 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
 
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit (8 x 32 pixel block)
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor (raw patches)
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
 
     // ---- transform role: thread = (segment sg, channel pair cp) of patch rows 2 i + (w >> 1), i = 0 .. 4: the rows are
     // wave-uniform (their offsets travel in SGPRs), the columns are per lane
@@ -2349,42 +2395,16 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
         for (int c = 0; c < 6; ++c) xoff[c] = (unsigned)(x0 + c) < (unsigned)a.inW ? (unsigned)((x0 + c) * s.C + 2 * cp) * 4u : OOR;
     };
     auto advance = [&]() {
-        if (++pchunk == n) {
-            pchunk = 0;
-            if (pu + G < a.n_units) {
-                pu += G;
-                step_tile(pby, pbx);
-            }
-            set_patch();
-        }
+        if (cursor_advance(a, n, G, pchunk, pu, pby, pbx)) set_patch();
     };
     f32x2 d2[5][6];                                            // the five row segments of the chunk under transform: (channel 2 cp, 2 cp + 1)
     auto gload = [&](int i, int c) {
         d2[i][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, rowok[i] ? xoff[c] : OOR, rowoff[i] + pchunk * 128, 0));
     };
-    // B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1] on six channel pairs
-    auto bt6 = [](f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5) {
-        const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2), f = pk_sub(x3, x1), h = pk_sub(x4, x2);
-        const f32x2 y0 = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
-        const f32x2 y5 = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
-        x0 = y0;
-        x1 = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
-        x2 = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
-        x3 = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
-        x4 = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
-        x5 = y5;
-    };
-    // V store address (dwords) of this thread: + buffer + 2 i rows + frequency * 256 (+ 128: the low piece); the swizzle key
-    // 2 (row & 1) + (segment >> 2) is the wave number for every item
-    const int vwoff = (wv >> 1) * WG::VROW + sg * 16 + (((cp >> 2) ^ ((-wv) & 3)) << 2) + (cp & 3);
+    const int vwoff = WG::v_store_off(wv, sg, cp);             // (+ buffer)
     auto split_store = [&](const f32x2 x, int vb, int i, int fq) {
         unsigned hi, lo;
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x.x), "v"(x.y));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x.x));                    // x - f32(hi), exact
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x.y));
-        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
+        split_hl(x.x, x.y, hi, lo);
         lds[vwoff + vb + 2 * i * WG::VROW + fq * WG::VFREQ] = hi;
         lds[vwoff + vb + 2 * i * WG::VROW + fq * WG::VFREQ + 128] = lo;
     };
@@ -2404,16 +2424,15 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
     };
 
     // ---- A operand (weights): fragment (chunk, ky, fq), consumed in the order (fq, ky)
-    const char *const wbase = reinterpret_cast<const char *>(a.wp_f4x1) + ((size_t)(g * 4 + wv) * n) * (18 * 2048);
-    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(wbase), 0, (unsigned)n * (18 * 2048), 0x00020000);
+    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(WG::w_base(a, g, wv, n)), 0, (unsigned)n * WG::W_BYTES, 0x00020000);
     const unsigned wvoff = lane * 16;
     constexpr int RW = 9;                                      // ring of three frequencies x three taps, fetched two frequencies ahead
     u32x4 Wh[RW], Wl[RW];
     f16x8 Ws[2][3];                                            // 2^-11 Uh, one frequency ahead
     auto wload = [&](int chunk, int fq, int ky) {
         const int slot = (fq % 3) * 3 + ky;
-        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048, 0);
-        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048 + 1024, 0);
+        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, WG::w_frag(chunk, fq, ky), 0);
+        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, WG::w_frag(chunk, fq, ky) + 1024, 0);
     };
     auto wscale = [&](int fq, int ky) {
         const _Float16 k = (_Float16)0x1p-11f;
@@ -2421,8 +2440,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
     };
     // ---- B operand: row pair s (rows s, s + 1) of frequency fq; ring of three, fetched two pairs ahead
     const int t16 = lane & 15, kl = lane >> 4;
-    const int vrd_e = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-(t16 >> 2)) & 3)) << 2);
-    const int vrd_o = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-((t16 >> 2) ^ 2)) & 3)) << 2);
+    const int vrd_e = WG::v_read_off(t16, kl, 0), vrd_o = WG::v_read_off(t16, kl, 1);
     constexpr int RB = 3;
     u32x4 Bh[RB], Bl[RB];
     auto bload = [&](int vb, int idx) {                        // idx = fq * 9 + s
@@ -2436,13 +2454,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
     const auto out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)(a.outH * a.outW * a.out_cstride) * 4u, 0x00020000);
     const auto res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.residual ? a.residual : a.out), 0,
                                                             (unsigned)(a.outH * a.outW * a.Cout) * 4u, 0x00020000);
-    const float *const wsc = reinterpret_cast<const float *>(a.wp_f4x1) + (size_t)n * 1152 * a.CoutPad;      // 1 / s: [f | m][CoutPad]
-    if (tid < 192) {                                           // the group is fixed per workgroup: its epilogue parameters go to LDS once
-        constexpr float L2E = 1.44269504088896341f;
-        const int arr = tid >> 5, c = g * 32 + (tid & 31);
-        const float v = arr < 4 ? a.params[arr * a.CoutPad + c] : wsc[(arr - 4) * a.CoutPad + c];
-        epar[arr][tid & 31] = (arr == 1 || arr == 5) ? v * -L2E : v;
-    }
+    epar_load(epar, a, WG::row_scales(a, n), g, tid);                          // the group is fixed per workgroup: its epilogue parameters go to LDS once
 
     // ---- prologue: patch(0) -> registers -> V(0); patch(1) -> registers; the first weight fragments and B operands
     set_patch();
@@ -2477,14 +2489,11 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
             for (int sp = 0; sp < 9; ++sp)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    // the (block, tap) pairs that read row pair sp: odd sp (nb, 1); even sp (nb - 1, 2) and then (nb, 0)
-                    const int nb = (sp & 1) ? sp >> 1 : (sp >> 1) - 1 + q, ky = (sp & 1) ? 1 : q ? 0 : 2;
-                    if (((sp & 1) && q) || nb < 0 || nb > 3) continue;
+                    const int nb = WG::pair_nb(sp, q), ky = WG::pair_ky(sp, q);    // the (block, tap) pairs that read row pair sp
+                    if (!WG::pair_live(sp, q)) continue;
 #pragma unroll
                     for (int pc = 0; pc < 3; ++pc) {
-                        // MFMA slot: row pairs 2, 4, 6 carry two (block, tap) pairs, the others one: first slots 0 3 6 12 15 21 24 30 33
-                        const int mb = 3 * sp + 3 * ((sp > 0 ? sp - 1 : 0) / 2);
-                        const int ms = mb + ((!(sp & 1) && q && sp > 0) ? 3 : 0) + pc, m = fq * 36 + ms, idx = fq * 9 + sp;
+                        const int mb = WG::slot_first(sp), ms = WG::slot(sp, q, pc), m = fq * 36 + ms, idx = fq * 9 + sp;
                         if (ms == mb) {
                             // B operands two row pairs ahead.  Before the first one of the next chunk: V(chunk + 1) is complete in
                             // every wave (last store at slot 138) and every wave has fetched its last B operand of this chunk
@@ -2527,9 +2536,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
         const int c0 = g * 32 + wv * 8 + 4 * cq;
         const int oy = by * 8 + 4 * hf + (t16 >> 3), ox = bx * 32 + 4 * (t16 & 7);           // this lane finishes rows oy, oy + 2
         const int cl = wv * 8 + 4 * cq;
-        const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
-        const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
-        const f32x4 isf = *reinterpret_cast<const f32x4 *>(&epar[4][cl]), ism = *reinterpret_cast<const f32x4 *>(&epar[5][cl]);
+        const auto [bf, bml, sc, sh, isf, ism] = epar_read(epar, cl);
         constexpr float LOG2E = 1.44269504088896341f;
         unsigned rvoff[2][4], ovoff[2][4];
 #pragma unroll
@@ -2551,31 +2558,14 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
             }
         f32x4 Y[4][4];                                                 // [block][pixel of the tile]
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            const f32x4 s1 = acc[nb][1] + acc[nb][2], d1 = pk_sub4(acc[nb][1], acc[nb][2]);
-            const f32x4 s2 = acc[nb][3] + acc[nb][4], dd2 = pk_sub4(acc[nb][3], acc[nb][4]);
-            Y[nb][0] = acc[nb][0] + s1 + s2;
-            Y[nb][1] = d1 + 2.0f * dd2;
-            Y[nb][2] = s1 + 4.0f * s2;
-            Y[nb][3] = d1 + 8.0f * dd2 + acc[nb][5];
-        }
+        for (int nb = 0; nb < 4; ++nb) at6(acc[nb], Y[nb]);
         // lanes 0..31 hold conv_f, lanes 32..63 conv_m of the same channels: after the swap the lower half finishes blocks 0, 1
         // and the upper half blocks 2, 3, both with f and m of a pixel in one lane
         f32x4 Yf[2][4], Ym[2][4];
 #pragma unroll
         for (int py = 0; py < 2; ++py)
 #pragma unroll
-            for (int px = 0; px < 4; ++px) {
-                u32x4 u0 = __builtin_bit_cast(u32x4, Y[py][px]), u1 = __builtin_bit_cast(u32x4, Y[py + 2][px]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                    u0[k] = sw[0];
-                    u1[k] = sw[1];
-                }
-                Yf[py][px] = __builtin_bit_cast(f32x4, u0);
-                Ym[py][px] = __builtin_bit_cast(f32x4, u1);
-            }
+            for (int px = 0; px < 4; ++px) fm_swap(Y[py][px], Y[py + 2][px], Yf[py][px], Ym[py][px]);
 #pragma unroll
         for (int py = 0; py < 2; ++py)
 #pragma unroll
@@ -2600,7 +2590,7 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
                 const f32x4 v = (f * sg_) * sc + sh + rv[py][px];
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[py][px], 0, 0);
             }
-        step_tile(by, bx);
+        step_tile(a, by, bx);
         __builtin_amdgcn_s_setprio(0);
     }
 }
@@ -2613,7 +2603,8 @@ __global__ __launch_bounds__(256, 1) void gated_conv_f4x1h_kernel(const ConvKArg
 // wave its SIMD has.  This kernel halves both (one V image, at most 256 registers) and leaves the overlap to the hardware: while one
 // workgroup transforms, waits for its patch or gates a unit, its partner on the same SIMDs issues MFMAs.
 //
-// Same unit, operand (wp_f4x1), walk, group map, epar, transform, split and epilogue arithmetic as the kernel above, and per
+// Same unit, operand (wp_f4x1), walk, group map, epar, transform, split and epilogue arithmetic as the kernel above — the shared blocks
+// (bt6, split_hl, at6, epar_load / epar_read, fm_swap) and F4x1Geom's addresses and slot arithmetic are called by both — and per
 // accumulator the same order of MFMAs (chunk, tap ky 0..2 as the row pairs arrive, piece pair 0..2): the output equals that kernel's
 // bit for bit (tests/test_gpu_conv_f4x1_pair.py).  What differs is the schedule of a chunk:
 //     barrier -> transform (registers -> V) -> barrier -> 216 MFMAs -> [unit epilogue ->] patch loads of the next chunk
@@ -2638,14 +2629,6 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
 
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit (8 x 32 pixel block)
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // patch cursor: one chunk ahead
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
 
     // ---- transform role (the kernel above's): thread = (segment sg, channel pair cp) of patch rows 2 i + (w >> 1), i = 0 .. 4
     const int cp = lane & 15, sg = (wv & 1) * 4 + (lane >> 4);
@@ -2668,14 +2651,7 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
         for (int c = 0; c < 6; ++c) xoff[c] = (unsigned)(x0 + c) < (unsigned)a.inW ? (unsigned)((x0 + c) * s.C + 2 * cp) * 4u : OOR;
     };
     auto advance = [&]() {
-        if (++pchunk == n) {
-            pchunk = 0;
-            if (pu + G < a.n_units) {
-                pu += G;
-                step_tile(pby, pbx);
-            }
-            set_patch();
-        }
+        if (cursor_advance(a, n, G, pchunk, pu, pby, pbx)) set_patch();
     };
     f32x2 d2[5][6];                                            // the five row segments of the chunk under transform: (channel 2 cp, 2 cp + 1)
     // a row outside the image reads through a descriptor of no records (zeros): the rows are wave-uniform, so the choice costs scalar
@@ -2688,41 +2664,24 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
             for (int c = 0; c < 6; ++c)
                 d2[i][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rowok[i] ? rsrc : rsrc_none, xoff[c], rowoff[i] + pchunk * 128, 0));
     };
-    auto bt6 = [](f32x2 &x0, f32x2 &x1, f32x2 &x2, f32x2 &x3, f32x2 &x4, f32x2 &x5) {
-        const f32x2 p = pk_add(x3, x4), q = pk_add(x1, x2), r = pk_sub(x4, x3), u = pk_sub(x1, x2), f = pk_sub(x3, x1), h = pk_sub(x4, x2);
-        const f32x2 y0 = __builtin_elementwise_fma(x2, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x0, f32x2{4.0f, 4.0f}, x4));
-        const f32x2 y5 = __builtin_elementwise_fma(x3, f32x2{-5.0f, -5.0f}, __builtin_elementwise_fma(x1, f32x2{4.0f, 4.0f}, x5));
-        x0 = y0;
-        x1 = __builtin_elementwise_fma(q, f32x2{-4.0f, -4.0f}, p);
-        x2 = __builtin_elementwise_fma(u, f32x2{4.0f, 4.0f}, r);
-        x3 = __builtin_elementwise_fma(f, f32x2{2.0f, 2.0f}, h);
-        x4 = __builtin_elementwise_fma(f, f32x2{-2.0f, -2.0f}, h);
-        x5 = y5;
-    };
-    const int vwoff = (wv >> 1) * WG::VROW + sg * 16 + (((cp >> 2) ^ ((-wv) & 3)) << 2) + (cp & 3);
+    const int vwoff = WG::v_store_off(wv, sg, cp);
     auto split_store = [&](const f32x2 x, int i, int fq) {
         unsigned hi, lo;
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x.x), "v"(x.y));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x.x));                    // x - f32(hi), exact
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x.y));
-        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
+        split_hl(x.x, x.y, hi, lo);
         lds[vwoff + 2 * i * WG::VROW + fq * WG::VFREQ] = hi;
         lds[vwoff + 2 * i * WG::VROW + fq * WG::VFREQ + 128] = lo;
     };
 
     // ---- A operand (weights): fragment (chunk, ky, fq), consumed in the order (fq, ky); ring of two frequencies
-    const char *const wbase = reinterpret_cast<const char *>(a.wp_f4x1) + ((size_t)(g * 4 + wv) * n) * (18 * 2048);
-    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(wbase), 0, (unsigned)n * (18 * 2048), 0x00020000);
+    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(WG::w_base(a, g, wv, n)), 0, (unsigned)n * WG::W_BYTES, 0x00020000);
     const unsigned wvoff = lane * 16;
     constexpr int RW = 6;
     u32x4 Wh[RW], Wl[RW];
     f16x8 Ws;                                                  // 2^-11 Uh of the (block, tap) pair that comes next
     auto wload = [&](int chunk, int fq, int ky) {
         const int slot = (fq & 1) * 3 + ky;
-        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048, 0);
-        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, ((chunk * 3 + ky) * 6 + fq) * 2048 + 1024, 0);
+        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, WG::w_frag(chunk, fq, ky), 0);
+        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, WG::w_frag(chunk, fq, ky) + 1024, 0);
     };
     auto wscale = [&](int fq, int ky) {
         const _Float16 k = (_Float16)0x1p-11f;
@@ -2730,8 +2689,7 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
     };
     // ---- B operand: row pair s (rows s, s + 1) of frequency fq; ring of three, fetched two pairs ahead
     const int t16 = lane & 15, kl = lane >> 4;
-    const int vrd_e = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-(t16 >> 2)) & 3)) << 2);
-    const int vrd_o = (t16 >> 3) * WG::VROW + (t16 & 7) * 16 + ((kl ^ ((-((t16 >> 2) ^ 2)) & 3)) << 2);
+    const int vrd_e = WG::v_read_off(t16, kl, 0), vrd_o = WG::v_read_off(t16, kl, 1);
     constexpr int RB = 3;
     u32x4 Bh[RB], Bl[RB];
     auto bload = [&](int idx) {                                // idx = fq * 9 + s
@@ -2745,13 +2703,7 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
     const auto out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)(a.outH * a.outW * a.out_cstride) * 4u, 0x00020000);
     const auto res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.residual ? a.residual : a.out), 0,
                                                             (unsigned)(a.outH * a.outW * a.Cout) * 4u, 0x00020000);
-    const float *const wsc = reinterpret_cast<const float *>(a.wp_f4x1) + (size_t)n * 1152 * a.CoutPad;      // 1 / s: [f | m][CoutPad]
-    if (tid < 192) {                                           // the group is fixed per workgroup: its epilogue parameters go to LDS once
-        constexpr float L2E = 1.44269504088896341f;
-        const int arr = tid >> 5, c = g * 32 + (tid & 31);
-        const float v = arr < 4 ? a.params[arr * a.CoutPad + c] : wsc[(arr - 4) * a.CoutPad + c];
-        epar[arr][tid & 31] = (arr == 1 || arr == 5) ? v * -L2E : v;
-    }
+    epar_load(epar, a, WG::row_scales(a, n), g, tid);                          // the group is fixed per workgroup: its epilogue parameters go to LDS once
 
     // ---- prologue: patch(0) -> registers
     set_patch();
@@ -2780,14 +2732,11 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
             for (int sp = 0; sp < 9; ++sp)
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    // the (block, tap) pairs that read row pair sp: odd sp (nb, 1); even sp (nb - 1, 2) and then (nb, 0)
-                    const int nb = (sp & 1) ? sp >> 1 : (sp >> 1) - 1 + q, ky = (sp & 1) ? 1 : q ? 0 : 2;
-                    if (((sp & 1) && q) || nb < 0 || nb > 3) continue;
+                    const int nb = WG::pair_nb(sp, q), ky = WG::pair_ky(sp, q);    // the (block, tap) pairs that read row pair sp
+                    if (!WG::pair_live(sp, q)) continue;
 #pragma unroll
                     for (int pc = 0; pc < 3; ++pc) {
-                        // MFMA slot: row pairs 2, 4, 6 carry two (block, tap) pairs, the others one: first slots 0 3 6 12 15 21 24 30 33
-                        const int mb = 3 * sp + 3 * ((sp > 0 ? sp - 1 : 0) / 2);
-                        const int ms = mb + ((!(sp & 1) && q && sp > 0) ? 3 : 0) + pc, idx = fq * 9 + sp;
+                        const int mb = WG::slot_first(sp), ms = WG::slot(sp, q, pc), idx = fq * 9 + sp;
                         if (ms == mb && idx + 2 < 54) bload(idx + 2);                    // B operands two row pairs ahead
                         const int ws = (fq & 1) * 3 + ky;
                         const f16x8 av = pc == 0 ? Ws : __builtin_bit_cast(f16x8, pc == 1 ? Wl[ws] : Wh[ws]);
@@ -2821,7 +2770,7 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
             }
         }
 
-        // ================= unit epilogue: the kernel above's, expression for expression =================
+        // ================= unit epilogue: the kernel above's, one block of accumulators at a time =================
         // the lane number once more, opaque to the compiler: it would otherwise move everything below that depends on the lane alone in
         // front of the unit loop and hold it in vector registers across the stages, which have none to spare
         int ln;
@@ -2830,9 +2779,7 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
         const int c0 = g * 32 + wv * 8 + 4 * cq;
         const int oy = by * 8 + 4 * hf + (e16 >> 3), ox = bx * 32 + 4 * (e16 & 7);           // this lane finishes rows oy, oy + 2
         const int cl = wv * 8 + 4 * cq;
-        const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
-        const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
-        const f32x4 isf = *reinterpret_cast<const f32x4 *>(&epar[4][cl]), ism = *reinterpret_cast<const f32x4 *>(&epar[5][cl]);
+        const auto [bf, bml, sc, sh, isf, ism] = epar_read(epar, cl);
         constexpr float LOG2E = 1.44269504088896341f;
         asm volatile("s_nop 15\n\ts_nop 3");                            // the last MFMA's result, read below through an asm the hazard checker does not see
 #pragma unroll
@@ -2861,27 +2808,17 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
                 for (int fq = 0; fq < 6; ++fq)
 #pragma unroll
                     for (int k = 0; k < 4; ++k) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(m[fq][k]) : "a"(acc[py + 2 * h][fq][k]));
-                const f32x4 s1 = m[1] + m[2], d1 = pk_sub4(m[1], m[2]);
-                const f32x4 s2 = m[3] + m[4], dd2 = pk_sub4(m[3], m[4]);
-                Y[h][0] = m[0] + s1 + s2;
-                Y[h][1] = d1 + 2.0f * dd2;
-                Y[h][2] = s1 + 4.0f * s2;
-                Y[h][3] = d1 + 8.0f * dd2 + m[5];
+                at6(m, Y[h]);
                 __builtin_amdgcn_sched_barrier(0);
             }
             // lanes 0..31 hold conv_f, lanes 32..63 conv_m of the same channels: after the swap the lower half finishes blocks 0, 1
             // and the upper half blocks 2, 3, both with f and m of a pixel in one lane
 #pragma unroll
             for (int px = 0; px < 4; ++px) {
-                u32x4 u0 = __builtin_bit_cast(u32x4, Y[0][px]), u1 = __builtin_bit_cast(u32x4, Y[1][px]);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                    u0[k] = sw[0];
-                    u1[k] = sw[1];
-                }
-                f32x4 f = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u0), isf, bf);
-                const f32x4 mm = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u1), ism, bml);
+                f32x4 yf, ym;
+                fm_swap(Y[0][px], Y[1][px], yf, ym);
+                f32x4 f = __builtin_elementwise_fma(yf, isf, bf);
+                const f32x4 mm = __builtin_elementwise_fma(ym, ism, bml);
                 if (a.elu) {
                     const f32x4 fe = f * LOG2E;
                     f32x4 e;
@@ -2902,7 +2839,7 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        step_tile(by, bx);
+        step_tile(a, by, bx);
         advance();                                                     // the next unit's first patch (the last unit: its own again)
         gload_patch();
     }
@@ -2954,14 +2891,6 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
 
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // staging cursor
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
 
     // ---- staging: thread = float4 e = tid + 512 i of the patch chunk (pixel e >> 3, channel quad e & 7)
     int soff[DG::NI];                                          // LDS dword offset of the hi piece (+ buffer); lo = the same ^ 16 dwords
@@ -2986,14 +2915,7 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
         }
     };
     auto advance = [&]() {
-        if (++pchunk == n) {
-            pchunk = 0;
-            if (pu + G < a.n_units) {
-                pu += G;
-                step_tile(pby, pbx);
-            }
-            set_patch();
-        }
+        if (cursor_advance(a, n, G, pchunk, pu, pby, pbx)) set_patch();
     };
     float4 st[DG::NI], stm[MUL ? DG::NI : 1];
     auto gload = [&]() {
@@ -3003,14 +2925,6 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
             if constexpr (MUL) stm[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_mul, aoff[i], pchunk * 128, 0));
         }
     };
-    auto split2 = [](float x, float y, unsigned &hi, unsigned &lo) {
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x), "v"(y));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x));                    // x - f32(hi), exact
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(y));
-        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
-    };
     auto lwrite = [&](int xb) {                                 // registers -> f16 pieces -> X[xb]
 #pragma unroll
         for (int i = 0; i < DG::NI; ++i) {
@@ -3018,8 +2932,8 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
             float4 v = st[i];
             if constexpr (MUL) v = make_float4(v.x * stm[i].x, v.y * stm[i].y, v.z * stm[i].z, v.w * stm[i].w);
             unsigned h0, l0, h1, l1;
-            split2(v.x, v.y, h0, l0);
-            split2(v.z, v.w, h1, l1);
+            split_hl(v.x, v.y, h0, l0);
+            split_hl(v.z, v.w, h1, l1);
             typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
             *reinterpret_cast<u32x2 *>(__builtin_assume_aligned(lds + xb + soff[i], 8)) = u32x2{h0, h1};
             *reinterpret_cast<u32x2 *>(__builtin_assume_aligned(lds + xb + (soff[i] ^ 16), 8)) = u32x2{l0, l1};
@@ -3055,12 +2969,7 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
 
     // ---- prologue: patch(0) -> X[0]; patch(1) on its way; the first two taps' weights; the epilogue's parameters into LDS (a load
     // from global memory inside a stage would queue behind, and wait for, the weight stream)
-    if (tid < 192) {
-        constexpr float L2E = 1.44269504088896341f;
-        const int arr = tid >> 5, c = g * 32 + (tid & 31);
-        const float v = arr < 4 ? a.params[arr * a.CoutPad + c] : wsc[(arr - 4) * a.CoutPad + c];
-        epar[arr][tid & 31] = (arr == 1 || arr == 5) ? v * -L2E : v;
-    }
+    epar_load(epar, a, wsc, g, tid);
     set_patch();
     gload();
     wload(0, 0, 0);
@@ -3092,8 +3001,8 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
         float4 v = st[i];
         if constexpr (MUL) v = make_float4(v.x * stm[i].x, v.y * stm[i].y, v.z * stm[i].z, v.w * stm[i].w);
         unsigned h0, l0, h1, l1;
-        split2(v.x, v.y, h0, l0);
-        split2(v.z, v.w, h1, l1);
+        split_hl(v.x, v.y, h0, l0);
+        split_hl(v.z, v.w, h1, l1);
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         *reinterpret_cast<u32x2 *>(__builtin_assume_aligned(lds + xb + soff[i], 8)) = u32x2{h0, h1};
         *reinterpret_cast<u32x2 *>(__builtin_assume_aligned(lds + xb + (soff[i] ^ 16), 8)) = u32x2{l0, l1};
@@ -3125,20 +3034,13 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const int rb = o >> 1, rs = o & 1, cl = rh * 16 + rb * 8 + 4 * cq;
-            const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
-            const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
-            const f32x4 isf = *reinterpret_cast<const f32x4 *>(&epar[4][cl]), ism = *reinterpret_cast<const f32x4 *>(&epar[5][cl]);
+            const auto [bf, bml, sc, sh, isf, ism] = epar_read(epar, cl);
             // lanes 0..31 hold conv_f, lanes 32..63 conv_m: after the exchange the lower half-wave owns pixel block (rs, 0), the upper
             // half block (rs, 1), f in one register and m in the other
-            u32x4 u0 = __builtin_bit_cast(u32x4, acc[rb][2 * rs]), u1 = __builtin_bit_cast(u32x4, acc[rb][2 * rs + 1]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                u0[k] = sw[0];
-                u1[k] = sw[1];
-            }
-            f32x4 f = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u0), isf, bf);
-            const f32x4 mm = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u1), ism, bml);
+            f32x4 yf, ym;
+            fm_swap(acc[rb][2 * rs], acc[rb][2 * rs + 1], yf, ym);
+            f32x4 f = __builtin_elementwise_fma(yf, isf, bf);
+            const f32x4 mm = __builtin_elementwise_fma(ym, ism, bml);
             if (a.elu) {
                 const f32x4 fe = f * LOG2E;
                 f32x4 e;
@@ -3203,7 +3105,7 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_kernel(const ConvKArgs 
         for (int i = 0; i < 8; ++i) acc[i >> 2][i & 3] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int chunk = 0; chunk < n; ++chunk) stage(chunk);
         epilogue();
-        step_tile(by, bx);
+        step_tile(a, by, bx);
     }
 }
 
@@ -3243,14 +3145,10 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
 
     int by = (blockIdx.x / groups) / a.tiles_x, bx = (blockIdx.x / groups) % a.tiles_x;      // running unit
     int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // staging cursor
-    auto step_tile = [&](int &ty_, int &tx_) {
-        ty_ += a.wino_dby;
-        tx_ += a.wino_dbx;
-        if (tx_ >= a.tiles_x) {
-            tx_ -= a.tiles_x;
-            ++ty_;
-        }
-    };
+
+    // (step_unit and split2 forward to the shared blocks through a lambda: called directly, the KS = 4 instance orders the register
+    //  copies at its loop edges differently — tools/isa_diff.py)
+    auto step_unit = [&](int &ty_, int &tx_) { step_tile(a, ty_, tx_); };
 
     // ---- staging: thread = float4 e = tid + 512 i of the patch chunk (pixel e >> 3, channel quad e & 7)
     int soff[DG::NI];                                          // LDS dword offset of the hi piece (+ buffer); lo = the same ^ 16 dwords
@@ -3280,7 +3178,7 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
             pchunk = 0;
             if (pu + G < a.n_units) {
                 pu += G;
-                step_tile(pby, pbx);
+                step_unit(pby, pbx);
             }
             set_patch();
         }
@@ -3293,14 +3191,7 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
             if constexpr (MUL) stm[i] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsrc_mul, aoff[i], pchunk * 128, 0));
         }
     };
-    auto split2 = [](float x, float y, unsigned &hi, unsigned &lo) {
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x), "v"(y));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x));                    // x - f32(hi), exact
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(y));
-        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
-    };
+    auto split2 = [](float x, float y, unsigned &hi, unsigned &lo) { split_hl(x, y, hi, lo); };
     auto lwrite = [&](int xb) {                                 // registers -> f16 pieces -> X[xb]
 #pragma unroll
         for (int i = 0; i < DG::NI; ++i) {
@@ -3412,20 +3303,13 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
 #pragma unroll
         for (int o = 0; o < 4; ++o) {
             const int rb = o >> 1, rs = o & 1, cl = rq * 16 + rb * 8 + 4 * cq;
-            const f32x4 bf = *reinterpret_cast<const f32x4 *>(&epar[0][cl]), bml = *reinterpret_cast<const f32x4 *>(&epar[1][cl]);
-            const f32x4 sc = *reinterpret_cast<const f32x4 *>(&epar[2][cl]), sh = *reinterpret_cast<const f32x4 *>(&epar[3][cl]);
-            const f32x4 isf = *reinterpret_cast<const f32x4 *>(&epar[4][cl]), ism = *reinterpret_cast<const f32x4 *>(&epar[5][cl]);
+            const auto [bf, bml, sc, sh, isf, ism] = epar_read(epar, cl);
             // lanes 0..31 hold conv_f, lanes 32..63 conv_m: after the exchange the lower half-wave owns image row 2 rs of the wave's four, the
             // upper half row 2 rs + 1, f in one register and m in the other
-            u32x4 u0 = __builtin_bit_cast(u32x4, acc[rb][2 * rs]), u1 = __builtin_bit_cast(u32x4, acc[rb][2 * rs + 1]);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const auto sw = __builtin_amdgcn_permlane32_swap(u0[k], u1[k], false, false);
-                u0[k] = sw[0];
-                u1[k] = sw[1];
-            }
-            f32x4 f = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u0), isf, bf);
-            const f32x4 mm = __builtin_elementwise_fma(__builtin_bit_cast(f32x4, u1), ism, bml);
+            f32x4 yf, ym;
+            fm_swap(acc[rb][2 * rs], acc[rb][2 * rs + 1], yf, ym);
+            f32x4 f = __builtin_elementwise_fma(yf, isf, bf);
+            const f32x4 mm = __builtin_elementwise_fma(ym, ism, bml);
             if (a.elu) {
                 const f32x4 fe = f * LOG2E;
                 f32x4 e;
@@ -3501,14 +3385,14 @@ __global__ __launch_bounds__(512, 1) void gated_conv_d3h_s2_kernel(const ConvKAr
     for (int u = blockIdx.x; u < a.n_units; u += G) {
         if (!live) {
             for (int chunk = 0; chunk < n; ++chunk) stage_idle();
-            step_tile(by, bx);
+            step_unit(by, bx);
             continue;
         }
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i >> 2][i & 3] = f32x4{0.f, 0.f, 0.f, 0.f};
         for (int chunk = 0; chunk < n; ++chunk) stage(chunk);
         epilogue();
-        step_tile(by, bx);
+        step_unit(by, bx);
     }
 }
 
@@ -4025,14 +3909,6 @@ __global__ __launch_bounds__(256, 2) void gated_conv_pxh_kernel(const ConvKArgs 
 #pragma unroll
     for (int e = 0; e < 4; ++e) load_step(e);
 
-    auto split2 = [](float x, float y, unsigned &hi, unsigned &lo) {
-        float r0, r1;
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(hi) : "v"(x), "v"(y));
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x));                    // x - f32(hi), exact
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(y));
-        const f32x2 rs = f32x2{r0, r1} * f32x2{2048.0f, 2048.0f};
-        asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(rs.x), "v"(rs.y));
-    };
 
     const bool quad_res = a.residual != nullptr;
     for (int u = w0; u < a.n_units; u += wslots) {
@@ -4060,10 +3936,10 @@ __global__ __launch_bounds__(256, 2) void gated_conv_pxh_kernel(const ConvKArgs 
                     for (int pt = 0; pt < PT; ++pt) {
                         const float4 v0 = ring[e][pt][0], v1 = ring[e][pt][1];
                         unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-                        split2(v0.x, v0.y, h0, l0);
-                        split2(v0.z, v0.w, h1, l1);
-                        split2(v1.x, v1.y, h2, l2);
-                        split2(v1.z, v1.w, h3, l3);
+                        split_hl(v0.x, v0.y, h0, l0);
+                        split_hl(v0.z, v0.w, h1, l1);
+                        split_hl(v1.x, v1.y, h2, l2);
+                        split_hl(v1.z, v1.w, h3, l3);
                         bh[pt] = u32x4{h0, h1, h2, h3};
                         bl[pt] = u32x4{l0, l1, l2, l3};
                     }
@@ -4355,8 +4231,6 @@ int pick_config(int ks, int s, int kc, int groups, int outH, int outW)
     return first_fit(ks, s, kc, groups);
 }
 
-int pad32(int c) { return (c + 31) / 32 * 32; }
-
 // ------------------------------------------------------------------------------------------
 // bilinear x4 upsample, align_corners=False (nn.Upsample, unet.py:200)
 // ------------------------------------------------------------------------------------------
@@ -4403,470 +4277,7 @@ extern "C" const char *read_conv_config_name(int config)
     return (config >= 0 && config < N_CONFIGS) ? g_configs[config].name : "";
 }
 
-extern "C" size_t read_conv_packed_floats(int Cin, int Cout, int ksize)
-{
-    if (Cin < 8 || Cin % 8 || Cout < 1 || (ksize != 1 && ksize != 3 && ksize != 4)) return 0;
-    return (size_t)Cin * ksize * ksize * 2 * pad32(Cout);
-}
-extern "C" size_t read_conv_param_floats(int Cout) { return Cout < 1 ? 0 : (size_t)4 * pad32(Cout); }
-
-extern "C" int read_conv_pack_weights_host(int Cin, int Cout, int ksize, int kc, const float *wf, const float *wm,
-                                           float *wpacked_host)
-{
-    READ_CHECK_ARG(wf && wm && wpacked_host, "read_conv_pack_weights_host: null pointer");
-    READ_CHECK_ARG(ksize == 1 || ksize == 3 || ksize == 4, "read_conv_pack_weights_host: ksize must be 1, 3 or 4");
-    // (for 1x1 layers the fragment order does not depend on kc: k8 steps are simply consecutive, so 16- and 32-channel
-    //  chunk kernels read the same blob)
-    READ_CHECK_ARG((kc == 8 || kc == 16 || (kc == 32 && ksize == 1)) && Cin >= kc && Cin % kc == 0,
-                   "read_conv_pack_weights_host: Cin=%d is not a multiple of kc=%d", Cin, kc);
-    READ_CHECK_ARG(Cout >= 1, "read_conv_pack_weights_host: Cout < 1");
-    const int CoutPad = pad32(Cout), NT = CoutPad / 16, KK = kc / 8, taps = ksize * ksize;
-    const int nchunks = Cin / kc;
-    size_t o = 0;
-    for (int chunk = 0; chunk < nchunks; ++chunk)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int kk = 0; kk < KK; ++kk)
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float *w = (nt & 1) ? wm : wf;
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j, ++o) {
-                            const int cout = (nt >> 1) * 32 + (lane & 31);
-                            const int cin = chunk * kc + kk * 8 + 4 * (lane >> 5) + j;
-                            wpacked_host[o] = cout < Cout ? w[((size_t)cout * Cin + cin) * taps + tap] : 0.0f;
-                        }
-                }
-    return READ_OK;
-}
-
-// The inverse of read_conv_pack_weights_host: the layer's weights (Cout, Cin, k, k), exact, out of its direct fragment order.
-extern "C" int read_conv_unpack_weights_host(int Cin, int Cout, int ksize, int kc, const float *wpacked_host, float *wf, float *wm)
-{
-    READ_CHECK_ARG(wf && wm && wpacked_host, "read_conv_unpack_weights_host: null pointer");
-    READ_CHECK_ARG((ksize == 1 || ksize == 3 || ksize == 4) && (kc == 8 || kc == 16 || (kc == 32 && ksize == 1)) && Cin >= kc && Cin % kc == 0 && Cout >= 1,
-                   "read_conv_unpack_weights_host: bad shape (Cin=%d kc=%d ksize=%d)", Cin, kc, ksize);
-    const int CoutPad = pad32(Cout), NT = CoutPad / 16, KK = kc / 8, taps = ksize * ksize;
-    const int nchunks = Cin / kc;
-    size_t o = 0;
-    for (int chunk = 0; chunk < nchunks; ++chunk)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int kk = 0; kk < KK; ++kk)
-                for (int nt = 0; nt < NT; ++nt) {
-                    float *w = (nt & 1) ? wm : wf;
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int j = 0; j < 4; ++j, ++o) {
-                            const int cout = (nt >> 1) * 32 + (lane & 31);
-                            const int cin = chunk * kc + kk * 8 + 4 * (lane >> 5) + j;
-                            if (cout < Cout) w[((size_t)cout * Cin + cin) * taps + tap] = wpacked_host[o];
-                        }
-                }
-    return READ_OK;
-}
-
-extern "C" size_t read_conv_wino_floats(int Cin, int Cout)
-{
-    if (Cin < 16 || Cin % 16 || Cout < 1) return 0;
-    return (size_t)Cin * 16 * 2 * pad32(Cout);
-}
-
-// U = G g G^T per (cout, cin) pair, packed [group][k8 step][row i][j][f|m][lane][4] (tests/wino_ref.py).
-extern "C" int read_conv_pack_wino_host(int Cin, int Cout, const float *wf, const float *wm, float *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_wino_host: null pointer");
-    READ_CHECK_ARG(Cin >= 16 && Cin % 16 == 0 && Cout >= 1, "read_conv_pack_wino_host: needs Cin %% 16 == 0 (got %d)", Cin);
-    static const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-    const int CoutPad = pad32(Cout), groups = CoutPad / 32, nsteps = Cin / 8;
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g)
-        for (int s = 0; s < nsteps; ++s)
-            for (int i = 0; i < 4; ++i)
-                for (int j = 0; j < 4; ++j)
-                    for (int fm = 0; fm < 2; ++fm) {
-                        const float *w = fm ? wm : wf;
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 4; ++e, ++o) {
-                                const int co = g * 32 + (lane & 31), ci = 8 * s + 4 * (lane >> 5) + e;
-                                float u = 0.0f;
-                                if (co < Cout) {
-                                    const float *k = w + ((size_t)co * Cin + ci) * 9;
-                                    for (int a = 0; a < 3; ++a)
-                                        for (int b = 0; b < 3; ++b) u += G[i][a] * k[a * 3 + b] * G[j][b];
-                                }
-                                out[o] = i == 2 ? -u : u;      // the kernel builds row 2 of B^T d negated
-                            }
-                    }
-    return READ_OK;
-}
-
-// The wave-autonomous Winograd kernel's order (tests/wino16_ref.py): [group][wave 4][chunk of 16 cin][a][j][lane][e]; lane
-// (i = lane & 15, kl = lane >> 4) holds U_{i < 8 ? f : m}[a][j][cin = 16 chunk + 4 kl + e][cout = 32 group + 8 wave + (i & 7)].
-extern "C" int read_conv_pack_w16_host(int Cin, int Cout, const float *wf, const float *wm, float *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_w16_host: null pointer");
-    READ_CHECK_ARG(Cin >= 16 && Cin % 16 == 0 && Cout >= 1, "read_conv_pack_w16_host: needs Cin %% 16 == 0 (got %d)", Cin);
-    static const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-    const int CoutPad = pad32(Cout), groups = CoutPad / 32, nchunks = Cin / 16;
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g)
-        for (int w = 0; w < 4; ++w)
-            for (int c = 0; c < nchunks; ++c)
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 4; ++e, ++o) {
-                                const int slot = lane & 15, co = g * 32 + w * 8 + (slot & 7), ci = 16 * c + 4 * (lane >> 4) + e;
-                                float u = 0.0f;
-                                if (co < Cout) {
-                                    const float *k = ((slot >> 3) ? wm : wf) + ((size_t)co * Cin + ci) * 9;
-                                    for (int a = 0; a < 3; ++a)
-                                        for (int b = 0; b < 3; ++b) u += G[i][a] * k[a * 3 + b] * G[j][b];
-                                }
-                                out[o] = u;
-                            }
-    return READ_OK;
-}
-
-extern "C" size_t read_conv_w4_floats(int Cin, int Cout)
-{
-    if (Cin < 16 || Cin % 16 || Cout < 1) return 0;
-    return (size_t)Cin * 36 * 2 * pad32(Cout);
-}
-
-// F(4x4,3x3): U = G g G^T (6 x 6) per (cout, cin) pair, G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1],
-// evaluated in double and rounded once; order [group][wave 4][chunk of 16 cin][frequency 6 xi + nu][lane][e] with lane
-// (i = lane & 15, kl = lane >> 4) = U_{i < 8 ? f : m}[xi][nu][cin = 16 chunk + 4 kl + e][cout = 32 group + 8 wave + (i & 7)]   (tests/wino4_ref.py)
-extern "C" int read_conv_pack_w4_host(int Cin, int Cout, const float *wf, const float *wm, float *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_w4_host: null pointer");
-    READ_CHECK_ARG(Cin >= 16 && Cin % 16 == 0 && Cout >= 1, "read_conv_pack_w4_host: needs Cin %% 16 == 0 (got %d)", Cin);
-    static const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
-    const int CoutPad = pad32(Cout), groups = CoutPad / 32, nchunks = Cin / 16;
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g)
-        for (int w = 0; w < 4; ++w)
-            for (int c = 0; c < nchunks; ++c)
-                for (int fq = 0; fq < 36; ++fq)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int e = 0; e < 4; ++e, ++o) {
-                            const int slot = lane & 15, co = g * 32 + w * 8 + (slot & 7), ci = 16 * c + 4 * (lane >> 4) + e;
-                            double u = 0.0;
-                            if (co < Cout) {
-                                const float *k = ((slot >> 3) ? wm : wf) + ((size_t)co * Cin + ci) * 9;
-                                for (int a = 0; a < 3; ++a)
-                                    for (int b = 0; b < 3; ++b) u += G[fq / 6][a] * (double)k[a * 3 + b] * G[fq % 6][b];
-                            }
-                            out[o] = (float)u;
-                        }
-    return READ_OK;
-}
-
-// F(4x4,3x3) operand of the split-operand kernel (gated_conv_wino4h_kernel): U = G g G^T in double, scaled per output ROW by the
-// power of two s that puts max |U s| of the row in [2^14, 2^15), cut into Uh = f16(U s) and Ul = f16(U s - Uh) (round to nearest
-// even, both); order [group][wave 4][chunk of 32 cin][frequency 36][piece Uh | Ul][lane][8 halfs], lane (i = lane & 15, kq = lane >> 4)
-// = rows as in read_conv_pack_w4_host, cin = 32 chunk + 8 kq + e; then 2 * CoutPad floats 1 / s ([conv_f rows | conv_m rows]).
-// Sized in floats like every block of a packed blob: Cin * 36 * 2 * CoutPad (the halfs) + 2 * CoutPad.   (tests/wino4h_ref.py)
-extern "C" size_t read_conv_w4h_floats(int Cin, int Cout)
-{
-    if (Cin < 32 || Cin % 32 || Cout < 1) return 0;
-    return (size_t)Cin * 36 * 2 * pad32(Cout) + 2 * (size_t)pad32(Cout);
-}
-
-namespace {
-// double -> IEEE binary16, round to nearest even, subnormals kept (the values are far inside the range: |x| < 2^15)
-unsigned short f16_bits_rtn(double x)
-{
-    const unsigned short sign = std::signbit(x) ? 0x8000u : 0u;
-    double ax = std::fabs(x);
-    if (ax == 0.0) return sign;
-    if (ax >= 65520.0) return (unsigned short)(sign | 0x7c00u);
-    int e;
-    (void)std::frexp(ax, &e);                                  // ax = f 2^e, f in [0.5, 1)
-    int ex = e - 1;                                            // ax = 1.m x 2^ex
-    if (ex < -14) ex = -14;                                    // subnormal: fixed quantum 2^-24
-    const double q = std::ldexp(1.0, ex - 10);                 // quantum of the 11-bit significand
-    const double r = std::nearbyint(ax / q);                   // ties to even (default rounding mode)
-    const double v = r * q;                                    // may have carried into the next binade: recompute the fields
-    if (v >= 65520.0) return (unsigned short)(sign | 0x7c00u);
-    if (v < std::ldexp(1.0, -14)) return (unsigned short)(sign | (unsigned short)std::lrint(v / std::ldexp(1.0, -24)));
-    int e2;
-    (void)std::frexp(v, &e2);
-    const int ex2 = e2 - 1;
-    const unsigned mant = (unsigned)std::lrint(v / std::ldexp(1.0, ex2 - 10)) - 1024u;
-    return (unsigned short)(sign | (unsigned)((ex2 + 15) << 10) | mant);
-}
-double f16_value(unsigned short h)
-{
-    const int e = (h >> 10) & 31, m = h & 1023;
-    const double v = e == 0 ? std::ldexp((double)m, -24) : std::ldexp((double)(1024 + m), e - 25);
-    return (h & 0x8000u) ? -v : v;
-}
-}  // namespace
-
-extern "C" int read_conv_pack_w4h_host(int Cin, int Cout, const float *wf, const float *wm, void *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_w4h_host: null pointer");
-    READ_CHECK_ARG(Cin >= 32 && Cin % 32 == 0 && Cout >= 1, "read_conv_pack_w4h_host: needs Cin %% 32 == 0 (got %d)", Cin);
-    static const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
-    const int CoutPad = pad32(Cout), nchunks = Cin / 32;
-    unsigned short *h = static_cast<unsigned short *>(out);
-    float *inv = reinterpret_cast<float *>(out) + (size_t)Cin * 36 * 2 * CoutPad;
-    std::vector<double> U((size_t)36 * Cin);
-    for (int row = 0; row < 2 * CoutPad; ++row) {               // row = [f | m] x padded output channel
-        const int fm = row / CoutPad, co = row % CoutPad;
-        double mx = 0.0;
-        if (co < Cout)
-            for (int ci = 0; ci < Cin; ++ci) {
-                const float *k = (fm ? wm : wf) + ((size_t)co * Cin + ci) * 9;
-                for (int fq = 0; fq < 36; ++fq) {
-                    double u = 0.0;
-                    for (int a = 0; a < 3; ++a)
-                        for (int b = 0; b < 3; ++b) u += G[fq / 6][a] * (double)k[a * 3 + b] * G[fq % 6][b];
-                    U[(size_t)fq * Cin + ci] = u;
-                    mx = std::fmax(mx, std::fabs(u));
-                }
-            }
-        else
-            std::fill(U.begin(), U.end(), 0.0);
-        int ex = 0;                                            // s = 2^ex: max |U| s in [2^14, 2^15)
-        if (mx > 0.0 && std::isfinite(mx)) {
-            int e;
-            (void)std::frexp(mx, &e);                          // mx in [2^(e-1), 2^e)
-            ex = 15 - e;
-            if (ex > 60) ex = 60;                              // a row of denormal weights: keep 1 / s an fp32 normal
-            if (ex < -60) ex = -60;
-        }
-        inv[row] = (float)std::ldexp(1.0, -ex);
-        const int g = co / 32, w = (co % 32) / 8, i = (co % 8) + 8 * fm;
-        for (int c = 0; c < nchunks; ++c)
-            for (int fq = 0; fq < 36; ++fq)
-                for (int kq = 0; kq < 4; ++kq)
-                    for (int e = 0; e < 8; ++e) {
-                        const double us = std::ldexp(U[(size_t)fq * Cin + 32 * c + 8 * kq + e], ex);
-                        const unsigned short hi = f16_bits_rtn(us), lo = f16_bits_rtn(us - f16_value(hi));
-                        const size_t frag = ((((size_t)(g * 4 + w) * nchunks + c) * 36 + fq) * 2) * 512;   // halfs; 512 per piece
-                        const int lane = i + 16 * kq;
-                        h[frag + (size_t)lane * 8 + e] = hi;
-                        h[frag + 512 + (size_t)lane * 8 + e] = lo;
-                    }
-    }
-    return READ_OK;
-}
-
-// F(4,3)-by-rows operand of gated_conv_f4x1h_kernel: U[ky] = G w[ky][:] in double (the filter transform along x only), scaled per
-// output ROW by the power of two s that puts max |U s| of the row in [2^14, 2^15), cut into Uh = f16(U s) and Ul = f16(U s - Uh);
-// order [group][wave 4][chunk of 32 cin][ky 3][frequency 6][piece Uh | Ul][lane][8 halfs], lanes as in read_conv_pack_w4h_host; then
-// 2 * CoutPad floats 1 / s ([conv_f rows | conv_m rows]).  Half the bytes of the F(4x4) order: Cin * 18 * pad32(Cout) * 2 halfs.
-extern "C" size_t read_conv_f4x1_floats(int Cin, int Cout)
-{
-    if (Cin < 32 || Cin % 32 || Cout < 1) return 0;
-    return (size_t)Cin * 18 * 2 * pad32(Cout) + 2 * (size_t)pad32(Cout);
-}
-
-extern "C" int read_conv_pack_f4x1_host(int Cin, int Cout, const float *wf, const float *wm, void *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_f4x1_host: null pointer");
-    READ_CHECK_ARG(Cin >= 32 && Cin % 32 == 0 && Cout >= 1, "read_conv_pack_f4x1_host: needs Cin %% 32 == 0 (got %d)", Cin);
-    static const double G[6][3] = {{0.25, 0.0, 0.0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                   {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0.0, 0.0, 1.0}};
-    const int CoutPad = pad32(Cout), nchunks = Cin / 32;
-    unsigned short *h = static_cast<unsigned short *>(out);
-    float *inv = reinterpret_cast<float *>(out) + (size_t)Cin * 18 * 2 * CoutPad;
-    std::vector<double> U((size_t)18 * Cin);                   // [ky][frequency][cin]
-    for (int row = 0; row < 2 * CoutPad; ++row) {               // row = [f | m] x padded output channel
-        const int fm = row / CoutPad, co = row % CoutPad;
-        double mx = 0.0;
-        if (co < Cout)
-            for (int ci = 0; ci < Cin; ++ci) {
-                const float *k = (fm ? wm : wf) + ((size_t)co * Cin + ci) * 9;
-                for (int t = 0; t < 18; ++t) {
-                    double u = 0.0;
-                    for (int b = 0; b < 3; ++b) u += G[t % 6][b] * (double)k[(t / 6) * 3 + b];
-                    U[(size_t)t * Cin + ci] = u;
-                    mx = std::fmax(mx, std::fabs(u));
-                }
-            }
-        else
-            std::fill(U.begin(), U.end(), 0.0);
-        int ex = 0;                                            // s = 2^ex: max |U| s in [2^14, 2^15)
-        if (mx > 0.0 && std::isfinite(mx)) {
-            int e;
-            (void)std::frexp(mx, &e);                          // mx in [2^(e-1), 2^e)
-            ex = 15 - e;
-            if (ex > 60) ex = 60;                              // a row of denormal weights: keep 1 / s an fp32 normal
-            if (ex < -60) ex = -60;
-        }
-        inv[row] = (float)std::ldexp(1.0, -ex);
-        const int g = co / 32, w = (co % 32) / 8, i = (co % 8) + 8 * fm;
-        for (int c = 0; c < nchunks; ++c)
-            for (int t = 0; t < 18; ++t)
-                for (int kq = 0; kq < 4; ++kq)
-                    for (int e = 0; e < 8; ++e) {
-                        const double us = std::ldexp(U[(size_t)t * Cin + 32 * c + 8 * kq + e], ex);
-                        const unsigned short hi = f16_bits_rtn(us), lo = f16_bits_rtn(us - f16_value(hi));
-                        const size_t frag = ((((size_t)(g * 4 + w) * nchunks + c) * 18 + t) * 2) * 512;     // halfs; 512 per piece
-                        const int lane = i + 16 * kq;
-                        h[frag + (size_t)lane * 8 + e] = hi;
-                        h[frag + 512 + (size_t)lane * 8 + e] = lo;
-                    }
-    }
-    return READ_OK;
-}
-
-// Operand of the direct split-operand kernel (gated_conv_d3h_kernel): the 3x3 weights themselves, scaled per output ROW by the power
-// of two s that puts the row's largest |w s| in [2^14, 2^15), cut into wh = f16(w s) and wl = f16(w s - wh); order
-// [group][row half rh 2][chunk of 32 cin][tap 9 = 3 ky + kx][row block rb 2][piece wh | wl][lane][8 halfs], lane (i = lane & 15,
-// kq = lane >> 4) = row i of the block (i < 8: conv_f of channel 32 g + 16 rh + 8 rb + i, else conv_m of channel ... + i - 8), cin = 32
-// chunk + 8 kq + e; then 2 * CoutPad floats 1 / s ([conv_f rows | conv_m rows]).   (tests/d3h_ref.py)
-extern "C" size_t read_conv_dkh_floats(int Cin, int Cout, int ksize)
-{
-    if (ksize == 1) return (Cin < 16 || Cin % 16 || Cout < 1) ? 0 : (size_t)Cin * 2 * pad32(Cout) + 2 * (size_t)pad32(Cout);
-    if (Cin < 32 || Cin % 32 || Cout < 1 || (ksize != 3 && ksize != 4)) return 0;
-    return (size_t)Cin * 2 * ksize * ksize * pad32(Cout) + 2 * (size_t)pad32(Cout);
-}
-extern "C" size_t read_conv_d3h_floats(int Cin, int Cout) { return read_conv_dkh_floats(Cin, Cout, 3); }
-extern "C" int read_conv_pack_dkh_host(int Cin, int Cout, int ksize, const float *wf, const float *wm, void *out);
-extern "C" int read_conv_pack_d3h_host(int Cin, int Cout, const float *wf, const float *wm, void *out)
-{
-    return read_conv_pack_dkh_host(Cin, Cout, 3, wf, wm, out);
-}
-
-// ... the same for a k x k kernel, k = 3 or 4 (tap = k ky + kx): the 4 x 4 / stride-2 layers run on the stride-2 kernel too
-extern "C" int read_conv_pack_dkh_host(int Cin, int Cout, int ksize, const float *wf, const float *wm, void *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_dkh_host: null pointer");
-    if (ksize == 1) {
-        // 1x1 layers (gated_conv_pxh_kernel, v_mfma_f32_32x32x16_f16 with the weights as the A operand): the same rows, scales and
-        // pieces in the order [k16 step][tile t = 2 group + (f | m)][wh | wl][lane][8 halfs], lane (i = lane & 31, h = lane >> 5) =
-        // row i of the tile (conv_f / conv_m of channel 32 group + i), cin = 16 step + 8 h + e; then the 2 * CoutPad floats 1 / s.
-        READ_CHECK_ARG(Cin >= 16 && Cin % 16 == 0 && Cout >= 1, "read_conv_pack_dkh_host: a 1x1 layer needs Cin %% 16 == 0 (got %d)", Cin);
-        const int CoutPad = pad32(Cout), nsteps = Cin / 16, NTL = CoutPad / 16;
-        unsigned short *h = static_cast<unsigned short *>(out);
-        float *inv = reinterpret_cast<float *>(out) + (size_t)Cin * 2 * CoutPad;
-        for (int row = 0; row < 2 * CoutPad; ++row) {
-            const int fm = row / CoutPad, co = row % CoutPad;
-            const float *k = co < Cout ? (fm ? wm : wf) + (size_t)co * Cin : nullptr;
-            double mx = 0.0;
-            if (k)
-                for (int i = 0; i < Cin; ++i) mx = std::fmax(mx, std::fabs((double)k[i]));
-            int ex = 0;
-            if (mx > 0.0 && std::isfinite(mx)) {
-                int e;
-                (void)std::frexp(mx, &e);
-                ex = 15 - e;
-                if (ex > 60) ex = 60;
-                if (ex < -60) ex = -60;
-            }
-            inv[row] = (float)std::ldexp(1.0, -ex);
-            const int t = 2 * (co / 32) + fm, i = co % 32;
-            for (int st = 0; st < nsteps; ++st)
-                for (int hh = 0; hh < 2; ++hh)
-                    for (int e = 0; e < 8; ++e) {
-                        const double ws = k ? std::ldexp((double)k[16 * st + 8 * hh + e], ex) : 0.0;
-                        const unsigned short hi = f16_bits_rtn(ws), lo = f16_bits_rtn(ws - f16_value(hi));
-                        const size_t frag = (((size_t)st * NTL + t) * 2) * 512;                   // halfs; 512 per piece
-                        const int lane = i + 32 * hh;
-                        h[frag + (size_t)lane * 8 + e] = hi;
-                        h[frag + 512 + (size_t)lane * 8 + e] = lo;
-                    }
-        }
-        return READ_OK;
-    }
-    READ_CHECK_ARG(ksize == 3 || ksize == 4, "read_conv_pack_dkh_host: ksize must be 1, 3 or 4");
-    READ_CHECK_ARG(Cin >= 32 && Cin % 32 == 0 && Cout >= 1, "read_conv_pack_dkh_host: needs Cin %% 32 == 0 (got %d)", Cin);
-    const int CoutPad = pad32(Cout), nchunks = Cin / 32, NT = ksize * ksize;
-    unsigned short *h = static_cast<unsigned short *>(out);
-    float *inv = reinterpret_cast<float *>(out) + (size_t)Cin * 2 * NT * CoutPad;
-    for (int row = 0; row < 2 * CoutPad; ++row) {               // row = [f | m] x padded output channel
-        const int fm = row / CoutPad, co = row % CoutPad;
-        const float *k = co < Cout ? (fm ? wm : wf) + (size_t)co * Cin * NT : nullptr;
-        double mx = 0.0;
-        if (k)
-            for (size_t i = 0; i < (size_t)Cin * NT; ++i) mx = std::fmax(mx, std::fabs((double)k[i]));
-        int ex = 0;
-        if (mx > 0.0 && std::isfinite(mx)) {
-            int e;
-            (void)std::frexp(mx, &e);
-            ex = 15 - e;
-            if (ex > 60) ex = 60;
-            if (ex < -60) ex = -60;
-        }
-        inv[row] = (float)std::ldexp(1.0, -ex);
-        const int g = co / 32, rh = (co % 32) / 16, rb = (co % 16) / 8, i = (co % 8) + 8 * fm;
-        for (int c = 0; c < nchunks; ++c)
-            for (int tap = 0; tap < NT; ++tap)
-                for (int kq = 0; kq < 4; ++kq)
-                    for (int e = 0; e < 8; ++e) {
-                        const double ws = k ? std::ldexp((double)k[(size_t)(32 * c + 8 * kq + e) * NT + tap], ex) : 0.0;
-                        const unsigned short hi = f16_bits_rtn(ws), lo = f16_bits_rtn(ws - f16_value(hi));
-                        const size_t frag = (((((size_t)(g * 2 + rh) * nchunks + c) * NT + tap) * 2 + rb) * 2) * 512;    // halfs; 512 per piece
-                        const int lane = i + 16 * kq;
-                        h[frag + (size_t)lane * 8 + e] = hi;
-                        h[frag + 512 + (size_t)lane * 8 + e] = lo;
-                    }
-    }
-    return READ_OK;
-}
-
-// 3x3 weights of a layer with 8, 16 or 32 input channels as the implicit-GEMM operand of the split-operand pixel-lane kernel: the matrix
-// W'[cout][k = tap Cin + ci] (tap = 3 ky + kx), k padded with zeros to whole k16 steps, in the 1x1 operand's order (read_conv_pack_dkh_host, ksize 1)
-extern "C" size_t read_conv_t3h_floats(int Cin, int Cout)
-{
-    return (Cin == 8 || Cin == 16 || Cin == 32) && Cout >= 1 ? read_conv_dkh_floats((9 * Cin + 15) / 16 * 16, Cout, 1) : 0;
-}
-
-extern "C" int read_conv_pack_t3h_host(int Cin, int Cout, const float *wf, const float *wm, void *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_t3h_host: null pointer");
-    READ_CHECK_ARG(read_conv_t3h_floats(Cin, Cout) > 0, "read_conv_pack_t3h_host: needs Cin = 8, 16 or 32 (got %d)", Cin);
-    const int K = (9 * Cin + 15) / 16 * 16;
-    std::vector<float> f((size_t)Cout * K, 0.0f), m((size_t)Cout * K, 0.0f);
-    for (int co = 0; co < Cout; ++co)
-        for (int ci = 0; ci < Cin; ++ci)
-            for (int tap = 0; tap < 9; ++tap) {
-                f[(size_t)co * K + tap * Cin + ci] = wf[((size_t)co * Cin + ci) * 9 + tap];
-                m[(size_t)co * K + tap * Cin + ci] = wm[((size_t)co * Cin + ci) * 9 + tap];
-            }
-    return read_conv_pack_dkh_host(K, Cout, 1, f.data(), m.data(), out);
-}
-
-// Small-Cout order (gated_conv_smallc_kernel): [tap][cin][f0 f1 f2 f3 | m0 m1 m2 m3], channels >= Cout zero.
-extern "C" size_t read_conv_sc_floats(int Cin, int Cout)
-{
-    return (Cin == 32 && Cout >= 1 && Cout <= 4) ? (size_t)9 * Cin * 8 : 0;      // the kernel is instantiated for 32 input channels
-}
-
-extern "C" int read_conv_pack_sc_host(int Cin, int Cout, const float *wf, const float *wm, float *out)
-{
-    READ_CHECK_ARG(wf && wm && out, "read_conv_pack_sc_host: null pointer");
-    READ_CHECK_ARG(read_conv_sc_floats(Cin, Cout) > 0, "read_conv_pack_sc_host: needs Cin == 32 and 1 <= Cout <= 4 (got %d, %d)", Cin, Cout);
-    for (int tap = 0; tap < 9; ++tap)
-        for (int ci = 0; ci < Cin; ++ci)
-            for (int j = 0; j < 8; ++j) {
-                const int co = j & 3;
-                out[((size_t)tap * Cin + ci) * 8 + j] = co < Cout ? ((j >> 2) ? wm : wf)[((size_t)co * Cin + ci) * 9 + tap] : 0.0f;
-            }
-    return READ_OK;
-}
-
-extern "C" int read_conv_pack_params_host(int Cout, const float *bf, const float *bm, const float *gamma,
-                                          const float *beta, const float *mean, const float *var, float eps,
-                                          float *params_host)
-{
-    READ_CHECK_ARG(bf && bm && gamma && beta && mean && var && params_host, "read_conv_pack_params_host: null pointer");
-    READ_CHECK_ARG(Cout >= 1, "read_conv_pack_params_host: Cout < 1");
-    const int CoutPad = pad32(Cout);
-    for (int c = 0; c < CoutPad; ++c) {
-        const bool ok = c < Cout;
-        // eval-mode BatchNorm folded to y = x*scale + shift (applied AFTER the gate product)
-        const float scale = ok ? gamma[c] / sqrtf(var[c] + eps) : 0.0f;
-        params_host[c] = ok ? bf[c] : 0.0f;
-        params_host[CoutPad + c] = ok ? bm[c] : 0.0f;
-        params_host[2 * CoutPad + c] = scale;
-        params_host[3 * CoutPad + c] = ok ? beta[c] - mean[c] * scale : 0.0f;
-    }
-    return READ_OK;
-}
+// (the host weight packers, read_conv_pack_*_host, are conv_pack.cpp)
 
 namespace readhip {
 

@@ -7,6 +7,9 @@ namespace readhip {
 // api_common.cpp: compute units of the current device, queried once per process (256 where the query fails)
 int device_cus();
 
+// Output channels padded to whole 32-channel groups: the unit of every packed weight order and of the conv kernels
+static inline int pad32(int c) { return (c + 31) / 32 * 32; }
+
 // conv.hip
 // Validates a descriptor, routes it (conv_route) and launches: shared by read_gated_conv_forward[_f4x1] and the UNet executor.
 // wp_f4x1: the F(4,3)-by-rows operand beside the descriptor, or NULL.

@@ -1,5 +1,5 @@
 """NumPy model of the split-operand Winograd F(4x4,3x3) kernel on v_mfma_f32_16x16x32_f16 (gated_conv_wino4h_kernel in
-read_amd/csrc/conv.hip): the host packer (row scales, f16 hi / lo pieces, fragment order), the transform thread's (tile, channel
+read_amd/csrc/conv.hip): the host packer (conv_pack.cpp: row scales, f16 hi / lo pieces, fragment order), the transform thread's (tile, channel
 pair) role, the hi / scaled-lo split of the transformed input, the swizzled V buffer, the MFMA operand and result lane maps, the
 three piece pairs per product and the 1 / s of the epilogue.  tests/test_wino_cpu.py compares it with torch's conv2d and the
 library's packer with this one, bit for bit.
