@@ -76,7 +76,7 @@ int read_device_arch(char *name, int len);
  *                     (read_conv_desc.pre_bilinear; measured level-to-slower, profiles/r5_up_fold_ab.md); plans created afterwards
  *   "wgrad_wino"      1 (default): 3x3/s1 weight gradients in the Winograd F(4x4,3x3) domain; 0: direct MFMA kernel; v > 1: the same
  *                     with 128 v workgroups aimed at (default 256)
- *   "conv_wave", "conv_kc32", "conv_stagger", "unet_streams": see csrc/conv.hip, csrc/unet.cpp.
+ *   "conv_wave", "conv_kc32", "conv_stagger": see csrc/conv.hip.
  * read_tuning_key(i) enumerates the keys (NULL past the end); read_tuning_get reads the current value, so that a
  * benchmark can record the state it ran with. */
 int read_tuning_set(const char *key, int value);

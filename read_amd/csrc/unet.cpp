@@ -261,7 +261,6 @@ struct Tensor {
     float *p = nullptr;   // null for external tensors until forward()
     int ext = -1;         // 0..3 = x0..x3, 4 = rgb output
     int H = 0, W = 0, C = 0;
-    int lane = 0;         // lane of the op that writes it
 };
 
 struct Op {
@@ -274,8 +273,6 @@ struct Op {
     int pre_t = -1;            // CONV: tensor of the pre-activation addend
     double flops;
     int is_c3s1;
-    int lane = 0;              // 0: the caller's stream; 1..3: side stream of SCM 0..2 (independent of the trunk)
-    int wait_mask = 0;         // side lanes whose results this (main-lane) op consumes
     std::string label;
 };
 
@@ -291,10 +288,6 @@ struct read_unet {
     std::vector<Op> ops;
     hipEvent_t *events = nullptr;
     int n_events = 0;
-    // the three SCM chains (15 small launches) run on side streams, concurrently with each other and with the first
-    // trunk layers; joined by events right before FAM2 / FAM1 / FAM0 read them
-    hipStream_t side[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t ev_start = nullptr, ev_done[3] = {nullptr, nullptr, nullptr};
 };
 
 namespace {
@@ -311,7 +304,6 @@ struct Builder {
     read_unet *u;
     bool dry;                   // size-only pass
     size_t used = 0;
-    int cur_lane = 0;
 
     int tensor(const std::string &name, int level, int C)
     {
@@ -421,14 +413,6 @@ struct Builder {
         if (cin != L.cin) set_error("internal: layer %s expects Cin=%d, plan gives %d", L.path.c_str(), L.cin, cin);
         if (o.C != (linear ? 2 : 1) * L.cout && o.ext < 0)
             set_error("internal: layer %s writes %d channels into a %d-channel tensor", L.path.c_str(), (linear ? 2 : 1) * L.cout, o.C);
-        op.lane = cur_lane;
-        u->tensors[out_t].lane = cur_lane;
-        if (cur_lane == 0) {
-            for (size_t i = 0; i < srcs.size(); ++i)
-                if (u->tensors[srcs[i].first].lane > 0) op.wait_mask |= 1 << (u->tensors[srcs[i].first].lane - 1);
-            if (mul_t >= 0 && u->tensors[mul_t].lane > 0) op.wait_mask |= 1 << (u->tensors[mul_t].lane - 1);
-            if (res_t >= 0 && u->tensors[res_t].lane > 0) op.wait_mask |= 1 << (u->tensors[res_t].lane - 1);
-        }
         u->ops.push_back(op);
     }
     void up4(int in_t, int out_t)
@@ -474,13 +458,11 @@ struct Builder {
         int c = tensor(p + ".c", level, P / 2);
         int d = tensor(p + ".d", level, P - IN_CH);
         int z = tensor(p + ".out", level, P);
-        cur_lane = 1 + n;
         conv(p + ".main.0", {{xin, 0}}, a);
         conv(p + ".main.1", {{a, 0}}, b);
         conv(p + ".main.2", {{b, 0}}, c);
         conv(p + ".main.3", {{c, 0}}, d);
         conv(p + ".conv", {{xin, 0}, {d, 0}}, z);
-        cur_lane = 0;
         return z;
     }
 
@@ -585,34 +567,11 @@ int check_hw(int H, int W)
     return READ_OK;
 }
 
-int g_unet_streams = 0;       // read_tuning_set("unet_streams", 1): SCM chains on side streams (measured slower: 135.8 vs 141.7 frames/s)
-
-int run(read_unet *u, const float *const ext[5], int rgb_cstride, hipStream_t s0, bool timed)
+// Every op goes onto the caller's stream, in plan order.
+int run(read_unet *u, const float *const ext[5], int rgb_cstride, hipStream_t s, bool timed)
 {
     int ev = 0;
-    if (!timed && g_unet_streams && !u->side[0]) {
-        for (int i = 0; i < 3; ++i) {
-            READ_CHECK_HIP(hipStreamCreateWithFlags(&u->side[i], hipStreamNonBlocking));
-            READ_CHECK_HIP(hipEventCreateWithFlags(&u->ev_done[i], hipEventDisableTiming));
-        }
-        READ_CHECK_HIP(hipEventCreateWithFlags(&u->ev_start, hipEventDisableTiming));
-    }
-    const bool fork = !timed && g_unet_streams && u->side[0];
-    int last_of_lane[4] = {-1, -1, -1, -1};
-    if (fork) {
-        READ_CHECK_HIP(hipEventRecord(u->ev_start, s0));          // inputs (and the previous frame) are ordered before this
-        for (int i = 0; i < 3; ++i) READ_CHECK_HIP(hipStreamWaitEvent(u->side[i], u->ev_start, 0));
-        for (size_t i = 0; i < u->ops.size(); ++i) last_of_lane[u->ops[i].lane] = (int)i;
-    }
-    int waited = 0;
-    for (size_t oi = 0; oi < u->ops.size(); ++oi) {
-        Op &op = u->ops[oi];
-        hipStream_t s = (fork && op.lane > 0) ? u->side[op.lane - 1] : s0;
-        if (fork && (op.wait_mask & ~waited)) {
-            for (int i = 0; i < 3; ++i)
-                if ((op.wait_mask & ~waited) & (1 << i)) READ_CHECK_HIP(hipStreamWaitEvent(s0, u->ev_done[i], 0));
-            waited |= op.wait_mask;
-        }
+    for (const Op &op : u->ops) {
         if (timed) READ_CHECK_HIP(hipEventRecord(u->events[ev++], s));
         auto ptr = [&](int t) -> const float * {
             if (t < 0) return nullptr;
@@ -638,13 +597,8 @@ int run(read_unet *u, const float *const ext[5], int rgb_cstride, hipStream_t s0
             const int rc = read_bilinear_up4(ptr(op.in_t), I.H, I.W, I.C, const_cast<float *>(ptr(op.out_t)), s);
             if (rc != READ_OK) return rc;
         }
-        if (fork && op.lane > 0 && (int)oi == last_of_lane[op.lane])
-            READ_CHECK_HIP(hipEventRecord(u->ev_done[op.lane - 1], s));
     }
-    if (fork)                                                       // a lane nobody consumed still joins the caller's stream
-        for (int i = 0; i < 3; ++i)
-            if (!(waited & (1 << i)) && last_of_lane[i + 1] >= 0) READ_CHECK_HIP(hipStreamWaitEvent(s0, u->ev_done[i], 0));
-    if (timed) READ_CHECK_HIP(hipEventRecord(u->events[ev++], s0));
+    if (timed) READ_CHECK_HIP(hipEventRecord(u->events[ev++], s));
     return READ_OK;
 }
 
@@ -774,7 +728,7 @@ extern "C" int read_unet_create_layout(read_unet_t **out, const float *packed, i
         delete u;
         return READ_EINVAL;
     }
-    *out = u;                     // (side streams are created on first use: the plan can be built without a device)
+    *out = u;                     // (nothing here touches a device: the plan can be built without one)
     return READ_OK;
 }
 
@@ -814,14 +768,6 @@ extern "C" void read_unet_destroy(read_unet_t *u)
     if (!u) return;
     for (int i = 0; i < u->n_events; ++i) (void)hipEventDestroy(u->events[i]);
     delete[] u->events;
-    for (int i = 0; i < 3; ++i) {
-        if (u->side[i]) {
-            (void)hipStreamSynchronize(u->side[i]);
-            (void)hipStreamDestroy(u->side[i]);
-        }
-        if (u->ev_done[i]) (void)hipEventDestroy(u->ev_done[i]);
-    }
-    if (u->ev_start) (void)hipEventDestroy(u->ev_start);
     delete u;
 }
 
@@ -906,7 +852,6 @@ extern "C" const float *read_unet_debug_tensor(read_unet_t *u, const char *name,
 
 namespace readhip {
 static const TuneRow k_unet_knobs[] = {
-    {"unet_streams", &g_unet_streams, TN_RAW, 0, 0},          // 0: SCM chains on the caller's stream
     {"unet_aff_split", &g_unet_aff_split, TN_FLAG, 0, 0},     // 0: AFF first convs as single 480-channel launches (plans created afterwards)
     {"unet_up_fold", &g_unet_up_fold, TN_FLAG, 0, 0},         // 0: Upsample4(bilinear) as a separate pass and Convs.k over the concat (plans created afterwards)
 };

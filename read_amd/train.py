@@ -85,18 +85,17 @@ def layer_route(cin, cout, k, stride):
     return LayerRoute(cin, cout, k, stride, fwd, fwd_kc, dgrad, 16, poly)
 
 
-def dgrad_method(route, H, W, capturing=False, polyphase=None):
+def dgrad_method(route, H, W, polyphase=None):
     """How the input gradient of a layer over an (H, W) input is computed (_dgrad runs it):
       'conv'     stride 1: the convolution kernel over d[f|m] with the layer's dgrad fragments
-      'poly'     stride 2, even H and W: four 3x3 / stride-1 dgrads, one per pixel parity (_poly_fragments) — not inside a captured
-                 step, whose retained backward graph is walked again after the weights have changed
+      'poly'     stride 2, even H and W: four 3x3 / stride-1 dgrads, one per pixel parity (_poly_fragments)
       'dilated'  3x3 / stride 2, even H and W: 'conv' over the zero-dilated d[f|m]
       'generic'  the vector kernel (read_conv_dgrad_generic)
     polyphase: POLYPHASE_DGRAD unless given.  Pure, like layer_route."""
     if route.stride == 1:
         return 'conv'
     even = H % 2 == 0 and W % 2 == 0
-    if (POLYPHASE_DGRAD if polyphase is None else polyphase) and route.poly is not None and even and not capturing:
+    if (POLYPHASE_DGRAD if polyphase is None else polyphase) and route.poly is not None and even:
         return 'poly'
     return 'dilated' if route.dgrad is not None and even else 'generic'
 
@@ -216,7 +215,7 @@ class _PackEntry:
         self.version, self.route = version, route           # _pack_version of the tensors packed; LayerRoute
         self.params, self.fwd = params, fwd                 # parameter block; forward fragments in the order route.fwd
         self.dgrad, self.dgrad_event = dgrad, None          # dgrad fragments in the order route.dgrad (None: not packed) + their event
-        self.event = event                                  # params / fwd are packed; None: by the step's pack plan or inside a capture
+        self.event = event                                  # params / fwd are packed; None: by the step's pack plan
         self.ref = None                                     # weakref of the conv_f weight the cache key is the id of (_cache_put)
 
     @property
@@ -294,8 +293,7 @@ def _layer_jobs(route, wf, wm, ts=None, identity_bn=False, fwd=True, dgrad=True)
 
 
 def _launch_jobs(jobs):
-    """One launch per job on the current stream: the path of a captured step, of a standalone GatedConvFn and of weights the step's
-    plan does not take."""
+    """One launch per job on the current stream: the path of a standalone GatedConvFn and of weights the step's plan does not take."""
     L, st = _lib.lib(), _lib.stream_ptr()
     for j in jobs:
         _lib.check(L.read_conv_pack_job(C.byref(j), st), "read_conv_pack_job")
@@ -306,10 +304,7 @@ def _packed_for(route, ts, identity_bn=False):
     running mean, running var), from the cache or packed now."""
     wf, wm = ts[0], ts[2]
     ver = _pack_version(route, ts, identity_bn)
-    # While a HIP graph is being captured (GraphedTrainStep) every layer packs afresh: the packing launches must be PART of
-    # the graph — it is replayed after every optimizer step — and a cache hit would freeze the fragments of the capture step in.
-    capturing = torch.cuda.is_current_stream_capturing()
-    hit = None if capturing else _PACK_CACHE.get(id(wf))
+    hit = _PACK_CACHE.get(id(wf))
     if hit is not None and hit.ref() is not wf:             # the id was recycled by another tensor: not this layer's entry
         hit = None
     if hit is not None and hit.version == ver:
@@ -321,13 +316,10 @@ def _packed_for(route, ts, identity_bn=False):
         return hit
     jobs = _layer_jobs(route, wf.detach().contiguous(), wm.detach().contiguous(), ts, identity_bn, dgrad=False)
     _launch_jobs(j for j, _out in jobs.values())
-    ev = None
-    if not capturing:             # an event recorded inside a capture must never be waited on from outside it (see backward)
-        ev = torch.cuda.Event()
-        ev.record()
+    ev = torch.cuda.Event()
+    ev.record()
     entry = _PackEntry(ver, route, jobs['params'][1], jobs['fwd'][1], event=ev)
-    if not capturing:                                         # a captured entry lives in the graph's memory pool, not in the cache
-        _cache_put(wf, entry)
+    _cache_put(wf, entry)
     return entry
 
 
@@ -335,10 +327,8 @@ def _pack_dgrad(entry, wf, wm):
     """Flipped / transposed fragments of the layer for its dgrad (direct or, for 3x3, Winograd) on the current stream."""
     jobs = _layer_jobs(entry.route, wf.detach().contiguous(), wm.detach().contiguous(), fwd=False)
     _launch_jobs(j for j, _out in jobs.values())
-    ev = None
-    if not torch.cuda.is_current_stream_capturing():
-        ev = torch.cuda.Event()
-        ev.record()
+    ev = torch.cuda.Event()
+    ev.record()
     entry.dgrad, entry.dgrad_event = jobs['dgrad'][1], ev
 
 
@@ -369,11 +359,10 @@ def _poly_fragments(wf, wm, route):
     cin, cout, k = route.cin, route.cout, route.k
     key = id(wf)
     ver = (wf._version, wm._version, wf.data_ptr(), wm.data_ptr(), route)
-    capturing = torch.cuda.is_current_stream_capturing()
-    hit = None if capturing else _POLY.get(key)
+    hit = _POLY.get(key)
     if hit is not None and hit.version == ver:
         cur = torch.cuda.current_stream(wf.device)
-        if hit.stream != cur.cuda_stream:                         # packed on another stream (e.g. a graph capture's warm-up)
+        if hit.stream != cur.cuda_stream:                         # packed on another stream (a caller that runs its steps on several)
             cur.wait_event(hit.event)
             hit.frags.record_stream(cur)
         return hit.frags
@@ -387,12 +376,11 @@ def _poly_fragments(wf, wm, route):
     buf = torch.empty((4, _fragment_floats(route.poly, 1, cin, cout, 3)), dtype=torch.float32, device=dev)
     # the dgrad jobs of four 3x3 pseudo-layers, one launch each
     _launch_jobs(_job(route.poly, 1, cin, cout, 3, route.dgrad_kc, buf[par], wp[par, 0], wp[par, 1]) for par in range(4))
-    if not capturing:
-        ev = torch.cuda.Event()
-        ev.record()
-        if key not in _POLY:
-            weakref.finalize(wf, _POLY.pop, key, None)
-        _POLY[key] = _PolyEntry(ver, buf, ev, torch.cuda.current_stream(dev).cuda_stream)
+    ev = torch.cuda.Event()
+    ev.record()
+    if key not in _POLY:
+        weakref.finalize(wf, _POLY.pop, key, None)
+    _POLY[key] = _PolyEntry(ver, buf, ev, torch.cuda.current_stream(dev).cuda_stream)
     return buf
 
 
@@ -455,23 +443,21 @@ class _PackPlan:
         sig = tuple(t._version for ts, _entry in self.layers for t in ts)
         cur = torch.cuda.current_stream()
         if sig == self.signature:
-            if self.event is not None and cur != self.stream and not torch.cuda.is_current_stream_capturing():
+            if cur != self.stream:
                 cur.wait_event(self.event)                # packed on another stream: order this one behind that launch
             return
         _lib.check(_lib.lib().read_conv_pack_batch(self.table.data_ptr(), self.njobs, self.total_blocks, _lib.stream_ptr()),
                    "read_conv_pack_batch")
         self.signature = sig
-        self.stream, self.event = cur, None
-        if not torch.cuda.is_current_stream_capturing():
-            self.event = torch.cuda.Event()
-            self.event.record(cur)
+        self.stream, self.event = cur, torch.cuda.Event()
+        self.event.record(cur)
         for ts, entry in self.layers:                     # the per-layer cache then hits for every layer (entry.event stays None)
             entry.version = _pack_version(entry.route, ts, self.identity_bn)
             _cache_put(ts[0], entry)
 
 
 def _net_tensors(net):
-    """The net's parameters and buffers, listed once: their addresses key what is built per net (pack plans, captured steps)."""
+    """The net's parameters and buffers, listed once: their addresses key what is built per net (the pack plans)."""
     ts = net.__dict__.get('_flat_tensors')
     if ts is None:
         ts = net.__dict__['_flat_tensors'] = list(net.parameters()) + list(net.buffers())
@@ -550,7 +536,7 @@ def _dgrad(method, route, dfm, H, W, wf, wm, entry=None, live=None, out=None):
             _pack_dgrad(entry, wf, wm)
         wd, ev = entry.dgrad, entry.dgrad_event
         wdw = wd if route.dgrad != _lib.PACK_DIRECT else None
-        if ev is not None:                   # None: packed by the step's forward HIP graph, ordered by the replay itself
+        if ev is not None:                   # None: packed by the step's pack plan, whose refresh() ordered this stream behind it
             torch.cuda.current_stream().wait_event(ev)
             wd.record_stream(torch.cuda.current_stream())
         zero = _zero_params(L.read_conv_param_floats(cin // 2), dev)
@@ -569,6 +555,9 @@ class GatedConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wf, bf, wm, bm, gamma, beta, mean, var, k, stride, elu, nb=1, v_num=1, v_den=1, bn_train=False, arena=None):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("read_amd.train: the training nodes cache packed weights and record events, so they cannot be captured "
+                               "into a HIP graph — a replay would run on the weights of the capture step")
         L = _lib.lib()
         st = _lib.stream_ptr()
         x = x.contiguous()
@@ -582,13 +571,9 @@ class GatedConvFn(torch.autograd.Function):
         entry = _packed_for(route, (wf, bf, wm, bm, gamma, beta, mean, var), identity_bn=bn_train)
         params, wp = entry.params, entry.fwd
         ctx.pack, ctx.route = entry, route
-        capturing = torch.cuda.is_current_stream_capturing()
-        # stride-2 layers: dgrad as four stride-1 dgrads, one per pixel parity (_poly_fragments) — not inside a captured step, whose
-        # retained backward graph is walked again after the weights have changed (the dilated / generic paths stay there)
-        ctx.method = method = dgrad_method(route, H, W, capturing)
-        # a captured step's backward (walked eagerly over the retained graph, on the capture's stream) keeps its weight gradients on
-        # that one stream: the side-stream hand-over is only exercised, and only verified, in the per-layer path
-        ctx.side = WGRAD_SIDE_STREAM and not capturing
+        # stride-2 layers: dgrad as four stride-1 dgrads, one per pixel parity (_poly_fragments)
+        ctx.method = method = dgrad_method(route, H, W)
+        ctx.side = WGRAD_SIDE_STREAM
         # the dgrad's fragments too, now: in the backward pass the wgrad kernels of the layers above fill the chip from their side
         # stream and a small packing launch between two dgrads waits 200 us for its turn (10 us here)
         if x.requires_grad:
@@ -627,10 +612,10 @@ class GatedConvFn(torch.autograd.Function):
         ctx.bn_train = bool(bn_train)
         ctx.bn_groups = groups
         ctx.arena = (arena, arena.reserve(8 * cout)) if arena is not None else None      # eval mode: sums + gradients; .train(): gradients
-        # the weights ride on the context, not in save_for_backward: a captured step's autograd graph is RETAINED and walked again
-        # after every optimizer step (_HybridStepFn) — saved tensors are version-checked, and the optimizer's in-place update of
-        # a parameter would read as "modified by an inplace operation"; a step's backward wants the weights of its own forward,
-        # which are the current ones
+        # the weights ride on the context, not in save_for_backward: the backward's dgrad reads the packed fragments, which hold the
+        # weights as they are when it runs (_PackPlan, assumption 2), and the generic dgrad reads wf / wm the same way.  Saved tensors
+        # are version-checked: a backward walked after an in-place update of a parameter (retain_graph across an optimizer step)
+        # would raise "modified by an inplace operation" for these two tensors alone
         ctx.weights = (wf_c, wm_c, gamma.detach() if bn_train else None, mean, var)      # mean / var: running buffers or batch statistics
         ctx.save_for_backward(x, fm, params)
         ctx.cfg = (k, stride, int(elu), H, W, cin, cout, Ho, Wo, bh, vh)
@@ -826,13 +811,11 @@ def unet_forward_train(net, x, x2, x4, x8, blk=(1, 1, 1)):
     """(h,w,8) NHWC pyramids -> (H,W,3); every tensor carries autograd history.  blk = (nb, v_num, v_den): the tensors hold
     nb items stacked vertically, v_num of every v_den rows of an item's block are valid (the rest: zero separator rows;
     ``stack_batch``).  Nearest resampling, concatenation, products and sums keep the separators zero by themselves."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    if PACK_BATCH and not capturing:
+    if PACK_BATCH:
         plan = _pack_plan(net, bool(net.training))         # every layer's parameter block and fragments: one launch
         if plan is not None:                               # None: a layout the batch packer does not take -> the per-layer packers
             plan.refresh()
-    # a captured step's autograd graph is walked again every step: its nodes must not share one zero-filled tensor across steps
-    net.__dict__['_grad_arena'] = None if capturing else _GradArena()
+    net.__dict__['_grad_arena'] = _GradArena()
     z2, z4, z8 = _scm(net, "SCM2", x2, blk), _scm(net, "SCM1", x4, blk), _scm(net, "SCM0", x8, blk)
     res1 = _res_blocks(net, "Encoder.0", _bc(net, "feat_extract.0", x, 3, blk=blk), blk)
     z = _bc(net, "feat_extract.1", res1, 3, stride=2, blk=blk)
@@ -877,197 +860,18 @@ def stack_batch(x_nchw, level):
     return x.reshape(-1, w, c).contiguous()
 
 
-# -----------------------------------------------------------------------------------------------------------------------
-# The training forward of the UNet from a HIP graph, its backward over the autograd graph of the capture
-# -----------------------------------------------------------------------------------------------------------------------
-# Round 3 read the training step as host-bound: 48 of 58 ms of host time inside the step's calls — 28 ms in the forward's 99 autograd
-# nodes, 15 ms walking them backward (bench.py host_phases_ms_per_step).  (Round 4's tools/train_host_probe.py showed most of that to
-# be time blocked on the full launch queue: the Python / launch path costs 17.5 ms per step at any crop size, the step is
-# device-bound.  The capture below stays as an option; it is not what made the step faster.)
-# The forward's launch sequence is the same every iteration — same shapes, same weights at the same addresses — so it is
-# captured ONCE per batch geometry into a HIP graph (hipGraph through torch.cuda.CUDAGraph) and replayed: one graph launch
-# (5 ms of host time) instead of ~600 Python-driven launches.  The capture runs the per-layer Python with autograd on, so it also
-# leaves the forward's autograd graph behind, its saved activations living in the HIP graph's memory pool; every replay rewrites
-# them in place, and the step's backward walks that SAME retained autograd graph (``torch.autograd.grad(..., retain_graph=True)``)
-# eagerly, on the capture's stream (weight gradients included: ctx.side is off for captured nodes).
-# Why not the backward from a graph as well (it was built first, with torch.cuda.make_graphed_callables, and measured,
-# profiles/README.md): a replayed hipGraph ran its branches back to back on this ROCm — kernel-trace overlap factor 1.06 against
-# 1.51 for the eager two-stream backward — so the step became GPU-bound at 63 ms instead of host-bound at 58.
-# Inside the forward graph: packing the weights' fragment orders (they change with every optimizer step), batch-statistics
-# BatchNorm with its running-buffer updates.  What the scheme cannot tolerate falls back to the per-layer path on its own: a second
-# forward before the first one's backward (the retained graph holds ONE set of activations), parameters moved to other addresses
-# (.cuda() / .to(): the key changes and a new graph is captured), hooks, anomaly mode, a failed capture.
-# Measured (profiles/README.md, round 4): the forward's host time falls from 28 to 1.3 ms, but the step does not get shorter —
-# 63 ms against 58: a step is ~1200 launches, the device spends ~8 us of gap on each however they are enqueued, and with the host
-# out of the way the device side is the bound.  So the capture is an OPTION (READ_AMD_GRAPH_TRAIN=1, read_amd.train.GRAPH_TRAIN),
-# not the default; what shortens the step is fewer launches (the pack plan above).
-GRAPH_TRAIN = os.environ.get("READ_AMD_GRAPH_TRAIN", "0") == "1"
-_GRAPH_CACHE_MAX = 4         # (geometry, mode) entries kept per net: an entry holds every activation of its step
-
-
-class _HybridStepFn(torch.autograd.Function):
-    """forward: copy the inputs into the capture's static buffers, replay the HIP graph; backward: the retained autograd graph."""
-
-    @staticmethod
-    def forward(ctx, step, n_in, *tensors):
-        for s_in, x in zip(step.static_in, tensors[:n_in]):
-            if s_in.data_ptr() != x.data_ptr():
-                s_in.data.copy_(x)                   # .data: no version bump on a tensor the retained graph may have saved
-        step.graph.replay()
-        step.generation += 1                         # the static activations now belong to THIS forward
-        ctx.step = step
-        ctx.generation = step.generation
-        ctx.n_tensors = len(tensors)
-        return step.out.detach()
-
-    @staticmethod
-    def backward(ctx, gout):
-        step = ctx.step
-        if ctx.generation != step.generation:
-            # a later forward has replayed the graph over the activations this backward would read (the `pending` latch was
-            # released because the parameters moved in between: a delayed backward after an optimizer step, load_state_dict
-            # or broadcast_parameters).  Eager autograd raises a version error here; returning gradients of the wrong
-            # activations silently would be worse.
-            raise RuntimeError("read_amd.train: backward of a captured forward whose buffers a later forward has replayed "
-                               f"(generation {ctx.generation}, now {step.generation}); run backward before the next forward, "
-                               "or set READ_AMD_GRAPH_TRAIN=0")
-        step.pending = False
-        grads = torch.autograd.grad([step.out], step.targets, [gout.contiguous()], retain_graph=True, allow_unused=True)
-        res = [None] * ctx.n_tensors
-        for slot, g in zip(step.target_slots, grads):
-            res[slot] = g
-        return (None, None, *res)
-
-
-_WARNED_PENDING = False
-
-
-class _GraphedStep:
-    def __init__(self, graph, static_in, out, params):
-        self.graph, self.static_in, self.out, self.params = graph, static_in, out, params
-        # gradient targets inside the retained graph: the static inputs that require grad, then the parameters — and where each
-        # one's gradient goes in _HybridStepFn's argument list (inputs first, parameters after them)
-        self.targets, self.target_slots = [], []
-        for i, t in enumerate(static_in):
-            if t.requires_grad:
-                self.targets.append(t)
-                self.target_slots.append(i)
-        for j, p_ in enumerate(params):
-            self.targets.append(p_)
-            self.target_slots.append(len(static_in) + j)
-        self.pending = False         # a forward whose backward has not run yet: its saved activations are still needed
-        self.pending_version = None  # ... and the parameter versions it saw (_graphed_step releases a stale latch)
-        self.generation = 0          # replays so far: a backward checks that its forward was the LAST one (_HybridStepFn.backward)
-
-    def __call__(self, xs):
-        self.pending = True
-        self.pending_version = tuple(p_._version for p_ in self.params)
-        return _HybridStepFn.apply(self, len(xs), *xs, *self.params)
-
-
-def _graph_key(net, xs, per_item):
-    ts = _net_tensors(net)
-    return (tuple(tuple(x.shape) for x in xs), tuple(bool(x.requires_grad) for x in xs), bool(net.training), bool(per_item),
-            hash(tuple(t.data_ptr() for t in ts)), hash(tuple(bool(t.requires_grad) for t in ts)))
-
-
-def _graphed_step(net, xs, per_item):
-    """-> the captured step for this geometry, or None (then the caller runs the per-layer path)."""
-    if not (GRAPH_TRAIN and torch.is_grad_enabled() and all(x.is_cuda and x.dtype == torch.float32 for x in xs)):
-        return None
-    if torch.cuda.is_current_stream_capturing() or torch.is_anomaly_enabled():
-        return None
-    if not any(p.requires_grad for p in net.parameters()) and not any(x.requires_grad for x in xs):
-        return None
-    if net._forward_hooks or net._backward_hooks or net._forward_pre_hooks:
-        return None
-    cache = net.__dict__.setdefault('_train_graphs', {})
-    key = _graph_key(net, xs, per_item)
-    g = cache.get(key)
-    if g is None:
-        if len(cache) >= _GRAPH_CACHE_MAX:
-            cache.pop(next(iter(cache)))
-        g = cache[key] = _capture_step(net, xs, per_item)
-    if g is False:
-        return None
-    if g.pending:
-        # A forward whose backward never ran (a validation pass under .train() with gradients on, an exception before backward())
-        # would latch `pending` for good.  Its saved activations can only still be wanted while the weights are the ones it saw:
-        # once an optimizer step has moved them, that forward's graph is spent — release the latch.
-        if tuple(p_._version for p_ in g.params) != g.pending_version:
-            g.pending = False
-        else:
-            global _WARNED_PENDING
-            if not _WARNED_PENDING:
-                _WARNED_PENDING = True
-                import warnings
-                warnings.warn("read_amd.train: a second forward before the first one's backward — this step runs on the per-layer "
-                              "path (READ_AMD_GRAPH_TRAIN=1 replays ONE step's buffers)")
-            return None                                  # a second forward before the first one's backward: that one keeps the buffers
-    return g
-
-
-def _capture_step(net, xs, per_item):
-    params = [p_ for p_ in net.parameters() if p_.requires_grad]
-    # the eager warm-up below would move the BatchNorm running buffers and num_batches_tracked in .train(): restored afterwards
-    # (the capture itself executes nothing)
-    saved = [b.detach().clone() for b in net.buffers()] if net.training else None
-    cur = torch.cuda.current_stream()
-    try:
-        static_in = [x.detach().clone().requires_grad_(x.requires_grad) for x in xs]
-        side = torch.cuda.Stream()
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):                        # warm-up: lazy initialisation, allocator, caches — off the capture
-            out = _unet_forward_train_batch_eager(net, static_in, per_item)
-            tg = [t for t in static_in if t.requires_grad] + params
-            if tg:
-                torch.autograd.grad([out], tg, [torch.ones_like(out)], allow_unused=True)
-            del out
-        cur.wait_stream(side)
-        torch.cuda.synchronize()
-        if saved is not None:
-            with torch.no_grad():
-                for b, v in zip(net.buffers(), saved):
-                    b.copy_(v)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):                        # autograd is on: the capture leaves the forward's autograd graph behind
-            out = _unet_forward_train_batch_eager(net, static_in, per_item)
-    except Exception as e:                                   # capture refused (an API the graph cannot hold, out of memory ...)
-        try:
-            torch.cuda.synchronize()
-        except Exception:
-            pass
-        if saved is not None:
-            with torch.no_grad():
-                for b, v in zip(net.buffers(), saved):
-                    b.copy_(v)
-        import warnings
-        warnings.warn(f"read_amd: HIP-graph capture of the UNet training forward failed ({type(e).__name__}: {e}); "
-                      "this geometry runs layer by layer")
-        return False
-    return _GraphedStep(graph, static_in, out, params)
+# bench.py is the reader of both: LAST_STEP_PATH after its timed steps, GRAPH_TRAIN (saved, cleared, restored) around its instrumented step
+GRAPH_TRAIN = False
+LAST_STEP_PATH = None
 
 
 def unet_forward_train_batch(net, xs, per_item_statistics=False):
     """xs: four (B,8,h,w) pyramids -> (B,3,H,W) through ONE stacked image.  In ``.train()`` the BatchNorm layers normalise with
     the statistics of the whole batch — ``nn.BatchNorm2d`` on a (B,C,h,w) tensor — unless ``per_item_statistics``: then every item
     is its own batch of one and the running buffers move B times in item order, which is what B separate calls of the net do
-    (``NetAndTexture.forward``, READ/models/compose.py:137-176).  The forward's launches come out of a HIP graph when the step
-    can be captured (``_graphed_step``; its backward then walks the capture's retained autograd graph), else from the per-layer
-    autograd nodes directly; ``LAST_STEP_PATH`` says which ('graph' / 'eager')."""
+    (``NetAndTexture.forward``, READ/models/compose.py:137-176)."""
     global LAST_STEP_PATH
-    g = _graphed_step(net, xs, per_item_statistics)
-    if g is not None:
-        LAST_STEP_PATH = 'graph'
-        return g(xs)
     LAST_STEP_PATH = 'eager'
-    return _unet_forward_train_batch_eager(net, xs, per_item_statistics)
-
-
-LAST_STEP_PATH = None
-
-
-def _unet_forward_train_batch_eager(net, xs, per_item_statistics=False):
     B, _, H, W = xs[0].shape
     if H % 16 or W % 16:
         raise ValueError(f"training crops must be multiples of 16, got {W}x{H}")

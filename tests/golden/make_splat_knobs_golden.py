@@ -12,7 +12,7 @@ import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-RETIRED = ["splat_zl2", "splat_kslot", "splat_items", "splat_compact"]
+RETIRED = ["splat_zl2", "splat_kslot", "splat_items", "splat_compact", "unet_streams"]
 VALUES = [-5, 0, 1, 3, 17, 300]
 
 

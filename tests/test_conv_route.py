@@ -102,7 +102,8 @@ def test_tuning_keys_and_normalisation_match_the_parent(rec):
     _defaults_guard()
     L = _lib.lib()
     keys = rc.tuning_keys(_lib)
-    assert keys == rec["tuning_keys"]
+    # the record was taken while "unet_streams" was a key; it is retired since (tests/test_splat_knobs.py holds it to "unknown key")
+    assert keys == [k for k in rec["tuning_keys"] if k != "unet_streams"]
     assert rec["knob_values"] == list(rc.KNOB_VALUES)
     table = rc.knob_table(_lib)
     assert table == rec["knobs"]

@@ -506,10 +506,10 @@ _METHOD = {"s1": "conv", "dilated": "dilated", "poly": "poly"}
 def _conv_dgrad(dfm_h, wf_h, wm_h, route, H, W, branch):
     """The three non-generic methods of read_amd.train.GatedConvFn.backward, driven with a chosen d[f|m] through the helper the backward
     pass itself calls (train._dgrad): "s1" stride 1, "dilated" 3x3 / stride 2 as the stride-1 dgrad of the zero-dilated d[f|m], "poly" one
-    3x3 / stride-1 dgrad per pixel parity.  The case names the method; the route function must offer it for this layer (under graph
-    capture for "dilated", which the polyphase method otherwise precedes).  -> dx (H, W, cin) on the host."""
+    3x3 / stride-1 dgrad per pixel parity.  The case names the method; the route function must offer it for this layer (with the
+    polyphase method switched off for "dilated", which it otherwise precedes).  -> dx (H, W, cin) on the host."""
     from read_amd import train
-    assert train.dgrad_method(route, H, W, capturing=branch == "dilated", polyphase=True) == _METHOD[branch], (branch, route)
+    assert train.dgrad_method(route, H, W, polyphase=branch != "dilated") == _METHOD[branch], (branch, route)
     dfm, wf, wm = _dev(dfm_h), _dev(wf_h), _dev(wm_h)
     dx = torch.full((H, W, route.cin), 7.0, device="cuda")
     assert train._dgrad(_METHOD[branch], route, dfm, H, W, wf, wm, out=dx) is dx

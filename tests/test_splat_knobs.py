@@ -1,6 +1,6 @@
 """CPU: the tuning keys answer as the recorded library did (tests/golden/splat_knobs.json, written by
 tests/golden/make_splat_knobs_golden.py): the order read_tuning_key enumerates them in, every default, and for each of a few
-values what read_tuning_set returns and what read_tuning_get then reads back.  The retired rasteriser options are unknown keys."""
+values what read_tuning_set returns and what read_tuning_get then reads back.  The retired options are unknown keys."""
 import ctypes as C
 import json
 import os
@@ -46,10 +46,10 @@ def test_tuning_keys_answer_as_recorded():
     assert _lib.tuning_state() == defaults
 
 
-def test_retired_rasteriser_options_are_unknown_keys():
+def test_retired_options_are_unknown_keys():
     rec = json.load(open(GOLDEN))
     L, v = _lib.lib(), C.c_int(0)
-    assert sorted(rec["retired"]) == ["splat_compact", "splat_items", "splat_kslot", "splat_zl2"]
+    assert sorted(rec["retired"]) == ["splat_compact", "splat_items", "splat_kslot", "splat_zl2", "unet_streams"]
     keys = _enumerate(L)
     for key in rec["retired"]:
         assert key not in keys

@@ -64,7 +64,6 @@ def test_route_table(monkeypatch):
     assert all(r.fwd_kc == (16 if r.cin % 16 == 0 else 8) and r.dgrad_kc == 16 for r in routes)
     monkeypatch.setattr(T, "POLYPHASE_DGRAD", True)
     assert _counts(routes) == {'conv': 93, 'poly': 6}
-    assert _counts(routes, capturing=True) == {'conv': 93, 'dilated': 3, 'generic': 3}
     assert _counts(routes, polyphase=False) == {'conv': 93, 'dilated': 3, 'generic': 3}
     monkeypatch.setattr(T, "POLYPHASE_DGRAD", False)
     assert _counts(routes) == {'conv': 93, 'dilated': 3, 'generic': 3}
@@ -96,6 +95,16 @@ def test_route_table(monkeypatch):
     assert _counts(off) == {'conv': 93, 'dilated': 3, 'generic': 3}
     monkeypatch.setattr(T, "USE_WINOGRAD", True)
     assert [T.layer_route(*l) for l in layers] == routes
+
+
+def test_training_nodes_refuse_to_be_captured(monkeypatch):
+    """GatedConvFn.forward is the door of every training path: under a stream capture it raises before any tensor or library call
+    (a replayed node would run on the packed weights of the capture step)."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    x, w, v = torch.zeros(4, 4, 8), torch.zeros(8, 8, 3, 3), torch.zeros(8)
+    with pytest.raises(RuntimeError, match="cannot be captured"):
+        T.GatedConvFn.apply(x, w, v, w, v, v, v, v, v, 3, 1, True)
 
 
 # ---- argument checks: (entry point, arguments with P = any non-null pointer) that must come back READ_EINVAL before any launch

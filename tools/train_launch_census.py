@@ -13,13 +13,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from read_amd import train as T  # noqa: E402
 
 sys.argv = ["bench.py", "--config", "train", "--no-cpu-baseline", "--steps", "3"]
 a = bench.parse()
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
-T.GRAPH_TRAIN = False
 
 
 def census(step):

@@ -1,4 +1,4 @@
-"""The UNet plan (105 launches, side streams for the SCM chains) replayed from a HIP graph against the eager enqueue, one frame at a
+"""The UNet plan (105 launches, all on the caller's stream) replayed from a HIP graph against the eager enqueue, one frame at a
 time on one stream (run on the GPU box): ms per frame, and the two outputs compared."""
 import os
 import sys
