@@ -594,10 +594,12 @@ int read_gated_conv_forward(const read_conv_desc *desc, void *stream);
  * = Cin * 18 * 2 * pad32(Cout) + 2 * pad32(Cout) floats (half the F(4x4) order), 0 unless Cin % 32 == 0; order
  * [group][wave 4][chunk of 32 cin][ky 3][frequency 6][Uh | Ul][lane][8 halfs], then 2 * pad32(Cout) floats 1 / s.
  * read_gated_conv_forward_f4x1 is read_gated_conv_forward with that operand (device) beside the descriptor, which is frozen at ABI
- * version 3: a family-5 launch with Cin >= read_tuning("conv_f4x1") (default 32; 0 = never), or config = -12 / -13, runs on the
- * F(4,3)-by-rows kernel; every other launch is unchanged.  The kernel has two forms with the same results, bit for bit: one workgroup
- * per CU (config = -12) and two resident workgroups per CU (config = -13, accepted and refused exactly where -12 is); the automatic
- * choice takes the form that measured faster for the launch's shape (profiles/f4x1_pair_ab.md).  desc.wpacked_w4h may stay NULL when only this order was packed: a launch
+ * version 3: a family-5 launch with Cin >= read_tuning("conv_f4x1") (default 32; 0 = never), or config = -12 / -13 / -14, runs on the
+ * F(4,3)-by-rows kernel; every other launch is unchanged.  The kernel has three forms with the same results, bit for bit: one workgroup
+ * per CU (config = -12), two resident workgroups per CU (config = -13, accepted and refused exactly where -12 is) and one eight-wave
+ * workgroup per CU that shares the input transform between two channel groups (config = -14, accepted where -12 is and
+ * Cout % 64 == 0, refused by name otherwise); the automatic choice takes the form that measured faster for the launch's shape
+ * (profiles/f4x1_pair_ab.md, profiles/f4x1_wide_ab.md).  desc.wpacked_w4h may stay NULL when only this order was packed: a launch
  * that would then need the F(4x4) order is refused with READ_EINVAL.  The input transform amplifies by at most 10 (F(4x4): 100), so
  * the f16 pieces cover activations up to about 6500. */
 size_t read_conv_f4x1_floats(int Cin, int Cout);

@@ -2846,6 +2846,280 @@ __global__ __launch_bounds__(256, 2) void f4x1_pair_conv_kernel(const ConvKArgs 
 }
 
 // ------------------------------------------------------------------------------------------
+// The F(4,3)-by-rows kernel for TWO CHANNEL GROUPS on one input transform (config -14).
+//
+// Why: a unit of the two kernels above is (8 x 32 pixels) x (32 output channels), so the C / 32 groups of a layer each load the same
+// 10 x 34 x 32 patch per chunk, run the same bt6 pass, make the same hi / lo splits and write the same V image: 2x the transform at
+// C = 64, 4x at C = 128, 8x at C = 256.  Here a unit is (8 x 32 pixels) x (the group pair 2 p, 2 p + 1) and one workgroup of EIGHT waves
+// carries it: per MFMA half the transform, patch loads, V stores and barriers; the weight stream and the V reads per MFMA are unchanged.
+//   * wave w = (gh = w >> 2, wv = w & 3) is wave wv of group 2 p + gh: same weights (F4x1Geom::w_base), same fragments, same (fq, ky)
+//     order, same V reads, epar per group — the operand needs no repacking;
+//   * ONE V image for the eight waves.  The 20 wave-items of a chunk (10 patch rows x 2 segment halves) are spread so that every SIMD
+//     still carries five: wave (gh, wv) takes the row parity and segment half of wv as above, items i = 0, 1, 2 for gh = 0 and i = 3, 4
+//     for gh = 1; values, swizzle and split are the shared blocks, so V holds the bits of the kernels above;
+//   * at most three items per thread = 36 patch registers instead of 60, which is what lets the first kernel's schedule back in under
+//     256 registers: V double-buffered, the transform of chunk + 1 beside the MFMAs of chunk (21 steps for gh = 0, 14 for gh = 1), the
+//     patch of chunk + 2 loaded into the registers the transform frees;
+//   * what it takes from the pair kernel, for the registers' sake: the weight ring of two frequencies fetched one frequency ahead
+//     (here across the chunk's and the unit's end as well), one fragment of 2^-11 Uh, one stage instance with the accumulators cleared
+//     in the accumulation file, the epilogue one block at a time.
+// Per accumulator the MFMAs come in the order of the kernels above (chunk, tap as the row pairs arrive, piece pair 0..2): the output
+// equals theirs bit for bit (tests/test_gpu_conv_f4x1_wide.py).  The host passes the WIDE unit count (blocks x groups / 2) and a grid
+// that is a multiple of groups / 2, so step_tile and cursor_advance walk it unchanged.
+// The symbol deliberately does not match gated_conv_*kernel: tests/test_isa_guards.py counts the kernels of that pattern.
+__global__ __launch_bounds__(512, 1) void f4x1_wide_conv_kernel(const ConvKArgs a)
+{
+    using WG = F4x1Geom;
+    __shared__ __attribute__((aligned(16))) unsigned lds[WG::LDS_DWORDS];                    // two V images: 122,880 bytes
+    __shared__ __attribute__((aligned(16))) float epar[2][6][32];  // per group of the pair: b_f, -log2e b_m, BN scale, BN shift, 1 / s_f, -log2e / s_m
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6), gh = w8 >> 2, wv = w8 & 3;
+    const SrcDev s = a.src[0];
+    const int pairs = a.CoutPad >> 6, G = gridDim.x;
+    const int g = 2 * (blockIdx.x % pairs) + gh;               // this wave's channel group
+    const int n = a.nchunks;                                   // 32-channel chunks
+
+    int by = (blockIdx.x / pairs) / a.tiles_x, bx = (blockIdx.x / pairs) % a.tiles_x;        // running unit (8 x 32 pixel block)
+    int pby = by, pbx = bx, pu = blockIdx.x, pchunk = 0;                                     // prefetch cursor (raw patches)
+
+    // ---- transform role: thread = (segment sg, channel pair cp) of patch rows 2 i + (wv >> 1), i = 3 gh + ii, ii = 0 .. 2 (gh = 1 has
+    // no third item: every use of it is behind a wave-uniform test)
+    const int cp = lane & 15, sg = (wv & 1) * 4 + (lane >> 4);
+    const bool third = gh == 0;
+    constexpr unsigned OOR = 0x80000000u;
+    unsigned xoff[6];
+    int rowoff[3];
+    bool rowok[3];
+    const unsigned src_bytes = (unsigned)(a.inH * s.W * s.C) * 4u;
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s.p), 0, src_bytes, 0x00020000);
+    const auto rsrc_none = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(s.p), 0, 0, 0x00020000);      // a row outside the image: zeros
+    auto set_patch = [&]() {
+        // the lane number once more, opaque to the compiler (see the pair kernel's epilogue): segment and channel pair are needed here
+        // once per unit and would otherwise sit in two vector registers across the stages
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int cp = ln & 15, sg = (wv & 1) * 4 + (ln >> 4);
+        const int y0 = pby * 8 - 1 + (wv >> 1) + 6 * gh, x0 = pbx * 32 + 4 * sg - 1;
+#pragma unroll
+        for (int ii = 0; ii < 3; ++ii) {
+            const int yy = y0 + 2 * ii;
+            rowok[ii] = (unsigned)yy < (unsigned)a.inH;
+            const int yc = yy < 0 ? 0 : yy >= a.inH ? a.inH - 1 : yy;
+            rowoff[ii] = yc * s.W * s.C * 4;
+        }
+#pragma unroll
+        for (int c = 0; c < 6; ++c) xoff[c] = (unsigned)(x0 + c) < (unsigned)a.inW ? (unsigned)((x0 + c) * s.C + 2 * cp) * 4u : OOR;
+    };
+    auto advance = [&]() {
+        if (cursor_advance(a, n, G, pchunk, pu, pby, pbx)) set_patch();
+    };
+    f32x2 d2[3][6];                                            // the row segments of the chunk under transform: (channel 2 cp, 2 cp + 1)
+    auto gload = [&](int ii, int c) {
+        d2[ii][c] = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(rowok[ii] ? rsrc : rsrc_none, xoff[c], rowoff[ii] + pchunk * 128, 0));
+    };
+    const int vwoff = WG::v_store_off(wv, sg, cp) + 6 * gh * WG::VROW;         // (+ buffer)
+    auto split_store = [&](const f32x2 x, int vb, int ii, int fq) {
+        unsigned hi, lo;
+        split_hl(x.x, x.y, hi, lo);
+        lds[vwoff + vb + 2 * ii * WG::VROW + fq * WG::VFREQ] = hi;
+        lds[vwoff + vb + 2 * ii * WG::VROW + fq * WG::VFREQ + 128] = lo;
+    };
+    // step j of item ii's transform, seven per item: the 1-D pass, then six frequencies (split + store); t_load refills the item's
+    // registers with the patch of the chunk after
+    auto t_step = [&](int vb, int ii, int j) {
+        if (ii == 2 && !third) return;
+        if (j == 0) bt6(d2[ii][0], d2[ii][1], d2[ii][2], d2[ii][3], d2[ii][4], d2[ii][5]);
+        else split_store(d2[ii][j - 1], vb, ii, j - 1);
+    };
+    auto t_load = [&](int ii) {
+        if (ii == 2 && !third) return;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) gload(ii, c);
+    };
+
+    // ---- A operand (weights): fragment (chunk, ky, fq), consumed in the order (fq, ky); ring of two frequencies, one frequency ahead
+    const auto wrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(WG::w_base(a, g, wv, n)), 0, (unsigned)n * WG::W_BYTES, 0x00020000);
+    const unsigned wvoff = lane * 16;
+    constexpr int RW = 6;
+    u32x4 Wh[RW], Wl[RW];
+    f16x8 Ws;                                                  // 2^-11 Uh of the (block, tap) pair that comes next
+    auto wload = [&](int chunk, int fq, int ky) {
+        const int slot = (fq & 1) * 3 + ky;
+        Wh[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, WG::w_frag(chunk, fq, ky), 0);
+        Wl[slot] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, wvoff, WG::w_frag(chunk, fq, ky) + 1024, 0);
+    };
+    auto wscale = [&](int fq, int ky) {
+        const _Float16 k = (_Float16)0x1p-11f;
+        Ws = __builtin_bit_cast(f16x8, Wh[(fq & 1) * 3 + ky]) * f16x8{k, k, k, k, k, k, k, k};
+    };
+    // ---- B operand: row pair s (rows s, s + 1) of frequency fq; ring of two, fetched one pair ahead (a third pair costs eight registers
+    // that this kernel does not have: with it the compiler spills to scratch; the SIMD's other wave covers the shorter lead)
+    const int t16 = lane & 15, kl = lane >> 4;
+    const int vrd_e = WG::v_read_off(t16, kl, 0), vrd_o = WG::v_read_off(t16, kl, 1);
+    constexpr int RB = 2, BA = RB - 1;
+    u32x4 Bh[RB], Bl[RB];
+    auto bload = [&](int vb, int idx) {                        // idx = fq * 9 + s
+        const int fq = idx / 9, sp = idx % 9;
+        const int o = vb + sp * WG::VROW + fq * WG::VFREQ + ((sp & 1) ? vrd_o : vrd_e);
+        Bh[idx % RB] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + o, 16));
+        Bl[idx % RB] = *reinterpret_cast<const u32x4 *>(__builtin_assume_aligned(lds + o + 128, 16));
+    };
+
+    f32x4 acc[4][6];
+    const auto out_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (unsigned)(a.outH * a.outW * a.out_cstride) * 4u, 0x00020000);
+    const auto res_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.residual ? a.residual : a.out), 0,
+                                                            (unsigned)(a.outH * a.outW * a.Cout) * 4u, 0x00020000);
+    epar_load(epar[gh], a, WG::row_scales(a, n), g, tid & 255);                // each half of the workgroup loads its group's parameters once
+
+    // ---- prologue: patch(0) -> registers -> V(0); patch(1) -> registers; the first weight fragments and B operands
+    set_patch();
+#pragma unroll
+    for (int ii = 0; ii < 3; ++ii) t_load(ii);
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) wload(0, 0, ky);
+    advance();
+#pragma unroll
+    for (int ii = 0; ii < 3; ++ii) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) t_step(0, ii, j);
+        t_load(ii);
+    }
+    advance();
+    wscale(0, 0);
+    __syncthreads();
+    bload(0, 0);
+
+    int v_cur = 0, v_nxt = WG::VBUF;
+
+    // One stage = one 32-channel chunk: 216 MFMAs (6 frequencies x 12 (block, tap) pairs x 3 piece pairs) in the order of the kernels
+    // above; beside them the transform of chunk + 1 (registers -> v_nxt) and the loads of patch(chunk + 2) into the registers the
+    // transform leaves behind.  Item ii is transformed beside frequency ii: its 1-D pass at slot 2, where the ring's other half is
+    // still empty (the pass needs ~30 registers for a moment), a split store every fourth slot behind it; its registers are
+    // refilled beside frequency 3 + ii, three frequencies before they are read.
+    auto stage_body = [&](int chunk) {
+        int nchunk = chunk + 1;                                       // wraps into the next unit (same weights)
+        nchunk = nchunk == n ? 0 : nchunk;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int fq = 0; fq < 6; ++fq)
+#pragma unroll
+            for (int sp = 0; sp < 9; ++sp)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const int nb = WG::pair_nb(sp, q), ky = WG::pair_ky(sp, q);    // the (block, tap) pairs that read row pair sp
+                    if (!WG::pair_live(sp, q)) continue;
+#pragma unroll
+                    for (int pc = 0; pc < 3; ++pc) {
+                        const int mb = WG::slot_first(sp), ms = WG::slot(sp, q, pc), idx = fq * 9 + sp;
+                        if (ms == mb) {
+                            // B operands one row pair ahead.  Before the first one of the next chunk: V(chunk + 1) is complete in
+                            // every wave (last store beside frequency 2) and every wave has fetched its last B operand of this chunk
+                            if (idx == 54 - BA) __syncthreads();
+                            if (idx + BA < 54) bload(v_cur, idx + BA);
+                            else bload(v_nxt, idx + BA - 54);
+                        }
+                        const int ws = (fq & 1) * 3 + ky;
+                        const f16x8 av = pc == 0 ? Ws : __builtin_bit_cast(f16x8, pc == 1 ? Wl[ws] : Wh[ws]);
+                        const f16x8 bv = __builtin_bit_cast(f16x8, pc == 0 ? Bl[idx % RB] : Bh[idx % RB]);
+                        acc[nb][fq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, bv, acc[nb][fq], 0, 0, 0);
+                        // ---- shadow items
+                        if (ms == 5 || ms == 11 || ms == 17) {                           // weights one frequency ahead
+                            if (fq < 5) wload(chunk, fq + 1, (ms - 5) / 6);
+                            else wload(nchunk, 0, (ms - 5) / 6);
+                        }
+                        if (pc == 1) {                                                   // 2^-11 Uh of the next pair: the taps come in the order 0 1 2 0 1 2 ...
+                            if (ms < 33) wscale(fq, (ms / 3 + 1) % 3);
+                            else wscale((fq + 1) % 6, 0);
+                        }
+                        if (fq < 3 && (ms & 3) == 2 && ms < 28) t_step(v_nxt, fq, ms >> 2);
+                        if (fq >= 3 && ms == 20) t_load(fq - 3);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+        advance();
+        const int v = v_cur;
+        v_cur = v_nxt;
+        v_nxt = v;
+    };
+
+    for (int u = blockIdx.x; u < a.n_units; u += G) {
+        // cleared where they live, in the accumulation file (see the pair kernel)
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+            for (int fq = 0; fq < 6; ++fq) asm volatile("v_accvgpr_write_b32 %0, 0\n\tv_accvgpr_write_b32 %1, 0\n\tv_accvgpr_write_b32 %2, 0\n\tv_accvgpr_write_b32 %3, 0"
+                                                        : "=a"(acc[nb][fq][0]), "=a"(acc[nb][fq][1]), "=a"(acc[nb][fq][2]), "=a"(acc[nb][fq][3]));
+        for (int chunk = 0; chunk < n; ++chunk) stage_body(chunk);
+
+        // ================= unit epilogue: the pair kernel's, one block of accumulators at a time =================
+        // (the patch of the next unit's second chunk, its first weight fragments and B operands stay live across it)
+        int ln;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));      // opaque lane number: see the pair kernel
+        const int e16 = ln & 15, cq = (ln >> 4) & 1, hf = ln >> 5;
+        const int c0 = g * 32 + wv * 8 + 4 * cq;
+        const int oy = by * 8 + 4 * hf + (e16 >> 3), ox = bx * 32 + 4 * (e16 & 7);           // this lane finishes rows oy, oy + 2
+        const int cl = wv * 8 + 4 * cq;
+        const auto [bf, bml, sc, sh, isf, ism] = epar_read(epar[gh], cl);
+        constexpr float LOG2E = 1.44269504088896341f;
+        asm volatile("s_nop 15\n\ts_nop 3");                            // the last MFMA's result, read below through an asm the hazard checker does not see
+#pragma unroll
+        for (int py = 0; py < 2; ++py) {
+            unsigned rvoff[4], ovoff[4];
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                const bool in = (oy + 2 * py < a.outH) & (ox + px < a.outW) & (c0 < a.Cout);
+                const int pix = (oy + 2 * py) * a.outW + ox + px;
+                rvoff[px] = in ? (unsigned)((pix * a.Cout + c0) * 4) : OOR;
+                ovoff[px] = in ? (unsigned)((pix * a.out_cstride + c0) * 4) : OOR;
+            }
+            f32x4 rv[4];
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                rv[px] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (a.residual) rv[px] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, rvoff[px], 0, 0));
+            }
+            f32x4 Y[2][4];                                             // blocks py and py + 2: [block][pixel of the tile]
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                f32x4 m[6];
+#pragma unroll
+                for (int fq = 0; fq < 6; ++fq)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(m[fq][k]) : "a"(acc[py + 2 * h][fq][k]));
+                at6(m, Y[h]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int px = 0; px < 4; ++px) {
+                f32x4 yf, ym;
+                fm_swap(Y[0][px], Y[1][px], yf, ym);
+                f32x4 f = __builtin_elementwise_fma(yf, isf, bf);
+                const f32x4 mm = __builtin_elementwise_fma(ym, ism, bml);
+                if (a.elu) {
+                    const f32x4 fe = f * LOG2E;
+                    f32x4 e;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) e[k] = __builtin_amdgcn_exp2f(fe[k]);
+                    e = e + f32x4{-1.0f, -1.0f, -1.0f, -1.0f};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) f[k] = f[k] > 0.0f ? f[k] : e[k];
+                }
+                f32x4 sg_, t;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) t[k] = __builtin_amdgcn_exp2f(mm[k]);
+                t = t + f32x4{1.0f, 1.0f, 1.0f, 1.0f};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sg_[k] = __builtin_amdgcn_rcpf(t[k]);
+                const f32x4 v = (f * sg_) * sc + sh + rv[px];
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), out_rsrc, ovoff[px], 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        step_tile(a, by, bx);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // DIRECT 3x3 / stride-1 gated convolution with split fp32 operands on the f16 matrix cores (round 6, second kernel of the round).
 //
 // Why: the attribution of the split-operand Winograd kernel above (profiles/r6_w4h_ablation.md) — its MFMAs are a fifth of its launch,
@@ -4129,7 +4403,7 @@ int find_config(int ks, int s, int kc, int P, int QG, int WM, int WN, int PF, in
 }
 
 // read_conv_desc.config below zero: the automatic choice, or a request for one kernel.  CFG_SC, CFG_PX, CFG_PXH, CFG_T3H and
-// CFG_F4X1 / CFG_F4X1_PAIR are refused where the kernel cannot run the launch; the others fall back to the automatic choice.
+// CFG_F4X1 / CFG_F4X1_PAIR / CFG_F4X1_WIDE are refused where the kernel cannot run the launch; the others fall back to the automatic choice.
 enum ConvForce {
     CFG_AUTO = -1,
     CFG_PX = -2,         // fp32 pixel-lane kernel (1x1)
@@ -4143,6 +4417,7 @@ enum ConvForce {
     CFG_T3H = -11,       // ... as an implicit GEMM over a 3x3 layer with 8 - 32 input channels
     CFG_F4X1 = -12,      // split-operand F(4,3) by rows, one workgroup per CU (gated_conv_f4x1h_kernel)
     CFG_F4X1_PAIR = -13, // ... two resident workgroups per CU (f4x1_pair_conv_kernel): accepted exactly where -12 is
+    CFG_F4X1_WIDE = -14, // ... one eight-wave workgroup per CU and two channel groups per unit (f4x1_wide_conv_kernel): accepted where -12 is and Cout % 64 == 0
 };
 
 // Tuning knobs (the table g_knobs further down: key, normalisation)
@@ -4354,7 +4629,7 @@ static int conv_uses_w4h(const read_conv_desc *d)
     // (FAM's x1 * x2 stays on the fp32 kernel: the second patch costs the transform thread another 72 registers, and the
     //  variant with a shallower weight ring measured SLOWER than the fp32 kernel — 101 / 79 / 68 us against 77 / 69 / 64 at C = 64 / 128 / 256)
     if (!d->wpacked_w4h || d->linear || d->mul || d->src[0].C % 32 != 0 || d->Cout % 32 != 0) return 0;
-    const bool forced = d->config == CFG_W4H || d->config == CFG_F4X1 || d->config == CFG_F4X1_PAIR;    // the F(4,3)-by-rows kernels belong to the same family
+    const bool forced = d->config == CFG_W4H || d->config == CFG_F4X1 || d->config == CFG_F4X1_PAIR || d->config == CFG_F4X1_WIDE;    // the F(4,3)-by-rows kernels belong to the same family
     if (!forced && (d->config != CFG_AUTO || g_w4h <= 0 || d->src[0].C < g_w4h)) return 0;
     return conv_w4_shape(d, d->wpacked_w4h, !forced);
 }
@@ -4473,7 +4748,7 @@ static ConvShape conv_shape(const read_conv_desc *d)
     return s;
 }
 
-enum ConvKernel { CK_SC, CK_T3H, CK_PXH, CK_PX, CK_D3H_S2, CK_D3H, CK_F4X1, CK_F4X1_PAIR, CK_W4H, CK_W4, CK_TABLE };
+enum ConvKernel { CK_SC, CK_T3H, CK_PXH, CK_PX, CK_D3H_S2, CK_D3H, CK_F4X1, CK_F4X1_PAIR, CK_F4X1_WIDE, CK_W4H, CK_W4, CK_TABLE };
 
 struct ConvRoute {
     ConvKernel kernel;
@@ -4496,6 +4771,21 @@ static int w4_units(const ConvShape &s) { return ceil_div(s.outW, 32) * ceil_div
 //   * Cin = 64 (two chunks, 836 units) gained 0.3 - 1.3 us, inside the spread: it stays; widths in between were not measured and stay too.
 static bool f4x1_pair_auto(int Cin, int n_units, int n_cu) { return n_units > n_cu && (Cin == 32 || Cin == 128); }
 
+// Which automatic F(4,3)-by-rows launches with Cout % 64 == 0 run as one eight-wave workgroup per CU on two channel groups
+// (f4x1_wide_conv_kernel); the results are the same bits.  n_units: the 32-channel units, as above; the wide kernel walks half as many.
+// A level enters only if it passes both marks: kernel alone (profiles/f4x1_wide_ab.md, 1216 x 352, alternated in one process with the
+// level's current kernel: the slowest wide cell under the fastest current cell, the gain above the current kernel's spread) and the
+// headline (profiles/f4x1_wide_bench.md: every run above every parent run, gain >= 3 x the parent's spread, latency mode not below).
+//   * Cin = 64 (418 wide units, two chunks): 44.8 -> 37.3 us per launch against config -12; enters;
+//   * Cin = 128 (220 wide units, four chunks): 38.4 -> 33.1 us against config -13; enters.  Both together: 321.9 -> 328.9 frames/s
+//     with two frames in flight, 265.9 -> 277.1 in latency mode;
+//   * Cin = 256 (120 wide units on 256 CUs): 38.9 -> 47.5 us alone — a CU carries twice the MFMAs of a unit and half the CUs idle.
+//     With two frames in flight the other frame takes the idle half (328.9 -> 334.7 frames/s), in latency mode nothing does
+//     (265.9 -> 259.8, below the parent): it stays, the predicate does not know the mode;
+//   * 5 n_units >= 8 n_cu: at least 0.8 wide units per CU (measured at 0.86 and 1.63, refused at 0.47); smaller images and widths in
+//     between were not measured and stay.
+static bool f4x1_wide_auto(int Cin, int n_units, int n_cu) { return (Cin == 64 || Cin == 128) && 5 * n_units >= 8 * n_cu; }
+
 // Precedence = the order of the tests.  wp_f4x1: the F(4,3)-by-rows operand that travels beside the descriptor, or NULL.
 static ConvRoute conv_route(const read_conv_desc *d, const void *wp_f4x1)
 {
@@ -4510,11 +4800,16 @@ static ConvRoute conv_route(const read_conv_desc *d, const void *wp_f4x1)
     // caller without its operand (a blob packed before the kernel existed) keeps running on the F(4x4) kernel
     // ... and of those the automatic choice sends the shapes of f4x1_pair_auto to the two-workgroups-per-CU form of the kernel (same bits)
     else if (conv_uses_w4h(d)) {
-        const bool forced = d->config == CFG_F4X1 || d->config == CFG_F4X1_PAIR;
+        // ... and the shapes of f4x1_wide_auto, tested first, to the two-groups-per-unit form (same bits); config -14 with Cout % 64 != 0
+        // has no kernel: it stays off the F(4,3)-by-rows route and its launcher refuses it by name
+        const bool wide_fits = d->Cout % 64 == 0;
+        const bool forced = d->config == CFG_F4X1 || d->config == CFG_F4X1_PAIR || (d->config == CFG_F4X1_WIDE && wide_fits);
         const bool f4x1 = wp_f4x1 && (forced || (d->config == CFG_AUTO && g_f4x1 > 0 && d->src[0].C >= g_f4x1));
-        const bool pair = f4x1 && (d->config == CFG_F4X1_PAIR ||
+        const bool wide = f4x1 && wide_fits && (d->config == CFG_F4X1_WIDE ||
+                                   (d->config == CFG_AUTO && f4x1_wide_auto(d->src[0].C, w4_units(conv_shape(d)), device_cus())));
+        const bool pair = f4x1 && !wide && (d->config == CFG_F4X1_PAIR ||
                                    (d->config == CFG_AUTO && f4x1_pair_auto(d->src[0].C, w4_units(conv_shape(d)), device_cus())));
-        r.kernel = !f4x1 ? CK_W4H : pair ? CK_F4X1_PAIR : CK_F4X1;
+        r.kernel = !f4x1 ? CK_W4H : wide ? CK_F4X1_WIDE : pair ? CK_F4X1_PAIR : CK_F4X1;
     }
     else if (conv_uses_w4(d)) r.kernel = CK_W4;
     else if (conv_sane(d)) {
@@ -4545,7 +4840,7 @@ static ConvRoute conv_route(const read_conv_desc *d, const void *wp_f4x1)
 static int route_family(const ConvRoute &r)
 {
     static const int family[] = {/* CK_SC */ 1, /* CK_T3H */ 8, /* CK_PXH */ 7, /* CK_PX */ 0, /* CK_D3H_S2 */ 6, /* CK_D3H */ 6,
-                                 /* CK_F4X1 */ 5, /* CK_F4X1_PAIR */ 5, /* CK_W4H */ 5, /* CK_W4 */ 4, /* CK_TABLE */ 0};
+                                 /* CK_F4X1 */ 5, /* CK_F4X1_PAIR */ 5, /* CK_F4X1_WIDE */ 5, /* CK_W4H */ 5, /* CK_W4 */ 4, /* CK_TABLE */ 0};
     return r.wino_auto ? 2 : family[r.kernel];
 }
 
@@ -4763,6 +5058,8 @@ static int refuse_f4x1_config(const read_conv_desc *d, bool f4x1)
                    "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
     READ_CHECK_ARG(d->config != CFG_F4X1_PAIR || f4x1, "read_gated_conv_forward: config -13 takes the launches of the split-operand 3x3/s1 family "
                    "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
+    READ_CHECK_ARG(d->config != CFG_F4X1_WIDE || f4x1, "read_gated_conv_forward: config -14 takes the launches of the split-operand 3x3/s1 family "
+                   "and needs the F(4,3)-by-rows operand (read_gated_conv_forward_f4x1)");
     return READ_OK;
 }
 
@@ -4800,7 +5097,7 @@ static int launch_d3h_s2(const read_conv_desc *d, ConvKArgs &a, const ConvShape 
 // F(4x4,3x3) in fp32 (CK_W4) or with split operands (CK_W4H), F(4,3) by rows (CK_F4X1), the direct split-operand kernel (CK_D3H)
 static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvShape &s, ConvKernel kernel, const void *wp_f4x1, hipStream_t stream)
 {
-    const bool d3h = kernel == CK_D3H, pair = kernel == CK_F4X1_PAIR, f4x1 = pair || kernel == CK_F4X1, w4h = f4x1 || kernel == CK_W4H;
+    const bool d3h = kernel == CK_D3H, pair = kernel == CK_F4X1_PAIR, wide = kernel == CK_F4X1_WIDE, f4x1 = pair || wide || kernel == CK_F4X1, w4h = f4x1 || kernel == CK_W4H;
     int rc = take_out_gated(d, kernel == CK_W4, a);
     if (rc != READ_OK) return rc;
     rc = refuse_f4x1_config(d, f4x1);
@@ -4816,8 +5113,10 @@ static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvSha
     READ_CHECK_ARG(!f4x1 || (uintptr_t)wp_f4x1 % 16 == 0, "read_gated_conv_forward: wpacked_f4x1 misaligned");
     a.nchunks = (w4h || d3h) ? s.Cin / 32 : s.Cin / s.kc;
     a.tiles_x = ceil_div(s.outW, 32);
-    a.n_units = w4_units(s);
-    const int n_cu = (pair ? 2 : 1) * device_cus(), groups = s.groups;      // resident workgroups: the pair kernel has two per CU
+    // resident workgroups: the pair kernel has two per CU; the wide kernel's units carry two channel groups, so its unit count and the
+    // multiple its grid keeps are those of groups / 2
+    const int n_cu = (pair ? 2 : 1) * device_cus(), groups = wide ? s.groups / 2 : s.groups;
+    a.n_units = wide ? w4_units(s) / 2 : w4_units(s);
     int cap = n_cu;
     if (g_w4_grid) {                                               // A/B: every workgroup the same number of units
         const int whole = n_cu - n_cu % groups > 0 ? n_cu - n_cu % groups : groups;
@@ -4831,7 +5130,10 @@ static int launch_w4_family(const read_conv_desc *d, ConvKArgs &a, const ConvSha
         fn = d->mul ? gated_conv_d3h_kernel<true> : gated_conv_d3h_kernel<false>;
         threads = 512;
     } else if (pair) fn = f4x1_pair_conv_kernel;
-    else if (f4x1) fn = gated_conv_f4x1h_kernel;
+    else if (wide) {
+        fn = f4x1_wide_conv_kernel;
+        threads = 512;
+    } else if (f4x1) fn = gated_conv_f4x1h_kernel;
     else if (w4h) fn = gated_conv_wino4h_kernel;
     READ_CHECK_ARG(!d->linear || !d->mul, "read_gated_conv_forward: linear launches take no multiplier");
     hipLaunchKernelGGL(fn, dim3((unsigned)nwg), dim3(threads), 0, stream, a);
@@ -4922,6 +5224,7 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
     case CK_D3H:
     case CK_F4X1:
     case CK_F4X1_PAIR:
+    case CK_F4X1_WIDE:
     case CK_W4H:
     case CK_W4: return launch_w4_family(d, a, s, r.kernel, wp_f4x1, stream);
     case CK_TABLE: return launch_table(d, a, s, r, stream);

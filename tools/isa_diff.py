@@ -12,7 +12,8 @@ each kernel's text (its label up to .Lfunc_end) is compared:
     differs         anything else (a kernel without a depth-1 loop is identical or differs)
 
 The one thing masked before comparing is the ordinal of the function inside the file in local labels (.LBB<n>_, .Lfunc_end<n>),
-which changes when a kernel is added or removed above.  Exit status 1 if any kernel differs or exists on one side only.
+which changes when a kernel is added or removed above, and with it the blanks that pad a label line's comment to its column (an ordinal
+of three digits where there were two shifts that padding by one).  Exit status 1 if any kernel differs or exists on one side only.
 """
 import os
 import re
@@ -27,6 +28,7 @@ from read_amd import build as B  # noqa: E402
 
 META = ("num_vgpr", "num_agpr", "numbered_sgpr", "private_seg_size")
 _ORDINAL = re.compile(r"(LBB|Lfunc_end|\bBB)\d+")
+_PAD = re.compile(r"[ \t]+;")
 
 
 def compile_asm(src, include, csrc, out):
@@ -56,7 +58,7 @@ def kernels(lines):
     for n in names:
         i = start[n]
         j = next(k for k in range(i, len(lines)) if lines[k].startswith(".Lfunc_end"))
-        text = [_ORDINAL.sub(r"\1", l) for l in lines[i:j + 1]]
+        text = [_PAD.sub(" ;", _ORDINAL.sub(r"\1", l)) for l in lines[i:j + 1]]
         meta = {k: sets.get((n, k)) for k in META}
         meta["lds"] = next(l.split()[1] for l in text if l.strip().startswith(".amdhsa_group_segment_fixed_size"))
         out[n] = (text, meta)

@@ -3,7 +3,8 @@
     python tools/pmc_levels.py <dir pass 1: SQ_VALU_MFMA_BUSY_CYCLES, GRBM_GUI_ACTIVE> <dir pass 2: SQ_INSTS_VALU, SQ_INSTS_MFMA> [kernel substring]
 
 The sweep runs the four C -> C shapes in level order, the same number of launches each: dispatches of the kernel are cut into four
-equal runs.  busy % = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs) (MI355X_MICROARCH.md).  Prints the markdown
+equal runs.  f4x1_wide_conv_kernel (config -14) has no launch at level 0, where there is one channel group: its dispatches (of
+`tools/w4h_ab.py --levels 1,2,3`, the same number of launches per level) are cut into three runs, levels 1 - 3.  busy % = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs) (MI355X_MICROARCH.md).  Prints the markdown
 rows `bench.py` reads back (profiles/r6_pmc_mfma_busy.md)."""
 import collections
 import csv
@@ -27,7 +28,9 @@ def main():
     sub = sys.argv[3] if len(sys.argv) > 3 else "gated_conv_wino4h_kernel"
     a, b = load(sys.argv[1], sub), load(sys.argv[2], sub)
     shapes = ["L0 C=32 352x1216", "L1 C=64 176x608", "L2 C=128 88x304", "L3 C=256 44x152"]
-    n, m = len(a) // 4, len(b) // 4
+    if a and all("f4x1_wide_conv_kernel" in r["name"] for r in a):
+        shapes = shapes[1:]
+    n, m = len(a) // len(shapes), len(b) // len(shapes)
     print("| kernel | grid | launches | avg µs | MFMA pipe busy % | MFMA per launch | VALU per launch | VALU per MFMA |")
     print("|---|---|---|---|---|---|---|---|")
     for i, sh in enumerate(shapes):

@@ -1,6 +1,6 @@
 """A/B of the F(4x4) kernels on the four dominant C->C shapes at 1216x352 (run on the GPU box): fp32 matrix cores (config -5)
 against split operands on the f16 matrix cores (config -7 F(4x4), -8 direct, -12 F(4,3) by rows, -13 the same with two workgroups per
-CU), all against the torch-fp32
+CU, -14 the same with two channel groups per unit: C % 64 == 0 only), all against the torch-fp32
 oracle on the CPU.  --rounds N repeats the alternation of the kernels N times in the same process (keys "... #r").
 
     python tools/w4h_ab.py [--iters 20] [--check 1] [--out gpurun_out/r6_w4h_ab.json]
@@ -78,9 +78,11 @@ def main():
         if a.check:
             with torch.no_grad():
                 ref = (unet_torch.basic_conv(st, "L", (xc * x2c if a.mul else xc)[None], 3, elu=True)[0] + rc).permute(1, 2, 0)
-        for rnd, (name, cfg) in [(r_, k_) for r_ in range(a.rounds) for k_ in (("fp32", -5), ("f16x3", -7), ("f4x1", -12), ("f4x1p", -13), ("d3h", -8))]:
-            if cfg in (-7, -12, -13) and a.mul:
+        for rnd, (name, cfg) in [(r_, k_) for r_ in range(a.rounds) for k_ in (("fp32", -5), ("f16x3", -7), ("f4x1", -12), ("f4x1p", -13), ("f4x1w", -14), ("d3h", -8))]:
+            if cfg in (-7, -12, -13, -14) and a.mul:
                 continue                                     # the Winograd split-operand kernel does not take FAM's multiply
+            if cfg == -14 and c % 64:
+                continue                                     # one channel group: nothing to share
             for _ in range(3):
                 gated_conv(pk, [(x, 0)], elu=True, residual=r, config=cfg, out=out, mul=x2)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
