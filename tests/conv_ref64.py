@@ -68,6 +68,40 @@ fe = f log2e, e = v_exp_f32(fe) - 1, v = (f sg) sc + sh + res; v_exp_f32 / v_rcp
               add of sh 1 — against S |g sigma| + |T| —; sh = beta - mean sc: 4.5 S |mean| + |T|; the residual add |y|)
 (gated_conv_pxh_kernel forms m = fma(acc, 1 / s, b_m) first and then m (-log2e): three roundings of at most u |m| <= u A_m, the same 3 u A_m.)
 First order; the neglected second-order terms are below 2^-10 of these while d_f, d_m < 2^-10: the factor SECOND_ORDER.
+
+RESAMPLED SOURCES (`assemble`).  The loader of gated_conv_pxh_kernel (`load_step`: sy = (ly[pt] << sl) >> sr, sx likewise, one of sl, sr
+zero by conv_prepare's SrcDev{..., shift > 0 ? shift : 0, shift < 0 ? -shift : 0}) reads source pixel dst << s of a finer source and
+dst >> -s of a coarser one.  Addressing only: the arithmetic and its bound are those of the concatenated image.
+A LAUNCH WITH AN ADDEND (`preact_bound_addend`; epilogue of gated_conv_pxh_kernel).  pp = pre + ((y >> pre_shift) pre_W + (x >>
+pre_shift)) pre_cstride, af = pp[pre_foff + cc], am = pp[pre_moff + cc] with cc = c0 < Cout ? c0 : Cout - 4 (a padded group reads valid
+channels and stores nothing), then
+  * f = fma(acc, 1 / s_f, b_f): the `+ 1` of preact_bound_direct, against the launch's OWN A (Af_own = conv(|x|, |w_f|) + |b_f|);
+  * f += af[qd]: one more rounding, u |f| of the finished value;
+  * the addend's own error d_pre, sampled as the addend is; zero for an addend the host gives.
+    |got_f - f|  <=  preact_bound_direct(own weights, own sources)  +  u |f|  +  d_pre          (m likewise; gated_bound on top, unchanged)
+The measure takes A_f = Af_own + |pre_f|: where the addend cancels the launch's own sum (|f| << A) the error stays of the size u A.
+THE CHAIN (`AFF_PLAN`, `aff_chain_reference`; build() of read_amd/csrc/unet.cpp under g_unet_aff_split).  q3 = W[:, z] z is a plain linear
+launch: d(q3) = preact_bound_direct(part 3).  Every later launch reads the coarser one as its addend at (y >> 1, x >> 1):
+    d(q_k) = preact_bound_direct(part k) + up(d(q_k+1)) + u |q_k|,     d_f(AFF_i) = preact_bound_direct(own part) + up(d(q)) + u |f|
+with up() the same sampling, |q_k| and |f| the float64 values of the UNSPLIT layer on assemble(...) (the chain computes the same sum,
+re-associated), each part's 1 / s from row_inv_scale of that part's stacked rows (the packer scales what it is given: `derive` stacks
+[f0 f1 f2 | m0 m1 m2] with zero bias), and nb = columns of the part / 16.  E is taken against A of the unsplit 480-channel layer.  The
+intermediate tensors are fp32: one stored with an f16 significand (2^-12 |q| relative) exceeds d(q) ~ (13 + 3 nb) u A wherever
+|q| > 2^-12 (13 + 3 nb) A — 0.012 A for the 256 columns of q3 —, which a sum of 256 products does on most elements.
+THE OUTPUT HEAD (family "sc", gated_conv_smallc_kernel; `preact_bound_sc`).  fp32 operands, no packer: no split terms, no W_FLOOR /
+X_FLOOR.  Per accumulator 9 x 32 = 288 v_fmac_f32 in the order (phase of CPH channels, tap, quad of the phase, channel of the quad), each
+one fused product-and-add = one rounding of a partial sum that is bounded by A: 288 u A; a tap outside the image arrives as zero
+(buffer load out of range) and its fmac is exact.  Then f = fa + params[c] (an add, not an fma): u |f|.
+    |got_f - f|  <=  288 u A_f  +  u |f|  +  TINY
+elu1 / sigmoidf (fast_exp(x) = v_exp_f32(x log2e), v_rcp_f32) against the gate epilogue above: elu1 is d_g term for term (fe = f log2e:
+constant and rounding, exp 2 u, the - 1); sigmoidf(m) forms (-m) log2e — the rounded constant and one rounding, 2 u |m| <= 2 u A_m where
+the split kernels have 3 u A_m — then exp, + 1, rcp as there; (f sg) sc + sh has no residual and may contract to an fma.  Every term is
+at most its counterpart: gated_bound is used unchanged.  Denormals: read_amd/build.py passes -O3 and no flush option, so the kernels are
+compiled with fp32 denormals ON (v_fmac_f32 keeps a subnormal partial sum); TINY stays for the results v_exp_f32 / v_rcp_f32 flush.
+bilinear_up4_kernel (`bilinear_up4_bound`).  The weights ly0, ly1, lx0, lx1 are multiples of 1/8 in [0, 1], exact in fp32, and sum to 1
+per axis.  o = ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11) without any contraction: each product lx v one rounding and their sum
+one: 2 u (lx0 |v00| + lx1 |v01|); the product with ly one more: 3 u; the final sum u |o| <= u sum w |v|: 4 u sum w |v| (an fma in
+the place of a product and a sum only removes roundings).  A constant image of 1.0 comes back exactly: the products k / 8 are exact and sum to 1.
 """
 import numpy as np
 import torch
@@ -90,7 +124,12 @@ SECOND_ORDER = 1.0 + 2.0 ** -10
 # the NumPy restatements of their pre-activations (tests/test_conv_accuracy_cpu.py) are held to the pxh kernel's linear row — the same
 # three-piece-pair arithmetic, measured without an epilogue.
 C_MEASURED = {"d3h": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}}, "d3h_s2": {"gated": {"a": 4.0, "b": 8.0, "c": 16.0, "d": 8.0}}, "pxh": {"gated": {"a": 4.0, "b": 4.0, "c": 8.0, "d": 4.0}, "linear": {"a": 4.0, "b": 2.0, "c": 2.0, "d": 1.0}}, "t3h": {"gated": {"a": 4.0, "b": 2.0, "c": 16.0, "d": 8.0}, "linear": {"a": 4.0, "b": 8.0, "c": 2.0, "d": 2.0}}, "w4h": {"gated": {"a": 1.0, "b": 8.0, "c": 16.0, "d": 8.0}},
-              "f4x1": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}}}      # f4x1: E against A_w, as w4h
+              "f4x1": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}},      # f4x1: E against A_w, as w4h
+              # pxh_pre: gated_conv_pxh_kernel with a pre-activation addend; chain: the six launches of the AFF chain against the unsplit layer;
+              # sc: gated_conv_smallc_kernel (the output head)
+              "pxh_pre": {"gated": {"a": 4.0, "b": 16.0, "c": 8.0, "d": 4.0}, "linear": {"a": 2.0, "b": 4.0, "c": 1.0, "d": 4.0}},      # (linear (c): R_max < 1 on every case)
+              "chain": {"gated": {"a": 2.0, "b": 4.0}, "linear": {"a": 4.0, "b": 8.0}},
+              "sc": {"gated": {"a": 4.0, "b": 4.0, "c": 4.0, "d": 16.0}}}
 
 
 def measured_cap(family, mode, cls):
@@ -126,9 +165,11 @@ class Ref:
     """All float64 CHW numpy arrays: f, m, Af, Am, y, B, and what the derived bound needs."""
 
 
-def reference(L, x, stride=1, elu=True, residual=None, mul=None):
+def reference(L, x, stride=1, elu=True, residual=None, mul=None, pre=None):
     """L: dict wf, bf, wm, bm, gamma, beta, mean, var (float32 arrays); x (C, H, W) float32 (concatenated / resampled as the layer sees
-    it); mul: FAM's second factor; residual (Cout, outH, outW)."""
+    it: `assemble`); mul: FAM's second factor; residual (Cout, outH, outW); pre = (pre_f, pre_m): the pre-activation addends at OUTPUT
+    resolution (`sample_addend`), added in float64: f = conv_f x + b_f + pre_f, A_f = conv(|x|, |w_f|) + |b_f| + |pre_f|; Af_own / Am_own
+    keep the launch's own part (without the addend), which is what its products and its accumulation are bounded by."""
     r = Ref()
     x64 = _t64(x) * (_t64(mul) if mul is not None else 1.0)
     wf, wm, bf, bm = _t64(L["wf"]), _t64(L["wm"]), _t64(L["bf"]), _t64(L["bm"])
@@ -138,6 +179,11 @@ def reference(L, x, stride=1, elu=True, residual=None, mul=None):
     r.m = _conv(x64, wm, bm, stride).numpy()
     r.Af = _conv(x64.abs(), wf.abs(), bf.abs(), stride).numpy()
     r.Am = _conv(x64.abs(), wm.abs(), bm.abs(), stride).numpy()
+    r.Af_own, r.Am_own = r.Af, r.Am
+    if pre is not None:
+        pf, pm = (np.asarray(p, np.float64) for p in pre)
+        r.f, r.m = r.f + pf, r.m + pm
+        r.Af, r.Am = r.Af + np.abs(pf), r.Am + np.abs(pm)
     r.X1 = _conv(x64.abs(), ones_w, None, stride).numpy()[0]                                     # (outH, outW): sum of |x| under the taps
     r.W1f = _conv(ones_x, wf.abs(), None, stride).numpy()                                        # sum of |w| over the taps inside the image
     r.W1m = _conv(ones_x, wm.abs(), None, stride).numpy()
@@ -159,12 +205,15 @@ def reference(L, x, stride=1, elu=True, residual=None, mul=None):
     return r
 
 
-def oracle_fp32(L, x, stride=1, elu=True, residual=None, mul=None, linear=False):
-    """The torch-fp32 restatement of BasicConv on the same inputs (what oracle.unet_torch.basic_conv computes): -> (Cout or 2 Cout, H, W)."""
+def oracle_fp32(L, x, stride=1, elu=True, residual=None, mul=None, linear=False, pre=None):
+    """The torch-fp32 restatement of BasicConv on the same inputs (what oracle.unet_torch.basic_conv computes): -> (Cout or 2 Cout, H, W).
+    pre = (pre_f, pre_m): fp32 addends at output resolution, added in fp32 to the fp32 pre-activations."""
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))       # noqa: E731
     xx = t(x) * t(mul) if mul is not None else t(x)
     f = _conv(xx, t(L["wf"]), t(L["bf"]), stride)
     m = _conv(xx, t(L["wm"]), t(L["bm"]), stride)
+    if pre is not None:
+        f, m = f + t(pre[0]), m + t(pre[1])
     if linear:
         return torch.cat([f, m]).numpy()
     if elu:
@@ -209,7 +258,7 @@ def row_inv_scale(w_rows):
 def preact_bound_direct(L, ref, family, which):
     """|got - f| (which = 'f') or |got - m| <= this, elementwise, for the direct split-operand families."""
     w = L["w" + which]
-    A, W1 = (ref.Af, ref.W1f) if which == "f" else (ref.Am, ref.W1m)
+    A, W1 = (ref.Af_own, ref.W1f) if which == "f" else (ref.Am_own, ref.W1m)     # (the launch's own products: an addend is not among them)
     cin, k = w.shape[1], w.shape[2]
     n = 12 + (1 if ref.mul else 0) + 3 * k_blocks(family, cin, k) + 1
     inv_s = row_inv_scale(w)[:, None, None]
@@ -333,6 +382,141 @@ def constant_outputs(L, ref):
     return mask, [(s[:, None, None] + res).astype(np.float32) for s in (sh_a, sh_b)]
 
 
+# ------------------------------------------------------------------------------------------ resampled sources and addends
+def assemble(xs, shifts, H, W):
+    """The nearest-resampled concatenation as the loader of gated_conv_pxh_kernel addresses it (sy = (ly << sl) >> sr, one of sl, sr zero:
+    conv_prepare): xs[i] (C_i, h_i, w_i), source pixel = dst << s for s > 0 (a finer source, sub-sampled), dst >> -s for s < 0 (a coarser
+    one, repeated) -> (sum C_i, H, W).  Plain index arrays: an index past a source raises."""
+    out = []
+    for x, s in zip(xs, shifts):
+        iy, ix = ((np.arange(n) << s) if s >= 0 else (np.arange(n) >> -s) for n in (H, W))
+        out.append(np.asarray(x)[:, iy[:, None], ix[None, :]])
+    return np.concatenate(out, 0)
+
+
+def sample_addend(t_hwc, f_off, m_off, cout, shift, H, W):
+    """The pre-activation addend as the epilogues address it (pp = pre + ((y >> pre_shift) preW + (x >> pre_shift)) pre_cstride, then
+    pre_foff + c, pre_moff + c): t (preH, preW, C) -> (pre_f, pre_m), each (cout, H, W), dtype of t."""
+    t = np.asarray(t_hwc)
+    px = t[(np.arange(H) >> shift)[:, None], (np.arange(W) >> shift)[None, :]]
+    return (np.ascontiguousarray(px[..., off:off + cout].transpose(2, 0, 1)) for off in (f_off, m_off))
+
+
+def preact_bound_addend(L, ref, family, which, total, d_pre=0.0):
+    """|got - f| <= this for a launch with an addend (module docstring, "A launch with an addend"): the launch's own bound, the rounding
+    of f1 + pre against the finished value `total`, and the addend's own error d_pre sampled as the addend is (0: given by the host)."""
+    return preact_bound_direct(L, ref, family, which) + U * np.abs(total) + d_pre
+
+
+# The AFF launch chain of the default plan (read_amd/csrc/unet.cpp, `if (g_unet_aff_split)`), one row per launch in the plan's order:
+# name, columns of the 480-channel concatenation [res1 32 | res2 64 | res3 128 | z 256] that the launch multiplies, AFF layers whose rows it
+# stacks ([f0 f1 f2 | m0 m1 m2]), (source, shift) list, linear, addend (name, f_off, m_off, shift), level of the output, and the sources
+# (with shifts) of the UNSPLIT layer restricted to the columns from this launch's first on — what the launch's output stands for.
+AFF_PLAN = (("q3", (224, 480), (0, 1, 2), ((3, 0),), True, None, 3, ((3, 0),)),
+            ("q2", (96, 224), (0, 1), ((2, 0),), True, ("q3", 0, 224, 1), 2, ((2, 0), (3, -1))),
+            ("a2", (0, 224), (2,), ((0, 2), (1, 1), (2, 0)), False, ("q3", 96, 320, 1), 2, ((0, 2), (1, 1), (2, 0), (3, -1))),
+            ("q1", (32, 96), (0,), ((1, 0),), True, ("q2", 0, 96, 1), 1, ((1, 0), (2, -1), (3, -2))),
+            ("a1", (0, 96), (1,), ((0, 1), (1, 0)), False, ("q2", 32, 128, 1), 1, ((0, 1), (1, 0), (2, -1), (3, -2))),
+            ("a0", (0, 32), (0,), ((0, 0),), False, ("q1", 0, 32, 1), 0, ((0, 0), (1, -1), (2, -2), (3, -3))))
+
+
+def part_layer(layers, c0, c1, own_bias):
+    """The rows of `layers` stacked, restricted to input columns c0 .. c1 - 1; zero bias unless own_bias (`derive` of unet.cpp: the bias
+    stays with the launch at the layer's own level)."""
+    cat = lambda key: np.concatenate([np.asarray(L[key]) for L in layers])                       # noqa: E731
+    P = {key: cat(key) for key in ("gamma", "beta", "mean", "var")}
+    for fm in "fm":
+        P["w" + fm] = np.ascontiguousarray(cat("w" + fm)[:, c0:c1])
+        P["b" + fm] = cat("b" + fm) if own_bias else np.zeros(P["w" + fm].shape[0], np.float32)
+    return P
+
+
+def run_aff_chain(layers, xs, launch):
+    """The six launches in the plan's order.  launch(name, L_part, [(x_i, shift)], pre, linear, (H, W) of the output) -> the launch's
+    output, in whatever form the caller's next launch takes as pre = (that output, f_off, m_off, shift).  -> {name: output}."""
+    outs = {}
+    for name, (c0, c1), li, srcs, linear, pre, level, _ in AFF_PLAN:
+        Lp = part_layer([layers[i] for i in li], c0, c1, own_bias=not linear)
+        outs[name] = launch(name, Lp, [(xs[i], s) for i, s in srcs], None if pre is None else (outs[pre[0]],) + tuple(pre[1:]), linear,
+                            xs[level].shape[1:])
+    return outs
+
+
+def aff_chain_inputs(cls, sizes=((20, 36), (10, 18), (5, 9), (3, 5))):
+    """-> (three AFF layers 480 -> 32 / 64 / 128, the sources res1 32, res2 64, res3 128, z 256 at their levels).  Class (a): tame_layer and
+    unit-scale sources.  Class (b): ONE checkpoint_like layer of 224 rows cut into the three (rows 0 .. 31, 32 .. 95, 96 .. 223), so that
+    all three share the per-input-channel scales 2^U(-8, 8) that the sources carry.  Without the packers' edge rows: the linear launches
+    have zero bias, so the row of fp32-denormal weights gives pre-activations of ~1e-38 with A_f of the same size — there the whole
+    result is inside TINY and E against u A_f measures nothing (8e6 on an MI355X, at 0.33 of the derived bound); the edge rows run with
+    addends in class (b) of the single launches, where the bias is the layer's own."""
+    chans = (32, 64, 128, 256)
+    offs = np.cumsum((0,) + chans)
+    if cls == "a":
+        rng = np.random.default_rng([73, 480])
+        layers = [tame_layer(480, 32 << i, 1, 73 + i) for i in range(3)]
+        x = rng.standard_normal((480,) + tuple(sizes[0])).astype(np.float32)
+    else:
+        L, x = checkpoint_like(480, 224, 1, sizes[0][0], sizes[0][1], 74, edge_rows=False)
+        rows = np.cumsum((0, 32, 64, 128))
+        layers = [{key: np.ascontiguousarray(v[rows[i]:rows[i + 1]]) for key, v in L.items()} for i in range(3)]
+    return layers, [np.ascontiguousarray(x[offs[k]:offs[k + 1], :h, :w]) for k, (h, w) in enumerate(sizes)]
+
+
+def aff_chain_reference(layers, xs, family="pxh"):
+    """-> {name: (ref, d_f, d_m, L, x)}: the float64 reference of the UNSPLIT layer L (for q_k: its stacked rows over the columns from part
+    k on) on x = assemble(...), and the bound composed level by level (module docstring, "The chain"):
+    d(q_k) = preact_bound_direct(part k) + up(d(q_k+1)) + u |q_k|."""
+    out = {}
+    for name, (c0, c1), li, srcs, linear, pre, level, full_srcs in AFF_PLAN:
+        H, W = xs[level].shape[1:]
+        Ls = [layers[i] for i in li]
+        Lfull, xfull = part_layer(Ls, c0, 480, own_bias=not linear), assemble([xs[i] for i, _ in full_srcs], [s for _, s in full_srcs], H, W)
+        full = reference(Lfull, xfull)
+        Lp = part_layer(Ls, c0, c1, own_bias=not linear)
+        own = reference(Lp, assemble([xs[i] for i, _ in srcs], [s for _, s in srcs], H, W))
+        d = []
+        for j, fm in enumerate("fm"):
+            b = preact_bound_direct(Lp, own, family, fm)
+            if pre is not None:
+                dq_f, dq_m = out[pre[0]][1:3]
+                dq = np.concatenate([dq_f, dq_m]).transpose(1, 2, 0)
+                b = b + U * np.abs(full.f if fm == "f" else full.m) + tuple(sample_addend(dq, pre[1], pre[2], b.shape[0], pre[3], H, W))[j]
+            d.append(b)
+        out[name] = (full, d[0], d[1], Lfull, xfull)
+    return out
+
+
+# ------------------------------------------------------------------------------------------ the output head and the up-sampling
+def preact_bound_sc(L, ref, which):
+    """|got - f| <= this for gated_conv_smallc_kernel (module docstring, "The output head")."""
+    w = L["w" + which]
+    A, val = (ref.Af_own, ref.f) if which == "f" else (ref.Am_own, ref.m)
+    return SECOND_ORDER * U * (w.shape[1] * w.shape[2] * w.shape[3]) * A + U * np.abs(val) + TINY
+
+
+def bilinear_up4_ref(x):
+    """nn.Upsample(scale_factor=4, mode='bilinear', align_corners=False) restated from the formula (src = 0.25 (dst + 0.5) - 0.5 clamped at
+    0, the upper neighbour clamped at the last index): x (C, h, w) float32 -> (value, sum w |v|), each (C, 4 h, 4 w) float64."""
+    def axis(n):
+        s = np.maximum(0.25 * (np.arange(4 * n) + 0.5) - 0.5, 0.0)
+        i0 = np.floor(s).astype(np.int64)
+        return i0, i0 + (i0 < n - 1), 1.0 - (s - i0), s - i0
+
+    (y0, y1, ly0, ly1), (x0, x1, lx0, lx1) = axis(x.shape[1]), axis(x.shape[2])
+
+    def interp(v):
+        top, bot = (v[:, r][:, :, x0] * lx0 + v[:, r][:, :, x1] * lx1 for r in (y0, y1))
+        return ly0[None, :, None] * top + ly1[None, :, None] * bot
+
+    v = np.asarray(x, np.float64)
+    return interp(v), interp(np.abs(v))
+
+
+def bilinear_up4_bound(absum):
+    """|got - value| <= this (module docstring, "bilinear_up4_kernel"); absum = sum w |v| of bilinear_up4_ref."""
+    return SECOND_ORDER * 4 * U * absum + TINY
+
+
 # ------------------------------------------------------------------------------------------ inputs
 def tame_layer(cin, cout, k, seed):
     """Class (a): the distribution every other test uses (read_amd.synthetic.make_unet_state: Conv2d default init, gamma and var in
@@ -397,6 +581,52 @@ def checkpoint_like(cin, cout, k, H, W, seed, edge_rows=True):
                 L["wm"][8 + j] = edge_row(kind, cin, k, rng)
         L["bf"][0] = 0.0                                          # the all-zero conv_f row with zero bias: act(0) = 0, the output is the BN constant
     return L, x
+
+
+SENTINEL = -7.0
+
+
+def source_sizes(shifts, H, W):
+    """The size of each source of a resampled concatenation at output size H x W: H << s for a finer source (whole, so that the first
+    source's size >> s gives H back), ((H - 1) >> -s) + 1 for a coarser one — the smallest that conv_prepare accepts."""
+    return [(H << s, W << s) if s >= 0 else (((H - 1) >> -s) + 1, ((W - 1) >> -s) + 1) for s in shifts]
+
+
+def split_sources(x_big, split, shifts, H, W):
+    """x_big (sum split, H << max shift, W << max shift) -> the sources, each the top-left corner of its channels at its own size."""
+    offs = np.cumsum([0] + list(split))
+    return [np.ascontiguousarray(x_big[offs[i]:offs[i + 1], :h, :w]) for i, (h, w) in enumerate(source_sizes(shifts, H, W))]
+
+
+def addend_size(shift, H, W):
+    return ((H - 1) >> shift) + 1, ((W - 1) >> shift) + 1
+
+
+def addend_tensor(rng, shape_hwc, f_off, m_off, cout, scale=1.0):
+    """(preH, preW, C) float32: standard normal times `scale` (a number or one value per output channel) in the channels the launch reads,
+    SENTINEL in every other one."""
+    t = np.full(shape_hwc, SENTINEL, np.float32)
+    for off in (f_off, m_off):
+        t[..., off:off + cout] = (rng.standard_normal(shape_hwc[:2] + (cout,)) * scale).astype(np.float32)
+    return t
+
+
+def cancelling_addend(t, own_f64, f_off, shift):
+    """The f slice of t replaced by -fl32(own pre-activation) of the top-left output pixel of every addend pixel: there the launch's own sum
+    and the addend cancel to the rounding of the former, |f| << A_f; the other pixels of the block see an addend of the same size."""
+    t = t.copy()
+    st = 1 << shift
+    t[..., f_off:f_off + own_f64.shape[0]] = -own_f64[:, ::st, ::st].astype(np.float32).transpose(1, 2, 0)
+    return t
+
+
+def addend_impulse_spots(pre_hw, cout):
+    """(row, column, channel) of single addend elements: the four corners and the last row / last column (shared by the odd rest of the
+    output) at channel 1, and the channels at the quad, half-wave and group boundaries (0, 3, 4, 31, 32, Cout - 1) at the last corner."""
+    ph, pw = pre_hw
+    spots = [(y, x_, 1) for (y, x_) in ((0, 0), (0, pw - 1), (ph - 1, 0), (ph - 1, pw - 1), (ph - 1, pw // 2), (ph // 2, pw - 1))]
+    spots += [(ph - 1, pw - 1, c) for c in sorted({0, 3, 4, 31, 32, cout - 1}) if c < cout]
+    return list(dict.fromkeys(spots))
 
 
 def impulse(cin, H, W, c, y, x_, amp):

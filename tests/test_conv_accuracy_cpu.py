@@ -481,3 +481,236 @@ def test_f4x1_model_overflows_just_past_the_documented_range():
         assert run_f4x1(tame, R64.f4x1_range_edge(cin, H, W, row=row, segment=segment, amp=6550.0), cls="d")["finite"]
         s = run_f4x1(tame, R64.f4x1_range_edge(cin, H, W, row=row, segment=segment, amp=6560.0), cls="d")
         assert not s["finite"] and not f4x1_inside_caps(s), (row, segment)
+
+
+# ------------------------------------------------------------------------------------------ addends, resampled sources, the AFF chain, the head
+def _sample(t, f_off, m_off, cout, shift, H, W, defect=None):
+    """R64.sample_addend, copied so that ONE line at a time can be broken."""
+    if defect == "m_from_f_offset":
+        m_off = f_off
+    if defect == "pre_shift_off_by_one":
+        shift += 1
+    iy, ix = np.arange(H) >> shift, np.arange(W) >> shift
+    if defect == "row_clamped":
+        iy = np.minimum(iy, t.shape[0] - 2)
+    px = t[iy[:, None], ix[None, :]]
+    return px[..., f_off:f_off + cout].transpose(2, 0, 1), px[..., m_off:m_off + cout].transpose(2, 0, 1)
+
+
+def _assemble(srcs, H, W, defect=None):
+    """R64.assemble, copied likewise: the first finer source read with >> where << is meant."""
+    out = []
+    for x, s in srcs:
+        wrong = defect == "shift_direction" and s > 0
+        iy, ix = ((np.arange(n) << s) if (s >= 0 and not wrong) else (np.arange(n) >> abs(s)) for n in (H, W))
+        out.append(x[:, iy[:, None], ix[None, :]])
+    return np.concatenate(out, 0)
+
+
+def pxh_launch_model(L, srcs, H, W, pre=None, defect=None):
+    """One launch of gated_conv_pxh_kernel up to its pre-activations, on tests/d3h_ref.split_conv_model_taps (acc / s as fp32):
+    fl32(fl32(acc / s + b) + pre), pre = (tensor (preH, preW, C), f_off, m_off, shift) -> [f | m] (H, W, 2 Cout) float32."""
+    x = np.ascontiguousarray(_assemble(srcs, H, W, defect).transpose(1, 2, 0))
+    cout = L["wf"].shape[0]
+    add = _sample(pre[0], pre[1], pre[2], cout, pre[3], H, W, defect) if pre is not None else (None, None)
+    out = []
+    for fm, p in zip("fm", add):
+        w2 = w_matrix(L["w" + fm])
+        acc = split_conv_model_taps(x, w2).astype(np.float64)
+        b = L["b" + fm].astype(np.float64)[None, None]
+        if p is None:
+            f = (acc + b).astype(np.float32)
+        elif defect == "addend_before_scaling":                  # fma(acc_s + pre, 1 / s, b)
+            f = (acc + p.transpose(1, 2, 0).astype(np.float64) * R64.row_inv_scale(w2)[None, None] + b).astype(np.float32)
+        else:
+            f = ((acc + b).astype(np.float32).astype(np.float64) + p.transpose(1, 2, 0)).astype(np.float32)
+        out.append(f)
+    return np.concatenate(out, 2)
+
+
+def _q(got_hwc, truth, bound):
+    return float((np.abs(got_hwc.transpose(2, 0, 1).astype(np.float64) - truth) / bound).max())
+
+
+ADDEND_SHAPE = ([32], (0,), 32, 13, 37, 64, 0, 32, 1)          # the AFF0 launch of the plan at an odd size: the last addend row and column are shared
+RESAMPLED_SHAPE = ([32, 64, 128], (1, 0, -1), 64, 13, 37)
+
+
+def addend_inputs(shape, cls):
+    """-> (L, srcs, pre) of class (a), (b) or (b) in its cancelling form ("bc")."""
+    split, shifts, cout, H, W, C, f_off, m_off, sh = shape
+    cin, big = sum(split), max(max(shifts), 0)
+    rng = np.random.default_rng([71, cin, cout, H])
+    if cls == "a":
+        L, xb = R64.tame_layer(cin, cout, 1, 71), rng.standard_normal((cin, H << big, W << big)).astype(np.float32)
+    else:
+        L, xb = R64.checkpoint_like(cin, cout, 1, H << big, W << big, 72)
+    xs = R64.split_sources(xb, split, shifts, H, W)
+    t = R64.addend_tensor(rng, R64.addend_size(sh, H, W) + (C,), f_off, m_off, cout, 1.0 if cls == "a" else 2.0 ** rng.uniform(-8, 8, cout))
+    if cls == "bc":
+        t = R64.cancelling_addend(t, R64.reference(L, R64.assemble(xs, shifts, H, W)).f, f_off, sh)
+    return L, list(zip(xs, shifts)), (t, f_off, m_off, sh)
+
+
+def addend_q(L, srcs, pre, H, W, defect=None):
+    """err / derived bound of the launch model's pre-activations, and of the torch-fp32 oracle's on the same inputs."""
+    cout = L["wf"].shape[0]
+    x = R64.assemble([s[0] for s in srcs], [s[1] for s in srcs], H, W)
+    add = tuple(R64.sample_addend(pre[0], pre[1], pre[2], cout, pre[3], H, W)) if pre is not None else None
+    ref = R64.reference(L, x, pre=add)
+    truth = np.concatenate([ref.f, ref.m])
+    if add is None:
+        bound = np.concatenate([R64.preact_bound_direct(L, ref, "pxh", fm) for fm in "fm"])
+    else:
+        bound = np.concatenate([R64.preact_bound_addend(L, ref, "pxh", fm, tot) for fm, tot in (("f", ref.f), ("m", ref.m))])
+    got = pxh_launch_model(L, srcs, H, W, pre, defect)
+    ora = R64.oracle_fp32(L, x, linear=True, pre=add)
+    return _q(got, truth, bound), float((np.abs(ora.astype(np.float64) - truth) / bound).max())
+
+
+@pytest.mark.parametrize("cls", ["a", "b", "bc"])
+def test_addend_epilogue_model_stays_inside_the_bound(cls):
+    """fl32(fl32(acc / s + b) + pre) on unit-scale and checkpoint-like inputs (the addend scaled per channel by 2^U(-8, 8), and the
+    cancelling form): inside preact_bound_direct(own) + u |f|; so is the torch-fp32 oracle: the inputs are fair."""
+    H, W = ADDEND_SHAPE[3:5]
+    q, q_oracle = addend_q(*addend_inputs(ADDEND_SHAPE, cls), H, W)
+    print("addend (%s): model err/bound %.3f, oracle %.3f" % (cls, q, q_oracle))
+    assert q <= 1.0 and q_oracle <= 1.0, (q, q_oracle)
+
+
+def test_resampled_concatenation_model_stays_inside_the_bound():
+    split, shifts, cout, H, W = RESAMPLED_SHAPE
+    for cls in "ab":
+        L, srcs, _ = addend_inputs((split, shifts, cout, H, W, 2 * cout, 0, cout, 1), cls)
+        q, q_oracle = addend_q(L, srcs, None, H, W)
+        print("resampled (%s): model err/bound %.3f, oracle %.3f" % (cls, q, q_oracle))
+        assert q <= 1.0 and q_oracle <= 1.0, (cls, q, q_oracle)
+
+
+def _round_to_11_bits(a):
+    m, e = np.frexp(a.astype(np.float64))
+    return np.ldexp(np.round(np.ldexp(m, 11)), e - 11).astype(np.float32)
+
+
+def chain_inputs(cls, sizes=((20, 36), (10, 18), (5, 9), (3, 5))):
+    """Three AFF layers 480 -> 32 / 64 / 128 and the four sources res1 32, res2 64, res3 128, z 256 at their levels; class (b): the layers
+    checkpoint-like with the sources scaled per channel as their weights are (inversely)."""
+    return R64.aff_chain_inputs(cls, sizes)
+
+
+def chain_q(layers, xs, defect=None):
+    """-> {launch: err / composed bound of its pre-activations [f | m]} for the six launches on the launch model."""
+    def launch(name, Lp, srcs, pre, linear, hw):
+        out = pxh_launch_model(Lp, srcs, hw[0], hw[1], pre)
+        return _round_to_11_bits(out) if (defect == "q_rounded_to_11_bits" and name == "q3") else out
+
+    outs = R64.run_aff_chain(layers, xs, launch)
+    refs = R64.aff_chain_reference(layers, xs)
+    return {name: _q(outs[name], np.concatenate([ref.f, ref.m]), np.concatenate([df, dm])) for name, (ref, df, dm, _, _) in refs.items()}
+
+
+@pytest.mark.parametrize("cls", ["a", "b"])
+def test_aff_chain_model_stays_inside_the_composed_bound(cls):
+    """The six launches of the plan on the launch model, every intermediate tensor fp32: each of q3, q2, q1 and the pre-activations of
+    the three gated launches inside d(q_k) = B_lin(part k) + up(d(q_k+1)) + u |q_k| against the UNSPLIT layer in float64."""
+    q = chain_q(*chain_inputs(cls))
+    print("chain (%s): " % cls + "  ".join("%s %.3f" % kv for kv in q.items()))
+    assert max(q.values()) <= 1.0, q
+
+
+def head_model(L, x, cph=8, defect=None):
+    """gated_conv_smallc_kernel up to its pre-activations: per accumulator a sequential fp32 fma chain in the kernel's order (phase of cph
+    channels, tap, quad of the phase, channel of the quad), then fl32(acc + b) -> [f | m] (2 Cout, H, W) float32.  (The fma is formed in
+    float64 — the product of two fp32 numbers is exact there — and rounded to fp32.)"""
+    cin, H, W = x.shape
+    xp = np.zeros((cin, H + 2, W + 2))
+    xp[:, 1:-1, 1:-1] = x
+    out = []
+    for fm in "fm":
+        w = L["w" + fm].astype(np.float64)
+        acc = np.zeros((w.shape[0], H, W), np.float32)
+        for ph in range(cin // cph):
+            for tap in range(9):
+                ky, kx = divmod(tap, 3)
+                for ch in range(ph * cph, (ph + 1) * cph):          # (quad, channel of the quad) = consecutive channels of the phase
+                    v = xp[ch, ky:ky + H, kx:kx + W]
+                    if defect == "tap_row_dropped" and tap == 7:
+                        v = v.copy()
+                        v[H - 2] = 0.0                               # tap (2, 1) of output row H - 2 reads the last image row: dropped
+                    acc = (w[:, ch, ky, kx][:, None, None] * v[None] + acc.astype(np.float64)).astype(np.float32)
+        out.append((acc.astype(np.float64) + L["b" + fm].astype(np.float64)[:, None, None]).astype(np.float32))
+    return np.concatenate(out)
+
+
+def head_q(cls, defect=None, shape=(3, 9, 33)):
+    cout, H, W = shape
+    if cls == "a":
+        L, x = R64.tame_layer(32, cout, 3, 75), np.random.default_rng(75).standard_normal((32, H, W)).astype(np.float32)
+    else:
+        L, x = R64.checkpoint_like(32, cout, 3, H, W, 76)
+    ref = R64.reference(L, x)
+    truth, bound = np.concatenate([ref.f, ref.m]), np.concatenate([R64.preact_bound_sc(L, ref, fm) for fm in "fm"])
+    got = head_model(L, x, defect=defect)
+    ora = R64.oracle_fp32(L, x, linear=True)
+    return float((np.abs(got.astype(np.float64) - truth) / bound).max()), float((np.abs(ora.astype(np.float64) - truth) / bound).max())
+
+
+@pytest.mark.parametrize("cls", ["a", "b"])
+def test_head_model_stays_inside_the_bound(cls):
+    q, q_oracle = head_q(cls)
+    print("head (%s): model err/bound %.3f, oracle %.3f" % (cls, q, q_oracle))
+    assert q <= 1.0 and q_oracle <= 1.0, (q, q_oracle)
+
+
+# One seeded defect per case; each must EXCEED the derived bound on classes (a) and (b) while the intact model (tests above) stays inside.
+NEW_DEFECTS = ["m_from_f_offset", "addend_before_scaling", "row_clamped", "q_rounded_to_11_bits", "pre_shift_off_by_one", "shift_direction", "tap_row_dropped"]
+
+
+@pytest.mark.parametrize("defect", NEW_DEFECTS)
+def test_seeded_addend_chain_and_head_defects_exceed_the_bound(defect):
+    for cls in "ab":
+        if defect == "q_rounded_to_11_bits":
+            q = chain_q(*chain_inputs(cls), defect=defect)
+            print("%s (%s): " % (defect, cls) + "  ".join("%s %.3f" % kv for kv in q.items()))
+            assert all(v > 1.0 for v in q.values()), q            # q3 itself and everything downstream of it
+        elif defect == "tap_row_dropped":
+            q, _ = head_q(cls, defect)
+            assert q > 1.0, (defect, cls, q)
+        elif defect == "shift_direction":
+            split, shifts, cout, H, W = RESAMPLED_SHAPE
+            L, srcs, _ = addend_inputs((split, shifts, cout, H, W, 2 * cout, 0, cout, 1), cls)
+            q, _ = addend_q(L, srcs, None, H, W, defect)
+            assert q > 1.0, (defect, cls, q)
+        else:
+            H, W = ADDEND_SHAPE[3:5]
+            q, _ = addend_q(*addend_inputs(ADDEND_SHAPE, cls), H, W, defect)
+            print("%s (%s): err/bound %.3f" % (defect, cls, q))
+            assert q > 1.0, (defect, cls, q)
+
+
+def test_oracle_stays_inside_the_derived_bound_on_every_new_gpu_case():
+    """The inputs of the resampled-source, addend, chain and head cases of tests/test_gpu_conv_accuracy.py are fair: the torch-fp32 oracle
+    alone — a correctly rounded fp32 evaluation in another order — is inside the derived bound on every element of every one of them."""
+    from tests import test_gpu_conv_accuracy as G
+    todo = [(c, False, "pxh") for c in G.cases_resampled()]
+    todo += [(c, lin, "pxh_pre") for cls in "abcd" for c, lin in G.cases_pre(cls)]
+    todo += [(c, False, "sc") for cls in "abcd" for c in G.cases_sc(cls)]
+    worst = {}
+    for case, linear, family in todo:
+        ref = case.ref()
+        ora = R64.oracle_fp32(case.L, case.x, elu=case.elu, residual=case.residual, linear=linear, pre=case.addend())
+        df, dm, _ = G._bounds(case, family)
+        truth, bound = (np.concatenate([ref.f, ref.m]), np.concatenate([df, dm])) if linear else (ref.y, R64.gated_bound(ref, df, dm))
+        q = float((np.abs(ora.astype(np.float64) - truth) / bound).max())
+        worst[(family, case.cls)] = max(worst.get((family, case.cls), 0.0), q)
+        assert q <= 1.0, (family, case.cls, case.name, q)
+    for cls in "ab":
+        layers, xs = R64.aff_chain_inputs(cls)
+        for name, (ref, df, dm, Lfull, xfull) in R64.aff_chain_reference(layers, xs).items():
+            linear = name.startswith("q")
+            ora = R64.oracle_fp32(Lfull, xfull, linear=linear)
+            truth, bound = (np.concatenate([ref.f, ref.m]), np.concatenate([df, dm])) if linear else (ref.y, R64.gated_bound(ref, df, dm))
+            q = float((np.abs(ora.astype(np.float64) - truth) / bound).max())
+            worst[("chain", cls)] = max(worst.get(("chain", cls), 0.0), q)
+            assert q <= 1.0, ("chain", cls, name, q)
+    print("oracle err / derived bound, worst per family and class: " + "  ".join("%s (%s) %.3f" % (f, c, q) for (f, c), q in sorted(worst.items())))

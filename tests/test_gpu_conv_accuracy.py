@@ -13,7 +13,18 @@ An automatic launch (config -1) of the 3x3 / stride-1 family is attributed BY IT
 report family 5 — and held to the bound and cap of the kernel that ran.
 Plus the persistent walk (shapes with more units than the device has compute units, impulses in a workgroup's second and third unit),
 FAM's x1 * x2 launches, the family query against the dispatch order, the loud failure past the documented range, and one whole network
-whose residual blocks carry checkpoint-like statistics against the float64 network.  Run with -s to see the table; lines start with "ACC|"."""
+whose residual blocks carry checkpoint-like statistics against the float64 network.
+What every frame of the default plan runs around those kernels is held to the same measure (families "pxh_pre", "chain", "sc" of
+FAMILY_ID / FORCE; derivations in tests/conv_ref64.py):
+  * gated_conv_pxh_kernel on nearest-resampled sources at sizes that are not powers of two apart (SHAPES_RESAMPLED; family pxh's caps);
+  * the same kernel with a host-given pre-activation addend in the plan's layouts (SHAPES_PRE: pre_f_off != 0, pre_m_off != Cout,
+    pre_cstride > 2 Cout, a shared last addend row / column, a padded channel group, a linear launch) on classes (a) - (d) — (b) also with
+    an addend that cancels the launch's own sum, (c) single addend elements over a zero image — with sentinels around what it may write;
+  * the six launches of the AFF chain in the plan's order against the float64 UNSPLIT 480-channel layer and the bound composed level by level;
+  * the output head gated_conv_smallc_kernel (SHAPES_SC, config -6, family 1), with and without ELU, and its fill channel;
+  * bilinear_up4_kernel against a float64 restatement of the formula (SHAPES_UP4).
+Every pxh launch of these runs forced (config -10) and automatic (-1) and must report family 7.
+Run with -s to see the table; lines start with "ACC|"."""
 import ctypes
 
 import numpy as np
@@ -25,8 +36,9 @@ from tests import conv_ref64 as R64
 
 pytestmark = pytest.mark.gpu
 
-FAMILY_ID = {"w4h": 5, "f4x1": 5, "d3h": 6, "d3h_s2": 6, "pxh": 7, "t3h": 8}
-FORCE = {"w4h": -7, "f4x1": -12, "d3h": -8, "d3h_s2": -1, "pxh": -10, "t3h": -11}          # stride 2 goes through the automatic choice, family asserted
+FAMILY_ID = {"w4h": 5, "f4x1": 5, "d3h": 6, "d3h_s2": 6, "pxh": 7, "t3h": 8, "pxh_pre": 7, "chain": 7, "sc": 1}
+FORCE = {"w4h": -7, "f4x1": -12, "d3h": -8, "d3h_s2": -1, "pxh": -10, "t3h": -11,         # stride 2 goes through the automatic choice, family asserted
+         "pxh_pre": -10, "chain": -10, "sc": -6}                                           # pxh_pre: gated_conv_pxh_kernel with an addend; chain: the six AFF launches; sc: the head
 DIRECT_FP32 = "k3s1c16_p2q1m4n1f1b2"
 
 
@@ -39,25 +51,42 @@ def _nhwc(a_chw):
 
 
 class Case:
-    def __init__(self, family, cls, name, L, x, stride=1, elu=True, residual=None, mul=None, split=None):
+    def __init__(self, family, cls, name, L, x, stride=1, elu=True, residual=None, mul=None, split=None, xs=None, shifts=None, pre=None):
+        """xs, shifts: the sources at their own sizes and their shifts (x is then their assembly, R64.assemble);
+        pre = (tensor (preH, preW, C) float32 on the host, f_off, m_off, shift): the pre-activation addend of the launch."""
+        if xs is not None:
+            H, W = (xs[0].shape[1] >> shifts[0], xs[0].shape[2] >> shifts[0]) if shifts[0] >= 0 else (xs[0].shape[1] << -shifts[0], xs[0].shape[2] << -shifts[0])
+            x, split = R64.assemble(xs, shifts, H, W), [s.shape[0] for s in xs]
         self.family, self.cls, self.name, self.L, self.x = family, cls, name, L, x
         self.stride, self.elu, self.residual, self.mul = stride, elu, residual, mul
         self.split = split if split is not None else [x.shape[0]]           # channels per source (pxh: concatenated sources)
+        self.xs, self.shifts, self.pre = xs, shifts, pre
         self.k = L["wf"].shape[2]
         self._ref = None
         self._bounds = {}
 
+    def addend(self):
+        """-> (pre_f, pre_m) at output resolution, float32, or None."""
+        if self.pre is None:
+            return None
+        t, f_off, m_off, shift = self.pre
+        return tuple(R64.sample_addend(t, f_off, m_off, self.L["wf"].shape[0], shift, self.x.shape[1], self.x.shape[2]))
+
     def ref(self):
         if self._ref is None:
-            self._ref = R64.reference(self.L, self.x, stride=self.stride, elu=self.elu, residual=self.residual, mul=self.mul)
+            self._ref = R64.reference(self.L, self.x, stride=self.stride, elu=self.elu, residual=self.residual, mul=self.mul, pre=self.addend())
         return self._ref
 
-    def launch(self, config, linear=False):
-        """-> ((C or 2 C, H, W) float32 on the host, kernel family of the launch)."""
+    def launch(self, config, linear=False, **more):
+        """-> ((C or 2 C, H, W) float32 on the host, kernel family of the launch).  With an addend the output is a slot of a tensor four
+        channels wider, filled with R64.SENTINEL: those four and the whole addend tensor must be unchanged afterwards."""
         pk = _pack(self.L, self.split)
         offs = np.cumsum([0] + self.split)
-        srcs = [(_nhwc(self.x[offs[i]:offs[i + 1]]), 0) for i in range(len(self.split))]
-        kw = dict(stride=self.stride, elu=self.elu, config=config)
+        if self.xs is not None:
+            srcs = [(_nhwc(x), s) for x, s in zip(self.xs, self.shifts)]
+        else:
+            srcs = [(_nhwc(self.x[offs[i]:offs[i + 1]]), 0) for i in range(len(self.split))]
+        kw = dict(stride=self.stride, elu=self.elu, config=config, **more)
         if linear:
             kw["linear"] = True
         else:
@@ -65,10 +94,19 @@ class Case:
                 kw["residual"] = _nhwc(self.residual)
             if self.mul is not None:
                 kw["mul"] = _nhwc(self.mul)
+        cs = pt = None
+        if self.pre is not None:
+            cs = self.L["wf"].shape[0] * (2 if linear else 1)
+            pt = torch.from_numpy(self.pre[0]).cuda()
+            kw.update(pre=(pt,) + tuple(self.pre[1:]), out=torch.full(self.x.shape[1:] + (cs + 4,), R64.SENTINEL, device="cuda"), out_channels=cs + 4)
         from read_amd import _lib
         fam = _lib.lib().read_conv_kernel_family(ctypes.byref(conv_desc(pk, srcs, **kw)))
         out = gated_conv(pk, srcs, **kw)
         torch.cuda.synchronize()
+        if pt is not None:
+            assert _same_bits(pt.cpu().numpy(), self.pre[0]), f"{self.name}: the launch changed its addend tensor"
+            assert bool((out[..., cs:] == R64.SENTINEL).all()), f"{self.name}: the launch wrote beyond its {cs} channels"
+            out = out[..., :cs]
         return out.cpu().numpy().transpose(2, 0, 1), fam
 
 
@@ -84,6 +122,11 @@ def _bounds(case, family):
             Awm = Awm + np.abs(case.L["bm"].astype(np.float64))[:, None, None]
             Bw = ref.S * (np.abs(ref.dact) * ref.sig * Awf + np.abs(ref.g) * ref.sig * (1.0 - ref.sig) * Awm) + np.abs(ref.y)
             case._bounds[family] = (df, dm, Bw)
+        elif family == "sc":
+            case._bounds[family] = (R64.preact_bound_sc(case.L, ref, "f"), R64.preact_bound_sc(case.L, ref, "m"), None)
+        elif family == "pxh_pre":
+            df, dm = (R64.preact_bound_addend(case.L, ref, "pxh", fm, tot) for fm, tot in (("f", ref.f), ("m", ref.m)))
+            case._bounds[family] = (df, dm, None)
         else:
             df, dm = (R64.preact_bound_direct(case.L, ref, family, fm) for fm in "fm")
             case._bounds[family] = (df, dm, None)
@@ -95,7 +138,14 @@ def check(case, config, linear=False, family=None, rows=None, assert_caps=True):
     comparison kernel, printed only)."""
     ref = case.ref()
     got, fam = case.launch(config, linear)
-    ora = R64.oracle_fp32(case.L, case.x, stride=case.stride, elu=case.elu, residual=case.residual, mul=case.mul, linear=linear)
+    ora = R64.oracle_fp32(case.L, case.x, stride=case.stride, elu=case.elu, residual=case.residual, mul=case.mul, linear=linear, pre=case.addend())
+    df, dm, Bw = _bounds(case, family) if family is not None else (None, None, None)
+    return judge(case.L, ref, got, ora, fam, df, dm, Bw, family, case.cls, case.name, config, linear, rows, assert_caps)
+
+
+def judge(L, ref, got, ora, fam, df, dm, Bw, family, cls, name, config, linear=False, rows=None, assert_caps=True):
+    """Measure one launch's output `got` and the oracle's `ora` against `ref`, print the table line and assert: the kernel family, finiteness,
+    the derived bound (d_f, d_m: the pre-activation bounds), the measured cap, the exact constants."""
     finite = bool(np.isfinite(got).all())
     clean = np.nan_to_num(got, nan=3e38, posinf=3e38, neginf=-3e38)
     if linear:
@@ -107,30 +157,29 @@ def check(case, config, linear=False, family=None, rows=None, assert_caps=True):
     q = float("nan")
     ea_max, ea_rms = e_max, e_rms
     if family is not None:
-        df, dm, Bw = _bounds(case, family)
         bound = np.concatenate([df, dm]) if linear else R64.gated_bound(ref, df, dm)
         q = float((np.abs(clean.astype(np.float64) - truth) / bound).max())
         if Bw is not None:
             # Winograd: no bound in terms of A exists (the transforms amplify).  The asserted statistic is E against the transformed-domain
             # condition term A_w; E against A is printed as E(A): that number shows what Winograd costs.
             e_max, e_rms = R64._stats(np.abs(clean.astype(np.float64) - truth), Bw)
-    row = dict(family=family or f"fp32[{fam}]", cls=case.cls, name=case.name, mode="linear" if linear else "gated", config=config, kernel=fam,
+    row = dict(family=family or f"fp32[{fam}]", cls=cls, name=name, mode="linear" if linear else "gated", config=config, kernel=fam,
                E_max=e_max, E_rms=e_rms, EA_max=ea_max, EA_rms=ea_rms, R_max=r_max, R_rms=r_rms, q=q, finite=finite)
     print("ACC| %-8s | %s | %-44s | %-6s | cfg %3d fam %d | E_max %10.2f | E_rms %9.3f | R_max %8.2f | R_rms %7.3f | E/R max %8.2f rms %8.2f | err/bound %6.3f | E(A) max %10.2f rms %9.3f" % (
-        row["family"], case.cls, case.name, row["mode"], config, fam, e_max, e_rms, r_max, r_rms, e_max / max(r_max, 1e-30), e_rms / max(r_rms, 1e-30), q, ea_max, ea_rms))
+        row["family"], cls, name, row["mode"], config, fam, e_max, e_rms, r_max, r_rms, e_max / max(r_max, 1e-30), e_rms / max(r_rms, 1e-30), q, ea_max, ea_rms))
     if rows is not None:
         rows.append(row)
     if family is None or not assert_caps:
         return row
-    what = f"{family} ({case.cls}) {case.name} {row['mode']} config {config}"
+    what = f"{family} ({cls}) {name} {row['mode']} config {config}"
     assert fam == FAMILY_ID[family], f"{what}: the launch took kernel family {fam}"
     assert finite, f"{what}: non-finite output inside the documented range"
     assert q <= 1.0, f"{what}: {q:.3f} x the derived bound (E_max {e_max:.1f}, E_rms {e_rms:.2f})"
     if r_max >= 1.0:
-        c = R64.measured_cap(family, row["mode"], case.cls)
+        c = R64.measured_cap(family, row["mode"], cls)
         assert e_rms <= c * r_rms and e_max <= c * r_max, f"{what}: E_max {e_max:.2f} E_rms {e_rms:.3f} against {c} x (R_max {r_max:.2f}, R_rms {r_rms:.3f})"
     if not linear:
-        mask, cands = R64.constant_outputs(case.L, ref)
+        mask, cands = R64.constant_outputs(L, ref)
         if mask.any():
             assert bool((np.equal(got, cands[0]) | np.equal(got, cands[1]))[mask].all()), f"{what}: outputs that no product reaches differ from the epilogue constant"
     return row
@@ -253,6 +302,190 @@ def run_family(family, rows=None, assert_caps=True, classes="abcd"):
 @pytest.mark.parametrize("family", ["w4h", "f4x1", "d3h", "d3h_s2", "pxh", "t3h"])
 def test_split_operand_family_against_fp64(hip, family):
     run_family(family)
+
+
+# ------------------------------------------------------------------------------------------ resampled sources, addends, the AFF chain
+# (sources, shifts, cout, H, W): a source coarser than an ODD-sized output, a finer first source, a padded channel group
+SHAPES_RESAMPLED = [([32, 64, 128], (1, 0, -1), 64, 13, 37), ([32, 64], (2, 0), 56, 9, 17)]
+# (sources, shifts, cout, H, W, channels of the addend tensor, f_off, m_off, pre_shift, linear): the layouts of the plan's AFF launches
+# (build() of read_amd/csrc/unet.cpp) at sizes whose last addend row and column are shared by an odd rest, and a padded channel group
+SHAPES_PRE = [([32], (0,), 32, 13, 37, 64, 0, 32, 1, False),
+              ([32, 64], (1, 0), 64, 12, 44, 192, 32, 128, 1, False),
+              ([32, 64, 128], (2, 1, 0), 128, 9, 17, 448, 96, 320, 1, False),
+              ([64], (0,), 56, 11, 38, 112, 0, 56, 2, False),
+              ([64], (0,), 96, 5, 9, 448, 0, 224, 1, True)]
+
+
+def _sources(shape, cls, seed):
+    """-> (L, xs) of class (a) / (d) (tame_layer, unit-scale sources times `amp`) or (b) (checkpoint_like)."""
+    split, shifts, cout, H, W = shape[:5]
+    cin, big = sum(split), max(max(shifts), 0)
+    if cls == "b":
+        L, xb = R64.checkpoint_like(cin, cout, 1, H << big, W << big, seed)
+    else:
+        L = R64.tame_layer(cin, cout, 1, seed)
+        xb = (np.random.default_rng([seed, cin, H, W]).standard_normal((cin, H << big, W << big)) * (2.0 ** -14 if cls == "d" else 1.0)).astype(np.float32)
+    return L, R64.split_sources(xb, split, shifts, H, W)
+
+
+def cases_resampled():
+    for j, shape in enumerate(SHAPES_RESAMPLED):
+        for cls in "ab":
+            L, xs = _sources(shape, cls, 900 + j)
+            yield Case("pxh", cls, f"resampled {shape[0]} shifts {shape[1]}->{shape[2]} {shape[3]}x{shape[4]}", L, None, elu=j == 0, xs=xs, shifts=shape[1])
+
+
+def cases_pre(cls):
+    """The cases of one class over SHAPES_PRE: (case, linear)."""
+    for j, shape in enumerate(SHAPES_PRE):
+        split, shifts, cout, H, W, C, f_off, m_off, sh, linear = shape
+        tag = f"{split}->{cout} {H}x{W} addend C={C} ({f_off},{m_off})>>{sh}"
+        rng = np.random.default_rng([910 + j, ord(cls)])
+        pre_shape = R64.addend_size(sh, H, W) + (C,)
+        mk = lambda name, L, xs, t, **kw: (Case("pxh_pre", cls, f"{name} {tag}", L, None, xs=xs, shifts=shifts, pre=(t, f_off, m_off, sh), **kw), linear)   # noqa: E731
+        if cls == "a":
+            L, xs = _sources(shape, "a", 910 + j)
+            yield mk("unit scale", L, xs, R64.addend_tensor(rng, pre_shape, f_off, m_off, cout), elu=j % 2 == 0,
+                     residual=_res(rng, cout, H, W) if (j == 1 and not linear) else None)
+        elif cls == "b":
+            L, xs = _sources(shape, "b", 920 + j)
+            t = R64.addend_tensor(rng, pre_shape, f_off, m_off, cout, 2.0 ** rng.uniform(-8, 8, cout))
+            yield mk("checkpoint-like, addend 2^U(-8,8)", L, xs, t, elu=j % 2 == 0)
+            own = R64.reference(L, R64.assemble(xs, shifts, H, W)).f
+            yield mk("checkpoint-like, cancelling addend", L, xs, R64.cancelling_addend(t, own, f_off, sh), elu=j % 2 == 1)
+        elif cls == "d":
+            L, xs = _sources(shape, "d", 930 + j)
+            yield mk("small scale 2^-14", L, xs, R64.addend_tensor(rng, pre_shape, f_off, m_off, cout, 2.0 ** -14))
+        elif cls == "c":
+            L = R64.tame_layer(sum(split), cout, 1, 940 + j)
+            zeros = [np.zeros((c,) + hw, np.float32) for c, hw in zip(split, R64.source_sizes(shifts, H, W))]
+            for (py, px, c) in R64.addend_impulse_spots(pre_shape[:2], cout):
+                for off, br in ((f_off, "f"), (m_off, "m")):
+                    t = np.full(pre_shape, R64.SENTINEL, np.float32)
+                    t[..., f_off:f_off + cout] = 0.0
+                    t[..., m_off:m_off + cout] = 0.0
+                    t[py, px, off + c] = 1.0
+                    yield mk(f"x = 0, addend 1 at ({py},{px}) {br}{c}", L, zeros, t)
+            if j == 0:                                                              # the input impulses of the other families, with a constant addend
+                t = np.full(pre_shape, R64.SENTINEL, np.float32)
+                t[..., f_off:f_off + cout] = 0.5
+                t[..., m_off:m_off + cout] = -0.25
+                for (c, y, x_) in R64.impulse_positions(sum(split), H, W):
+                    yield mk(f"impulse 1 at c{c} ({y},{x_}), constant addend", L, [R64.impulse(sum(split), H, W, c, y, x_, 1.0)], t)
+
+
+def test_resampled_sources_against_fp64(hip):
+    """The (ly << sl) >> sr addressing of gated_conv_pxh_kernel's loader at sizes that are NOT powers of two apart (13 x 37 read from
+    7 x 19 and from 26 x 74; 9 x 17 from 36 x 68), forced (config -10) and automatic: family 7 both, the bound and caps of family pxh."""
+    for case in cases_resampled():
+        for cfg in (FORCE["pxh"], -1):
+            check(case, cfg, family="pxh")
+
+
+@pytest.mark.parametrize("cls", ["a", "b", "c", "d"])
+def test_pxh_with_addend_against_fp64(hip, cls):
+    """gated_conv_pxh_kernel with a host-given pre-activation addend in the layouts of the plan (pre_f_off != 0, pre_m_off != Cout,
+    pre_cstride > 2 Cout, a last addend row / column shared by an odd output size, a padded channel group, pre_shift 2, a linear launch),
+    against reference(..., pre=...) and preact_bound_direct(own) + u |f| (tests/conv_ref64.py, "A launch with an addend"), config -10 and
+    -1, family 7 both.  The addend tensor and the channels of `out` beyond the launch's own stay as they were (Case.launch)."""
+    for case, linear in cases_pre(cls):
+        for cfg in (FORCE["pxh_pre"], -1):
+            check(case, cfg, linear=linear, family="pxh_pre")
+
+
+@pytest.mark.parametrize("cls", ["a", "b"])
+def test_aff_chain_against_fp64(hip, cls):
+    """The six launches of the default plan's AFF chain (R64.AFF_PLAN: q3 -> q2 -> AFF2 -> q1 -> AFF1 -> AFF0) on res1 32 x 20 x 36,
+    res2 64 x 10 x 18, res3 128 x 5 x 9, z 256 x 3 x 5: each of q3, q2, q1 and each gated output against the float64 reference of the UNSPLIT
+    layer on assemble(...) and the bound composed level by level; config -10 and -1, every launch family 7."""
+    from read_amd import _lib
+    layers, xs = R64.aff_chain_inputs(cls)
+    refs = R64.aff_chain_reference(layers, xs)
+    for cfg in (FORCE["chain"], -1):
+        fams = {}
+
+        def launch(name, Lp, srcs, pre, linear, hw):
+            pk = _pack(Lp, [x.shape[0] for x, _ in srcs])
+            srcs_d = [(_nhwc(x), s) for x, s in srcs]
+            kw = dict(config=cfg, linear=linear, pre=pre)
+            fams[name] = _lib.lib().read_conv_kernel_family(ctypes.byref(conv_desc(pk, srcs_d, **kw)))
+            out = gated_conv(pk, srcs_d, **kw)
+            assert tuple(out.shape[:2]) == tuple(hw), (name, out.shape, hw)
+            return out
+
+        outs = R64.run_aff_chain(layers, xs, launch)
+        torch.cuda.synchronize()
+        for name, (ref, df, dm, Lfull, xfull) in refs.items():
+            linear = name.startswith("q")
+            got = outs[name].cpu().numpy().transpose(2, 0, 1)
+            judge(Lfull, ref, got, R64.oracle_fp32(Lfull, xfull, linear=linear), fams[name], df, dm, None, "chain", cls,
+                  f"{name} of the chain ({'tame' if cls == 'a' else 'checkpoint-like'})", cfg, linear=linear)
+
+
+# ------------------------------------------------------------------------------------------ the output head and the up-sampling
+SHAPES_SC = [(3, 9, 33), (3, 17, 65), (4, 8, 32), (1, 9, 33)]          # (cout, H, W): READ's 32 -> 3 head on partial 8 x 32 tiles, a full tile, one channel
+
+
+def cases_sc(cls):
+    for j, (cout, H, W) in enumerate(SHAPES_SC):
+        rng = np.random.default_rng([950 + j, ord(cls)])
+        tag = f"32->{cout} {H}x{W}"
+        for elu in (True, False):
+            if cls == "a":
+                yield Case("sc", cls, f"unit scale {tag} elu={elu}", R64.tame_layer(32, cout, 3, 950 + j), rng.standard_normal((32, H, W)).astype(np.float32), elu=elu)
+            elif cls == "b":
+                L, x = R64.checkpoint_like(32, cout, 3, H, W, 960 + j, edge_rows=(j == 1))        # (the edge rows would be all of a 3-row layer)
+                yield Case("sc", cls, f"checkpoint-like {tag} elu={elu}", L, x, elu=elu)
+            elif cls == "d":
+                for amp, label in ((2.0 ** -14, "2^-14"), (1e-6, "1e-6")):
+                    yield Case("sc", cls, f"small scale {label} {tag} elu={elu}", R64.tame_layer(32, cout, 3, 970 + j), (rng.standard_normal((32, H, W)) * amp).astype(np.float32), elu=elu)
+            elif cls == "c" and j == 0:
+                L = R64.tame_layer(32, cout, 3, 980)
+                for amp in (1.0, 2.0 ** -10):
+                    for (c, y, x_) in R64.impulse_positions(32, H, W):
+                        if elu or (y in (0, H - 1) or x_ in (0, W - 1)):                         # without ELU: the border impulses
+                            yield Case("sc", cls, f"impulse {amp:g} at c{c} ({y},{x_}) elu={elu}", L, R64.impulse(32, H, W, c, y, x_, amp), elu=elu)
+                yield Case("sc", cls, f"constant 1 elu={elu}", L, R64.constant_image(32, H, W), elu=elu)
+                yield Case("sc", cls, f"checkerboard +-1 elu={elu}", L, R64.checkerboard(32, H, W), elu=elu)
+
+
+@pytest.mark.parametrize("cls", ["a", "b", "c", "d"])
+def test_output_head_against_fp64(hip, cls):
+    """gated_conv_smallc_kernel (config -6, family 1): 288 sequential v_fmac_f32 per accumulator, against 288 u A + u |f| and the gate
+    epilogue's bound (tests/conv_ref64.py, "The output head")."""
+    for case in cases_sc(cls):
+        check(case, FORCE["sc"], family="sc")
+
+
+def test_output_head_fill(hip):
+    """out_channels = 4, fill = 1.0 on the 32 -> 3 head: the fourth channel is the fill, exactly, and the three real ones are the bits of
+    the launch without it."""
+    case = next(iter(cases_sc("a")))
+    plain, fam = case.launch(FORCE["sc"])
+    filled, fam4 = case.launch(FORCE["sc"], out_channels=4, fill=1.0)
+    assert fam == 1 and fam4 == 1 and filled.shape[0] == 4
+    assert bool((filled[3] == np.float32(1.0)).all()) and _same_bits(np.ascontiguousarray(filled[:3]), plain)
+
+
+SHAPES_UP4 = [(32, 1, 1), (64, 3, 2), (128, 5, 19), (256, 2, 7)]          # (C, h, w)
+
+
+def test_bilinear_up4_against_fp64(hip):
+    """bilinear_up4_kernel against the float64 restatement of the formula (R64.bilinear_up4_ref) and 4 u sum w |v|, on unit-scale and
+    per-channel-scaled inputs; a constant image of 1.0 comes back exactly 1.0."""
+    from read_amd.gated_conv import bilinear_up4
+    for j, (c, h, w) in enumerate(SHAPES_UP4):
+        rng = np.random.default_rng([990 + j])
+        for label, scale in (("unit scale", np.ones(c)), ("2^U(-8,8) per channel", 2.0 ** rng.uniform(-8, 8, c))):
+            x = (rng.standard_normal((c, h, w)) * scale[:, None, None]).astype(np.float32)
+            got = bilinear_up4(_nhwc(x)).cpu().numpy().transpose(2, 0, 1)
+            want, absum = R64.bilinear_up4_ref(x)
+            err = np.abs(got.astype(np.float64) - want)
+            q = float((err / R64.bilinear_up4_bound(absum)).max())
+            print("ACC| up4      | %s | %-44s | E_max %6.2f | err/bound %6.3f" % ("a" if label == "unit scale" else "b", f"{label} {c} {h}x{w}", R64._stats(err, absum)[0], q))
+            assert got.shape == (c, 4 * h, 4 * w) and q <= 1.0, (c, h, w, label, q)
+        ones = bilinear_up4(_nhwc(np.ones((c, h, w), np.float32))).cpu().numpy()
+        assert bool((ones == np.float32(1.0)).all()), (c, h, w)
 
 
 # ------------------------------------------------------------------------------------------ the persistent walk
