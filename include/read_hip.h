@@ -406,6 +406,22 @@ typedef struct read_gather_table {
 int read_gather_forward_tables(const read_gather_table *tables, int count, int C, int levels,
                                const int32_t *const *idx_levels, const int64_t *count_levels,
                                float *const *feat_levels, void *stream);
+/* Its adjoint (csrc/gather.hip, gather_tables_backward_kernel; the definition is tests/joint_texture_model.py): the gradient with respect
+ * to the RAW rows, g = dfeat * act_t'(y), y = the forward's output of that pixel (feat_levels, the levels read_gather_forward_tables
+ * wrote; may be NULL when every table's activation is 0): act' = 1 (none), y (1 - y) (sigmoid), 1 - y y (tanh).  Same item mapping,
+ * table selection and clamps as the forward, so the row addressed is exactly the row the forward read (an id below 0: row 0 of table 0;
+ * an id in a gap or past the end: the last row of the last table whose base is <= id).  Two outputs, either or both:
+ *   pairs  g_levels[l] is [count_l][C]: g of every pixel, written once — deterministic, no atomics; with the level's ids these are the
+ *          (id, gradient row) pairs read_rmsprop_sorted_tables takes.  With activation 0, g == dfeat bit for bit.
+ *   dense  drows_tables[t] is table t's [n_t][C] gradient rows, g added by fp32 atomics at the local id; a NULL entry = that table is
+ *          frozen: nothing of it is written.
+ * All levels in one launch; stream-ordered, allocates nothing, no synchronisation.  READ_EINVAL before any device work for everything
+ * read_gather_forward_tables refuses (rows_nc itself is not read and may be NULL), and: feat_levels NULL while some activation is not 0,
+ * neither output requested (g_levels NULL and no non-NULL entry of drows_tables), a buffer that is not 16-byte aligned. */
+int read_gather_backward_tables(const read_gather_table *tables, int count, int C, int levels,
+                                const int32_t *const *idx_levels, const int64_t *count_levels,
+                                const float *const *dfeat_levels, const float *const *feat_levels,
+                                float *const *g_levels, float *const *drows_tables, void *stream);
 /*
  * Scene stitching: several fitted scenes ("parts", 1..READ_STITCH_MAX_PARTS) in one frame.  Every part is rasterised on its own
  * (read_splat_forward*, camera M_s = M_0 @ P_s) into a pyramid of LOCAL ids and depths; this call merges the pyramids and gathers
@@ -752,6 +768,23 @@ size_t read_rmsprop_sorted_scratch_ints(void);
 int read_rmsprop_sorted(float *rows, float *sq, int32_t *stamp, int C, int64_t n_rows, const int32_t *sorted_ids,
                         const int64_t *perm, const float *g, int64_t n, int step, float lr, float alpha, float eps,
                         int32_t *scratch, void *stream);
+/* The sorted update over a TABLE LIST (read_gather_table's id ranges: table t of count, 1..READ_GATHER_MAX_TABLES, owns the merged ids
+ * [id_base_t, id_base_t + n_t); id_base_0 = 0, bases ascend, ranges do not overlap, gaps may remain): sorted_ids are merged ids.  One
+ * pass over the sorted pairs; the head of every run finds its table (the last whose base is <= id), sums the run in sorted order and
+ * updates (rows_t, sq_t, stamp_t) at the local id with THAT table's step.  With contiguous ranges and equal steps this is
+ * read_rmsprop_sorted on the concatenated table; count = 1: read_rmsprop_sorted itself, bit for bit.
+ * A run whose id is below 0, in a gap, past the last range, or in a table with trainable == 0 is SKIPPED: no state is touched.  This
+ * deliberately differs from the gather's clamp (read_gather_forward_tables reads the nearest row for such an id): as in
+ * read_rmsprop_sorted an out-of-range id is a caller's error that the id range check reports, not a row to train.
+ * scratch: read_rmsprop_sorted_scratch_ints() int32, as read_rmsprop_sorted's.  A table with trainable == 0 may leave rows / sq / stamp
+ * NULL and step 0.  READ_EINVAL before any device work for: a null table list, sorted_ids, perm, g or scratch, count outside
+ * 1..READ_GATHER_MAX_TABLES, C outside 1..16, n < 0, a table with n < 1, bases that break the rule above or leave the int32 range, a
+ * trainable table with a null pointer or step < 1. */
+typedef struct read_rmsprop_table {
+    float *rows; float *sq; int32_t *stamp; int64_t n; int64_t id_base; int step; int trainable;
+} read_rmsprop_table;
+int read_rmsprop_sorted_tables(const read_rmsprop_table *tables, int count, int C, const int32_t *sorted_ids, const int64_t *perm,
+                               const float *g, int64_t n, float lr, float alpha, float eps, int32_t *scratch, void *stream);
 
 /* ---------------------------------------------------------------- UNet */
 

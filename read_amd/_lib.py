@@ -79,6 +79,12 @@ class GatherTable(C.Structure):
     _fields_ = [("rows_nc", C.c_void_p), ("n", C.c_int64), ("id_base", C.c_int64), ("activation", C.c_int)]
 
 
+class RmspropTable(C.Structure):
+    """read_rmsprop_table (include/read_hip.h): one table of a read_rmsprop_sorted_tables call (trainable 0 = frozen)."""
+    _fields_ = [("rows", C.c_void_p), ("sq", C.c_void_p), ("stamp", C.c_void_p), ("n", C.c_int64), ("id_base", C.c_int64),
+                ("step", C.c_int), ("trainable", C.c_int)]
+
+
 READ_ANNOTATE_STATS = 12
 
 
@@ -160,6 +166,7 @@ SIGNATURES = {
     "read_gather_forward_ss": (_i, [_vp, _i64, _i, _i, _i, _pp, C.POINTER(_i), C.POINTER(_i), _i, _pp, _i, _vp]),
     "read_gather_forward_tables": (_i, [C.POINTER(GatherTable), _i, _i, _i, _pp, C.POINTER(_i64), _pp, _vp]),
     "read_gather_backward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _vp]),
+    "read_gather_backward_tables": (_i, [C.POINTER(GatherTable), _i, _i, _i, _pp, C.POINTER(_i64), _pp, _pp, _pp, _pp, _vp]),
     "read_stitch_gather_forward": (_i, [C.POINTER(StitchPart), _i, _i, _i, C.POINTER(_i64), _pp, _pp, _pp, _pp, _vp]),
     "read_bilinear_down": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
     "read_bilinear_down_backward": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp]),
@@ -225,6 +232,7 @@ SIGNATURES = {
     "read_rmsprop_sparse": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _vp, _i64, _i, _f, _f, _f, _vp]),
     "read_rmsprop_sorted_scratch_ints": (_sz, []),
     "read_rmsprop_sorted": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _i64, _i, _f, _f, _f, _vp, _vp]),
+    "read_rmsprop_sorted_tables": (_i, [C.POINTER(RmspropTable), _i, _i, _vp, _vp, _vp, _i64, _f, _f, _f, _vp, _vp]),
     "read_unet_layer_count": (_i, []),
     "read_unet_layer_info": (_i, [_i, C.POINTER(C.c_char_p), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                   C.POINTER(_i), C.POINTER(_i)]),

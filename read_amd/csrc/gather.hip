@@ -8,6 +8,8 @@
 // Backward = scatter-add of dL/dfeat into the rows (autograd of texture.py:61).
 // HBM-bound: algorithmic bytes = sum_l px_l * (4 + 4C + 4C).
 // Scene stitching (stitch_gather_kernel): the same gather over S parts' pyramids, the nearest part per pixel — 8S + 4C + 4C.
+// Several tables behind one index image (gather_tables_kernel) and its adjoint (gather_tables_backward_kernel: 4 + 4C + 4C [+ 4C with an
+// activation] per pixel in pairs mode) — what a stitched scene trains through.
 #include "common.h"
 
 using namespace readhip;
@@ -306,6 +308,78 @@ __global__ __launch_bounds__(256) void gather_backward_kernel(float *__restrict_
     }
 }
 
+// The adjoint of gather_tables_kernel (read_gather_backward_tables): its item mapping, its table selection and its clamps, so the row
+// addressed is the row the forward read.  g = dfeat * act'(y) from the forward's own output y; written per pixel (pairs: one 16-byte
+// store per lane, no atomics) and / or added into the selected table's gradient rows (dense; a NULL table is frozen and skipped).
+struct GatherTablesBwd {
+    float *drows[READ_GATHER_MAX_TABLES];
+    long long n[READ_GATHER_MAX_TABLES];
+    long long base[READ_GATHER_MAX_TABLES];
+    int act[READ_GATHER_MAX_TABLES];
+    int count;
+};
+
+struct LevelTableBwdT {
+    const int32_t *idx[READ_MAX_LEVELS];
+    const float *dfeat[READ_MAX_LEVELS];
+    const float *feat[READ_MAX_LEVELS];       // the forward's output; not read where the selected table's activation is 0
+    float *g[READ_MAX_LEVELS];                // pairs mode: all levels set, or none (then want_pairs is 0)
+    long long end[READ_MAX_LEVELS];
+    int levels;
+};
+
+__device__ __forceinline__ float act_slope(float y, int activation)      // act'(x) from y = act(x)
+{
+    return activation == 1 ? y * (1.0f - y) : 1.0f - y * y;
+}
+
+__global__ __launch_bounds__(256) void gather_tables_backward_kernel(GatherTablesBwd tt, int C, LevelTableBwdT tab, int want_pairs,
+                                                                     int want_dense)
+{
+    const int qpp = C >> 2;
+    const long long total = tab.end[tab.levels - 1];
+    for (long long item = (long long)blockIdx.x * blockDim.x + threadIdx.x; item < total;
+         item += (long long)gridDim.x * blockDim.x) {
+        int l = 0;
+        long long base = 0;
+#pragma unroll
+        for (int k = 0; k < READ_MAX_LEVELS - 1; ++k)
+            if (k < tab.levels - 1 && item >= tab.end[k]) { l = k + 1; base = tab.end[k]; }
+        const long long local = item - base;
+        const long long pix = local / qpp;
+        const int q = (int)(local - pix * qpp);
+        const long long gid = tab.idx[l][pix];
+        float *drows = tt.drows[0];
+        long long n = tt.n[0], b = 0;
+        int act = tt.act[0];
+        for (int t = 1; t < tt.count; ++t) {
+            const bool take = gid >= tt.base[t];
+            drows = take ? tt.drows[t] : drows;
+            n = take ? tt.n[t] : n;
+            b = take ? tt.base[t] : b;
+            act = take ? tt.act[t] : act;
+        }
+        long long id = gid - b;
+        id = id < 0 ? 0 : (id >= n ? n - 1 : id);
+        float4 g = *reinterpret_cast<const float4 *>(tab.dfeat[l] + pix * C + 4 * q);
+        if (act) {
+            const float4 y = *reinterpret_cast<const float4 *>(tab.feat[l] + pix * C + 4 * q);
+            g.x *= act_slope(y.x, act);
+            g.y *= act_slope(y.y, act);
+            g.z *= act_slope(y.z, act);
+            g.w *= act_slope(y.w, act);
+        }
+        if (want_pairs) *reinterpret_cast<float4 *>(tab.g[l] + pix * C + 4 * q) = g;
+        if (want_dense && drows) {
+            float *dst = drows + id * C + 4 * q;
+            atomicAdd(dst + 0, g.x);
+            atomicAdd(dst + 1, g.y);
+            atomicAdd(dst + 2, g.z);
+            atomicAdd(dst + 3, g.w);
+        }
+    }
+}
+
 // (C, N) -> N x C: lane = point, C strided-but-coalesced loads, one contiguous row store.
 __global__ __launch_bounds__(256) void texture_to_rows_kernel(const float *__restrict__ tex, long long n, int C,
                                                               float *__restrict__ rows)
@@ -342,6 +416,36 @@ int check_levels(const char *who, int64_t n, int C, int levels, const void *idx,
     READ_CHECK_ARG(C >= 4 && C % 4 == 0 && C <= 64, "%s: C must be a multiple of 4 in [4,64] (got %d)", who, C);
     READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d", who, READ_MAX_LEVELS);
     READ_CHECK_ARG(idx && count && ptrs, "%s: null level table", who);
+    return READ_OK;
+}
+
+// The table list of read_gather_forward_tables / read_gather_backward_tables: the id-range rule, checked once for both.  The backward
+// never reads the rows (need_rows false).
+int fill_tables(const char *who, const read_gather_table *tables, int count, GatherTables *tt, bool need_rows = true)
+{
+    memset(tt, 0, sizeof(*tt));
+    for (int t = 0; t < count; ++t) {
+        const read_gather_table &g = tables[t];
+        READ_CHECK_ARG(!need_rows || (g.rows_nc && (uintptr_t)g.rows_nc % 16 == 0), "%s: table %d: rows null or misaligned", who, t);
+        READ_CHECK_ARG(g.n >= 1, "%s: table %d: empty descriptor table", who, t);
+        READ_CHECK_ARG(g.activation >= 0 && g.activation <= 2, "%s: table %d: activation must be 0,1,2", who, t);
+        if (t == 0)
+            READ_CHECK_ARG(g.id_base == 0, "%s: table 0: id_base must be 0 (got %lld)", who, (long long)g.id_base);
+        else {
+            READ_CHECK_ARG(g.id_base > tables[t - 1].id_base, "%s: table %d: id_base %lld does not ascend", who, t,
+                           (long long)g.id_base);
+            READ_CHECK_ARG(g.id_base >= tables[t - 1].id_base + tables[t - 1].n,
+                           "%s: table %d: id_base %lld overlaps the range of table %d, which ends at %lld", who, t,
+                           (long long)g.id_base, t - 1, (long long)(tables[t - 1].id_base + tables[t - 1].n));
+        }
+        READ_CHECK_ARG(g.id_base <= (int64_t)INT32_MAX && g.n <= (int64_t)INT32_MAX && g.id_base + g.n <= (int64_t)INT32_MAX,
+                       "%s: table %d: id_base %lld + n %lld leaves the int32 id range", who, t, (long long)g.id_base, (long long)g.n);
+        tt->rows[t] = g.rows_nc;
+        tt->n[t] = g.n;
+        tt->base[t] = g.id_base;
+        tt->act[t] = g.activation;
+    }
+    tt->count = count;
     return READ_OK;
 }
 
@@ -411,29 +515,8 @@ extern "C" int read_gather_forward_tables(const read_gather_table *tables, int c
     READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d (got %d)", who, READ_MAX_LEVELS, levels);
     READ_CHECK_ARG(tables && idx_levels && count_levels && feat_levels, "%s: null table list or level table", who);
     GatherTables tt;
-    memset(&tt, 0, sizeof(tt));
-    for (int t = 0; t < count; ++t) {
-        const read_gather_table &g = tables[t];
-        READ_CHECK_ARG(g.rows_nc && (uintptr_t)g.rows_nc % 16 == 0, "%s: table %d: rows null or misaligned", who, t);
-        READ_CHECK_ARG(g.n >= 1, "%s: table %d: empty descriptor table", who, t);
-        READ_CHECK_ARG(g.activation >= 0 && g.activation <= 2, "%s: table %d: activation must be 0,1,2", who, t);
-        if (t == 0)
-            READ_CHECK_ARG(g.id_base == 0, "%s: table 0: id_base must be 0 (got %lld)", who, (long long)g.id_base);
-        else {
-            READ_CHECK_ARG(g.id_base > tables[t - 1].id_base, "%s: table %d: id_base %lld does not ascend", who, t,
-                           (long long)g.id_base);
-            READ_CHECK_ARG(g.id_base >= tables[t - 1].id_base + tables[t - 1].n,
-                           "%s: table %d: id_base %lld overlaps the range of table %d, which ends at %lld", who, t,
-                           (long long)g.id_base, t - 1, (long long)(tables[t - 1].id_base + tables[t - 1].n));
-        }
-        READ_CHECK_ARG(g.id_base <= (int64_t)INT32_MAX && g.n <= (int64_t)INT32_MAX && g.id_base + g.n <= (int64_t)INT32_MAX,
-                       "%s: table %d: id_base %lld + n %lld leaves the int32 id range", who, t, (long long)g.id_base, (long long)g.n);
-        tt.rows[t] = g.rows_nc;
-        tt.n[t] = g.n;
-        tt.base[t] = g.id_base;
-        tt.act[t] = g.activation;
-    }
-    tt.count = count;
+    int rc = fill_tables(who, tables, count, &tt);
+    if (rc) return rc;
     LevelTable tab;
     memset(&tab, 0, sizeof(tab));
     long long acc = 0;
@@ -581,6 +664,66 @@ extern "C" int read_gather_backward(float *drows_nc, int64_t n, int C, int level
     if (blocks > 256 * 8) blocks = 256 * 8;
     hipLaunchKernelGGL(gather_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), drows_nc,
                        (long long)n, C, tab);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+extern "C" int read_gather_backward_tables(const read_gather_table *tables, int count, int C, int levels,
+                                           const int32_t *const *idx_levels, const int64_t *count_levels,
+                                           const float *const *dfeat_levels, const float *const *feat_levels,
+                                           float *const *g_levels, float *const *drows_tables, void *stream)
+{
+    const char *who = "read_gather_backward_tables";
+    READ_CHECK_ARG(count >= 1 && count <= READ_GATHER_MAX_TABLES, "%s: count must be 1..%d tables (got %d)", who,
+                   READ_GATHER_MAX_TABLES, count);
+    READ_CHECK_ARG(C >= 4 && C % 4 == 0 && C <= 64, "%s: C must be a multiple of 4 in [4,64] (got %d)", who, C);
+    READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d (got %d)", who, READ_MAX_LEVELS, levels);
+    READ_CHECK_ARG(tables && idx_levels && count_levels && dfeat_levels, "%s: null table list or level table", who);
+    GatherTables fwd;
+    int rc = fill_tables(who, tables, count, &fwd, false);
+    if (rc) return rc;
+    GatherTablesBwd tt;
+    memset(&tt, 0, sizeof(tt));
+    bool any_act = false, any_dense = false;
+    for (int t = 0; t < count; ++t) {
+        tt.n[t] = fwd.n[t];
+        tt.base[t] = fwd.base[t];
+        tt.act[t] = fwd.act[t];
+        any_act = any_act || fwd.act[t] != 0;
+        if (drows_tables && drows_tables[t]) {
+            READ_CHECK_ARG((uintptr_t)drows_tables[t] % 16 == 0, "%s: table %d: gradient rows misaligned", who, t);
+            tt.drows[t] = drows_tables[t];
+            any_dense = true;
+        }
+    }
+    tt.count = count;
+    READ_CHECK_ARG(feat_levels || !any_act, "%s: feat_levels is null while a table has an activation (act' needs the forward's output)",
+                   who);
+    READ_CHECK_ARG(g_levels || any_dense, "%s: no outputs (g_levels is null and no table has gradient rows)", who);
+    LevelTableBwdT tab;
+    memset(&tab, 0, sizeof(tab));
+    long long acc = 0;
+    const int qpp = C / 4;
+    for (int l = 0; l < levels; ++l) {
+        READ_CHECK_ARG(count_levels[l] >= 0, "%s: negative pixel count", who);
+        READ_CHECK_ARG(count_levels[l] == 0 || (idx_levels[l] && dfeat_levels[l] && (!any_act || feat_levels[l]) &&
+                                                (!g_levels || g_levels[l])), "%s: null level %d", who, l);
+        READ_CHECK_ARG((uintptr_t)dfeat_levels[l] % 16 == 0, "%s: dfeat level %d misaligned", who, l);
+        READ_CHECK_ARG(!any_act || (uintptr_t)feat_levels[l] % 16 == 0, "%s: feat level %d misaligned", who, l);
+        READ_CHECK_ARG(!g_levels || (uintptr_t)g_levels[l] % 16 == 0, "%s: g level %d misaligned", who, l);
+        tab.idx[l] = idx_levels[l];
+        tab.dfeat[l] = dfeat_levels[l];
+        if (any_act) tab.feat[l] = feat_levels[l];
+        if (g_levels) tab.g[l] = g_levels[l];
+        acc += count_levels[l] * qpp;
+        tab.end[l] = acc;
+    }
+    tab.levels = levels;
+    if (acc == 0) return READ_OK;
+    int64_t blocks = ceil_div64(acc, 256);
+    if (blocks > 256 * 8) blocks = 256 * 8;
+    hipLaunchKernelGGL(gather_tables_backward_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), tt, C, tab,
+                       g_levels != nullptr ? 1 : 0, any_dense ? 1 : 0);
     READ_CHECK_LAUNCH();
     return READ_OK;
 }

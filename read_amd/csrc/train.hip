@@ -1699,6 +1699,151 @@ extern "C" int read_rmsprop_sorted(float *rows, float *sq, int32_t *stamp, int C
     return READ_OK;
 }
 
+// The sorted update over a table list (read_rmsprop_sorted_tables): rmsprop_sorted_kernel with the table of a run found by the gather's
+// compare-and-select loop (the last table whose base is <= id; wave-uniform trip count, the list travels by value in the kernel
+// arguments).  Unlike the gather, which clamps, a run that no trainable table owns (id below 0, in a gap, past the end, frozen table)
+// is skipped.  A long run is queued with its MERGED id — long_list keeps its (id, start, length) layout, so rmsprop_long_partial_kernel
+// serves both entry points unchanged — and rmsprop_long_tables_final_kernel resolves the table again.
+struct RmsTables {
+    float *rows[READ_GATHER_MAX_TABLES];
+    float *sq[READ_GATHER_MAX_TABLES];
+    int *stamp[READ_GATHER_MAX_TABLES];
+    long long n[READ_GATHER_MAX_TABLES];
+    long long base[READ_GATHER_MAX_TABLES];
+    int step[READ_GATHER_MAX_TABLES];
+    int count;
+};
+
+struct RmsSlot {
+    float *rows, *sq;
+    int *stamp;
+    long long local;      // < 0: nobody trains this id
+    int step;
+};
+
+__device__ __forceinline__ RmsSlot rms_resolve(const RmsTables &tt, long long id)
+{
+    RmsSlot s = {tt.rows[0], tt.sq[0], tt.stamp[0], 0, tt.step[0]};
+    long long n = tt.n[0], b = 0;
+    for (int t = 1; t < tt.count; ++t) {
+        const bool take = id >= tt.base[t];
+        s.rows = take ? tt.rows[t] : s.rows;
+        s.sq = take ? tt.sq[t] : s.sq;
+        s.stamp = take ? tt.stamp[t] : s.stamp;
+        s.step = take ? tt.step[t] : s.step;
+        n = take ? tt.n[t] : n;
+        b = take ? tt.base[t] : b;
+    }
+    s.local = (id < 0 || id - b >= n || !s.rows) ? -1 : id - b;           // rows == NULL: the table is frozen
+    return s;
+}
+
+__global__ __launch_bounds__(256) void rmsprop_sorted_tables_kernel(RmsTables tt, int C, const int32_t *__restrict__ sorted_ids,
+                                                                    const long long *__restrict__ perm, const float *__restrict__ g,
+                                                                    long long n, float lr, float alpha, float eps,
+                                                                    int *__restrict__ long_list)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long id = sorted_ids[i];
+    if (i > 0 && sorted_ids[i - 1] == id) return;                   // not the head of its run
+    const RmsSlot s = rms_resolve(tt, id);
+    if (s.local < 0) return;
+    long long lo = i + 1, hi = n;                                   // first index past the run
+    while (lo < hi) {
+        const long long mid = (lo + hi) >> 1;
+        if (sorted_ids[mid] == id) lo = mid + 1;
+        else hi = mid;
+    }
+    const long long len = lo - i;
+    if (len > LONG_RUN) {
+        const int slot = atomicAdd(long_list, 1);
+        if (slot < MAX_LONG) {
+            long_list[1 + 3 * slot] = (int)id;
+            long_list[2 + 3 * slot] = (int)i;
+            long_list[3 + 3 * slot] = (int)len;
+            return;
+        }
+    }
+    float acc[RMS_MAX_C];
+    for (int c = 0; c < C; ++c) acc[c] = 0.0f;
+    for (long long j = i; j < lo; ++j) {
+        const float *row = g + perm[j] * C;
+        for (int c = 0; c < C; ++c) acc[c] += row[c];
+    }
+    rmsprop_row(s.rows, s.sq, s.stamp, C, s.local, acc, s.step, lr, alpha, eps);
+}
+
+__global__ __launch_bounds__(64) void rmsprop_long_tables_final_kernel(RmsTables tt, int C, float lr, float alpha, float eps,
+                                                                       const int *__restrict__ long_list,
+                                                                       const float *__restrict__ partial)
+{
+    __shared__ float total[RMS_MAX_C];
+    const int count = long_list[0] < MAX_LONG ? long_list[0] : MAX_LONG;
+    if ((int)blockIdx.x >= count) return;
+    if ((int)threadIdx.x < C) {
+        float s = 0.0f;
+        for (int k = 0; k < LONG_SUB; ++k) s += partial[((size_t)blockIdx.x * LONG_SUB + k) * RMS_MAX_C + threadIdx.x];
+        total[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const RmsSlot s = rms_resolve(tt, long_list[1 + 3 * blockIdx.x]);         // queued runs have an owner: local >= 0
+        rmsprop_row(s.rows, s.sq, s.stamp, C, s.local, total, s.step, lr, alpha, eps);
+    }
+}
+
+extern "C" int read_rmsprop_sorted_tables(const read_rmsprop_table *tables, int count, int C, const int32_t *sorted_ids,
+                                          const int64_t *perm, const float *g, int64_t n, float lr, float alpha, float eps,
+                                          int32_t *scratch, void *stream)
+{
+    const char *who = "read_rmsprop_sorted_tables";
+    READ_CHECK_ARG(count >= 1 && count <= READ_GATHER_MAX_TABLES, "%s: count must be 1..%d tables (got %d)", who,
+                   READ_GATHER_MAX_TABLES, count);
+    READ_CHECK_ARG(tables && sorted_ids && perm && g && scratch, "%s: null pointer", who);
+    READ_CHECK_ARG(C >= 1 && C <= RMS_MAX_C && n >= 0, "%s: bad sizes (C %d must be 1..%d, n %lld)", who, C, RMS_MAX_C, (long long)n);
+    RmsTables tt;
+    memset(&tt, 0, sizeof(tt));
+    for (int t = 0; t < count; ++t) {
+        const read_rmsprop_table &r = tables[t];
+        READ_CHECK_ARG(r.n >= 1, "%s: table %d: empty descriptor table", who, t);
+        if (t == 0)
+            READ_CHECK_ARG(r.id_base == 0, "%s: table 0: id_base must be 0 (got %lld)", who, (long long)r.id_base);
+        else {
+            READ_CHECK_ARG(r.id_base > tables[t - 1].id_base, "%s: table %d: id_base %lld does not ascend", who, t,
+                           (long long)r.id_base);
+            READ_CHECK_ARG(r.id_base >= tables[t - 1].id_base + tables[t - 1].n,
+                           "%s: table %d: id_base %lld overlaps the range of table %d, which ends at %lld", who, t,
+                           (long long)r.id_base, t - 1, (long long)(tables[t - 1].id_base + tables[t - 1].n));
+        }
+        READ_CHECK_ARG(r.id_base <= (int64_t)INT32_MAX && r.n <= (int64_t)INT32_MAX && r.id_base + r.n <= (int64_t)INT32_MAX,
+                       "%s: table %d: id_base %lld + n %lld leaves the int32 id range", who, t, (long long)r.id_base, (long long)r.n);
+        tt.n[t] = r.n;
+        tt.base[t] = r.id_base;
+        if (!r.trainable) continue;                                 // frozen: its pointers stay NULL in the kernel's list
+        READ_CHECK_ARG(r.rows && r.sq && r.stamp, "%s: table %d: trainable with a null rows / sq / stamp", who, t);
+        READ_CHECK_ARG(r.step >= 1, "%s: table %d: step must be >= 1 (got %d)", who, t, r.step);
+        tt.rows[t] = r.rows;
+        tt.sq[t] = r.sq;
+        tt.stamp[t] = r.stamp;
+        tt.step[t] = r.step;
+    }
+    tt.count = count;
+    if (n == 0) return READ_OK;
+    READ_CHECK_HIP(hipMemsetAsync(scratch, 0, sizeof(int), as_stream(stream)));
+    hipLaunchKernelGGL(rmsprop_sorted_tables_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, as_stream(stream), tt, C,
+                       sorted_ids, (const long long *)perm, g, (long long)n, lr, alpha, eps, scratch);
+    READ_CHECK_LAUNCH();
+    float *partial = reinterpret_cast<float *>(scratch + LONG_LIST_WORDS);
+    hipLaunchKernelGGL(rmsprop_long_partial_kernel, dim3(LONG_SUB, MAX_LONG), dim3(256), 0, as_stream(stream), C,
+                       (const long long *)perm, g, (const int *)scratch, partial);
+    READ_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rmsprop_long_tables_final_kernel, dim3(MAX_LONG), dim3(64), 0, as_stream(stream), tt, C, lr, alpha, eps,
+                       (const int *)scratch, (const float *)partial);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
 extern "C" int read_rmsprop_sparse(float *rows, float *sq, float *grad, int32_t *stamp, int C, int64_t n_rows,
                                    const int32_t *ids, int64_t n_ids, int step, float lr, float alpha, float eps, void *stream)
 {

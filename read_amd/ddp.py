@@ -191,6 +191,10 @@ class DataParallelStep:
     def __init__(self, net, textures=(), group=None, broadcast=True):
         # pipeline.textures is {dataset id: PointTexture} (READ/pipelines/ogl.py:82-97): a mapping gives its values
         self.net, self.textures, self.group = net, list(textures.values() if hasattr(textures, 'values') else textures), group
+        for tex in self.textures:
+            if hasattr(tex, 'parts'):
+                raise NotImplementedError("a JointTexture under DataParallelStep: the ragged all-gather of descriptor pairs is per "
+                                          "single table; train the joint on one GPU, or its parts as PointTextures")
         self.arena = GradientArena(net.parameters(), group)
         if broadcast:                                    # as torch DDP at construction: parameters, buffers — and the descriptor tables
             broadcast_parameters(net, 0, group)

@@ -18,7 +18,7 @@ the UNet engine consumes without a copy.
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-from .texture import _RangeCheck, bilinear_down, gather_pyramid
+from .texture import PointTexture, _RangeCheck, bilinear_down
 from .unet import UNet
 
 
@@ -88,14 +88,18 @@ class NetAndTexture(nn.Module):
         tokens = list(item)
         assert 'uv' in tokens[0], 'first input must be uv'
         only_uv = all('uv' in t for t in tokens)
-        needs_grad = torch.is_grad_enabled() and texture.texture_.requires_grad
+        # the texture is a PointTexture or a JointTexture (merged ids over several tables): both answer device, wants_grad(),
+        # num_ids() and lookup_pyramid(); supersampling over a joint is refused by name
+        if self.ss > 1 and hasattr(texture, 'parts'):
+            raise NotImplementedError(f"supersampling {self.ss} with a JointTexture: the table gather has no bilinear reduce")
+        needs_grad = torch.is_grad_enabled() and texture.wants_grad()
         if only_uv and not needs_grad:
-            ids = [texture._ids(item[t]).to(texture.texture_.device) for t in tokens]
+            ids = [PointTexture._ids(item[t]).to(texture.device) for t in tokens]
             # out-of-range ids (wrong texture for this scene) raise IndexError without a device->host sync per frame:
             # the check of THIS lookup is queued, the previous ones are polled (texture._RangeCheck); the gather clamps
             self._range_check.poll()
-            self._range_check.queue(ids[0], texture.texture_.shape[-1])
-            feats = gather_pyramid(texture.rows(), ids, texture.activation, ss=self.ss)     # ss > 1: fused bilinear reduce
+            self._range_check.queue(ids[0], texture.num_ids())
+            feats = texture.lookup_pyramid(ids, ss=self.ss)                                 # ss > 1: fused bilinear reduce
             return [f.permute(0, 3, 1, 2) for f in feats]
         scales, extras = [], []
         for t in tokens:
@@ -103,7 +107,7 @@ class NetAndTexture(nn.Module):
                 scales.append([texture(item[t])])
                 extras = scales[-1]
             else:
-                extras.insert(len(extras) - 1, item[t].to(texture.texture_.device))
+                extras.insert(len(extras) - 1, item[t].to(texture.device))
         out = [torch.cat(parts, 1) if len(parts) > 1 else parts[0] for parts in scales]
         if self.ss > 1:                         # compose.py:162-163, as a HIP node (differentiable)
             out = [bilinear_down(x, self.ss) for x in out]

@@ -185,6 +185,9 @@ class OGL:
         textures = [model._modules[str(t)] for t in self.texture_ids]
         raster = scene.rasterizer()
         for s, tex in enumerate(textures):
+            if hasattr(tex, 'parts'):
+                raise NotImplementedError(f"a JointTexture as the texture of part {s} on OGL's fast path: the stitched gather takes one "
+                                          "PointTexture per part; pass the parts' own texture ids (the joint serves the dict path)")
             if raster.part(s).n != tex.texture_.shape[-1]:
                 raise ValueError(f"part {s}: descriptor table has {tex.texture_.shape[-1]} points, the part's cloud "
                                  f"{raster.part(s).n}")

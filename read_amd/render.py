@@ -578,6 +578,21 @@ class StitchedScene:
         c = self.counts()
         return [sum(c[:s]) for s in range(len(c))]
 
+    def joint_texture(self, textures):
+        """The parts' PointTextures (one per part, in part order) as ONE ``JointTexture`` over this scene's merged ids — what
+        NetAndTexture looks up and trains with the id pyramid MultiscaleRender draws of this scene."""
+        from .texture import JointTexture
+        textures = list(textures)
+        counts = self.counts()
+        if len(textures) != len(counts):
+            raise ValueError(f"{len(textures)} textures for {len(counts)} parts")
+        for s, (tex, n) in enumerate(zip(textures, counts)):
+            if not hasattr(tex, 'num_ids') or tex.num_ids() != n:
+                have = tex.num_ids() if hasattr(tex, 'num_ids') else type(tex).__name__
+                raise ValueError(f"part {s}: a descriptor table whose size does not match: the table has {have} points, the "
+                                 f"part's cloud {n}")
+        return JointTexture(textures, self.id_base())
+
     def set_part_pose(self, s, P):
         s = self._index(s)
         self.part_poses[s] = None if P is None else np.array(P, np.float32).reshape(4, 4)

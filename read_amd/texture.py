@@ -86,6 +86,38 @@ def gather_tables_pyramid(tables, idx_levels, out=None):
     return out
 
 
+def gather_tables_backward(tables, idx_levels, dfeat_levels, feat_levels=None, pairs=False, drows=None):
+    """The adjoint of ``gather_tables_pyramid`` (read_gather_backward_tables): g = dfeat * act'(y) per pixel, one launch.
+
+    tables: [(n_t, id_base, activation), ...] — n_t the table's row count, or its (n_t, C) rows (only the count is used);
+    dfeat_levels / feat_levels: NHWC gradients and the forward's own outputs [(B,h,w,C)...] (feat_levels may be None when every
+    activation is 'none').  pairs=True -> [(B*h*w, C)...], g of every pixel (no atomics; with the ids: the sorted optimizer's
+    pairs).  drows: None, or one (n_t, C) gradient-row tensor per table to ADD into (None entries: that table is frozen).
+    -> the pairs' levels (or None)."""
+    if not 1 <= len(tables) <= _lib.READ_GATHER_MAX_TABLES:
+        raise ValueError(f"the table gather takes 1..{_lib.READ_GATHER_MAX_TABLES} tables, got {len(tables)}")
+    Cc = int(dfeat_levels[0].shape[-1])
+    table = (_lib.GatherTable * len(tables))()
+    for t, (rows, id_base, activation) in enumerate(tables):
+        table[t].rows_nc, table[t].n = None, int(rows.shape[0]) if torch.is_tensor(rows) else int(rows)
+        table[t].id_base, table[t].activation = int(id_base), _ACT[activation]
+    if drows is not None:
+        if len(drows) != len(tables):
+            raise ValueError(f"drows has {len(drows)} entries for {len(tables)} tables")
+        for t, d in enumerate(drows):
+            if d is not None and (tuple(d.shape) != (table[t].n, Cc) or not d.is_contiguous() or d.dtype != torch.float32):
+                raise ValueError(f"table {t}: gradient rows must be a contiguous fp32 ({table[t].n}, {Cc}) tensor")
+    levels = len(idx_levels)
+    dfeat_levels = [d.contiguous() for d in dfeat_levels]
+    g = [torch.empty((int(i.numel()), Cc), dtype=torch.float32, device=dfeat_levels[0].device) for i in idx_levels] if pairs else None
+    counts = (C.c_int64 * levels)(*[int(i.numel()) for i in idx_levels])
+    arr = lambda ts: None if ts is None else _lib.ptr_array([None if t is None else t.data_ptr() for t in ts])
+    _lib.check(_lib.lib().read_gather_backward_tables(
+        table, len(tables), Cc, levels, arr(idx_levels), counts, arr(dfeat_levels), arr(feat_levels), arr(g), arr(drows),
+        _lib.stream_ptr()), "read_gather_backward_tables")
+    return g
+
+
 def stitch_gather_pyramid(parts, out=None, want_index=False, want_depth=False, want_part=False, want_feat=True, ss=1):
     """Scene stitching (read_stitch_gather_forward): merge the parts' pyramids and gather from the winner's table, one launch.
 
@@ -455,6 +487,187 @@ class PointTexture(Texture):
         """Fast path: int32 index maps of all scales -> NHWC feature maps, one launch."""
         return gather_pyramid(self.rows(), idx_levels, self.activation)
 
+    # ---- what NetAndTexture asks of a texture (JointTexture answers the same four) ----------------------------------------------
+    @property
+    def device(self):
+        return self.texture_.device
+
+    def wants_grad(self):
+        return self.texture_.requires_grad
+
+    def num_ids(self):
+        """Ids 0 .. num_ids() - 1 are valid for this texture."""
+        return int(self.texture_.shape[-1])
+
+    def lookup_pyramid(self, idx_levels, ss=1):
+        """The no-gradient lookup of all scales in one launch; ss > 1: the fused bilinear reduce of gather_pyramid."""
+        return gather_pyramid(self.rows(), idx_levels, self.activation, ss=ss)
+
     def check_ids(self):
         """Wait for the queued id range checks of forward() and raise IndexError if one of them failed."""
         self._range_check.flush()
+
+
+class _JointGatherFn(torch.autograd.Function):
+    """JointTexture's lookup with a gradient: merged ids (B,H,W) -> NHWC (B,H,W,C) through the table gather (the activations are
+    applied inside the launch), backward through its adjoint read_gather_backward_tables.  Sparse mode queues (merged ids, g) on the
+    joint as _GatherRowsFn does on a PointTexture; dense mode returns every trainable part's (1,C,N) gradient.  ``params`` are the
+    trainable parts' ``texture_`` — present so that autograd calls backward at all."""
+
+    @staticmethod
+    def forward(ctx, ids, joint, *params):
+        ctx.joint = joint
+        y = gather_tables_pyramid(joint.tables(), [ids])[0]
+        ctx.save_for_backward(ids, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        ids, y = ctx.saved_tensors
+        m = ctx.joint
+        meta = m.tables(rows=False)
+        feat = [y] if any(p.activation != 'none' for p in m.parts) else None
+        if m.sparse_training:
+            g = gather_tables_backward(meta, [ids], [grad], feat, pairs=True)[0]
+            m._pending.append((ids.reshape(-1), g))
+            ev = torch.cuda.Event()                 # backward may run on a batch item's own stream (NetAndTexture.forward)
+            ev.record()
+            m._scatter_events.append(ev)
+            return (None, None) + (None,) * len(m.trainable_parts())
+        drows = [torch.zeros_like(p.rows()) if p.wants_grad() else None for p in m.parts]
+        gather_tables_backward(meta, [ids], [grad], feat, drows=drows)
+        return (None, None) + tuple(rows_to_texture(d)[None] for d in drows if d is not None)
+
+
+class JointTexture(Texture):
+    """1..8 ``PointTexture`` parts of equal channel count served as ONE texture of merged ids: part t owns the ids
+    [id_base_t, id_base_t + n_t) (``stitch.id_bases`` of the parts' sizes by default; explicit ascending, non-overlapping bases
+    with gaps are accepted — the rule of read_gather_forward_tables).  With equal activations and contiguous ranges, looking up
+    and training through the joint is looking up and training the concatenated table; nothing is concatenated or copied.
+
+    The parts stay ordinary modules: they may be registered elsewhere under their own ids, trained alone in another iteration, and
+    saved by their own ``state_dict``.  A part with ``texture_.requires_grad == False`` is frozen.  ``sparse_training`` is set on
+    the joint and forwarded to the parts; in that mode backward queues (merged ids, gradient rows) on the JOINT (``take_pending``)
+    for ``SparseDescriptorRMSprop``.  Ids below 0 or in a gap are clamped by the lookup as the table gather documents and are never
+    trained; ids past the last range are reported by ``check_ids`` one lookup late, as PointTexture's."""
+
+    def __init__(self, textures, id_bases=None):
+        super().__init__()
+        textures = list(textures)
+        if not 1 <= len(textures) <= _lib.READ_GATHER_MAX_TABLES:
+            raise ValueError(f"a JointTexture has 1..{_lib.READ_GATHER_MAX_TABLES} parts, got {len(textures)}")
+        for t, p in enumerate(textures):
+            if not isinstance(p, PointTexture):
+                raise ValueError(f"part {t}: a JointTexture joins PointTexture modules, got {type(p).__name__}")
+        chans = [int(p.texture_.shape[1]) for p in textures]
+        if len(set(chans)) != 1:
+            raise ValueError(f"the parts' descriptor tables differ in their channel count: {chans}")
+        sizes = [p.num_ids() for p in textures]
+        if id_bases is None:
+            from .stitch import id_bases as prefix_bases
+            id_bases = prefix_bases(sizes)
+        id_bases = [int(b) for b in id_bases]
+        if len(id_bases) != len(textures):
+            raise ValueError(f"id_bases has {len(id_bases)} entries for {len(textures)} parts")
+        if id_bases[0] != 0:
+            raise ValueError(f"id_bases[0] must be 0 (got {id_bases[0]})")
+        for t in range(1, len(id_bases)):
+            if id_bases[t] < id_bases[t - 1] + sizes[t - 1]:
+                raise ValueError(f"part {t}: id_base {id_bases[t]} overlaps the range of part {t - 1}, which ends at "
+                                 f"{id_bases[t - 1] + sizes[t - 1]}")
+        if id_bases[-1] + sizes[-1] > (1 << 31) - 1:
+            raise ValueError(f"merged ids up to {id_bases[-1] + sizes[-1]} leave the int32 id range")
+        self.parts = nn.ModuleList(textures)
+        self.id_bases = id_bases
+        self.num_channels = chans[0]
+        self._range_check = _RangeCheck()
+        self._pending = []                  # (merged ids, gradient rows) pairs the optimizer has not consumed
+        self._scatter_events = []
+        self.sparse_training = any(p.sparse_training for p in textures)
+
+    @property
+    def sparse_training(self):
+        return self._sparse_training
+
+    @sparse_training.setter
+    def sparse_training(self, flag):
+        self._sparse_training = bool(flag)
+        for p in self.parts:
+            p.sparse_training = bool(flag)
+
+    # ---- the parts as a table list ------------------------------------------------------------------------------------------------
+    def tables(self, rows=True):
+        """[(rows_t | n_t, id_base_t, activation_t), ...]: gather_tables_pyramid's / gather_tables_backward's table list."""
+        return [(p.rows() if rows else p.num_ids(), b, p.activation) for p, b in zip(self.parts, self.id_bases)]
+
+    def trainable_parts(self):
+        return [p for p in self.parts if p.wants_grad()]
+
+    @property
+    def device(self):
+        return self.parts[0].device
+
+    def wants_grad(self):
+        return any(p.wants_grad() for p in self.parts)
+
+    def num_ids(self):
+        """The end of the last part's id range."""
+        return self.id_bases[-1] + self.parts[-1].num_ids()
+
+    def _on_gpu(self):
+        for t, p in enumerate(self.parts):
+            if not p.texture_.is_cuda:
+                raise ValueError(f"JointTexture: part {t} is not loaded on the GPU (move the joint, or the module it is registered "
+                                 "in, with .cuda(); NetAndTexture.load_textures takes the joint's own id)")
+
+    def lookup_pyramid(self, idx_levels, ss=1):
+        if ss > 1:
+            raise NotImplementedError(f"supersampling {ss} with a JointTexture: the table gather has no fused bilinear reduce")
+        self._on_gpu()
+        return gather_tables_pyramid(self.tables(), idx_levels)
+
+    def forward_pyramid(self, idx_levels):
+        """Fast path: int32 maps of merged ids at all scales -> NHWC feature maps, one launch."""
+        return self.lookup_pyramid(idx_levels)
+
+    def forward(self, inputs):
+        """merged ids (B,1|3,H,W) float or int -> (B,C,H,W) view of an NHWC tensor."""
+        ids = PointTexture._ids(inputs)
+        self._on_gpu()
+        ids = ids.to(self.device)
+        self._range_check.poll()
+        self._range_check.queue(ids, self.num_ids(), signed=True)
+        if torch.is_grad_enabled() and self.wants_grad():
+            sample = _JointGatherFn.apply(ids, self, *[p.texture_ for p in self.trainable_parts()])
+        else:
+            sample = gather_tables_pyramid(self.tables(), [ids])[0]
+        return sample.permute(0, 3, 1, 2)
+
+    # ---- training state -----------------------------------------------------------------------------------------------------------
+    def null_grad(self):
+        for p in self.parts:
+            p.null_grad()
+        self._pending = []
+        self._scatter_events = []
+
+    def take_pending(self):
+        """(merged ids (n,) int32, gradient rows (n,C)) of every backward pass since the last optimizer step, or None."""
+        if not self._pending:
+            return None
+        cur = torch.cuda.current_stream()
+        for ev in self._scatter_events:             # gradients produced on other streams must have landed
+            cur.wait_event(ev)
+        self._scatter_events = []
+        ids = torch.cat([p[0] for p in self._pending]).contiguous()
+        g = torch.cat([p[1] for p in self._pending]).contiguous()
+        self._pending = []
+        return ids, g
+
+    def reg_loss(self):
+        return sum((p.reg_loss() for p in self.parts), 0.)
+
+    def check_ids(self):
+        """Wait for the queued id range checks (the joint's and the parts') and raise IndexError if one of them failed."""
+        self._range_check.flush()
+        for p in self.parts:
+            p.check_ids()

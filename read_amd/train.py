@@ -895,12 +895,57 @@ class SparseDescriptorRMSprop:
     applied lazily when the row is touched again (csrc/train.hip), which makes every row's trajectory equal the dense one.
 
     Duck-types what ``train.py`` uses of a torch optimizer: ``step()``, ``zero_grad()``, ``param_groups`` (lr),
-    ``state_dict()`` / ``load_state_dict()``."""
+    ``state_dict()`` / ``load_state_dict()``.
+
+    ``textures`` may hold ``JointTexture`` modules: a joint with queued pairs does one sort of its merged ids and one
+    ``read_rmsprop_sorted_tables`` over its parts.  The state (sq, stamp, step) is kept per PART, where a part trained alone keeps
+    it, so a part may be stepped through a joint in one iteration and alone in the next.  When a joint steps, every trainable
+    part's step advances, touched or not: the dense optimizer on the concatenated parameter.  A list without joints takes the
+    single-table path unchanged."""
 
     def __init__(self, textures, lr=1e-1, alpha=0.99, eps=1e-8):
         self.textures = list(textures)
-        self.param_groups = [{'params': [t.texture_ for t in self.textures], 'lr': lr, 'alpha': alpha, 'eps': eps}]
+        self.param_groups = [{'params': [t.texture_ for t in self._tables()], 'lr': lr, 'alpha': alpha, 'eps': eps}]
         self.state = {}
+        self._joint_scratch = {}
+
+    def _tables(self):
+        """The PointTextures that carry state, once each: the list's own and the joints' parts, in order of first appearance."""
+        out, seen = [], set()
+        for tex in self.textures:
+            for t in getattr(tex, 'parts', None) or [tex]:
+                if id(t) not in seen:
+                    seen.add(id(t))
+                    out.append(t)
+        return out
+
+    def _step_joint(self, joint, g):
+        pend = joint.take_pending()
+        live = joint.trainable_parts()
+        if pend is None or not live:
+            return
+        L = _lib.lib()
+        table = (_lib.RmspropTable * len(joint.parts))()
+        for t, (part, base) in enumerate(zip(joint.parts, joint.id_bases)):
+            table[t].n, table[t].id_base = part.num_ids(), int(base)
+            if not part.wants_grad():
+                continue                                      # frozen: trainable 0, no pointers, no state
+            s = self._state(part)
+            s['step'] += 1
+            rows = part.training_rows()
+            table[t].rows, table[t].sq, table[t].stamp = rows.data_ptr(), s['sq'].data_ptr(), s['stamp'].data_ptr()
+            table[t].step, table[t].trainable = s['step'], 1
+        pids, pg = pend
+        sorted_ids, perm = torch.sort(pids, stable=True)
+        scratch = self._joint_scratch.get(pids.device)
+        if scratch is None:
+            scratch = self._joint_scratch[pids.device] = torch.zeros(int(L.read_rmsprop_sorted_scratch_ints()), dtype=torch.int32,
+                                                                     device=pids.device)
+        _lib.check(L.read_rmsprop_sorted_tables(table, len(joint.parts), int(pg.shape[1]), sorted_ids.data_ptr(), perm.data_ptr(),
+                                                pg.data_ptr(), int(pids.numel()), float(g['lr']), float(g['alpha']), float(g['eps']),
+                                                scratch.data_ptr(), _lib.stream_ptr()), "read_rmsprop_sorted_tables")
+        for part in live:
+            part.rows_changed()
 
     def _state(self, tex):
         s = self.state.get(id(tex))
@@ -914,6 +959,9 @@ class SparseDescriptorRMSprop:
         g = self.param_groups[0]
         L = _lib.lib()
         for tex in self.textures:
+            if hasattr(tex, 'parts'):             # a JointTexture: one sorted update over its parts' tables
+                self._step_joint(tex, g)
+                continue
             if tex._touched:                      # someone asked for the dense gradient rows: everything goes through them
                 tex.grad_rows()
             pend = tex.take_pending()
@@ -947,11 +995,11 @@ class SparseDescriptorRMSprop:
     def state_dict(self):
         return {'param_groups': [{k: v for k, v in self.param_groups[0].items() if k != 'params'}],
                 'state': [{k: (v.cpu() if torch.is_tensor(v) else v) for k, v in self._state(t).items() if k != 'scratch'}
-                          for t in self.textures]}
+                          for t in self._tables()]}
 
     def load_state_dict(self, sd):
         self.param_groups[0].update(sd['param_groups'][0])
-        for t, s in zip(self.textures, sd['state']):
+        for t, s in zip(self._tables(), sd['state']):
             cur = self._state(t)
             cur['step'] = s['step']
             cur['sq'].copy_(s['sq'])
