@@ -214,7 +214,7 @@ typedef struct read_splat_instances {
     const float *xyz; const int32_t *ids; int64_t n;   /* device: the point pool (own objects' points, then foreign ones) */
     int count;                                         /* instances */
     const int64_t *first; const int64_t *npts;         /* host, count each: instance i draws pool points [first[i], first[i] + npts[i]) */
-    const float *M;                                    /* host, count x 16: M_i (pinhole) or the panorama layout of read_splat_forward_pano */
+    const float *M;                                    /* host, count x 16: M_i (pinhole), the panorama layout of read_splat_forward_pano, or 12 rows + 4 ignored (read_splat_forward_lens) */
     const unsigned char *visible;                      /* host, count, or NULL */
 } read_splat_instances;
 /* read_splat_forward_objects with an instance list in place of the partition: same routes (cell path for the static part with cells,
@@ -232,6 +232,35 @@ int read_splat_forward_pano_instances(const float *xyz, const int32_t *ids, int6
                                       int W, int H, int levels, const read_splat_instances *inst,
                                       int32_t *const *idx_levels, float *const *depth_levels,
                                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* Lens cameras: a pinhole with Brown-Conrady distortion (model 0) and a Kannala-Brandt fisheye (model 1) (csrc/splat.hip,
+ * splat_lens_kernel; the definition is tests/lens_model.py).  cam_host = 32 floats on the host (camera.lens_camera): [0..11] three
+ * UNSCALED rows applied to (x, y, z, 1) giving c0 = x_c, c1 = y_c and c3 = -z_c (the forward distance); [12] sx = P[0,0],
+ * [13] ox = P[0,2], [14] sy = P[1,1], [15] oy = P[1,2]; [16] za = P[2,2], [17] zb = P[2,3]; [18] the limit; [19] the model, 0.0f or
+ * 1.0f; [20..24] the coefficients (model 0: OpenCV's k1, k2, p1, p2, k3; model 1: OpenCV's fisheye k1..k4); [25..31] zero.  Per
+ * point, in fp32 without fused operations — model 0: a = c0 / c3, b = c1 / c3, r2 = a a + b b, drawn only if c3 > 0 and
+ * r2 <= limit, (a', b') = the distorted (a, b), d = c3; model 1: rho = sqrt(c0 c0 + c1 c1), theta = atan2(rho, c3), drawn only if
+ * theta <= limit, (a', b') = (c0, c1) theta_d(theta) / rho (the axis point rho = 0 lands on the principal point),
+ * d = sqrt(c0 c0 + c1 c1 + c3 c3) — then nx = sx a' - ox, ny = sy b' - oy, nz = (zb - za d) / d and pixel and depth as in every
+ * pass.  Per pixel the minimum (depth, id) wins, empty pixels are (0, 0.0f), levels are formed as in read_splat_forward.
+ *
+ * xyz / ids / n, objs, the warm start, the workspace (left EMPTY; pinhole, panorama and lens frames may alternate on it in any
+ * order), stream ordering: as for read_splat_forward_pano.  objs->M (and inst->M) = count x 16 floats: the 12 rows of object k,
+ * (R4 @ P_k)[:3] with R4 = the camera's rows and (0, 0, 0, 1) beneath, then 4 floats that are ignored; the twenty scalars are the
+ * frame's.  READ_EINVAL before any device work for null pointers, W or H not a multiple of 2^(levels-1), non-finite camera entries
+ * (the limit of model 0 may be +inf), a model other than 0 or 1, a limit that is negative or NaN or above pi for model 1, and a
+ * malformed objs->begin (inst->first, inst->npts). */
+int read_splat_forward_lens(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H, int levels,
+                            const read_splat_objects *objs, int32_t *const *idx_levels, float *const *depth_levels,
+                            void *workspace, size_t workspace_bytes, void *stream);
+/* read_splat_forward_lens with an instance list (inst must not be NULL; no warm start). */
+int read_splat_forward_lens_instances(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host,
+                                      int W, int H, int levels, const read_splat_instances *inst,
+                                      int32_t *const *idx_levels, float *const *depth_levels,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+/* read_splat_project_points under a lens camera: the same device function as read_splat_forward_lens's pass. */
+int read_splat_lens_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel, float *depth,
+                                   void *stream);
 
 /* Measurement aid for bench.py (roofline.mfma_sustained): one workgroup of four waves per CU, every wave `iters` rounds of 16 independent
  * v_mfma_f32_16x16x4_f32 and nothing else.  scratch: >= 256 floats per CU on the device (never written); *flops receives the number of

@@ -148,6 +148,9 @@ SIGNATURES = {
     "read_splat_forward_instances": (_i, [_vp, _vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_forward_pano_instances": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_pano_project_points": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp]),
+    "read_splat_forward_lens": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
+    "read_splat_forward_lens_instances": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
+    "read_splat_lens_project_points": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp]),
     "read_splat_forward_cells": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _i, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_hint_next_camera": (_i, [_vp, C.POINTER(_f)]),
     "read_splat_profile_last": (_i, [C.POINTER(_f)]),

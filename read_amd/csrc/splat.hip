@@ -1286,6 +1286,106 @@ __global__ __launch_bounds__(256) void splat_pano_seed_kernel(const float *__res
     if (pix >= 0) fold_key_agent(keys + pix, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id);
 }
 
+// ---- lens cameras: distorted pinhole and fisheye (read_splat_forward_lens) ---------------------------------------------------
+// Again only the per-point projection differs.  The camera is 32 floats formed on the host (camera.lens_camera): c[0..11] three
+// UNSCALED rows applied to (x, y, z, 1) — c0 = x_c, c1 = y_c, c3 = -z_c — and twenty scalars, the same for every range of a frame,
+// which travel once per launch as LensScalars: sx, ox, sy, oy = P[0,0], P[0,2], P[1,1], P[1,2]; za, zb = P[2,2], P[2,3]; the
+// limit; the model (0 = Brown-Conrady pinhole, 1 = Kannala-Brandt fisheye); k[5] in OpenCV's order; seven zeros.
+// tests/lens_model.py is the definition; this restates it: fp32, no contraction, sums left to right, IEEE division, correctly
+// rounded square root, Horner with separate multiply and add.  The model is uniform over a launch, so the branch is scalar.
+struct LensScalars {
+    float s[20];
+};
+
+// One point under one lens camera (rows r[12], scalars ls); returns the pixel or -1.  A point past the limit, NaN and Inf fall out
+// through `keep` and `inside`; the fisheye's axis point (rho = 0) is kept and lands on the principal point.
+__device__ __forceinline__ int project_lens_one(float x, float y, float z, const float *r, const LensScalars &ls, int W, int H,
+                                                float &depth, int &xx_out, int &yy_out)
+{
+    const float c0 = r[0] * x + r[1] * y + r[2] * z + r[3] * 1.0f;
+    const float c1 = r[4] * x + r[5] * y + r[6] * z + r[7] * 1.0f;
+    const float c3 = r[8] * x + r[9] * y + r[10] * z + r[11] * 1.0f;
+    const float sx = ls.s[0], ox = ls.s[1], sy = ls.s[2], oy = ls.s[3], za = ls.s[4], zb = ls.s[5], limit = ls.s[6];
+    float a2, b2, d;
+    bool keep;
+    if (ls.s[7] == 0.0f) {
+        const float k1 = ls.s[8], k2 = ls.s[9], p1 = ls.s[10], p2 = ls.s[11], k3 = ls.s[12];
+        const float a = c0 / c3, b = c1 / c3;
+        const float r2 = a * a + b * b;
+        keep = (c3 > 0.0f) & (r2 <= limit);
+        const float rad = ((k3 * r2 + k2) * r2 + k1) * r2 + 1.0f;
+        const float xo = a, yo = -b;                             // OpenCV's axes: its y points down
+        const float xy2 = 2.0f * (xo * yo);
+        const float tx = p1 * xy2 + p2 * (r2 + 2.0f * (xo * xo));
+        const float ty = p1 * (r2 + 2.0f * (yo * yo)) + p2 * xy2;
+        a2 = xo * rad + tx;
+        b2 = -(yo * rad + ty);
+        d = c3;
+    } else {
+        const float k1 = ls.s[8], k2 = ls.s[9], k3 = ls.s[10], k4 = ls.s[11];
+        const float rho = __builtin_sqrtf(c0 * c0 + c1 * c1);
+        const float theta = pano_atan2(rho, c3);
+        keep = theta <= limit;
+        const float t2 = theta * theta;
+        const float theta_d = theta * ((((k4 * t2 + k3) * t2 + k2) * t2 + k1) * t2 + 1.0f);
+        const float q = rho == 0.0f ? 0.0f : theta_d / rho;
+        a2 = q * c0;
+        b2 = q * c1;
+        d = __builtin_sqrtf(c0 * c0 + c1 * c1 + c3 * c3);
+    }
+    const float nx = sx * a2 - ox;
+    const float ny = sy * b2 - oy;
+    const float nz = (zb - za * d) / d;
+    // from here on: the tail of project_one
+    const bool inside = (nx >= -1.0f) & (nx <= 1.0f) & (ny >= -1.0f) & (ny <= 1.0f) &
+                        (nz >= -1.0f) & (nz <= 1.0f);
+    const float u = ((float)W * (nx + 1.0f)) * 0.5f;
+    const float v = ((float)H * (1.0f - ny)) * 0.5f;
+    depth = (nz + 1.0f) * 0.5f;
+    const int xx = (int)u, yy = (int)v;
+    const bool ok = keep & inside & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H);
+    xx_out = xx;
+    yy_out = yy;
+    return ok ? yy * W + xx : -1;
+}
+
+// splat_pano_kernel under lens cameras: ob.m[k] holds range k's 12 rows (its other 4 floats are ignored), ls the frame's scalars.
+__global__ __launch_bounds__(256) void splat_lens_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
+                                                         ObjBatch ob, LensScalars ls, int W, int H,
+                                                         unsigned long long *__restrict__ keys)
+{
+    const int b = (int)blockIdx.x;
+    int j = 0;
+    for (int k = 1; k < ob.count; ++k)
+        if (b >= ob.block0[k]) j = k;
+    const long long i = ob.first[j] + (long long)(b - ob.block0[j]) * 256 + threadIdx.x;
+    if (i >= ob.last[j]) return;
+    float d;
+    int xx, yy;
+    const int pix = project_lens_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], ls, W, H, d, xx, yy);
+    if (pix < 0) return;
+    const unsigned id = ids ? (unsigned)ids[i] : (unsigned)i;
+    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | id;
+    unsigned long long *k = keys + pix;
+    if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
+}
+
+// Warm start of an unlabelled lens frame: splat_pano_seed_kernel under the lens camera (cam.m[0..11] = the rows).
+__global__ __launch_bounds__(256) void splat_lens_seed_kernel(const float *__restrict__ xyz, long long n, Cam1 cam, LensScalars ls,
+                                                              int W, int H, unsigned long long *__restrict__ keys,
+                                                              const SplatHeader *hdr, const int *__restrict__ prev_idx)
+{
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= W * H || !prev_idx) return;
+    if (!(hdr->valid == 1 && hdr->W == W && hdr->H == H)) return;
+    const int id = prev_idx[p];
+    if (id < 0 || id >= n) return;
+    float d;
+    int xx, yy;
+    const int pix = project_lens_one(xyz[3ll * id], xyz[3ll * id + 1], xyz[3ll * id + 2], cam.m, ls, W, H, d, xx, yy);
+    if (pix >= 0) fold_key_agent(keys + pix, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id);
+}
+
 struct ResolveOut {
     int32_t *idx[READ_MAX_LEVELS];
     float *depth[READ_MAX_LEVELS];
@@ -1706,11 +1806,13 @@ struct ObjectsDraw {
 };
 
 int objects_flush(ObjBatch &ob, int &blocks, const float *xyz, const int32_t *ids, int W, int H, unsigned long long *keys,
-                  hipStream_t stream, bool pano = false)
+                  hipStream_t stream, bool pano = false, const LensScalars *lens = nullptr)
 {
     if (ob.count == 0) return READ_OK;
     ob.block0[ob.count] = blocks;
-    if (pano)
+    if (lens)
+        hipLaunchKernelGGL(splat_lens_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, *lens, W, H, keys);
+    else if (pano)
         hipLaunchKernelGGL(splat_pano_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys);
     else
         hipLaunchKernelGGL(splat_objects_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys);
@@ -1732,22 +1834,24 @@ void objects_add(ObjBatch &ob, int &blocks, int64_t first, int64_t last, const f
 
 // Every visible, non-empty range of `od` into the key image: stream-ordered, OBJ_MAX ranges per launch, no synchronisation.
 // pano: the matrices are panorama cameras (splat_pano_kernel), and ids0 may be NULL (the static range's ids are its indices).
-int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, hipStream_t stream, bool pano = false)
+// lens: the matrices are the rows of lens cameras with the frame's scalars *lens (splat_lens_kernel); ids0 as for pano.
+int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, hipStream_t stream, bool pano = false,
+                   const LensScalars *lens = nullptr)
 {
     ObjBatch ob;
     memset(&ob, 0, sizeof(ob));
     int blocks = 0, rc;
     if (od.n0 > 0) {
         objects_add(ob, blocks, 0, od.n0, od.M0);
-        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, stream, pano)) != READ_OK) return rc;
+        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, stream, pano, lens)) != READ_OK) return rc;
     }
     for (int k = 0; k < od.count; ++k) {
         const int64_t first = od.first[k], last = first + od.npts[k];
         if ((od.visible && !od.visible[k]) || last == first) continue;                      // hidden or empty: not launched
         objects_add(ob, blocks, first, last, od.M + 16 * (size_t)k);
-        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano)) != READ_OK) return rc;
+        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano, lens)) != READ_OK) return rc;
     }
-    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano);
+    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano, lens);
 }
 
 // ---- per-kernel durations of the LAST cell-path frame (read_tuning_set("splat_prof", 1) + read_splat_profile_last): HIP events
@@ -2802,12 +2906,41 @@ int check_pano_cameras(const char *who, const float *cam_host, const read_splat_
     return READ_OK;
 }
 
-// What the four entry points ask of their arguments, in one order: outputs, the static part, the ranges (objs or inst, whichever
-// the symbol takes; both NULL: none), the pyramid, the cameras of a panorama, alignment, workspace size.  cam_host != NULL: a
-// panorama frame, whose static part may come without ids (its indices are its ids) and has no cell blob.
+// the host-side conditions on a lens camera (camera.lens_camera, 32 floats): every entry but the limit finite, the model 0 or 1,
+// the limit not NaN, not negative and, for the fisheye, not above the fp32 pi its arctangent ends at (model 0 may carry +inf)
+const char *lens_cam_fault(const float *c)
+{
+    for (int i = 0; i < 32; ++i)
+        if (i != 18 && !std::isfinite(c[i])) return "a camera entry is not finite";
+    if (c[19] != 0.0f && c[19] != 1.0f) return "the model must be 0 (distorted pinhole) or 1 (fisheye)";
+    if (!(c[18] >= 0.0f)) return "the limit is negative or NaN";
+    if (c[19] == 1.0f && c[18] > 3.14159265358979323846f) return "the limit of a fisheye must not exceed pi";
+    return nullptr;
+}
+
+// the frame's lens camera and the 12 rows of every range that will be launched (the 4 floats after them are ignored)
+int check_lens_cameras(const char *who, const float *cam_host, const read_splat_objects *objs, const read_splat_instances *inst)
+{
+    const char *fault = lens_cam_fault(cam_host);
+    READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
+    const int count = objs ? objs->count : inst ? inst->count : 0;
+    const float *M = objs ? objs->M : inst ? inst->M : nullptr;
+    const unsigned char *visible = objs ? objs->visible : inst ? inst->visible : nullptr;
+    for (int k = 0; k < count; ++k) {
+        if ((visible && !visible[k]) || (objs ? objs->begin[k + 1] == objs->begin[k] : inst->npts[k] == 0)) continue;
+        for (int i = 0; i < 12; ++i)
+            READ_CHECK_ARG(std::isfinite(M[16 * (size_t)k + i]), "%s: %s %d: a camera row entry is not finite", who,
+                           objs ? "objs->M of object" : "inst->M of instance", k);
+    }
+    return READ_OK;
+}
+
+// What the six entry points ask of their arguments, in one order: outputs, the static part, the ranges (objs or inst, whichever
+// the symbol takes; both NULL: none), the pyramid, the cameras of a panorama or a lens, alignment, workspace size.  cam_host !=
+// NULL: a panorama frame (lens: a lens frame), whose static part may come without ids (its indices are its ids) and has no cell blob.
 int check_frame_args(const char *who, const float *cam_host, const float *xyz, const int32_t *ids, const void *cells, int64_t n,
                      const read_splat_objects *objs, const read_splat_instances *inst, int W, int H, int levels,
-                     int32_t *const *idx_levels, float *const *depth_levels, const void *ws, size_t ws_bytes)
+                     int32_t *const *idx_levels, float *const *depth_levels, const void *ws, size_t ws_bytes, bool lens = false)
 {
     const bool pano = cam_host != nullptr;
     int rc = READ_OK;
@@ -2820,7 +2953,8 @@ int check_frame_args(const char *who, const float *cam_host, const float *xyz, c
     READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad size (%d,%d)", who, W, H);
     const int mask = (1 << (levels - 1)) - 1;
     READ_CHECK_ARG(((W | H) & mask) == 0, "%s: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", who, W, H, mask + 1);
-    if (pano && (rc = check_pano_cameras(who, cam_host, objs, inst)) != READ_OK) return rc;
+    if (pano && (rc = lens ? check_lens_cameras(who, cam_host, objs, inst) : check_pano_cameras(who, cam_host, objs, inst)) != READ_OK)
+        return rc;
     READ_CHECK_ARG((uintptr_t)ws % 256 == 0 && (uintptr_t)cells % 256 == 0, "%s: workspace %smust be 256-byte aligned", who,
                    pano ? "" : "and cells ");
     if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
@@ -2853,8 +2987,10 @@ int objects_frame(ObjectsDraw od, const float *xyz_static, const int32_t *ids_st
 
 // The panorama frame once the arguments are checked: one range launch for the static part, the ranges of od, the resolve.
 // Seeds carry implicit ids: only a cloud drawn whole, with its indices as ids, keeps and uses them.
+// lens: cam_host is a lens camera of 32 floats — its first 16 are the static range's ObjBatch entry (12 rows, 4 ignored), its
+// last 20 the frame's LensScalars; the frame is otherwise the panorama's, launch for launch.
 int pano_frame(ObjectsDraw od, const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, bool whole, int W, int H,
-               int levels, int32_t *const *idx_levels, float *const *depth_levels, void *ws, hipStream_t s)
+               int levels, int32_t *const *idx_levels, float *const *depth_levels, void *ws, hipStream_t s, bool lens = false)
 {
     const WsLayout L = ws_layout(ws, 1, W, H);
     const bool seeds = whole && !ids && n > 0 && g_splat_mode == MODE_HIZ;
@@ -2862,15 +2998,21 @@ int pano_frame(ObjectsDraw od, const float *xyz, const int32_t *ids, int64_t n, 
     od.ids0 = ids;
     od.n0 = n;
     od.M0 = cam_host;
+    LensScalars ls;
+    if (lens) memcpy(ls.s, cam_host + 12, sizeof(ls.s));
     if (const int rc = ws_forget_prediction(ws, s); rc != READ_OK) return rc;
     if (seeds && g_splat_seeds) {
         Cam1 cam;
         memcpy(cam.m, od.M0, sizeof(cam.m));
-        hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, W, H, L.keys,
-                           (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
+        if (lens)
+            hipLaunchKernelGGL(splat_lens_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, ls, W, H,
+                               L.keys, (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
+        else
+            hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, W, H, L.keys,
+                               (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
         READ_CHECK_LAUNCH();
     }
-    const int rc = objects_launch(od, W, H, L.keys, s, true);
+    const int rc = objects_launch(od, W, H, L.keys, s, !lens, lens ? &ls : nullptr);
     if (rc != READ_OK) return rc;
     return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
 }
@@ -2934,6 +3076,36 @@ extern "C" int read_splat_forward_pano_instances(const float *xyz, const int32_t
                                     ws_bytes);
     if (rc != READ_OK) return rc;
     return pano_frame(instances_draw(inst), xyz, ids, n, cam_host, false, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+}
+
+// Lens camera: the whole cloud (objs NULL; the previous frame's winners warm-start it) or a labelled cloud's static part plus its
+// objects as a partition (no seeds).  objs->M = count x 16: the rows of object k, then 4 ignored floats.
+extern "C" int read_splat_forward_lens(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H, int levels,
+                                       const read_splat_objects *objs, int32_t *const *idx_levels, float *const *depth_levels,
+                                       void *ws, size_t ws_bytes, void *stream)
+{
+    const char *who = "read_splat_forward_lens";
+    READ_CHECK_ARG(cam_host && ws, "%s: null pointer (cam_host or workspace)", who);
+    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, objs, nullptr, W, H, levels, idx_levels, depth_levels, ws,
+                                    ws_bytes, true);
+    if (rc != READ_OK) return rc;
+    std::vector<int64_t> ranges;
+    return pano_frame(partition_draw(objs, ranges), xyz, ids, n, cam_host, !objs, W, H, levels, idx_levels, depth_levels, ws,
+                      as_stream(stream), true);
+}
+
+// Lens camera, the list itself (no warm start: the ids are explicit).
+extern "C" int read_splat_forward_lens_instances(const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, int W, int H,
+                                                 int levels, const read_splat_instances *inst, int32_t *const *idx_levels,
+                                                 float *const *depth_levels, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *who = "read_splat_forward_lens_instances";
+    READ_CHECK_ARG(cam_host && inst && ws, "%s: null pointer (cam_host, inst or workspace)", who);
+    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, nullptr, inst, W, H, levels, idx_levels, depth_levels, ws,
+                                    ws_bytes, true);
+    if (rc != READ_OK) return rc;
+    return pano_frame(instances_draw(inst), xyz, ids, n, cam_host, false, W, H, levels, idx_levels, depth_levels, ws,
+                      as_stream(stream), true);
 }
 
 extern "C" int read_splat_forward_gl(const float *xyz, int64_t n, const float *M_host, int W, int H,
@@ -3041,6 +3213,42 @@ extern "C" int read_splat_pano_project_points(const float *xyz, int64_t n, const
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(pano_project_points_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), xyz, (long long)n, cam,
                        W, H, pixel, depth);
+    READ_CHECK_LAUNCH();
+    return READ_OK;
+}
+
+namespace {
+// project_points_kernel under a lens camera: project_lens_one as the frame's passes use it, without the z-test.
+__global__ __launch_bounds__(256) void lens_project_points_kernel(const float *__restrict__ xyz, long long n, Cam1 cam, LensScalars ls,
+                                                                  int W, int H, int32_t *__restrict__ pixel, float *__restrict__ depth)
+{
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float d;
+        int xx, yy;
+        const int pix = project_lens_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cam.m, ls, W, H, d, xx, yy);
+        pixel[i] = pix;
+        if (depth) depth[i] = d;
+    }
+}
+}  // namespace
+
+extern "C" int read_splat_lens_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel,
+                                              float *depth, void *stream)
+{
+    READ_CHECK_ARG(n >= 0 && (n == 0 || (xyz && pixel)), "read_splat_lens_project_points: null pointer");
+    READ_CHECK_ARG(cam_host, "read_splat_lens_project_points: cam_host is null");
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_lens_project_points: bad W/H (%d,%d)", W, H);
+    const char *fault = lens_cam_fault(cam_host);
+    READ_CHECK_ARG(!fault, "read_splat_lens_project_points: cam_host: %s", fault);
+    if (n == 0) return READ_OK;
+    Cam1 cam;
+    LensScalars ls;
+    for (int i = 0; i < 16; ++i) cam.m[i] = cam_host[i];
+    for (int i = 0; i < 20; ++i) ls.s[i] = cam_host[12 + i];
+    long long blocks = ceil_div64(n, 256);
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(lens_project_points_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), xyz, (long long)n, cam,
+                       ls, W, H, pixel, depth);
     READ_CHECK_LAUNCH();
     return READ_OK;
 }

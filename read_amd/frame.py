@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .camera import level_sizes, pano_camera, total_matrix
+from .camera import lens_camera, level_sizes, pano_camera, total_matrix
 from .raster import PointCloudRasterizer
 from .texture import gather_pyramid, gather_tables_pyramid, texture_to_rows
 from .unet import LAYOUT_FULL, UNetEngine, default_layout, layout_of, pack_state
@@ -128,6 +128,9 @@ class FrameRenderer:
     def rasterize_pano(self, cam):
         return self.raster.render_pano(cam, self.W, self.H, self.levels, out=(self.idx, self.depth))
 
+    def rasterize_lens(self, cam):
+        return self.raster.render_lens(cam, self.W, self.H, self.levels, out=(self.idx, self.depth))
+
     def gather(self, out=None):
         out = self.feat if out is None else out
         if self.foreign_rows:
@@ -149,6 +152,10 @@ class FrameRenderer:
     def render_pano_total(self, cam, out=None, channels=4):
         """render_total's twin for a panorama camera (the 16 floats of camera.pano_camera): only the raster step differs."""
         return self._frame(lambda: self.rasterize_pano(cam), out, channels)
+
+    def render_lens_total(self, cam, out=None, channels=4):
+        """render_total's twin for a lens camera (the 32 floats of camera.lens_camera): only the raster step differs."""
+        return self._frame(lambda: self.rasterize_lens(cam), out, channels)
 
     def _frame(self, rasterize, out, channels):
         if not self._slots:
@@ -201,3 +208,12 @@ class FrameRenderer:
         if proj is None:
             raise ValueError("no projection matrix set")
         return self.render_pano_total(pano_camera(proj, view_matrix, hfov_deg), out, channels)
+
+    def render_lens(self, view_matrix, model, coeffs, limit=None, proj_matrix=None, out=None, channels=4):
+        """A frame through a lens: model 0 = a pinhole with Brown-Conrady distortion (coeffs k1, k2, p1, p2, k3), model 1 = a
+        Kannala-Brandt fisheye (coeffs k1..k4); limit as in camera.lens_camera (None: just inside where the distortion folds
+        back).  view_matrix camera->world.  Object edits apply; frames_in_flight as for ``render_total``."""
+        proj = self.proj if proj_matrix is None else np.asarray(proj_matrix, np.float32)
+        if proj is None:
+            raise ValueError("no projection matrix set")
+        return self.render_lens_total(lens_camera(proj, view_matrix, model, coeffs, limit), out, channels)

@@ -84,6 +84,9 @@ class OGL:
         pano = getattr(self.renderer.scene, 'panorama', None) is not None
         if pano:
             self._require_fast("a panorama camera (set_panorama)", input_dict)
+        lens = getattr(self.renderer.scene, 'lens', None) is not None
+        if lens:
+            self._require_fast("a lens camera (set_lens)", input_dict)
         foreign = bool(getattr(self.renderer.scene, 'foreign_objects', None))
         if foreign:
             self._require_fast("foreign objects (add_foreign_object)", input_dict, ": the table gather has no supersampled form")
@@ -100,6 +103,9 @@ class OGL:
                 if pano:                                         # Scene.set_panorama: only the raster step differs
                     scene.take_next_total_matrix()               # an announced next camera is ignored (and consumed)
                     idx, _ = raster.render_pano(scene.pano_camera(), W, H, len(fmts), want_depth=False)
+                elif lens:                                       # Scene.set_lens: likewise
+                    scene.take_next_total_matrix()
+                    idx, _ = raster.render_lens(scene.lens_camera(), W, H, len(fmts), want_depth=False)
                 else:
                     idx, _ = raster.render(scene.total_matrix(), ss * W, ss * H, len(fmts), want_depth=False,
                                            next_total=scene.take_next_total_matrix())      # Scene.announce_next_camera_view
@@ -138,6 +144,9 @@ class OGL:
         if getattr(scene, 'panorama', None) is not None:
             raise NotImplementedError(f"a panorama camera (set_panorama) with {what}: the instance match re-projects with the "
                                       "pinhole projection")
+        if getattr(scene, 'lens', None) is not None:
+            raise NotImplementedError(f"a lens camera (set_lens) with {what}: the instance match re-projects with the pinhole "
+                                      "projection")
         self._require_fast(what, None, ": annotations describe the level-0 frame at the output size")
         texture = model._modules[str(model._loaded_textures[0])] if model._loaded_textures else model._modules['0']
         W, H = self.viewport_size
@@ -160,7 +169,7 @@ class OGL:
         return {'output': out, 'net_input': [f.permute(0, 3, 1, 2) for f in feats], 'annotation': annotation}
 
     def _require_fast(self, what, input_dict, ss_note=''):
-        """``what`` — foreign objects, a panorama camera, scene stitching — is drawn on the fast path only (for foreign objects:
+        """``what`` — foreign objects, a panorama or lens camera, scene stitching — is drawn on the fast path only (for foreign objects:
         the dict path's single-table lookup would see ids >= N).  What would leave the fast path is refused by name."""
         model, scene = self.model, self.renderer.scene
         if input_dict is not None:
@@ -181,6 +190,8 @@ class OGL:
         model, scene = self.model, self.renderer.scene
         if scene.panorama is not None:
             raise NotImplementedError("a panorama camera (set_panorama) on a StitchedScene: stitched frames are pinhole frames")
+        if scene.lens is not None:
+            raise NotImplementedError("a lens camera (set_lens) on a StitchedScene: stitched frames are pinhole frames")
         self._require_fast("scene stitching (StitchedScene)", input_dict)
         textures = [model._modules[str(t)] for t in self.texture_ids]
         raster = scene.rasterizer()

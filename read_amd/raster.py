@@ -198,6 +198,17 @@ class PointCloudRasterizer:
         out[:, 12:] = cam[12:]
         return out
 
+    def lens_instance_cameras(self, cam):
+        """The (I,16) float32 rows of the instances, in handle order, for the lens camera ``cam`` (camera.lens_camera): floats
+        0..11 are ``object_matrix(R4, P_i)[:3]``, R4 = cam's three rows with (0, 0, 0, 1) beneath; the other 4 are ignored (0
+        here) — the twenty scalars belong to the frame and travel once."""
+        cam = np.asarray(cam, np.float32).reshape(32)
+        R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
+        lst = self._instance_list()
+        out = np.zeros((len(lst), 16), np.float32)
+        out[:, :12] = object_matrices(R4, [P for _, P, _ in lst])[:, :3].reshape(-1, 12)
+        return out
+
     def _instances_struct(self, matrices):
         """The read_splat_instances of this frame: its host arrays (first, npts, visible, M) are built here and kept on self
         until the next frame."""
@@ -313,6 +324,30 @@ class PointCloudRasterizer:
                                                  dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano")
         return idx, dep
 
+    def render_lens(self, cam, W, H, levels=5, want_depth=True, out=None):
+        """One frame under a lens camera — a distorted pinhole or a fisheye: ``cam`` = the 32 floats of ``camera.lens_camera``
+        -> (idx_levels, depth_levels) as ``render`` gives them.  One camera per call; object labels, instances, poses and
+        visibility are honoured.  The whole cloud is read every frame (no chunk culling under a lens); without labels the
+        previous frame's winners warm-start the pass.  Pinhole, panorama and lens frames may alternate on one rasteriser."""
+        cam = _host_f32(cam).reshape(-1, 32)
+        if cam.shape[0] != 1:
+            raise ValueError("render_lens renders one camera per call")
+        idx, dep, idx_p, dep_p = self._outputs(1, W, H, levels, want_depth, out)
+        ws = self._workspace(1, W, H)
+        cam_p = cam.ctypes.data_as(C.POINTER(C.c_float))
+        L = _lib.lib()
+        if self._inst is not None:
+            inst = self._instances_struct(self.lens_instance_cameras(cam[0]))
+            # a cloud without labels is static as a whole: its points' indices are their ids, and none are passed
+            ids = (self._static_ids.data_ptr() or None) if self.labels is not None else None
+            _lib.check(L.read_splat_forward_lens_instances(
+                self._static_xyz.data_ptr() or None, ids, self.n_static, cam_p, W, H, levels, C.byref(inst), idx_p, dep_p,
+                ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_lens_instances")
+        else:
+            _lib.check(L.read_splat_forward_lens(self.xyz.data_ptr() or None, None, self.n, cam_p, W, H, levels, None, idx_p,
+                                                 dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_lens")
+        return idx, dep
+
     def bind(self, W, H, levels, out, totals):
         """A pre-bound frame call for loops that must not be host-bound (benchmark stages): every ctypes argument is built ONCE —
         the outputs ``out`` = (idx levels, depth levels or None) and the list of camera matrices ``totals`` — and
@@ -340,19 +375,22 @@ class PointCloudRasterizer:
         return call
 
     def render_gl(self, total_m, W, H, point_size=1.0, relative=False, min_point_size=1.0, discard=None, drop=None,
-                  perturb=None, perturb_hash=None, want_depth=True, point_sizes=None, pano=None):
+                  perturb=None, perturb_hash=None, want_depth=True, point_sizes=None, pano=None, lens=None):
         """ONE level of ONE camera at its own size with the GL twin's point options (read_splat_forward_gl):
         point_size / relative ("pN" / "psN" tokens, READ/gl/programs.py:183-192), discard = bool/uint8 (N,) array or
         tensor (set_point_discard), drop = (p, seed) seeded drop, perturb = (N,2) clip-space offsets
         (set_point_perturb), perturb_hash = (amp, seed), point_sizes = (N,) per-point sizes (set_point_sizes; they replace
         point_size as in the shader, programs.py:183-187).  -> (idx (1,H,W) int32, depth (1,H,W) fp32 | None).
-        pano = a panorama camera (camera.pano_camera) is refused: the GL twin is a pinhole."""
+        pano = a panorama camera (camera.pano_camera) is refused: the GL twin is a pinhole; so is lens = a lens camera
+        (camera.lens_camera)."""
         if self.labels is not None:
             raise NotImplementedError("render_gl (GL-twin point options) with object labels")
         if getattr(self, '_inst', None) is not None:
             raise NotImplementedError("render_gl (GL-twin point options) with added objects or instances (add_object / add_instance)")
         if pano is not None:
             raise NotImplementedError("render_gl (GL-twin point options) with a panorama camera: render_pano draws 1-px point ids")
+        if lens is not None:
+            raise NotImplementedError("render_gl (GL-twin point options) with a lens camera: render_lens draws 1-px point ids")
         M = _host_f32(total_m).reshape(-1, 16)
         if M.shape[0] != 1:
             raise ValueError("render_gl renders one camera per call")

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .camera import level_sizes, pano_camera, total_matrix
+from .camera import lens_camera, level_sizes, pano_camera, total_matrix
 from .raster import PointCloudRasterizer, index_to_float
 
 
@@ -187,6 +187,7 @@ class Scene:
         self.object_poses = {}            # label -> 4x4
         self.object_hidden = set()        # labels not drawn
         self.panorama = None              # set_panorama: horizontal field in degrees of the cylindrical camera, None = pinhole
+        self.lens = None                  # set_lens: (model, coeffs, limit) of the lens camera, None = the ideal pinhole
         self.foreign_objects = []         # scene editing, add: [(xyz (m,3), PointTexture)] of add_foreign_object, in order
         self.instances = {}               # handle -> {'k', 'P', 'visible'} of add_object_instance, replayed into a rebuilt rasteriser
         self._next_instance = 0
@@ -404,6 +405,8 @@ class Scene:
         point-id pyramid on the fast path raises NotImplementedError while a panorama is set."""
         if hfov_deg is not None and not 0.0 < float(hfov_deg) <= 360.0:
             raise ValueError(f"hfov_deg must lie in (0, 360], got {hfov_deg!r}")
+        if hfov_deg is not None and self.lens is not None:
+            raise ValueError("set_panorama with a lens camera set (set_lens): a scene has one camera; set_lens(None) first")
         self.panorama = None if hfov_deg is None else float(hfov_deg)
 
     def pano_camera(self):
@@ -413,6 +416,31 @@ class Scene:
             raise ValueError("no panorama set (set_panorama)")
         view = np.linalg.inv(self.model_matrix.astype(np.float64)) @ self.view_matrix.astype(np.float64)
         return pano_camera(self.proj_matrix, view, self.panorama)
+
+    def set_lens(self, model, coeffs=None, limit=None):
+        """Extension (not in NNScene): the scene's camera gets a lens at the current view — model 0 a pinhole with Brown-Conrady
+        distortion (coeffs = OpenCV's k1, k2, p1, p2, k3), model 1 a Kannala-Brandt fisheye (coeffs = OpenCV's fisheye k1..k4);
+        ``set_lens(None)`` returns to the ideal pinhole.  limit as in camera.lens_camera (None: just inside where the distortion
+        folds back; smaller: a field mask).  ``OGL.infer`` stays on its fast path and rasterises with
+        ``PointCloudRasterizer.render_lens``, and ``MultiscaleRender.render`` serves the point-id pyramid under the lens, so a
+        scene is fitted through it as through the pinhole.  Object edits apply; an announced next camera is ignored; everything
+        that is not the point-id pyramid raises NotImplementedError while a lens is set."""
+        if model is None:
+            self.lens = None
+            return
+        if self.panorama is not None:
+            raise ValueError("set_lens with a panorama camera set (set_panorama): a scene has one camera; set_panorama(None) first")
+        coeffs = () if coeffs is None else tuple(float(c) for c in np.asarray(coeffs, np.float64).reshape(-1))
+        lens_camera(np.eye(4), np.eye(4), model, coeffs, limit)                  # the checks of camera.lens_camera, now
+        self.lens = (int(model), coeffs, None if limit is None else float(limit))
+
+    def lens_camera(self):
+        """The 32 floats of camera.lens_camera for the current view, model and projection matrices (points are taken to the
+        camera by inv(view) @ model, as in ``total_matrix``)."""
+        if self.lens is None:
+            raise ValueError("no lens set (set_lens)")
+        view = np.linalg.inv(self.model_matrix.astype(np.float64)) @ self.view_matrix.astype(np.float64)
+        return lens_camera(self.proj_matrix, view, *self.lens)
 
     def set_use_light(self, use_light):
         if use_light:
@@ -495,6 +523,9 @@ class Scene:
         if self.panorama is not None:
             raise NotImplementedError("a panorama camera (set_panorama) with select_masks: the occlusion window compares clip w, "
                                       "which is no depth under the cylindrical camera; select from pinhole views")
+        if self.lens is not None:
+            raise NotImplementedError("a lens camera (set_lens) with select_masks: the views are projected with the ideal pinhole; "
+                                      "select from undistorted views")
         if self.augmented():
             raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with select_masks: the views are "
                                       "level-0 frames of the plain cloud")
@@ -529,6 +560,9 @@ class Scene:
             raise ValueError("scene has no point cloud (set_vertices)")
         if self.panorama is not None:
             raise NotImplementedError("a panorama camera (set_panorama) with annotate_frame: the instance match re-projects with the "
+                                      "pinhole projection")
+        if self.lens is not None:
+            raise NotImplementedError("a lens camera (set_lens) with annotate_frame: the instance match re-projects with the "
                                       "pinhole projection")
         if self.augmented():
             raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with annotate_frame: annotations "
@@ -627,6 +661,16 @@ class StitchedScene:
     def panorama(self):
         return next((sc.panorama for sc in self.scenes if sc.panorama is not None), None)
 
+    def set_lens(self, model, coeffs=None, limit=None):
+        if model is not None:
+            raise NotImplementedError("a lens camera on a StitchedScene: stitched frames are pinhole frames")
+        for sc in self.scenes:
+            sc.set_lens(None)
+
+    @property
+    def lens(self):
+        return next((sc.lens for sc in self.scenes if sc.lens is not None), None)
+
     def set_model_view(self, m):
         for sc in self.scenes:
             sc.set_model_view(m)
@@ -719,6 +763,8 @@ class MultiscaleRender:
             what = "a StitchedScene" if getattr(scene, 'stitched', False) else "MultiscaleRender (the dict path)"
             raise NotImplementedError(f"a panorama camera (set_panorama) on {what}: only OGL.infer's fast path and "
                                       "FrameRenderer.render_pano draw it")
+        if getattr(scene, 'lens', None) is not None:
+            return self._render_lens(scene, input_format, fmts, W, H)
         if getattr(scene, 'stitched', False):
             return self._render_stitched(scene, input_format, fmts, W, H)
         if getattr(scene, 'foreign_objects', None):
@@ -752,6 +798,30 @@ class MultiscaleRender:
             x = self._render_token(cfg, w, h)
             out[fmt] = self._package(x, fmt)
         return out
+
+    def _render_lens(self, scene, input_format, fmts, W, H):
+        """A lens camera (Scene.set_lens): the plain point-id pyramid through ``render_lens`` — what TexturePipeline trains
+        with; everything else is refused by name."""
+        what = "a lens camera (set_lens)"
+        if getattr(scene, 'stitched', False):
+            raise NotImplementedError(f"{what} on a StitchedScene: stitched frames are pinhole frames")
+        if getattr(scene, 'foreign_objects', None):
+            raise NotImplementedError("foreign objects (add_foreign_object) on MultiscaleRender (the dict path): its id tokens would "
+                                      "carry ids past the scene's descriptor table; only OGL.infer's fast path and FrameRenderer "
+                                      "draw them")
+        if self.ss > 1:
+            raise NotImplementedError(f"supersampling {self.ss} with {what}")
+        if scene.augmented():
+            raise NotImplementedError(f"GL-twin augmentation (point sizes, discard, drop, perturb) with {what}")
+        if not is_point_id_pyramid(input_format):
+            bad = next(f for i, f in enumerate(fmts) if not is_point_id_pyramid(','.join(fmts[:i + 1])))
+            raise NotImplementedError(f"token {bad!r} with {what}: only the point-id pyramid is drawn through a lens")
+        if W % (1 << (len(fmts) - 1)) or H % (1 << (len(fmts) - 1)):
+            raise NotImplementedError(f"{what} at {W}x{H}: the point-id pyramid needs sizes that are multiples of "
+                                      f"{1 << (len(fmts) - 1)}")
+        idx, _ = scene.rasterizer().render_lens(scene.lens_camera(), W, H, len(fmts), want_depth=False)
+        self.last_index = idx
+        return {fmt: self._package(self._id_image(ids_l[0]), fmt) for fmt, ids_l in zip(fmts, idx)}
 
     def _render_stitched(self, scene, input_format, fmts, W, H):
         """A StitchedScene: the point-id pyramid of merged global ids; everything else is refused by name."""
