@@ -406,8 +406,10 @@ int read_texture_to_rows(const float *tex_cn, int64_t n, int C, float *rows_nc, 
 int read_rows_to_texture(const float *rows_nc, int64_t n, int C, float *tex_cn, void *stream);
 
 /*
- * feat_l[p][c] = rows[idx_l[p]][c]  for every level l and pixel p (NHWC, C % 4 == 0).
- *   count_levels[l] = number of pixels of level l (B*h_l*w_l); activation: 0 none, 1 sigmoid, 2 tanh
+ * feat_l[p][c] = act(rows[idx_l[p]][c])  for every level l and pixel p (NHWC, C % 4 == 0, C <= 64).
+ *   count_levels[l] = number of pixels of level l (B*h_l*w_l; 0 = an empty level, its pointers may be NULL);
+ *   activation: 0 none, 1 sigmoid, 2 tanh.  An id below 0 reads row 0, an id >= n reads row n - 1 (the clamp of the table gather).
+ *   Activation 0 hands the row's bits through (-0, subnormals and NaN payloads included); NaN gives NaN, +-inf gives 0 / 1 / +-1.
  */
 int read_gather_forward(const float *rows_nc, int64_t n, int C, int levels,
                         const int32_t *const *idx_levels, const int64_t *count_levels,
@@ -415,7 +417,11 @@ int read_gather_forward(const float *rows_nc, int64_t n, int C, int levels,
 /* Supersampled lookup (READ/gl/nn.py:100-101 + READ/models/compose.py:162-163): index maps rendered at ss x the feature
  * size; feat_l = bilinear-downscale-by-ss (align_corners = False, torch's F.interpolate(scale_factor = 1/ss)) of the
  * activated samples, fused: each output pixel blends the four samples around source coordinate (o + 0.5) * ss - 0.5.
- *   h_levels[l], w_levels[l] = OUTPUT size of level l; idx_l is [B][ss*h][ss*w]; feat_l is [B][h][w][C]. */
+ *   h_levels[l], w_levels[l] = OUTPUT size of level l; idx_l is [B][ss*h][ss*w]; feat_l is [B][h][w][C].
+ *   ss = 1..8, ids clamped as in read_gather_forward.  For odd ss the source coordinate is an integer: the output is the activated
+ *   centre sample, bit for bit what read_gather_forward returns for that id (ss = 1: read_gather_forward itself), whatever its
+ *   neighbours hold.  For even ss it is the mean of four activated samples (weights 1/4, at most three rounded additions); a
+ *   non-finite sample makes the outputs that blend it non-finite. */
 int read_gather_forward_ss(const float *rows_nc, int64_t n, int C, int levels, int B,
                            const int32_t *const *idx_levels, const int *h_levels, const int *w_levels, int ss,
                            float *const *feat_levels, int activation, void *stream);
@@ -486,7 +492,10 @@ int read_stitch_gather_forward(const read_stitch_part *parts, int count, int C, 
                                const int64_t *count_levels,
                                int32_t *const *idx_levels, float *const *depth_levels,
                                unsigned char *const *part_levels, float *const *feat_levels, void *stream);
-/* drows[idx_l[p]][c] += dfeat_l[p][c]   (fp32 atomics; drows must be zeroed by the caller). */
+/* drows[idx_l[p]][c] += dfeat_l[p][c]   (fp32 atomics; drows must be zeroed by the caller).  The ids are clamped as in
+ * read_gather_forward: the gradient of an id below 0 lands on row 0, that of an id >= n on row n - 1 — the row the forward read.
+ * Into zeroed rows, a row addressed once holds that gradient's bits and a row nobody addressed stays +0; a row addressed k times is
+ * a sum in an order that changes from run to run, within (k - 1) u sum |dfeat| (u = 2^-24) of the exact sum. */
 int read_gather_backward(float *drows_nc, int64_t n, int C, int levels,
                          const int32_t *const *idx_levels, const int64_t *count_levels,
                          const float *const *dfeat_levels, void *stream);
@@ -494,7 +503,10 @@ int read_gather_backward(float *drows_nc, int64_t n, int C, int levels,
 /* Bilinear down-scale by an integer factor ss (2..8) of `planes` NCHW planes [ss*h][ss*w] -> [h][w]: torch's
  * F.interpolate(scale_factor = 1/ss, mode = 'bilinear', align_corners = False) as READ/models/compose.py:162-163 applies it to
  * network inputs that mix non-uv tokens with texture samples (the all-uv case is fused into read_gather_forward_ss), and its
- * adjoint (din is written, not accumulated). */
+ * adjoint (din is written, not accumulated): exactly dout / 4 on the 2 x 2 footprint of even ss, dout on the centre sample of odd
+ * ss, +0 on every other sample.  The forward at odd ss still blends with the weights 1, 0, 0, 0: finite inputs give the centre
+ * sample's VALUE, but a -0 comes back as +0 and a non-finite neighbour makes the output NaN — the bit identity of odd ss is a promise
+ * of read_gather_forward_ss only. */
 int read_bilinear_down(const float *in, int64_t planes, int h, int w, int ss, float *out, void *stream);
 int read_bilinear_down_backward(const float *dout, int64_t planes, int h, int w, int ss, float *din, void *stream);
 

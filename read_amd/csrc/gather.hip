@@ -119,6 +119,9 @@ __global__ __launch_bounds__(256) void gather_forward_ss_kernel(const float *__r
         o.y = wy0 * (wx0 * v[0].y + lx * v[1].y) + ly * (wx0 * v[2].y + lx * v[3].y);
         o.z = wy0 * (wx0 * v[0].z + lx * v[1].z) + ly * (wx0 * v[2].z + lx * v[3].z);
         o.w = wy0 * (wx0 * v[0].w + lx * v[1].w) + ly * (wx0 * v[2].w + lx * v[3].w);
+        // odd ss: the source coordinate is the centre sample itself.  The blend's zero-weight terms would turn a -0 sample into +0
+        // and a non-finite neighbour into NaN; the sample is returned as it is (wave-uniform: ss is a kernel argument)
+        if (ss & 1) o = v[0];
         *reinterpret_cast<float4 *>(tab.feat[l] + pix * C + 4 * q) = o;
     }
 }
@@ -271,7 +274,8 @@ __global__ __launch_bounds__(256) void bilinear_down_backward_kernel(const float
         if (y == y1) wy += ly;
         if (x == x0) wx += 1.0f - lx;
         if (x == x1) wx += lx;
-        din[i] = wy * wx * dout[(p * h + oy) * w + ox];
+        const float wgt = wy * wx;                  // 1/4 on the footprint of even ss, 1 on the centre of odd ss, 0 elsewhere
+        din[i] = wgt != 0.0f ? wgt * dout[(p * h + oy) * w + ox] : 0.0f;   // +0 outside the footprint, whatever the sign of dout
     }
 }
 
