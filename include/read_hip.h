@@ -262,6 +262,58 @@ int read_splat_forward_lens_instances(const float *xyz, const int32_t *ids, int6
 int read_splat_lens_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel, float *depth,
                                    void *stream);
 
+/* LiDAR sweep: the range image and the point list of a spinning LiDAR placed in the fitted scene (csrc/lidar.hip; the definition
+ * is tests/lidar_model.py).  cam_host = 16 floats on the host (camera.lidar_camera): [0..11] three UNSCALED rows applied to
+ * (x, y, z, 1) giving c0 = x_c, c1 = y_c and c3 = -z_c (forward), [12] kx = 2 / hfov_rad, [13] rmin > 0, [14] rmax >= rmin,
+ * [15] delta >= 0, a beam's acceptance half-width in radians.  elev_host = B beam elevations in radians on the host, finite and
+ * strictly ascending, 1 <= B <= 128; row b of every image is beam b.  W = azimuth columns, B W < 2^31.  Per point, in fp32 without
+ * fused operations: q = c0 c0 + c3 c3, rho = sqrt(q), theta = atan2(c0, c3), phi = atan2(c1, rho), r = sqrt(q + c1 c1); column =
+ * (int)((W (theta kx + 1)) 0.5) while -1 <= theta kx <= 1 and the column is below W; beam = the b of the smallest
+ * |phi - elev[b]| (ties to the lower b) while that is <= delta; drawn while rmin <= r <= rmax.  Per cell b W + column the minimum of
+ * range bits << 32 | id wins.
+ *
+ * The see-through filter then works on the complete image: a return of range r is kept iff r <= near scale + slack, near = the
+ * smallest range among the returns with |db| <= wb, |dc| <= wc (rows clipped; columns modulo W iff wrap, else clipped; the cell
+ * itself counts); wb = wc = 0 keeps everything.  Outputs, each NULL or a device buffer: range / idx (B x W; empty cells 0.0f / 0);
+ * count (one int32: the kept returns, also beyond capacity); cell / ret_id (capacity each) and ret_xyz (capacity x 3): the first
+ * min(count, capacity) kept returns in ascending cell order, ret_xyz in the sensor frame along the beam —
+ * x = (r ce_b) st_c, y = r se_b, z = -((r ce_b) ct_c) from the device tables beam_dir (B x 2: cos, sin of elev[b]) and col_dir
+ * (W x 2: sin, cos of ((c + 0.5) / W 2 - 1) / kx), each formed on the host in float64 and rounded once; they are needed only with
+ * ret_xyz.
+ *
+ * xyz / ids / n (device): the cloud, or a labelled cloud's static part; ids == NULL: the id is the point's index.  inst: NULL, or
+ * the list of read_splat_forward_pano_instances with inst->M = count x 16 floats in the LiDAR layout (rows (R4 @ P_i)[:3], the four
+ * scalars repeat).  The workspace is the sweep's own (read_lidar_workspace_bytes(B, W), 256-byte aligned, filled once by
+ * read_lidar_workspace_init): every sweep leaves all of it as init did, so sweeps of any sizes that fit follow each other on it
+ * without a memset, and the rasteriser's workspace is not touched — frames and sweeps interleave freely.  Stream-ordered, allocates
+ * nothing, no synchronisation, no kernel waits for another workgroup.  READ_EINVAL with a message naming the call, before any
+ * device work, for: null pointers with work to do; B outside 1..128, W < 1, B W >= 2^31; a table that is not finite and strictly
+ * ascending; non-finite camera entries, also of every drawn instance; kx < 1 / pi; rmin <= 0; rmax < rmin; delta < 0; wb or wc
+ * outside 0..4; scale < 1 or slack < 0 or either not finite; capacity < 0; a malformed instance list; READ_ENOMEM for a workspace
+ * that is too small. */
+size_t read_lidar_workspace_bytes(int B, int W);
+int read_lidar_workspace_init(void *workspace, size_t workspace_bytes, void *stream);
+typedef struct read_lidar_args {
+    const float *xyz; const int32_t *ids; int64_t n;   /* device: the cloud or the static part; ids NULL = the indices */
+    const read_splat_instances *inst;                  /* NULL, or the instance list (M in the LiDAR layout) */
+    const float *cam_host;                             /* host, 16 */
+    const float *elev_host;                            /* host, B */
+    int B, W;
+    const float *beam_dir; const float *col_dir;       /* device, B x 2 and W x 2; may be NULL without ret_xyz */
+    int wb, wc, wrap;                                  /* the filter's window (0..4 each) and whether columns wrap */
+    float scale, slack;                                /* lim = near scale + slack; scale = fp32(1 + rel) >= 1, slack >= 0 */
+    float *range; int32_t *idx;                        /* device, B x W each, or NULL */
+    int32_t *count;                                    /* device, 1, or NULL */
+    int32_t *cell; int32_t *ret_id; float *ret_xyz;    /* device, capacity (x 3), or NULL */
+    int64_t capacity;
+    void *workspace; size_t workspace_bytes;
+} read_lidar_args;
+int read_lidar_sweep(const read_lidar_args *args, void *stream);
+/* The per-point function of read_lidar_sweep's pass alone: cell[i] = the cell of point i or -1, range[i] = its range (0.0f where
+ * cell[i] = -1).  Same checks of cam_host, elev_host, B and W. */
+int read_lidar_project_points(const float *xyz, int64_t n, const float *cam_host, const float *elev_host, int B, int W,
+                              int32_t *cell, float *range, void *stream);
+
 /* Measurement aid for bench.py (roofline.mfma_sustained): one workgroup of four waves per CU, every wave `iters` rounds of 16 independent
  * v_mfma_f32_16x16x4_f32 and nothing else.  scratch: >= 256 floats per CU on the device (never written); *flops receives the number of
  * floating-point operations the launch executes — the caller times the launch on `stream`.  Not on the render path. */

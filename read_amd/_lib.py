@@ -71,6 +71,16 @@ class SplatInstances(C.Structure):
                 ("npts", C.c_void_p), ("M", C.c_void_p), ("visible", C.c_void_p)]
 
 
+class LidarArgs(C.Structure):
+    """read_lidar_args (include/read_hip.h): one read_lidar_sweep call."""
+    _fields_ = [("xyz", C.c_void_p), ("ids", C.c_void_p), ("n", C.c_int64), ("inst", C.POINTER(SplatInstances)),
+                ("cam_host", C.c_void_p), ("elev_host", C.c_void_p), ("B", C.c_int), ("W", C.c_int),
+                ("beam_dir", C.c_void_p), ("col_dir", C.c_void_p), ("wb", C.c_int), ("wc", C.c_int), ("wrap", C.c_int),
+                ("scale", C.c_float), ("slack", C.c_float), ("range", C.c_void_p), ("idx", C.c_void_p), ("count", C.c_void_p),
+                ("cell", C.c_void_p), ("ret_id", C.c_void_p), ("ret_xyz", C.c_void_p), ("capacity", C.c_int64),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 READ_GATHER_MAX_TABLES = 8
 
 
@@ -151,6 +161,10 @@ SIGNATURES = {
     "read_splat_forward_lens": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_forward_lens_instances": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _vp, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_lens_project_points": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _vp]),
+    "read_lidar_workspace_bytes": (_sz, [_i, _i]),
+    "read_lidar_workspace_init": (_i, [_vp, _sz, _vp]),
+    "read_lidar_sweep": (_i, [C.POINTER(LidarArgs), _vp]),
+    "read_lidar_project_points": (_i, [_vp, _i64, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "read_splat_forward_cells": (_i, [_vp, _vp, _i64, C.POINTER(_f), _i, _i, _i, _i, _pp, _pp, _vp, _sz, _vp]),
     "read_splat_hint_next_camera": (_i, [_vp, C.POINTER(_f)]),
     "read_splat_profile_last": (_i, [C.POINTER(_f)]),

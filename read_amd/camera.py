@@ -61,6 +61,33 @@ def pano_camera(proj_matrix, view_matrix, hfov_deg):
     return np.ascontiguousarray(cam.astype(np.float32))
 
 
+def lidar_camera(view_matrix, hfov_deg=360., rmin=0.5, rmax=120., half_width=np.deg2rad(0.2)):
+    """The sensor of ``PointCloudRasterizer.sweep_lidar``: 16 float32 numbers, formed here in float64 and rounded once — like
+    ``total_matrix`` an INPUT to the kernels, never re-derived on the device.
+
+    [0:12]  three UNSCALED rows applied to (x, y, z, 1): c0 = x_c, c1 = y_c, c3 = -z_c (forward), with (x_c, y_c, z_c, 1) =
+            inv(view) @ (x, y, z, 1); ``view_matrix`` is sensor->world.  These are the lens camera's rows; no projection matrix
+    [12]    kx = 2 / hfov_rad: the azimuth column is W * (atan2(c0, c3) * kx + 1) / 2;  hfov_deg in (0, 360]
+    [13:15] rmin > 0 and rmax >= rmin: a return's metric range lies in [rmin, rmax]
+    [15]    half_width >= 0: a beam accepts elevations within this many RADIANS of its own"""
+    hfov = float(hfov_deg)
+    if not 0.0 < hfov <= 360.0:
+        raise ValueError(f"hfov_deg must lie in (0, 360], got {hfov_deg!r}")
+    rmin, rmax, half_width = float(rmin), float(rmax), float(half_width)
+    if not (0.0 < rmin <= rmax and np.isfinite(rmax)):
+        raise ValueError(f"a LiDAR needs 0 < rmin <= rmax < inf, got rmin = {rmin!r}, rmax = {rmax!r}")
+    if not (half_width >= 0.0 and np.isfinite(half_width)):
+        raise ValueError(f"half_width must be a finite angle >= 0 (radians), got {half_width!r}")
+    w2c = np.linalg.inv(np.asarray(view_matrix, np.float64).reshape(4, 4))
+    cam = np.empty(16, np.float64)
+    cam[0:4] = w2c[0]
+    cam[4:8] = w2c[1]
+    cam[8:12] = -w2c[2]
+    cam[12] = 2.0 / (hfov * (np.pi / 180.0))
+    cam[13], cam[14], cam[15] = rmin, rmax, half_width
+    return np.ascontiguousarray(cam.astype(np.float32))
+
+
 LENS_PINHOLE, LENS_FISHEYE = 0, 1      # model 0: Brown-Conrady (k1, k2, p1, p2, k3); model 1: Kannala-Brandt (k1, k2, k3, k4)
 LENS_LIMIT_SHARE = 0.999               # the default limit, as a share of the radial profile's first stationary point
 

@@ -18,6 +18,11 @@ int launch_gated_conv(const read_conv_desc *d, hipStream_t stream, const void *w
 int conv_family(const read_conv_desc *d);
 void conv_set_trace(void *buf, size_t bytes);
 
+// splat.hip
+// What a read_splat_instances must be (count, pointers, every range inside its n points): READ_OK, or READ_EINVAL with a message
+// that starts with `who`.  The checks of read_splat_forward_instances and its panorama and lens twins; read_lidar_sweep shares them.
+int check_instances(const char *who, const read_splat_instances *inst);
+
 // One row of a module's table of tuning keys; the order of the rows is the order read_tuning_key enumerates them in.
 enum TuneNorm {
     TN_RAW,

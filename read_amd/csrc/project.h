@@ -71,4 +71,29 @@ __device__ __forceinline__ int project_one(float x, float y, float z, const floa
     return ok ? yy * W + xx : -1;
 }
 
+// The arctangent of the panorama, lens and LiDAR cameras (splat.hip, lidar.hip); tests/pano_model.py::atan2_model is the definition.
+// atan2 of the model: t = small / large of (|a|, |b|) by compare-and-select (NaN takes the 'false' side, as NumPy's where),
+// Abramowitz & Stegun 4.4.49 by Horner in t^2, then the octant fix-ups.  The literals are the model's ATAN_COEFFS, bit for bit.
+__device__ __forceinline__ float pano_atan2(float a, float b)
+{
+    const float ax = fabsf(a), az = fabsf(b);
+    const bool swap = ax > az;
+    const float large = swap ? ax : az, small = swap ? az : ax;
+    const float t = large == 0.0f ? 0.0f : small / large;
+    const float s = t * t;
+    float p = 0.0028662257f;
+    p = p * s + -0.0161657367f;
+    p = p * s + 0.0429096138f;
+    p = p * s + -0.0752896400f;
+    p = p * s + 0.1065626393f;
+    p = p * s + -0.1420889944f;
+    p = p * s + 0.1999355085f;
+    p = p * s + -0.3333314528f;
+    p = p * s + 1.0f;
+    float r = p * t;
+    if (swap) r = 1.57079632679489661923f - r;
+    if (b < 0.0f) r = 3.14159265358979323846f - r;
+    return copysignf(r, a);
+}
+
 }  // namespace readhip

@@ -1198,30 +1198,7 @@ __global__ __launch_bounds__(256) void splat_objects_kernel(const float *__restr
 // c1 = P[1,1] y_c, c3 = -z_c —, c[12] = kx = 2 / hfov_rad, c[13] = ky = P[1,2], c[14] = za = P[2,2], c[15] = zb = P[2,3].
 // tests/pano_model.py is the definition; this restates it: fp32, no contraction, sums left to right, IEEE division, correctly
 // rounded square root.  No chunk culling here: a cylinder does not map a box to the hull of its corners.
-//
-// atan2 of the model: t = small / large of (|a|, |b|) by compare-and-select (NaN takes the 'false' side, as NumPy's where),
-// Abramowitz & Stegun 4.4.49 by Horner in t^2, then the octant fix-ups.  The literals are the model's ATAN_COEFFS, bit for bit.
-__device__ __forceinline__ float pano_atan2(float a, float b)
-{
-    const float ax = fabsf(a), az = fabsf(b);
-    const bool swap = ax > az;
-    const float large = swap ? ax : az, small = swap ? az : ax;
-    const float t = large == 0.0f ? 0.0f : small / large;
-    const float s = t * t;
-    float p = 0.0028662257f;
-    p = p * s + -0.0161657367f;
-    p = p * s + 0.0429096138f;
-    p = p * s + -0.0752896400f;
-    p = p * s + 0.1065626393f;
-    p = p * s + -0.1420889944f;
-    p = p * s + 0.1999355085f;
-    p = p * s + -0.3333314528f;
-    p = p * s + 1.0f;
-    float r = p * t;
-    if (swap) r = 1.57079632679489661923f - r;
-    if (b < 0.0f) r = 3.14159265358979323846f - r;
-    return copysignf(r, a);
-}
+// The model's arctangent, pano_atan2, lives in project.h (lidar.hip shares it).
 
 // One point under one panorama camera; returns the pixel or -1.  rho = 0, NaN and Inf fall out through `inside`.
 __device__ __forceinline__ int project_pano_one(float x, float y, float z, const float *c, int W, int H,
@@ -2830,8 +2807,10 @@ int check_partition(const char *who, const read_splat_objects *objs)
     return READ_OK;
 }
 
-// what a read_splat_instances must be: ranges inside its n points (they may repeat and overlap)
-int check_instances(const char *who, const read_splat_instances *inst)
+}  // namespace
+
+// what a read_splat_instances must be: ranges inside its n points (they may repeat and overlap); lidar.hip asks the same (internal.h)
+int readhip::check_instances(const char *who, const read_splat_instances *inst)
 {
     READ_CHECK_ARG(inst->count >= 0, "%s: inst->count = %d is negative", who, inst->count);
     READ_CHECK_ARG(inst->n >= 0 && inst->n <= 0xFFFFFFFEll, "%s: inst->n out of range", who);
@@ -2847,6 +2826,7 @@ int check_instances(const char *who, const read_splat_instances *inst)
     return READ_OK;
 }
 
+namespace {
 ObjectsDraw instances_draw(const read_splat_instances *inst)
 {
     ObjectsDraw od{};

@@ -348,6 +348,51 @@ class PointCloudRasterizer:
                                                  dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_lens")
         return idx, dep
 
+    def lidar_instance_cameras(self, cam):
+        """The (I,16) float32 sensors of the instances, in handle order, for the sensor ``cam`` (camera.lidar_camera): the layout
+        is the panorama's — rows ``object_matrix(R4, P_i)[:3]``, the four scalars (kx, rmin, rmax, half-width) repeat."""
+        return self.pano_instance_cameras(cam)
+
+    def _lidar_workspace(self, B, W):
+        """The sweeps' own workspace, apart from the frames': one for every sensor (a sweep leaves it as init did), grown when a
+        larger sensor comes."""
+        need = _lib.lib().read_lidar_workspace_bytes(B, W)
+        ws = getattr(self, '_lidar_ws', None)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            _lib.check(_lib.lib().read_lidar_workspace_init(ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_lidar_workspace_init")
+            self._lidar_ws = ws
+        return ws
+
+    def _return_labels(self):
+        """labels[id] for every id a return can carry: the cloud's labels, then every foreign object's number (K + 1 + ordinal,
+        as in ``annotate``); None for a cloud without labels and foreign objects."""
+        if self.labels is None and not self._foreign:
+            return None
+        K = len(self._own_ranges) if self._inst is not None else 0
+        own = self.labels if self.labels is not None else torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        return torch.cat([own] + [torch.full((int(f.shape[0]),), K + 1 + j, dtype=torch.int32, device=self.device)
+                                  for j, (f, _) in enumerate(self._foreign)])
+
+    def sweep_lidar(self, sensor, cam, out=None):
+        """One LiDAR sweep (read_amd/lidar.py): ``sensor`` = a ``LidarSensor``, ``cam`` = its 16 floats at the
+        sensor's pose (``sensor.camera(view)``) -> a ``LidarSweep`` (``out``: one to write into).  Object labels, poses, visibility
+        and instances are honoured as in ``render_pano``; the whole cloud is read every sweep.  Stream-ordered, nothing is
+        synchronised; sweeps use a workspace of their own, so frames and sweeps interleave freely."""
+        from . import lidar
+        out = lidar.LidarSweep(sensor, device=self.device) if out is None else out
+        ws = self._lidar_workspace(sensor.B, sensor.W)
+        cam = _host_f32(cam).reshape(16)
+        if self._inst is not None:
+            inst = self._instances_struct(self.lidar_instance_cameras(cam))
+            # a cloud without labels is static as a whole: its points' indices are their ids, and none are passed
+            ids = (self._static_ids.data_ptr() or None) if self.labels is not None else None
+            lidar.sweep(sensor, cam, self._static_xyz.data_ptr() or None, ids, self.n_static, C.pointer(inst), ws, out)
+        else:
+            lidar.sweep(sensor, cam, self.xyz.data_ptr() or None, None, self.n, None, ws, out)
+        out._label_table = self._return_labels()
+        return out
+
     def bind(self, W, H, levels, out, totals):
         """A pre-bound frame call for loops that must not be host-bound (benchmark stages): every ctypes argument is built ONCE —
         the outputs ``out`` = (idx levels, depth levels or None) and the list of camera matrices ``totals`` — and

@@ -442,6 +442,20 @@ class Scene:
         view = np.linalg.inv(self.model_matrix.astype(np.float64)) @ self.view_matrix.astype(np.float64)
         return lens_camera(self.proj_matrix, view, *self.lens)
 
+    def lidar_sweep(self, sensor, view_matrix=None):
+        """Extension (not in NNScene): one sweep of the ``lidar.LidarSensor`` placed at ``view_matrix`` (sensor -> world; None =
+        the scene's camera view) -> a ``lidar.LidarSweep``: range image, point ids and the return list, with the current object
+        edits.  Points are taken to the sensor by inv(view) @ model, as in ``pano_camera``; the LiDAR is a sensor of its own, so
+        the projection matrix, ``set_panorama`` and ``set_lens`` play no part."""
+        if self.xyz is None:
+            raise ValueError("scene has no point cloud (set_vertices)")
+        if self.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with lidar_sweep: a sweep ranges "
+                                      "the cloud's points as they are")
+        view = self.view_matrix if view_matrix is None else np.asarray(view_matrix, np.float32)
+        view = np.linalg.inv(self.model_matrix.astype(np.float64)) @ view.astype(np.float64)
+        return self.rasterizer().sweep_lidar(sensor, sensor.camera(view))
+
     def set_use_light(self, use_light):
         if use_light:
             raise NotImplementedError("the viewer's lighting pass is not part of the render path")
@@ -689,6 +703,10 @@ class StitchedScene:
     def annotate_frame(self, *args, **kwargs):
         raise NotImplementedError("annotate_frame on a StitchedScene: instances belong to a part and the merged frame carries "
                                   "stitched ids; annotate the parts' own frames")
+
+    def lidar_sweep(self, *args, **kwargs):
+        raise NotImplementedError("lidar_sweep on a StitchedScene: a sweep ranges one cloud and its instances; sweep the parts "
+                                  "(scenes[s].lidar_sweep)")
 
     def select_boxes(self, *args, **kwargs):
         raise NotImplementedError("select_boxes on a StitchedScene: labels belong to a part; select on the parts "
