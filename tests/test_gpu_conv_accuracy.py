@@ -7,8 +7,12 @@ generators).  Each case is asserted against
     profiles/conv_accuracy_fp64.md (twice the largest measured ratio, rounded up to a power of two) — not where the oracle's error is
     below one unit (R_max < 1: impulses, where oneDNN is exact);
   * exactness where no product reaches the output (gamma = 0, an all-zero conv_f row with zero bias): the epilogue constant, ==.
-Every element of every case is measured.  The fp32 kernels (Winograd F(4x4) config -5, one direct fp32 configuration) run on the 3x3
-cases for the printed table only: they are the baseline the split kernels replaced.
+Every element of every case is measured.  The fp32 kernels the split kernels replaced (Winograd F(4x4), config -5, family 4; one direct
+fp32 configuration, family 0) are still what the full weight layout falls back to (conv_w4h = 0): on the 3x3 / stride-1 cases of classes
+(a) - (c) their linear launches are held to the fp32 bound of the training forward (tests/train_ref64.py: conv_forward_bound) and their
+gated launches to gated_bound composed from it — families "fp32_w4", "fp32_direct"; no measured cap: the derived bound, the kernel
+family, finiteness and the exact constants.  Class (d) is built for the f16 range these kernels do not have: one case at 2e4 must be
+finite.
 An automatic launch (config -1) of the 3x3 / stride-1 family is attributed BY ITS BITS — the F(4x4) and the F(4,3)-by-rows kernel both
 report family 5 — and held to the bound and cap of the kernel that ran.
 Plus the persistent walk (shapes with more units than the device has compute units, impulses in a workgroup's second and third unit),
@@ -33,13 +37,19 @@ import torch
 
 from read_amd.gated_conv import PackedGatedConv, config_names, conv_desc, gated_conv
 from tests import conv_ref64 as R64
+from tests import train_ref64 as T
 
 pytestmark = pytest.mark.gpu
 
-FAMILY_ID = {"w4h": 5, "f4x1": 5, "d3h": 6, "d3h_s2": 6, "pxh": 7, "t3h": 8, "pxh_pre": 7, "chain": 7, "sc": 1}
+FAMILY_ID = {"w4h": 5, "f4x1": 5, "d3h": 6, "d3h_s2": 6, "pxh": 7, "t3h": 8, "pxh_pre": 7, "chain": 7, "sc": 1, "fp32_w4": 4, "fp32_direct": 0}
 FORCE = {"w4h": -7, "f4x1": -12, "d3h": -8, "d3h_s2": -1, "pxh": -10, "t3h": -11,         # stride 2 goes through the automatic choice, family asserted
          "pxh_pre": -10, "chain": -10, "sc": -6}                                           # pxh_pre: gated_conv_pxh_kernel with an addend; chain: the six AFF launches; sc: the head
 DIRECT_FP32 = "k3s1c16_p2q1m4n1f1b2"
+FP32 = {"fp32_w4": "w4", "fp32_direct": "direct"}                                          # the fp32 kernels: family of T.conv_forward_bound
+
+
+def fp32_config(family):
+    return -5 if family == "fp32_w4" else config_names().index(DIRECT_FP32)
 
 
 def _pack(L, src_channels):
@@ -110,11 +120,19 @@ class Case:
         return out.cpu().numpy().transpose(2, 0, 1), fam
 
 
-def _bounds(case, family):
-    """-> (d_f, d_m, B_w): the pre-activation bounds and, for the Winograd family, the condition term B with A_w in the place of A."""
+def _bounds(case, family, linear=False):
+    """-> (d_f, d_m, B_w): the pre-activation bounds and, for the Winograd family, the condition term B with A_w in the place of A (a
+    linear launch of the fp32 Winograd kernel: [A_w + |b_f| | A_w + |b_m|])."""
+    if (family, linear) in case._bounds:
+        return case._bounds[(family, linear)]
     if family not in case._bounds:
         ref = case.ref()
-        if family in ("w4h", "f4x1"):
+        if family in FP32:
+            (df, cf), (dm, cm) = (T.conv_forward_bound(case.L, case.x, ref, FP32[family], fm) for fm in "fm")
+            Bw = ref.S * (np.abs(ref.dact) * ref.sig * cf + np.abs(ref.g) * ref.sig * (1.0 - ref.sig) * cm) + np.abs(ref.y)
+            case._bounds[(family, True)] = (df, dm, np.concatenate([cf, cm]) if family == "fp32_w4" else None)
+            case._bounds[family] = (df, dm, Bw if family == "fp32_w4" else None)
+        elif family in ("w4h", "f4x1"):
             preact = R64.preact_bound_wino if family == "w4h" else R64.preact_bound_f4x1
             df, Awf = preact(case.L, case.x, ref, "f")
             dm, Awm = preact(case.L, case.x, ref, "m")
@@ -130,7 +148,7 @@ def _bounds(case, family):
         else:
             df, dm = (R64.preact_bound_direct(case.L, ref, family, fm) for fm in "fm")
             case._bounds[family] = (df, dm, None)
-    return case._bounds[family]
+    return case._bounds.get((family, linear), case._bounds[family])
 
 
 def check(case, config, linear=False, family=None, rows=None, assert_caps=True):
@@ -139,7 +157,7 @@ def check(case, config, linear=False, family=None, rows=None, assert_caps=True):
     ref = case.ref()
     got, fam = case.launch(config, linear)
     ora = R64.oracle_fp32(case.L, case.x, stride=case.stride, elu=case.elu, residual=case.residual, mul=case.mul, linear=linear, pre=case.addend())
-    df, dm, Bw = _bounds(case, family) if family is not None else (None, None, None)
+    df, dm, Bw = _bounds(case, family, linear) if family is not None else (None, None, None)
     return judge(case.L, ref, got, ora, fam, df, dm, Bw, family, case.cls, case.name, config, linear, rows, assert_caps)
 
 
@@ -175,7 +193,7 @@ def judge(L, ref, got, ora, fam, df, dm, Bw, family, cls, name, config, linear=F
     assert fam == FAMILY_ID[family], f"{what}: the launch took kernel family {fam}"
     assert finite, f"{what}: non-finite output inside the documented range"
     assert q <= 1.0, f"{what}: {q:.3f} x the derived bound (E_max {e_max:.1f}, E_rms {e_rms:.2f})"
-    if r_max >= 1.0:
+    if r_max >= 1.0 and family not in FP32:
         c = R64.measured_cap(family, row["mode"], cls)
         assert e_rms <= c * r_rms and e_max <= c * r_max, f"{what}: E_max {e_max:.2f} E_rms {e_rms:.3f} against {c} x (R_max {r_max:.2f}, R_rms {r_rms:.3f})"
     if not linear:
@@ -294,14 +312,29 @@ def run_family(family, rows=None, assert_caps=True, classes="abcd"):
             if cls in "ab" and FORCE[family] != -1:
                 # the automatic choice: held to the bound and caps of whichever split-operand kernel it takes, printed otherwise
                 check(case, -1, family=attribute_auto(case), rows=rows, assert_caps=assert_caps)
-            if cls in "ab" and case.k == 3 and case.stride == 1 and family in ("w4h", "d3h") and case.x.shape[0] % 16 == 0:
-                check(case, -5, family=None, rows=rows)                                      # fp32 Winograd F(4x4): printed only
-                check(case, config_names().index(DIRECT_FP32), family=None, rows=rows)      # fp32 direct: printed only
 
 
 @pytest.mark.parametrize("family", ["w4h", "f4x1", "d3h", "d3h_s2", "pxh", "t3h"])
 def test_split_operand_family_against_fp64(hip, family):
     run_family(family)
+
+
+def fp32_cases(cls):
+    """The 3x3 / stride-1 cases the fp32 kernels have always run on — classes (a), (b) of families w4h and d3h — and class (c) of w4h
+    (d3h's structured cases are the same)."""
+    for family in ("w4h", "d3h") if cls in "ab" else ("w4h",):
+        for case in ALL_CLASSES[cls](family):
+            if case.k == 3 and case.stride == 1 and case.x.shape[0] % 16 == 0:
+                yield case
+
+
+@pytest.mark.parametrize("cls", ["a", "b", "c"])
+@pytest.mark.parametrize("family", list(FP32))
+def test_fp32_kernels_against_fp64(hip, family, cls):
+    """The fp32 Winograd F(4x4) kernel (config -5) and the direct fp32 configuration, linear and gated (module docstring)."""
+    for case in fp32_cases(cls):
+        for linear in (True, False):
+            check(case, fp32_config(family), linear=linear, family=family)
 
 
 # ------------------------------------------------------------------------------------------ resampled sources, addends, the AFF chain
@@ -560,6 +593,17 @@ def test_f4x1_fails_loudly_past_its_range(hip):
     x = (np.random.default_rng(78).standard_normal((64, 24, 40)) * 2.0e4).astype(np.float32)
     got, fam = Case("f4x1", "d", "normal x 2e4", L, x).launch(FORCE["f4x1"])
     assert fam == 5 and not np.isfinite(got).all(), "overflow of the f16 pieces must not pass silently"
+
+
+def test_fp32_kernels_stay_finite_past_the_f16_range(hip):
+    """The counterpart of test_f4x1_fails_loudly_past_its_range: on the same activations of ~2e4 the fp32 kernels have no range to leave —
+    finite, and inside the fp32 bound like every other case."""
+    L = R64.tame_layer(64, 64, 3, 78)
+    x = (np.random.default_rng(78).standard_normal((64, 24, 40)) * 2.0e4).astype(np.float32)
+    case = Case("fp32", "d", "normal x 2e4", L, x)
+    for fp32 in FP32:
+        for linear in (True, False):
+            assert check(case, fp32_config(fp32), linear=linear, family=fp32)["finite"]
 
 
 def test_fam_multiply_through_the_direct_split_kernel(hip):

@@ -5,7 +5,10 @@
     kernels' own order of operations and without fused multiply-adds, stay inside the derived bounds on every input class;
   * the restatements reproduce the class (d) behaviour DESIGN.md quotes (the dgamma error in units of the centred condition term grows
     with |mean| / std; a constant channel misses beta by about u |mean| scale);
-  * the generators do what they claim."""
+  * the generators do what they claim;
+  * the forward's linear launches (tests/train_forward_cases.py): the fp32 restatement of the three convolution kernels and the fused gate
+    passes every assertion of tests/test_gpu_train_forward_accuracy.py, each seeded defect of the mutation catalogue fails one, and
+    conv_forward_bound restates conv_dgrad_bound."""
 import numpy as np
 import pytest
 import torch
@@ -13,8 +16,9 @@ import torch.nn.functional as F
 
 from tests import conv_ref64 as R64
 from tests import train_ref64 as T
-from tests.train_fp32 import (bn_bwd_coeff32, bn_forward32, bn_grads32, gate32, gate_backward32, wgrad_direct32,  # noqa: F401
-                              wgrad_wino32)
+from tests import train_forward_cases as FC
+from tests.train_fp32 import (GUARD, MUTATIONS, bn_bwd_coeff32, bn_forward32, bn_grads32, gate32, gate_backward32,  # noqa: F401
+                              linear_launch32, wgrad_direct32, wgrad_wino32)
 
 f32 = np.float32
 
@@ -169,6 +173,112 @@ def test_fp32_restatements_of_both_wgrad_kernels_stay_inside_the_derived_bounds(
             assert (Aw >= A * (1 - 1e-12)).all()                       # the transformed-domain condition term dominates the direct one
             got = wgrad_wino32(x, d, T.wgrad4_plan(cin, cout, H))
             assert T.worst(np.abs(got - ref), T.wgrad_wino_bound(Aw, cin, cout, H, W)) <= 1.0, (cin, cout, H, W, cls)
+
+
+# ------------------------------------------------------------------------------------------ the forward's linear launches
+VARIANTS = ((True, False), (False, True), (True, True), (False, False))                          # (elu, identity_bn), as the GPU test launches them
+
+
+def _run_assertions(case, family, elu_identity, block_h=0, valid_h=0, mut=None, unstacked=None):
+    """The restatement's buffers of one launch per variant through the assertions the GPU test applies to the device's.
+    -> (failures, err / bound of every judged row, (fm, y) of the last variant)."""
+    fails = []
+    judge = FC.bound_judge(fails)
+    out = None
+    for elu, identity in elu_identity:
+        sc, sh = FC.scale_shift32(case.L, identity)
+        fm_buf, y_buf = linear_launch32(case.L, case.x, case.stride, family, elu, sc, sh, block_h, valid_h, mut=mut)
+        fm = FC.check_preactivations(case, family, fm_buf, judge, fails.append)
+        if family == "direct":
+            return fails, judge.ratios, (fm, None)
+        y = FC.check_gated(case, family, fm, y_buf, elu, identity, block_h, valid_h, judge, fails.append,
+                           unstacked=None if unstacked is None else unstacked[(elu, identity)])
+        out = (fm, y)
+    return fails, judge.ratios, out
+
+
+@pytest.mark.parametrize("family", ["direct", "w2", "w4"])
+def test_fp32_restatement_of_the_forward_launches_stays_inside_the_derived_bound(family):
+    """tests/train_fp32.py linear_launch32 — the direct kernel as a sequential fp32 sum over (tap, channel), F(2x2) and F(4x4) through
+    their fp32 transforms, the fused gate with fast_exp32 — on classes (a), (b), (d) at the GPU test's layers and sizes: every assertion
+    of the GPU test holds, and the closest approach to the derived bounds is printed."""
+    worst = {}
+    for layer in FC.LAYERS[family]:
+        for hw in FC.SIZES[layer[3]]:
+            for case in FC.cases(layer, hw, classes="abd"):
+                fails, ratios, _ = _run_assertions(case, family, VARIANTS[:2])
+                assert not fails, fails
+                for fam, cls, _name, q in ratios:
+                    worst[(fam, cls)] = max(worst.get((fam, cls), 0.0), q)
+    print(f"forward restatement [{family}], worst err / bound:", {f"{k[0]} ({k[1]})": round(v, 3) for k, v in sorted(worst.items())})
+    assert max(worst.values()) <= 1.0
+
+
+def test_every_seeded_defect_of_the_forward_launch_breaks_an_assertion():
+    """The mutation catalogue: each defect built into the restatement must fail at least one assertion of the GPU test on at least one
+    of its cases (and the unmutated restatement none).  A defect that passes means the cases are too weak."""
+    flat = {"w2": [((32, 3, 3, 1), (9, 21), "a"), ((48, 20, 3, 1), (9, 21), "b")],
+            "w4": [((48, 40, 3, 1), (9, 21), "a"), ((48, 40, 3, 1), (12, 20), "b"), ((64, 24, 3, 1), (9, 21), "d")],
+            "direct": [((8, 16, 3, 1), (9, 21), "a"), ((64, 56, 1, 1), (9, 21), "b")]}
+    stacked = {"w2": [((16, 32, 3, 1), FC.GEOMETRIES[1])], "w4": [((32, 8, 3, 1), FC.GEOMETRIES[0])]}
+    runs = []                                                        # (family, case, block_h, valid_h, unstacked)
+    for family, rows in flat.items():
+        for layer, hw, cls in rows:
+            runs.append((family, next(FC.cases(layer + (None,), hw, classes=cls)), 0, 0, None))
+    for family, rows in stacked.items():
+        for layer, (H, W, bh, vh) in rows:
+            case = next(FC.cases(layer + (None,), (H, W), classes="a"))
+            plain = {}
+            for variant in VARIANTS:
+                fails, _, plain[variant] = _run_assertions(case, family, (variant,))
+                assert not fails, fails
+            runs.append((family, case, bh, vh, plain))
+    for family, case, bh, vh, plain in runs:
+        fails, _, _ = _run_assertions(case, family, VARIANTS, bh, vh, unstacked=plain)
+        assert not fails, ("the unmutated restatement", case.name, fails)
+    for mut in MUTATIONS:
+        caught = [case.name for family, case, bh, vh, plain in runs if _run_assertions(case, family, VARIANTS, bh, vh, mut=mut, unstacked=plain)[0]]
+        print(f"mutation {mut}: caught on {len(caught)} of {len(runs)} cases")
+        assert caught, f"no assertion of the forward tests sees the defect '{mut}'"
+    # block geometry taken at the input scale of a stride-2 layer: GatedConvFn's y against the launch with T.block_geometry(out rows)
+    layer, (H, W), nb, v = (32, 64, 3, 2), (24, 12), 3, (3, 4)
+    case = next(FC.cases(layer + (None,), (H, W), classes="a"))
+    sc, sh = FC.scale_shift32(case.L, False)
+    fm = linear_launch32(case.L, case.x, 2, "direct", True, sc, sh, 0, 0)[0][:-GUARD].reshape(case.oh * case.ow, -1)
+    a, _, s = gate32(fm, case.cout, True)
+    y = (((a * s).astype(f32) * sc[None]).astype(f32) + sh[None]).astype(f32)
+    want = y * T.valid_rows(len(y), case.ow, *T.block_geometry(case.oh, nb, *v))[:, None]
+    wrong = y * T.valid_rows(len(y), case.ow, *T.block_geometry(H, nb, *v))[:, None]
+    assert T.block_geometry(case.oh, nb, *v) == (4, 3) and not np.array_equal(want.view(np.uint32), wrong.view(np.uint32))
+
+
+def test_forward_bound_restates_the_dgrad_bound_and_the_bias_cases_are_exact():
+    """A 32 -> 16 layer with zero bias is the dgrad's virtual layer of a 32-channel layer: conv_forward_bound gives conv_dgrad_bound's
+    numbers.  Class (d): the float64 reference's pre-activations ARE the biases."""
+    rng = np.random.default_rng(12)
+    H, W = 9, 21
+    L = R64.tame_layer(32, 16, 3, 5)
+    L["bf"], L["bm"] = np.zeros(16, f32), np.zeros(16, f32)
+    x = rng.standard_normal((32, H, W)).astype(f32)
+    ref = R64.reference(L, x)
+    for which, val, A in (("f", ref.f, ref.Af), ("m", ref.m, ref.Am)):
+        wv = L["w" + which].astype(np.float64)
+        d_hwc, value = np.ascontiguousarray(x.transpose(1, 2, 0)), val.transpose(1, 2, 0)
+        b, cond = T.conv_forward_bound(L, x, ref, "direct", which)
+        assert np.array_equal(b.transpose(1, 2, 0), T.conv_dgrad_bound(d_hwc, wv, A.transpose(1, 2, 0), value, "direct")) and np.array_equal(cond, A)
+        for fam in ("w2", "w4"):
+            b, cond = T.conv_forward_bound(L, x, ref, fam, which)
+            b0, Aw = T.conv_dgrad_bound(d_hwc, wv, None, value, fam)
+            assert np.array_equal(b.transpose(1, 2, 0), b0) and np.array_equal(cond.transpose(1, 2, 0), Aw)
+    for layer in ((32, 3, 3, 1, None), (48, 40, 3, 1, None), (64, 32, 4, 2, None)):
+        case = next(FC.cases(layer, FC.SIZES[layer[3]][0], classes="d"))
+        r = case.ref()
+        assert np.array_equal(r.f, np.broadcast_to(case.L["bf"].astype(np.float64)[:, None, None], r.f.shape))
+        assert np.array_equal(r.m, np.broadcast_to(case.L["bm"].astype(np.float64)[:, None, None], r.m.shape))
+        assert {float(b) for b in case.L["bf"]} <= {float(f32(e)) for e in FC.F_EDGES} and (np.abs(case.L["bm"]) >= 88).any()
+        for fam in ("direct",) if layer[3] == 2 else ("w2", "w4"):
+            df, dm, cf, cm = case.bounds(fam)
+            assert np.array_equal(cf, np.abs(r.f)) and np.array_equal(cm, np.abs(r.m))         # no product in the condition terms either
 
 
 # ------------------------------------------------------------------------------------------ class (d)

@@ -1,7 +1,9 @@
 """NumPy fp32 restatements of the training kernels (read_amd/csrc/train.hip) in the kernels' own order of operations, without fused
 multiply-adds: the gate / BatchNorm chain (modes 0 / 1 / 2, bn_bwd_coeff, bn_stats in fp64, bn_finalize, bn_apply) and both
-weight-gradient kernels.  tests/test_train_accuracy_cpu.py holds them to the derived bounds of tests/train_ref64.py;
-tests/test_gpu_train_accuracy.py uses them, summing sequentially, as the yardstick R_seq."""
+weight-gradient kernels; and of the forward's linear launches on the three fp32 convolution kernels of read_amd/csrc/conv.hip with the
+Winograd kernels' fused gate (linear_launch32, which can also carry one seeded defect: MUTATIONS).  tests/test_train_accuracy_cpu.py
+holds them to the derived bounds of tests/train_ref64.py; tests/test_gpu_train_accuracy.py and tests/test_gpu_train_forward_accuracy.py
+use them, summing sequentially, as the yardstick R_seq."""
 import numpy as np
 
 from tests import train_ref64 as T
@@ -22,6 +24,129 @@ def gate32(fm, C, elu):
         da = np.where(f > 0, f32(1), a + f32(1)).astype(f32) if elu else np.ones_like(f)
         s = (1.0 / (f32(1) + fast_exp32(-m)).astype(np.float64)).astype(f32)
     return a, da, s
+
+
+# ------------------------------------------------------------------------------------------ the forward's linear launches
+def conv_direct32(x_chw, w, stride, drop=()):
+    """The convolution WITHOUT its bias as a sequential fp32 sum over (tap, channel): one rounded product and one rounded addition per
+    term — the direct kernel's arithmetic in one of the orders the MFMAs may take, and the yardstick R_seq.  drop: channels left out
+    (the mutation catalogue).  -> (Cout, outH, outW) float32."""
+    cout, cin, k, _ = w.shape
+    pad = (k - 1) // 2
+    H, W = x_chw.shape[1:]
+    oh, ow = T.out_hw(k, stride, H, W)
+    xp = np.zeros((cin, H + 2 * pad + k, W + 2 * pad + k), f32)
+    xp[:, pad:pad + H, pad:pad + W] = x_chw
+    acc = np.zeros((cout, oh, ow), f32)
+    for ky in range(k):
+        for kx in range(k):
+            win = xp[:, ky:ky + stride * oh:stride, kx:kx + stride * ow:stride]
+            for c in range(cin):
+                if c not in drop:
+                    acc = acc + w[:, c, ky, kx][:, None, None] * win[c][None]
+    return acc
+
+
+def _at4(a):
+    """The output transform of gated_conv_wino4_kernel along axis 0 (conv.hip: s1, d1, s2, d2, R[0] = acc + s1 + s2, ...)."""
+    s1, d1, s2, d2 = a[1] + a[2], a[1] - a[2], a[3] + a[4], a[3] - a[4]
+    return np.stack([(a[0] + s1) + s2, d1 + f32(2) * d2, s1 + f32(4) * s2, (d1 + f32(8) * d2) + a[5]]).astype(f32)
+
+
+def _at2(a):
+    """F(2x2): r0 = acc0 + acc1 + acc2, r1 = acc1 - acc2 - acc3."""
+    return np.stack([(a[0] + a[1]) + a[2], (a[1] - a[2]) - a[3]]).astype(f32)
+
+
+def _bt4(d):
+    """F(2x2) input transform along axis 0: one difference (or sum) per output."""
+    return np.stack([d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]]).astype(f32)
+
+
+def conv_wino32(x_chw, w, m, drop=()):
+    """The convolution WITHOUT its bias through F(m x m, 3 x 3), m = 2 / 4, every step in fp32: the filter transform of
+    tests/wino_ref.py (fp32) / tests/wino4_ref.py (double, rounded once, as the packers do), the input transform B^T d B in two fp32
+    passes, the channel sum sequentially, the output transform in the kernels' order of additions.  -> (Cout, H, W) float32."""
+    from tests import wino4_ref, wino_ref
+    cout, cin = w.shape[:2]
+    H, W = x_chw.shape[1:]
+    p = m + 2
+    ty, tx = -(-H // m), -(-W // m)
+    xp = np.zeros((cin, m * ty + 2, m * tx + 2), f32)
+    xp[:, 1:H + 1, 1:W + 1] = x_chw
+    iy = (m * np.arange(ty))[:, None] + np.arange(p)[None]
+    ix = (m * np.arange(tx))[:, None] + np.arange(p)[None]
+    d = xp[:, iy[:, None, :, None], ix[None, :, None, :]].transpose(3, 4, 0, 1, 2)                # (p, p, cin, ty, tx)
+    bt, at = (_bt4, _at2) if m == 2 else (_bt6, _at4)
+    Uw = (wino_ref.filter_transform if m == 2 else wino4_ref.filter_transform4)(w)                # (p, p, cin, cout)
+    V = bt(bt(d).transpose(1, 0, 2, 3, 4)).transpose(1, 0, 2, 3, 4)
+    M = np.zeros((p, p, cout, ty, tx), f32)
+    for c in range(cin):
+        if c not in drop:
+            M = M + Uw[:, :, c, :, None, None] * V[:, :, c, None]
+    Y = at(at(M).transpose(1, 0, 2, 3, 4)).transpose(1, 0, 2, 3, 4)                               # (m, m, cout, ty, tx)
+    return np.ascontiguousarray(Y.transpose(2, 3, 0, 4, 1).reshape(cout, m * ty, m * tx)[:, :H, :W])
+
+
+MUTATIONS = ("bm_added_to_f", "bias_at_next_channel", "scale_of_channel_mod_32", "separator_gt", "separator_on_tile_row", "m_stored_at_cp",
+             "column_past_width", "elu_after_sigmoid", "exp_without_minus_one", "dropped_chunk")
+SENTINEL = f32(7.0)
+GUARD = 64
+
+
+def linear_launch32(L, x_chw, stride, family, elu, sc, sh, block_h, valid_h, mut=None):
+    """One linear launch of read_gated_conv_forward as the training forward issues it, restated in fp32 with the stores into flat
+    buffers that end in a guard band of GUARD sentinels: -> (fm buffer, y buffer or None).  family "direct" (no fused gate) / "w2" /
+    "w4"; sc, sh (Cout,) float32: the scale and shift of the params block.  mut: one of MUTATIONS — the defects the GPU test's
+    assertions must see (tests/test_train_accuracy_cpu.py)."""
+    wf, wm = L["wf"], L["wm"]
+    cout, cin, k, _ = wf.shape
+    cp32 = (cout + 31) // 32 * 32
+    pad = lambda a: np.concatenate([np.asarray(a, f32), np.zeros(cp32 + 1 - cout, f32)])             # noqa: E731  (one past the block: zero)
+    bf, bm, scp, shp = pad(L["bf"]), pad(L["bm"]), pad(sc), pad(sh)
+    drop = tuple(range(32, 48)) if mut == "dropped_chunk" and cin == 48 else ()
+    conv = (lambda w: conv_direct32(x_chw, w, stride, drop)) if family == "direct" else (lambda w: conv_wino32(x_chw, w, 2 if family == "w2" else 4, drop))
+    Yf, Ym = conv(wf), conv(wm)
+    _, oh, ow = Yf.shape
+    c = np.arange(cout)
+    bi = np.where((c >= cout // 32 * 32) & (cout % 32 != 0), c + 1, c) if mut == "bias_at_next_channel" else c
+    f = (Yf + (bm if mut == "bm_added_to_f" else bf)[bi][:, None, None]).astype(f32)
+    mm = (Ym + bm[bi][:, None, None]).astype(f32)
+    n = oh * ow * 2 * cout
+    fm_buf = np.full(n + GUARD, SENTINEL, f32)
+    pix = (np.arange(oh)[:, None] * ow + np.arange(ow)[None]) * (2 * cout)                           # (oh, ow)
+    fm_buf[pix[None] + c[:, None, None]] = f
+    fm_buf[pix[None] + ((cout + 7) // 8 * 8 if mut == "m_stored_at_cp" else cout) + c[:, None, None]] = mm
+    tile = {"direct": 4, "w2": 2, "w4": 4}[family]
+    past = mut == "column_past_width" and ow % tile != 0
+
+    def store_past(buf, idx, vals):                                   # the partial tile's next column lands on the next row's first pixel
+        ok = idx < buf.size
+        buf[idx[ok]] = vals[ok]
+
+    if past:
+        store_past(fm_buf, (pix[:, -1] + 2 * cout)[None] + c[:, None], f[:, :, -1])
+    if family == "direct":
+        return fm_buf, None
+    with np.errstate(over="ignore", invalid="ignore"):
+        e = fast_exp32(np.minimum(f, f32(0)))
+        act = (lambda v: np.where(v > 0, v, (fast_exp32(np.minimum(v, f32(0))) - f32(1)).astype(f32))) if elu else (lambda v: v)
+        a = np.where(f > 0, f, e if mut == "exp_without_minus_one" else (e - f32(1)).astype(f32)).astype(f32) if elu else f
+        s = (1.0 / (f32(1) + fast_exp32(-mm)).astype(np.float64)).astype(f32)
+        g = act((f * s).astype(f32)).astype(f32) if mut == "elu_after_sigmoid" else (a * s).astype(f32)
+    ci = c % 32 if mut == "scale_of_channel_mod_32" else c
+    v = ((g * scp[ci][:, None, None]).astype(f32) + shp[ci][:, None, None]).astype(f32)
+    rows = np.arange(oh)
+    if block_h > 0:
+        r = rows // tile * tile if mut == "separator_on_tile_row" else rows
+        sep = (r % block_h > valid_h) if mut == "separator_gt" else (r % block_h >= valid_h)
+        v[:, sep] = 0.0
+    y_buf = np.full(oh * ow * cout + GUARD, SENTINEL, f32)
+    ypix = (rows[:, None] * ow + np.arange(ow)[None]) * cout
+    y_buf[ypix[None] + c[:, None, None]] = v
+    if past:
+        store_past(y_buf, (ypix[:, -1] + cout)[None] + c[:, None], v[:, :, -1])
+    return fm_buf, y_buf
 
 
 def kernel_sum32(vals, blocks, rows):

@@ -2,7 +2,8 @@
 error bounds with the roundings they count, two fp32 yardsticks, and the inputs on which these kernels can go wrong.  Plain NumPy and
 torch-float64 on the CPU; nothing from read_amd or oracle/ takes part in the arithmetic.  u, EPS, TINY, `gated_bound` and the
 generators come from tests/conv_ref64.py.  tests/test_train_accuracy_cpu.py runs NumPy fp32 restatements of the kernels through the
-measure, tests/test_gpu_train_accuracy.py the kernels themselves.
+measure, tests/test_gpu_train_accuracy.py the kernels themselves.  The forward's linear launches on the fp32 convolution kernels
+(`conv_forward_bound`, derivation in front of it) are run by tests/test_gpu_train_forward_accuracy.py.
 
 LAYOUT.  As the device sees it: pixel-major, fm (P, 2 C) = [f | m], dy / y / g (P, C), d[f|m] (P, 2 Cp) with Cp = C padded to 8; a
 stacked batch is `block_h` rows per item of which the first `valid_h` are valid, the rest separator rows (`valid_rows`).
@@ -770,6 +771,49 @@ def conv_dgrad_bound(d_hwc, wv, cond, value, family):
         return SECOND_ORDER * U * (k * k * c2 + 1) * cond + TINY
     Aw, Ain = wino_forward_terms(np.ascontiguousarray(d_hwc.astype(np.float64).transpose(2, 0, 1)), wv, 2 if family == "w2" else 4)
     return SECOND_ORDER * U * ((c2 + 11) * Aw + 4 * Ain + np.abs(value.transpose(2, 0, 1))).transpose(1, 2, 0) + TINY, Aw.transpose(1, 2, 0)
+
+
+# ------------------------------------------------------------------------------------------ the forward's linear launches
+# GatedConvFn.forward -> _linear_conv: the layer's OWN filters through the same three fp32 kernels (read_amd/csrc/conv.hip), linear = 1.
+# The count is conv_dgrad_bound's with Cin in the place of 2 Cp, and the bias, which the dgrad's virtual layer does not have:
+#   direct (the workgroup-tiled kernel): k k Cin rounded products added in some order by the MFMAs (and, with WK > 1, over the waves'
+#     LDS partials, conv.hip:358-364), then ONE addition f += bf + pf (conv.hip:369-370; pf = 0 without an addend, so bf + pf is exact):
+#         |got - f| <= u (k k Cin + 1) A_f,      A_f = sum |x| |w| + |b|     (every partial sum and the biased value are bounded by A_f)
+#     A 1x1 layer whose Cout is no multiple of 32 (64 -> 56) also reports family 0 but runs on the fp32 pixel-lane kernel
+#     (conv_uses_px; gated_conv_px_kernel, linear epilogue at conv.hip:3999): Cin fused multiply-adds and the bias: the same count.
+#   F(2x2) (gated_conv_wino_kernel): the filter transform 4 u (pack_wino_body: two fp32 passes of two roundings), the input transform 2 u
+#     against A_in (one difference per pass), the product 1, the channel sum Cin, the output transform 4 u (conv.hip:953-954 and 965-966:
+#     r0 = acc0 + acc1 + acc2, Y = R0 + R1 + R2: two additions per pass), then f = Y + bf (conv.hip:981, 984): one rounding of the
+#     biased value, u |f|;
+#   F(4x4) (gated_conv_wino4_kernel<false, 1>): the filter transform 4 u (evaluated in double and rounded once: generous), the input
+#     transform 4 u against A_in (bt6: two roundings per pass), the product 1, the channel sum Cin (v_mfma_f32_16x16x4_f32: four
+#     products per instruction, Cin / 4 instructions per frequency), the output transform 6 u (conv.hip:1894-1908: R[0] = acc + s1 + s2,
+#     three additions on the longest path per pass), then Y[p][px] + bb (conv.hip:1922): u |f|;
+#         |got - f| <= u ((Cin + 1 + 4 + 6) A_w + 4 A_in + |f|),       A_w, A_in of wino_forward_terms, the bias in neither.
+#   With b = 0 these ARE conv_dgrad_bound's numbers: its `+ 1` (direct) and its |dx| term (Winograd) are the epilogue's addition, which
+#   the dgrad performs with a zero bias.  Where every weight of a row is zero (class (d) of the forward tests) A_w = A_in = 0 and the
+#   accumulators are +0: the stored value is the exact sum 0 + b — b itself, except that (+0) + (-0) is +0.
+# The measure takes cond = A_f (direct) or A_w + |b| (Winograd), as tests/test_gpu_conv_accuracy.py does for the split-operand kernels.
+FORWARD_FAMILY = {"direct": 0, "w2": 2, "w4": 4}                   # read_conv_kernel_family of the three kernels
+
+
+def conv_forward_bound(L, x_chw, ref, family, which):
+    """|got - f| (which = "f") or |got - m| <= bound, elementwise, for the linear launch of the layer L on x: -> (bound, cond), each
+    (Cout, outH, outW).  ref = conv_ref64.reference(L, x, stride); family "direct" / "w2" / "w4"."""
+    w, b = np.asarray(L["w" + which], np.float64), np.abs(np.asarray(L["b" + which], np.float64))[:, None, None]
+    cin, k = w.shape[1], w.shape[2]
+    A, val = (ref.Af, ref.f) if which == "f" else (ref.Am, ref.m)
+    if family == "direct":
+        return SECOND_ORDER * U * (k * k * cin + 1) * A + TINY, A
+    Aw, Ain = wino_forward_terms(np.asarray(x_chw, np.float64), w, 2 if family == "w2" else 4)
+    return SECOND_ORDER * U * ((cin + 11) * Aw + 4 * Ain + np.abs(val)) + TINY, Aw + b
+
+
+def block_geometry(out_h, nb, v_num, v_den):
+    """(block_h, valid_h) of a stacked batch of nb items at a layer whose OUTPUT has out_h rows (read_amd/train.py, GatedConvFn.forward:
+    `bh = Ho // nb if nb > 1 else 0`, `vh = bh * v_num // v_den`) — the rule gate_forward_kernel's separator_row applies to output rows."""
+    bh = out_h // nb if nb > 1 else 0
+    return bh, bh * v_num // v_den
 
 
 def poly_pseudo_weights(w, k):
