@@ -154,7 +154,7 @@ int read_splat_forward_cells(const float *xyz, void *cells, int64_t n, const flo
                              int levels, int32_t *const *idx_levels, float *const *depth_levels,
                              void *workspace, size_t workspace_bytes, void *stream);
 
-/* Scene editing (csrc/splat.hip, splat_objects_kernel).  A scene = a static part (label 0) plus objects k = 0..count-1, each with its
+/* Scene editing (csrc/splat.hip, range_splat_kernel<PinholeCam>).  A scene = a static part (label 0) plus objects k = 0..count-1, each with its
  * own matrix M_k = M_0 @ P_k (P_k maps the object's points, in the cloud's coordinates, to their new place; computed on the host).
  * Every visible point is projected with its label's matrix by the arithmetic of every pass; per pixel the minimum (depth, ORIGINAL
  * id) wins, empty pixels are (0, 0.0f), levels are formed as in read_splat_forward.  Index images carry the original ids.
@@ -183,7 +183,7 @@ int read_splat_forward_objects(const float *xyz_static, const int32_t *ids_stati
                                int32_t *const *idx_levels, float *const *depth_levels, void *workspace, size_t workspace_bytes,
                                void *stream);
 
-/* Panorama camera: cylindrical projection (csrc/splat.hip, splat_pano_kernel; the definition is tests/pano_model.py).  cam_host =
+/* Panorama camera: cylindrical projection (csrc/splat.hip, range_splat_kernel<PanoCam>; the definition is tests/pano_model.py).  cam_host =
  * 16 floats on the host (camera.pano_camera): [0..11] three rows applied to (x, y, z, 1) giving c0 = x_c, c1 = P[1,1] y_c and
  * c3 = -z_c (the forward distance), [12] kx = 2 / hfov_rad, [13] ky = P[1,2], [14] za = P[2,2], [15] zb = P[2,3].  Per point, in
  * fp32 without fused operations: rho = sqrt(c0 c0 + c3 c3), nx = atan2(c0, c3) kx, ny = c1 / rho - ky, nz = (zb - za rho) / rho,
@@ -234,7 +234,7 @@ int read_splat_forward_pano_instances(const float *xyz, const int32_t *ids, int6
                                       void *workspace, size_t workspace_bytes, void *stream);
 
 /* Lens cameras: a pinhole with Brown-Conrady distortion (model 0) and a Kannala-Brandt fisheye (model 1) (csrc/splat.hip,
- * splat_lens_kernel; the definition is tests/lens_model.py).  cam_host = 32 floats on the host (camera.lens_camera): [0..11] three
+ * range_splat_kernel<LensCam>; the definition is tests/lens_model.py).  cam_host = 32 floats on the host (camera.lens_camera): [0..11] three
  * UNSCALED rows applied to (x, y, z, 1) giving c0 = x_c, c1 = y_c and c3 = -z_c (the forward distance); [12] sx = P[0,0],
  * [13] ox = P[0,2], [14] sy = P[1,1], [15] oy = P[1,2]; [16] za = P[2,2], [17] zb = P[2,3]; [18] the limit; [19] the model, 0.0f or
  * 1.0f; [20..24] the coefficients (model 0: OpenCV's k1, k2, p1, p2, k3; model 1: OpenCV's fisheye k1..k4); [25..31] zero.  Per

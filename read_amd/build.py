@@ -49,7 +49,7 @@ def build(force: bool = False, verbose: bool = False, debug: bool = False) -> st
     FLAGS = globals()["FLAGS"] + (["-DREAD_DEBUG_KNOBS"] if debug else []) + [f"-D{d}" for d in os.environ.get("READ_EXTRA_DEFINES", "").split()]
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(ROOT, "include", "read_hip.h"), os.path.join(ROOT, "include", "read_hip_debug.h"), os.path.join(CSRC, "common.h"),
-               os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "project.h")]
+               os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "project.h"), os.path.join(CSRC, "ranges.h")]
     SOURCES = globals()["SOURCES"] + (DEBUG_SOURCES if debug else [])
     hipcc = _hipcc()
     jobs = []

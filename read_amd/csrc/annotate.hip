@@ -5,7 +5,7 @@
 //   annotate_pixels_kernel   one lane per pixel: id -> object through the labels / the foreign ranges, then the first instance of that
 //                            object whose matrix puts the point on this pixel at this depth; 16 B per pixel; the visible statistics go
 //                            out once per wave and instance, not once per pixel
-//   annotate_extents_kernel  the shape of splat_objects_kernel: <= 32 ranges per launch, four points per thread; a workgroup reduces
+//   annotate_extents_kernel  the shape of range_splat_kernel<PinholeCam>: <= 32 ranges per launch, four points per thread; a workgroup reduces
 //                            count, box and nearest depth and issues one set of atomics; 12 B per drawn point
 //
 // The match is exact because project_one here is the frame's device function on the same matrix bits.  Compiled with

@@ -10,6 +10,7 @@
 
 #include "internal.h"
 #include "project.h"
+#include "ranges.h"
 
 namespace readhip {
 namespace {
@@ -17,7 +18,6 @@ namespace {
 constexpr int LIDAR_MAX_BEAMS = 128;
 constexpr int LIDAR_MAX_WINDOW = 4;
 constexpr int LIDAR_TILE = 256;                      // cells per workgroup of the three image launches: one per lane
-constexpr int RANGE_MAX = 32;                        // ranges per launch of the pass, as splat_pano_kernel's OBJ_MAX
 constexpr unsigned long long EMPTY = 0xFFFFFFFFFFFFFFFFull;
 
 struct BeamTable {
@@ -26,13 +26,6 @@ struct BeamTable {
 struct LidarCam {
     float m[16];
 };
-struct RangeBatch {
-    float m[RANGE_MAX][16];
-    long long first[RANGE_MAX], last[RANGE_MAX];     // range k = points [first, last)
-    int block0[RANGE_MAX + 1];                       // first workgroup of range k; block0[count] = the grid
-    int count;
-};
-
 // The beam of elevation angle phi in the ascending table e[0..B) (LDS): lo = the number of entries below phi by a branch-free
 // binary search, then the two neighbours lo - 1 and lo, the tie to the lower.  The model defines the beam by a linear scan for
 // the first smallest d_b = |phi - e[b]|; fp32 subtraction is monotone, so d_b does not rise up to lo - 1 and does not fall from lo
@@ -77,31 +70,26 @@ __device__ __forceinline__ int lidar_project_one(float x, float y, float z, cons
     return d <= c[15] ? b * W + col : -1;
 }
 
-// splat_pano_kernel under LiDAR cameras: rb.m[k] holds range k's 16 camera floats, workgroup -> range from the host prefix.  The
-// whole cloud (or a labelled cloud's static part) is one range; ids == NULL: the id is the point's index.  The beam table comes
-// in the kernel arguments and is staged into LDS once per workgroup: the search indexes it per lane.
+// range_splat_kernel's shape under LiDAR cameras: ob.m[k] holds range k's 16 camera floats, workgroup -> range from the host prefix
+// (ranges.h).  The whole cloud (or a labelled cloud's static part) is one range; ids == NULL: the id is the point's index.  The
+// beam table comes in the kernel arguments and is staged into LDS once per workgroup: the search indexes it per lane.
 __global__ __launch_bounds__(256) void lidar_pass_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
-                                                         RangeBatch rb, BeamTable bt, int B, int W,
+                                                         ObjBatch ob, BeamTable bt, int B, int W,
                                                          unsigned long long *__restrict__ keys)
 {
     __shared__ float e[LIDAR_MAX_BEAMS];
     if (threadIdx.x < LIDAR_MAX_BEAMS) e[threadIdx.x] = bt.e[threadIdx.x];
     __syncthreads();
-    const int blk = (int)blockIdx.x;
-    int j = 0;
-    for (int k = 1; k < rb.count; ++k)
-        if (blk >= rb.block0[k]) j = k;
-    const long long i = rb.first[j] + (long long)(blk - rb.block0[j]) * 256 + threadIdx.x;
-    if (i >= rb.last[j]) return;
+    const int b = (int)blockIdx.x, j = range_of_block(ob, b);
+    const long long i = range_point(ob, j, b);
+    if (i >= ob.last[j]) return;
     float r;
-    const int cell = lidar_project_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], rb.m[j], e, B, W, r);
+    const int cell = lidar_project_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], e, B, W, r);
     if (cell < 0) return;
     const unsigned id = ids ? (unsigned)ids[i] : (unsigned)i;
     const unsigned long long key = ((unsigned long long)__float_as_uint(r) << 32) | id;
     unsigned long long *k = keys + cell;
-    // relaxed agent-scope load and min, as the rasteriser's passes: keys only decrease, so "not below what I see" is final
-    if (key < __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        __hip_atomic_fetch_min(k, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
 }
 
 // The per-point function alone (read_lidar_project_points).
@@ -284,34 +272,11 @@ int check_sensor(const char *who, const float *cam_host, const float *elev_host,
 int check_lidar_instances(const char *who, const read_splat_instances *inst)
 {
     if (const int rc = check_instances(who, inst); rc != READ_OK) return rc;
-    for (int i = 0; i < inst->count; ++i) {
-        if ((inst->visible && !inst->visible[i]) || inst->npts[i] == 0) continue;          // hidden or empty: not launched
+    return for_each_range(nullptr, inst, [&](int i, int64_t, int64_t, const float *M) -> int {
         for (int k = 0; k < 16; ++k)
-            READ_CHECK_ARG(std::isfinite(inst->M[16 * (size_t)i + k]), "%s: inst->M of instance %d: a camera entry is not finite", who, i);
-    }
-    return READ_OK;
-}
-
-int pass_flush(RangeBatch &rb, int &blocks, const float *xyz, const int32_t *ids, const BeamTable &bt, int B, int W,
-               unsigned long long *keys, hipStream_t stream)
-{
-    if (rb.count == 0) return READ_OK;
-    rb.block0[rb.count] = blocks;
-    hipLaunchKernelGGL(lidar_pass_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, rb, bt, B, W, keys);
-    READ_CHECK_LAUNCH();
-    rb.count = 0;
-    blocks = 0;
-    return READ_OK;
-}
-
-void pass_add(RangeBatch &rb, int &blocks, int64_t first, int64_t last, const float *M)
-{
-    const int k = rb.count++;
-    memcpy(rb.m[k], M, sizeof(rb.m[k]));
-    rb.first[k] = first;
-    rb.last[k] = last;
-    rb.block0[k] = blocks;
-    blocks += (int)ceil_div64(last - first, 256);
+            READ_CHECK_ARG(std::isfinite(M[k]), "%s: inst->M of instance %d: a camera entry is not finite", who, i);
+        return READ_OK;
+    });
 }
 
 }  // namespace
@@ -358,23 +323,14 @@ extern "C" int read_lidar_sweep(const read_lidar_args *a, void *stream)
     hipStream_t s = as_stream(stream);
     BeamTable bt;
     for (int b = 0; b < LIDAR_MAX_BEAMS; ++b) bt.e[b] = a->elev_host[b < a->B ? b : a->B - 1];
-    // the pass: the static part, then every visible, non-empty instance, RANGE_MAX ranges per launch
-    RangeBatch rb;
-    memset(&rb, 0, sizeof(rb));
-    int blocks = 0;
-    if (a->n > 0) {
-        pass_add(rb, blocks, 0, a->n, a->cam_host);
-        if ((rc = pass_flush(rb, blocks, a->xyz, a->ids, bt, a->B, a->W, L.keys, s)) != READ_OK) return rc;
-    }
-    if (a->inst) {
-        const read_splat_instances *in = a->inst;
-        for (int k = 0; k < in->count; ++k) {
-            if ((in->visible && !in->visible[k]) || in->npts[k] == 0) continue;
-            pass_add(rb, blocks, in->first[k], in->first[k] + in->npts[k], in->M + 16 * (size_t)k);
-            if (rb.count == RANGE_MAX && (rc = pass_flush(rb, blocks, in->xyz, in->ids, bt, a->B, a->W, L.keys, s)) != READ_OK) return rc;
-        }
-        if ((rc = pass_flush(rb, blocks, in->xyz, in->ids, bt, a->B, a->W, L.keys, s)) != READ_OK) return rc;
-    }
+    // the pass: the static part, then every visible, non-empty instance, OBJ_MAX ranges per launch
+    rc = launch_ranges(a->xyz, a->ids, a->n, a->cam_host, nullptr, a->inst,
+                       [&](const ObjBatch &ob, int blocks, const float *xyz, const int32_t *ids) -> int {
+                           hipLaunchKernelGGL(lidar_pass_kernel, dim3((unsigned)blocks), dim3(256), 0, s, xyz, ids, ob, bt, a->B, a->W, L.keys);
+                           READ_CHECK_LAUNCH();
+                           return READ_OK;
+                       });
+    if (rc != READ_OK) return rc;
     hipLaunchKernelGGL(lidar_filter_kernel, dim3((unsigned)L.tiles), dim3(LIDAR_TILE), 0, s, L.keys, a->B, a->W, a->wb, a->wc, a->wrap ? 1 : 0,
                        a->scale, a->slack, L.fkeys, a->range, a->idx, L.counts);
     READ_CHECK_LAUNCH();

@@ -1,6 +1,9 @@
-// The pinhole projection of one point, shared by every translation unit that must land a point in the same pixel as the
-// rasteriser does (splat.hip, select.hip).  Bit-exact fp32: include it only from files compiled with -ffp-contract=off.
+// The projection of one point under every camera model, shared by every translation unit that must land a point in the same pixel
+// as the rasteriser does (splat.hip, select.hip, annotate.hip, lidar.hip), and the camera types the rasteriser's range kernels are
+// written over.  Bit-exact fp32: include it only from files compiled with -ffp-contract=off.
 #pragma once
+#include <cmath>
+
 #include "common.h"
 
 namespace readhip {
@@ -48,6 +51,23 @@ __device__ __forceinline__ void div3_ieee(float a0, float a1, float a2, float b,
     }
 }
 
+// point_render.cu:141-147: normalised device coordinates to the pixel (or -1), the depth and the integer column and row.  `keep` is
+// what the camera itself asks of the point (a lens's limit; true where it asks nothing).
+__device__ __forceinline__ int ndc_pixel(float nx, float ny, float nz, bool keep, int W, int H, float &depth, int &xx_out, int &yy_out)
+{
+    // NaN compares false everywhere: written so that NaN is rejected (canonical semantics).
+    const bool inside = (nx >= -1.0f) & (nx <= 1.0f) & (ny >= -1.0f) & (ny <= 1.0f) &
+                        (nz >= -1.0f) & (nz <= 1.0f);
+    const float u = ((float)W * (nx + 1.0f)) * 0.5f;
+    const float v = ((float)H * (1.0f - ny)) * 0.5f;
+    depth = (nz + 1.0f) * 0.5f;
+    const int xx = (int)u, yy = (int)v;
+    const bool ok = keep & inside & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H);
+    xx_out = xx;
+    yy_out = yy;
+    return ok ? yy * W + xx : -1;
+}
+
 // point_render.cu:135-147 for one point and one camera; returns the pixel or -1.
 __device__ __forceinline__ int project_one(float x, float y, float z, const float *M, int W, int H,
                                            float &depth, int &xx_out, int &yy_out)
@@ -58,17 +78,7 @@ __device__ __forceinline__ int project_one(float x, float y, float z, const floa
     const float c3 = M[12] * x + M[13] * y + M[14] * z + M[15] * 1.0f;
     float nx, ny, nz;
     div3_ieee(c0, c1, c2, c3, nx, ny, nz);
-    // NaN compares false everywhere: written so that NaN is rejected (canonical semantics).
-    const bool inside = (nx >= -1.0f) & (nx <= 1.0f) & (ny >= -1.0f) & (ny <= 1.0f) &
-                        (nz >= -1.0f) & (nz <= 1.0f);
-    const float u = ((float)W * (nx + 1.0f)) * 0.5f;
-    const float v = ((float)H * (1.0f - ny)) * 0.5f;
-    depth = (nz + 1.0f) * 0.5f;
-    const int xx = (int)u, yy = (int)v;
-    const bool ok = inside & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H);
-    xx_out = xx;
-    yy_out = yy;
-    return ok ? yy * W + xx : -1;
+    return ndc_pixel(nx, ny, nz, true, W, H, depth, xx_out, yy_out);
 }
 
 // The arctangent of the panorama, lens and LiDAR cameras (splat.hip, lidar.hip); tests/pano_model.py::atan2_model is the definition.
@@ -95,5 +105,151 @@ __device__ __forceinline__ float pano_atan2(float a, float b)
     if (b < 0.0f) r = 3.14159265358979323846f - r;
     return copysignf(r, a);
 }
+
+// ---- panorama camera: cylindrical projection --------------------------------------------------------------------------------
+// Only the per-point projection differs from the pinhole; keys, z-test, resolve, gather and UNet are the frame's as ever.  The
+// camera is 16 floats formed on the host (camera.pano_camera): c[0..11] three rows applied to (x, y, z, 1) — c0 = x_c,
+// c1 = P[1,1] y_c, c3 = -z_c —, c[12] = kx = 2 / hfov_rad, c[13] = ky = P[1,2], c[14] = za = P[2,2], c[15] = zb = P[2,3].
+// tests/pano_model.py is the definition; this restates it: fp32, no contraction, sums left to right, IEEE division, correctly
+// rounded square root.  No chunk culling here: a cylinder does not map a box to the hull of its corners.
+// One point under one panorama camera; returns the pixel or -1.  rho = 0, NaN and Inf fall out through `inside`.
+__device__ __forceinline__ int project_pano_one(float x, float y, float z, const float *c, int W, int H,
+                                                float &depth, int &xx_out, int &yy_out)
+{
+    const float c0 = c[0] * x + c[1] * y + c[2] * z + c[3] * 1.0f;
+    const float c1 = c[4] * x + c[5] * y + c[6] * z + c[7] * 1.0f;
+    const float c3 = c[8] * x + c[9] * y + c[10] * z + c[11] * 1.0f;
+    const float rho = __builtin_sqrtf(c0 * c0 + c3 * c3);
+    const float theta = pano_atan2(c0, c3);
+    const float nx = theta * c[12];
+    const float ny = c1 / rho - c[13];
+    const float nz = (c[15] - c[14] * rho) / rho;
+    return ndc_pixel(nx, ny, nz, true, W, H, depth, xx_out, yy_out);
+}
+
+// ---- lens cameras: distorted pinhole and fisheye ------------------------------------------------------------------------------
+// Again only the per-point projection differs.  The camera is 32 floats formed on the host (camera.lens_camera): c[0..11] three
+// UNSCALED rows applied to (x, y, z, 1) — c0 = x_c, c1 = y_c, c3 = -z_c — and twenty scalars, the same for every range of a frame,
+// which travel once per launch as LensScalars: sx, ox, sy, oy = P[0,0], P[0,2], P[1,1], P[1,2]; za, zb = P[2,2], P[2,3]; the
+// limit; the model (0 = Brown-Conrady pinhole, 1 = Kannala-Brandt fisheye); k[5] in OpenCV's order; seven zeros.
+// tests/lens_model.py is the definition; this restates it: fp32, no contraction, sums left to right, IEEE division, correctly
+// rounded square root, Horner with separate multiply and add.  The model is uniform over a launch, so the branch is scalar.
+struct LensScalars {
+    float s[20];
+};
+
+// One point under one lens camera (rows r[12], scalars ls); returns the pixel or -1.  A point past the limit, NaN and Inf fall out
+// through `keep` and `inside`; the fisheye's axis point (rho = 0) is kept and lands on the principal point.
+__device__ __forceinline__ int project_lens_one(float x, float y, float z, const float *r, const LensScalars &ls, int W, int H,
+                                                float &depth, int &xx_out, int &yy_out)
+{
+    const float c0 = r[0] * x + r[1] * y + r[2] * z + r[3] * 1.0f;
+    const float c1 = r[4] * x + r[5] * y + r[6] * z + r[7] * 1.0f;
+    const float c3 = r[8] * x + r[9] * y + r[10] * z + r[11] * 1.0f;
+    const float sx = ls.s[0], ox = ls.s[1], sy = ls.s[2], oy = ls.s[3], za = ls.s[4], zb = ls.s[5], limit = ls.s[6];
+    float a2, b2, d;
+    bool keep;
+    if (ls.s[7] == 0.0f) {
+        const float k1 = ls.s[8], k2 = ls.s[9], p1 = ls.s[10], p2 = ls.s[11], k3 = ls.s[12];
+        const float a = c0 / c3, b = c1 / c3;
+        const float r2 = a * a + b * b;
+        keep = (c3 > 0.0f) & (r2 <= limit);
+        const float rad = ((k3 * r2 + k2) * r2 + k1) * r2 + 1.0f;
+        const float xo = a, yo = -b;                             // OpenCV's axes: its y points down
+        const float xy2 = 2.0f * (xo * yo);
+        const float tx = p1 * xy2 + p2 * (r2 + 2.0f * (xo * xo));
+        const float ty = p1 * (r2 + 2.0f * (yo * yo)) + p2 * xy2;
+        a2 = xo * rad + tx;
+        b2 = -(yo * rad + ty);
+        d = c3;
+    } else {
+        const float k1 = ls.s[8], k2 = ls.s[9], k3 = ls.s[10], k4 = ls.s[11];
+        const float rho = __builtin_sqrtf(c0 * c0 + c1 * c1);
+        const float theta = pano_atan2(rho, c3);
+        keep = theta <= limit;
+        const float t2 = theta * theta;
+        const float theta_d = theta * ((((k4 * t2 + k3) * t2 + k2) * t2 + k1) * t2 + 1.0f);
+        const float q = rho == 0.0f ? 0.0f : theta_d / rho;
+        a2 = q * c0;
+        b2 = q * c1;
+        d = __builtin_sqrtf(c0 * c0 + c1 * c1 + c3 * c3);
+    }
+    const float nx = sx * a2 - ox;
+    const float ny = sy * b2 - oy;
+    const float nz = (zb - za * d) / d;
+    return ndc_pixel(nx, ny, nz, keep, W, H, depth, xx_out, yy_out);
+}
+
+// ---- the camera seam ----------------------------------------------------------------------------------------------------------
+// One type per camera model; everything above the per-point projection (range kernel, seed kernel, project-points kernel, the
+// host's checks and frames) is written once over it.  A camera carries what is uniform over a launch and says, for the host,
+//   whole_cloud   it reads the cloud itself: no cell blob, and ids may be NULL (a point's id is its index)
+//   host_name     what the C ABI calls its 16 or 32 host floats
+//   from_host     the launch's camera from those floats
+//   frame_fault   what is wrong with the frame's camera floats, or NULL;  range_fault: the same for one range's 16 floats
+struct PinholeCam {
+    static constexpr bool whole_cloud = false;
+    static constexpr const char *host_name = "M_host";
+    static PinholeCam from_host(const float *) { return {}; }
+    static const char *frame_fault(const float *) { return nullptr; }
+    __device__ __forceinline__ int project(float x, float y, float z, const float *M, int W, int H, float &depth, int &xx, int &yy) const
+    {
+        return project_one(x, y, z, M, W, H, depth, xx, yy);
+    }
+};
+
+struct PanoCam {
+    static constexpr bool whole_cloud = true;
+    static constexpr const char *host_name = "cam_host";
+    static PanoCam from_host(const float *) { return {}; }
+    // 16 finite floats, kx = 2 / hfov_rad with hfov in (0, 2 pi]
+    static const char *frame_fault(const float *c)
+    {
+        for (int i = 0; i < 16; ++i)
+            if (!std::isfinite(c[i])) return "a camera entry is not finite";
+        if (!(c[12] >= (float)(1.0 / 3.14159265358979323846))) return "kx = 2 / hfov_rad must be >= 1 / pi (a field of at most 360 degrees)";
+        return nullptr;
+    }
+    static const char *range_fault(const float *c) { return frame_fault(c); }
+    __device__ __forceinline__ int project(float x, float y, float z, const float *c, int W, int H, float &depth, int &xx, int &yy) const
+    {
+        return project_pano_one(x, y, z, c, W, H, depth, xx, yy);
+    }
+};
+
+struct LensCam {
+    LensScalars ls;
+    static constexpr bool whole_cloud = true;
+    static constexpr const char *host_name = "cam_host";
+    // cam_host is 32 floats: its first 16 are a range's entry (12 rows, 4 ignored), its last 20 the frame's scalars
+    static LensCam from_host(const float *c)
+    {
+        LensCam cam;
+        memcpy(cam.ls.s, c + 12, sizeof(cam.ls.s));
+        return cam;
+    }
+    // every entry but the limit finite, the model 0 or 1, the limit not NaN, not negative and, for the fisheye, not above the fp32
+    // pi its arctangent ends at (model 0 may carry +inf)
+    static const char *frame_fault(const float *c)
+    {
+        for (int i = 0; i < 32; ++i)
+            if (i != 18 && !std::isfinite(c[i])) return "a camera entry is not finite";
+        if (c[19] != 0.0f && c[19] != 1.0f) return "the model must be 0 (distorted pinhole) or 1 (fisheye)";
+        if (!(c[18] >= 0.0f)) return "the limit is negative or NaN";
+        if (c[19] == 1.0f && c[18] > 3.14159265358979323846f) return "the limit of a fisheye must not exceed pi";
+        return nullptr;
+    }
+    // the 12 rows of a range (the 4 floats after them are ignored)
+    static const char *range_fault(const float *m)
+    {
+        for (int i = 0; i < 12; ++i)
+            if (!std::isfinite(m[i])) return "a camera row entry is not finite";
+        return nullptr;
+    }
+    __device__ __forceinline__ int project(float x, float y, float z, const float *r, int W, int H, float &depth, int &xx, int &yy) const
+    {
+        return project_lens_one(x, y, z, r, ls, W, H, depth, xx, yy);
+    }
+};
 
 }  // namespace readhip

@@ -32,6 +32,7 @@
 #include <atomic>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -41,6 +42,7 @@
 #pragma clang fp contract(off)
 
 #include "project.h"
+#include "ranges.h"
 
 using namespace readhip;
 
@@ -68,15 +70,6 @@ struct Cam1 {
 //              Exact: seeds are real points of this cloud, bounds are upper bounds of the final depths.
 enum { MODE_AGENT = 1, MODE_HIZ = 7 };
 
-// relaxed agent-scope load = global_load_dwordx2 sc1: served by L2, never by the CU's stale L1
-__device__ __forceinline__ unsigned long long peek_key_agent(const unsigned long long *k)
-{
-    return __hip_atomic_load(k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void fold_key_agent(unsigned long long *k, unsigned long long key)
-{
-    __hip_atomic_fetch_min(k, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // Far bounds are stored as 16 bits: the upper half (bfloat16, truncated = rounded DOWN) of e = fl(1 - d_max).  Depth
 // is d = 1 - O(znear / z), so e keeps 8 mantissa bits of the DISTANCE (0.4 %) where a half-precision d would resolve
 // only ~5 m at 30 m.  Reject iff fl(1 - d) < bound: rounding is monotonic, so fl(1 - d) < fl(1 - d_max) implies
@@ -1163,95 +1156,38 @@ __global__ __launch_bounds__(256) void splat_project_gl_kernel(const float *__re
 // A scene = a static part (label 0) and objects k >= 1, each a contiguous range of one compacted array of points with the points'
 // ORIGINAL ids and its own matrix M_k = M_0 @ P_k (computed on the host).  After the static part's passes, every visible object's
 // points are projected with project_one under M_k and folded into the frame's level-0 key image as (depth bits << 32 | original
-// id) — the same keys, the same min; the resolve then forms the levels as for any frame.  Up to OBJ_MAX ranges per launch, their
-// matrices in the kernel arguments; workgroup b works on the range whose first workgroup (a host prefix of block counts) is the
-// last one <= b — a scalar scan of <= OBJ_MAX entries per workgroup, no search per point.
-constexpr int OBJ_MAX = 32;
-struct ObjBatch {
-    float m[OBJ_MAX][16];
-    long long first[OBJ_MAX], last[OBJ_MAX];        // range k = points [first, last) of the compacted arrays
-    int block0[OBJ_MAX + 1];                        // first workgroup of range k; block0[count] = the grid
-    int count;
-};
-
-__global__ __launch_bounds__(256) void splat_objects_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
-                                                            ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys)
+// id) — the same keys, the same min; the resolve then forms the levels as for any frame.  ObjBatch (ranges.h) carries the ranges
+// of a launch.  The panorama and the lens cameras (project.h) draw the whole cloud, or a labelled cloud's static part, the same
+// way, as one more range: ob.m[k] holds range k's 16 camera floats, and ids == NULL says that a point's id is its index.
+//
+// A camera's per-launch scalars are a kernel argument only where it has some: Arg is empty for the pinhole and the panorama and
+// {LensCam} for the lens (with_cam_arg), so the arguments after it keep the offsets they have without it.
+template <class Cam, class... Arg>
+__global__ __launch_bounds__(256) void range_splat_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids, ObjBatch ob,
+                                                          Arg... arg, int W, int H, unsigned long long *__restrict__ keys)
 {
-    const int b = (int)blockIdx.x;
-    int j = 0;
-    for (int k = 1; k < ob.count; ++k)
-        if (b >= ob.block0[k]) j = k;
-    const long long i = ob.first[j] + (long long)(b - ob.block0[j]) * 256 + threadIdx.x;
+    const Cam cam{arg...};
+    const int b = (int)blockIdx.x, j = range_of_block(ob, b);
+    const long long i = range_point(ob, j, b);
     if (i >= ob.last[j]) return;
     float d;
     int xx, yy;
-    const int pix = project_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], W, H, d, xx, yy);
+    const int pix = cam.project(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], W, H, d, xx, yy);
     if (pix < 0) return;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)ids[i];
-    unsigned long long *k = keys + pix;
-    if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
-}
-
-// ---- panorama camera: cylindrical projection (read_splat_forward_pano) ------------------------------------------------------
-// Only the per-point projection differs from the pinhole; keys, z-test, resolve, gather and UNet are the frame's as ever.  The
-// camera is 16 floats formed on the host (camera.pano_camera): c[0..11] three rows applied to (x, y, z, 1) — c0 = x_c,
-// c1 = P[1,1] y_c, c3 = -z_c —, c[12] = kx = 2 / hfov_rad, c[13] = ky = P[1,2], c[14] = za = P[2,2], c[15] = zb = P[2,3].
-// tests/pano_model.py is the definition; this restates it: fp32, no contraction, sums left to right, IEEE division, correctly
-// rounded square root.  No chunk culling here: a cylinder does not map a box to the hull of its corners.
-// The model's arctangent, pano_atan2, lives in project.h (lidar.hip shares it).
-
-// One point under one panorama camera; returns the pixel or -1.  rho = 0, NaN and Inf fall out through `inside`.
-__device__ __forceinline__ int project_pano_one(float x, float y, float z, const float *c, int W, int H,
-                                                float &depth, int &xx_out, int &yy_out)
-{
-    const float c0 = c[0] * x + c[1] * y + c[2] * z + c[3] * 1.0f;
-    const float c1 = c[4] * x + c[5] * y + c[6] * z + c[7] * 1.0f;
-    const float c3 = c[8] * x + c[9] * y + c[10] * z + c[11] * 1.0f;
-    const float rho = __builtin_sqrtf(c0 * c0 + c3 * c3);
-    const float theta = pano_atan2(c0, c3);
-    const float nx = theta * c[12];
-    const float ny = c1 / rho - c[13];
-    const float nz = (c[15] - c[14] * rho) / rho;
-    // from here on: the tail of project_one
-    const bool inside = (nx >= -1.0f) & (nx <= 1.0f) & (ny >= -1.0f) & (ny <= 1.0f) &
-                        (nz >= -1.0f) & (nz <= 1.0f);
-    const float u = ((float)W * (nx + 1.0f)) * 0.5f;
-    const float v = ((float)H * (1.0f - ny)) * 0.5f;
-    depth = (nz + 1.0f) * 0.5f;
-    const int xx = (int)u, yy = (int)v;
-    const bool ok = inside & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H);
-    xx_out = xx;
-    yy_out = yy;
-    return ok ? yy * W + xx : -1;
-}
-
-// splat_objects_kernel under panorama cameras: ob.m[k] holds range k's 16 camera floats.  The whole cloud (or a labelled cloud's
-// static part) is one range; ids == NULL: the id is the point's index.
-__global__ __launch_bounds__(256) void splat_pano_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
-                                                         ObjBatch ob, int W, int H, unsigned long long *__restrict__ keys)
-{
-    const int b = (int)blockIdx.x;
-    int j = 0;
-    for (int k = 1; k < ob.count; ++k)
-        if (b >= ob.block0[k]) j = k;
-    const long long i = ob.first[j] + (long long)(b - ob.block0[j]) * 256 + threadIdx.x;
-    if (i >= ob.last[j]) return;
-    float d;
-    int xx, yy;
-    const int pix = project_pano_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], W, H, d, xx, yy);
-    if (pix < 0) return;
-    const unsigned id = ids ? (unsigned)ids[i] : (unsigned)i;
+    const unsigned id = !Cam::whole_cloud || ids ? (unsigned)ids[i] : (unsigned)i;
     const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | id;
     unsigned long long *k = keys + pix;
     if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
 }
 
-// Warm start of an unlabelled panorama frame: splat_seed_kernel under the panorama camera.  Last frame's winners (the resolve's
+// Warm start of an unlabelled whole-cloud frame: splat_seed_kernel under the frame's camera.  Last frame's winners (the resolve's
 // keep = 1 image) are folded in first, so the big pass's early-out works from its first wave; seeds are real points: exact.
-__global__ __launch_bounds__(256) void splat_pano_seed_kernel(const float *__restrict__ xyz, long long n, Cam1 cam,
-                                                              int W, int H, unsigned long long *__restrict__ keys,
-                                                              const SplatHeader *hdr, const int *__restrict__ prev_idx)
+template <class Cam, class... Arg>
+__global__ __launch_bounds__(256) void range_seed_kernel(const float *__restrict__ xyz, long long n, Cam1 rows, Arg... arg, int W, int H,
+                                                         unsigned long long *__restrict__ keys, const SplatHeader *hdr,
+                                                         const int *__restrict__ prev_idx)
 {
+    const Cam cam{arg...};
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= W * H || !prev_idx) return;
     if (!(hdr->valid == 1 && hdr->W == W && hdr->H == H)) return;
@@ -1259,108 +1195,33 @@ __global__ __launch_bounds__(256) void splat_pano_seed_kernel(const float *__res
     if (id < 0 || id >= n) return;
     float d;
     int xx, yy;
-    const int pix = project_pano_one(xyz[3ll * id], xyz[3ll * id + 1], xyz[3ll * id + 2], cam.m, W, H, d, xx, yy);
+    const int pix = cam.project(xyz[3ll * id], xyz[3ll * id + 1], xyz[3ll * id + 2], rows.m, W, H, d, xx, yy);
     if (pix >= 0) fold_key_agent(keys + pix, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id);
 }
 
-// ---- lens cameras: distorted pinhole and fisheye (read_splat_forward_lens) ---------------------------------------------------
-// Again only the per-point projection differs.  The camera is 32 floats formed on the host (camera.lens_camera): c[0..11] three
-// UNSCALED rows applied to (x, y, z, 1) — c0 = x_c, c1 = y_c, c3 = -z_c — and twenty scalars, the same for every range of a frame,
-// which travel once per launch as LensScalars: sx, ox, sy, oy = P[0,0], P[0,2], P[1,1], P[1,2]; za, zb = P[2,2], P[2,3]; the
-// limit; the model (0 = Brown-Conrady pinhole, 1 = Kannala-Brandt fisheye); k[5] in OpenCV's order; seven zeros.
-// tests/lens_model.py is the definition; this restates it: fp32, no contraction, sums left to right, IEEE division, correctly
-// rounded square root, Horner with separate multiply and add.  The model is uniform over a launch, so the branch is scalar.
-struct LensScalars {
-    float s[20];
-};
-
-// One point under one lens camera (rows r[12], scalars ls); returns the pixel or -1.  A point past the limit, NaN and Inf fall out
-// through `keep` and `inside`; the fisheye's axis point (rho = 0) is kept and lands on the principal point.
-__device__ __forceinline__ int project_lens_one(float x, float y, float z, const float *r, const LensScalars &ls, int W, int H,
-                                                float &depth, int &xx_out, int &yy_out)
+// One thread per point: the pixel it projects to (or -1) and its depth — the camera's projection as every pass uses it, without
+// the z-test.
+template <class Cam, class... Arg>
+__global__ __launch_bounds__(256) void project_points_kernel(const float *__restrict__ xyz, long long n, Cam1 rows, Arg... arg, int W,
+                                                             int H, int32_t *__restrict__ pixel, float *__restrict__ depth)
 {
-    const float c0 = r[0] * x + r[1] * y + r[2] * z + r[3] * 1.0f;
-    const float c1 = r[4] * x + r[5] * y + r[6] * z + r[7] * 1.0f;
-    const float c3 = r[8] * x + r[9] * y + r[10] * z + r[11] * 1.0f;
-    const float sx = ls.s[0], ox = ls.s[1], sy = ls.s[2], oy = ls.s[3], za = ls.s[4], zb = ls.s[5], limit = ls.s[6];
-    float a2, b2, d;
-    bool keep;
-    if (ls.s[7] == 0.0f) {
-        const float k1 = ls.s[8], k2 = ls.s[9], p1 = ls.s[10], p2 = ls.s[11], k3 = ls.s[12];
-        const float a = c0 / c3, b = c1 / c3;
-        const float r2 = a * a + b * b;
-        keep = (c3 > 0.0f) & (r2 <= limit);
-        const float rad = ((k3 * r2 + k2) * r2 + k1) * r2 + 1.0f;
-        const float xo = a, yo = -b;                             // OpenCV's axes: its y points down
-        const float xy2 = 2.0f * (xo * yo);
-        const float tx = p1 * xy2 + p2 * (r2 + 2.0f * (xo * xo));
-        const float ty = p1 * (r2 + 2.0f * (yo * yo)) + p2 * xy2;
-        a2 = xo * rad + tx;
-        b2 = -(yo * rad + ty);
-        d = c3;
-    } else {
-        const float k1 = ls.s[8], k2 = ls.s[9], k3 = ls.s[10], k4 = ls.s[11];
-        const float rho = __builtin_sqrtf(c0 * c0 + c1 * c1);
-        const float theta = pano_atan2(rho, c3);
-        keep = theta <= limit;
-        const float t2 = theta * theta;
-        const float theta_d = theta * ((((k4 * t2 + k3) * t2 + k2) * t2 + k1) * t2 + 1.0f);
-        const float q = rho == 0.0f ? 0.0f : theta_d / rho;
-        a2 = q * c0;
-        b2 = q * c1;
-        d = __builtin_sqrtf(c0 * c0 + c1 * c1 + c3 * c3);
+    const Cam cam{arg...};
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        float d;
+        int xx, yy;
+        const int pix = cam.project(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], rows.m, W, H, d, xx, yy);
+        pixel[i] = pix;
+        if (depth) depth[i] = d;
     }
-    const float nx = sx * a2 - ox;
-    const float ny = sy * b2 - oy;
-    const float nz = (zb - za * d) / d;
-    // from here on: the tail of project_one
-    const bool inside = (nx >= -1.0f) & (nx <= 1.0f) & (ny >= -1.0f) & (ny <= 1.0f) &
-                        (nz >= -1.0f) & (nz <= 1.0f);
-    const float u = ((float)W * (nx + 1.0f)) * 0.5f;
-    const float v = ((float)H * (1.0f - ny)) * 0.5f;
-    depth = (nz + 1.0f) * 0.5f;
-    const int xx = (int)u, yy = (int)v;
-    const bool ok = keep & inside & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H);
-    xx_out = xx;
-    yy_out = yy;
-    return ok ? yy * W + xx : -1;
 }
 
-// splat_pano_kernel under lens cameras: ob.m[k] holds range k's 12 rows (its other 4 floats are ignored), ls the frame's scalars.
-__global__ __launch_bounds__(256) void splat_lens_kernel(const float *__restrict__ xyz, const int32_t *__restrict__ ids,
-                                                         ObjBatch ob, LensScalars ls, int W, int H,
-                                                         unsigned long long *__restrict__ keys)
+// f() for a camera without per-launch scalars, f(cam) for one with: the trailing template arguments and the middle kernel
+// arguments of the three kernels above.
+template <class Cam, class F>
+void with_cam_arg(const Cam &cam, F &&f)
 {
-    const int b = (int)blockIdx.x;
-    int j = 0;
-    for (int k = 1; k < ob.count; ++k)
-        if (b >= ob.block0[k]) j = k;
-    const long long i = ob.first[j] + (long long)(b - ob.block0[j]) * 256 + threadIdx.x;
-    if (i >= ob.last[j]) return;
-    float d;
-    int xx, yy;
-    const int pix = project_lens_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], ob.m[j], ls, W, H, d, xx, yy);
-    if (pix < 0) return;
-    const unsigned id = ids ? (unsigned)ids[i] : (unsigned)i;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | id;
-    unsigned long long *k = keys + pix;
-    if (key < peek_key_agent(k)) fold_key_agent(k, key);         // keys only decrease: "not below what I see" is final
-}
-
-// Warm start of an unlabelled lens frame: splat_pano_seed_kernel under the lens camera (cam.m[0..11] = the rows).
-__global__ __launch_bounds__(256) void splat_lens_seed_kernel(const float *__restrict__ xyz, long long n, Cam1 cam, LensScalars ls,
-                                                              int W, int H, unsigned long long *__restrict__ keys,
-                                                              const SplatHeader *hdr, const int *__restrict__ prev_idx)
-{
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= W * H || !prev_idx) return;
-    if (!(hdr->valid == 1 && hdr->W == W && hdr->H == H)) return;
-    const int id = prev_idx[p];
-    if (id < 0 || id >= n) return;
-    float d;
-    int xx, yy;
-    const int pix = project_lens_one(xyz[3ll * id], xyz[3ll * id + 1], xyz[3ll * id + 2], cam.m, ls, W, H, d, xx, yy);
-    if (pix >= 0) fold_key_agent(keys + pix, ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id);
+    if constexpr (std::is_empty_v<Cam>) f();
+    else f(cam);
 }
 
 struct ResolveOut {
@@ -1770,65 +1631,27 @@ StripInfo make_strips(int W)
 
 // ---- scene editing: the object launches of a frame ------------------------------------------------------------------------
 struct ObjectsDraw {
-    const float *xyz;                 // device: every object's points, object after object
-    const int32_t *ids;               // device: their original ids
-    const int64_t *first, *npts;      // host, count each: range k = [first[k], first[k] + npts[k]) (ranges may repeat and overlap)
-    const float *M;                   // host, count x 16
-    const unsigned char *visible;     // host, count, or NULL (all visible)
-    int count;
+    const read_splat_objects *objs;   // the ranges as the caller wrote them: a checked partition, a checked list, or neither
+    const read_splat_instances *inst;
     const float *xyz0;                // the static part as one more range (route without cells); n0 = 0: none
-    const int32_t *ids0;
+    const int32_t *ids0;              // NULL under a whole-cloud camera: the static range's ids are its indices
     int64_t n0;
     const float *M0;
 };
 
-int objects_flush(ObjBatch &ob, int &blocks, const float *xyz, const int32_t *ids, int W, int H, unsigned long long *keys,
-                  hipStream_t stream, bool pano = false, const LensScalars *lens = nullptr)
+// Every visible, non-empty range of `od` into the key image under `cam`, whose camera floats od.M0 and the ranges' M carry.
+template <class Cam>
+int objects_launch(const ObjectsDraw &od, const Cam &cam, int W, int H, unsigned long long *keys, hipStream_t stream)
 {
-    if (ob.count == 0) return READ_OK;
-    ob.block0[ob.count] = blocks;
-    if (lens)
-        hipLaunchKernelGGL(splat_lens_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, *lens, W, H, keys);
-    else if (pano)
-        hipLaunchKernelGGL(splat_pano_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys);
-    else
-        hipLaunchKernelGGL(splat_objects_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, xyz, ids, ob, W, H, keys);
-    READ_CHECK_LAUNCH();
-    ob.count = 0;
-    blocks = 0;
-    return READ_OK;
-}
-
-void objects_add(ObjBatch &ob, int &blocks, int64_t first, int64_t last, const float *M)
-{
-    const int k = ob.count++;
-    memcpy(ob.m[k], M, sizeof(ob.m[k]));
-    ob.first[k] = first;
-    ob.last[k] = last;
-    ob.block0[k] = blocks;
-    blocks += (int)ceil_div64(last - first, 256);
-}
-
-// Every visible, non-empty range of `od` into the key image: stream-ordered, OBJ_MAX ranges per launch, no synchronisation.
-// pano: the matrices are panorama cameras (splat_pano_kernel), and ids0 may be NULL (the static range's ids are its indices).
-// lens: the matrices are the rows of lens cameras with the frame's scalars *lens (splat_lens_kernel); ids0 as for pano.
-int objects_launch(const ObjectsDraw &od, int W, int H, unsigned long long *keys, hipStream_t stream, bool pano = false,
-                   const LensScalars *lens = nullptr)
-{
-    ObjBatch ob;
-    memset(&ob, 0, sizeof(ob));
-    int blocks = 0, rc;
-    if (od.n0 > 0) {
-        objects_add(ob, blocks, 0, od.n0, od.M0);
-        if ((rc = objects_flush(ob, blocks, od.xyz0, od.ids0, W, H, keys, stream, pano, lens)) != READ_OK) return rc;
-    }
-    for (int k = 0; k < od.count; ++k) {
-        const int64_t first = od.first[k], last = first + od.npts[k];
-        if ((od.visible && !od.visible[k]) || last == first) continue;                      // hidden or empty: not launched
-        objects_add(ob, blocks, first, last, od.M + 16 * (size_t)k);
-        if (ob.count == OBJ_MAX && (rc = objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano, lens)) != READ_OK) return rc;
-    }
-    return objects_flush(ob, blocks, od.xyz, od.ids, W, H, keys, stream, pano, lens);
+    return launch_ranges(od.xyz0, od.ids0, od.n0, od.M0, od.objs, od.inst,
+                         [&](const ObjBatch &ob, int blocks, const float *xyz, const int32_t *ids) -> int {
+                             with_cam_arg(cam, [&](auto... arg) {
+                                 hipLaunchKernelGGL(HIP_KERNEL_NAME(range_splat_kernel<Cam, decltype(arg)...>), dim3((unsigned)blocks),
+                                                    dim3(256), 0, stream, xyz, ids, ob, arg..., W, H, keys);
+                             });
+                             READ_CHECK_LAUNCH();
+                             return READ_OK;
+                         });
 }
 
 // ---- per-kernel durations of the LAST cell-path frame (read_tuning_set("splat_prof", 1) + read_splat_profile_last): HIP events
@@ -1924,7 +1747,7 @@ int cells_frame(const CellCloud &cc, const float *M_host, int W, int H, int leve
     // ---- scene editing: the objects join the key image before the resolve (profile slot 3 includes them).  The bound image
     // stays the static part's: an upper bound of the static depths, so also of the merged ones
     if (objs) {
-        const int rc = objects_launch(*objs, W, H, ws.keys, stream);
+        const int rc = objects_launch(*objs, PinholeCam{}, W, H, ws.keys, stream);
         if (rc != READ_OK) return rc;
     }
     // ---- resolve; with an announced next camera the same launch prepares the next frame's set
@@ -2789,8 +2612,8 @@ extern "C" int read_splat_forward_cells(const float *xyz, void *cells, int64_t n
 }
 
 // ---- scene editing: the edited frame ------------------------------------------------------------------------------------------
-// One frame behind four symbols: a static part plus a list of point ranges, each with its matrix and visible flag.  The symbols
-// differ in the camera (pinhole / panorama) and in how the caller writes the ranges down (a partition or the list itself).
+// One frame behind six symbols: a static part plus a list of point ranges, each with its matrix and visible flag.  The symbols
+// differ in the camera (pinhole / panorama / lens) and in how the caller writes the ranges down (a partition or the list itself).
 // Every check precedes the first launch.
 namespace {
 // what a read_splat_objects must be: `count` consecutive ranges that tile its n points
@@ -2827,116 +2650,38 @@ int readhip::check_instances(const char *who, const read_splat_instances *inst)
 }
 
 namespace {
-ObjectsDraw instances_draw(const read_splat_instances *inst)
-{
-    ObjectsDraw od{};
-    od.xyz = inst->xyz;
-    od.ids = inst->ids;
-    od.first = inst->first;
-    od.npts = inst->npts;
-    od.M = inst->M;
-    od.visible = inst->visible;
-    od.count = inst->count;
-    return od;
-}
-
-// a checked partition (NULL: no ranges) as the list: first / npts live in `ranges` for the length of the call
-ObjectsDraw partition_draw(const read_splat_objects *objs, std::vector<int64_t> &ranges)
-{
-    ObjectsDraw od{};
-    if (!objs) return od;
-    ranges.resize(2 * (size_t)objs->count);
-    int64_t *first = ranges.data(), *npts = first + objs->count;
-    for (int k = 0; k < objs->count; ++k) {
-        first[k] = objs->begin[k];
-        npts[k] = objs->begin[k + 1] - objs->begin[k];
-    }
-    od.xyz = objs->xyz;
-    od.ids = objs->ids;
-    od.first = first;
-    od.npts = npts;
-    od.M = objs->M;
-    od.visible = objs->visible;
-    od.count = objs->count;
-    return od;
-}
-
-// the host-side conditions on a panorama camera: 16 finite floats, kx = 2 / hfov_rad with hfov in (0, 2 pi]
-const char *pano_cam_fault(const float *c)
-{
-    for (int i = 0; i < 16; ++i)
-        if (!std::isfinite(c[i])) return "a camera entry is not finite";
-    if (!(c[12] >= (float)(1.0 / 3.14159265358979323846))) return "kx = 2 / hfov_rad must be >= 1 / pi (a field of at most 360 degrees)";
-    return nullptr;
-}
-
-// the frame's camera and the camera of every range that will be launched (a partition's or a list's: one of the two, or neither)
-int check_pano_cameras(const char *who, const float *cam_host, const read_splat_objects *objs, const read_splat_instances *inst)
-{
-    const char *fault = pano_cam_fault(cam_host);
-    READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
-    const int count = objs ? objs->count : inst ? inst->count : 0;
-    const float *M = objs ? objs->M : inst ? inst->M : nullptr;
-    const unsigned char *visible = objs ? objs->visible : inst ? inst->visible : nullptr;
-    for (int k = 0; k < count; ++k) {
-        if ((visible && !visible[k]) || (objs ? objs->begin[k + 1] == objs->begin[k] : inst->npts[k] == 0)) continue;
-        fault = pano_cam_fault(M + 16 * (size_t)k);
-        READ_CHECK_ARG(!fault, "%s: %s %d: %s", who, objs ? "objs->M of object" : "inst->M of instance", k, fault);
-    }
-    return READ_OK;
-}
-
-// the host-side conditions on a lens camera (camera.lens_camera, 32 floats): every entry but the limit finite, the model 0 or 1,
-// the limit not NaN, not negative and, for the fisheye, not above the fp32 pi its arctangent ends at (model 0 may carry +inf)
-const char *lens_cam_fault(const float *c)
-{
-    for (int i = 0; i < 32; ++i)
-        if (i != 18 && !std::isfinite(c[i])) return "a camera entry is not finite";
-    if (c[19] != 0.0f && c[19] != 1.0f) return "the model must be 0 (distorted pinhole) or 1 (fisheye)";
-    if (!(c[18] >= 0.0f)) return "the limit is negative or NaN";
-    if (c[19] == 1.0f && c[18] > 3.14159265358979323846f) return "the limit of a fisheye must not exceed pi";
-    return nullptr;
-}
-
-// the frame's lens camera and the 12 rows of every range that will be launched (the 4 floats after them are ignored)
-int check_lens_cameras(const char *who, const float *cam_host, const read_splat_objects *objs, const read_splat_instances *inst)
-{
-    const char *fault = lens_cam_fault(cam_host);
-    READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
-    const int count = objs ? objs->count : inst ? inst->count : 0;
-    const float *M = objs ? objs->M : inst ? inst->M : nullptr;
-    const unsigned char *visible = objs ? objs->visible : inst ? inst->visible : nullptr;
-    for (int k = 0; k < count; ++k) {
-        if ((visible && !visible[k]) || (objs ? objs->begin[k + 1] == objs->begin[k] : inst->npts[k] == 0)) continue;
-        for (int i = 0; i < 12; ++i)
-            READ_CHECK_ARG(std::isfinite(M[16 * (size_t)k + i]), "%s: %s %d: a camera row entry is not finite", who,
-                           objs ? "objs->M of object" : "inst->M of instance", k);
-    }
-    return READ_OK;
-}
-
 // What the six entry points ask of their arguments, in one order: outputs, the static part, the ranges (objs or inst, whichever
-// the symbol takes; both NULL: none), the pyramid, the cameras of a panorama or a lens, alignment, workspace size.  cam_host !=
-// NULL: a panorama frame (lens: a lens frame), whose static part may come without ids (its indices are its ids) and has no cell blob.
+// the symbol takes; both NULL: none), the pyramid, the frame's camera and the camera of every range that will be launched,
+// alignment, workspace size.  A whole-cloud camera's static part may come without ids (its indices are its ids) and has no cell
+// blob; the pinhole's matrices are not looked into.
+template <class Cam>
 int check_frame_args(const char *who, const float *cam_host, const float *xyz, const int32_t *ids, const void *cells, int64_t n,
                      const read_splat_objects *objs, const read_splat_instances *inst, int W, int H, int levels,
-                     int32_t *const *idx_levels, float *const *depth_levels, const void *ws, size_t ws_bytes, bool lens = false)
+                     int32_t *const *idx_levels, float *const *depth_levels, const void *ws, size_t ws_bytes)
 {
-    const bool pano = cam_host != nullptr;
+    constexpr bool whole = Cam::whole_cloud;
     int rc = READ_OK;
     READ_CHECK_ARG(idx_levels || depth_levels, "%s: no outputs requested", who);
-    READ_CHECK_ARG(n >= 0 && n <= 0xFFFFFFFEll, "%s: %s out of range", who, pano ? "n" : "n_static");
-    READ_CHECK_ARG(n == 0 || (xyz && (ids || pano)), "%s: null pointer (%s)", who, pano ? "xyz" : "static xyz or ids");
+    READ_CHECK_ARG(n >= 0 && n <= 0xFFFFFFFEll, "%s: %s out of range", who, whole ? "n" : "n_static");
+    READ_CHECK_ARG(n == 0 || (xyz && (ids || whole)), "%s: null pointer (%s)", who, whole ? "xyz" : "static xyz or ids");
     if (objs && (rc = check_partition(who, objs)) != READ_OK) return rc;
     if (inst && (rc = check_instances(who, inst)) != READ_OK) return rc;
     READ_CHECK_ARG(levels >= 1 && levels <= READ_MAX_LEVELS, "%s: levels must be 1..%d", who, READ_MAX_LEVELS);
     READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad size (%d,%d)", who, W, H);
     const int mask = (1 << (levels - 1)) - 1;
     READ_CHECK_ARG(((W | H) & mask) == 0, "%s: W and H (%d,%d) must be multiples of 2^(levels-1) = %d", who, W, H, mask + 1);
-    if (pano && (rc = lens ? check_lens_cameras(who, cam_host, objs, inst) : check_pano_cameras(who, cam_host, objs, inst)) != READ_OK)
-        return rc;
+    if constexpr (whole) {
+        const char *fault = Cam::frame_fault(cam_host);
+        READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
+        rc = for_each_range(objs, inst, [&](int k, int64_t, int64_t, const float *M) -> int {
+            fault = Cam::range_fault(M);
+            READ_CHECK_ARG(!fault, "%s: %s %d: %s", who, objs ? "objs->M of object" : "inst->M of instance", k, fault);
+            return READ_OK;
+        });
+        if (rc != READ_OK) return rc;
+    }
     READ_CHECK_ARG((uintptr_t)ws % 256 == 0 && (uintptr_t)cells % 256 == 0, "%s: workspace %smust be 256-byte aligned", who,
-                   pano ? "" : "and cells ");
+                   whole ? "" : "and cells ");
     if (ws_bytes < read_splat_workspace_bytes(1, W, H)) {
         set_error("%s: workspace %zu < %zu bytes", who, ws_bytes, read_splat_workspace_bytes(1, W, H));
         return READ_ENOMEM;
@@ -2944,57 +2689,62 @@ int check_frame_args(const char *who, const float *cam_host, const float *xyz, c
     return READ_OK;
 }
 
-// The pinhole frame once the arguments are checked: od carries the ranges; the route of the static part is chosen here.
-int objects_frame(ObjectsDraw od, const float *xyz_static, const int32_t *ids_static, void *cells, int64_t n_static,
-                  const float *M_host, int W, int H, int levels, int32_t *const *idx_levels, float *const *depth_levels, void *ws,
-                  hipStream_t s)
+// The pinhole frame once the arguments are checked: od carries the ranges and the static part; its route is chosen here.
+int objects_frame(ObjectsDraw od, void *cells, int W, int H, int levels, int32_t *const *idx_levels, float *const *depth_levels,
+                  void *ws, hipStream_t s)
 {
     const WsLayout L = ws_layout(ws, 1, W, H);
-    od.xyz0 = xyz_static;
-    od.ids0 = ids_static;
-    od.M0 = M_host;
     // the cell path for the static part (its blob from read_splat_cells_build_ids), the objects after its pass B
-    if (cells && g_splat_cells && g_splat_mode == MODE_HIZ && n_static >= (1 << 20) && (W & 15) == 0)
-        return cells_frame(cell_cloud(cells, n_static), M_host, W, H, levels, idx_levels, depth_levels, L, s, 0, &od);
-    // Otherwise the static part is one more range of splat_objects_kernel with M_0 and its explicit ids (never the plain pass,
+    if (cells && g_splat_cells && g_splat_mode == MODE_HIZ && od.n0 >= (1 << 20) && (W & 15) == 0) {
+        const int64_t n_static = od.n0;
+        od.n0 = 0;
+        return cells_frame(cell_cloud(cells, n_static), od.M0, W, H, levels, idx_levels, depth_levels, L, s, 0, &od);
+    }
+    // Otherwise the static part is one more range of range_splat_kernel with M_0 and its explicit ids (never the plain pass,
     // whose keys and warm start carry implicit ids), and the resolve keeps no seeds
     if (const int rc = ws_forget_prediction(ws, s); rc != READ_OK) return rc;
-    od.n0 = n_static;
-    const int rc = objects_launch(od, W, H, L.keys, s);
+    const int rc = objects_launch(od, PinholeCam{}, W, H, L.keys, s);
     if (rc != READ_OK) return rc;
     return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, 0, s);
 }
 
-// The panorama frame once the arguments are checked: one range launch for the static part, the ranges of od, the resolve.
-// Seeds carry implicit ids: only a cloud drawn whole, with its indices as ids, keeps and uses them.
-// lens: cam_host is a lens camera of 32 floats — its first 16 are the static range's ObjBatch entry (12 rows, 4 ignored), its
-// last 20 the frame's LensScalars; the frame is otherwise the panorama's, launch for launch.
-int pano_frame(ObjectsDraw od, const float *xyz, const int32_t *ids, int64_t n, const float *cam_host, bool whole, int W, int H,
-               int levels, int32_t *const *idx_levels, float *const *depth_levels, void *ws, hipStream_t s, bool lens = false)
+// The frame of a camera that reads the whole cloud, once the arguments are checked: one range launch for the static part (od.M0:
+// the first 16 of the camera's host floats), the ranges of od, the resolve.  Seeds carry implicit ids: only a cloud drawn whole,
+// with its indices as ids, keeps and uses them.
+template <class Cam>
+int whole_cloud_frame(const ObjectsDraw &od, const Cam &cam, int W, int H, int levels, int32_t *const *idx_levels,
+                      float *const *depth_levels, void *ws, hipStream_t s)
 {
     const WsLayout L = ws_layout(ws, 1, W, H);
-    const bool seeds = whole && !ids && n > 0 && g_splat_mode == MODE_HIZ;
-    od.xyz0 = xyz;
-    od.ids0 = ids;
-    od.n0 = n;
-    od.M0 = cam_host;
-    LensScalars ls;
-    if (lens) memcpy(ls.s, cam_host + 12, sizeof(ls.s));
+    const bool seeds = !od.objs && !od.inst && !od.ids0 && od.n0 > 0 && g_splat_mode == MODE_HIZ;
     if (const int rc = ws_forget_prediction(ws, s); rc != READ_OK) return rc;
     if (seeds && g_splat_seeds) {
-        Cam1 cam;
-        memcpy(cam.m, od.M0, sizeof(cam.m));
-        if (lens)
-            hipLaunchKernelGGL(splat_lens_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, ls, W, H,
-                               L.keys, (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
-        else
-            hipLaunchKernelGGL(splat_pano_seed_kernel, dim3(ceil_div(W * H, 256)), dim3(256), 0, s, od.xyz0, (long long)od.n0, cam, W, H, L.keys,
-                               (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
+        Cam1 rows;
+        memcpy(rows.m, od.M0, sizeof(rows.m));
+        with_cam_arg(cam, [&](auto... arg) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(range_seed_kernel<Cam, decltype(arg)...>), dim3(ceil_div(W * H, 256)), dim3(256), 0, s,
+                               od.xyz0, (long long)od.n0, rows, arg..., W, H, L.keys, (const SplatHeader *)L.hdr, (const int *)L.prev[0]);
+        });
         READ_CHECK_LAUNCH();
     }
-    const int rc = objects_launch(od, W, H, L.keys, s, !lens, lens ? &ls : nullptr);
+    const int rc = objects_launch(od, cam, W, H, L.keys, s);
     if (rc != READ_OK) return rc;
     return resolve_launch(L.keys, 1, 0, W, H, levels, idx_levels, depth_levels, 0, L, seeds ? 1 : 0, s);
+}
+
+// One edited frame behind the six symbols: the checks, then the camera's frame.
+template <class Cam>
+int edited_frame(const char *who, const float *xyz, const int32_t *ids, void *cells, int64_t n, const float *cam_host, int W, int H,
+                 int levels, const read_splat_objects *objs, const read_splat_instances *inst, int32_t *const *idx_levels,
+                 float *const *depth_levels, void *ws, size_t ws_bytes, void *stream)
+{
+    const int rc = check_frame_args<Cam>(who, cam_host, xyz, ids, cells, n, objs, inst, W, H, levels, idx_levels, depth_levels, ws, ws_bytes);
+    if (rc != READ_OK) return rc;
+    const ObjectsDraw od{objs, inst, xyz, ids, n, cam_host};
+    if constexpr (Cam::whole_cloud)
+        return whole_cloud_frame(od, Cam::from_host(cam_host), W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+    else
+        return objects_frame(od, cells, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
 }
 }  // namespace
 
@@ -3007,12 +2757,8 @@ extern "C" int read_splat_forward_objects(const float *xyz_static, const int32_t
 {
     const char *who = "read_splat_forward_objects";
     READ_CHECK_ARG(M_host && objs && ws, "%s: null pointer (M_host, objs or workspace)", who);
-    const int rc = check_frame_args(who, nullptr, xyz_static, ids_static, cells, n_static, objs, nullptr, W, H, levels, idx_levels,
-                                    depth_levels, ws, ws_bytes);
-    if (rc != READ_OK) return rc;
-    std::vector<int64_t> ranges;
-    return objects_frame(partition_draw(objs, ranges), xyz_static, ids_static, cells, n_static, M_host, W, H, levels, idx_levels,
-                         depth_levels, ws, as_stream(stream));
+    return edited_frame<PinholeCam>(who, xyz_static, ids_static, cells, n_static, M_host, W, H, levels, objs, nullptr, idx_levels,
+                                    depth_levels, ws, ws_bytes, stream);
 }
 
 // Panorama: the whole cloud (objs NULL; the previous frame's winners warm-start it) or a labelled cloud's static part plus its
@@ -3023,11 +2769,8 @@ extern "C" int read_splat_forward_pano(const float *xyz, const int32_t *ids, int
 {
     const char *who = "read_splat_forward_pano";
     READ_CHECK_ARG(cam_host && ws, "%s: null pointer (cam_host or workspace)", who);
-    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, objs, nullptr, W, H, levels, idx_levels, depth_levels, ws,
-                                    ws_bytes);
-    if (rc != READ_OK) return rc;
-    std::vector<int64_t> ranges;
-    return pano_frame(partition_draw(objs, ranges), xyz, ids, n, cam_host, !objs, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+    return edited_frame<PanoCam>(who, xyz, ids, nullptr, n, cam_host, W, H, levels, objs, nullptr, idx_levels, depth_levels, ws, ws_bytes,
+                                 stream);
 }
 
 // Pinhole, the list itself.
@@ -3038,11 +2781,8 @@ extern "C" int read_splat_forward_instances(const float *xyz_static, const int32
 {
     const char *who = "read_splat_forward_instances";
     READ_CHECK_ARG(M_host && inst && ws, "%s: null pointer (M_host, inst or workspace)", who);
-    const int rc = check_frame_args(who, nullptr, xyz_static, ids_static, cells, n_static, nullptr, inst, W, H, levels, idx_levels,
-                                    depth_levels, ws, ws_bytes);
-    if (rc != READ_OK) return rc;
-    return objects_frame(instances_draw(inst), xyz_static, ids_static, cells, n_static, M_host, W, H, levels, idx_levels,
-                         depth_levels, ws, as_stream(stream));
+    return edited_frame<PinholeCam>(who, xyz_static, ids_static, cells, n_static, M_host, W, H, levels, nullptr, inst, idx_levels,
+                                    depth_levels, ws, ws_bytes, stream);
 }
 
 // Panorama, the list itself (no warm start: the ids are explicit).
@@ -3052,10 +2792,8 @@ extern "C" int read_splat_forward_pano_instances(const float *xyz, const int32_t
 {
     const char *who = "read_splat_forward_pano_instances";
     READ_CHECK_ARG(cam_host && inst && ws, "%s: null pointer (cam_host, inst or workspace)", who);
-    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, nullptr, inst, W, H, levels, idx_levels, depth_levels, ws,
-                                    ws_bytes);
-    if (rc != READ_OK) return rc;
-    return pano_frame(instances_draw(inst), xyz, ids, n, cam_host, false, W, H, levels, idx_levels, depth_levels, ws, as_stream(stream));
+    return edited_frame<PanoCam>(who, xyz, ids, nullptr, n, cam_host, W, H, levels, nullptr, inst, idx_levels, depth_levels, ws, ws_bytes,
+                                 stream);
 }
 
 // Lens camera: the whole cloud (objs NULL; the previous frame's winners warm-start it) or a labelled cloud's static part plus its
@@ -3066,12 +2804,8 @@ extern "C" int read_splat_forward_lens(const float *xyz, const int32_t *ids, int
 {
     const char *who = "read_splat_forward_lens";
     READ_CHECK_ARG(cam_host && ws, "%s: null pointer (cam_host or workspace)", who);
-    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, objs, nullptr, W, H, levels, idx_levels, depth_levels, ws,
-                                    ws_bytes, true);
-    if (rc != READ_OK) return rc;
-    std::vector<int64_t> ranges;
-    return pano_frame(partition_draw(objs, ranges), xyz, ids, n, cam_host, !objs, W, H, levels, idx_levels, depth_levels, ws,
-                      as_stream(stream), true);
+    return edited_frame<LensCam>(who, xyz, ids, nullptr, n, cam_host, W, H, levels, objs, nullptr, idx_levels, depth_levels, ws, ws_bytes,
+                                 stream);
 }
 
 // Lens camera, the list itself (no warm start: the ids are explicit).
@@ -3081,11 +2815,8 @@ extern "C" int read_splat_forward_lens_instances(const float *xyz, const int32_t
 {
     const char *who = "read_splat_forward_lens_instances";
     READ_CHECK_ARG(cam_host && inst && ws, "%s: null pointer (cam_host, inst or workspace)", who);
-    const int rc = check_frame_args(who, cam_host, xyz, ids, nullptr, n, nullptr, inst, W, H, levels, idx_levels, depth_levels, ws,
-                                    ws_bytes, true);
-    if (rc != READ_OK) return rc;
-    return pano_frame(instances_draw(inst), xyz, ids, n, cam_host, false, W, H, levels, idx_levels, depth_levels, ws,
-                      as_stream(stream), true);
+    return edited_frame<LensCam>(who, xyz, ids, nullptr, n, cam_host, W, H, levels, nullptr, inst, idx_levels, depth_levels, ws, ws_bytes,
+                                 stream);
 }
 
 extern "C" int read_splat_forward_gl(const float *xyz, int64_t n, const float *M_host, int W, int H,
@@ -3132,105 +2863,46 @@ extern "C" int read_splat_forward_gl(const float *xyz, int64_t n, const float *M
 }
 
 namespace {
-// One thread per point: the pixel it projects to (or -1) and its depth — project_one as every pass uses it, without the z-test.
-__global__ __launch_bounds__(256) void project_points_kernel(const float *__restrict__ xyz, long long n, Cam1 cam, int W, int H,
-                                                             int32_t *__restrict__ pixel, float *__restrict__ depth)
+// The three project-points symbols: the checks in one order, then project_points_kernel under the camera.
+template <class Cam>
+int project_points(const char *who, const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel, float *depth,
+                   void *stream)
 {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float d;
-        int xx, yy;
-        const int pix = project_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cam.m, W, H, d, xx, yy);
-        pixel[i] = pix;
-        if (depth) depth[i] = d;
-    }
+    READ_CHECK_ARG(n >= 0 && (n == 0 || (xyz && pixel)), "%s: null pointer", who);
+    READ_CHECK_ARG(cam_host, "%s: %s is null", who, Cam::host_name);
+    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "%s: bad W/H (%d,%d)", who, W, H);
+    const char *fault = Cam::frame_fault(cam_host);
+    READ_CHECK_ARG(!fault, "%s: cam_host: %s", who, fault);
+    if (n == 0) return READ_OK;
+    Cam1 rows;
+    memcpy(rows.m, cam_host, sizeof(rows.m));
+    long long blocks = ceil_div64(n, 256);
+    if (blocks > 65536) blocks = 65536;
+    with_cam_arg(Cam::from_host(cam_host), [&](auto... arg) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(project_points_kernel<Cam, decltype(arg)...>), dim3((unsigned)blocks), dim3(256), 0,
+                           as_stream(stream), xyz, (long long)n, rows, arg..., W, H, pixel, depth);
+    });
+    READ_CHECK_LAUNCH();
+    return READ_OK;
 }
 }  // namespace
 
 extern "C" int read_splat_project_points(const float *xyz, int64_t n, const float *M_host, int W, int H, int32_t *pixel,
                                          float *depth, void *stream)
 {
-    READ_CHECK_ARG(n >= 0 && (n == 0 || (xyz && pixel)), "read_splat_project_points: null pointer");
-    READ_CHECK_ARG(M_host, "read_splat_project_points: M_host is null");
-    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_project_points: bad W/H (%d,%d)", W, H);
-    if (n == 0) return READ_OK;
-    Cam1 cam;
-    for (int i = 0; i < 16; ++i) cam.m[i] = M_host[i];
-    long long blocks = ceil_div64(n, 256);
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(project_points_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), xyz, (long long)n, cam, W,
-                       H, pixel, depth);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
+    return project_points<PinholeCam>("read_splat_project_points", xyz, n, M_host, W, H, pixel, depth, stream);
 }
-
-namespace {
-// project_points_kernel under a panorama camera: project_pano_one as the frame's passes use it, without the z-test.
-__global__ __launch_bounds__(256) void pano_project_points_kernel(const float *__restrict__ xyz, long long n, Cam1 cam, int W, int H,
-                                                                  int32_t *__restrict__ pixel, float *__restrict__ depth)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float d;
-        int xx, yy;
-        const int pix = project_pano_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cam.m, W, H, d, xx, yy);
-        pixel[i] = pix;
-        if (depth) depth[i] = d;
-    }
-}
-}  // namespace
 
 extern "C" int read_splat_pano_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel,
                                               float *depth, void *stream)
 {
-    READ_CHECK_ARG(n >= 0 && (n == 0 || (xyz && pixel)), "read_splat_pano_project_points: null pointer");
-    READ_CHECK_ARG(cam_host, "read_splat_pano_project_points: cam_host is null");
-    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_pano_project_points: bad W/H (%d,%d)", W, H);
-    const char *fault = pano_cam_fault(cam_host);
-    READ_CHECK_ARG(!fault, "read_splat_pano_project_points: cam_host: %s", fault);
-    if (n == 0) return READ_OK;
-    Cam1 cam;
-    for (int i = 0; i < 16; ++i) cam.m[i] = cam_host[i];
-    long long blocks = ceil_div64(n, 256);
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(pano_project_points_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), xyz, (long long)n, cam,
-                       W, H, pixel, depth);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
+    return project_points<PanoCam>("read_splat_pano_project_points", xyz, n, cam_host, W, H, pixel, depth, stream);
 }
-
-namespace {
-// project_points_kernel under a lens camera: project_lens_one as the frame's passes use it, without the z-test.
-__global__ __launch_bounds__(256) void lens_project_points_kernel(const float *__restrict__ xyz, long long n, Cam1 cam, LensScalars ls,
-                                                                  int W, int H, int32_t *__restrict__ pixel, float *__restrict__ depth)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        float d;
-        int xx, yy;
-        const int pix = project_lens_one(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], cam.m, ls, W, H, d, xx, yy);
-        pixel[i] = pix;
-        if (depth) depth[i] = d;
-    }
-}
-}  // namespace
 
 extern "C" int read_splat_lens_project_points(const float *xyz, int64_t n, const float *cam_host, int W, int H, int32_t *pixel,
                                               float *depth, void *stream)
 {
-    READ_CHECK_ARG(n >= 0 && (n == 0 || (xyz && pixel)), "read_splat_lens_project_points: null pointer");
-    READ_CHECK_ARG(cam_host, "read_splat_lens_project_points: cam_host is null");
-    READ_CHECK_ARG(W >= 1 && H >= 1 && (long long)W * H < (1ll << 31), "read_splat_lens_project_points: bad W/H (%d,%d)", W, H);
-    const char *fault = lens_cam_fault(cam_host);
-    READ_CHECK_ARG(!fault, "read_splat_lens_project_points: cam_host: %s", fault);
-    if (n == 0) return READ_OK;
-    Cam1 cam;
-    LensScalars ls;
-    for (int i = 0; i < 16; ++i) cam.m[i] = cam_host[i];
-    for (int i = 0; i < 20; ++i) ls.s[i] = cam_host[12 + i];
-    long long blocks = ceil_div64(n, 256);
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(lens_project_points_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), xyz, (long long)n, cam,
-                       ls, W, H, pixel, depth);
-    READ_CHECK_LAUNCH();
-    return READ_OK;
+    return project_points<LensCam>("read_splat_lens_project_points", xyz, n, cam_host, W, H, pixel, depth, stream);
 }
 
 extern "C" int read_index_to_float(const int32_t *idx, int64_t count, float *out, void *stream)

@@ -125,11 +125,14 @@ class FrameRenderer:
     def rasterize(self, total_m, next_total=None):
         return self.raster.render(total_m, self.W, self.H, self.levels, out=(self.idx, self.depth), next_total=next_total)
 
+    def _rasterize_with(self, render, cam):
+        return render(cam, self.W, self.H, self.levels, out=(self.idx, self.depth))
+
     def rasterize_pano(self, cam):
-        return self.raster.render_pano(cam, self.W, self.H, self.levels, out=(self.idx, self.depth))
+        return self._rasterize_with(self.raster.render_pano, cam)
 
     def rasterize_lens(self, cam):
-        return self.raster.render_lens(cam, self.W, self.H, self.levels, out=(self.idx, self.depth))
+        return self._rasterize_with(self.raster.render_lens, cam)
 
     def gather(self, out=None):
         out = self.feat if out is None else out
@@ -151,11 +154,11 @@ class FrameRenderer:
 
     def render_pano_total(self, cam, out=None, channels=4):
         """render_total's twin for a panorama camera (the 16 floats of camera.pano_camera): only the raster step differs."""
-        return self._frame(lambda: self.rasterize_pano(cam), out, channels)
+        return self._frame(lambda: self._rasterize_with(self.raster.render_pano, cam), out, channels)
 
     def render_lens_total(self, cam, out=None, channels=4):
         """render_total's twin for a lens camera (the 32 floats of camera.lens_camera): only the raster step differs."""
-        return self._frame(lambda: self.rasterize_lens(cam), out, channels)
+        return self._frame(lambda: self._rasterize_with(self.raster.render_lens, cam), out, channels)
 
     def _frame(self, rasterize, out, channels):
         if not self._slots:
@@ -193,27 +196,25 @@ class FrameRenderer:
             for slot in self._slots:
                 slot["stream"].synchronize()
 
-    def render(self, view_matrix, proj_matrix=None, out=None, channels=4):
-        """view_matrix: camera->world 4x4 (the reference's convention); -> H x W x 4 RGBA (alpha = 1)."""
+    def _proj(self, proj_matrix):
+        """The caller's projection matrix, or the one set at construction."""
         proj = self.proj if proj_matrix is None else np.asarray(proj_matrix, np.float32)
         if proj is None:
             raise ValueError("no projection matrix set")
-        return self.render_total(total_matrix(proj, view_matrix), out, channels)
+        return proj
+
+    def render(self, view_matrix, proj_matrix=None, out=None, channels=4):
+        """view_matrix: camera->world 4x4 (the reference's convention); -> H x W x 4 RGBA (alpha = 1)."""
+        return self.render_total(total_matrix(self._proj(proj_matrix), view_matrix), out, channels)
 
     def render_pano(self, view_matrix, hfov_deg, proj_matrix=None, out=None, channels=4):
         """A panorama (cylindrical) frame with a horizontal field of hfov_deg in (0, 360]: view_matrix camera->world; of the
         projection matrix only the vertical scale / offset and the depth entries are used (camera.pano_camera).  Object edits
         apply; frames_in_flight as for ``render_total``."""
-        proj = self.proj if proj_matrix is None else np.asarray(proj_matrix, np.float32)
-        if proj is None:
-            raise ValueError("no projection matrix set")
-        return self.render_pano_total(pano_camera(proj, view_matrix, hfov_deg), out, channels)
+        return self.render_pano_total(pano_camera(self._proj(proj_matrix), view_matrix, hfov_deg), out, channels)
 
     def render_lens(self, view_matrix, model, coeffs, limit=None, proj_matrix=None, out=None, channels=4):
         """A frame through a lens: model 0 = a pinhole with Brown-Conrady distortion (coeffs k1, k2, p1, p2, k3), model 1 = a
         Kannala-Brandt fisheye (coeffs k1..k4); limit as in camera.lens_camera (None: just inside where the distortion folds
         back).  view_matrix camera->world.  Object edits apply; frames_in_flight as for ``render_total``."""
-        proj = self.proj if proj_matrix is None else np.asarray(proj_matrix, np.float32)
-        if proj is None:
-            raise ValueError("no projection matrix set")
-        return self.render_lens_total(lens_camera(proj, view_matrix, model, coeffs, limit), out, channels)
+        return self.render_lens_total(lens_camera(self._proj(proj_matrix), view_matrix, model, coeffs, limit), out, channels)

@@ -187,14 +187,20 @@ class PointCloudRasterizer:
         """The (I,16) float32 matrices M_i = object_matrix(M_0, P_i) of the instances, in handle order, for the camera total_m."""
         return object_matrices(total_m, [P for _, P, _ in self._instance_list()]).reshape(-1, 16)
 
+    def _instance_rows(self, cam, floats):
+        """(cam as ``floats`` float32, an (I,16) array of zeros with ``object_matrix(R4, P_i)[:3]`` in floats 0..11 of instance i):
+        R4 = cam's three rows with (0, 0, 0, 1) beneath, the instances in handle order."""
+        cam = np.asarray(cam, np.float32).reshape(floats)
+        R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
+        lst = self._instance_list()
+        out = np.zeros((len(lst), 16), np.float32)
+        out[:, :12] = object_matrices(R4, [P for _, P, _ in lst])[:, :3].reshape(-1, 12)
+        return cam, out
+
     def pano_instance_cameras(self, cam):
         """The (I,16) float32 panorama cameras of the instances, in handle order, for the camera ``cam`` (camera.pano_camera): the
         rows are ``object_matrix(R4, P_i)[:3]``, R4 = cam's three rows with (0, 0, 0, 1) beneath; kx, ky, za, zb repeat."""
-        cam = np.asarray(cam, np.float32).reshape(16)
-        R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
-        lst = self._instance_list()
-        out = np.empty((len(lst), 16), np.float32)
-        out[:, :12] = object_matrices(R4, [P for _, P, _ in lst])[:, :3].reshape(-1, 12)
+        cam, out = self._instance_rows(cam, 16)
         out[:, 12:] = cam[12:]
         return out
 
@@ -202,12 +208,7 @@ class PointCloudRasterizer:
         """The (I,16) float32 rows of the instances, in handle order, for the lens camera ``cam`` (camera.lens_camera): floats
         0..11 are ``object_matrix(R4, P_i)[:3]``, R4 = cam's three rows with (0, 0, 0, 1) beneath; the other 4 are ignored (0
         here) — the twenty scalars belong to the frame and travel once."""
-        cam = np.asarray(cam, np.float32).reshape(32)
-        R4 = np.concatenate([cam[:12].reshape(3, 4), np.array([[0, 0, 0, 1]], np.float32)], 0)
-        lst = self._instance_list()
-        out = np.zeros((len(lst), 16), np.float32)
-        out[:, :12] = object_matrices(R4, [P for _, P, _ in lst])[:, :3].reshape(-1, 12)
-        return out
+        return self._instance_rows(cam, 32)[1]
 
     def _instances_struct(self, matrices):
         """The read_splat_instances of this frame: its host arrays (first, npts, visible, M) are built here and kept on self
@@ -305,47 +306,35 @@ class PointCloudRasterizer:
         ``render`` gives them.  One camera per call; object labels, poses and visibility are honoured.  The whole cloud is read
         every frame (no chunk culling under a cylinder); without labels the previous frame's winners warm-start the pass.
         Pinhole and panorama frames may alternate on one rasteriser."""
-        cam = _host_f32(cam).reshape(-1, 16)
-        if cam.shape[0] != 1:
-            raise ValueError("render_pano renders one camera per call")
-        idx, dep, idx_p, dep_p = self._outputs(1, W, H, levels, want_depth, out)
-        ws = self._workspace(1, W, H)
-        cam_p = cam.ctypes.data_as(C.POINTER(C.c_float))
-        L = _lib.lib()
-        if self._inst is not None:
-            inst = self._instances_struct(self.pano_instance_cameras(cam[0]))
-            # a cloud without labels is static as a whole: its points' indices are their ids, and none are passed
-            ids = (self._static_ids.data_ptr() or None) if self.labels is not None else None
-            _lib.check(L.read_splat_forward_pano_instances(
-                self._static_xyz.data_ptr() or None, ids, self.n_static, cam_p, W, H, levels, C.byref(inst), idx_p, dep_p,
-                ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano_instances")
-        else:
-            _lib.check(L.read_splat_forward_pano(self.xyz.data_ptr() or None, None, self.n, cam_p, W, H, levels, None, idx_p,
-                                                 dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_pano")
-        return idx, dep
+        return self._render_whole(cam, 16, self.pano_instance_cameras, "read_splat_forward_pano", "render_pano", W, H, levels,
+                                  want_depth, out)
 
     def render_lens(self, cam, W, H, levels=5, want_depth=True, out=None):
         """One frame under a lens camera — a distorted pinhole or a fisheye: ``cam`` = the 32 floats of ``camera.lens_camera``
         -> (idx_levels, depth_levels) as ``render`` gives them.  One camera per call; object labels, instances, poses and
         visibility are honoured.  The whole cloud is read every frame (no chunk culling under a lens); without labels the
         previous frame's winners warm-start the pass.  Pinhole, panorama and lens frames may alternate on one rasteriser."""
-        cam = _host_f32(cam).reshape(-1, 32)
+        return self._render_whole(cam, 32, self.lens_instance_cameras, "read_splat_forward_lens", "render_lens", W, H, levels,
+                                  want_depth, out)
+
+    def _render_whole(self, cam, floats, instance_cameras, symbol, who, W, H, levels, want_depth, out):
+        """One frame of a camera that reads the whole cloud: ``floats`` host floats, ``symbol`` (+ ``_instances`` with ranges)."""
+        cam = _host_f32(cam).reshape(-1, floats)
         if cam.shape[0] != 1:
-            raise ValueError("render_lens renders one camera per call")
+            raise ValueError(f"{who} renders one camera per call")
         idx, dep, idx_p, dep_p = self._outputs(1, W, H, levels, want_depth, out)
         ws = self._workspace(1, W, H)
         cam_p = cam.ctypes.data_as(C.POINTER(C.c_float))
-        L = _lib.lib()
         if self._inst is not None:
-            inst = self._instances_struct(self.lens_instance_cameras(cam[0]))
+            inst = self._instances_struct(instance_cameras(cam[0]))
             # a cloud without labels is static as a whole: its points' indices are their ids, and none are passed
             ids = (self._static_ids.data_ptr() or None) if self.labels is not None else None
-            _lib.check(L.read_splat_forward_lens_instances(
+            _lib.check(getattr(_lib.lib(), symbol + "_instances")(
                 self._static_xyz.data_ptr() or None, ids, self.n_static, cam_p, W, H, levels, C.byref(inst), idx_p, dep_p,
-                ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_lens_instances")
+                ws.data_ptr(), ws.numel(), _lib.stream_ptr()), symbol + "_instances")
         else:
-            _lib.check(L.read_splat_forward_lens(self.xyz.data_ptr() or None, None, self.n, cam_p, W, H, levels, None, idx_p,
-                                                 dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "read_splat_forward_lens")
+            _lib.check(getattr(_lib.lib(), symbol)(self.xyz.data_ptr() or None, None, self.n, cam_p, W, H, levels, None, idx_p,
+                                                   dep_p, ws.data_ptr(), ws.numel(), _lib.stream_ptr()), symbol)
         return idx, dep
 
     def lidar_instance_cameras(self, cam):

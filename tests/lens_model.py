@@ -1,6 +1,6 @@
 """The lens camera of the fast render path — a distorted pinhole and a fisheye — defined once in NumPy.
 
-``project_lens_one`` in read_amd/csrc/splat.hip restates ``project``: fp32 throughout, no fused operations, sums left to right,
+``project_lens_one`` in read_amd/csrc/project.h restates ``project``: fp32 throughout, no fused operations, sums left to right,
 IEEE division, correctly rounded square root, polynomials by Horner with separate multiply and add.  The camera is the 32 fp32
 numbers of ``read_amd.camera.lens_camera``: r[12] (three unscaled rows applied to (x, y, z, 1): c0 = x_c, c1 = y_c, c3 = -z_c),
 sx, ox, sy, oy = P[0,0], P[0,2], P[1,1], P[1,2], za, zb = P[2,2], P[2,3], the limit, the model (0.0 / 1.0), five coefficients.

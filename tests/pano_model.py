@@ -1,6 +1,6 @@
 """The panorama (cylindrical) camera of the fast render path, defined once in NumPy.
 
-``project_pano_one`` in read_amd/csrc/splat.hip restates ``project``: fp32 throughout, no fused operations, sums left to
+``project_pano_one`` in read_amd/csrc/project.h restates ``project``: fp32 throughout, no fused operations, sums left to
 right, IEEE division and correctly rounded square root.  The camera is the 16 fp32 numbers of ``read_amd.camera.pano_camera``:
 r[12] (three rows applied to (x, y, z, 1): c0 = x_c, c1 = P[1,1] y_c, c3 = -z_c), kx = 2 / hfov_rad, ky = P[1,2], za = P[2,2],
 zb = P[2,3].
@@ -64,7 +64,7 @@ def ndc(xyz, cam):
 
 
 def tail(nx, ny, nz, W, H):
-    """The tail of project_one: -> (pixel or -1 (int32), depth fp32, u, v)."""
+    """ndc_pixel, which project_one ends with: -> (pixel or -1 (int32), depth fp32, u, v)."""
     with np.errstate(all='ignore'):
         inside = (nx >= f32(-1)) & (nx <= f32(1)) & (ny >= f32(-1)) & (ny <= f32(1)) & (nz >= f32(-1)) & (nz <= f32(1))
         u = (f32(W) * (nx + f32(1))) * f32(0.5)

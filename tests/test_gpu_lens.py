@@ -252,7 +252,7 @@ def test_labels_moved_hidden_and_empty(hip, lens):
 
 
 def test_thirty_three_instances_cross_the_flush(hip):
-    """33 copies of object 1 beside the object itself: 34 ranges, two launches of splat_lens_kernel (32 ranges each at most)."""
+    """33 copies of object 1 beside the object itself: 34 ranges, two launches of range_splat_kernel<LensCam> (32 ranges each at most)."""
     n = 5000
     xyz = pc.ring_cloud(n, 17)
     labels = pc.labels_for(n, 5, n_objects=1, share=0.04)

@@ -13,6 +13,7 @@ from read_amd.raster import PointCloudRasterizer
 from read_amd.render import Scene
 from tests import lidar_cases as lc
 from tests import lidar_model as lm
+from tests import pano_cases as pc
 
 pytestmark = pytest.mark.gpu
 
@@ -221,6 +222,36 @@ def test_labelled_cloud_moved_hidden_and_drawn_twice(hip):
     assert plain.count == want['count'] and np.array_equal(bits(plain.points.cpu().numpy()), bits(want['xyz']))
     with pytest.raises(ValueError, match="sensor"):
         r.sweep_lidar(sensor, lc.sensor_cam(sensor.elev, 120.0, 0.5))
+
+
+def test_thirty_three_instances_cross_the_flush(hip):
+    """33 copies of object 1 beside the object itself: 34 ranges, two launches of lidar_pass_kernel (32 ranges each at most), one
+    copy hidden: range image, ids and return list against the model's sweep over the same ranges."""
+    n = 5000
+    xyz = pc.ring_cloud(n, 17)
+    labels = pc.labels_for(n, 5, n_objects=1, share=0.04)
+    sel = np.flatnonzero(labels == 1)
+    assert 100 < sel.size < 1000
+    r = PointCloudRasterizer(xyz, labels=labels)
+    rng = np.random.default_rng(8)
+    poses = [pc.translation(rng.uniform(-6.0, 6.0, 3)) for _ in range(33)]
+    hs = [r.add_instance(1, P) for P in poses]
+    r.set_instance_visible(hs[31], False)
+    sensor = lidar.LidarSensor(np.linspace(-20.0, 10.0, 16), 256, window=(1, 2), rel=0.05, slack=0.2)
+    cam = sensor.camera(lc.pose(yaw=20.0, pitch=-2.0, roll=1.0, t=(0.3, 0.2, 0.1)))
+    assert r.lidar_instance_cameras(cam).shape == (34, 16)
+    shown = [(1, P) for i, P in enumerate(poses) if i != 31]
+    keys = lm.labelled_keys(xyz, labels, cam, sensor.elev, sensor.W, {}, set(), extra=shown)
+    assert (keys != lm.labelled_keys(xyz, labels, cam, sensor.elev, sensor.W, {}, set())).sum() > 30      # the copies show
+    last = lm.key_image(xyz[sel], lm.object_camera(cam, poses[32]), sensor.elev, sensor.W, ids=sel)
+    assert ((last != lm.EMPTY_KEY) & (last == keys)).any()           # and so does the one past the 32-range flush
+    want = lm.sweep(None, cam, sensor.elev, sensor.W, (1, 2), True, sensor.scale, sensor.slack, keys=keys)
+    sw = r.sweep_lidar(sensor, cam)
+    assert np.array_equal(bits(sw.range.cpu().numpy()), bits(want['range'])) and np.array_equal(sw.ids.cpu().numpy(), want['idx'])
+    count = sw.count
+    assert count == want['count'] > 100
+    assert np.array_equal(sw.cells[:count].cpu().numpy(), want['cell']) and np.array_equal(sw.return_ids[:count].cpu().numpy(), want['id'])
+    assert sw.points.shape == (count, 3) and np.array_equal(bits(sw.points.cpu().numpy()), bits(want['xyz']))
 
 
 # ---- Scene.lidar_sweep, and frames around it ---------------------------------------------------------------------------------------

@@ -223,6 +223,33 @@ def test_forward_pano_partition_equals_the_rasteriser(hip):
     assert not np.array_equal(keys, pm.labelled_keys(xyz, labels, cam, {}, set(), W, H))          # the move and the hiding show
 
 
+def test_thirty_three_instances_cross_the_flush(hip):
+    """33 copies of object 1 beside the object itself: 34 ranges, two launches of range_splat_kernel under the panorama camera (32
+    ranges each at most), one copy hidden."""
+    W, H = 128, 48
+    n = 5000
+    xyz = pc.ring_cloud(n, 17)
+    labels = pc.labels_for(n, 5, n_objects=1, share=0.04)
+    sel = np.flatnonzero(labels == 1)
+    assert 100 < sel.size < 1000
+    r = PointCloudRasterizer(xyz, labels=labels)
+    rng = np.random.default_rng(8)
+    poses = [pc.translation(rng.uniform(-6.0, 6.0, 3)) for _ in range(33)]
+    hs = [r.add_instance(1, P) for P in poses]
+    r.set_instance_visible(hs[31], False)
+    cam = camera.pano_camera(pc.proj(W, H), pc.pose(yaw=20.0, pitch=-5.0, roll=6.0), 360.0)
+    assert r.pano_instance_cameras(cam).shape == (34, 16)
+    keys = pm.labelled_keys(xyz, labels, cam, {}, set(), W, H)
+    before = keys.copy()
+    for i, P in enumerate(poses):
+        if i != 31:
+            pm.key_image(xyz[sel], pm.object_camera(cam, P), W, H, ids=sel, keys=keys)
+    assert (keys != before).sum() > 30                               # the copies show
+    last = pm.key_image(xyz[sel], pm.object_camera(cam, poses[32]), W, H, ids=sel)
+    assert ((last != pm.EMPTY_KEY) & (last == keys)).any()           # and so does the one past the 32-range flush
+    assert_frame(*r.render_pano(cam, W, H, LEVELS), *pm.pyramid_of(keys, W, H, LEVELS), "33 instances")
+
+
 # ---- FrameRenderer ---------------------------------------------------------------------------------------------------------------
 def _check_rgb(got, ref, what):
     diff = got.double() - ref.double()

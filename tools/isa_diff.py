@@ -1,6 +1,6 @@
 """Does a source change alter the gfx950 code of a kernel?  One verdict per kernel symbol.
 
-    python tools/isa_diff.py REV [file.hip]          (file defaults to conv.hip)
+    python tools/isa_diff.py REV [file.hip] [--pair OLD=NEW ...]          (file defaults to conv.hip)
 
 REV's read_amd/csrc/<file> is written into a temporary directory beside REV's headers (csrc/*.h, include/*.h); that copy and the
 working tree's file are compiled with the product's flags (read_amd.build.FLAGS + PER_FILE) plus -S --cuda-device-only, and
@@ -14,7 +14,11 @@ each kernel's text (its label up to .Lfunc_end) is compared:
 The one thing masked before comparing is the ordinal of the function inside the file in local labels (.LBB<n>_, .Lfunc_end<n>),
 which changes when a kernel is added or removed above, and with it the blanks that pad a label line's comment to its column (an ordinal
 of three digits where there were two shifts that padding by one).  Exit status 1 if any kernel differs or exists on one side only.
+
+--pair OLD=NEW compares a kernel across a rename: OLD and NEW are substrings of the demangled names, each matching exactly one kernel
+of REV and of the working tree; the two are compared as one kernel, with the symbol itself masked in the compared text as well.
 """
+import argparse
 import os
 import re
 import subprocess
@@ -87,13 +91,21 @@ def demangle(names):
     for tool in ("llvm-cxxfilt", "c++filt"):
         try:
             out = subprocess.run([tool], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
-            return {n: o.replace("(anonymous namespace)::", "") for n, o in zip(names, out)}
+            return dict(zip(names, out))
         except (OSError, subprocess.CalledProcessError):
             continue
     return {n: n for n in names}
 
 
-def main(rev, name="conv.hip"):
+def paired(pretty, side, text, which):
+    """The one symbol of `side` whose demangled name contains `text`."""
+    hits = [n for n in side if text in pretty[n]]
+    if len(hits) != 1:
+        sys.exit(f"--pair: {text!r} matches {len(hits)} kernels of {which}: " + ", ".join(pretty[n] for n in hits))
+    return hits[0]
+
+
+def main(rev, name="conv.hip", pairs=()):
     with tempfile.TemporaryDirectory() as tmp:
         csrc, inc = os.path.join(tmp, "csrc"), os.path.join(tmp, "include")
         os.makedirs(csrc)
@@ -109,6 +121,13 @@ def main(rev, name="conv.hip"):
             new = ex.submit(compile_asm, os.path.join(B.CSRC, name), os.path.join(ROOT, "include"), B.CSRC, os.path.join(tmp, "new.s"))
             old, new = kernels(old.result()), kernels(new.result())
     pretty = demangle(sorted(set(old) | set(new)))
+    for pair in pairs:                                 # the renamed kernel takes its new symbol on both sides
+        o, n = (paired(pretty, side, text, which) for side, text, which in zip((old, new), pair.split("=", 1), (rev, "the working tree")))
+        text, meta = old.pop(o)
+        old[n] = ([l.replace(o, "<kernel>") for l in text], meta)
+        new[n] = ([l.replace(n, "<kernel>") for l in new[n][0]], new[n][1])
+        pretty[n] = f"{pretty[o]}  ->  {pretty[n]}"
+    pretty = {n: p.replace("(anonymous namespace)::", "") for n, p in pretty.items()}
     count = {}
     print(f"{name}: {rev} against the working tree, {len(old)} / {len(new)} kernels")
     print("verdict | lines old / new | vgpr agpr sgpr scratch lds | kernel")
@@ -127,6 +146,9 @@ def main(rev, name="conv.hip"):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) < 2:
-        sys.exit(__doc__)
-    sys.exit(main(*sys.argv[1:3]))
+    ap = argparse.ArgumentParser(usage=__doc__)
+    ap.add_argument("rev")
+    ap.add_argument("file", nargs="?", default="conv.hip")
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW")
+    a = ap.parse_args()
+    sys.exit(main(a.rev, a.file, a.pair))

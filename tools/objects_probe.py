@@ -14,7 +14,7 @@ centre and a drift).
                        five GL-twin passes), per frame, wall clock
   today_set_vertices_ms  the route for MOVING them: the moved cloud through Scene.set_vertices + OGL.infer (new rasteriser: upload,
                        cell build, no warm start), per frame, wall clock
---raster-only: only the objects lap (for a rocprofv3 --kernel-trace --stats run that lists splat_objects_kernel).
+--raster-only: only the objects lap (for a rocprofv3 --kernel-trace --stats run that lists range_splat_kernel<PinholeCam>).
 """
 import argparse
 import json
