@@ -451,6 +451,70 @@ typedef struct read_annotate_args {
  * negative first or npts, first + npts past the pool. */
 int read_annotate_frame(const read_annotate_args *args, void *stream);
 
+/* ---------------------------------------------------------------- frame flow (extension) */
+
+/* Where each pixel's surface point goes in the next frame: optical flow, the depth there and whether it is still seen, between two
+ * states of one edited scene (csrc/flow.hip).  The contract is tests/flow_model.py, held bit for bit.  State A (idx0, depth0, M0, d_M,
+ * d_visible) is the frame the labels live on, state B (idx0_next, depth0_next, M0_next, d_M_next, d_visible_next) the frame they point
+ * into: both are LEVEL-0 pinhole frames of read_splat_forward_instances over the same cloud, labels, pool and W x H, and the B tables
+ * are indexed by A's list positions (an instance that B no longer has is hidden there).
+ *
+ * Per pixel p of A: empty (idx0 = 0 and the bits of depth0 = 0) -> state EMPTY.  Otherwise id -> object k and point as in
+ * read_annotate_frame.  The drawer: for k = 0 the static scene (M0 / M0_next; M0 must reproduce pixel p and depth0[p]'s bits), for
+ * k >= 1 the FIRST instance i in list order that is visible in A, draws k and under whose d_M[i] the point projects to pixel p with
+ * depth0[p]'s bits (the annotation's walk).  No drawer, an id no range holds, or a static point M0 does not reproduce: UNMATCHED and
+ * *unmatched += 1.  With u = ((float)W (nx + 1)) 0.5f, v = ((float)H (1 - ny)) 0.5f the continuous pixel coordinates of the point (the
+ * pixel is their integer part) and d = (nz + 1) 0.5f — fp32, no contraction, sums left to right, IEEE division —: (u_a, v_a) under A's
+ * drawer matrix, (u_b, v_b, d_b) and the pixel q under B's.  The drawer hidden in B: HIDDEN.  q >= 0: VISIBLE iff idx0_next[q] = id and
+ * the bits of depth0_next[q] equal d_b's (a tie of two copies of one point counts as visible), else OCCLUDED.  q = -1 with nz in
+ * [-1, 1] and nx, ny finite: OFF_IMAGE; any other q = -1: CLIPPED.
+ *
+ * flow[p] = (u_b - u_a, v_b - v_a) and depth_next[p] = d_b for VISIBLE, OCCLUDED and OFF_IMAGE; +0.0f, all three, for every other state.
+ * counts[s] = pixels in state s (counts[7] stays 0).  stats[i][0..3] of instance i, by list position: px (pixels it drew in A), visible,
+ * occluded, outside (OFF_IMAGE + CLIPPED); an instance hidden in B keeps px only.  Integer adds: order-free. */
+#define READ_FLOW_STATES 8
+#define READ_FLOW_STATS  4
+#define READ_FLOW_EMPTY     0
+#define READ_FLOW_VISIBLE   1
+#define READ_FLOW_OCCLUDED  2
+#define READ_FLOW_OFF_IMAGE 3
+#define READ_FLOW_CLIPPED   4
+#define READ_FLOW_HIDDEN    5
+#define READ_FLOW_UNMATCHED 6
+typedef struct read_flow_args {
+    const float *xyz; int64_t n;           /* device: the scene cloud, n x 3 */
+    const int32_t *labels;                 /* device, n, or NULL = every point static */
+    int K_own;                             /* own objects: labels lie in [0, K_own] */
+    int n_foreign;                         /* 0 .. READ_GATHER_MAX_TABLES - 1 */
+    const read_annotate_foreign *foreign;  /* host, n_foreign: id bases ascend from n without overlap */
+    const float *pool_xyz; int64_t pool_n; /* device: the point pool of read_splat_instances */
+    int count;                             /* instances I of state A */
+    const int32_t *obj;                    /* host, count: the object (1..K) instance i draws (checked, not uploaded) */
+    const float *d_M;                      /* device, count x 16: M_i of state A */
+    const int32_t *d_visible;              /* device, count: 0 = hidden in A */
+    const int32_t *d_obj_begin;            /* device, K + 1 */
+    const int32_t *d_obj_list;             /* device, count */
+    const float *d_M_next;                 /* device, count x 16: M_i of state B, by A's list positions */
+    const int32_t *d_visible_next;         /* device, count: 0 = hidden in B (or gone) */
+    const float *M0; const float *M0_next; /* host, 16 each: the cameras of A and B; they travel in the kernel arguments */
+    const int32_t *idx0; const float *depth0;             /* device: A's level-0 frame */
+    const int32_t *idx0_next; const float *depth0_next;   /* device: B's level-0 frame */
+    int W, H;
+    float *flow;                           /* device, W * H x 2, 8-byte aligned */
+    float *depth_next;                     /* device, W * H */
+    int32_t *state;                        /* device, W * H */
+    int32_t *counts;                       /* device, READ_FLOW_STATES */
+    int32_t *stats;                        /* device, count x READ_FLOW_STATS */
+    int32_t *unmatched;                    /* device, 1 */
+} read_flow_args;
+/* Stream-ordered, allocates nothing, no synchronisation: one init launch (counts, the statistics rows and *unmatched) and the pixel
+ * pass (8 B read and 16 B written per pixel, plus the points).  count = 0: no table is read, object pixels are UNMATCHED and static
+ * pixels flow.  READ_EINVAL with a message, before any device work, for: null pointers with work to do (flow not 8-byte aligned
+ * included), W or H < 1 or W * H >= 2^31, n, K_own, count or pool_n below 0 (n or pool_n above INT32_MAX), n_foreign outside
+ * 0 .. READ_GATHER_MAX_TABLES - 1, an object number outside [1, K], foreign bases that do not ascend from n (or overlap, or pass
+ * INT32_MAX, or leave the pool), a non-finite entry of M0 or M0_next. */
+int read_flow_frame(const read_flow_args *args, void *stream);
+
 /* ---------------------------------------------------------------- descriptor gather / scatter */
 
 /* (C, N) channel-major texture  ->  N x C row-major rows (and back, for gradients). */

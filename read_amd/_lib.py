@@ -114,6 +114,23 @@ class AnnotateArgs(C.Structure):
                 ("out_obj", C.c_void_p), ("out_inst", C.c_void_p), ("stats", C.c_void_p), ("unmatched", C.c_void_p)]
 
 
+READ_FLOW_STATES = 8
+READ_FLOW_STATS = 4
+
+
+class FlowArgs(C.Structure):
+    """read_flow_args (include/read_hip.h): one read_flow_frame call."""
+    _fields_ = [("xyz", C.c_void_p), ("n", C.c_int64), ("labels", C.c_void_p), ("K_own", C.c_int), ("n_foreign", C.c_int),
+                ("foreign", C.POINTER(AnnotateForeign)), ("pool_xyz", C.c_void_p), ("pool_n", C.c_int64), ("count", C.c_int),
+                ("obj", C.c_void_p), ("d_M", C.c_void_p), ("d_visible", C.c_void_p), ("d_obj_begin", C.c_void_p),
+                ("d_obj_list", C.c_void_p), ("d_M_next", C.c_void_p), ("d_visible_next", C.c_void_p),
+                ("M0", C.c_void_p), ("M0_next", C.c_void_p),
+                ("idx0", C.c_void_p), ("depth0", C.c_void_p), ("idx0_next", C.c_void_p), ("depth0_next", C.c_void_p),
+                ("W", C.c_int), ("H", C.c_int),
+                ("flow", C.c_void_p), ("depth_next", C.c_void_p), ("state", C.c_void_p), ("counts", C.c_void_p),
+                ("stats", C.c_void_p), ("unmatched", C.c_void_p)]
+
+
 READ_STITCH_MAX_PARTS = 8
 
 
@@ -177,6 +194,7 @@ SIGNATURES = {
     "read_select_vote": (_i, [_vp, _i64, C.POINTER(_f), _i, _i, _vp, _vp, _f, _f, _vp, _vp]),
     "read_select_finish": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "read_annotate_frame": (_i, [C.POINTER(AnnotateArgs), _vp]),
+    "read_flow_frame": (_i, [C.POINTER(FlowArgs), _vp]),
     "read_texture_to_rows": (_i, [_vp, _i64, _i, _vp, _vp]),
     "read_rows_to_texture": (_i, [_vp, _i64, _i, _vp, _vp]),
     "read_gather_forward": (_i, [_vp, _i64, _i, _i, _pp, C.POINTER(_i64), _pp, _i, _vp]),

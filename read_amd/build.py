@@ -18,14 +18,14 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libreadhip.so")
-SOURCES = ["api_common.cpp", "splat.hip", "select.hip", "annotate.hip", "lidar.hip", "gather.hip", "conv.hip", "conv_pack.cpp", "train.hip", "unet.cpp"]
+SOURCES = ["api_common.cpp", "splat.hip", "select.hip", "annotate.hip", "flow.hip", "lidar.hip", "gather.hip", "conv.hip", "conv_pack.cpp", "train.hip", "unet.cpp"]
 DEBUG_SOURCES = ["probe.hip"]        # measurement probes (read_hip_debug.h): libreadhip_debug.so only, never the product
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-x", "hip",
          "-I", os.path.join(ROOT, "include"), "-I", CSRC, "-Wall", "-Wno-unused-function"]
-# the rasteriser's pixel assignment must be bit-exact fp32: no a*b+c contraction (select.hip and annotate.hip project with the same code; lidar.hip restates tests/lidar_model.py)
+# the rasteriser's pixel assignment must be bit-exact fp32: no a*b+c contraction (select.hip, annotate.hip and flow.hip project with the same code; lidar.hip restates tests/lidar_model.py)
 # gather / train: fp32 atomicAdd as the hardware global_atomic_add_f32 (the default lowers it to a compare-and-swap loop)
-PER_FILE = {"splat.hip": ["-ffp-contract=off"], "select.hip": ["-ffp-contract=off"], "annotate.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"], "conv.hip": ["-fno-slp-vectorize"], "gather.hip": ["-munsafe-fp-atomics"],
+PER_FILE = {"splat.hip": ["-ffp-contract=off"], "select.hip": ["-ffp-contract=off"], "annotate.hip": ["-ffp-contract=off"], "flow.hip": ["-ffp-contract=off"], "lidar.hip": ["-ffp-contract=off"], "conv.hip": ["-fno-slp-vectorize"], "gather.hip": ["-munsafe-fp-atomics"],
             "train.hip": ["-munsafe-fp-atomics"]}
 
 
@@ -49,7 +49,8 @@ def build(force: bool = False, verbose: bool = False, debug: bool = False) -> st
     FLAGS = globals()["FLAGS"] + (["-DREAD_DEBUG_KNOBS"] if debug else []) + [f"-D{d}" for d in os.environ.get("READ_EXTRA_DEFINES", "").split()]
     os.makedirs(OBJ, exist_ok=True)
     headers = [os.path.join(ROOT, "include", "read_hip.h"), os.path.join(ROOT, "include", "read_hip_debug.h"), os.path.join(CSRC, "common.h"),
-               os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "project.h"), os.path.join(CSRC, "ranges.h")]
+               os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "project.h"), os.path.join(CSRC, "ranges.h"),
+               os.path.join(CSRC, "pixel_tables.h")]
     SOURCES = globals()["SOURCES"] + (DEBUG_SOURCES if debug else [])
     hipcc = _hipcc()
     jobs = []

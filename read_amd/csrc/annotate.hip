@@ -2,7 +2,7 @@
 // boxes, counts and nearest depth (the contract is tests/annotate_model.py, held bit for bit).
 //
 //   annotate_init_kernel     the statistics rows (zeros, INT32_MAX, -1 and n_pts: no memset writes all of them) and the counter
-//   annotate_pixels_kernel   one lane per pixel: id -> object through the labels / the foreign ranges, then the first instance of that
+//   annotate_pixels_kernel   one lane per pixel (pixel_tables.h, shared with flow.hip): id -> object through the labels / the foreign ranges, then the first instance of that
 //                            object whose matrix puts the point on this pixel at this depth; 16 B per pixel; the visible statistics go
 //                            out once per wave and instance, not once per pixel
 //   annotate_extents_kernel  the shape of range_splat_kernel<PinholeCam>: <= 32 ranges per launch, four points per thread; a workgroup reduces
@@ -15,6 +15,7 @@
 
 #pragma clang fp contract(off)
 
+#include "pixel_tables.h"
 #include "project.h"
 
 using namespace readhip;
@@ -22,20 +23,9 @@ using namespace readhip;
 namespace {
 
 constexpr int STATS = READ_ANNOTATE_STATS;
-constexpr int MAX_FOREIGN = READ_GATHER_MAX_TABLES - 1;
+constexpr int MAX_FOREIGN = PIXEL_MAX_FOREIGN;
 constexpr int32_t I32_MAX = 0x7fffffff;
 // stats row: 0 vis_px | 1 vx0 2 vy0 3 vx1 4 vy1 | 5 in_pts | 6 ax0 7 ay0 8 ax1 9 ay1 | 10 near_bits | 11 n_pts
-
-struct ForeignRanges {
-    long long base[MAX_FOREIGN], n[MAX_FOREIGN], first[MAX_FOREIGN];
-    int count;
-};
-
-struct PixelTables {
-    const float *M;
-    const int32_t *visible, *value, *obj_begin, *obj_list;
-    int count, K, K_own;
-};
 
 __global__ __launch_bounds__(256) void annotate_init_kernel(int32_t *__restrict__ stats, const int32_t *__restrict__ npts, int count,
                                                             int32_t *__restrict__ unmatched)
@@ -78,43 +68,17 @@ __global__ __launch_bounds__(256) void annotate_pixels_kernel(const float *__res
         const int32_t id = idx0[p];
         const uint32_t dbits = __float_as_uint(depth0[p]);
         if (!((id == 0) & (dbits == 0u))) {
-            int k = -1;
-            const float *pt = nullptr;
-            if (id >= 0 && (long long)id < n) {
-                k = labels ? labels[id] : 0;
-                if (k > tb.K_own) k = -1;                     // a label past the own objects: no range holds it
-                pt = xyz + 3ll * id;
-            } else {
-                for (int f = 0; f < fr.count; ++f)
-                    if ((long long)id >= fr.base[f] && (long long)id < fr.base[f] + fr.n[f]) {
-                        k = tb.K_own + 1 + f;
-                        pt = pool_xyz + 3 * (fr.first[f] + ((long long)id - fr.base[f]));
-                    }
-            }
+            const float *pt;
+            const int k = pixel_object(id, xyz, n, labels, pool_xyz, fr, tb.K_own, pt);
             if (k < 0) {
                 lost = true;
             } else if (k == 0) {
                 obj = 0;
             } else {
                 obj = k;
-                lost = true;
-                if (tb.count > 0) {
-                    const float x = pt[0], y = pt[1], z = pt[2];
-                    const int j1 = min(tb.obj_begin[k], tb.count);              // a table out of step must not read past its end
-                    for (int j = max(tb.obj_begin[k - 1], 0); j < j1; ++j) {
-                        const int i = tb.obj_list[j];
-                        if ((unsigned)i >= (unsigned)tb.count || tb.visible[i] == 0) continue;
-                        float d;
-                        int xx, yy;
-                        const int pix = project_one(x, y, z, tb.M + 16 * (size_t)i, W, H, d, xx, yy);
-                        if ((long long)pix == p && __float_as_uint(d) == dbits) {
-                            won = i;
-                            value = tb.value[i];
-                            lost = false;
-                            break;
-                        }
-                    }
-                }
+                won = pixel_drawer(tb, k, pt, p, dbits, W, H);
+                if (won >= 0) value = tb.value[won];
+                lost = won < 0;
             }
         }
         out_obj[p] = obj;

@@ -1,5 +1,5 @@
 // The projection of one point under every camera model, shared by every translation unit that must land a point in the same pixel
-// as the rasteriser does (splat.hip, select.hip, annotate.hip, lidar.hip), and the camera types the rasteriser's range kernels are
+// as the rasteriser does (splat.hip, select.hip, annotate.hip, flow.hip, lidar.hip), and the camera types the rasteriser's range kernels are
 // written over.  Bit-exact fp32: include it only from files compiled with -ffp-contract=off.
 #pragma once
 #include <cmath>
@@ -79,6 +79,34 @@ __device__ __forceinline__ int project_one(float x, float y, float z, const floa
     float nx, ny, nz;
     div3_ieee(c0, c1, c2, c3, nx, ny, nz);
     return ndc_pixel(nx, ny, nz, true, W, H, depth, xx_out, yy_out);
+}
+
+// project_one with what ndc_pixel rounds away kept (flow.hip; tests/flow_model.py is the definition): the continuous pixel
+// coordinates u, v that the pixel is the integer part of, and the normalised device coordinates, which tell a point beside the image
+// (nz in [-1, 1], nx and ny finite) from one cut by a plane.  The same operations on the same operands as project_one / ndc_pixel, so
+// pixel and depth are theirs bit for bit.  M is anything indexed 0..15: a table row, or a matrix in the kernel arguments.
+struct SubPixel {
+    float u, v, depth, nx, ny, nz;
+    int pix;                                    // the pixel, or -1
+};
+
+template <class Mat>
+__device__ __forceinline__ SubPixel project_one_subpixel(float x, float y, float z, const Mat &M, int W, int H)
+{
+    const float c0 = M[0] * x + M[1] * y + M[2] * z + M[3] * 1.0f;
+    const float c1 = M[4] * x + M[5] * y + M[6] * z + M[7] * 1.0f;
+    const float c2 = M[8] * x + M[9] * y + M[10] * z + M[11] * 1.0f;
+    const float c3 = M[12] * x + M[13] * y + M[14] * z + M[15] * 1.0f;
+    SubPixel s;
+    div3_ieee(c0, c1, c2, c3, s.nx, s.ny, s.nz);
+    const bool inside = (s.nx >= -1.0f) & (s.nx <= 1.0f) & (s.ny >= -1.0f) & (s.ny <= 1.0f) & (s.nz >= -1.0f) & (s.nz <= 1.0f);
+    s.u = ((float)W * (s.nx + 1.0f)) * 0.5f;
+    s.v = ((float)H * (1.0f - s.ny)) * 0.5f;
+    s.depth = (s.nz + 1.0f) * 0.5f;
+    const int xx = (int)s.u, yy = (int)s.v;
+    const bool ok = inside & (xx >= 0) & (xx < W) & (yy >= 0) & (yy < H);
+    s.pix = ok ? yy * W + xx : -1;
+    return s;
 }
 
 // The arctangent of the panorama, lens and LiDAR cameras (splat.hip, lidar.hip); tests/pano_model.py::atan2_model is the definition.

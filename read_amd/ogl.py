@@ -168,6 +168,41 @@ class OGL:
             annotation = raster.annotate(M[0], W, H, idx[0], dep[0])
         return {'output': out, 'net_input': [f.permute(0, 3, 1, 2) for f in feats], 'annotation': annotation}
 
+    def infer_tracked(self):
+        """``infer_annotated``'s fast path with the frame snapshot for the frame flow in place of the annotation: -> {'output',
+        'net_input', 'state'}; 'state' is a ``flow.FrameState`` of the level-0 frame the output was painted from, for
+        ``Scene.flow_between`` with the state of another call.  'output' is ``infer()``'s frame bit for bit.  What the flow does not
+        cover is refused by name."""
+        model, scene = self.model, self.renderer.scene
+        what = "frame flow (infer_tracked)"
+        if getattr(scene, 'stitched', False):
+            raise NotImplementedError(f"{what} on a StitchedScene: instances belong to a part; take the flow of the parts' own frames")
+        if getattr(scene, 'panorama', None) is not None:
+            raise NotImplementedError(f"a panorama camera (set_panorama) with {what}: the flow re-projects with the pinhole "
+                                      "projection")
+        if getattr(scene, 'lens', None) is not None:
+            raise NotImplementedError(f"a lens camera (set_lens) with {what}: the flow re-projects with the pinhole projection")
+        self._require_fast(what, None, ": the flow describes the level-0 frame at the output size")
+        texture = model._modules[str(model._loaded_textures[0])] if model._loaded_textures else model._modules['0']
+        W, H = self.viewport_size
+        fmts = self.input_format.replace(' ', '').split(',')
+        raster = scene.rasterizer()
+        if raster.n != texture.texture_.shape[-1]:
+            raise ValueError(f"descriptor table has {texture.texture_.shape[-1]} points, the scene cloud {raster.n}")
+        M = scene.total_matrix()
+        if M.shape[0] != 1:
+            raise NotImplementedError(f"more than one camera with {what}")
+        self.last_path = 'fast'
+        with torch.set_grad_enabled(False):
+            idx, dep = raster.render(M, W, H, len(fmts), want_depth=True, next_total=scene.take_next_total_matrix())
+            if scene.has_foreign():
+                feats = gather_tables_pyramid(scene.gather_tables(texture), idx)
+            else:
+                feats = gather_pyramid(texture.rows(), idx, texture.activation, ss=1)
+            out = model.net.engine(H, W).forward(feats[0][0], feats[1][0], feats[2][0], feats[3][0], channels=4)
+            state = raster.frame_state(M[0], W, H, idx[0], dep[0])
+        return {'output': out, 'net_input': [f.permute(0, 3, 1, 2) for f in feats], 'state': state}
+
     def _require_fast(self, what, input_dict, ss_note=''):
         """``what`` — foreign objects, a panorama or lens camera, scene stitching — is drawn on the fast path only (for foreign objects:
         the dict path's single-table lookup would see ids >= N).  What would leave the fast path is refused by name."""

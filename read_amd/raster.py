@@ -251,6 +251,36 @@ class PointCloudRasterizer:
                                   [k for k, _, _ in lst], self.instance_matrices(M0[0]), [v for _, _, v in lst],
                                   list(self._inst.keys()), W, H, idx0, depth0)
 
+    def frame_state(self, total_m, W, H, idx0, depth0):
+        """The snapshot the frame flow works from (read_amd/flow.py): the camera, the CURRENT instance list with
+        its matrices (``instance_matrices``: the frame's own host arithmetic) and the level-0 frame (idx0, depth0) that
+        ``render(total_m, W, H, ...)`` wrote with them, by reference -> ``FrameState``.  No device work."""
+        from . import flow as fl
+        M0 = _host_f32(total_m).reshape(-1, 16)
+        if M0.shape[0] != 1:
+            raise NotImplementedError(f"more than one camera ({M0.shape[0]}) with frame_state: an edited frame has one")
+        W, H = int(W), int(H)
+        for name, t, dt in (("idx0", idx0, torch.int32), ("depth0", depth0, torch.float32)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dt and t.numel() == W * H and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} CUDA tensor of {H}x{W} pixels")
+        if self._inst is None:
+            return fl.FrameState(self, M0[0], [], [], np.zeros((0, 16), np.float32), [], W, H, idx0, depth0)
+        lst = self._instance_list()
+        return fl.FrameState(self, M0[0], list(self._inst.keys()), [k for k, _, _ in lst], self.instance_matrices(M0[0]),
+                             [v for _, _, v in lst], W, H, idx0, depth0)
+
+    def flow(self, a, b):
+        """Frame flow from ``FrameState`` a to b, both this rasteriser's: -> ``FrameFlow`` — per pixel of a's frame the motion of
+        its surface point to b's frame, its depth there and whether it is still seen (visible / occluded / off_image / clipped /
+        hidden), per instance the counts.  B's instances are matched to A's list positions by handle; a handle removed since A is
+        hidden in B.  ValueError when the states come from different rasterisers or the pool or object count changed between
+        them.  Stream-ordered; ``FrameFlow.check()`` tells whether frame A and its list belonged together."""
+        from . import flow as fl
+        if a.raster is not self or b.raster is not self:
+            raise ValueError("flow: the two frame states come from different rasterisers (this one made "
+                             f"{'neither' if a.raster is not self and b.raster is not self else 'only one'} of them)")
+        return fl.flow_between(a, b)
+
     def _outputs(self, B, W, H, levels, want_depth, out):
         """The level lists (idx, depth | None) of a frame — fresh ones, or the caller's ``out`` — and the host arrays of their
         device pointers."""

@@ -589,6 +589,41 @@ class Scene:
         idx, dep = raster.render(M, W, H, 1)
         return raster.annotate(M[0], W, H, idx[0], dep[0])
 
+    # ---- frame flow: per-pixel motion between two edited frames (read_amd/flow.py) ---------------------------
+    def capture_frame(self, viewport_size, level=0):
+        """Extension: render level 0 with depth of the current camera and edits through the live rasteriser into tensors of its own
+        and snapshot it with the instance list -> a ``flow.FrameState`` for ``flow_between``.  Pinhole frames of the 1-px point-id
+        raster only."""
+        if self.xyz is None:
+            raise ValueError("scene has no point cloud (set_vertices)")
+        if self.panorama is not None:
+            raise NotImplementedError("a panorama camera (set_panorama) with capture_frame: the flow re-projects with the pinhole "
+                                      "projection")
+        if self.lens is not None:
+            raise NotImplementedError("a lens camera (set_lens) with capture_frame: the flow re-projects with the pinhole projection")
+        if self.augmented():
+            raise NotImplementedError("GL-twin augmentation (point sizes, discard, drop, perturb) with capture_frame: the flow "
+                                      "describes the 1-px point-id frame")
+        if int(level) != 0:
+            raise NotImplementedError(f"level {int(level)} with capture_frame: levels above 0 hold the 2x2 minima of level 0, not "
+                                      "points drawn at their own pixel")
+        W, H = int(viewport_size[0]), int(viewport_size[1])
+        raster = self.rasterizer()
+        M = self.total_matrix()
+        if M.shape[0] != 1:
+            raise NotImplementedError("more than one camera with capture_frame")
+        idx, dep = raster.render(M, W, H, 1)
+        return raster.frame_state(M[0], W, H, idx[0], dep[0])
+
+    def flow_between(self, a, b):
+        """Extension: the frame flow from ``capture_frame`` state a to state b -> a ``flow.FrameFlow``: per pixel of a's frame the
+        motion of its surface point, its depth in b and whether it is still seen; per instance the counts
+        (``annotation_handle`` maps the scene's handles).  Camera moves, poses, visibility, added and removed instances between
+        the two captures are followed; what rebuilds the rasteriser (new labels, a new cloud, a new foreign object) is refused
+        with ValueError."""
+        from . import flow as fl
+        return fl.flow_between(a, b)
+
 
 class StitchedScene:
     """Extension (not in NNScene): several ``Scene`` objects ("parts", 1..8) drawn into one frame — scene stitching
@@ -699,6 +734,14 @@ class StitchedScene:
 
     def total_matrix(self):
         return self.scenes[0].total_matrix()
+
+    def capture_frame(self, *args, **kwargs):
+        raise NotImplementedError("capture_frame on a StitchedScene: instances belong to a part and the merged frame carries "
+                                  "stitched ids; take the flow of the parts' own frames")
+
+    def flow_between(self, *args, **kwargs):
+        raise NotImplementedError("flow_between on a StitchedScene: instances belong to a part and the merged frame carries "
+                                  "stitched ids; take the flow of the parts' own frames")
 
     def annotate_frame(self, *args, **kwargs):
         raise NotImplementedError("annotate_frame on a StitchedScene: instances belong to a part and the merged frame carries "
