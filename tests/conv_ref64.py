@@ -102,6 +102,17 @@ bilinear_up4_kernel (`bilinear_up4_bound`).  The weights ly0, ly1, lx0, lx1 are 
 per axis.  o = ly0 (lx0 v00 + lx1 v01) + ly1 (lx0 v10 + lx1 v11) without any contraction: each product lx v one rounding and their sum
 one: 2 u (lx0 |v00| + lx1 |v01|); the product with ly one more: 3 u; the final sum u |o| <= u sum w |v|: 4 u sum w |v| (an fma in
 the place of a product and a sum only removes roundings).  A constant image of 1.0 comes back exactly: the products k / 8 are exact and sum to 1.
+CLASS (e): DEGENERATE SIZES (`SHAPES_E_*`, `degenerate_positions`, `degenerate_images`).  The library accepts every viewport that is a
+positive multiple of 16; at 16 x 16 the four UNet levels are 16 x 16, 8 x 8, 4 x 4 and 2 x 2.  Class (e) holds every family to the same
+measure and the same derived bounds at those levels and below: an image smaller than one 8 x 32 unit / 4 x 4 tile / 4-pixel segment in
+both directions, a stride-2 parity plane of one pixel, a nearest-resampled source or an addend of 2 x 2 or a single pixel, a 6 x 6
+Winograd patch that is halo on all four sides.  No term of the bounds depends on the image size: A, A_w, A_in, X1, W1 are sums over the
+taps INSIDE the image (a tap outside loads zero and has no pieces to lose), so a corner output of a constant-1 image sees 4 taps, an
+edge 6 and the interior 9 in the reference and in the bound alike, and a halo mistake is an error of order 1 against a bound of order
+1e-6.  Inputs per shape: unit scale (with a residual where the family takes one, ELU alternating), a constant 1, a checkerboard, and
+impulses of 1 and 2^-10 at every pixel where H W <= 16 (else the corners, the mid-edges and the centre) in channels 1 % C and C - 1.
+The caps of class (e) are measured as the others are (C_MEASURED), but over a handful of pixels the oracle's own R is noisy: they are
+set per family and mode from the class (e) rows of profiles/conv_accuracy_fp64.md and apply where R_max >= 1 only.
 """
 import numpy as np
 import torch
@@ -123,13 +134,15 @@ SECOND_ORDER = 1.0 + 2.0 ** -10
 # seeds, not by a factor.  Winograd (w4h): E against A_w (module docstring).  The d3h / d3h_s2 / w4h kernels have no linear launches;
 # the NumPy restatements of their pre-activations (tests/test_conv_accuracy_cpu.py) are held to the pxh kernel's linear row — the same
 # three-piece-pair arithmetic, measured without an epilogue.
-C_MEASURED = {"d3h": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}}, "d3h_s2": {"gated": {"a": 4.0, "b": 8.0, "c": 16.0, "d": 8.0}}, "pxh": {"gated": {"a": 4.0, "b": 4.0, "c": 8.0, "d": 4.0}, "linear": {"a": 4.0, "b": 2.0, "c": 2.0, "d": 1.0}}, "t3h": {"gated": {"a": 4.0, "b": 2.0, "c": 16.0, "d": 8.0}, "linear": {"a": 4.0, "b": 8.0, "c": 2.0, "d": 2.0}}, "w4h": {"gated": {"a": 1.0, "b": 8.0, "c": 16.0, "d": 8.0}},
-              "f4x1": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0}},      # f4x1: E against A_w, as w4h
+C_MEASURED = {"d3h": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0, "e": 32.0}}, "d3h_s2": {"gated": {"a": 4.0, "b": 8.0, "c": 16.0, "d": 8.0, "e": 32.0}}, "pxh": {"gated": {"a": 4.0, "b": 4.0, "c": 8.0, "d": 4.0, "e": 8.0}, "linear": {"a": 4.0, "b": 2.0, "c": 2.0, "d": 1.0, "e": 4.0}}, "t3h": {"gated": {"a": 4.0, "b": 2.0, "c": 16.0, "d": 8.0, "e": 16.0}, "linear": {"a": 4.0, "b": 8.0, "c": 2.0, "d": 2.0, "e": 4.0}}, "w4h": {"gated": {"a": 1.0, "b": 8.0, "c": 16.0, "d": 8.0, "e": 32.0}},
+              "f4x1": {"gated": {"a": 4.0, "b": 16.0, "c": 16.0, "d": 8.0, "e": 32.0}},      # f4x1: E against A_w, as w4h
               # pxh_pre: gated_conv_pxh_kernel with a pre-activation addend; chain: the six launches of the AFF chain against the unsplit layer;
               # sc: gated_conv_smallc_kernel (the output head)
-              "pxh_pre": {"gated": {"a": 4.0, "b": 16.0, "c": 8.0, "d": 4.0}, "linear": {"a": 2.0, "b": 4.0, "c": 1.0, "d": 4.0}},      # (linear (c): R_max < 1 on every case)
-              "chain": {"gated": {"a": 2.0, "b": 4.0}, "linear": {"a": 4.0, "b": 8.0}},
-              "sc": {"gated": {"a": 4.0, "b": 4.0, "c": 4.0, "d": 16.0}}}
+              "pxh_pre": {"gated": {"a": 4.0, "b": 16.0, "c": 8.0, "d": 4.0, "e": 8.0}, "linear": {"a": 2.0, "b": 4.0, "c": 1.0, "d": 4.0}},      # (linear (c): R_max < 1 on every case)
+              "chain": {"gated": {"a": 2.0, "b": 4.0, "e": 4.0}, "linear": {"a": 4.0, "b": 8.0, "e": 4.0}},
+              # class (e) only: the two other forms of the F(4,3)-by-rows kernel, forced (the bits of f4x1: the same rows, the same cap)
+              "f4x1_pair": {"gated": {"e": 32.0}}, "f4x1_wide": {"gated": {"e": 32.0}},
+              "sc": {"gated": {"a": 4.0, "b": 4.0, "c": 4.0, "d": 16.0, "e": 8.0}}}
 
 
 def measured_cap(family, mode, cls):
@@ -149,6 +162,23 @@ def k_blocks(family, cin, k):
     if family in ("w4h", "f4x1"):
         return cin // 32
     raise ValueError(family)
+
+
+_FILTER_MEMO = {}
+
+
+def filter_memo(w, tag, fn, also=()):
+    """fn(w) for a weight array, kept for the last few arrays: the filter-side transforms of a 256 -> 256 layer cost more than
+    everything else of a case on a 2 x 2 image, and the cases of one shape share their layer.  Keyed by the IDENTITY of w and of every
+    array in `also` (what fn reads besides w), which the memo keeps alive.  The arrays must not be edited in place after their first
+    use here — the memo cannot see that; the generators of this module finish a layer before they hand it out."""
+    key = (id(w), tag) + tuple(id(a) for a in also)
+    hit = _FILTER_MEMO.get(key)
+    if hit is None or hit[0] is not w or any(x is not y for x, y in zip(hit[1], also)):
+        while len(_FILTER_MEMO) >= 16:
+            _FILTER_MEMO.pop(next(iter(_FILTER_MEMO)))
+        hit = _FILTER_MEMO[key] = (w, tuple(also), fn(w))
+    return hit[2]
 
 
 # ------------------------------------------------------------------------------------------ reference
@@ -279,7 +309,7 @@ def wino_terms(L, x, which):
     B64, A64 = BT.astype(np.float64), AT.astype(np.float64)
     V = np.abs(np.einsum("ia,ctuab,jb->tuijc", B64, d, B64, optimize=True))
     Vin = np.einsum("ia,ctuab,jb->tuijc", np.abs(B64), np.abs(d), np.abs(B64), optimize=True)
-    Uabs = np.ascontiguousarray(np.abs(np.einsum("ia,ocab,jb->ijco", G, w, G)))
+    Uabs = filter_memo(L["w" + which], "wino", lambda a: np.ascontiguousarray(np.abs(np.einsum("ia,ocab,jb->ijco", G, np.asarray(a, np.float64), G))))
 
     def per_frequency(Vt):                                                                       # sum_c |V_c| |U_c|: one matrix product per frequency
         Vf = np.ascontiguousarray(Vt.transpose(2, 3, 0, 1, 4)).reshape(6, 6, ty * tx, cin)
@@ -303,7 +333,7 @@ def preact_bound_wino(L, x, ref, which):
     Aw, Ain, V1, U1 = wino_terms(L, x, which)
     w = L["w" + which]
     n = 12 + 3 * k_blocks("w4h", w.shape[1], 3) + 6
-    inv_s = wino_filter_inv_scale(w)[:, None, None]
+    inv_s = filter_memo(w, "wino 1/s", wino_filter_inv_scale)[:, None, None]
     val = np.abs(ref.f if which == "f" else ref.m)
     return U * (n * Aw + 4 * Ain + val) + W_FLOOR * inv_s * V1 + X_FLOOR * U1 + TINY, Aw
 
@@ -326,7 +356,7 @@ def f4x1_terms(L, x, which):
     cout, cin = w.shape[:2]
     _, H, W = x.shape
     nt = (W + 3) // 4
-    Uabs = np.ascontiguousarray(np.abs(np.einsum("fb,ocab->faco", G.astype(np.float64), w)))      # [fq][ky][cin][co]
+    Uabs = filter_memo(L["w" + which], "f4x1", lambda a: np.ascontiguousarray(np.abs(np.einsum("fb,ocab->faco", G.astype(np.float64), np.asarray(a, np.float64)))))   # [fq][ky][cin][co]
     absAT = np.abs(AT).astype(np.float64)
     inside = np.array([[0 <= y + ky - 1 < H for ky in range(3)] for y in range(H)], np.float64)   # (y, ky): the tap's row is in the image
     out = []
@@ -353,7 +383,7 @@ def preact_bound_f4x1(L, x, ref, which):
     Aw, Ain, V1, U1 = f4x1_terms(L, x, which)
     w = L["w" + which]
     n = 12 + 9 * k_blocks("f4x1", w.shape[1], 3) + 3
-    inv_s = f4x1_filter_inv_scale(w)[:, None, None]
+    inv_s = filter_memo(w, "f4x1 1/s", f4x1_filter_inv_scale)[:, None, None]
     val = np.abs(ref.f if which == "f" else ref.m)
     return U * (n * Aw + 2 * Ain + val) + W_FLOOR * inv_s * V1 + 2 * X_FLOOR * U1 + TINY, Aw
 
@@ -684,3 +714,48 @@ def f4x1_range_edge(cin, H, W, row=0, segment=1, amp=6550.0):
     x = np.zeros((cin, H, W), np.float32)
     x[:, :, 4 * segment - 1:4 * segment + 5] = (np.sign(BT[row]).astype(np.float32) * np.float32(amp))[None, None, :]
     return x
+
+
+# ------------------------------------------------------------------------------------------ class (e): degenerate sizes
+# (C, H, W) of the 3x3 / stride-1 C -> C families: the plan's own levels at a 16 x 16 viewport (32 x 16 x 16 ... 256 x 2 x 2), their
+# 16 x 48 / 48 x 16 neighbours, and smaller: one pixel, one row, one column, one pixel more than a unit's width, two columns.
+SHAPES_E_S1 = [(256, 2, 2), (256, 2, 6), (256, 6, 2), (128, 4, 4), (128, 4, 12), (128, 1, 1), (64, 8, 8), (64, 1, 7), (64, 7, 1), (64, 3, 5),
+               (32, 16, 16), (32, 2, 33), (32, 9, 2)]
+# (cin, cout, k, input H, W) of the stride-2 family: every output is non-empty (k3: ((H - 1) >> 1) + 1, k4: H >> 1)
+SHAPES_E_S2 = [(32, 64, 3, 16, 16), (32, 64, 3, 2, 2), (32, 64, 3, 1, 1), (32, 64, 3, 3, 3), (32, 64, 3, 2, 6), (64, 128, 3, 8, 8), (64, 128, 3, 1, 5),
+               (128, 256, 3, 4, 4), (128, 256, 3, 2, 2), (256, 128, 4, 2, 2), (256, 128, 4, 2, 6), (128, 64, 4, 4, 4), (64, 32, 4, 8, 8), (64, 32, 4, 2, 2)]
+SHAPES_E_PXH = [([256], 256), ([128, 128], 128), ([8, 56], 64)]           # (sources, cout) at SIZES_E_PXH
+SIZES_E_PXH = [(1, 1), (2, 2), (2, 6), (4, 4), (7, 1)]
+SHAPES_E_T3H = [(8, 32), (8, 16)]                                          # (cin, cout) at SIZES_E_T3H
+SIZES_E_T3H = [(1, 1), (2, 2), (2, 6), (16, 16), (5, 1)]
+SIZES_E_SC = [(1, 1), (2, 2), (16, 16), (7, 33), (16, 1)]                  # the 32 -> 3 head
+# SHAPES_RESAMPLED's first layout at outputs whose coarse source is 2 x 2 / one pixel (the fine one 8 x 8 / 4 x 4)
+SHAPES_E_RESAMPLED = [([32, 64, 128], (1, 0, -1), 64, 4, 4), ([32, 64, 128], (1, 0, -1), 64, 2, 2)]
+# the three AFF layouts of SHAPES_PRE at outputs 2 x 2, 4 x 4, 8 x 8: the addend, one level coarser, has 1, 2 and 4 rows
+LAYOUTS_E_PRE = [([32], (0,), 32, 64, 0, 32, 1), ([32, 64], (1, 0), 64, 192, 32, 128, 1), ([32, 64, 128], (2, 1, 0), 128, 448, 96, 320, 1)]
+SIZES_E_PRE = [(2, 2), (4, 4), (8, 8)]
+SIZES_E_CHAIN = ((16, 16), (8, 8), (4, 4), (2, 2))                         # res1, res2, res3, z of a 16 x 16 viewport
+
+
+def degenerate_positions(H, W):
+    """(y, x) of the impulses of class (e): every pixel where H W <= 16, else the four corners, the mid-edges and the centre.  A list
+    of its own: impulse_positions assumes an image that holds the patch of tile (1, 1)."""
+    if H * W <= 16:
+        return [(y, x_) for y in range(H) for x_ in range(W)]
+    pos = [(0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1), (0, W // 2), (H - 1, W // 2), (H // 2, 0), (H // 2, W - 1), (H // 2, W // 2)]
+    return list(dict.fromkeys(pos))
+
+
+def degenerate_images(cin, H, W, seed):
+    """The inputs of class (e) at one shape: (name, x (cin, H, W) float32, elu, unit_scale).  Unit scale, a constant 1, a checkerboard,
+    impulses of 1 and 2^-10 at degenerate_positions in channels 1 % cin and cin - 1; ELU alternates over the list."""
+    rng = np.random.default_rng([seed, cin, H, W])
+    yield "unit scale", rng.standard_normal((cin, H, W)).astype(np.float32), seed % 2 == 0, True
+    yield "constant 1", constant_image(cin, H, W), True, False
+    yield "checkerboard +-1", checkerboard(cin, H, W), False, False
+    j = 0
+    for amp in (1.0, 2.0 ** -10):
+        for c in dict.fromkeys((1 % cin, cin - 1)):
+            for (y, x_) in degenerate_positions(H, W):
+                yield f"impulse {amp:g} at c{c} ({y},{x_})", impulse(cin, H, W, c, y, x_, amp), j % 2 == 0, False
+                j += 1

@@ -12,13 +12,16 @@ from tests.d3h_ref import pack_d1h_blob, pack_d3h_blob, split_conv_model, split_
 
 
 # ------------------------------------------------------------------------------------------ plumbing
-def im2col(x_chw, k, stride):
-    """-> (outH, outW, k k Cin), index tap * Cin + ci (the order of read_conv_pack_t3h_host), zero padding (k - 1) // 2."""
+def im2col(x_chw, k, stride, clamped=False):
+    """-> (outH, outW, k k Cin), index tap * Cin + ci (the order of read_conv_pack_t3h_host), zero padding (k - 1) // 2.  clamped: a
+    seeded defect — the border taken by clamping the coordinate instead of padding with zeros."""
     cin, H, W = x_chw.shape
     pad = (k - 1) // 2
     oh, ow = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     xp = np.zeros((cin, H + 2 * pad + stride, W + 2 * pad + stride), np.float32)
     xp[:, pad:pad + H, pad:pad + W] = x_chw
+    if clamped:
+        xp = np.pad(x_chw, ((0, 0), (pad, pad + stride), (pad, pad + stride)), mode="edge").astype(np.float32)
     taps = [xp[:, ky:ky + stride * oh:stride, kx:kx + stride * ow:stride] for ky in range(k) for kx in range(k)]
     return np.ascontiguousarray(np.concatenate(taps, 0).transpose(1, 2, 0))
 
@@ -60,13 +63,20 @@ def split_model(cols, w2, defect=None):
         return (out * np.ldexp(1.0, -ex)[None, None, :]).astype(np.float32)
 
 
+GEOMETRY_DEFECTS = ("border_clamped", "ragged_unwritten")      # of the launch around the arithmetic: class (e) must catch them
+
+
 def run_direct(L, x, k, stride, family, model=split_model, defect=None, cls="a"):
-    """One layer's pre-activations [f | m] through a model -> dict of E, R, the worst err / derived bound, finiteness."""
+    """One layer's pre-activations [f | m] through a model -> dict of E, R, the worst err / derived bound, finiteness.  The defects of
+    GEOMETRY_DEFECTS leave the arithmetic alone: the border by clamping; the outputs of a ragged last 4 x 4 tile left as they were
+    (R64.SENTINEL, what the tests fill an output with)."""
     ref = R64.reference(L, x, stride=stride)
-    cols = im2col(x, k, stride)
-    kw = {} if defect is None else {"defect": defect}
+    cols = im2col(x, k, stride, clamped=defect == "border_clamped")
+    kw = {} if defect is None or defect in GEOMETRY_DEFECTS else {"defect": defect}
     got = [(model(cols, w_matrix(L["w" + fm]), **kw) + L["b" + fm][None, None, :]).transpose(2, 0, 1) for fm in "fm"]
     got = np.concatenate(got)
+    if defect == "ragged_unwritten":
+        got[:, got.shape[1] // 4 * 4:], got[:, :, got.shape[2] // 4 * 4:] = R64.SENTINEL, R64.SENTINEL
     finite = bool(np.isfinite(got).all())
     bound = np.concatenate([R64.preact_bound_direct(L, ref, family, fm) for fm in "fm"])
     err = np.abs(np.nan_to_num(got.astype(np.float64), nan=1e300, posinf=1e300, neginf=-1e300) - np.concatenate([ref.f, ref.m]))
@@ -274,8 +284,12 @@ def run_wino(L, x, halfs_edit=None, cls="a"):
     cout, cin = L["wf"].shape[:2]
     cp = (cout + 31) // 32 * 32
     wf, wm = np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"])
-    blob = np.zeros(_lib.lib().read_conv_w4h_floats(cin, cout), np.float32)
-    assert _lib.lib().read_conv_pack_w4h_host(cin, cout, wf.ctypes.data, wm.ctypes.data, blob.ctypes.data) == 0
+    def pack(_):
+        blob = np.zeros(_lib.lib().read_conv_w4h_floats(cin, cout), np.float32)
+        assert _lib.lib().read_conv_pack_w4h_host(cin, cout, wf.ctypes.data, wm.ctypes.data, blob.ctypes.data) == 0
+        return blob
+
+    blob = R64.filter_memo(L["wf"], "w4h blob", pack, also=(L["wm"],))   # (the cases of one class (e) shape share their layer)
     halfs = blob[:-2 * cp].view(np.float16).reshape(cp // 32, 4, cin // 32, 36, 2, 64, 8).copy()
     inv = blob[-2 * cp:].reshape(2, cp).copy()
     if halfs_edit is not None:
@@ -358,7 +372,7 @@ def run_f4x1(L, x, halfs_edit=None, cls="a"):
     run_wino: E against the transformed-domain condition term A_w, (EA) against A; `got` = [f | m] for the checks that look at elements."""
     from tests import test_f4x1_model as F4
     cout, cin = L["wf"].shape[:2]
-    halfs, inv = F4.pack_f4x1(np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"]))
+    halfs, inv = R64.filter_memo(L["wf"], "f4x1 blob", lambda _: F4.pack_f4x1(np.ascontiguousarray(L["wf"]), np.ascontiguousarray(L["wm"])), also=(L["wm"],))
     halfs, inv = halfs.copy(), inv.copy()
     if halfs_edit is not None:
         halfs_edit(halfs, inv)
@@ -714,3 +728,107 @@ def test_oracle_stays_inside_the_derived_bound_on_every_new_gpu_case():
             worst[("chain", cls)] = max(worst.get(("chain", cls), 0.0), q)
             assert q <= 1.0, ("chain", cls, name, q)
     print("oracle err / derived bound, worst per family and class: " + "  ".join("%s (%s) %.3f" % (f, c, q) for (f, c), q in sorted(worst.items())))
+
+
+# ------------------------------------------------------------------------------------------ class (e): degenerate sizes
+def degenerate_direct_cases():
+    """(family, k, stride, L, name, x, (outH, outW)) over the class (e) shapes of the direct split-operand families."""
+    for j, (c, H, W) in enumerate(R64.SHAPES_E_S1):
+        L = R64.tame_layer(c, c, 3, 1100 + j)
+        for name, x, _, _ in R64.degenerate_images(c, H, W, 1100 + j):
+            yield "d3h", 3, 1, L, f"{c} {H}x{W} {name}", x
+    for j, (cin, cout, k, H, W) in enumerate(R64.SHAPES_E_S2):
+        L = R64.tame_layer(cin, cout, k, 1200 + j)
+        for name, x, _, _ in R64.degenerate_images(cin, H, W, 1200 + j):
+            yield "d3h_s2", k, 2, L, f"{cin}->{cout} k{k}s2 {H}x{W} {name}", x
+    for family, layers in (("pxh", [(sum(s), co, 1, R64.SIZES_E_PXH) for s, co in R64.SHAPES_E_PXH]), ("t3h", [(ci, co, 3, R64.SIZES_E_T3H) for ci, co in R64.SHAPES_E_T3H])):
+        for j, (cin, cout, k, sizes) in enumerate(layers):
+            L = R64.tame_layer(cin, cout, k, 1300 + j)
+            for (H, W) in sizes:
+                for name, x, _, _ in R64.degenerate_images(cin, H, W, 1300 + j):
+                    yield family, k, 1, L, f"{cin}->{cout} {H}x{W} {name}", x
+
+
+def test_direct_split_models_on_degenerate_sizes():
+    """Class (e) (tests/conv_ref64.py): the three-piece-pair arithmetic at 16 x 16 down to 1 x 1, every shape and input the GPU test
+    runs, inside the derived bound, finite, exact zeros — the references and the bounds are right there before any kernel is blamed."""
+    worst = {}
+    for family, k, stride, L, name, x in degenerate_direct_cases():
+        s = run_direct(L, x, k, stride, family, model=split_conv_model_taps, cls="e")
+        worst[family] = max(worst.get(family, 0.0), s["q"])
+        assert inside_caps(s, family), (family, name, s)
+    print("class (e), direct split models, worst err / bound: " + "  ".join("%s %.3f" % kv for kv in sorted(worst.items())))
+
+
+@pytest.mark.parametrize("defect", GEOMETRY_DEFECTS)
+def test_geometry_defects_exceed_the_bound_on_degenerate_sizes(defect):
+    """The border by clamping instead of zero padding; the outputs of a ragged last 4 x 4 tile left unwritten.  On every class (e) shape
+    of the 3x3 / 4x4 families that has a border tap / a ragged tile, the unit-scale case, the constant and the checkerboard must each
+    exceed the caps (on a constant 1 a corner sees 9 taps where 4 are due: an error of order 1), and so must an impulse on a border
+    pixel / every impulse; the intact model stays inside them (the test above)."""
+    seen = 0
+    for family, k, stride, L, name, x in degenerate_direct_cases():
+        if k == 1 or x.shape[0] > 64:                                      # (the geometry is the same at every channel count)
+            continue
+        oh, ow = (x.shape[1] + 2 * ((k - 1) // 2) - k) // stride + 1, (x.shape[2] + 2 * ((k - 1) // 2) - k) // stride + 1
+        if defect == "ragged_unwritten" and oh % 4 == 0 and ow % 4 == 0:
+            continue
+        dense = "impulse" not in name
+        if defect == "border_clamped" and not dense:
+            _, y, x_ = np.argwhere(x != 0)[0].tolist()
+            # a clamped coordinate re-reads a border pixel where a tap of some output falls outside on that side: always above and to
+            # the left (pad >= 1); below / to the right iff the last output's last tap, (o - 1) stride - pad + k - 1, passes the image —
+            # at stride 1 always, at stride 2 for some sizes only.  An impulse elsewhere (interior, or on a far border that no tap
+            # leaves) is read exactly as with zero padding: not a case of this defect.
+            pad, Hh, Ww = (k - 1) // 2, x.shape[1], x.shape[2]
+            below, right = (oh - 1) * stride - pad + k - 1 >= Hh, (ow - 1) * stride - pad + k - 1 >= Ww
+            assert stride == 2 or (below and right)
+            if not (y == 0 or x_ == 0 or (y == Hh - 1 and below) or (x_ == Ww - 1 and right)):
+                continue
+        s = run_direct(L, x, k, stride, family, model=split_conv_model_taps, defect=defect, cls="e")
+        hit = not inside_caps(s, family)
+        seen += 1
+        print("%-16s %-7s %-44s err/bound %10.3g  %s" % (defect, family, name, s["q"], "CAUGHT" if hit else "-"))
+        assert hit, (defect, family, name, s)                            # (intact: test_direct_split_models_on_degenerate_sizes)
+    assert seen > 100, seen
+
+
+def test_winograd_models_on_degenerate_sizes():
+    """The lane-exact model of gated_conv_wino4h_kernel and the model of gated_conv_f4x1h_kernel, on the library's packed operands, over
+    the 3x3 / stride-1 shapes of class (e): a 6 x 6 patch that is halo on all four sides, segments and tiles that hang over the image
+    in both directions.  F(4,3) by rows: every input of every shape.  F(4x4): the unit-scale case and the constant 1 (on which a halo
+    mistake is an error of order 1) at every shape, every input at C = 32 — the lane-exact model takes seconds per case at C = 256."""
+    worst = {"w4h": 0.0, "f4x1": 0.0}
+    for j, (c, H, W) in enumerate(R64.SHAPES_E_S1):
+        L = R64.tame_layer(c, c, 3, 1100 + j)
+        for name, x, _, _ in R64.degenerate_images(c, H, W, 1100 + j):
+            s = run_f4x1(L, x, cls="e")
+            worst["f4x1"] = max(worst["f4x1"], s["q"])
+            assert f4x1_inside_caps(s), ("f4x1", c, H, W, name, {k: v for k, v in s.items() if k != "got"})
+            if c == 32 or name in ("unit scale", "constant 1"):
+                s = run_wino(L, x, cls="e")
+                worst["w4h"] = max(worst["w4h"], s["q"])
+                assert wino_inside_caps(s), ("w4h", c, H, W, name, s)
+    print("class (e), Winograd models, worst err / bound: " + "  ".join("%s %.3f" % kv for kv in sorted(worst.items())))
+
+
+def test_launch_models_on_degenerate_sizes():
+    """pxh_launch_model on the resampled-source and addend cases of class (e) (a coarse source of 2 x 2 / one pixel, addends of one,
+    two and four rows), head_model on the head's, and the chain on the levels of a 16 x 16 viewport: inside the derived bounds."""
+    from tests import test_gpu_conv_accuracy as G
+    worst = {}
+    for group, family in (("resampled", "pxh"), ("pxh_pre", "pxh_pre"), ("sc", "sc")):
+        for cases in G.cases_e(group):
+            for case in cases:
+                ref = case.ref()
+                df, dm, _ = G._bounds(case, family)
+                H, W = case.x.shape[1:]
+                got = head_model(case.L, case.x).transpose(1, 2, 0) if family == "sc" else pxh_launch_model(case.L, list(zip(case.xs, case.shifts)), H, W, case.pre)
+                q = _q(got, np.concatenate([ref.f, ref.m]), np.concatenate([df, dm]))
+                worst[group] = max(worst.get(group, 0.0), q)
+                assert q <= 1.0, (group, case.name, q)
+    for cls in "ab":
+        q = chain_q(*chain_inputs(cls, R64.SIZES_E_CHAIN))
+        worst["chain " + cls] = max(q.values())
+        assert max(q.values()) <= 1.0, (cls, q)
+    print("class (e), launch models, worst err / bound: " + "  ".join("%s %.3f" % kv for kv in sorted(worst.items())))

@@ -28,6 +28,8 @@ FAMILY_ID / FORCE; derivations in tests/conv_ref64.py):
   * the output head gated_conv_smallc_kernel (SHAPES_SC, config -6, family 1), with and without ELU, and its fill channel;
   * bilinear_up4_kernel against a float64 restatement of the formula (SHAPES_UP4).
 Every pxh launch of these runs forced (config -10) and automatic (-1) and must report family 7.
+Class (e), degenerate sizes: every family above — and the pair and wide forms of the F(4,3)-by-rows kernel — at the plan's levels of a
+16 x 16 viewport and below, forced and automatic, every launch also inside guard bands (the section at the end of this file).
 Run with -s to see the table; lines start with "ACC|"."""
 import ctypes
 
@@ -46,6 +48,10 @@ FORCE = {"w4h": -7, "f4x1": -12, "d3h": -8, "d3h_s2": -1, "pxh": -10, "t3h": -11
          "pxh_pre": -10, "chain": -10, "sc": -6}                                           # pxh_pre: gated_conv_pxh_kernel with an addend; chain: the six AFF launches; sc: the head
 DIRECT_FP32 = "k3s1c16_p2q1m4n1f1b2"
 FP32 = {"fp32_w4": "w4", "fp32_direct": "direct"}                                          # the fp32 kernels: family of T.conv_forward_bound
+# class (e) also forces the two other forms of the F(4,3)-by-rows kernel (tests/test_gpu_conv_f4x1_pair.py, _wide.py): the bound of f4x1
+FAMILY_ID.update(f4x1_pair=5, f4x1_wide=5)
+FORCE.update(f4x1_pair=-13, f4x1_wide=-14)
+SAME_BOUND = {"f4x1_pair": "f4x1", "f4x1_wide": "f4x1"}
 
 
 def fp32_config(family):
@@ -123,6 +129,7 @@ class Case:
 def _bounds(case, family, linear=False):
     """-> (d_f, d_m, B_w): the pre-activation bounds and, for the Winograd family, the condition term B with A_w in the place of A (a
     linear launch of the fp32 Winograd kernel: [A_w + |b_f| | A_w + |b_m|])."""
+    family = SAME_BOUND.get(family, family)
     if (family, linear) in case._bounds:
         return case._bounds[(family, linear)]
     if family not in case._bounds:
@@ -431,8 +438,14 @@ def test_aff_chain_against_fp64(hip, cls):
     """The six launches of the default plan's AFF chain (R64.AFF_PLAN: q3 -> q2 -> AFF2 -> q1 -> AFF1 -> AFF0) on res1 32 x 20 x 36,
     res2 64 x 10 x 18, res3 128 x 5 x 9, z 256 x 3 x 5: each of q3, q2, q1 and each gated output against the float64 reference of the UNSPLIT
     layer on assemble(...) and the bound composed level by level; config -10 and -1, every launch family 7."""
+    _aff_chain(cls, R64.aff_chain_inputs(cls), cls, "")
+
+
+def _aff_chain(cls, inputs, row_cls, tag, guarded=False, rows=None, assert_caps=True):
+    """The chain on `inputs` = (layers, sources), judged as class `row_cls`.  guarded: every launch a second time with its sources and
+    its addend inside NaN bands and its output inside sentinel bands (class (e), `Guarded`): the same bits, untouched bands."""
     from read_amd import _lib
-    layers, xs = R64.aff_chain_inputs(cls)
+    layers, xs = inputs
     refs = R64.aff_chain_reference(layers, xs)
     for cfg in (FORCE["chain"], -1):
         fams = {}
@@ -444,6 +457,13 @@ def test_aff_chain_against_fp64(hip, cls):
             fams[name] = _lib.lib().read_conv_kernel_family(ctypes.byref(conv_desc(pk, srcs_d, **kw)))
             out = gated_conv(pk, srcs_d, **kw)
             assert tuple(out.shape[:2]) == tuple(hw), (name, out.shape, hw)
+            if guarded:
+                g = Guarded()
+                kw_g = dict(kw, pre=None if pre is None else (g.input(pre[0]),) + tuple(pre[1:]), out=g.output(tuple(out.shape)))
+                gated_conv(pk, [(g.input(t), s) for t, s in srcs_d], **kw_g)
+                torch.cuda.synchronize()
+                bad = g.problems(out)
+                assert not bad, f"{name} of the chain {tag} config {cfg}: {bad}"
             return out
 
         outs = R64.run_aff_chain(layers, xs, launch)
@@ -451,8 +471,8 @@ def test_aff_chain_against_fp64(hip, cls):
         for name, (ref, df, dm, Lfull, xfull) in refs.items():
             linear = name.startswith("q")
             got = outs[name].cpu().numpy().transpose(2, 0, 1)
-            judge(Lfull, ref, got, R64.oracle_fp32(Lfull, xfull, linear=linear), fams[name], df, dm, None, "chain", cls,
-                  f"{name} of the chain ({'tame' if cls == 'a' else 'checkpoint-like'})", cfg, linear=linear)
+            judge(Lfull, ref, got, R64.oracle_fp32(Lfull, xfull, linear=linear), fams[name], df, dm, None, "chain", row_cls,
+                  f"{name} of the chain ({'tame' if cls == 'a' else 'checkpoint-like'}){tag}", cfg, linear=linear, rows=rows, assert_caps=assert_caps)
 
 
 # ------------------------------------------------------------------------------------------ the output head and the up-sampling
@@ -726,3 +746,238 @@ def test_unet_with_checkpoint_like_statistics_against_fp64(hip):
         assert kinds.count(5) >= 70, kinds                                          # the residual blocks run on the Winograd split-operand kernels
         got = eng.forward(*[x.cuda() for x in xs]).permute(2, 0, 1).cpu()
         _check_rgb(got, ref, "checkpoint-like statistics against fp64, inner maximum %g" % target)
+
+
+# ------------------------------------------------------------------------------------------ class (e): degenerate sizes
+# Every family at the plan's own levels of a 16 x 16 viewport and below (tests/conv_ref64.py, "Class (e)": the shapes, the inputs, why
+# the bounds hold unchanged).  Each launch runs twice: on plainly allocated tensors, and with every tensor it reads inside NaN bands
+# and the one it writes inside sentinel bands (GUARD floats before and after, tests/train_fp32.py) — the same bits, a finite result,
+# untouched bands: a load past a tensor's end may be masked before arithmetic, it may not reach it.  include/read_hip.h documents no
+# slack that a caller owes, so none is given.  GUARD floats are 256 bytes: the views keep the alignment of the allocation.
+from tests.train_fp32 import GUARD, SENTINEL as BAND          # noqa: E402
+
+
+class Guarded:
+    """The tensors of one guarded launch."""
+
+    def __init__(self):
+        self.ins, self.out_flat, self.out = [], None, None
+
+    def input(self, t):
+        """A device or host array -> an equal view inside a NaN-filled flat buffer with GUARD floats on either side."""
+        t = torch.as_tensor(t).cuda()
+        flat = torch.full((t.numel() + 2 * GUARD,), float("nan"), device="cuda")
+        view = flat[GUARD:GUARD + t.numel()].view(t.shape)
+        view.copy_(t)
+        self.ins.append((flat, view, t.clone()))
+        return view
+
+    def output(self, shape):
+        n = int(np.prod(shape))
+        self.out_flat = torch.full((n + 2 * GUARD,), float(BAND), device="cuda")
+        self.out = self.out_flat[GUARD:GUARD + n].view(shape)
+        return self.out
+
+    def problems(self, plain_out):
+        """-> what went wrong, as a list of strings: a band written, an input changed, a non-finite output, other bits than `plain_out`."""
+        bad = []
+        if not bool((self.out_flat[:GUARD] == float(BAND)).all() and (self.out_flat[-GUARD:] == float(BAND)).all()):
+            bad.append("wrote into the band around its output")
+        for flat, view, orig in self.ins:
+            if not bool(torch.isnan(flat[:GUARD]).all() and torch.isnan(flat[-GUARD:]).all() and torch.equal(view.view(torch.int32), orig.view(torch.int32))):
+                bad.append("changed an input or its band")
+        if not bool(torch.isfinite(self.out).all()):
+            bad.append("a load outside a tensor reached the arithmetic: non-finite output")
+        if plain_out is not None and not torch.equal(self.out.view(torch.int32), plain_out.view(torch.int32)):
+            bad.append("other bits than on plainly allocated tensors")
+        return bad
+
+
+_PACKS = {}
+
+
+def _pack_once(L, split):
+    key = (id(L), tuple(split))
+    if key not in _PACKS:
+        _PACKS[key] = (L, _pack(L, list(split)))              # (L is kept alive: its id is the key)
+    return _PACKS[key][1]
+
+
+def launch_e(case, config, linear=False):
+    """-> (output (C or 2 C, H, W) of the guarded launch or None, kernel family, message of a refusal or None, problems)."""
+    from read_amd import _lib
+    L_ = _lib.lib()
+    pk = _pack_once(case.L, case.split)
+    hwc = lambda a: np.ascontiguousarray(np.asarray(a, np.float32).transpose(1, 2, 0))          # noqa: E731
+    offs = np.cumsum([0] + list(case.split))
+    src_np = [(hwc(x), s) for x, s in zip(case.xs, case.shifts)] if case.xs is not None else [(hwc(case.x[offs[i]:offs[i + 1]]), 0) for i in range(len(case.split))]
+    cout = case.L["wf"].shape[0]
+    cs = cout * (2 if linear else 1)
+    oh, ow = _out_hw(case.k, case.stride, case.x.shape[1], case.x.shape[2])
+    plain = None
+    for guarded in (False, True):
+        g = Guarded()
+        put = g.input if guarded else (lambda a: torch.as_tensor(a).cuda())
+        srcs = [(put(a), s) for a, s in src_np]
+        kw = dict(stride=case.stride, elu=case.elu, config=config)
+        if linear:
+            kw["linear"] = True
+        else:
+            if case.residual is not None:
+                kw["residual"] = put(hwc(case.residual))
+            if case.mul is not None:
+                kw["mul"] = put(hwc(case.mul))
+        if case.pre is not None:
+            kw["pre"] = (put(case.pre[0]),) + tuple(case.pre[1:])
+        out = g.output((oh, ow, cs))
+        d = conv_desc(pk, srcs, out=out, **kw)
+        fam = L_.read_conv_kernel_family(ctypes.byref(d))
+        f4 = getattr(pk, "wpacked_f4x1", None)
+        rc = (L_.read_gated_conv_forward_f4x1(ctypes.byref(d), f4.data_ptr(), _lib.stream_ptr()) if f4 is not None
+              else L_.read_gated_conv_forward(ctypes.byref(d), _lib.stream_ptr()))
+        msg = L_.read_last_error().decode("utf-8", "replace") if rc != 0 else None
+        torch.cuda.synchronize()
+        if rc != 0:
+            # a forced configuration "forces it where the shape fits": a refusal is READ_EINVAL with a message, before any device work
+            assert rc == -22 and msg and config != -1, f"{case.name} config {config}: return {rc}, message {msg!r}"
+            assert bool((g.out_flat == float(BAND)).all()), f"{case.name} config {config}: a refused launch wrote"
+            return None, fam, msg, []
+        if guarded:
+            return out.cpu().numpy().transpose(2, 0, 1), fam, None, g.problems(plain)
+        plain = out.clone()
+
+
+def check_e(case, config, family, linear=False, rows=None, assert_caps=True):
+    """check() for class (e): the guarded launch, judge()'s assertions, and the guard bands.  A refused forced configuration is
+    asserted to be a refusal (launch_e) and printed as one."""
+    got, fam, refusal, problems = launch_e(case, config, linear)
+    mode = "linear" if linear else "gated"
+    if refusal is not None:
+        print("ACC| %-8s | e | %-44s | %-6s | cfg %3d fam %d | REFUSED: %s" % (family, case.name, mode, config, fam, refusal))
+        if rows is not None:
+            rows.append(dict(family=family, cls="e", name=case.name, mode=mode, config=config, kernel=fam, refused=refusal))
+        return None
+    if (linear, "ora") not in case._bounds:
+        case._bounds[(linear, "ora")] = R64.oracle_fp32(case.L, case.x, stride=case.stride, elu=case.elu, residual=case.residual, mul=case.mul, linear=linear, pre=case.addend())
+    df, dm, Bw = _bounds(case, family, linear)
+    row = judge(case.L, case.ref(), got, case._bounds[(linear, "ora")], fam, df, dm, Bw, family, "e", case.name, config, linear, rows, assert_caps)
+    row["problems"] = problems
+    assert not (problems and assert_caps), f"{family} (e) {case.name} {mode} config {config}: {problems}"
+    return row
+
+
+AUTO_FAMILY = {0: "fp32_direct", 1: "sc", 4: "fp32_w4", 6: "d3h", 7: "pxh", 8: "t3h"}
+_CASES_E = {}
+
+
+def cases_e(group):
+    """The cases of one group of class (e), built once and shared by the families that run them: [[the cases of one shape, the
+    unit-scale one first]]."""
+    if group in _CASES_E:
+        return _CASES_E[group]
+    shapes = []
+    if group == "s1":
+        for j, (c, H, W) in enumerate(R64.SHAPES_E_S1):
+            L, rng = R64.tame_layer(c, c, 3, 1100 + j), np.random.default_rng([1100 + j])
+            shapes.append([Case("s1", "e", f"{c} {H}x{W} {name}", L, x, elu=elu, residual=_res(rng, c, H, W) if unit else None)
+                           for name, x, elu, unit in R64.degenerate_images(c, H, W, 1100 + j)])
+    elif group == "d3h_s2":
+        for j, (cin, cout, k, H, W) in enumerate(R64.SHAPES_E_S2):
+            L = R64.tame_layer(cin, cout, k, 1200 + j)
+            shapes.append([Case("d3h_s2", "e", f"{cin}->{cout} k{k}s2 {H}x{W} {name}", L, x, stride=2, elu=elu) for name, x, elu, _ in R64.degenerate_images(cin, H, W, 1200 + j)])
+    elif group in ("pxh", "t3h", "sc"):
+        layers = {"pxh": [(split, cout, 1, R64.SIZES_E_PXH) for split, cout in R64.SHAPES_E_PXH],
+                  "t3h": [([cin], cout, 3, R64.SIZES_E_T3H) for cin, cout in R64.SHAPES_E_T3H], "sc": [([32], 3, 3, R64.SIZES_E_SC)]}[group]
+        for j, (split, cout, k, sizes) in enumerate(layers):
+            L = R64.tame_layer(sum(split), cout, k, 1300 + j)
+            for (H, W) in sizes:
+                rng = np.random.default_rng([1300 + j, H, W])
+                shapes.append([Case(group, "e", f"{split}->{cout} {H}x{W} {name}", L, x, elu=elu, split=split, residual=_res(rng, cout, H, W) if unit and group != "sc" else None)
+                               for name, x, elu, unit in R64.degenerate_images(sum(split), H, W, 1300 + j)])
+    elif group == "resampled":
+        for j, shape in enumerate(R64.SHAPES_E_RESAMPLED):
+            split, shifts, cout, H, W = shape
+            big = max(max(shifts), 0)
+            L = R64.tame_layer(sum(split), cout, 1, 1400 + j)
+            shapes.append([Case("pxh", "e", f"resampled {split} {shifts}->{cout} {H}x{W} {name}", L, None, elu=elu, xs=R64.split_sources(xb, split, shifts, H, W), shifts=shifts)
+                           for name, xb, elu, _ in R64.degenerate_images(sum(split), H << big, W << big, 1400 + j)])
+    elif group == "pxh_pre":
+        for j, (split, shifts, cout, C, f_off, m_off, sh) in enumerate(R64.LAYOUTS_E_PRE):
+            L = R64.tame_layer(sum(split), cout, 1, 1500 + j)
+            big = max(max(shifts), 0)
+            for (H, W) in R64.SIZES_E_PRE:
+                rng = np.random.default_rng([1500 + j, H, W])
+                pre_shape = R64.addend_size(sh, H, W) + (C,)
+                flat = np.full(pre_shape, R64.SENTINEL, np.float32)                              # a constant addend: 0.5 to f, -0.25 to m
+                flat[..., f_off:f_off + cout], flat[..., m_off:m_off + cout] = 0.5, -0.25
+                tag = f"{split}->{cout} {H}x{W} addend C={C}>>{sh}"
+                mk = lambda name, xs, t, elu: Case("pxh_pre", "e", f"{tag} {name}", L, None, elu=elu, xs=xs, shifts=shifts, pre=(t, f_off, m_off, sh))   # noqa: E731
+                cases = [mk(name, R64.split_sources(xb, split, shifts, H, W), R64.addend_tensor(rng, pre_shape, f_off, m_off, cout) if unit else flat, elu)
+                         for name, xb, elu, unit in R64.degenerate_images(sum(split), H << big, W << big, 1500 + j)]
+                zeros = [np.zeros((c,) + hw, np.float32) for c, hw in zip(split, R64.source_sizes(shifts, H, W))]
+                for amp in (1.0, 2.0 ** -10):                                                    # single addend elements over a zero image
+                    for (py, px) in R64.degenerate_positions(*pre_shape[:2]):
+                        for off, br in ((f_off, "f"), (m_off, "m")):
+                            for c in dict.fromkeys((1 % cout, cout - 1)):
+                                t = np.full(pre_shape, R64.SENTINEL, np.float32)
+                                t[..., f_off:f_off + cout], t[..., m_off:m_off + cout] = 0.0, 0.0
+                                t[py, px, off + c] = amp
+                                cases.append(mk(f"x = 0, addend {amp:g} at ({py},{px}) {br}{c}", zeros, t, True))
+                shapes.append(cases)
+    else:
+        raise ValueError(group)
+    _CASES_E[group] = shapes
+    return shapes
+
+
+# what runs each group: (family whose bound and cap apply, forced configuration or None: the fp32 kernels' own, linear launches too)
+RUNS_E = {"w4h": ("s1", False), "f4x1": ("s1", False), "f4x1_pair": ("s1", False), "f4x1_wide": ("s1", False), "d3h": ("s1", False),
+          "fp32_w4": ("s1", True), "fp32_direct": ("s1", True), "d3h_s2": ("d3h_s2", False), "pxh": ("pxh", True), "t3h": ("t3h", True),
+          "sc": ("sc", False), "resampled": ("resampled", False), "pxh_pre": ("pxh_pre", False)}
+
+
+def run_e(family, rows=None, assert_caps=True):
+    group, linear_too = RUNS_E[family]
+    fam = "pxh" if family == "resampled" else family
+    config = fp32_config(fam) if fam in FP32 else -9 if fam == "d3h_s2" else FORCE[fam]
+    for cases in cases_e(group):
+        for case in cases:
+            if fam == "f4x1_wide" and case.L["wf"].shape[0] % 64 != 0:
+                continue                                                  # the wide form exists where two channel groups do: not a case of it
+            check_e(case, config, fam, rows=rows, assert_caps=assert_caps)
+            if linear_too:
+                check_e(case, config, fam, linear=True, rows=rows, assert_caps=assert_caps)
+
+
+def run_e_auto(group, rows=None, assert_caps=True):
+    """Every shape of the group on the automatic route (config -1): attributed once per shape, on the unit-scale case (the route looks at
+    the shape, not at the data; an impulse can give two kernels the same bits), and held to the bound and cap of the family that ran."""
+    for cases in cases_e(group):
+        fam = attribute_auto(cases[0])
+        if fam is None:
+            fam = AUTO_FAMILY[cases[0].launch(-1)[1]]
+        if fam == "d3h" and cases[0].stride == 2:
+            fam = "d3h_s2"                                                # family 6 both; the stride-2 form has its own rows and cap
+        if fam == "pxh" and cases[0].pre is not None:
+            fam = "pxh_pre"                                               # the same kernel; the bound of a launch with an addend
+        for case in cases:
+            row = check_e(case, -1, fam, rows=rows, assert_caps=assert_caps)
+            assert row is not None, f"{case.name}: the automatic route refused an accepted shape"
+
+
+@pytest.mark.parametrize("family", list(RUNS_E))
+def test_degenerate_sizes_against_fp64(hip, family):
+    """Class (e), every family forced (module comment above; the shapes of tests/conv_ref64.py)."""
+    run_e(family)
+
+
+@pytest.mark.parametrize("group", ["s1", "d3h_s2", "pxh", "t3h", "sc", "resampled", "pxh_pre"])
+def test_degenerate_sizes_on_the_automatic_route(hip, group):
+    run_e_auto(group)
+
+
+@pytest.mark.parametrize("cls", ["a", "b"])
+def test_aff_chain_degenerate_against_fp64(hip, cls):
+    """test_aff_chain_against_fp64 at the levels of a 16 x 16 viewport: res1 32 x 16 x 16, res2 64 x 8 x 8, res3 128 x 4 x 4, z 256 x 2 x 2,
+    every launch also guarded."""
+    _aff_chain(cls, R64.aff_chain_inputs(cls, R64.SIZES_E_CHAIN), "e", " 16x16..2x2", guarded=True)

@@ -287,6 +287,100 @@ def test_unet_batch_statistics_mode_vs_oracle(hip):
     _close(y_eval, ref_eval, "fused eval forward after a train-mode pass", rtol=2e-5)
 
 
+@pytest.mark.parametrize("train_mode", [False, True], ids=["eval", "batch-statistics"])
+@pytest.mark.parametrize("B,H,W", [(3, 16, 16), (1, 32, 16)])
+def test_unet_training_graph_at_16_pixel_crops_vs_fp64_autograd(hip, B, H, W, train_mode):
+    """The two graph tests above at the smallest crops the library accepts: three stacked 16 x 16 crops (levels 16 x 16 ... 2 x 2 per
+    item, feat_extract.7 writes ONE pixel per item) and one 32 x 16 crop, against torch.autograd through the oracle in FLOAT64.  The
+    same measure (_close) and the same tolerances: 2e-5 forward / 1e-4 input gradients / 2e-4 parameter gradients in eval mode,
+    1e-4 / 5e-4 / 1e-3 with batch statistics; all 594 parameter gradients and the four input gradients.  Every miss is collected and
+    reported together."""
+    f_tol, x_tol, p_tol = (1e-4, 5e-4, 1e-3) if train_mode else (2e-5, RTOL, 2e-4)
+    state = synthetic.make_unet_state(UNET_SPEC, 13 if not train_mode else 17)
+    net = UNet()
+    net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in state.items()})
+    net.cuda()
+    net.train() if train_mode else net.eval()
+    rng = np.random.default_rng([3, B, H, W])
+    xs = [torch.from_numpy(rng.random((B, 8, H >> l, W >> l)).astype(np.float32)) for l in range(4)]
+    st_r = {k: torch.from_numpy(np.asarray(v)).double().requires_grad_("running" not in k) for k, v in state.items() if np.asarray(v).dtype == np.float32}
+    xs_r = [x.double().requires_grad_(True) for x in xs]
+    out_r = unet_torch.unet_forward(st_r, *xs_r, training=train_mode)
+    assert out_r.dtype == torch.float64
+    g = torch.from_numpy(rng.standard_normal(tuple(out_r.shape)).astype(np.float32))
+    out_r.backward(g.double())
+    xs_d = [x.cuda().requires_grad_(True) for x in xs]
+    out = net(*xs_d)
+    assert out.shape == (B, 3, H, W) and out.grad_fn is not None
+    missed = []
+
+    def close(got, ref, what, rtol):
+        try:
+            return _close(got, ref, what, rtol=rtol)
+        except AssertionError as e:
+            missed.append(str(e))
+            return float("nan")
+
+    close(out, out_r, "forward", f_tol)
+    out.backward(g.cuda())
+    for l in range(4):
+        close(xs_d[l].grad, xs_r[l].grad, f"dx level {l}", x_tol)
+    errs = []
+    for name, p in net.named_parameters():
+        if name.startswith("ConvsOut."):                            # never executed (unet.py:181-186)
+            continue
+        assert p.grad is not None and st_r[name].grad is not None, name
+        errs.append(close(p.grad, st_r[name].grad, name, p_tol))
+    print(f"B={B} {H}x{W} {'batch statistics' if train_mode else 'eval'}: {len(errs)} parameter gradients, worst relative error {np.nanmax(errs):.2e}, {len(missed)} missed")
+    assert len(errs) >= 594
+    if train_mode:
+        # the running statistics the pass moved (over 1 - 4 pixels per item at the coarse levels), then the fused eval plan on them
+        sd = net.state_dict()
+        for k in sd:
+            if "running_" in k and not k.startswith("ConvsOut."):
+                close(sd[k].cpu(), st_r[k], k, 1e-4)
+            if k.endswith("num_batches_tracked") and not k.startswith("ConvsOut."):
+                assert int(sd[k]) == 1, k
+        net.eval()
+        with torch.no_grad():
+            y_eval = net(*[x.cuda() for x in xs])
+            ref_eval = unet_torch.unet_forward(st_r, *[x.double() for x in xs])
+        close(y_eval, ref_eval, "fused eval forward after a train-mode pass", 2e-5)
+    else:
+        # a single item takes the unstacked graph; inference afterwards still uses the fused plan and sees the same weights
+        one = net(*[x[B - 1:B].cuda().requires_grad_(True) for x in xs])
+        close(one, out_r[B - 1:B], "single-item training forward", 2e-5)
+        with torch.no_grad():
+            y2 = net(*[x.cuda() for x in xs])
+        close(y2, out_r, "fused forward after training forward", 2e-5)
+    assert not missed, f"{len(missed)} tensors outside their tolerance: " + "; ".join(missed[:12])
+
+
+def test_batch_statistics_over_one_pixel_on_a_single_16_pixel_crop(hip):
+    """One 16 x 16 crop in .train(): feat_extract.7 writes ONE pixel, so its BatchNorm has one value per channel.  The reference
+    refuses that (torch's F.batch_norm raises ValueError; asserted on the oracle), so there is no graph to compare with; what the
+    library does there is stated and held: it runs, the batch variance of that layer is 0 (its running_var moves to 0.9 of the old
+    value: momentum 0.1, unbiased = biased at a count of one), and output and gradients are finite.  The kernels at a count of one
+    against float64: tests/test_gpu_train_accuracy.py, the degenerate batch-statistics rows."""
+    H = W = 16
+    state = synthetic.make_unet_state(UNET_SPEC, 17)
+    net = UNet()
+    net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in state.items()})
+    net.cuda().train()
+    rng = np.random.default_rng([5, H, W])
+    xs = [torch.from_numpy(rng.random((1, 8, H >> l, W >> l)).astype(np.float32)) for l in range(4)]
+    st_r = {k: torch.from_numpy(np.asarray(v)).clone() for k, v in state.items()}
+    with pytest.raises(ValueError, match="more than 1 value per channel"):
+        unet_torch.unet_forward(st_r, *xs, training=True)
+    xs_d = [x.cuda().requires_grad_(True) for x in xs]
+    out = net(*xs_d)
+    out.backward(torch.ones_like(out))
+    assert bool(torch.isfinite(out).all()) and all(bool(torch.isfinite(x.grad).all()) for x in xs_d)
+    assert all(bool(torch.isfinite(p.grad).all()) for n, p in net.named_parameters() if not n.startswith("ConvsOut."))
+    key = "feat_extract.7.block.norm.running_var"
+    _close(net.state_dict()[key].cpu(), 0.9 * torch.from_numpy(np.asarray(state[key])), key, rtol=1e-6)
+
+
 def test_sparse_rmsprop_equals_dense_torch_rmsprop(hip):
     """Rows touched in some steps only: the lazily decayed sparse update must follow torch.optim.RMSprop's dense trajectory."""
     from read_amd.texture import PointTexture

@@ -136,10 +136,33 @@ def _torch32_eval(fm, dy, C, L, elu, residual, v):
     return (y.detach() * vm).numpy(), t.grad[:, :C].numpy(), t.grad[:, C:].numpy(), par["gamma"].grad.numpy(), par["beta"].grad.numpy()
 
 
+# Degenerate sizes: 1, 4 and 12 pixels (the coarse levels of a 16-pixel crop: 1 x 1, 2 x 2, 2 x 6) and three stacked 2 x 2 items with
+# one separator row each, at 3, 9 and 256 channels.  Batch statistics over ONE value per channel (what feat_extract.7 sees on a single
+# 16 x 16 crop) are refused by torch's F.batch_norm, so the torch yardstick does not exist for that geometry; the library computes them
+# (mean = the value, var = 0, y = beta, running_var moves towards 0) and is held there to the float64 reference of tests/train_ref64.py,
+# which has no such restriction, to the derived bounds and to the sequential yardstick alone.
+TINY_GEOM = ((1, 1, 0, 0, (1,)), (4, 2, 0, 0, (1,)), (12, 6, 0, 0, (1,)), (3 * 3 * 2, 2, 3, 2, (1, 3)))
+
+
+def _tiny_gate_cases(batch_statistics):
+    for C in (3, 9, 256):
+        for cls in "ab":
+            for geom in TINY_GEOM:
+                yield C, cls, geom
+
+
 def test_gate_forward_and_eval_backward(hip):
     """read_gate_forward, read_gate_backward, read_bn_param_grads."""
+    _gate_eval_rows(hip, _gate_cases())
+
+
+def test_gate_forward_and_eval_backward_at_degenerate_sizes(hip):
+    _gate_eval_rows(hip, _tiny_gate_cases(False))
+
+
+def _gate_eval_rows(hip, cases):
     st = _lib.stream_ptr()
-    for C, cls, (P, W, bh, vh, _groups) in _gate_cases():
+    for C, cls, (P, W, bh, vh, _groups) in cases:
         fm, dy, L = _gate_inputs(cls, P, C, 21)
         if cls == "d":                                               # eval mode after training: the running statistics are the channels' own
             g64 = T.Gate(fm, C, True).g
@@ -214,9 +237,22 @@ def _torch32_bn(fm, dy, C, L, v, grp, groups, momentum):
 
 def test_batch_statistics_batchnorm_forward_and_backward(hip):
     """read_bn_train_forward, read_gate_backward_bn, read_bn_param_grads_groups: both group modes."""
+    _bn_rows(hip, _gate_cases())
+
+
+def test_batch_statistics_batchnorm_at_degenerate_sizes(hip):
+    """... statistics over 4 and 12 values per channel, and per item over the 4 valid pixels of each of three stacked 2 x 2 items.
+    dbeta is given the rule's second yardstick here, a sequential fp32 sum of dy (the larger tests pass torch's alone): over 12 terms
+    autograd's reduction can land within one unit where any other order of the same additions is at two (measured on the CPU on the
+    (b) case of C = 256: both the sequential sum and torch.sum are at 2.03, autograd's dbeta at 1.03), and the cap 2 max(R, 1) is meant
+    to be taken over the orders a correct sum may use."""
+    _bn_rows(hip, _tiny_gate_cases(True), dbeta_seq=True)
+
+
+def _bn_rows(hip, cases, dbeta_seq=False):
     st = _lib.stream_ptr()
     mom = 0.1
-    for C, cls, (P, W, bh, vh, group_modes) in _gate_cases():
+    for C, cls, (P, W, bh, vh, group_modes) in cases:
         fm, dy, L = _gate_inputs(cls, P, C, 22)
         cp, cpad = T.pad8(C), (C + 31) // 32 * 32
         v = T.valid_rows(P, W, bh, vh)
@@ -241,18 +277,21 @@ def test_batch_statistics_batchnorm_forward_and_backward(hip):
             yt = np.zeros((P, C), f32)
             ys, rm_s, rv_s = np.zeros((P, C), f32), L["mean"].copy(), L["var"].copy()
             rm_t, rv_t = torch.from_numpy(L["mean"].copy()), torch.from_numpy(L["var"].copy())
+            torch_ok = min(int((v & (grp == j)).sum()) for j in range(groups)) > 1     # F.batch_norm refuses one value per channel
+            only = (lambda d: d) if torch_ok else (lambda d: {k_: v_ for k_, v_ in d.items() if k_ != "torch"})
             for j in range(groups):
                 sel = v & (grp == j)
                 ys[sel], _, _, rm_s, rv_s = bn_forward32(g_dev[sel], L["gamma"], L["beta"], mom, rm_s, rv_s)
-                yt[sel] = F.batch_norm(torch.from_numpy(g_dev[sel]).t()[None], rm_t, rv_t, torch.from_numpy(L["gamma"]), torch.from_numpy(L["beta"]),
-                                       training=True, momentum=mom, eps=T.EPS)[0].t().numpy()
-            judge("bn_fwd y", cls, name, y_h, fwd.y, fwd.cond_y, fwd.bound_y, {"torch": yt, "seq": ys},
+                if torch_ok:
+                    yt[sel] = F.batch_norm(torch.from_numpy(g_dev[sel]).t()[None], rm_t, rv_t, torch.from_numpy(L["gamma"]), torch.from_numpy(L["beta"]),
+                                           training=True, momentum=mom, eps=T.EPS)[0].t().numpy()
+            judge("bn_fwd y", cls, name, y_h, fwd.y, fwd.cond_y, fwd.bound_y, only({"torch": yt, "seq": ys}),
                   extra=" E(xhat) max %.2f torch %.2f |" % (T.stats(np.abs(y_h - fwd.y), fwd.cond_y_centered)[0], T.stats(np.abs(yt - fwd.y), fwd.cond_y_centered)[0]))
             assert not y_h[~v].any(), name + ": separator rows of y are not zero"
             judge("bn_fwd stat", cls, name, stat_h, fwd.stat, fwd.cond_stat, fwd.bound_stat, {})
             judge("bn_fwd running", cls, name, np.stack([rm_h, rv_h]), np.stack([fwd.running_mean, fwd.running_var]),
                   np.stack([fwd.cond_rm, fwd.cond_rv]), np.stack([fwd.bound_rm, fwd.bound_rv]),
-                  {"torch": np.stack([rm_t.numpy(), rv_t.numpy()]), "seq": np.stack([rm_s, rv_s])})
+                  only({"torch": np.stack([rm_t.numpy(), rv_t.numpy()]), "seq": np.stack([rm_s, rv_s])}))
             # backward with the forward's statistics
             dfm = torch.full((P, 2 * cp), 7.0, device="cuda")
             sums = torch.zeros((groups, 4, C), device="cuda")
@@ -264,7 +303,8 @@ def test_batch_statistics_batchnorm_forward_and_backward(hip):
                                                       grads[2].data_ptr(), grads[3].data_ptr(), st))
             dfm_h, grads_h = _host(dfm), _host(grads)
             ref = T.GateBackwardBn(dy, fm, C, L["gamma"], True, W, bh, vh, groups, stat_h)
-            _, _, _, dft, dmt, dgt, dbt = _torch32_bn(fm, dy, C, L, v, grp, groups, mom)
+            zc = np.zeros(C, f32)
+            _, _, _, dft, dmt, dgt, dbt = _torch32_bn(fm, dy, C, L, v, grp, groups, mom) if torch_ok else (None, None, None, np.zeros((P, C), f32), np.zeros((P, C), f32), zc, zc)
             dfs, dms, dgs = np.zeros((P, C), f32), np.zeros((P, C), f32), np.zeros(C, f32)
             one = np.ones(C, f32)
             for j in range(groups):
@@ -278,8 +318,8 @@ def test_batch_statistics_batchnorm_forward_and_backward(hip):
             cdf, cdm = ref.cond_dg * gt.sig * gt.da_abs, ref.cond_dg * gt.a_abs * gt.sig * (1 + gt.sig)
             cdf_dg = (gt.f > 0) & (gt.sig == 1.0) & v[:, None]       # where df IS dg (the ratio and constant channels of class (d))
             dg_dev = np.where(cdf_dg, dfm_h[:, :C], ref.dg)
-            judge("bn_bwd df", cls, name, dfm_h[:, :C], ref.df, cdf, ref.bound_df, {"torch": dft, "seq": dfs}, lead=ref.lead_df if raised else None)
-            judge("bn_bwd dm", cls, name, dfm_h[:, cp:cp + C], ref.dm, cdm, ref.bound_dm, {"torch": dmt, "seq": dms}, lead=ref.lead_dm if raised else None)
+            judge("bn_bwd df", cls, name, dfm_h[:, :C], ref.df, cdf, ref.bound_df, only({"torch": dft, "seq": dfs}), lead=ref.lead_df if raised else None)
+            judge("bn_bwd dm", cls, name, dfm_h[:, cp:cp + C], ref.dm, cdm, ref.bound_dm, only({"torch": dmt, "seq": dms}), lead=ref.lead_dm if raised else None)
             assert not dfm_h[:, C:cp].any() and not dfm_h[:, cp + C:].any() and not dfm_h[~v].any(), name + ": padding / separator rows of d[f|m]"
             per_kind = ""
             if raised and P == 1536:
@@ -287,12 +327,15 @@ def test_batch_statistics_batchnorm_forward_and_backward(hip):
                 eg = np.where(cdf_dg > 0, np.abs(dg_dev - ref.dg) / np.maximum(T.U * ref.cond_dg, 1e-300), 0.0).max(0)
                 per_kind = " per kind E(dgamma) / worst E(dg): " + ", ".join("%s %.1f / %.1f" % (k_, max(e[c] for c in range(C) if c % 7 == i), max(eg[c] for c in range(C) if c % 7 == i))
                                                                                  for i, k_ in enumerate(T.D_CHANNELS)) + " |"
-            judge("bn_bwd dgamma", cls, name, grads_h[2], ref.dgamma, _centred(ref), ref.bound_dgamma, {"torch": dgt, "seq": dgs},
+            judge("bn_bwd dgamma", cls, name, grads_h[2], ref.dgamma, _centred(ref), ref.bound_dgamma, only({"torch": dgt, "seq": dgs}),
                   lead=ref.lead_dgamma_terms + (ref.lead_dgamma if raised else 0), zero_cond_by_bound=True, extra=per_kind)
-            judge("bn_bwd dbeta", cls, name, grads_h[3], ref.dbeta, ref.cond_dbeta, ref.bound_dbeta, {"torch": dbt})
-            judge("bn_bwd dbf", cls, name, grads_h[0], ref.dbf, cdf.sum(0), ref.bound_dbf, {"torch": dft.sum(0), "seq": np.add.accumulate(dfs, axis=0, dtype=f32)[-1]},
+            yard_dbeta = only({"torch": dbt})
+            if dbeta_seq:
+                yard_dbeta["seq"] = np.add.accumulate(dy * v[:, None].astype(f32), axis=0, dtype=f32)[-1]
+            judge("bn_bwd dbeta", cls, name, grads_h[3], ref.dbeta, ref.cond_dbeta, ref.bound_dbeta, yard_dbeta)
+            judge("bn_bwd dbf", cls, name, grads_h[0], ref.dbf, cdf.sum(0), ref.bound_dbf, only({"torch": dft.sum(0), "seq": np.add.accumulate(dfs, axis=0, dtype=f32)[-1]}),
                   lead=ref.lead_dbf + (ref.lead_df.sum(0) if raised else 0))
-            judge("bn_bwd dbm", cls, name, grads_h[1], ref.dbm, cdm.sum(0), ref.bound_dbm, {"torch": dmt.sum(0), "seq": np.add.accumulate(dms, axis=0, dtype=f32)[-1]},
+            judge("bn_bwd dbm", cls, name, grads_h[1], ref.dbm, cdm.sum(0), ref.bound_dbm, only({"torch": dmt.sum(0), "seq": np.add.accumulate(dms, axis=0, dtype=f32)[-1]}),
                   lead=ref.lead_dbm + (ref.lead_dm.sum(0) if raised else 0))
     finish()
 
@@ -464,13 +507,83 @@ def _winograd_wgrad_cases(hip, rng):
             assert np.array_equal(same[0], got[0]) and np.array_equal(same[1], got[1]), name + ": accumulating a zero gradient changed the buffer"
 
 
+def test_weight_gradient_at_degenerate_sizes(hip):
+    """read_conv_wgrad at the sizes of a 16-pixel crop's coarse levels.  With the Winograd-domain knob on, C -> C 3x3 / stride-1 layers
+    (32, 128, 256) at 2 x 2, 1 x 1, 2 x 6 and 4 x 12: read_conv_wgrad_family sends an image of fewer than four rows to the direct kernels
+    (family 0: it has no whole 4 x 4 tile) and 4 x 12 to the Winograd-domain kernels (family 4); each row is held to the bound of the
+    family that the route names — class (a), a constant, and impulses of d[f|m] at every pixel of the 2 x 2.  With the knob off, one
+    stride-1, one k3 / stride-2 and one k4 / stride-2 layer at 1 x 1 and 2 x 2 (k4 at 1 x 1 has an empty output: left out), class (a)
+    and every impulse read back exactly."""
+    rng = np.random.default_rng(131)
+    knob = _knob(hip)
+    try:
+        _knob(hip, 1)
+        for c in (32, 128, 256):
+            for (H, W) in ((2, 2), (1, 1), (2, 6), (4, 12)):
+                fam = hip.read_conv_wgrad_family(c, 3, 1, H, W)
+                assert fam == (4 if H >= 4 else 0), (c, H, W, fam)
+                wino = fam == 4
+                bound = (lambda Aw, prev: T.wgrad_wino_bound(Aw, c, c, H, W)) if wino else (lambda A, prev: T.wgrad_direct_bound(A, c, c, 3, H, W))
+                kw = dict(cond_fn=T.wgrad_wino_Aw) if wino else {}
+                rows = [(cls, "", _wgrad_inputs(cls, c, c, H, W, H, W, rng)) for cls in ("a", "const")]
+                if (H, W) == (2, 2):
+                    xi = T.small_integers((H, W, c), rng)
+                    for (py, px) in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                        d = np.zeros((H, W, c), f32)
+                        d[py, px] = 1.0
+                        rows.append(("impulse", f" impulse {py},{px}", (xi, d, d)))
+                for cls, tag, (x, df, dm) in rows:
+                    got = _wgrad(hip, x, _dfm(df, dm, c), c, 3, 1)
+                    _judge_wgrad("wgrad_wino" if wino else "wgrad", "a" if cls == "a" else "c", f"{c}->{c} {H}x{W}{tag} [family {fam}]", got, x, (df, dm), 3, 1,
+                                 bound, **kw)
+        _knob(hip, 0)
+        for (cin, cout, k, stride) in ((48, 20, 3, 1), (32, 64, 3, 2), (64, 32, 4, 2)):
+            for (H, W) in ((1, 1), (2, 2)):
+                oh, ow = T.out_hw(k, stride, H, W)
+                if oh == 0:
+                    continue
+                assert hip.read_conv_wgrad_family(cin, k, stride, H, W) == 0
+                name = f"{cin}->{cout} k{k} s{stride} {H}x{W}"
+                x, df, dm = _wgrad_inputs("a", cin, cout, H, W, oh, ow, rng)
+                got = _wgrad(hip, x, _dfm(df, dm, cout), cout, k, stride)
+                _judge_wgrad("wgrad", "a", name, got, x, (df, dm), k, stride, lambda A, prev: T.wgrad_direct_bound(A, cin, cout, k, oh, ow))
+                xi = T.small_integers((H, W, cin), rng)
+                pad = (k - 1) // 2
+                xp = np.zeros((H + 2 * pad + k, W + 2 * pad + k, cin), f32)
+                xp[pad:pad + H, pad:pad + W] = xi
+                for py in range(oh):
+                    for px in range(ow):
+                        for amp in (1.0, 2.0 ** -10):
+                            d = np.zeros((oh, ow, cout), f32)
+                            d[py, px] = amp
+                            got = _wgrad(hip, xi, _dfm(d, d, cout), cout, k, stride)
+                            want = np.broadcast_to((f32(amp) * xp[py * stride:py * stride + k, px * stride:px * stride + k]).transpose(2, 0, 1)[None], got[0].shape)
+                            assert np.array_equal(got[0], want) and np.array_equal(got[1], want), f"{name}: impulse at {(py, px)} x {amp}"
+                print("TACC| %-12s | c | %-46s | %d impulse positions x 2 amplitudes read back exactly" % ("wgrad", name, oh * ow))
+    finally:
+        _knob(hip, knob)
+    finish()
+
+
 # ------------------------------------------------------------------------------------------ generic input gradient
 def test_generic_input_gradient(hip):
     """read_conv_dgrad_generic: (k3, s2) and (k4, s2) at odd sizes."""
-    rng = np.random.default_rng(34)
+    _generic_dgrad_rows(hip, np.random.default_rng(34), ((9, 13), (7, 7)))
+    finish()
+
+
+def test_generic_input_gradient_at_degenerate_sizes(hip):
+    """... at 2 x 2 (output 1 x 1) and 3 x 1 (k3: output 2 x 1; k4: 1 x 0, an empty d[f|m]: left out)."""
+    _generic_dgrad_rows(hip, np.random.default_rng(134), ((2, 2), (3, 1)))
+    finish()
+
+
+def _generic_dgrad_rows(hip, rng, sizes):
     st = _lib.stream_ptr()
     for k in (3, 4):
-        for (H, W) in ((9, 13), (7, 7)):
+        for (H, W) in sizes:
+            if 0 in T.out_hw(k, 2, H, W):
+                continue
             for cin in (8, 32):
                 for cout in (3, 40):
                     for cls in "abc":
@@ -496,7 +609,6 @@ def test_generic_input_gradient(hip):
                               {"torch": T.dgrad_torch32(dfm, cout, w[0], w[1], k, 2, H, W), "seq": T.dgrad_seq32(dfm, cout, w[0], w[1], k, 2, H, W)})
                         if cls == "c":
                             assert np.array_equal(got.astype(np.float64), ref), name + ": the impulse's weights are not read back exactly"
-    finish()
 
 
 # ------------------------------------------------------------------------------------------ input gradient through the convolution kernels
@@ -526,11 +638,24 @@ def test_input_gradient_through_the_convolution_kernels(hip):
     """Stride 1 (k1, k3; 2 pad8(Cout) = 16, 48, 80, 112, 128 virtual input channels), dilated 3x3 / stride 2, polyphase k3 / k4: the fp32
     convolution kernels in linear mode over d[f|m] with flipped, transposed weights.  cond = sum |d| |w|; the Winograd launches are held
     to the transformed-domain term A_w (asserted), E against cond is printed as E(A)."""
-    from read_amd import train
-    rng = np.random.default_rng(37)
-    cin = 32
     cases = [("s1", k, 1, cout, hw) for k in (1, 3) for cout in (3, 20, 40, 56, 64) for hw in ((9, 21), (12, 20))]
     cases += [(br, k, 2, cout, (8, 12)) for (br, k) in (("dilated", 3), ("poly", 3), ("poly", 4)) for cout in (3, 40)]
+    _conv_dgrad_rows(np.random.default_rng(37), cases)
+    finish()
+
+
+def test_input_gradient_through_the_convolution_kernels_at_degenerate_sizes(hip):
+    """... "s1" at 1 x 1, 2 x 2 and 2 x 6; "dilated" and "poly" (k3, k4) at inputs of 2 x 2 (d[f|m] is one pixel: three of the four
+    parity planes of the polyphase form are empty or one pixel) and 4 x 4."""
+    cases = [("s1", k, 1, cout, hw) for k in (1, 3) for cout in (3, 40, 64) for hw in ((1, 1), (2, 2), (2, 6))]
+    cases += [(br, k, 2, cout, hw) for (br, k) in (("dilated", 3), ("poly", 3), ("poly", 4)) for cout in (3, 40) for hw in ((2, 2), (4, 4))]
+    _conv_dgrad_rows(np.random.default_rng(137), cases)
+    finish()
+
+
+def _conv_dgrad_rows(rng, cases):
+    from read_amd import train
+    cin = 32
     for branch, k, stride, cout, (H, W) in cases:
         for cls in "ab":
             oh, ow = T.out_hw(k, stride, H, W)
@@ -562,15 +687,25 @@ def test_input_gradient_through_the_convolution_kernels(hip):
                     d_in[::2, ::2] = dfm
                 bound, Aw = T.conv_dgrad_bound(d_in, T.virtual_weights(w[0], w[1]), None, ref, fam)
             judge("dgrad_conv", cls, name, got, ref, Aw, bound, yard, extra=" E(A) max %.2f rms %.3f |" % T.stats(np.abs(got - ref), cond))
-    finish()
 
 
 # ------------------------------------------------------------------------------------------ bilinear x 4
 def test_bilinear_up4_forward_and_backward(hip):
     """read_bilinear_up4_blocks, read_bilinear_up4_backward.  No R_seq: the only sums are the backward's <= 36 terms per thread."""
-    rng = np.random.default_rng(35)
+    _up4_rows(hip, np.random.default_rng(35), ((1, 1, 0, 0), (2, 5, 0, 0), (5, 3, 0, 0), (10, 3, 5, 3)))
+    finish()
+
+
+def test_bilinear_up4_on_stacked_one_and_four_pixel_items(hip):
+    """... three stacked items of 1 x 1 and of 2 x 2 valid pixels, one separator row each (what a batch of three 16 x 16 crops gives
+    feat_extract.7 and feat_extract.3)."""
+    _up4_rows(hip, np.random.default_rng(135), ((6, 1, 2, 1), (9, 2, 3, 2)))
+    finish()
+
+
+def _up4_rows(hip, rng, geometries):
     st = _lib.stream_ptr()
-    for (H, W, bh, vh) in ((1, 1, 0, 0), (2, 5, 0, 0), (5, 3, 0, 0), (10, 3, 5, 3)):
+    for (H, W, bh, vh) in geometries:
         for C in (4, 8):
             for cls in "ab":
                 sc = T.scales_b(C, rng) if cls == "b" else np.ones(C)
@@ -590,7 +725,6 @@ def test_bilinear_up4_forward_and_backward(hip):
                 judge("up4_bwd", cls, name, gotb, refb, condb, boundb, {"torch": T.up4_torch32(d, H, W, bh, vh, True)})
                 if bh:
                     assert not got.reshape(H // bh, 4 * bh, -1)[:, 4 * vh:].any() and not gotb.reshape(H // bh, bh, -1)[:, vh:].any(), name + ": separator rows"
-    finish()
 
 
 # ------------------------------------------------------------------------------------------ Huber
@@ -598,7 +732,7 @@ def test_huber_loss_and_gradient(hip):
     """read_huber_loss: the per-element gradient and the summed loss."""
     rng = np.random.default_rng(36)
     st = _lib.stream_ptr()
-    for n in (1, 255, 257, 1000):
+    for n in (1, 3, 255, 257, 1000):
         for cls in "ab":
             t = (rng.standard_normal(n) * (2.0 ** rng.uniform(-8, 6, n) if cls == "b" else 1.0)).astype(f32)
             o = (t + rng.standard_normal(n) * 1.5).astype(f32)

@@ -138,8 +138,19 @@ LAUNCHES = [(family, layer) for family in ("direct", "w2", "w4") for layer in FC
 @pytest.mark.parametrize("family,layer", LAUNCHES, ids=[f"{fam}-{FC.layer_name(l).replace(' ', '_')}" for fam, l in LAUNCHES])
 def test_forward_linear_launch(hip, family, layer):
     """Assertions 1 and 2 for one layer at both sizes, every input class."""
+    _forward_rows(family, layer, FC.SIZES[layer[3]])
+
+
+@pytest.mark.parametrize("family,layer", LAUNCHES, ids=[f"{fam}-{FC.layer_name(l).replace(' ', '_')}" for fam, l in LAUNCHES])
+def test_forward_linear_launch_at_degenerate_sizes(hip, family, layer):
+    """The same at 2 x 2, 4 x 4 and 1 x 1 (FC.SIZES_TINY: the coarse levels of a 16-pixel crop; an impulse at every pixel), the guard
+    bands behind fm and y included.  A 4x4 / stride-2 layer has no output at 1 x 1: that size is not a launch."""
+    _forward_rows(family, layer, [hw for hw in FC.SIZES_TINY if 0 not in T.out_hw(layer[2], layer[3], *hw)])
+
+
+def _forward_rows(family, layer, sizes):
     with _switched(layer[4]) as train:
-        for hw in FC.SIZES[layer[3]]:
+        for hw in sizes:
             for case in FC.cases(layer, hw):
                 dev = _Layer(train, case, family)
                 first, yard_fm = None, _fm_yard(case)

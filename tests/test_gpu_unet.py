@@ -5,6 +5,7 @@ against the oracle restatement.
 Stated tolerance (fp32 MFMA vs fp32 oneDNN, 40+ gated-conv layers deep; measured 2e-7 / 148 dB): max |diff| <= 5e-6,
 PSNR >= 120 dB, and — because the random-weight RGB output has a per-channel spread of only ~0.01-0.03 — the error
 RELATIVE to the signal: rms(diff) <= 1e-4 * std(ref) (the north-star budget is 0.5 dB of PSNR)."""
+import ctypes
 import os
 
 import numpy as np
@@ -383,3 +384,159 @@ def test_lean_weight_blob_renders_the_same_frame(hip):
         _check_rgb(y2.cpu(), y.cpu(), "F(2x2) kernels from the full blob against F(4x4) from the lean one")
     finally:
         _lib.check(_lib.lib().read_tuning_set(b"conv_w4", 32))
+
+
+# ------------------------------------------------------------------------------------------ the smallest viewports
+# Every viewport that is a positive multiple of 16 is accepted.  At 16 x 16 the four levels are 16 x 16, 8 x 8, 4 x 4 and 2 x 2, the
+# 4x4 / stride-2 layer feat_extract.7 writes ONE pixel and the rasteriser's fifth level is 1 x 1: every kernel of the plan runs on an
+# image smaller than its unit.  16 x 48 / 48 x 16 / 32 x 16 are ragged in one direction, 80 x 112 has W / 8 = 14 (no multiple of 4)
+# and a ragged tile row, 16 x 1216 is one tile row of the headline width.
+TINY_VIEWPORTS = [(16, 16), (16, 48), (48, 16), (32, 16), (80, 112), (16, 1216)]
+# tap of oracle.unet_torch.unet_forward -> tensor of the plan (read_amd/csrc/unet.cpp, Builder::build: the fourth block of a
+# resblocks() ring lands in its ".y2")
+ORACLE_TAPS = {"res1": "Encoder.0.y2", "res2": "Encoder.1.y2", "res3": "Encoder.2.y2", "zb": "Encoder.3.y2", "z2": "SCM2.out", "z4": "SCM1.out",
+               "z8": "SCM0.out", "aff0": "aff0.out", "aff1": "aff1.out", "aff2": "aff2.out", "d3": "Decoder.3.y2"}
+_TINY = {}
+
+
+def _tiny_net():
+    """One seeded state, its float64 copy and its full-layout blob on the device, shared by the tests below."""
+    from read_amd.unet import LAYOUT_FULL, pack_state
+    if not _TINY:
+        state = synthetic.make_unet_state(UNET_SPEC, 9)
+        _TINY["state"] = state
+        _TINY["st64"] = {k: torch.from_numpy(np.asarray(v)).double() for k, v in state.items() if np.asarray(v).dtype.kind == "f"}
+        _TINY["full"] = torch.from_numpy(pack_state(state, layout=LAYOUT_FULL)).cuda()
+    return _TINY
+
+
+def _tiny_case(H, W):
+    """-> (inputs (h, w, 8) per level on the host, float64 RGB (3, H, W), float64 taps), computed once per viewport."""
+    if (H, W) not in _TINY:
+        g = torch.Generator().manual_seed(1000 * H + W)
+        xs = [torch.rand(H >> l, W >> l, 8, generator=g) for l in range(4)]
+        taps = {}
+        with torch.no_grad():
+            ref = unet_torch.unet_forward(_tiny_net()["st64"], *[x.permute(2, 0, 1)[None].double() for x in xs], taps=taps)[0]
+        assert ref.dtype == torch.float64
+        _TINY[(H, W)] = (xs, ref, taps)
+    return _TINY[(H, W)]
+
+
+def _check_taps(eng, taps, what):
+    for key, name in ORACLE_TAPS.items():
+        t = eng.debug_tensor(name).permute(2, 0, 1).cpu().double()
+        r = taps[key][0]
+        assert t.shape == r.shape, (what, key, t.shape, r.shape)
+        bad = float(((t - r).abs() / r.abs().clamp(min=1.0)).max())
+        print("%s: tap %-5s %-14s %s relative error %.3e" % (what, key, name, tuple(t.shape), bad))
+        assert bad <= TAP_REL, f"{what}: {key} ({name}): relative error {bad:.3e}"
+
+
+def _assert_split_operand_plan(eng, xs_dev, what):
+    """The default plan's 3x3 / stride-1 launches ran on the split-operand kernels (5; FAM's three on the direct one, 6), none on
+    the fp32 Winograd kernel (4): the assertion of test_split_operand_plan_against_the_fp32_plan, so that a silent fallback at a
+    small size does not pass for them."""
+    kinds = [k for (_, _, _, k) in eng.profile(*xs_dev)]
+    assert kinds.count(5) >= 70 and kinds.count(6) == 3 and kinds.count(4) == 0, (what, kinds)
+
+
+@pytest.mark.parametrize("H,W", TINY_VIEWPORTS)
+def test_unet_engine_at_the_smallest_viewports_against_fp64(hip, H, W):
+    """UNetEngine (default plan, full layout) against unet_torch.unet_forward in FLOAT64 at the three network guards, and every tap
+    the oracle exposes against the plan's tensor at TAP_REL.  read_unet_create writes nothing into the workspace (unet.cpp: the
+    Builder only hands out addresses; UNetEngine allocates it with torch.empty), so the workspace is filled with NaN before the
+    first forward: a launch that reads what no launch wrote — a halo, a row past a ragged unit — shows in the frame."""
+    from read_amd.unet import UNetEngine
+    xs, ref, taps = _tiny_case(H, W)
+    xs_dev = [x.cuda() for x in xs]
+    eng = UNetEngine(_tiny_net()["full"], H, W)
+    eng.ws.fill_(0xFF)                                           # every float of it: 0xFFFFFFFF, a NaN
+    got = eng.forward(*xs_dev).clone()
+    torch.cuda.synchronize()
+    what = f"{H}x{W} against fp64"
+    assert bool(torch.isfinite(got).all()), f"{what}: non-finite frame from a NaN-filled workspace"
+    _check_rgb(got.permute(2, 0, 1).cpu(), ref, what)
+    _check_taps(eng, taps, what)
+    _assert_split_operand_plan(eng, xs_dev, what)
+    again = eng.forward(*xs_dev)
+    torch.cuda.synchronize()
+    assert torch.equal(got, again), f"{what}: the second frame of the same engine differs"
+
+
+@pytest.mark.parametrize("H,W", [(16, 16), (80, 112)])
+def test_plan_knobs_at_the_smallest_viewports_against_fp64(hip, H, W):
+    """The four unet_aff_split x unet_up_fold plans, conv_f4x1 = 0 (the F(4x4) split-operand kernel in the place of F(4,3) by rows) and
+    conv_w4h = 0 (the fp32 Winograd kernel, full layout) at 16 x 16 and 80 x 112: each against the float64 network at the three guards.
+    A plan is built under the knobs of its creation: one UNetEngine per plan on the shared full-layout blob (what UNet.invalidate()
+    leads to, without packing the state again)."""
+    from read_amd import _lib
+    from read_amd.unet import UNetEngine
+    xs, ref, _ = _tiny_case(H, W)
+    xs_dev = [x.cuda() for x in xs]
+    L = _lib.lib()
+    default = {}
+    for key in (b"unet_aff_split", b"unet_up_fold", b"conv_f4x1", b"conv_w4h"):     # what the knobs hold now is what they go back to
+        val = ctypes.c_int(-1)
+        _lib.check(L.read_tuning_get(key, ctypes.byref(val)))
+        default[key] = val.value
+    assert default[b"unet_aff_split"] == 1 and default[b"unet_up_fold"] == 0 and default[b"conv_f4x1"] > 0 and default[b"conv_w4h"] > 0, default
+    plans = [{b"unet_aff_split": s, b"unet_up_fold": f} for s in (1, 0) for f in (0, 1)] + [{b"conv_f4x1": 0}, {b"conv_w4h": 0}]
+    outs = []
+    try:
+        for plan in plans:
+            for key, v in {**default, **plan}.items():
+                _lib.check(L.read_tuning_set(key, v))
+            eng = UNetEngine(_tiny_net()["full"], H, W)
+            what = f"{H}x{W} " + (" ".join(f"{k.decode()}={v}" for k, v in plan.items()))
+            outs.append(eng.forward(*xs_dev).permute(2, 0, 1).cpu())
+            _check_rgb(outs[-1], ref, what)
+            labels = eng.launch_labels()
+            assert any(l.startswith("up4(") for l in labels) == (plan.get(b"unet_up_fold", 0) == 0) and ("AFFq3" in labels) == (plan.get(b"unet_aff_split", 1) == 1), (what, labels)
+            if plan == plans[0]:
+                _assert_split_operand_plan(eng, xs_dev, what)
+            elif b"conv_w4h" in plan:
+                kinds = [k for (_, _, _, k) in eng.profile(*xs_dev)]
+                assert kinds.count(5) == 0 and kinds.count(4) >= 70, (what, kinds)
+            del eng
+    finally:
+        for key, v in default.items():
+            _lib.check(L.read_tuning_set(key, v))
+    assert not torch.equal(outs[0], outs[4]) and not torch.equal(outs[0], outs[5]), "conv_f4x1 = 0 / conv_w4h = 0 did not change the arithmetic"
+
+
+@pytest.mark.parametrize("N", [5000, (1 << 20) + 4321], ids=["plain", "cells"])
+@pytest.mark.parametrize("W,H", [(16, 16), (48, 16)])
+def test_frame_renderer_at_the_smallest_viewports(hip, W, H, N):
+    """FrameRenderer at 16 x 16 and 16 rows x 48 columns, on a cloud below the cell-ordering threshold and on one above it: all five
+    index / depth levels bit for bit against oracle.raster_multiscale (the fifth is 1 x 1 / 1 x 3), the frame at the network guards
+    against net_and_texture_forward, and frames_in_flight = 2 equal to one frame at a time over four poses."""
+    if ("cloud", N) not in _TINY:
+        _TINY[("cloud", N)] = (synthetic.make_cloud(N, 5), synthetic.make_descriptors(N))
+    xyz, desc = _TINY[("cloud", N)]
+    state = _tiny_net()["state"]
+    proj = synthetic.make_proj(W, H, f=float(W))
+    seq = FrameRenderer(xyz, desc, _tiny_net()["full"], W, H, proj_matrix=proj)            # (the packed blob: the state is not packed again)
+    assert (seq.raster.cells is not None) == (N > (1 << 20))
+    poses = [synthetic.sweep_pose(k) for k in (0, 1, 2, 40)]
+    want = []
+    for k, pose in enumerate(poses):
+        rgba = seq.render(pose).clone()
+        want.append(rgba)
+        if k not in (1, 3):                                               # (a warm-started frame and one after a jump)
+            continue
+        M = camera.total_matrix(proj, pose)[0]
+        idx, dep = oracle.raster_multiscale(xyz, M, W, H, 5, threads=8)
+        assert tuple(seq.idx[4].shape[1:]) == (H >> 4, W >> 4)
+        for l in range(5):
+            assert np.array_equal(seq.idx[l][0].cpu().numpy(), idx[l]), f"{W}x{H} pose {k}: index level {l}"
+            assert np.array_equal(seq.depth[l][0].cpu().numpy().view(np.uint32), dep[l].view(np.uint32)), f"{W}x{H} pose {k}: depth level {l}"
+        with torch.no_grad():
+            ref = unet_torch.net_and_texture_forward(state, desc[None], idx)[0]
+        _check_rgb(rgba[:, :, :3].permute(2, 0, 1).cpu(), ref, f"frame {W}x{H}, {N} points, pose {k}")
+        assert bool((rgba[:, :, 3] == 1).all())
+    seq.set_frames_in_flight(2)                                           # the same renderer, now with two plans and two streams
+    outs = [seq.render(p) for p in poses]
+    seq.sync()
+    for i, (g, w) in enumerate(zip(outs, want)):
+        assert torch.equal(g, w), f"{W}x{H}, {N} points: pipelined frame {i} differs"

@@ -99,7 +99,23 @@ def test_huber_and_up4_references_agree_with_torch_double():
 # ------------------------------------------------------------------------------------------ restatements inside the bounds
 @pytest.mark.parametrize("C", [3, 9, 32])
 def test_fp32_restatement_of_the_gate_chain_stays_inside_the_derived_bounds(C):
-    for cls, P, W, bh, vh, groups, (fm, dy, L) in _cases(C):
+    _gate_chain_inside_bounds(C, _cases(C))
+
+
+# 1 (batch statistics over one value: var = 0, y = beta), 4 and 12 pixels and three stacked 2 x 2 items with one separator row each (statistics over the batch, and per item over 4 values):
+# the coarse levels of a 16-pixel crop, the geometries of tests/test_gpu_train_accuracy.py's degenerate rows
+TINY_GEOM = ((1, 1, 0, 0, 1), (4, 2, 0, 0, 1), (12, 6, 0, 0, 1), (18, 2, 3, 2, 1), (18, 2, 3, 2, 3))
+
+
+@pytest.mark.parametrize("C", [3, 9, 256])
+def test_fp32_restatement_of_the_gate_chain_at_degenerate_sizes(C):
+    """The references and bounds of the gate / BatchNorm chain are right at a handful of pixels before any kernel is blamed there."""
+    _gate_chain_inside_bounds(C, ((cls, P, W, bh, vh, groups, mk(P, C, 6)) for cls, mk in (("a", T.unit_case), ("b", T.checkpoint_case))
+                                  for (P, W, bh, vh, groups) in TINY_GEOM))
+
+
+def _gate_chain_inside_bounds(C, cases):
+    for cls, P, W, bh, vh, groups, (fm, dy, L) in cases:
         what = f"class {cls} C {C} P {P} block {bh}/{vh} groups {groups}"
         v = T.valid_rows(P, W, bh, vh)
         sc = (L["gamma"] / np.sqrt((L["var"] + f32(T.EPS)).astype(f32)).astype(f32)).astype(f32)
@@ -142,8 +158,18 @@ def test_fp32_restatement_of_the_gate_chain_stays_inside_the_derived_bounds(C):
 
 
 def test_fp32_restatements_of_both_wgrad_kernels_stay_inside_the_derived_bounds():
-    rng = np.random.default_rng(9)
-    for (cin, cout, k, stride, H, W) in ((8, 3, 3, 1, 7, 9), (8, 5, 4, 2, 13, 5), (16, 4, 1, 1, 7, 9), (8, 3, 3, 2, 7, 9)):
+    _wgrad_inside_bounds(np.random.default_rng(9), ((8, 3, 3, 1, 7, 9), (8, 5, 4, 2, 13, 5), (16, 4, 1, 1, 7, 9), (8, 3, 3, 2, 7, 9)), ((32, 3, 8, 12), (32, 4, 44, 8)))
+
+
+def test_fp32_restatements_of_both_wgrad_kernels_at_degenerate_sizes():
+    """The direct kernel at 1 x 1 and 2 x 2 (stride 1, k3 / stride 2, k4 / stride 2: one output pixel), the Winograd-domain one at a
+    single tile row (4 x 4, 4 x 12): the smallest image read_conv_wgrad_family gives it."""
+    direct = [(8, 3, 3, 1, h, h) for h in (1, 2)] + [(8, 3, 3, 2, h, h) for h in (1, 2)] + [(8, 5, 4, 2, 2, 2)]
+    _wgrad_inside_bounds(np.random.default_rng(19), direct, ((32, 3, 4, 4), (32, 4, 4, 12)), impulse=(1, 2))
+
+
+def _wgrad_inside_bounds(rng, direct, wino, impulse=(3, 4)):
+    for (cin, cout, k, stride, H, W) in direct:
         for cls in "abc":
             oh, ow = T.out_hw(k, stride, H, W)
             sx, sd = (T.scales_b(cin, rng), T.scales_b(cout, rng)) if cls == "b" else (np.ones(cin), np.ones(cout))
@@ -160,14 +186,14 @@ def test_fp32_restatements_of_both_wgrad_kernels_stay_inside_the_derived_bounds(
                     d = np.zeros((oh, ow, cout), f32)
                     d[py, px] = 2.0 ** -10
                     assert np.array_equal(wgrad_direct32(x, d, k, stride, T.wgrad_plan(cin, cout, k, oh)).astype(np.float64), T.wgrad_ref(x, d, k, stride)[0])
-    for (cin, cout, H, W) in ((32, 3, 8, 12), (32, 4, 44, 8)):
+    for (cin, cout, H, W) in wino:
         for cls in "abc":
             sx, sd = (T.scales_b(cin, rng), T.scales_b(cout, rng)) if cls == "b" else (np.ones(cin), np.ones(cout))
             x = (rng.standard_normal((H, W, cin)) * sx).astype(f32)
             d = (rng.standard_normal((H, W, cout)) * sd).astype(f32)
             if cls == "c":                                           # an impulse of d on a tile boundary over small integers
                 x, d = T.small_integers((H, W, cin), rng), np.zeros((H, W, cout), f32)
-                d[3, 4] = 1.0
+                d[impulse] = 1.0
             ref, A = T.wgrad_ref(x, d, 3, 1)
             Aw = T.wgrad_wino_Aw(x, d)
             assert (Aw >= A * (1 - 1e-12)).all()                       # the transformed-domain condition term dominates the direct one
@@ -202,10 +228,21 @@ def test_fp32_restatement_of_the_forward_launches_stays_inside_the_derived_bound
     """tests/train_fp32.py linear_launch32 — the direct kernel as a sequential fp32 sum over (tap, channel), F(2x2) and F(4x4) through
     their fp32 transforms, the fused gate with fast_exp32 — on classes (a), (b), (d) at the GPU test's layers and sizes: every assertion
     of the GPU test holds, and the closest approach to the derived bounds is printed."""
+    _forward_restatement_inside_bounds(family, lambda layer: FC.SIZES[layer[3]], "abd")
+
+
+@pytest.mark.parametrize("family", ["direct", "w2", "w4"])
+def test_fp32_restatement_of_the_forward_launches_at_degenerate_sizes(family):
+    """... at 2 x 2, 4 x 4 and 1 x 1 (FC.SIZES_TINY), class (c) with its impulse at every pixel included: the references, the bounds and
+    the exactness assertions are right at those sizes before any kernel is blamed."""
+    _forward_restatement_inside_bounds(family, lambda layer: [hw for hw in FC.SIZES_TINY if 0 not in T.out_hw(layer[2], layer[3], *hw)], "abcd")
+
+
+def _forward_restatement_inside_bounds(family, sizes_of, classes):
     worst = {}
     for layer in FC.LAYERS[family]:
-        for hw in FC.SIZES[layer[3]]:
-            for case in FC.cases(layer, hw, classes="abd"):
+        for hw in sizes_of(layer):
+            for case in FC.cases(layer, hw, classes=classes):
                 fails, ratios, _ = _run_assertions(case, family, VARIANTS[:2])
                 assert not fails, fails
                 for fam, cls, _name, q in ratios:

@@ -64,6 +64,18 @@ def bias_edges(cout, shift):
     return np.array(F_EDGES, f32)[c % len(F_EDGES)], np.array(M_EDGES, f32)[(c // len(F_EDGES) + c) % len(M_EDGES)]
 
 
+SIZES_TINY = ((2, 2), (4, 4), (1, 1))                               # the coarse levels of a 16-pixel crop: smaller than any tile of the three kernels
+
+
+def impulse_spots(cin, H, W):
+    """(channel, y, x) of the impulses of class (c): the two corners and a pixel of the second tile row; on an image that does not hold
+    that pixel (SIZES_TINY) every pixel (R64.degenerate_positions), the channels 0, cin - 1 and an odd middle one in turn."""
+    if H > 4 and W > 2:
+        return ((0, 0, 0), (cin - 1, H - 1, W - 1), ((cin // 2) | 1, 4, min(16, W - 2)))
+    chans = (0, cin - 1, (cin // 2) | 1)
+    return tuple((chans[j % 3], y, x_) for j, (y, x_) in enumerate(R64.degenerate_positions(H, W)))
+
+
 def cases(layer, hw, classes="abcd"):
     """The cases of one layer at one size: (a) unit scale; (b) checkpoint-like: per-channel scales T.scales_b on the inputs and on the 2 Cout
     weight rows (the biases follow their rows), BatchNorm statistics of R64.checkpoint_like; (c) impulses of 1.0 over small-integer weights,
@@ -88,7 +100,7 @@ def cases(layer, hw, classes="abcd"):
     if "c" in classes:
         L = dict(tame)
         L["wf"], L["wm"] = T.small_integers((cout, cin, k, k), rng), T.small_integers((cout, cin, k, k), rng)
-        for (c, y, x_) in ((0, 0, 0), (cin - 1, H - 1, W - 1), ((cin // 2) | 1, 4, min(16, W - 2))):
+        for (c, y, x_) in impulse_spots(cin, H, W):
             yield Case(layer, hw, "c", f"impulse c{c} ({y},{x_})", L, R64.impulse(cin, H, W, c, y, x_, 1.0))
         yield Case(layer, hw, "c", "constant 1", dict(tame), R64.constant_image(cin, H, W))
         yield Case(layer, hw, "c", "checkerboard", dict(tame), R64.checkerboard(cin, H, W))

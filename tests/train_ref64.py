@@ -751,7 +751,7 @@ def wino_forward_terms(x_chw, w, m):
     d = xp[:, iy[:, None, :, None], ix[None, :, None, :]]
     V = np.abs(np.einsum("ia,ctuab,jb->tuijc", Bt, d, Bt))
     Vin = np.einsum("ia,ctuab,jb->tuijc", np.abs(Bt), np.abs(d), np.abs(Bt))
-    Uabs = np.einsum("ia,ocab,jb->ijco", np.abs(Gm), np.abs(w), np.abs(Gm))
+    Uabs = R64.filter_memo(w, ("fp32 wino", m), lambda a: np.einsum("ia,ocab,jb->ijco", np.abs(Gm), np.abs(a), np.abs(Gm)))
     out = []
     for Vx in (V, Vin):
         M = np.einsum("tuijc,ijco->tuijo", Vx, Uabs)
@@ -800,7 +800,7 @@ FORWARD_FAMILY = {"direct": 0, "w2": 2, "w4": 4}                   # read_conv_k
 def conv_forward_bound(L, x_chw, ref, family, which):
     """|got - f| (which = "f") or |got - m| <= bound, elementwise, for the linear launch of the layer L on x: -> (bound, cond), each
     (Cout, outH, outW).  ref = conv_ref64.reference(L, x, stride); family "direct" / "w2" / "w4"."""
-    w, b = np.asarray(L["w" + which], np.float64), np.abs(np.asarray(L["b" + which], np.float64))[:, None, None]
+    w, b = R64.filter_memo(L["w" + which], "f64", lambda a: np.asarray(a, np.float64)), np.abs(np.asarray(L["b" + which], np.float64))[:, None, None]
     cin, k = w.shape[1], w.shape[2]
     A, val = (ref.Af, ref.f) if which == "f" else (ref.Am, ref.m)
     if family == "direct":
